@@ -34,6 +34,16 @@ Extra fields of the JSON line:
                     reachable (`--reference-path`, default /root/reference: the authoring container), else the
                     committed measurement of profiles/reference_python_timing.json (`same_run` says which).
 
+A plain run (no `--full`) sets up, warms up, times the `--steps` steps and prints the line: `value` / `ms_per_step`
+and the `config` of the workload.  Everything else above — value_end_to_end, value_with_order / find_order, roofline,
+cpu_baseline, the concurrent-contexts figure and the one-hashgraph split (unless `--split strong` or `--emulate-parts`
+asks for it) — takes runs of its own and is measured only with `--full`; without it those fields are null.
+
+--dump-outputs DIR writes what the last timed step computed, as a caller of the path receives it, to DIR/<name>.npy
+(float64, 64 MB at most; larger tables as a fixed, seeded sample of rows, with the row indices next to them):
+new_c, rounds, witnesses, famous and sampled can_see rows.  The inputs depend only on the arguments, so two builds can
+be compared output for output.
+
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -142,6 +152,47 @@ def guarded(fn, timeout_s, on_timeout, linger_s=1.0):
         return fn()
     finally:
         timer.cancel()
+
+
+DUMP_CAP_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, h, new_c, seed):
+    """The last timed step's results, as a caller of divide_rounds + decide_fame reads them back, as float64 .npy files.
+    Event-indexed tables larger than their share of DUMP_CAP_BYTES are sampled: fixed, seeded row blocks, sorted,
+    whose indices are written as <name>_rows.npy."""
+    os.makedirs(out_dir, exist_ok=True)
+    N, n = h.num_events, h.n
+    rng = np.random.default_rng(seed)
+    share = DUMP_CAP_BYTES // 4          # rounds / can_see / witnesses / famous get a quarter each; new_c is tiny
+
+    def rows_within(n_rows, row_bytes):
+        if n_rows * row_bytes <= share:
+            return None
+        blk = 256
+        k = max(1, share // (row_bytes * blk))
+        starts = np.sort(rng.choice(max(1, n_rows // blk), size=min(k, max(1, n_rows // blk)), replace=False)) * blk
+        return np.unique(np.concatenate([np.arange(s, min(n_rows, s + blk)) for s in starts]))
+
+    def save(name, a, rows=None):
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, np.float64))
+        if rows is not None:
+            np.save(os.path.join(out_dir, name + "_rows.npy"), rows.astype(np.float64))
+
+    save("new_c", np.asarray(list(new_c), np.int64))
+    rows = rows_within(N, 8)
+    save("rounds", h.rounds() if rows is None else h.rounds()[rows], rows)
+    wit, fam = h.witnesses(), h.famous()
+    rows = rows_within(len(wit), 8 * n)
+    save("witnesses", wit if rows is None else wit[rows], rows)
+    save("famous", fam if rows is None else fam[rows], rows)
+    rows = rows_within(N, 8 * n)
+    if rows is None:
+        save("can_see", h.can_see())
+    else:
+        starts = rows[np.r_[True, np.diff(rows) > 1]]
+        ends = rows[np.r_[np.diff(rows) > 1, True]] + 1
+        save("can_see", np.concatenate([h.can_see(int(a), int(b - a)) for a, b in zip(starts, ends)]), rows)
 
 
 def strong_section(args, pkg, part_mod, rep, torch, rank, local_rank, world, n, N, stream, new_c, barrier):
@@ -299,6 +350,11 @@ def main():
     ap.add_argument("--one-device", action="store_true", help="test hook: every rank uses cuda:0 (needs --backend gloo: RCCL refuses two ranks on one device)")
     ap.add_argument("--reference-path", default="/root/reference", help="source tree of the Python reference (timed in-run when present)")
     ap.add_argument("--reference-events", type=int, default=8000, help="prefix of the stream timed through the Python reference (~20 s at 256 members)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything besides `value`: end to end, find_order, roofline, CPU baseline, concurrent contexts, "
+                         "the one-hashgraph split (a plain run leaves those fields null)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's results (new_c, rounds, witnesses, famous, sampled can_see rows) to DIR/<name>.npy")
     args = ap.parse_args()
 
     import torch
@@ -352,11 +408,14 @@ def main():
     new_c = last["new_c"]
     ms_per_step = dt / args.steps * 1e3
     value = rep.aggregate_throughput(N, args.steps, dt)   # events all ranks processed / the slowest rank's time
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, ctxs[(args.warmup + args.steps - 1) % n_ctx], new_c, args.seed)
+
 
     # ---- two passes at once on ONE GPU (two contexts, two host threads): how much of the chip one latency-bound pass leaves
     # idle.  Reported next to `value`, never as `value`: a node divides ONE hashgraph, and ms_per_step is that pass's latency.
     conc = None
-    if args.concurrent > 1 and n_ctx >= args.concurrent and world == 1:
+    if args.full and args.concurrent > 1 and n_ctx >= args.concurrent and world == 1:
         per = max(2, args.steps // args.concurrent)
 
         def worker(j):
@@ -382,7 +441,7 @@ def main():
 
     # ---- end to end: host SoA in -> round[N], witness table, famous, new_c on the host ----
     e2e = None
-    if args.e2e_steps > 0:
+    if args.full and args.e2e_steps > 0:
         h = ctxs[-1]
 
         def e2e_step():
@@ -405,140 +464,143 @@ def main():
         assert len(r_e2e[0]) == N and list(r_e2e[3]) == list(new_c)
 
     # ---- per-kernel roofline table: one extra profiled pass (plain launches, hipEvent pairs) ----
-    h = ctxs[0]
-    h.rewind()
-    h.set_profiling(True)
-    c0 = h.counters()
-    h.divide_rounds(0, N)
-    new_c_prof = h.decide_fame()
-    tm = h.timings()
-    c1 = h.counters()
-    tally_name = h.tally_kernel   # the step-3 kernel THIS pass used (the library chooses per call, DESIGN.md §4 "Which tally")
-    h.set_profiling(False)
-    t_fo = time.perf_counter()
-    ordered = h.find_order(new_c_prof)   # N1 (outside the metric): reported for information only
-    find_order_first_ms = (time.perf_counter() - t_fo) * 1e3   # first call of the context: allocates its buffers, fetches the chain pool
-    fo_ms = []
-    for _ in range(5):                     # the same call again on the same context, five times: what a running node pays (the first two after the
-                                           # buffers were allocated run ~0.8 ms slower than the ones behind them, every time: all five are in the line)
+    roofline, cd, find_order_ms, find_order_first_ms, fo_ms, ordered = None, {}, None, None, [], []
+    c1 = ctxs[0].counters()
+    if args.full:
+        h = ctxs[0]
         h.rewind()
+        h.set_profiling(True)
+        c0 = h.counters()
         h.divide_rounds(0, N)
-        nc2 = h.decide_fame()
-        h.synchronize()
+        new_c_prof = h.decide_fame()
+        tm = h.timings()
+        c1 = h.counters()
+        tally_name = h.tally_kernel   # the step-3 kernel THIS pass used (the library chooses per call, DESIGN.md §4 "Which tally")
+        h.set_profiling(False)
         t_fo = time.perf_counter()
-        ordered2 = h.find_order(nc2)
-        fo_ms.append((time.perf_counter() - t_fo) * 1e3)
-        assert np.array_equal(ordered, ordered2)
-    find_order_ms = sorted(fo_ms)[2]       # the median of the five
-    cd = {k: c1[k] - c0[k] for k in c1}
-    wkey = workload_key(n, N, args.mode, args.p0, args.p1)
-    traffic, rocprof_us, traffic_commit, traffic_workload, traffic_stale = load_traffic(wkey)
+        ordered = h.find_order(new_c_prof)   # N1 (outside the metric): reported for information only
+        find_order_first_ms = (time.perf_counter() - t_fo) * 1e3   # first call of the context: allocates its buffers, fetches the chain pool
+        fo_ms = []
+        for _ in range(5):                     # the same call again on the same context, five times: what a running node pays (the first two after the
+                                               # buffers were allocated run ~0.8 ms slower than the ones behind them, every time: all five are in the line)
+            h.rewind()
+            h.divide_rounds(0, N)
+            nc2 = h.decide_fame()
+            h.synchronize()
+            t_fo = time.perf_counter()
+            ordered2 = h.find_order(nc2)
+            fo_ms.append((time.perf_counter() - t_fo) * 1e3)
+            assert np.array_equal(ordered, ordered2)
+        find_order_ms = sorted(fo_ms)[2]       # the median of the five
+        cd = {k: c1[k] - c0[k] for k in c1}
+        wkey = workload_key(n, N, args.mode, args.p0, args.p1)
+        traffic, rocprof_us, traffic_commit, traffic_workload, traffic_stale = load_traffic(wkey)
 
-    def fam(name, launches, total_ms, alg_bytes_total, served_by, note=None):
-        launches = max(1, int(launches))
-        avg_ms = total_ms / launches
-        ach = alg_bytes_total / launches / (avg_ms * 1e-3) / 1e9 if avg_ms > 0 else 0.0
-        d = {"kernel": name, "launches": launches, "avg_launch_us": round(avg_ms * 1e3, 2),
-             "total_ms": round(total_ms, 3), "alg_bytes_per_launch": int(alg_bytes_total / launches),
-             "achieved_GBps": round(ach, 1), "frac": round(ach / PEAK_GBPS, 5),
-             "hbm_bytes_per_launch_pmc": traffic.get(name), "served_by": served_by}
-        rp = rocprof_us.get(name)
-        if rp:   # this family's time per pass in rocprofv3's plain kernel trace of this workload (profiles/traffic.json): no event brackets in it
-            ru = rp * 1e3 / launches
-            d["total_ms_rocprof"] = rp
-            d["avg_launch_us_rocprof"] = round(ru, 2)
-            d["achieved_GBps_rocprof"] = round(alg_bytes_total / launches / (ru * 1e-6) / 1e9, 1)
-            d["frac_rocprof"] = round(d["achieved_GBps_rocprof"] / PEAK_GBPS, 5)
-            if traffic.get(name):
-                d["frac_hbm_measured"] = round(traffic[name] / (ru * 1e-6) / 1e9 / PEAK_GBPS, 5)
-        if note:
-            d["note"] = note
-        return d
+        def fam(name, launches, total_ms, alg_bytes_total, served_by, note=None):
+            launches = max(1, int(launches))
+            avg_ms = total_ms / launches
+            ach = alg_bytes_total / launches / (avg_ms * 1e-3) / 1e9 if avg_ms > 0 else 0.0
+            d = {"kernel": name, "launches": launches, "avg_launch_us": round(avg_ms * 1e3, 2),
+                 "total_ms": round(total_ms, 3), "alg_bytes_per_launch": int(alg_bytes_total / launches),
+                 "achieved_GBps": round(ach, 1), "frac": round(ach / PEAK_GBPS, 5),
+                 "hbm_bytes_per_launch_pmc": traffic.get(name), "served_by": served_by}
+            rp = rocprof_us.get(name)
+            if rp:   # this family's time per pass in rocprofv3's plain kernel trace of this workload (profiles/traffic.json): no event brackets in it
+                ru = rp * 1e3 / launches
+                d["total_ms_rocprof"] = rp
+                d["avg_launch_us_rocprof"] = round(ru, 2)
+                d["achieved_GBps_rocprof"] = round(alg_bytes_total / launches / (ru * 1e-6) / 1e9, 1)
+                d["frac_rocprof"] = round(d["achieved_GBps_rocprof"] / PEAK_GBPS, 5)
+                if traffic.get(name):
+                    d["frac_hbm_measured"] = round(traffic[name] / (ru * 1e-6) / 1e9 / PEAK_GBPS, 5)
+            if note:
+                d["note"] = note
+            return d
 
-    npad = ((n + 63) // 64) * 64
-    cs_impl = int(os.environ.get("SW_CANSEE_IMPL", "6" if npad <= 256 else "3"))
-    cs_name = "k_cansee_flow" if cs_impl >= 6 else "k_cansee_stream"
-    cs_note = "12n B per event (2 parent rows read, 1 written); bound by the dependency chain of the DAG (about 3.4 N/n levels)"
-    if cs_name == "k_cansee_stream":   # the level sweep: the parents' 8n B per event never leave LDS, only the row is written
-        cs_note = ("12n B per event algorithmic (2 parent rows read, 1 written); the parent rows come from per-member LDS rings, so 4n B per event "
-                   "cross the HBM interface; latency-bound on %d DAG levels (one LDS round trip + one barrier each)" % cd.get("levels", 0))
-    if cd.get("chunk_sweeps", 0) > 0:  # the chunk-parallel sweep ran (k_cansee_chunks: the launch's span includes its gated repair kernels)
-        cs_name = "k_cansee_chunks"
-        cs_note = ("12n B per event (2 parent rows read, 1 written); %d chunks swept concurrently in %d launches, each from a halo of "
-                   "32 npad events: the dependency chain per launch is the chunk's, not the sub-batch's; %d provisional entries, "
-                   "%d chunks swept twice" % (cd["chunk_sweeps"], tm["cansee_launches"], cd["chunk_provisional"], cd["chunk_resweeps"]))
-    kernels = [
-        fam(cs_name, tm["cansee_launches"], tm["cansee_kernel_ms"], 12 * n * (N - n), "hbm", cs_note),
-        fam("k_resolve_band", tm["resolve_launches"], tm["resolve_ms"], cd["band_events"] * (4 * n + n // 8), "hbm/L2",
-            "4n B read + n/8 B written per band event; the replicated resolve step (latency: ~1 000 instructions and two dependent round trips) is most of its time"),
-        fam(tally_name, tm["tally_launches"], tm["tally_ms"], cd["tally_evals"] * (4 * n + n * n // 8 + 8), "L2",
-            "one can_see row + n gathered n-bit masks per evaluation (%d evaluations this pass%s); the gathers hit the "
-            "L2-resident band table, so the rate is an L2-gather rate, not HBM"
-            % (cd["tally_evals"], ": the two-level search evaluates only the slots it probes" if tally_name == "k_tally_tree" else "")),
-        fam("k_elections", 1, tm["elections_ms"], cd["majority_evals"] * (n // 8), "L2/LDS"),
-    ]
-    # the dominant kernel: the largest total among the families whose bytes come from HBM, by rocprofv3's durations where
-    # the committed trace of this workload gives them (the hipEvent brackets of the profiled pass add 2-3 us to every launch
-    # of the loop kernels: 297 launches of 8 us looked longer than 6 launches of 460 us), else by this run's brackets
-    hbm_fams = [k for k in kernels if k["served_by"].startswith("hbm")]
-    dom = max(hbm_fams, key=lambda k: k.get("total_ms_rocprof", k["total_ms"]))
-    dr_b, df_b = algorithmic_bytes(n, cd, N)
-    path_gbps = (dr_b + df_b) / (ms_per_step * 1e-3) / 1e9
-    # counter-measured HBM bytes of one pass: per-launch figures of the committed --pmc passes x the launches of THIS run
-    # (round loop: iterations that did work; finalize / voter masks: one launch per sub-batch)
-    hbm_pmc = None
-    if traffic:
-        per_pass = {cs_name: tm["cansee_launches"], "k_resolve_band": cd["round_iterations"], tally_name: cd["round_iterations"],
-                    "k_elections": 1, "k_voter_masks_bits": tm["cansee_launches"],
-                    # (round numbers / sees-masks: written by the band pass of k_resolve_band, then one check + one launch for the listed leftovers per sub-batch)
-                    "k_finalize_check": tm["cansee_launches"], "k_finalize_listed": tm["cansee_launches"], "k_finalize_events": 0}
-        if all(traffic.get(k) is not None for k in (cs_name, "k_resolve_band", tally_name)):
-            hbm_pmc = int(sum(traffic.get(k, 0) * v for k, v in per_pass.items()))
-    path_frac = round(path_gbps / PEAK_GBPS, 5)
-    frac_note = None
-    if path_frac > 1.0:
-        frac_note = ("above 1: SURVEY.md §8d's algorithmic bytes count the tally's n^2 / 8 mask gathers per event, which this path serves from L2 "
-                     "(the band-mask table is a few MB): what crosses the HBM interface is frac_hbm_measured")
-    roofline = {
-        # the headline fraction is the WHOLE PATH's: algorithmic bytes of one pass / ms_per_step against the HBM
-        # peak — `achieved` / `frac`; what the counters saw crossing the HBM interface is `traffic` (bytes per step) /
-        # `frac_hbm_measured`.  The kernel named here is the HBM-served family with the largest total time; its own rate is in
-        # `dominant_kernel` and in the table.  A family whose bytes are L2 gathers (the tallies) is never quoted against HBM.
-        "bound": "hbm", "kernel": dom["kernel"], "achieved": round(path_gbps, 2), "peak": PEAK_GBPS,
-        "unit": "GB/s", "frac": path_frac, "frac_note": frac_note, "traffic": hbm_pmc,
-        "scope": "whole pass (sw_rewind + sw_divide_rounds + sw_decide_fame): algorithmic bytes per step / ms_per_step; "
-                 "traffic = HBM bytes per step by the counters",
-        "dominant_kernel": {k: dom.get(k) for k in ("kernel", "launches", "avg_launch_us", "avg_launch_us_rocprof", "alg_bytes_per_launch",
-                                                     "achieved_GBps", "frac", "achieved_GBps_rocprof", "frac_rocprof",
-                                                     "hbm_bytes_per_launch_pmc", "frac_hbm_measured", "served_by")},
-        "traffic_source": ("profiles/traffic.json[%s] (rocprofv3 --pmc FETCH_SIZE x2 + WRITE_SIZE, separate passes, commit %s, %s); "
-                           "not measured by this run" % (wkey, traffic_commit, traffic_workload)) if traffic else
-                          ("none: profiles/traffic.json holds no counter pass of workload %s on this kernel source%s"
-                           % (wkey, " (STALE: measured on other kernel source)" if traffic_stale else "")),
-        "traffic_stale": bool(traffic_stale),
-        "hbm_bytes_per_step_pmc": hbm_pmc,
-        "frac_hbm_measured": round(hbm_pmc / (ms_per_step * 1e-3) / 1e9 / PEAK_GBPS, 5) if hbm_pmc else None,
-        "hbm_bytes_note": "sum over kernel families of (PMC bytes per launch, profiles/traffic.json) x (launches of this run's profiled pass) "
-                          "/ ms_per_step: what actually crosses the HBM interface, against algorithmic bytes in frac",
-        "avg_launch_us": dom["avg_launch_us"], "launches": dom["launches"],
-        "dominant_by": "largest time per pass among the HBM-served kernel families (rocprofv3's plain kernel trace of this workload where profiles/traffic.json has it, else this run's event brackets)",
-        "kernels": kernels,
-        "path_algorithmic_GBps": round(path_gbps, 2), "path_frac": path_frac,
-        "path_note": "whole-pass algorithmic bytes (SURVEY.md §8d) / ms_per_step: the path is bound by its dependency "
-                     "chains (DAG levels, rounds), not by bandwidth",
-        "counters": {k: cd[k] for k in ("levels", "round_iterations", "tally_evals", "band_events", "voter_evals",
-                                        "majority_evals", "coin_votes", "coin_flips", "far_hops",
-                                        "chunk_sweeps", "chunk_provisional", "chunk_repaired", "chunk_resweeps",
-                                        "finalize_from_rows") if k in cd},
-        "phase_ms": {k: round(v, 3) for k, v in (("can_see_stream_span", tm["can_see_ms"]), ("round_loop_span", tm["rounds_ms"]),
-                                                 ("aux_finalize_voter_span", tm["finalize_ms"]), ("fame", tm["fame_ms"]))},
-        "phase_note": "profiled pass = plain launches with event pairs (slower than the graph-replayed timed steps); "
-                      "can_see and aux spans run on their own streams and overlap the round loop",
-    }
+        npad = ((n + 63) // 64) * 64
+        cs_impl = int(os.environ.get("SW_CANSEE_IMPL", "6" if npad <= 256 else "3"))
+        cs_name = "k_cansee_flow" if cs_impl >= 6 else "k_cansee_stream"
+        cs_note = "12n B per event (2 parent rows read, 1 written); bound by the dependency chain of the DAG (about 3.4 N/n levels)"
+        if cs_name == "k_cansee_stream":   # the level sweep: the parents' 8n B per event never leave LDS, only the row is written
+            cs_note = ("12n B per event algorithmic (2 parent rows read, 1 written); the parent rows come from per-member LDS rings, so 4n B per event "
+                       "cross the HBM interface; latency-bound on %d DAG levels (one LDS round trip + one barrier each)" % cd.get("levels", 0))
+        if cd.get("chunk_sweeps", 0) > 0:  # the chunk-parallel sweep ran (k_cansee_chunks: the launch's span includes its gated repair kernels)
+            cs_name = "k_cansee_chunks"
+            cs_note = ("12n B per event (2 parent rows read, 1 written); %d chunks swept concurrently in %d launches, each from a halo of "
+                       "32 npad events: the dependency chain per launch is the chunk's, not the sub-batch's; %d provisional entries, "
+                       "%d chunks swept twice" % (cd["chunk_sweeps"], tm["cansee_launches"], cd["chunk_provisional"], cd["chunk_resweeps"]))
+        kernels = [
+            fam(cs_name, tm["cansee_launches"], tm["cansee_kernel_ms"], 12 * n * (N - n), "hbm", cs_note),
+            fam("k_resolve_band", tm["resolve_launches"], tm["resolve_ms"], cd["band_events"] * (4 * n + n // 8), "hbm/L2",
+                "4n B read + n/8 B written per band event; the replicated resolve step (latency: ~1 000 instructions and two dependent round trips) is most of its time"),
+            fam(tally_name, tm["tally_launches"], tm["tally_ms"], cd["tally_evals"] * (4 * n + n * n // 8 + 8), "L2",
+                "one can_see row + n gathered n-bit masks per evaluation (%d evaluations this pass%s); the gathers hit the "
+                "L2-resident band table, so the rate is an L2-gather rate, not HBM"
+                % (cd["tally_evals"], ": the two-level search evaluates only the slots it probes" if tally_name == "k_tally_tree" else "")),
+            fam("k_elections", 1, tm["elections_ms"], cd["majority_evals"] * (n // 8), "L2/LDS"),
+        ]
+        # the dominant kernel: the largest total among the families whose bytes come from HBM, by rocprofv3's durations where
+        # the committed trace of this workload gives them (the hipEvent brackets of the profiled pass add 2-3 us to every launch
+        # of the loop kernels: 297 launches of 8 us looked longer than 6 launches of 460 us), else by this run's brackets
+        hbm_fams = [k for k in kernels if k["served_by"].startswith("hbm")]
+        dom = max(hbm_fams, key=lambda k: k.get("total_ms_rocprof", k["total_ms"]))
+        dr_b, df_b = algorithmic_bytes(n, cd, N)
+        path_gbps = (dr_b + df_b) / (ms_per_step * 1e-3) / 1e9
+        # counter-measured HBM bytes of one pass: per-launch figures of the committed --pmc passes x the launches of THIS run
+        # (round loop: iterations that did work; finalize / voter masks: one launch per sub-batch)
+        hbm_pmc = None
+        if traffic:
+            per_pass = {cs_name: tm["cansee_launches"], "k_resolve_band": cd["round_iterations"], tally_name: cd["round_iterations"],
+                        "k_elections": 1, "k_voter_masks_bits": tm["cansee_launches"],
+                        # (round numbers / sees-masks: written by the band pass of k_resolve_band, then one check + one launch for the listed leftovers per sub-batch)
+                        "k_finalize_check": tm["cansee_launches"], "k_finalize_listed": tm["cansee_launches"], "k_finalize_events": 0}
+            if all(traffic.get(k) is not None for k in (cs_name, "k_resolve_band", tally_name)):
+                hbm_pmc = int(sum(traffic.get(k, 0) * v for k, v in per_pass.items()))
+        path_frac = round(path_gbps / PEAK_GBPS, 5)
+        frac_note = None
+        if path_frac > 1.0:
+            frac_note = ("above 1: SURVEY.md §8d's algorithmic bytes count the tally's n^2 / 8 mask gathers per event, which this path serves from L2 "
+                         "(the band-mask table is a few MB): what crosses the HBM interface is frac_hbm_measured")
+        roofline = {
+            # the headline fraction is the WHOLE PATH's: algorithmic bytes of one pass / ms_per_step against the HBM
+            # peak — `achieved` / `frac`; what the counters saw crossing the HBM interface is `traffic` (bytes per step) /
+            # `frac_hbm_measured`.  The kernel named here is the HBM-served family with the largest total time; its own rate is in
+            # `dominant_kernel` and in the table.  A family whose bytes are L2 gathers (the tallies) is never quoted against HBM.
+            "bound": "hbm", "kernel": dom["kernel"], "achieved": round(path_gbps, 2), "peak": PEAK_GBPS,
+            "unit": "GB/s", "frac": path_frac, "frac_note": frac_note, "traffic": hbm_pmc,
+            "scope": "whole pass (sw_rewind + sw_divide_rounds + sw_decide_fame): algorithmic bytes per step / ms_per_step; "
+                     "traffic = HBM bytes per step by the counters",
+            "dominant_kernel": {k: dom.get(k) for k in ("kernel", "launches", "avg_launch_us", "avg_launch_us_rocprof", "alg_bytes_per_launch",
+                                                         "achieved_GBps", "frac", "achieved_GBps_rocprof", "frac_rocprof",
+                                                         "hbm_bytes_per_launch_pmc", "frac_hbm_measured", "served_by")},
+            "traffic_source": ("profiles/traffic.json[%s] (rocprofv3 --pmc FETCH_SIZE x2 + WRITE_SIZE, separate passes, commit %s, %s); "
+                               "not measured by this run" % (wkey, traffic_commit, traffic_workload)) if traffic else
+                              ("none: profiles/traffic.json holds no counter pass of workload %s on this kernel source%s"
+                               % (wkey, " (STALE: measured on other kernel source)" if traffic_stale else "")),
+            "traffic_stale": bool(traffic_stale),
+            "hbm_bytes_per_step_pmc": hbm_pmc,
+            "frac_hbm_measured": round(hbm_pmc / (ms_per_step * 1e-3) / 1e9 / PEAK_GBPS, 5) if hbm_pmc else None,
+            "hbm_bytes_note": "sum over kernel families of (PMC bytes per launch, profiles/traffic.json) x (launches of this run's profiled pass) "
+                              "/ ms_per_step: what actually crosses the HBM interface, against algorithmic bytes in frac",
+            "avg_launch_us": dom["avg_launch_us"], "launches": dom["launches"],
+            "dominant_by": "largest time per pass among the HBM-served kernel families (rocprofv3's plain kernel trace of this workload where profiles/traffic.json has it, else this run's event brackets)",
+            "kernels": kernels,
+            "path_algorithmic_GBps": round(path_gbps, 2), "path_frac": path_frac,
+            "path_note": "whole-pass algorithmic bytes (SURVEY.md §8d) / ms_per_step: the path is bound by its dependency "
+                         "chains (DAG levels, rounds), not by bandwidth",
+            "counters": {k: cd[k] for k in ("levels", "round_iterations", "tally_evals", "band_events", "voter_evals",
+                                            "majority_evals", "coin_votes", "coin_flips", "far_hops",
+                                            "chunk_sweeps", "chunk_provisional", "chunk_repaired", "chunk_resweeps",
+                                            "finalize_from_rows") if k in cd},
+            "phase_ms": {k: round(v, 3) for k, v in (("can_see_stream_span", tm["can_see_ms"]), ("round_loop_span", tm["rounds_ms"]),
+                                                     ("aux_finalize_voter_span", tm["finalize_ms"]), ("fame", tm["fame_ms"]))},
+            "phase_note": "profiled pass = plain launches with event pairs (slower than the graph-replayed timed steps); "
+                          "can_see and aux spans run on their own streams and overlap the round loop",
+        }
 
     # ---- CPU baseline: the oracle (C port of the reference algorithm), 1 core, bounded sample ----
     cpu_baseline = None
-    if rank == 0 and world == 1 and args.cpu_sample > 0:
+    if args.full and rank == 0 and world == 1 and args.cpu_sample > 0:
         from oracle.oracle import Oracle
         M = min(args.cpu_sample, N)
         o = Oracle(n)
@@ -573,6 +635,10 @@ def main():
                 pass
 
     value_replicas, ms_replicas = value, ms_per_step
+
+    def rnd(x, k):
+        return None if x is None else round(x, k)
+
     line_lock, line_done = threading.Lock(), [False]
 
     def emit(strong):
@@ -596,8 +662,8 @@ def main():
             "value_concurrent_contexts": conc,
             "value_strong": strong["events_per_s"] if strong and "events_per_s" in strong else None,
             "strong": strong,
-            "value_with_order": round(N / ((ms_replicas + find_order_ms) * 1e-3), 1) if world == 1 else None,
-            "find_order_ms": round(find_order_ms, 3), "find_order_first_call_ms": round(find_order_first_ms, 3),
+            "value_with_order": round(N / ((ms_replicas + find_order_ms) * 1e-3), 1) if world == 1 and find_order_ms is not None else None,
+            "find_order_ms": rnd(find_order_ms, 3), "find_order_first_call_ms": rnd(find_order_first_ms, 3),
             "find_order_calls_ms": [round(x, 3) for x in fo_ms],
             "config": {"workload": "%d members, %d events, %s hashgraph, one batch "
                                    "divide_rounds + decide_fame per step" % (
@@ -610,9 +676,9 @@ def main():
                                       if use_strong else ("replicas x%d (no data-path collective); the one-hashgraph split is `value_strong`" % world),
                        "rounds": c1["rounds"], "ingest_s_untimed": round(ingest_s, 3),
                        "new_c_last_step": int(len(new_c)),
-                       "coin_round_votes": cd["coin_votes"], "coin_round_votes_from_signature_bit": cd["coin_flips"],
+                       "coin_round_votes": cd.get("coin_votes"), "coin_round_votes_from_signature_bit": cd.get("coin_flips"),
                        "generator": {"mode": args.mode, "p0": args.p0, "p1": args.p1},
-                       "find_order_ms_untimed": round(find_order_ms, 2), "events_ordered": int(len(ordered))},
+                       "find_order_ms_untimed": rnd(find_order_ms, 2), "events_ordered": int(len(ordered)) if args.full else None},
             "roofline": roofline, "cpu_baseline": cpu_baseline,
         }
         print(json.dumps(out), flush=True)
@@ -632,7 +698,8 @@ def main():
         except Exception as exc:  # noqa: BLE001 — the replicas line is still printed; the failure is part of it
             return {"error": repr(exc)}
 
-    strong = guarded(run_split, args.strong_timeout if world > 1 else 0, on_timeout, linger_s=1.0 if rank == 0 else 3.0)
+    if args.full or args.split == "strong" or args.emulate_parts > 1:
+        strong = guarded(run_split, args.strong_timeout if world > 1 else 0, on_timeout, linger_s=1.0 if rank == 0 else 3.0)
     emit(strong)
     rep.close()
 

@@ -5,7 +5,7 @@ python py-swirld_amd/build.py --force > /dev/null 2>&1
 out=gpurun_out/${1:-cumask}; mkdir -p $out
 B="--cpu-sample 0 --e2e-steps 0 --steps 10 --warmup 2"
 for cus in 0 192 128 96; do
-  SW_CS_CUS=$cus timeout 120 python bench.py $B > $out/bench_cus$cus.json 2> $out/err_$cus.log
+  SW_CS_CUS=$cus timeout 120 python bench.py --full $B > $out/bench_cus$cus.json 2> $out/err_$cus.log
   python - $out/bench_cus$cus.json $cus <<'PY'
 import json,sys
 try:

@@ -9,4 +9,4 @@ grep "^mode" $out/vmm_remap.log
 timeout 700 python -m pytest tests -m gpu -q -p no:cacheprovider > $out/pytest_gpu.log 2>&1; echo "rc=$?" >> $out/pytest_gpu.log
 grep -E "Failed:|passed|failed|^rc=" $out/pytest_gpu.log | cut -c1-1500
 timeout 300 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $out/smoke.log 2>&1; tail -1 $out/smoke.log
-timeout 400 python bench.py > $out/bench.json 2> $out/bench.err; cut -c1-400 $out/bench.json
+timeout 400 python bench.py --full > $out/bench.json 2> $out/bench.err; cut -c1-400 $out/bench.json

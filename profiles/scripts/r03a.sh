@@ -10,7 +10,7 @@ tail -4 $O/pytest_subset.log
 B="--cpu-sample 0 --e2e-steps 0 --steps 10 --warmup 2"
 for cfg in "4 0" "1 0" "4 1" "4 2" "2 1" "8 0"; do
   set -- $cfg
-  SW_CHUNKS=$1 SW_CHUNK_CFG=$2 timeout 200 python bench.py $B > $O/bench_256x1M_chunks$1_cfg$2.json 2>> $O/err.log
+  SW_CHUNKS=$1 SW_CHUNK_CFG=$2 timeout 200 python bench.py --full $B > $O/bench_256x1M_chunks$1_cfg$2.json 2>> $O/err.log
 done
 python - $O <<'PY'
 import json,glob,sys
@@ -21,5 +21,5 @@ for f in sorted(glob.glob(sys.argv[1]+"/bench_*.json")):
     except Exception as e: print(f, "ERR", e)
 PY
 for ch in 4 1; do
-  SW_CHUNKS=$ch SW_DEBUG_TIMING=1 timeout 100 python bench.py --cpu-sample 0 --e2e-steps 0 --steps 3 --warmup 1 --contexts 1 > /dev/null 2> $O/debug_timing_chunks$ch.log; echo "chunks=$ch"; grep "sub-batch\|stages" $O/debug_timing_chunks$ch.log | tail -6
+  SW_CHUNKS=$ch SW_DEBUG_TIMING=1 timeout 100 python bench.py --full --cpu-sample 0 --e2e-steps 0 --steps 3 --warmup 1 --contexts 1 > /dev/null 2> $O/debug_timing_chunks$ch.log; echo "chunks=$ch"; grep "sub-batch\|stages" $O/debug_timing_chunks$ch.log | tail -6
 done

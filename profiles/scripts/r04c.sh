@@ -13,5 +13,5 @@ cat $O/knobs_tree_1024x2M.log
 SW_TALLY_IMPL=2 SW_PIPE=1 timeout 100 python profiles/loop_phases.py 256 1000000 > $O/loop_phases_tree.txt 2>&1
 SW_PIPE=1 timeout 100 python profiles/loop_phases.py 256 1000000 > $O/loop_phases_flat.txt 2>&1
 head -40 $O/loop_phases_tree.txt
-SW_DEBUG_TIMING=1 timeout 300 python bench.py --cpu-sample 0 --e2e-steps 0 --steps 2 --warmup 1 > $O/bench_order.json 2> $O/bench_order.err
+SW_DEBUG_TIMING=1 timeout 300 python bench.py --full --cpu-sample 0 --e2e-steps 0 --steps 2 --warmup 1 > $O/bench_order.json 2> $O/bench_order.err
 grep "find_order\]" $O/bench_order.err | tail -12

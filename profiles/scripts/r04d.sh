@@ -10,7 +10,7 @@ timeout 200 python profiles/knob_sweep.py 64 100000 9 -- - SW_BAND_PRE=1024 SW_B
 cat $O/knobs_pf_64x100k.log
 SW_BAND_PRE=6144 SW_PIPE=1 timeout 100 python profiles/loop_phases.py 256 1000000 > $O/loop_phases_pf.txt 2>&1
 head -16 $O/loop_phases_pf.txt
-SW_DEBUG_TIMING=1 timeout 300 python bench.py --cpu-sample 0 --e2e-steps 0 --steps 2 --warmup 1 > $O/bench_order.json 2> $O/bench_order.err
+SW_DEBUG_TIMING=1 timeout 300 python bench.py --full --cpu-sample 0 --e2e-steps 0 --steps 2 --warmup 1 > $O/bench_order.json 2> $O/bench_order.err
 grep "find_order\]" $O/bench_order.err | tail -12
 python -c "
 import json; d=json.load(open('$O/bench_order.json')); print('find_order_ms', d['find_order_ms'], 'ordered', d['config']['events_ordered'])"

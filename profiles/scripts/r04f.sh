@@ -18,6 +18,6 @@ SW_ROWS16=0 SW_PIPE=1 timeout 100 python profiles/loop_phases.py 256 1000000 > $
 sed -n 1,16p $O/loop_phases_vec32.txt
 SW_PIPE=1 timeout 100 python profiles/loop_phases.py 256 1000000 > $O/loop_phases_vec16.txt 2>&1
 sed -n 12,15p $O/loop_phases_vec16.txt
-timeout 300 python bench.py --cpu-sample 0 --e2e-steps 0 --steps 2 --warmup 1 > $O/bench_order.json 2> $O/bench_order.err
+timeout 300 python bench.py --full --cpu-sample 0 --e2e-steps 0 --steps 2 --warmup 1 > $O/bench_order.json 2> $O/bench_order.err
 python -c "
 import json; d=json.load(open('$O/bench_order.json')); print('find_order_ms', d['find_order_ms'], 'first', d['find_order_first_call_ms'], 'value', d['value'])"

@@ -6,7 +6,7 @@ export TMPDIR=/tmp
 SW_DEBUG_CLOCKS=2 timeout 100 python profiles/resolve_time.py 256 1000000 > $O/resolve_time.txt 2>&1
 SW_DEBUG_CLOCKS=1 timeout 100 python profiles/resolve_time.py 256 1000000 >> $O/resolve_time.txt 2>&1
 cat $O/resolve_time.txt
-timeout 300 python bench.py --steps 12 --warmup 3 --cpu-sample 0 > $O/bench_default.json 2> $O/bench_default.err
+timeout 300 python bench.py --full --steps 12 --warmup 3 --cpu-sample 0 > $O/bench_default.json 2> $O/bench_default.err
 python -c "
 import json; d=json.load(open('$O/bench_default.json')); print(d['value'], d['ms_per_step'], d['value_end_to_end'], d['value_concurrent_contexts'], d['find_order_ms'], d['find_order_first_call_ms'])"
 SW_COMMIT=$(cat .commit_id 2>/dev/null || echo unknown) timeout 600 bash profiles/run_profiles.sh r04h > $O/prof.log 2>&1

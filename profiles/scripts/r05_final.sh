@@ -9,7 +9,7 @@ SW_COMMIT=$(cat .commit_id 2>/dev/null || echo unknown) timeout 600 bash profile
 cp gpurun_out/prof_$1/traffic.json profiles/traffic.json   # (so that the bench lines below carry PMC bytes of this code)
 head -16 gpurun_out/prof_$1/kernel_stats.txt
 python profiles/pass_timeline.py gpurun_out/prof_$1/kt_results.db 9 > $O/pass_timeline_256x1M.txt 2>&1; tail -1 $O/pass_timeline_256x1M.txt
-timeout 400 python bench.py --steps 20 --warmup 5 > $O/bench_default.json 2> $O/bench_default.err
+timeout 400 python bench.py --full --steps 20 --warmup 5 > $O/bench_default.json 2> $O/bench_default.err
 python -c "
 import json; s=open('$O/bench_default.json').read(); d=json.loads(s[s.index('{\"metric\"'):]); print(d['value'], d['ms_per_step'], d['value_end_to_end'], d['roofline']['kernel'], d['roofline']['frac'], d['roofline']['path_frac'], d['find_order_ms'], d['value_with_order'], d['value_concurrent_contexts'], d['roofline']['traffic_stale'])
 for k in d['roofline']['kernels']: print(k['kernel'], k['launches'], k['avg_launch_us'], k['total_ms'], k['frac'], k['hbm_bytes_per_launch_pmc'])"
@@ -20,16 +20,16 @@ timeout 120 python profiles/subbatch_times.py > $O/subbatch_times_256x1M.txt 2>&
 timeout 120 python profiles/fame_time.py 256 1000000 > $O/fame_time.txt 2>&1
 timeout 120 python profiles/order_laps.py 256 1000000 > $O/order_laps_256x1M.txt 2>&1; tail -3 $O/order_laps_256x1M.txt
 B="--cpu-sample 0 --e2e-steps 0 --contexts 1 --concurrent 0"
-timeout 200 python bench.py $B --steps 5 --warmup 2 --members 1024 --events 2000000 > $O/bench_1024x2M.json 2>> $O/err.log
-timeout 200 python bench.py $B --steps 10 --warmup 2 --members 64 --events 100000 > $O/bench_64x100k.json 2>> $O/err.log
-timeout 300 python bench.py $B --steps 3 --warmup 1 --mode 2 --p0 0.95 --p1 0.002 > $O/bench_hot_members_256x1M.json 2>> $O/err.log
-timeout 300 python bench.py $B --steps 3 --warmup 1 --mode 2 --p0 0.35 --p1 0.02 > $O/bench_coin_stress_256x1M.json 2>> $O/err.log
-timeout 300 python bench.py $B --steps 3 --warmup 1 --mode 1 --p0 0.02 > $O/bench_two_cliques_256x1M.json 2>> $O/err.log
-timeout 300 python bench.py $B --steps 3 --warmup 1 --mode 3 --p0 0.5 > $O/bench_stale_other_parents_256x1M.json 2>> $O/err.log
-timeout 400 python bench.py $B --steps 3 --warmup 1 --events 10000000 > $O/bench_256x10M.json 2>> $O/err.log
-timeout 300 python bench.py --cpu-sample 0 --e2e-steps 0 --concurrent 0 --steps 3 --warmup 1 --emulate-parts 4 > $O/bench_emulated_split.json 2>> $O/err.log
+timeout 200 python bench.py --full $B --steps 5 --warmup 2 --members 1024 --events 2000000 > $O/bench_1024x2M.json 2>> $O/err.log
+timeout 200 python bench.py --full $B --steps 10 --warmup 2 --members 64 --events 100000 > $O/bench_64x100k.json 2>> $O/err.log
+timeout 300 python bench.py --full $B --steps 3 --warmup 1 --mode 2 --p0 0.95 --p1 0.002 > $O/bench_hot_members_256x1M.json 2>> $O/err.log
+timeout 300 python bench.py --full $B --steps 3 --warmup 1 --mode 2 --p0 0.35 --p1 0.02 > $O/bench_coin_stress_256x1M.json 2>> $O/err.log
+timeout 300 python bench.py --full $B --steps 3 --warmup 1 --mode 1 --p0 0.02 > $O/bench_two_cliques_256x1M.json 2>> $O/err.log
+timeout 300 python bench.py --full $B --steps 3 --warmup 1 --mode 3 --p0 0.5 > $O/bench_stale_other_parents_256x1M.json 2>> $O/err.log
+timeout 400 python bench.py --full $B --steps 3 --warmup 1 --events 10000000 > $O/bench_256x10M.json 2>> $O/err.log
+timeout 300 python bench.py --full --cpu-sample 0 --e2e-steps 0 --concurrent 0 --steps 3 --warmup 1 --emulate-parts 4 > $O/bench_emulated_split.json 2>> $O/err.log
 if [ "$2" = "c5" ]; then
-timeout 900 python bench.py $B --steps 2 --warmup 0 --members 1024 --mode 2 --p0 0.40 --p1 0.02 --events 50000000 > $O/bench_c5_1024x50M.json 2>> $O/err.log
+timeout 900 python bench.py --full $B --steps 2 --warmup 0 --members 1024 --mode 2 --p0 0.40 --p1 0.02 --events 50000000 > $O/bench_c5_1024x50M.json 2>> $O/err.log
 fi
 python - $O <<'PY'
 import json,glob,sys

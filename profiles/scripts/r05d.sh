@@ -14,8 +14,8 @@ SWEEP_LIB=$B timeout 300 python profiles/knob_sweep.py 1024 2000000 3 -- - > $O/
 timeout 300 python profiles/knob_sweep.py 1024 2000000 3 -- - SW_GRAPH=0 >> $O/ab_1024x2M.log 2>&1; cat $O/ab_1024x2M.log
 GEN_MODE=1 GEN_P0=0.02 timeout 200 python profiles/knob_sweep.py 256 1000000 5 -- - SW_GRAPH=0 - > $O/knobs_cliques_256x1M.log 2>&1; cat $O/knobs_cliques_256x1M.log
 timeout 200 python profiles/knob_sweep.py 256 10000000 3 -- - SW_GRAPH=0 > $O/knobs_256x10M.log 2>&1; cat $O/knobs_256x10M.log
-timeout 300 python bench.py --steps 20 --warmup 5 --cpu-sample 0 --e2e-steps 0 --contexts 1 > $O/bench_graph.json 2> $O/bench_graph.err; python -c "
+timeout 300 python bench.py --full --steps 20 --warmup 5 --cpu-sample 0 --e2e-steps 0 --contexts 1 > $O/bench_graph.json 2> $O/bench_graph.err; python -c "
 import json;d=json.loads(open('$O/bench_graph.json').read().strip().splitlines()[-1]);print('bench graph', d['value'], d['ms_per_step'])"
-SW_GRAPH=0 timeout 300 python bench.py --steps 20 --warmup 5 --cpu-sample 0 --e2e-steps 0 --contexts 1 > $O/bench_plain.json 2> $O/bench_plain.err; python -c "
+SW_GRAPH=0 timeout 300 python bench.py --full --steps 20 --warmup 5 --cpu-sample 0 --e2e-steps 0 --contexts 1 > $O/bench_plain.json 2> $O/bench_plain.err; python -c "
 import json;d=json.loads(open('$O/bench_plain.json').read().strip().splitlines()[-1]);print('bench plain', d['value'], d['ms_per_step'])"
 timeout 900 python -m pytest tests/test_gpu_parity.py tests/test_gpu_random.py tests/test_gpu_partition.py -m gpu -x -q > $O/pytest.log 2>&1; tail -3 $O/pytest.log

@@ -3,7 +3,7 @@
 O=gpurun_out/$1; mkdir -p $O; VAR=$2; shift 2
 python py-swirld_amd/build.py --force > $O/build.log 2>&1 || { echo BUILD FAILED; tail -5 $O/build.log; exit 1; }
 for v in "$@"; do
-  env $VAR=$v timeout 200 python bench.py --cpu-sample 0 --e2e-steps 0 --steps 10 --warmup 2 $BENCH_ARGS > $O/bench_${VAR}_$v.json 2>> $O/err.log
+  env $VAR=$v timeout 200 python bench.py --full --cpu-sample 0 --e2e-steps 0 --steps 10 --warmup 2 $BENCH_ARGS > $O/bench_${VAR}_$v.json 2>> $O/err.log
   python - $O/bench_${VAR}_$v.json "$VAR=$v" <<'PY'
 import json,sys
 try:

@@ -1,7 +1,8 @@
-"""Drives the UNMODIFIED reference (/root/reference/swirld.py) on a dense-index
-event stream.  Test scaffolding: used by tests/golden/make_golden.py (authoring
-container only) and by the differential tests that are skipped when the reference
-tree is absent (it does not exist on the GPU box).
+"""Drives the UNMODIFIED reference (swirld.py of the reference tree, SWIRLD_REFERENCE_PATH)
+on a dense-index event stream.  Test scaffolding: used by the fixture generators
+tests/golden/make_golden.py, make_random_golden.py and make_node_golden.py, which need the
+reference tree, and by bench.py --full's timing of the reference where the tree is present;
+the tests themselves compare against the fixtures stored.
 """
 import contextlib
 import hashlib

@@ -73,7 +73,7 @@ def _worker(rank, world, port, hang_rank, timeout_s, q, members=12, events=3000)
     torch.cuda.device_count = lambda: 1
     sys.argv = ["bench.py", "--gpus", str(world), "--backend", "gloo", "--one-device", "--members", str(members), "--events", str(events),
                 "--steps", "2", "--warmup", "1", "--contexts", "1", "--concurrent", "0", "--cpu-sample", "0", "--e2e-steps", "1",
-                "--reference-events", "0", "--strong-timeout", str(timeout_s)]
+                "--reference-events", "0", "--strong-timeout", str(timeout_s), "--full"]
     buf = io.StringIO()
     real = sys.stdout
     sys.stdout = buf
