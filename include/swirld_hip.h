@@ -258,6 +258,8 @@ typedef struct sw_counters {
     /* ABI v5 */
     int64_t finalize_from_rows;  /* events whose round / sees-mask no band pass of their own round wrote: recomputed from their rows */
     int64_t order_rounds_host_sorted; /* find_order: rounds the host sorted (a tie on timestamp and the first 8 key bytes)   */
+    int64_t gated_calls;         /* divide_rounds calls that ran ONE round loop gated on the device by the sweep (SW_GATED)           */
+    int64_t gated_idle_iterations; /* ... iterations of those loops (inside round_iterations) in which every searching member waited for the sweep */
 } sw_counters;
 int sw_get_counters(sw_ctx* ctx, sw_counters* out);
 /* The same for a caller built against another version of this header: copies min(out_bytes, sizeof(sw_counters))

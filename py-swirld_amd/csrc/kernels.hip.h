@@ -35,7 +35,25 @@ struct RState {
     u64 band_events;  // band events whose threshold mask was (re)built (work of k_resolve_band's step 2)
     int fin_from;     // first event of THIS run's sub-batch: band events from here on get their round and sees-mask from the band pass
     int pad_;         // diagnostics (SW_DEBUG_CLOCKS): iterations of the context before this loop — the index base of the phase stamps
+    int stage;        // gated loop (SW_GATED): sub-batches of the call whose sweep this iteration's windows and band may read (0: not gated)
+    int stages;       // ... the call's sub-batches: a member exhausted before stage == stages waits in its round instead of leaving it
+    int idle;         // gated loop: iterations that published no candidate while members were searching — every one of them waited
+                      // for the sweep (a member exhausted at its final chain length leaves the round, so nothing else can leave a
+                      // searching member without a window)
+    int pad2_;
 };
+
+// Device word the can_see sweep stream publishes its progress in (gated loop): `vis` = sub-batches of the call whose
+// sweep (fixups and repairs included) is complete.  It lives in the read-back block behind the two loop states
+// (SW_GATE_OFF), so the loop kernels reach it from LoopBufs::st without a kernel argument of their own; k_loop_init
+// sets the two table pointers.  `bounds` [stage][npad] = visible chain lengths, `cuts` [stage] = visible events.
+struct LoopGate {
+    int vis;
+    int pad_;
+    const int* bounds;
+    const long long* cuts;
+};
+#define SW_GATE_OFF 208
 
 struct FameCounters {
     u64 voter_evals;     // V  (swirld.py:247-254)
@@ -1251,9 +1269,15 @@ __device__ __forceinline__ void pin_arg(uint32_t v) { asm volatile("" ::"s"(v));
 // call would otherwise pay five separate copies / fills, ~10 us each).
 __global__ void __launch_bounds__(1024)
 k_loop_init(LoopBufs B, int npad, int r_start, int N, int ncap, const int* __restrict__ visible_len, int* chain_len, int eval_src, int fin_from,
-            int iter_base) {
-    // chain lengths visible to this run = the sub-batch's row of the cut table (already on the device)
-    for (int i = threadIdx.x; i < npad; i += blockDim.x) { chain_len[i] = visible_len[i]; B.treecnt[i] = 0; }
+            int iter_base, int stages, const int* bounds, const long long* cuts) {
+    // chain lengths visible to this run = the sub-batch's row of the cut table (already on the device), in both halves
+    // (the gated loop's writer block refreshes the next iteration's half from the stage it latched); [2][npad]: the member's
+    // chain length at the end of the call — it waits for the sweep only while its visible chain is shorter
+    for (int i = threadIdx.x; i < npad; i += blockDim.x) {
+        chain_len[i] = chain_len[npad + i] = visible_len[i];
+        chain_len[2 * npad + i] = stages > 0 ? bounds[(size_t)stages * npad + i] : visible_len[i];
+        B.treecnt[i] = 0;
+    }
     if (eval_src)   // the previous run ended on an odd iteration: its exhaustion marks are in half 1, this run reads half 0
         for (int i = threadIdx.x; i < npad; i += blockDim.x) { B.evalround[i] = B.evalround[npad + i]; B.evalpos[i] = B.evalpos[npad + i]; }
     if (threadIdx.x == 0) {
@@ -1263,7 +1287,14 @@ k_loop_init(LoopBufs B, int npad, int r_start, int N, int ncap, const int* __res
         t.ncap = ncap;
         t.fin_from = fin_from;
         t.pad_ = iter_base;   // (diagnostics only: iterations of this context before this loop — the index base of the phase stamps; the host counts them and resets the count on a rewind)
+        t.stage = stages > 0 ? 1 : 0;
+        t.stages = stages;
         B.st[0] = t;
+        if (stages > 0) {   // (`vis` belongs to the sweep stream: not written here)
+            LoopGate* g = reinterpret_cast<LoopGate*>(reinterpret_cast<char*>(B.st) + SW_GATE_OFF);
+            g->bounds = bounds;
+            g->cuts = cuts;
+        }
     }
     for (int i = threadIdx.x; i < 2 * npad; i += blockDim.x) {
         B.unres[i] = 0;
@@ -1274,6 +1305,13 @@ k_loop_init(LoopBufs B, int npad, int r_start, int N, int ncap, const int* __res
     }
 }
 
+// The sweep stream's progress word of the gated loop (LoopGate::vis): one thread, one plain store, behind the sweep of the
+// sub-batch on the same stream — the kernel boundary in front of it makes the sweep's rows complete, the one behind it
+// publishes the word.
+__global__ void k_set_stage(LoopGate* g, int v) {
+    if (threadIdx.x == 0) __hip_atomic_store(&g->vis, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
 // Step 1 (replicated, one thread per member): consume the tally results, advance the
 // per-member cursors, commit lo[r+1] when every member is resolved, enter the next round that
 // has work, derive the band.  Step 2: threshold masks of the band events, Mb[k-mlo] bit c_ =
@@ -1282,7 +1320,7 @@ k_loop_init(LoopBufs B, int npad, int r_start, int N, int ncap, const int* __res
 template <int NW, bool FAST, bool SPLIT = false>
 __global__ void __launch_bounds__(1024)
 k_resolve_band(LoopBufs B, int par, int npad, int K, int gallop_after, int skip, int NEARCAP, int MCAP, int Rcap,
-               const int* __restrict__ chain_start, const int* __restrict__ chain_len,
+               const int* __restrict__ chain_start, int* __restrict__ chain_len,
                const int* __restrict__ chain_ev, int* lo, int* lopos,
                const int* __restrict__ L, const int* __restrict__ cr, const int* __restrict__ op, u64* Mb,
                int* __restrict__ round_out, u64* __restrict__ S_out, int* __restrict__ Pc, const SplitDst* __restrict__ sdp) {
@@ -1327,9 +1365,20 @@ k_resolve_band(LoopBufs B, int par, int npad, int K, int gallop_after, int skip,
     const int s_mlo = si->mlo, s_mhi = si->mhi, s_ncap = si->ncap;
     const int fin_from = si->fin_from;
     const int dbg_it = iter + si->pad_;   // (diagnostics: stamps are indexed by the iteration of the CONTEXT — the loops of a call's sub-batches one behind the other)
+    // gated loop (SW_GATED): the windows of this iteration read the chain lengths of stage `stage`; before the call's last
+    // stage a member whose window reaches the end of its visible chain WAITS in the round in progress (it stays searching,
+    // its cursor at the end of the chain) instead of leaving it.  The sweep's progress word is read here with the other
+    // head loads (agent-scope relaxed = an `sc1` load: not served by a stale L1 line) and latched by the writer block for
+    // the NEXT iteration, whose kernels start behind this kernel's end — the kernel-boundary acquire that makes them see the
+    // rows of every sweep complete before this load.
+    const int stage = si->stage, stages = si->stages;
+    const bool last = stage >= stages;
+    const LoopGate* gate = reinterpret_cast<const LoopGate*>(reinterpret_cast<const char*>(B.st) + SW_GATE_OFF);
+    const int vis_ld = __hip_atomic_load(&gate->vis, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     const int cq = member ? c : 0;
     const int cs = chain_start[cq];
-    const int clen_ld = chain_len[cq];  // events of member c visible to this run
+    const int clen_ld = chain_len[in + cq];  // events of member c visible to this iteration ([2][npad]: the gated loop's writer refreshes the other half)
+    const int clen_fin_ld = chain_len[2 * npad + cq];   // ... and at the end of the call (row [2])
     const int un_ld = B.unres[in + cq];
     int curc = B.cur[in + cq];
     const u64 fev_ld = B.found64[in + cq];
@@ -1341,6 +1390,10 @@ k_resolve_band(LoopBufs B, int par, int npad, int K, int gallop_after, int skip,
     const int in_pos_next = B.pos_next[in + cq];
     const int thr_ld = B.lo_r[in + cq];
     const int clen = member ? clen_ld : 0;
+    // the member's chain is complete for this call (or the loop is not gated): reaching its end exhausts it.  Decided per
+    // member, so that a member whose chain stops growing early in the call (a silent or crashed member) leaves its round at
+    // once instead of holding every round back until the last sweep is done.
+    const bool fin_m = last || !member || clen >= clen_fin_ld;
     int un = member ? un_ld : 0;
     const u64 fev = member ? fev_ld : ~0ull;
     const int fnd = fev == ~0ull ? SW_INF : (int)((fev >> 26) & 63);   // smallest candidate slot whose tally passed
@@ -1389,19 +1442,19 @@ k_resolve_band(LoopBufs B, int par, int npad, int K, int gallop_after, int skip,
     // a window only brackets the first passing position in [cursor, cursor + skip]: the member looks
     // again from the cursor; a failing slot 0 rules out the skipped positions as well.
     int strd = gsv & 0xff, miss = (gsv >> 8) & 0xff, skp = (gsv >> 16) & 0xff;
+    // slots the previous launch offered (positions curc + j * strd < clen, j < K), as its writer counted them: the gated
+    // loop's chain may have grown since, so they are not recomputed from this iteration's clen
+    const int offered = (gsv >> 24) & 63;
     bool refined = false;
     if (iter > 0 && un && skp) {
         if ((fnd == 0 && jf != 0) || jf == 0) {  // look again from the cursor
-            evaluated = jf != SW_INF ? jf : (clen - curc < K ? clen - curc : K);  // (tallies of the offset window)
+            evaluated = jf != SW_INF ? jf : offered;  // (tallies of the offset window)
             curc -= skp;
             refined = true;
         }
         skp = 0;
     }
     if (iter > 0 && un && !refined) {
-        // slots offered by the previous launch: positions curc + j * strd < clen, j < K
-        const int offered = strd == 1 ? (clen - curc < K ? clen - curc : K)
-                                      : ((clen - 1 - curc) / strd + 1 < K ? (clen - 1 - curc) / strd + 1 : K);
         evaluated = jf != SW_INF ? jf : offered;
         if (fnd != SW_INF && fnd < jf) {
             if (strd == 1 || fnd == 0) {
@@ -1433,17 +1486,22 @@ k_resolve_band(LoopBufs B, int par, int npad, int K, int gallop_after, int skip,
                 far_wait = 1;
                 frc = 0;
             }
-        } else if (strd == 1 && curc + K >= clen) {  // chain exhausted: no round-(r+1) event of c (yet)
-            un = 0;
-            evr_now = r;
-            evp_now = clen;
+        } else if (strd == 1 && curc + offered >= clen) {  // chain exhausted: no round-(r+1) event of c (yet)
+            if (fin_m) {
+                un = 0;
+                evr_now = r;
+                evp_now = clen;
+            } else
+                curc = clen;   // (gated loop) waits in round r for the next stage's events of c
         } else if (strd > 1 && curc + K * strd >= clen) {  // the tail of the chain: contiguous windows
             curc += (offered - 1) * strd + 1;
             strd = 1;
         } else {
             curc += (offered - 1) * strd + 1;  // = curc + K for a contiguous window
-            if (miss < 255) ++miss;
-            if (gallop_after > 0 && miss >= gallop_after) strd = K < 255 ? K : 255;
+            if (offered > 0) {   // (0: a waiting member of the gated loop whose chain grew — it had no window)
+                if (miss < 255) ++miss;
+                if (gallop_after > 0 && miss >= gallop_after) strd = K < 255 ? K : 255;
+            }
         }
     }
     // ---- far candidates (inheritance): every earlier position of c being false, the cursor
@@ -1527,7 +1585,7 @@ k_resolve_band(LoopBufs B, int par, int npad, int K, int gallop_after, int skip,
                 bool resumed = false;
                 if (evr_now == r && evp_now > start) { start = evp_now; resumed = true; }
                 curc = start;
-                un = start < clen;
+                un = start < clen || !fin_m;   // (gated loop: a member with nothing visible to search waits while its chain still grows)
                 if (un && !resumed && skip > 0 && start + skip < clen) { curc = start + skip; skp = skip; }
             }
             // count(act), count(un), min(lr over the active members) with one barrier; the LDS
@@ -1571,8 +1629,9 @@ k_resolve_band(LoopBufs B, int par, int npad, int K, int gallop_after, int skip,
     if (done) un = 0;
     SW_STAMP(stamp && B.dbg_minor, dbg_it, sb + 4);
     // candidates of member c in the next tally launch: chain positions [curc, curc + K)
-    const int live = !un ? 0 : strd == 1 ? (clen - curc < K ? clen - curc : K)
-                                         : ((clen - 1 - curc) / strd + 1 < K ? (clen - 1 - curc) / strd + 1 : K);
+    const int live_ = !un ? 0 : strd == 1 ? (clen - curc < K ? clen - curc : K)
+                                          : ((clen - 1 - curc) / strd + 1 < K ? (clen - 1 - curc) / strd + 1 : K);
+    const int live = live_ > 0 ? live_ : 0;
     const int maxc = !live ? -1 : (curc == spec_cur && strd == 1 ? spec_last : chain_ev[cs + curc + (live - 1) * strd]);
     SW_STAMP(stamp && B.dbg_minor, dbg_it, 12);
     int s_max = -1, s_cnt = 0;
@@ -1644,6 +1703,15 @@ k_resolve_band(LoopBufs B, int par, int npad, int K, int gallop_after, int skip,
     }
     SW_STAMP(stamp && B.dbg_minor, dbg_it, 14);
     if (writer) {
+        // gated loop: the stage of the next iteration = the sweep's progress seen at this kernel's head (never backwards,
+        // never beyond the call's sub-batches); its chain lengths go to the half of chain_len the next iteration reads
+        int stg_next = stage, N_next = N;
+        if (!last) {
+            const int v = vis_ld < stages ? vis_ld : stages;
+            if (v > stage) { stg_next = v; N_next = (int)gate->cuts[v]; }
+        }
+        if (stages > 0 && member)
+            chain_len[out + c] = stg_next != stage ? gate->bounds[(unsigned)(stg_next * npad + c)] : clen;
         if (member) {
             B.unres[out + c] = un;
             B.cur[out + c] = curc;
@@ -1655,7 +1723,7 @@ k_resolve_band(LoopBufs B, int par, int npad, int K, int gallop_after, int skip,
             B.found64[out + c] = ~0ull;
             B.farslot[out + c] = SW_INF;
             B.force[out + c] = frc;
-            B.gallop[out + c] = strd | (miss << 8) | (skp << 16);
+            B.gallop[out + c] = strd | (miss << 8) | (skp << 16) | (live << 24);
         }
         if (c == 0) {
             RState t = *si;
@@ -1663,6 +1731,8 @@ k_resolve_band(LoopBufs B, int par, int npad, int K, int gallop_after, int skip,
             t.mask_from = mask_from;
             t.ncap = ncap;
             t.iter = iter + 1; t.n_unres = nun;
+            t.stage = stg_next; t.N = N_next;
+            if (nun > 0 && s_max < 0 && !done) t.idle = si->idle + 1;
             t.evals = si->evals + (u64)s_cnt;
             t.band_events = si->band_events + (u64)((need_mask && !done) ? mhi - mask_from : 0);
             if (done) t.max_round = max_round;

@@ -184,7 +184,8 @@ struct sw_ctx {
     hipEvent_t ev_user = nullptr;
     std::vector<int32_t> chain_cap;   // per member: capacity of its segment
     int64_t pool_used = 0;             // ints of the chain pool handed out
-    DBuf<int32_t> d_chain_len;    // npad: events per member visible to the running round loop
+    DBuf<int32_t> d_chain_len;    // [3][npad]: events per member visible to the running round loop, by iteration parity (the gated
+                                  // loop's grow), then at the end of the call
     std::vector<int32_t> blk_hmin, blk_hmax;  // height span per 4096-event block (ingest-time index)
     std::vector<int32_t> divided_head;
     DBuf<uint32_t> d_stake;       // npad
@@ -234,6 +235,7 @@ struct sw_ctx {
     unsigned char* h_rb = nullptr;        // the read-back slot that was read last (one of h_rb_all's)
     unsigned char* h_rb_all = nullptr;    // SW_PROV_ROWS pinned slots: the loops of a call's sub-batches are read back one behind the other
     std::vector<hipEvent_t> rb_events, shot_events;   // per slot: read-back complete / last iteration enqueued so far
+    int gated = 1;   // SW_GATED: one round loop per large call, gated on the device by the sweep's progress (0: one loop per sub-batch)
     int shot_pct = 100, shot_extra = 2;   // SW_SHOT_PCT / SW_SHOT_EXTRA: a loop's first shot = predicted iterations x pct / 100 + extra (tests: 50 makes every loop top up)
     size_t rb_bytes = 0;
     RState* d_state = nullptr;
@@ -287,6 +289,9 @@ struct sw_ctx {
                            // the loop ≈ 8 us (profiles/r04y_loop_phases_256x1M.txt: iterations 23, 47, 71, ... are the slow ones)
     GraphKey loop_key{};
     int64_t stat_iters = 0, stat_events = 0;  // iterations-per-event history (first-shot sizing)
+    // iterations-per-event history of the gated loop, kept apart from the per-sub-batch loops' (first-shot sizing).  It counts
+    // the iterations that waited for the sweep too: the first shot has to cover them, or the call ends on host top-ups.
+    int64_t gstat_iters = 0, gstat_events = 0;
 
     // profiling
     bool profiling = false;
@@ -945,7 +950,7 @@ void enqueue_iteration_split(sw_ctx* c, int par) {
     if (!sdp) { c->split->abort.store(1); c->split_failed = true; return; }
     const long long it = c->split_iter++;
     hipLaunchKernelGGL((k_resolve_band<NW, false, true>), dim3(c->band_blocks), dim3(bt), 0, c->stream, B, par, np, K, c->gallop_after, c->skip,
-                       c->NEARCAP, c->MCAP, c->Rcap, (const int*)c->d_chain_start.p, (const int*)c->d_chain_len.p,
+                       c->NEARCAP, c->MCAP, c->Rcap, (const int*)c->d_chain_start.p, c->d_chain_len.p,
                        (const int*)c->d_chain_ev.p, c->d_lo.p, c->d_lopos.p,
                        (const int*)c->d_L.p, (const int*)c->d_cr.p, (const int*)c->d_op.p, c->d_Mb.p + NW, c->d_round.p, c->d_S.p, c->d_Pc.p + 1, sdp);
     if (!split_meet(c, 0, it)) { c->split_failed = true; return; }
@@ -981,7 +986,7 @@ void enqueue_iteration_emulated(sw_ctx* c, int par, int parts) {
     for (int q = 0; q < parts; ++q) { sd.part = q; sdq[q] = split_dev(c, q, sd); if (!sdq[q]) { c->split_failed = true; return; } }
     for (int q = 0; q < parts; ++q) {
         hipLaunchKernelGGL((k_resolve_band<NW, false, true>), dim3(c->band_blocks), dim3(bt), 0, c->stream, B, par, np, K, c->gallop_after, c->skip,
-                           c->NEARCAP, c->MCAP, c->Rcap, (const int*)c->d_chain_start.p, (const int*)c->d_chain_len.p,
+                           c->NEARCAP, c->MCAP, c->Rcap, (const int*)c->d_chain_start.p, c->d_chain_len.p,
                            (const int*)c->d_chain_ev.p, c->d_lo.p, c->d_lopos.p,
                            (const int*)c->d_L.p, (const int*)c->d_cr.p, (const int*)c->d_op.p, c->d_Mb.p + NW, c->d_round.p, c->d_S.p, c->d_Pc.p + 1, sdq[q]);
     }
@@ -1016,7 +1021,7 @@ void enqueue_iteration(sw_ctx* c, int par, std::vector<Span>* tally_spans, std::
     if (resolve_spans) sr = span_begin(c);
     auto resolve_band = [&](auto kern) {
         hipLaunchKernelGGL(kern, dim3(band_blocks), dim3(bt), 0, c->stream, B, par, np, K, c->gallop_after, c->skip,
-                           c->NEARCAP, c->MCAP, c->Rcap, (const int*)c->d_chain_start.p, (const int*)c->d_chain_len.p,
+                           c->NEARCAP, c->MCAP, c->Rcap, (const int*)c->d_chain_start.p, c->d_chain_len.p,
                            (const int*)c->d_chain_ev.p, c->d_lo.p, c->d_lopos.p,
                            (const int*)c->d_L.p, (const int*)c->d_cr.p, (const int*)c->d_op.p, c->d_Mb.p + NW, c->d_round.p, c->d_S.p, c->d_Pc.p + 1, (const SplitDst*)nullptr);
     };
@@ -1129,10 +1134,11 @@ int launch_finalize(sw_ctx* c, hipStream_t ax, int64_t first, int64_t K, int R, 
 // first shot of a round loop: the predicted number of iterations for this many events (from the iterations-per-event rate of
 // earlier runs); without a measured rate about one round per 11.7 n events (SURVEY.md §8 probe) plus the round in progress —
 // a small call must not pay for a long first shot
-inline int predict_shot(const sw_ctx* c, int64_t n_new_events) {
+inline int predict_shot(const sw_ctx* c, int64_t n_new_events, bool gated = false) {
     int shot = std::min<int64_t>(c->BATCH, 2 + (n_new_events / (12 * (int64_t)c->n) + 1) * 2);
-    if (c->stat_iters > 0 && c->stat_events > 0) {
-        const double pred = (double)c->stat_iters / (double)c->stat_events * (double)n_new_events;
+    const int64_t si = gated ? c->gstat_iters : c->stat_iters, se = gated ? c->gstat_events : c->stat_events;
+    if (si > 0 && se > 0) {
+        const double pred = (double)si / (double)se * (double)n_new_events;
         shot = std::max(2, (int)(pred * c->shot_pct / 100.0) + c->shot_extra);
     }
     return std::min(shot, 4096) & ~1;
@@ -1145,7 +1151,8 @@ int run_round_loop(sw_ctx* c, int r_start, int64_t limit, int64_t n_new_events, 
     const int np = c->npad, K = c->K;
     hipLaunchKernelGGL(k_loop_init, dim3(1), dim3(std::min(2 * np, 1024)), 0, c->stream, loop_bufs(c), np, r_start,
                        (int)limit, c->NEARCAP, (const int*)visible_len, c->d_chain_len.p, c->eval_src,
-                       (int)std::min<int64_t>(fin_from, 0x7fffffff), (int)std::min<int64_t>(c->ctr.round_iterations - c->dbg_iter_base, 0x7fffffff));
+                       (int)std::min<int64_t>(fin_from, 0x7fffffff), (int)std::min<int64_t>(c->ctr.round_iterations - c->dbg_iter_base, 0x7fffffff),
+                       0, (const int*)nullptr, (const long long*)nullptr);
     c->eval_src = 0;
     c->ctr.kernel_launches++;
     std::vector<Span> tally_spans, resolve_spans;
@@ -1384,6 +1391,11 @@ int do_divide(sw_ctx* c, int64_t first, int64_t K) {
     hipStream_t cs = c->stream_cs;
     HIPCHK(c, hipEventRecord(c->ev_main_mark, c->stream));
     HIPCHK(c, hipStreamWaitEvent(cs, c->ev_main_mark, 0));
+    // ONE round loop for the whole call, gated on the device by the sweep's progress (SW_GATED=1): the dataflow sweep of a
+    // plain table, not the split loop (its meetings are host calls), not preswept ranges, not the windowed table
+    const bool gated = c->gated && S > 1 && S <= SW_PROV_ROWS && flow && !preswept && !c->split && !c->split_emulate && !c->vm.active && np <= 256;
+    LoopGate* d_gate = reinterpret_cast<LoopGate*>(c->d_rb + SW_GATE_OFF);
+    if (gated) hipLaunchKernelGGL(k_set_stage, dim3(1), dim3(64), 0, cs, d_gate, 0);   // (the previous loop is done: cs waited for it)
     hipEvent_t cs_t0 = nullptr, cs_t1 = nullptr;
     if (c->profiling) { cs_t0 = next_event(c); cs_t1 = next_event(c); (void)hipEventRecord(cs_t0, cs); }
     std::vector<Span> cansee_spans;
@@ -1495,6 +1507,7 @@ int do_divide(sw_ctx* c, int64_t first, int64_t K) {
         }
         span_end(c, scs, cs);
         if (c->profiling) cansee_spans.push_back(scs);
+        if (gated) { hipLaunchKernelGGL(k_set_stage, dim3(1), dim3(64), 0, cs, d_gate, i + 1); c->ctr.kernel_launches++; }
         HIPCHK(c, hipEventRecord(c->cs_events[i], cs));
     }
     if (c->profiling) (void)hipEventRecord(cs_t1, cs);
@@ -1538,7 +1551,7 @@ int do_divide(sw_ctx* c, int64_t first, int64_t K) {
     };
     // what follows a finished loop i (its state is in c->h_rb): the chunk counters of its sweep, the host mirror of the front rounds,
     // and the finalize / witness-row / voter-mask launches of its sub-batch, armed here and enqueued behind the next loop's shot
-    auto after_loop = [&](int i, int r_start, int64_t fin_from, hipEvent_t loop_done) -> int {
+    auto chunk_check = [&](int i) {
         if (c->chunk_plan[i].G >= 2) {
             // the sweep of this sub-batch is complete (the loop waited for it) and its counters came back with the
             // loop state: provisional entries per chunk, entries the repair changed.  (A loop never reports SW_OK
@@ -1556,6 +1569,9 @@ int do_divide(sw_ctx* c, int64_t first, int64_t K) {
             }
             c->ctr.chunk_repaired += pv[(size_t)SW_PROV_ROWS * SW_MAX_CHUNKS + i];
         }
+    };
+    auto after_loop = [&](int i, int r_start, int64_t fin_from, hipEvent_t loop_done) -> int {
+        chunk_check(i);
         // host mirror of the per-member front round (kept by the resolve kernel, read back with the loop state)
         const int R = c->R;
         for (int m = 0; m < n; ++m) c->front[m] = std::max(c->front[m], c->front_dev[m]);
@@ -1591,7 +1607,126 @@ int do_divide(sw_ctx* c, int64_t first, int64_t K) {
         clk.mark(&c->stage_us[4]);
         return SW_OK;
     };
-    for (int i = 0; i < S; ++i) {
+    // ---- the gated loop (SW_GATED=1): ONE round loop over the whole call.  The sweep stream publishes how many sub-batches it
+    // has swept (k_set_stage) and the resolve step latches that one iteration late: no seam between sub-batches (host round
+    // trip, read-back, k_loop_init, first-shot logic), no round searched twice, a member at the end of its visible chain waits
+    // in its round.  The predicted iterations of the whole call go out in pieces of about one sub-batch, each read back into
+    // its own pinned slot: the host waits for the previous piece while the next one runs, and finalizes the events below the
+    // band of the round in progress beside the loop; witness rows and voter masks follow the loop, as the last sub-batch's did.
+    auto run_gated = [&]() -> int {
+        bool row0_dirty = false;
+        const int r_start = start_round(S - 1, &row0_dirty);   // (clen_prev is row 0: every member the call adds events to)
+        HIPCHK(c, hipStreamWaitEvent(c->stream, c->cs_events[0], 0));
+        if (row0_dirty) CHK(upload_row0());
+        clk.mark(&c->stage_us[1]);
+        const bool dbg_t = c->debug_timing;
+        const auto dbg_t0 = std::chrono::steady_clock::now();
+        const int64_t dbg_it0 = c->ctr.round_iterations;
+        if (dbg_t) (void)hipStreamSynchronize(c->stream);   // separates "waiting for the first sweep" from the loop itself
+        const auto dbg_t1 = std::chrono::steady_clock::now();
+        hipLaunchKernelGGL(k_loop_init, dim3(1), dim3(std::min(2 * np, 1024)), 0, c->stream, loop_bufs(c), np, r_start,
+                           (int)cut[1], c->NEARCAP, (const int*)(c->d_bounds.p + np), c->d_chain_len.p, c->eval_src,
+                           c->fin_band ? (int)first : 0x7fffffff, (int)std::min<int64_t>(c->ctr.round_iterations - c->dbg_iter_base, 0x7fffffff),
+                           S, (const int*)c->d_bounds.p, (const long long*)c->d_cuts.p);
+        c->eval_src = 0;
+        c->ctr.kernel_launches++;
+        std::vector<Span> tally_spans, resolve_spans;
+        std::vector<Span>* tsp = c->profiling ? &tally_spans : nullptr;
+        std::vector<Span>* rsp = c->profiling ? &resolve_spans : nullptr;
+        const int total = predict_shot(c, K, true);
+        const int P = std::min(S, SW_PROV_ROWS);
+        CHK(ensure_rounds(c, c->R + total + 8));
+        RState st{};
+        int64_t fin_from = first;
+        int launched = 0;
+        auto enqueue_piece = [&](int j, int n_it) -> int {
+            CHK(launch_iterations<NW>(c, n_it, tsp, rsp));
+            launched += n_it;
+            HIPCHK(c, hipGetLastError());
+            HIPCHK(c, hipMemcpyAsync(c->h_rb_all + (size_t)j * c->rb_bytes, c->d_rb, c->rb_bytes, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, hipEventRecord(c->rb_events[j], c->stream));
+            return SW_OK;
+        };
+        // read-back slot j: loop state, sweep error flag, front rounds, chunk counters
+        auto take = [&](int j) -> int {
+            HIPCHK(c, hipEventSynchronize(c->rb_events[j]));
+            c->h_rb = c->h_rb_all + (size_t)j * c->rb_bytes;
+            memcpy(&st, c->h_rb, sizeof st);
+            int ferr = 0;
+            memcpy(&ferr, c->h_rb + 2 * sizeof(RState), sizeof ferr);
+            if (ferr) return fail(c, SW_EIO, "can_see sweep gave up polling (code %d): internal protocol error", ferr);
+            if (st.err) return fail(c, SW_ERANGE, "round table capacity exceeded (internal)");
+            return SW_OK;
+        };
+        // events below the band of the round in progress have their final round (rows 0 .. st.r of the table are final: a
+        // round commits only when every member has its next-round event or is exhausted at the last stage)
+        auto early_fin = [&](int j) -> int {
+            const int64_t upto = std::min<int64_t>(std::min(st.mlo, st.N), first + K);
+            if (!c->fin_band || st.done || st.iter <= 0 || upto < fin_from + 16384) return SW_OK;
+            HIPCHK(c, hipStreamWaitEvent(c->stream_aux, c->rb_events[j], 0));
+            if (c->profiling && !fin_t0) { fin_t0 = next_event(c); (void)hipEventRecord(fin_t0, c->stream_aux); }
+            CHK(launch_finalize<NW>(c, c->stream_aux, fin_from, upto - fin_from, st.r + 1, c->fin_blocks));
+            fin_from = upto;
+            return SW_OK;
+        };
+        const int piece = std::max(2, (total / P) & ~1);
+        int left = total, j = 0;
+        bool taken_last = false;
+        for (; left > 0 && j < P; ++j) {
+            const int n_it = j == P - 1 ? left : std::min(left, piece);
+            CHK(enqueue_piece(j, n_it));
+            left -= n_it;
+            if (j > 0) {   // (the GPU has piece j queued behind the one the host waits for)
+                CHK(take(j - 1));
+                if (st.done) { taken_last = true; break; }
+                CHK(early_fin(j - 1));
+            }
+        }
+        if (!taken_last) CHK(take(j - 1));
+        // top-ups as in run_round_loop, one read-back each
+        while (!st.done) {
+            if ((int64_t)launched > (int64_t)c->max_height + 2 + c->N / c->K + 4096 + total)
+                return fail(c, SW_EIO, "round loop did not terminate after %d iterations (r=%d)", launched, st.r);
+            const int shot = launched < 8 ? 2 : (launched < 48 ? 8 : 4);
+            CHK(ensure_rounds(c, c->R + launched + shot + 4));
+            CHK(enqueue_piece(0, shot));
+            CHK(take(0));
+        }
+        if (K >= 4096) {
+            c->gstat_iters += st.iter;
+            c->gstat_events += K;
+        }
+        c->eval_src = st.iter & 1;
+        c->R = st.max_round + 1;
+        memcpy(c->front_dev.data(), c->h_rb + 256, np * sizeof(int32_t));
+        if (c->unit_stake && c->tally_impl == 2) {
+            const int32_t* tc = reinterpret_cast<const int32_t*>(c->h_rb + ((unsigned char*)c->d_treecnt - c->d_rb));
+            for (int m = 0; m < np; ++m) c->ctr.tally_evals += tc[m];
+        } else
+        c->ctr.tally_evals += (int64_t)st.evals;
+        c->ctr.far_hops += (int64_t)st.far_hops;
+        c->ctr.round_iterations += st.iter;   // (every iteration the loop executed; those that waited for the sweep also in gated_idle_iterations)
+        c->ctr.gated_calls += 1;
+        c->ctr.gated_idle_iterations += st.idle;
+        c->ctr.band_events += (int64_t)st.band_events;
+        if (c->profiling) {
+            for (size_t i = 0; i < tally_spans.size() && (int)i < st.iter - 1; ++i) { tally_ms += span_ms(tally_spans[i]); ++tally_launches; }
+            for (size_t i = 0; i < resolve_spans.size() && (int)i < st.iter; ++i) { c->tm.resolve_ms += span_ms(resolve_spans[i]); c->tm.resolve_launches++; }
+        }
+        if (dbg_t) {
+            const auto dbg_t2 = std::chrono::steady_clock::now();
+            const double w = std::chrono::duration<double, std::milli>(dbg_t1 - dbg_t0).count();
+            const double l = std::chrono::duration<double, std::milli>(dbg_t2 - dbg_t1).count();
+            fprintf(stderr, "[sw] gated loop: %d sub-batches, %lld events, waited %.3f ms for the first sweep, loop %.3f ms, %lld iterations + %d waiting, %d launched in %d pieces\n",
+                    S, (long long)K, w, l, (long long)(c->ctr.round_iterations - dbg_it0 - st.idle), st.idle, launched, j);
+        }
+        clk.mark(&c->stage_us[2]);
+        for (int i = 0; i < S - 1; ++i) chunk_check(i);   // (every sweep is complete: the loop ended at the last stage)
+        HIPCHK(c, hipEventRecord(c->ev_loop_done, c->stream));
+        return after_loop(S - 1, r_start, fin_from, c->ev_loop_done);
+    };
+    if (gated) CHK(run_gated());
+    for (int i = 0; i < S && !gated; ++i) {
         const int64_t limit = cut[i + 1];
         bool row0_dirty = false;
         const int r_start = start_round(i, &row0_dirty);
@@ -2320,6 +2455,7 @@ int sw_create(int n_members, const uint64_t* stake, int coin_period, int device,
     knob("SW_TALLY_FILTER", 0, 1, &c->tally_filter);
     knob("SW_SPLIT_EMULATE", 0, SW_MAX_PARTS, &c->split_emulate);   // (measurement: the parts of a split played by one context; pin SW_TALLY_IMPL=1 with it)
     knob("SW_SHOT_PCT", 10, 400, &c->shot_pct);
+    knob("SW_GATED", 0, 1, &c->gated);
     knob("SW_SHOT_EXTRA", 0, 64, &c->shot_extra);
     knob("SW_CHUNK_MIN", 64, 1 << 30, &c->chunk_min);
     c->halo = 32 * (int64_t)c->npad;
@@ -2392,7 +2528,7 @@ int sw_create(int n_members, const uint64_t* stake, int coin_period, int device,
         CHIP(hipEventCreateWithFlags(&c->ev_small, hipEventDisableTiming));
     }
     {
-        static_assert(2 * sizeof(RState) + sizeof(int) <= 256, "readback block header");
+        static_assert(2 * sizeof(RState) + sizeof(int) <= SW_GATE_OFF && SW_GATE_OFF % 8 == 0 && SW_GATE_OFF + sizeof(LoopGate) <= 256, "readback block header");
         const size_t tree_off = 256 + (size_t)c->npad * sizeof(int32_t);
         const size_t prov_off = tree_off + (size_t)c->npad * sizeof(int32_t);
         c->rb_bytes = prov_off + (size_t)SW_PROV_ROWS * (SW_MAX_CHUNKS + 1) * sizeof(unsigned);
@@ -2436,7 +2572,7 @@ int sw_create(int n_members, const uint64_t* stake, int coin_period, int device,
     CHIP(hipEventCreateWithFlags(&c->ev_cs_done, hipEventDisableTiming));
     CHIP(hipEventCreateWithFlags(&c->ev_main_mark, hipEventDisableTiming));
     CHIP(hipEventCreateWithFlags(&c->ev_loop_done, hipEventDisableTiming));
-    CCHK(dgrow(c, c->d_chain_len, np, 0));
+    CCHK(dgrow(c, c->d_chain_len, 3 * np, 0));
     CCHK(dgrow(c, c->d_chain_start, np, 0));
     CCHK(dgrow(c, c->d_chain_cnt, np, 0));
     // band masks; row 0 stays all-zero (the bit-sliced tally points "not a hop" at it), the band
