@@ -235,6 +235,7 @@ struct sw_ctx {
     unsigned char* h_rb = nullptr;        // the read-back slot that was read last (one of h_rb_all's)
     unsigned char* h_rb_all = nullptr;    // SW_PROV_ROWS pinned slots: the loops of a call's sub-batches are read back one behind the other
     std::vector<hipEvent_t> rb_events, shot_events;   // per slot: read-back complete / last iteration enqueued so far
+    int gate_lag = 0, gate_step = 1;   // SW_GATE_LAG / SW_GATE_STEP (test hook): the gated loop's stages published by the host, `gate_step` more every `gate_lag` iterations (0: by the sweep stream)
     int gated = 1;   // SW_GATED: one round loop per large call, gated on the device by the sweep's progress (0: one loop per sub-batch)
     int shot_pct = 100, shot_extra = 2;   // SW_SHOT_PCT / SW_SHOT_EXTRA: a loop's first shot = predicted iterations x pct / 100 + extra (tests: 50 makes every loop top up)
     size_t rb_bytes = 0;
@@ -1507,7 +1508,7 @@ int do_divide(sw_ctx* c, int64_t first, int64_t K) {
         }
         span_end(c, scs, cs);
         if (c->profiling) cansee_spans.push_back(scs);
-        if (gated) { hipLaunchKernelGGL(k_set_stage, dim3(1), dim3(64), 0, cs, d_gate, i + 1); c->ctr.kernel_launches++; }
+        if (gated && !c->gate_lag) { hipLaunchKernelGGL(k_set_stage, dim3(1), dim3(64), 0, cs, d_gate, i + 1); c->ctr.kernel_launches++; }
         HIPCHK(c, hipEventRecord(c->cs_events[i], cs));
     }
     if (c->profiling) (void)hipEventRecord(cs_t1, cs);
@@ -1672,6 +1673,36 @@ int do_divide(sw_ctx* c, int64_t first, int64_t K) {
         const int piece = std::max(2, (total / P) & ~1);
         int left = total, j = 0;
         bool taken_last = false;
+        // SW_GATE_LAG (test hook): the stage schedule fixed by the ORDER OF LAUNCHES on the loop stream instead of by the race
+        // with the sweep stream.  Pieces of exactly `lag` iterations; behind each the loop stream waits for the sweeps of the
+        // next `gate_step` sub-batches and publishes them itself with the same k_set_stage: iteration t loads
+        // vis = min(S, 1 + (t / lag) * gate_step).  Nothing on the device waits for `vis`, every publication is enqueued
+        // behind a sweep already in the queue, and the iteration bound below ends a loop that does not finish.  The pinned
+        // slots are reused in turn (the host is one piece behind, as below).
+        if (const int lag = c->gate_lag; lag > 0) {
+            left = 0;
+            taken_last = true;
+            int pub = 1;   // (stage 1 is the loop's own start: k_loop_init)
+            const int64_t bound = (int64_t)c->max_height + 2 + c->N / c->K + 4096 + total + (int64_t)lag * S;
+            for (;; ++j) {
+                if ((int64_t)launched > bound)
+                    return fail(c, SW_EIO, "round loop did not terminate after %d iterations (r=%d, SW_GATE_LAG=%d)", launched, st.r, lag);
+                CHK(ensure_rounds(c, c->R + launched + lag + 4));
+                CHK(enqueue_piece(j % SW_PROV_ROWS, lag));
+                if (pub < S) {
+                    const int v = std::min(S, pub + c->gate_step);
+                    for (int i = pub; i < v; ++i) HIPCHK(c, hipStreamWaitEvent(c->stream, c->cs_events[i], 0));
+                    hipLaunchKernelGGL(k_set_stage, dim3(1), dim3(64), 0, c->stream, d_gate, v);
+                    c->ctr.kernel_launches++;
+                    pub = v;
+                }
+                if (j > 0) {
+                    CHK(take((j - 1) % SW_PROV_ROWS));
+                    if (st.done) break;
+                    CHK(early_fin((j - 1) % SW_PROV_ROWS));
+                }
+            }
+        }
         for (; left > 0 && j < P; ++j) {
             const int n_it = j == P - 1 ? left : std::min(left, piece);
             CHK(enqueue_piece(j, n_it));
@@ -1692,7 +1723,7 @@ int do_divide(sw_ctx* c, int64_t first, int64_t K) {
             CHK(enqueue_piece(0, shot));
             CHK(take(0));
         }
-        if (K >= 4096) {
+        if (K >= 4096 && !c->gate_lag) {   // (first-shot history is for real schedules)
             c->gstat_iters += st.iter;
             c->gstat_events += K;
         }
@@ -2456,6 +2487,9 @@ int sw_create(int n_members, const uint64_t* stake, int coin_period, int device,
     knob("SW_SPLIT_EMULATE", 0, SW_MAX_PARTS, &c->split_emulate);   // (measurement: the parts of a split played by one context; pin SW_TALLY_IMPL=1 with it)
     knob("SW_SHOT_PCT", 10, 400, &c->shot_pct);
     knob("SW_GATED", 0, 1, &c->gated);
+    knob("SW_GATE_LAG", 0, 256, &c->gate_lag);      // (test hooks, DESIGN.md §4: the gated loop's stage schedule fixed by the host)
+    knob("SW_GATE_STEP", 1, SW_PROV_ROWS, &c->gate_step);
+    if (c->gate_lag & 1) knob_err = "SW_GATE_LAG: an even number in [0, 256] (iteration parity)";
     knob("SW_SHOT_EXTRA", 0, 64, &c->shot_extra);
     knob("SW_CHUNK_MIN", 64, 1 << 30, &c->chunk_min);
     c->halo = 32 * (int64_t)c->npad;

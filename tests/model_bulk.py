@@ -533,3 +533,247 @@ def bulk_rounds_v3(n, cr, sp, op, stake, K=4, NEARCAP=None, CAPMAX=None, gallop_
         lo.append(lo_next)
         pos = pos_next
     return L, np.array(lo, np.int64).astype(np.int32), stats
+
+
+def bulk_rounds_gated(n, cr, sp, op, stake, cuts, vis_at, K=4, NEARCAP=None, CAPMAX=None, gallop_after=2, skip=0, mutant=None, stats=None):
+    """The GATED round loop (k_loop_init / k_resolve_band / the tally with stages > 0): bulk_rounds_v3 as ONE flat
+    sequence of iterations over a call whose events become visible stage by stage.
+      * `cuts`: event limits of the call's sub-batches — stage s (1 .. S = len(cuts)) sees the events < cuts[s - 1] and of
+        member c the first bounds[s][c] chain positions (what k_chain_bounds derives from the cuts); cuts[-1] == len(cr);
+      * `vis_at(t)`: the value of LoopGate::vis that iteration t loads at its head.
+    Kernel rules mirrored: stage 1 at the start; the value loaded in iteration t takes effect in t + 1, never backwards, capped
+    at S; iteration t first consumes the verdicts of the tally of t - 1 (whose windows were cut from the chain lengths of
+    stage(t - 1)) with the chain lengths of stage(t), then publishes windows, look-up band and band cap from stage(t) alone;
+    a member whose contiguous window reached the end of its visible chain is exhausted iff that chain is its chain at the end
+    of the call (or the stage is the last), else it WAITS: it stays unresolved with its cursor at the end of the chain, so the
+    round does not commit; a member that enters a round with nothing visible to search stays unresolved likewise while its
+    chain still grows; an iteration that publishes no candidate while members are searching is IDLE.  Row 0 of the table
+    holds the first event of every member the CALL adds events to (the host uploads it), visible or not.
+    Checked inside (AssertionError): (a) no candidate, band event, row or hop at or beyond the current stage's limit is read;
+    (b) no (member, round, chain position) is tallied twice, except the positions the refinements of bulk_rounds_v3
+    re-examine by design (the bracket of a strided window, the look-again of an offset window).
+    `mutant` (tests only, never the default): "no_wait" — exhausted at the end of the visible chain regardless;
+    "reset_cursor" — a waiting member's cursor goes back to the round's start; "early_latch" — the windows use the chain
+    lengths of the stage just loaded while band, limit and latch stay one iteration late.
+    Returns (L, lo, stats); stats has iters (the device's count: every launch up to and including the one that
+    finds no active member), idle (idle iterations), tallies (iterations whose tally had candidates — what bulk_rounds_v3
+    counts as `iters`), member_waits (member-iterations spent waiting), evals, grows, stage_at (the stage of every iteration).  A dict passed as `stats` is the one filled and returned: a schedule
+    that depends on the loop's progress (publish only after an idle iteration) reads it from inside vis_at."""
+    N = len(cr)
+    stake = np.asarray(stake, np.int64)
+    T = int(stake.sum())
+    cuts = [int(x) for x in cuts]
+    S = len(cuts)
+    assert S >= 1 and cuts[-1] == N and all(a < b for a, b in zip([0] + cuts, cuts))
+    lim = [0] + cuts
+    NEARCAP = NEARCAP or 8 * n
+    CAPMAX = max(CAPMAX or N, NEARCAP)
+    L = can_see_rows(n, cr, sp, op)
+    chains = [np.nonzero(cr == c)[0].astype(np.int64) for c in range(n)]
+    bounds = np.array([[int(np.searchsorted(ch, lim[s])) for ch in chains] for s in range(S + 1)], np.int64)
+    clen_fin = bounds[S]
+    lo = [np.array([ch[0] if len(ch) else INF for ch in chains], np.int64)]
+    lopos = [np.zeros(n, np.int64)]
+    stats = {} if stats is None else stats
+    stats.update(iters=0, idle=0, member_waits=0, evals=0, grows=0, tallies=0, stage_at=[])
+    stage = 1
+    r = 0
+    un = np.zeros(n, bool)
+    cur = np.zeros(n, np.int64)
+    stride = np.ones(n, np.int64)
+    miss = np.zeros(n, np.int64)
+    skp = np.zeros(n, np.int64)
+    offered = np.zeros(n, np.int64)
+    frc = np.zeros(n, bool)
+    found = [None] * n
+    farslot = [None] * n
+    lo_next = np.full(n, INF, np.int64)
+    pos_next = np.zeros(n, np.int64)
+    thr = np.full(n, INF, np.int64)
+    ncap, mlo, mhi = NEARCAP, 0, 0
+    masks = {}
+    tallied = {}          # (member, round) -> chain positions tallied so far            [check (b)]
+    last_window = [[] for _ in range(n)]
+    t = 0
+    done = False
+    while not done:
+        assert t <= 4 * N + 64 * S + 64, "model: the gated loop does not terminate"
+        v = int(vis_at(t))
+        Nst = lim[stage]
+        clen = bounds[stage]
+        if mutant == "early_latch":
+            clen = bounds[max(stage, min(v, S))]
+        fin_m = (clen >= clen_fin) | (stage >= S)
+
+        def visible(e):                               # check (a)
+            assert 0 <= e < Nst, "model: event %d read at stage %d (limit %d)" % (e, stage, Nst)
+            return e
+
+        # ---- consume the verdicts of the previous tally
+        far_wait = []
+        if t > 0:
+            for c in np.nonzero(un)[0]:
+                f, jf, s_, off = found[c], farslot[c], int(stride[c]), int(offered[c])
+                if skp[c]:
+                    look_again = (f == 0 and jf != 0) or jf == 0
+                    if look_again:
+                        cur[c] -= skp[c]
+                        tallied.setdefault((c, r), set()).difference_update(last_window[c])
+                    skp[c] = 0
+                    if look_again:
+                        continue
+                if f is not None and (jf is None or f < jf):
+                    if s_ == 1 or f == 0:
+                        pos_next[c] = cur[c] + f * s_
+                        lo_next[c] = chains[c][pos_next[c]]
+                        un[c] = False
+                    else:                             # bracketed: (slot f-1, slot f]
+                        cur[c] += (f - 1) * s_ + 1
+                        stride[c] = 1
+                        tallied[(c, r)].difference_update(last_window[c])
+                elif jf is not None:
+                    if s_ > 1 and jf > 0:
+                        cur[c] += (jf - 1) * s_ + 1
+                        stride[c] = 1
+                    else:
+                        cur[c] += jf * s_
+                        stride[c] = 1
+                        far_wait.append(c)
+                        frc[c] = False
+                elif s_ == 1 and cur[c] + off >= clen[c]:     # the end of the visible chain
+                    if fin_m[c] or mutant == "no_wait":
+                        un[c] = False                 # exhausted: no round-(r+1) event of c
+                    else:
+                        cur[c] = lopos[r][c] if mutant == "reset_cursor" else clen[c]
+                        stats["member_waits"] += 1
+                elif s_ > 1 and cur[c] + K * s_ >= clen[c]:   # the tail of the chain: contiguous windows
+                    cur[c] += (off - 1) * s_ + 1
+                    stride[c] = 1
+                else:
+                    cur[c] += (off - 1) * s_ + 1
+                    if off > 0:                       # (0: a waiting member whose chain grew — it had no window)
+                        miss[c] = min(miss[c] + 1, 255)
+                        if gallop_after > 0 and miss[c] >= gallop_after:
+                            stride[c] = min(K, 255)
+        # ---- far cursor candidates: inheritance from the other-parent (on the state as it is behind the step above)
+        grow = False
+        if far_wait:
+            res = ~un
+            ln = lo_next.copy()                       # (lo[r+1][b] of a resolved b; INF: none)
+            cp = [int(chains[b][cur[b]]) if cur[b] < clen[b] else int(INF) for b in range(n)]
+            for c in far_wait:
+                e = visible(int(chains[c][cur[c]]))
+                q = int(op[e])
+                b = int(cr[q])
+                g = False
+                if res[b]:
+                    if q >= ln[b]:
+                        lo_next[c], pos_next[c], un[c] = e, cur[c], False
+                    else:
+                        g = True
+                elif q < cp[b]:
+                    g = True
+                if g:
+                    grow = True
+                    if ncap >= CAPMAX:
+                        frc[c] = True                 # cap exhausted: tallied with on-the-fly hop masks
+        if grow and ncap < CAPMAX:
+            ncap = min(2 * ncap, CAPMAX)
+            stats["grows"] += 1
+        # ---- every member resolved: commit the round, enter the next one that has work
+        need_mask = False
+        if not un.any():
+            if t > 0:
+                lo.append(lo_next.copy())
+                lopos.append(pos_next.copy())
+                r += 1
+            lr, start = lo[r], lopos[r]
+            while True:
+                act = lr < INF
+                un = act & ((start < clen) | ~fin_m)
+                cur = start.copy()
+                skp[:] = 0
+                if skip > 0:
+                    off_ = un & (start + skip < clen)
+                    cur[off_] += skip
+                    skp[off_] = skip
+                if not act.any():
+                    done = True
+                    break
+                if un.any():
+                    mlo = int(lr[act].min())
+                    thr = lr.copy()
+                    lo_next = np.full(n, INF, np.int64)
+                    pos_next = np.zeros(n, np.int64)
+                    need_mask = True
+                    ncap = NEARCAP
+                    frc[:] = False
+                    stride[:] = 1
+                    miss[:] = 0
+                    break
+                r += 1                                 # nothing to search in this round
+                lr, start = np.full(n, INF, np.int64), np.zeros(n, np.int64)
+                lo.append(lr.copy())
+                lopos.append(start.copy())
+        if done:
+            un[:] = False
+        # ---- windows and band of this iteration, from the current stage alone
+        live = np.zeros(n, np.int64)
+        s_max = -1
+        for c in np.nonzero(un)[0]:
+            lv = (clen[c] - cur[c]) if stride[c] == 1 else ((clen[c] - 1 - cur[c]) // stride[c] + 1)
+            live[c] = max(0, min(K, lv))
+            if live[c]:
+                s_max = max(s_max, visible(int(chains[c][cur[c] + (live[c] - 1) * stride[c]])))
+        want = min(s_max + 1, mlo + ncap, Nst)
+        mask_from = mlo
+        if need_mask:
+            mhi = max(want, mlo)
+            masks = {}
+        elif not done and want > mhi:
+            mask_from, mhi, need_mask = mhi, want, True
+        if un.any() and s_max < 0 and not done:
+            stats["idle"] += 1
+        stage_next = stage
+        if stage < S and min(v, S) > stage:
+            stage_next = min(v, S)                    # latched for the NEXT iteration
+        stats["stage_at"].append(stage)
+        stats["iters"] += 1
+        t += 1
+        if done:
+            break
+        if need_mask:
+            for k in range(mask_from, mhi):
+                visible(k)
+                if k >= thr[cr[k]]:
+                    masks[k] = L[k] >= thr
+        # ---- tally
+        stats["tallies"] += int(live.any())           # (the unit of bulk_rounds_v3's `iters`: passes that had candidates)
+        for c in range(n):
+            found[c] = farslot[c] = None
+            offered[c] = live[c]
+            last_window[c] = []
+            for j in range(int(live[c])):
+                p = int(cur[c] + j * stride[c])
+                e = visible(int(chains[c][p]))
+                if max(int(sp[e]), int(op[e])) >= mhi and not (j == 0 and frc[c]):
+                    farslot[c] = j                    # far: not tallied, nor any slot behind it
+                    break
+                seen = tallied.setdefault((c, r), set())
+                assert p not in seen, "model: member %d, round %d, chain position %d tallied twice" % (c, r, p)   # check (b)
+                seen.add(p)
+                last_window[c].append(p)
+                stats["evals"] += 1
+                P = L[e].copy()
+                P[cr[e]] = sp[e]
+                hits = np.zeros(n, np.int64)
+                for c2 in np.nonzero(P >= thr)[0]:
+                    k = visible(int(P[c2]))
+                    hits += stake[c2] * (masks[k] if k < mhi else (L[k] >= thr))
+                if 3 * int(np.count_nonzero(3 * hits > 2 * T)) > 2 * T:
+                    found[c] = j
+                    break                             # (later slots pass too: the predicate is monotone along the chain)
+        stage = stage_next
+    while len(lo) > 1 and not (lo[-1] < INF).any():
+        lo.pop()                                      # all-INF rows are not rounds
+    return L, np.array(lo, np.int64).astype(np.int32), stats

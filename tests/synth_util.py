@@ -1,5 +1,5 @@
 """Test helper: numpy front-end of the library's host-side synthetic generator
-(sw_synth_hashgraph, py-swirld_amd/csrc/synth.cpp)."""
+(sw_synth_hashgraph, py-swirld_amd/csrc/synth.cpp), and stream surgery shared by the gated-loop tests."""
 import importlib
 import os
 import sys
@@ -14,3 +14,17 @@ if ROOT not in sys.path:
 def synth(n, N, seed, mode=0, p0=0.0, p1=0.0):
     pkg = importlib.import_module("py-swirld_amd")
     return pkg.synth_hashgraph(n, N, seed, mode, p0, p1)
+
+
+def silence(stream, member, at):
+    """The stream with every event of `member` from event index `at` on left out (the member falls silent mid-stream):
+    other-parents that pointed at a removed event point at the member's last event before `at` instead."""
+    cr, sp, op, t, sig = [np.asarray(x) for x in stream]
+    idx = np.arange(len(cr))
+    keep = ~((cr == member) & (idx >= at))
+    last = int(idx[(cr == member) & (idx < at)].max())
+    new = np.cumsum(keep) - 1
+    op2 = np.where((op >= 0) & ~keep[np.maximum(op, 0)], last, op)
+    sp2 = np.where(sp >= 0, new[np.maximum(sp, 0)], -1)
+    op2 = np.where(op2 >= 0, new[np.maximum(op2, 0)], -1)
+    return (cr[keep].astype(cr.dtype), sp2[keep].astype(sp.dtype), op2[keep].astype(op.dtype), t[keep], sig[keep])

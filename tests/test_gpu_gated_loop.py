@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 from oracle_pool import compare_state
+from synth_util import silence
 
 pytestmark = pytest.mark.gpu
 
@@ -40,20 +41,6 @@ def oracle_run(n, stream, chunk):
     return o, ncs
 
 
-def silence(stream, member, at):
-    """The stream with every event of `member` from event index `at` on left out (the member falls silent mid-stream):
-    other-parents that pointed at a removed event point at the member's last event before `at` instead."""
-    cr, sp, op, t, sig = [np.asarray(x) for x in stream]
-    idx = np.arange(len(cr))
-    keep = ~((cr == member) & (idx >= at))
-    last = int(idx[(cr == member) & (idx < at)].max())
-    new = np.cumsum(keep) - 1
-    op2 = np.where((op >= 0) & ~keep[np.maximum(op, 0)], last, op)
-    sp2 = np.where(sp >= 0, new[np.maximum(sp, 0)], -1)
-    op2 = np.where(op2 >= 0, new[np.maximum(op2, 0)], -1)
-    return (cr[keep].astype(cr.dtype), sp2[keep].astype(sp.dtype), op2[keep].astype(op.dtype), t[keep], sig[keep])
-
-
 CUTS_12 = ",".join("%.4f" % (k / 12) for k in range(1, 12))
 
 
@@ -69,6 +56,8 @@ CUTS_12 = ",".join("%.4f" % (k / 12) for k in range(1, 12))
 def test_gated_loop_matches_oracle(pkg, monkeypatch, n, N, seed, mode, p0, p1, env):
     stream = pkg.synth_hashgraph(n, N, seed, mode, p0, p1)
     o, onc = oracle_run(n, stream, N)
+    for k, v in env.items():   # (SW_CUTS is read by every divide_rounds call, not when the context is created: set for the whole test)
+        monkeypatch.setenv(k, v)
     h, ncs = run(pkg, n, stream, N, dict(env, SW_GATED="1"), monkeypatch)
     assert h.counters()["gated_calls"] == 1, "the call must take the gated loop"
     assert ncs == onc
