@@ -12,7 +12,6 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
-#include <functional>
 #include <string>
 #include <thread>
 #include <type_traits>
@@ -234,7 +233,7 @@ struct sw_ctx {
     unsigned char* d_rb = nullptr;
     unsigned char* h_rb = nullptr;        // the read-back slot that was read last (one of h_rb_all's)
     unsigned char* h_rb_all = nullptr;    // SW_PROV_ROWS pinned slots: the loops of a call's sub-batches are read back one behind the other
-    std::vector<hipEvent_t> rb_events, shot_events;   // per slot: read-back complete / last iteration enqueued so far
+    std::vector<hipEvent_t> rb_events;   // per slot: read-back complete
     int gate_lag = 0, gate_step = 1;   // SW_GATE_LAG / SW_GATE_STEP (test hook): the gated loop's stages published by the host, `gate_step` more every `gate_lag` iterations (0: by the sweep stream)
     int gated = 1;   // SW_GATED: one round loop per large call, gated on the device by the sweep's progress (0: one loop per sub-batch)
     int shot_pct = 100, shot_extra = 2;   // SW_SHOT_PCT / SW_SHOT_EXTRA: a loop's first shot = predicted iterations x pct / 100 + extra (tests: 50 makes every loop top up)
@@ -1146,90 +1145,6 @@ inline int predict_shot(const sw_ctx* c, int64_t n_new_events, bool gated = fals
 }
 
 template <int NW>
-int run_round_loop(sw_ctx* c, int r_start, int64_t limit, int64_t n_new_events, const int32_t* visible_len, float* tally_ms_out, int* tally_launches_out,
-                   const std::function<int()>* after_first_shot = nullptr, const std::function<int(const RState&)>* mid_loop = nullptr,
-                   int64_t fin_from = 0x7fffffff) {
-    const int np = c->npad, K = c->K;
-    hipLaunchKernelGGL(k_loop_init, dim3(1), dim3(std::min(2 * np, 1024)), 0, c->stream, loop_bufs(c), np, r_start,
-                       (int)limit, c->NEARCAP, (const int*)visible_len, c->d_chain_len.p, c->eval_src,
-                       (int)std::min<int64_t>(fin_from, 0x7fffffff), (int)std::min<int64_t>(c->ctr.round_iterations - c->dbg_iter_base, 0x7fffffff),
-                       0, (const int*)nullptr, (const long long*)nullptr);
-    c->eval_src = 0;
-    c->ctr.kernel_launches++;
-    std::vector<Span> tally_spans, resolve_spans;
-    RState st{};
-    int launched = 0;
-    // first shot: the predicted number of iterations (predict_shot), then short top-ups until the loop reports done
-    int shot = predict_shot(c, n_new_events);
-    // `mid_loop` (the last sub-batch of a large call): the first shot stops `mid_pct` % of the way, the host looks at the loop
-    // state once — every event below the band of the round in progress has its final round by then — and hands it to the
-    // caller, which finalizes those events beside the rest of the loop instead of behind it; the rest of the prediction follows
-    int rest = 0;
-    if (mid_loop && shot >= 64 && c->mid_pct > 0) {
-        const int head = std::max(2, (int)((int64_t)shot * c->mid_pct / 100) & ~1);
-        rest = std::max(2, (shot - head) & ~1);
-        shot = head;
-    }
-    for (;;) {
-        CHK(ensure_rounds(c, c->R + launched + shot + 4));
-        CHK(launch_iterations<NW>(c, shot, c->profiling && !c->split ? &tally_spans : nullptr, c->profiling && !c->split ? &resolve_spans : nullptr));
-        if (c->split_failed) { c->poisoned = true; return fail(c, SW_EIO, "split round loop: a linked context did not arrive at iteration %lld (sw_split_link: every part calls sw_divide_rounds)", c->split_iter); }
-        // host work that is off the critical path (the finalize / witness / voter-mask launches of the PREVIOUS sub-batch, on
-        // their own stream) goes here: the GPU is already busy with this sub-batch's first shot
-        if (launched == 0 && after_first_shot) CHK((*after_first_shot)());
-        launched += shot;
-        HIPCHK(c, hipGetLastError());
-        // loop state, sweep error flag (the sweep of this sub-batch is complete) and the members' front
-        // rounds: ONE copy into pinned memory
-        HIPCHK(c, hipMemcpyAsync(c->h_rb, c->d_rb, c->rb_bytes, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        memcpy(&st, c->h_rb, sizeof st);
-        int ferr = 0;
-        memcpy(&ferr, c->h_rb + 2 * sizeof(RState), sizeof ferr);
-        memcpy(c->front_dev.data(), c->h_rb + 256, np * sizeof(int32_t));
-        if (ferr) return fail(c, SW_EIO, "can_see sweep gave up polling (code %d): internal protocol error", ferr);
-        if (st.err) return fail(c, SW_ERANGE, "round table capacity exceeded (internal)");
-        if (st.done) break;
-        // rounds <= DAG height + 1, retries <= N / K: anything beyond that is a bug, not work
-        if ((int64_t)launched > (int64_t)c->max_height + 2 + c->N / K + 4096)
-            return fail(c, SW_EIO, "round loop did not terminate after %d iterations (r=%d)", launched, st.r);
-        if (rest) {
-            CHK((*mid_loop)(st));
-            shot = rest;
-            rest = 0;
-        } else
-        shot = launched < 8 ? 2 : (launched < 48 ? 8 : 4);
-    }
-    if (n_new_events >= 4096) {  // keep the rate estimate to runs where it means something
-        c->stat_iters += st.iter;
-        c->stat_events += n_new_events;
-    }
-    // the per-member exhaustion marks persist across runs; the next run reads half 0: its k_loop_init moves them there
-    // (two small device copies here sat in the gap between two sub-batches' loops)
-    c->eval_src = st.iter & 1;
-    c->R = st.max_round + 1;
-    if (c->unit_stake && c->tally_impl == 2) {   // the tree search counts the tallies it really evaluated (per member, read back with the state)
-        const int32_t* tc = reinterpret_cast<const int32_t*>(c->h_rb + ((unsigned char*)c->d_treecnt - c->d_rb));
-        for (int m = 0; m < np; ++m) c->ctr.tally_evals += tc[m];
-    } else
-    c->ctr.tally_evals += (int64_t)st.evals;
-    c->ctr.far_hops += (int64_t)st.far_hops;
-    c->ctr.round_iterations += st.iter;
-    if (c->profiling) {
-        float ms = 0.f;
-        int cnt = 0;
-        // only the launches that did work (iterations before `done`)
-        for (size_t i = 0; i < tally_spans.size() && (int)i < st.iter - 1; ++i) { ms += span_ms(tally_spans[i]); ++cnt; }
-        *tally_ms_out += ms;
-        *tally_launches_out += cnt;
-        for (size_t i = 0; i < resolve_spans.size() && (int)i < st.iter; ++i) { c->tm.resolve_ms += span_ms(resolve_spans[i]); c->tm.resolve_launches++; }
-    }
-    c->ctr.band_events += (int64_t)st.band_events;
-    return SW_OK;
-}
-
-
-template <int NW>
 int launch_voter_masks(sw_ctx* c, int r0, int R, hipStream_t strm) {
     const int np = c->npad;
     if (R > c->Sw_rows) {
@@ -1299,16 +1214,55 @@ struct StageClock {
     }
 };
 
-template <int NW>
-int do_divide(sw_ctx* c, int64_t first, int64_t K) {
-    const int np = c->npad, n = c->n;
-    c->ev_used = 0;
-    StageClock clk(c->debug_timing);
-    c->stage_calls += 1;
-    Span sp_total = span_begin(c);
-    // ---- sub-batches: the can_see sweep of sub-batch i+1 (stream_cs) overlaps the round loop
-    // of sub-batch i (main stream); a kernel boundary separates producer and consumer of a row
-    std::vector<int64_t> cut{first};
+// ==== sw_divide_rounds, host side =================================================================
+// do_divide (at the end of this section) calls the phases below in order; DESIGN.md §4 maps every phase to its
+// function and to the stream it enqueues on.
+
+// The finalize / witness-row / voter-mask launches of a finished sub-batch.  The rounds of every event below its limit are
+// final (later sub-batches only add lo entries that compare greater than every existing event), so they are produced on a
+// third stream, overlapping the round loop of the next sub-batch — and ENQUEUED behind that loop's first shot
+// (flush_tail): armed by after_loop, they must wait for the finished loop's kernels, which the aux stream learns from an
+// event recorded behind them.
+struct DeferredTail {
+    bool armed;
+    int i, r_start, R;      // the sub-batch, the start round of its loop, the rounds behind it
+    int64_t a0, k0;         // its events that no early finalize has taken: [a0, a0 + k0)
+    hipEvent_t loop_done;   // recorded behind its loop
+};
+
+// one sw_divide_rounds call: what its phases hand on to each other (scratch that outlives the call — bounds_stage,
+// ccuts_stage, chunk_plan — stays in sw_ctx)
+struct DivideCall {
+    const int64_t first, K;
+    // sub-batches: the can_see sweep of sub-batch i+1 (stream_cs) overlaps the round loop of sub-batch i (main stream);
+    // a kernel boundary separates producer and consumer of a row
+    std::vector<int64_t> cut;      // [S + 1] event limits of the sub-batches
+    int S = 0;
+    bool flow = false;             // the dataflow sweep (else the level-bucketed one)
+    bool preswept = false;         // the rows are already in the table: no sweep
+    bool gated = false;            // one device-gated round loop for the whole call (run_gated)
+    std::vector<int> hmins, nlevs; // level-bucketed sweep: lowest height and levels per sub-batch
+    bool bounds_pending = false;   // the cut table is still on its way back (ev_bounds)
+    std::vector<int32_t> clen_prev, clen;   // members' visible chain lengths before and after the sub-batch in hand: rows of the cut table
+    int64_t fin_from = 0;          // events of the running loop's sub-batch below this one were finalized beside the loop
+    DeferredTail tail{};
+    StageClock clk;
+    // profiling
+    Span sp_total, sp_rl;
+    hipEvent_t cs_t0 = nullptr, cs_t1 = nullptr, fin_t0 = nullptr;
+    float tally_ms = 0.f;
+    int tally_launches = 0;
+    std::vector<Span> cansee_spans;
+    DivideCall(const sw_ctx* c, int64_t first_, int64_t K_) : first(first_), K(K_), clk(c->debug_timing) {}
+};
+
+LoopGate* loop_gate(sw_ctx* c) { return reinterpret_cast<LoopGate*>(c->d_rb + SW_GATE_OFF); }
+
+// ---- phase: cut plan
+void plan_cuts(const sw_ctx* c, DivideCall& d) {
+    const int64_t first = d.first, K = d.K;
+    std::vector<int64_t>& cut = d.cut;
+    cut.assign(1, first);
     if (const char* cs_ = getenv("SW_CUTS"); cs_ && K >= 65536) {  // tuning hook: cut points as fractions of K
         for (const char* q = cs_; *q;) {
             char* end = nullptr;
@@ -1335,102 +1289,125 @@ int do_divide(sw_ctx* c, int64_t first, int64_t K) {
         }
     }
     cut.push_back(first + K);
-    const int S = (int)cut.size() - 1;
-    const bool flow = c->cansee_impl >= 6;
-    // Which tally (round 4, profiles/r04l_*): the two-level search with a window of 32 wins on 256-member hashgraphs whose
-    // members are about equally active — uniform gossip +2.6 %, two cliques +18 %, stale other-parents +16 %, 4 M events
-    // +4.7 %, mild skew +5 % — and loses where a third of the members is 50 times less active (-9 %) and at 64 / 128
-    // members (-8 / -10 %).  Decided per large call from the members' event counts; SW_TALLY_IMPL / SW_TALLY_K pin it.
-    if (c->tally_auto && c->unit_stake) {
-        int impl = 1;
-        if (np == 256 && n > 200 && K >= 65536) {
-            int32_t lo_ = 0x7fffffff, hi_ = 0;
-            for (int m = 0; m < n; ++m) { lo_ = std::min(lo_, c->nev[m]); hi_ = std::max(hi_, c->nev[m]); }
-            if (lo_ > 0 && (int64_t)hi_ <= 8 * (int64_t)lo_) impl = 2;
-        }
-        c->tally_impl = impl;
-        if (c->K_auto) c->K = impl == 2 ? 32 : c->K_flat;
+    d.S = (int)cut.size() - 1;
+    d.flow = c->cansee_impl >= 6;
+}
+
+// ---- phase: which tally (round 4, profiles/r04l_*): the two-level search with a window of 32 wins on 256-member hashgraphs whose
+// members are about equally active — uniform gossip +2.6 %, two cliques +18 %, stale other-parents +16 %, 4 M events
+// +4.7 %, mild skew +5 % — and loses where a third of the members is 50 times less active (-9 %) and at 64 / 128
+// members (-8 / -10 %).  Decided per large call from the members' event counts; SW_TALLY_IMPL / SW_TALLY_K pin it.
+void choose_tally(sw_ctx* c, const DivideCall& d) {
+    if (!c->tally_auto || !c->unit_stake) return;
+    int impl = 1;
+    if (c->npad == 256 && c->n > 200 && d.K >= 65536) {
+        int32_t lo_ = 0x7fffffff, hi_ = 0;
+        for (int m = 0; m < c->n; ++m) { lo_ = std::min(lo_, c->nev[m]); hi_ = std::max(hi_, c->nev[m]); }
+        if (lo_ > 0 && (int64_t)hi_ <= 8 * (int64_t)lo_) impl = 2;
     }
-    // rows already in the table (event-range split: swept by sw_cansee_range or imported): no sweep, the round
-    // loop still waits for whatever the sweep stream has in flight (imports, repairs)
-    bool preswept = false;
+    c->tally_impl = impl;
+    if (c->K_auto) c->K = impl == 2 ? 32 : c->K_flat;
+}
+
+// ---- phase: rows already in the table (event-range split: swept by sw_cansee_range or imported): no sweep, the round
+// loop still waits for whatever the sweep stream has in flight (imports, repairs)
+int test_preswept(sw_ctx* c, DivideCall& d) {
+    const int64_t first = d.first, K = d.K;
     for (const auto& pr : c->present) {
-        if (first >= pr.first && first + K <= pr.second) preswept = true;
+        if (first >= pr.first && first + K <= pr.second) d.preswept = true;
         else if (first < pr.second && first + K > pr.first)
             return fail(c, SW_EINVAL, "divide_rounds [%lld, %lld) straddles the rows [%lld, %lld) already present (sw_cansee_range / sw_import_rows)",
                         (long long)first, (long long)(first + K), (long long)pr.first, (long long)pr.second);
     }
-    std::vector<int> hmins(S), nlevs(S);
+    return SW_OK;
+}
+
+// ---- phase: level tables of the level-bucketed sweep
+int size_level_tables(sw_ctx* c, DivideCall& d) {
+    d.hmins.assign(d.S, 0);
+    d.nlevs.assign(d.S, 0);
+    if (d.flow || d.preswept) return SW_OK;
     int max_nlev = 1;
     int64_t max_k = 1;
-    if (!flow && !preswept) {
-        CHK(ensure_dag_h(c));  // the level-bucketed kernels need the heights (swirld.py:117-120)
-        for (int i = 0; i < S; ++i) {
-            int hmax;
-            height_span(c, cut[i], cut[i + 1], &hmins[i], &hmax);
-            nlevs[i] = hmax - hmins[i] + 1;
-            max_nlev = std::max(max_nlev, nlevs[i]);
-            max_k = std::max(max_k, cut[i + 1] - cut[i]);
-            c->ctr.levels += nlevs[i];
-        }
-        CHK(dgrow(c, c->d_lev_cnt, max_nlev, 0));
-        CHK(dgrow(c, c->d_lev_start, max_nlev + 1, 0));
-        CHK(dgrow(c, c->d_lev_cursor, max_nlev, 0));
-        CHK(dgrow(c, c->d_desc, max_k, 0));
-        CHK(dgrow(c, c->d_lev_pin, max_k, 0));
-        CHK(dgrow(c, c->d_lev_pos, max_k, 0));
-        CHK(dgrow(c, c->d_lev_cback, max_nlev, 0));
-        CHK(dgrow(c, c->d_lev_pinbase, max_nlev + 1, 0));
+    CHK(ensure_dag_h(c));  // the level-bucketed kernels need the heights (swirld.py:117-120)
+    for (int i = 0; i < d.S; ++i) {
+        int hmax;
+        height_span(c, d.cut[i], d.cut[i + 1], &d.hmins[i], &hmax);
+        d.nlevs[i] = hmax - d.hmins[i] + 1;
+        max_nlev = std::max(max_nlev, d.nlevs[i]);
+        max_k = std::max(max_k, d.cut[i + 1] - d.cut[i]);
+        c->ctr.levels += d.nlevs[i];
     }
-    while ((int)c->cs_events.size() < S) {
+    CHK(dgrow(c, c->d_lev_cnt, max_nlev, 0));
+    CHK(dgrow(c, c->d_lev_start, max_nlev + 1, 0));
+    CHK(dgrow(c, c->d_lev_cursor, max_nlev, 0));
+    CHK(dgrow(c, c->d_desc, max_k, 0));
+    CHK(dgrow(c, c->d_lev_pin, max_k, 0));
+    CHK(dgrow(c, c->d_lev_pos, max_k, 0));
+    CHK(dgrow(c, c->d_lev_cback, max_nlev, 0));
+    CHK(dgrow(c, c->d_lev_pinbase, max_nlev + 1, 0));
+    return SW_OK;
+}
+
+// ---- phase: the sweep stream opens behind whatever the main stream still has in flight (a small append returns without a
+// host synchronisation); decides whether the call runs gated
+int open_sweep_stream(sw_ctx* c, DivideCall& d) {
+    while ((int)c->cs_events.size() < d.S) {
         hipEvent_t e;
         HIPCHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
         c->cs_events.push_back(e);
     }
-    // ---- enqueue every can_see sweep on its own stream (behind whatever the main stream still has in
-    // flight: a small append returns without a host synchronisation)
     hipStream_t cs = c->stream_cs;
     HIPCHK(c, hipEventRecord(c->ev_main_mark, c->stream));
     HIPCHK(c, hipStreamWaitEvent(cs, c->ev_main_mark, 0));
     // ONE round loop for the whole call, gated on the device by the sweep's progress (SW_GATED=1): the dataflow sweep of a
     // plain table, not the split loop (its meetings are host calls), not preswept ranges, not the windowed table
-    const bool gated = c->gated && S > 1 && S <= SW_PROV_ROWS && flow && !preswept && !c->split && !c->split_emulate && !c->vm.active && np <= 256;
-    LoopGate* d_gate = reinterpret_cast<LoopGate*>(c->d_rb + SW_GATE_OFF);
-    if (gated) hipLaunchKernelGGL(k_set_stage, dim3(1), dim3(64), 0, cs, d_gate, 0);   // (the previous loop is done: cs waited for it)
-    hipEvent_t cs_t0 = nullptr, cs_t1 = nullptr;
-    if (c->profiling) { cs_t0 = next_event(c); cs_t1 = next_event(c); (void)hipEventRecord(cs_t0, cs); }
-    std::vector<Span> cansee_spans;
+    d.gated = c->gated && d.S > 1 && d.S <= SW_PROV_ROWS && d.flow && !d.preswept && !c->split && !c->split_emulate && !c->vm.active && c->npad <= 256;
+    if (d.gated) hipLaunchKernelGGL(k_set_stage, dim3(1), dim3(64), 0, cs, loop_gate(c), 0);   // (the previous loop is done: cs waited for it)
+    if (c->profiling) { d.cs_t0 = next_event(c); d.cs_t1 = next_event(c); (void)hipEventRecord(d.cs_t0, cs); }
     if (c->profiling) { c->tm.resolve_ms = 0.f; c->tm.resolve_launches = 0; }
-    // chain positions of the cuts: bounds[i][m] = events of member m below cut[i].  One cut pair that
-    // ends at the last appended event (a Node's call) is known on the host: chain lengths at the last
-    // divide and now.  Otherwise device binary searches over the chain pool.
+    return SW_OK;
+}
+
+// ---- phase: chain positions of the cuts: bounds[i][m] = events of member m below cut[i].  One cut pair that
+// ends at the last appended event (a Node's call) is known on the host: chain lengths at the last
+// divide and now.  Otherwise device binary searches over the chain pool.
+int build_bounds(sw_ctx* c, DivideCall& d) {
+    const int np = c->npad, S = d.S;
+    hipStream_t cs = c->stream_cs;
     std::vector<int32_t>& bounds_h = c->bounds_stage;
-    bool bounds_pending = false;
     bounds_h.resize((size_t)(S + 1) * np);
     CHK(dgrow(c, c->d_bounds, (size_t)(S + 1) * np, 0));
-    if (S == 1 && first + K == c->N) {
+    if (S == 1 && d.first + d.K == c->N) {
         std::copy(c->divided_cnt.begin(), c->divided_cnt.end(), bounds_h.begin());
         std::fill(bounds_h.begin() + np, bounds_h.end(), 0);
         std::copy(c->nev.begin(), c->nev.end(), bounds_h.begin() + np);
         HIPCHK(c, hipMemcpyAsync(c->d_bounds.p, bounds_h.data(), bounds_h.size() * sizeof(int32_t), hipMemcpyHostToDevice, cs));
-    } else {
-        CHK(dgrow(c, c->d_cuts, S + 1, 0));
-        std::vector<long long> cuts_ll(cut.begin(), cut.end());
-        HIPCHK(c, hipMemcpyAsync(c->d_cuts.p, cuts_ll.data(), (S + 1) * sizeof(long long), hipMemcpyHostToDevice, cs));
-        hipLaunchKernelGGL(k_chain_bounds, dim3(S + 1), dim3(np), 0, cs, (const int*)c->d_chain_start.p, (const int*)c->d_chain_cnt.p,
-                           (const int*)c->d_chain_ev.p, (const long long*)c->d_cuts.p, np, c->d_bounds.p);
-        c->ctr.kernel_launches++;
-        // (read back behind the kernel; the host needs the table only for the round loops below: it waits for
-        // `ev_bounds` there, after every sweep has been enqueued — the GPU starts sweeping ~0.1 ms earlier)
-        HIPCHK(c, hipMemcpyAsync(bounds_h.data(), c->d_bounds.p, bounds_h.size() * sizeof(int32_t), hipMemcpyDeviceToHost, cs));
-        if (!c->ev_bounds) HIPCHK(c, hipEventCreateWithFlags(&c->ev_bounds, hipEventDisableTiming));
-        HIPCHK(c, hipEventRecord(c->ev_bounds, cs));
-        bounds_pending = true;
+        return SW_OK;
     }
-    // ---- chunk plan: a sub-batch long enough is cut into G chunks that are swept concurrently, each from
-    // `halo` events before its start (k_cansee_chunks); their chain positions come from one more search kernel
+    CHK(dgrow(c, c->d_cuts, S + 1, 0));
+    std::vector<long long> cuts_ll(d.cut.begin(), d.cut.end());
+    HIPCHK(c, hipMemcpyAsync(c->d_cuts.p, cuts_ll.data(), (S + 1) * sizeof(long long), hipMemcpyHostToDevice, cs));
+    hipLaunchKernelGGL(k_chain_bounds, dim3(S + 1), dim3(np), 0, cs, (const int*)c->d_chain_start.p, (const int*)c->d_chain_cnt.p,
+                       (const int*)c->d_chain_ev.p, (const long long*)c->d_cuts.p, np, c->d_bounds.p);
+    c->ctr.kernel_launches++;
+    // (read back behind the kernel; the host needs the table only for the round loops: do_divide waits for
+    // `ev_bounds` after every sweep has been enqueued — the GPU starts sweeping ~0.1 ms earlier)
+    HIPCHK(c, hipMemcpyAsync(bounds_h.data(), c->d_bounds.p, bounds_h.size() * sizeof(int32_t), hipMemcpyDeviceToHost, cs));
+    if (!c->ev_bounds) HIPCHK(c, hipEventCreateWithFlags(&c->ev_bounds, hipEventDisableTiming));
+    HIPCHK(c, hipEventRecord(c->ev_bounds, cs));
+    d.bounds_pending = true;
+    return SW_OK;
+}
+
+// ---- phase: chunk plan: a sub-batch long enough is cut into G chunks that are swept concurrently, each from
+// `halo` events before its start (k_cansee_chunks); their chain positions come from one more search kernel
+int plan_chunks(sw_ctx* c, const DivideCall& d) {
+    const int np = c->npad, S = d.S;
+    const std::vector<int64_t>& cut = d.cut;
+    hipStream_t cs = c->stream_cs;
     c->chunk_plan.assign(S, sw_ctx::ChunkPlan{});
-    bool may_chunk = flow && !preswept && np <= 256 && c->chunks > 1 && !c->chunks_off && S <= SW_PROV_ROWS;
+    bool may_chunk = d.flow && !d.preswept && np <= 256 && c->chunks > 1 && !c->chunks_off && S <= SW_PROV_ROWS;
     if (c->debug_timing && S > SW_PROV_ROWS)   // (only the SW_CUTS tuning hook can ask for that many sub-batches)
         fprintf(stderr, "[sw] %d sub-batches: more than %d, swept unchunked\n", S, SW_PROV_ROWS);
     if (may_chunk && c->vm.active && !c->vm_scratch_ok) {   // windowed table: the scratch rows are mapped by the first call that can use them
@@ -1438,370 +1415,466 @@ int do_divide(sw_ctx* c, int64_t first, int64_t K) {
         for (int i = 0; i < S; ++i) any = any || (cut[i + 1] - cut[i]) / c->chunk_min >= 2;
         if (any) CHK(vm_map_scratch(c));
     }
-    if (may_chunk && (c->vm.active ? c->vm_scratch_ok : c->d_L.cap >= table_elems(c, c->cap))) {   // (the halo scratch rows exist: they live behind the table's last row)
-        std::vector<long long>& ccuts = c->ccuts_stage;
-        ccuts.clear();
-        int max_g = 0;
-        for (int i = 0; i < S; ++i) {
-            const int64_t a = cut[i], len = cut[i + 1] - cut[i];
-            const int G = (int)std::min<int64_t>(c->chunks, len / c->chunk_min);
-            if (G < 2) continue;
-            sw_ctx::ChunkPlan& pl = c->chunk_plan[i];
-            pl.G = G;
-            pl.row0 = (int)ccuts.size();
-            for (int k = 0; k <= G; ++k) pl.a[k] = a + len * k / G;
-            for (int k = 0; k < G; ++k) {
-                pl.w[k] = k == 0 ? a : std::max(a, pl.a[k] - c->halo);
-                ccuts.push_back(pl.w[k]);
-                ccuts.push_back(pl.a[k]);
-            }
-            ccuts.push_back(pl.a[G]);   // rows 2G and 2G + 1: the end, twice — chunk k ends at row 2k + 3 for every k
-            ccuts.push_back(pl.a[G]);
-            max_g = std::max(max_g, G);
-        }
-        if (!ccuts.empty()) {
-            CHK(dgrow(c, c->d_ccuts, ccuts.size(), 0));
-            CHK(dgrow(c, c->d_cbnd, ccuts.size() * (size_t)np, 0));
-            // (pageable source: the copy is staged before the call returns)
-            HIPCHK(c, hipMemcpyAsync(c->d_ccuts.p, ccuts.data(), ccuts.size() * sizeof(long long), hipMemcpyHostToDevice, cs));
-            hipLaunchKernelGGL(k_chain_bounds, dim3((unsigned)ccuts.size()), dim3(np), 0, cs, (const int*)c->d_chain_start.p,
-                               (const int*)c->d_chain_cnt.p, (const int*)c->d_chain_ev.p, (const long long*)c->d_ccuts.p, np, c->d_cbnd.p);
-            HIPCHK(c, hipMemsetAsync(c->d_prov, 0, (size_t)SW_PROV_ROWS * (SW_MAX_CHUNKS + 1) * sizeof(unsigned), cs));
-            c->ctr.kernel_launches++;
-        }
-    }
+    // (the halo scratch rows must exist: they live behind the table's last row)
+    if (!may_chunk || !(c->vm.active ? c->vm_scratch_ok : c->d_L.cap >= table_elems(c, c->cap))) return SW_OK;
+    std::vector<long long>& ccuts = c->ccuts_stage;
+    ccuts.clear();
     for (int i = 0; i < S; ++i) {
-        const int64_t a = cut[i], k = cut[i + 1] - cut[i];
+        const int64_t a = cut[i], len = cut[i + 1] - cut[i];
+        const int G = (int)std::min<int64_t>(c->chunks, len / c->chunk_min);
+        if (G < 2) continue;
+        sw_ctx::ChunkPlan& pl = c->chunk_plan[i];
+        pl.G = G;
+        pl.row0 = (int)ccuts.size();
+        for (int k = 0; k <= G; ++k) pl.a[k] = a + len * k / G;
+        for (int k = 0; k < G; ++k) {
+            pl.w[k] = k == 0 ? a : std::max(a, pl.a[k] - c->halo);
+            ccuts.push_back(pl.w[k]);
+            ccuts.push_back(pl.a[k]);
+        }
+        ccuts.push_back(pl.a[G]);   // rows 2G and 2G + 1: the end, twice — chunk k ends at row 2k + 3 for every k
+        ccuts.push_back(pl.a[G]);
+    }
+    if (ccuts.empty()) return SW_OK;
+    CHK(dgrow(c, c->d_ccuts, ccuts.size(), 0));
+    CHK(dgrow(c, c->d_cbnd, ccuts.size() * (size_t)np, 0));
+    // (pageable source: the copy is staged before the call returns)
+    HIPCHK(c, hipMemcpyAsync(c->d_ccuts.p, ccuts.data(), ccuts.size() * sizeof(long long), hipMemcpyHostToDevice, cs));
+    hipLaunchKernelGGL(k_chain_bounds, dim3((unsigned)ccuts.size()), dim3(np), 0, cs, (const int*)c->d_chain_start.p,
+                       (const int*)c->d_chain_cnt.p, (const int*)c->d_chain_ev.p, (const long long*)c->d_ccuts.p, np, c->d_cbnd.p);
+    HIPCHK(c, hipMemsetAsync(c->d_prov, 0, (size_t)SW_PROV_ROWS * (SW_MAX_CHUNKS + 1) * sizeof(unsigned), cs));
+    c->ctr.kernel_launches++;
+    return SW_OK;
+}
+
+// the level-bucketed sweep of the events [a, a + k): histogram of the heights, the levels' offsets, the events' descriptors
+// scattered by level, then the sweep itself (`scs`: the span of that last kernel)
+template <int NW>
+int launch_cansee_levels(sw_ctx* c, int64_t a, int64_t k, int hmin, int nlev, Span* scs) {
+    const int np = c->npad;
+    hipStream_t cs = c->stream_cs;
+    HIPCHK(c, hipMemsetAsync(c->d_lev_cnt.p, 0, nlev * sizeof(int32_t), cs));
+    HIPCHK(c, hipMemsetAsync(c->d_lev_pin.p, 0, (size_t)k, cs));
+    const int eb = (int)((k + 255) / 256);
+    const int ringH = cansee_cfg(np, c->ring_H_req).H;
+    hipLaunchKernelGGL(k_level_hist, dim3(eb), dim3(256), 0, cs, (const int*)c->d_ht.p, (int)a, (int)k, hmin, c->d_lev_cnt.p,
+                       (const int*)c->d_cr.p, (const int*)c->d_op.p, (const int*)c->d_seq.p, (const int*)c->d_chain_start.p,
+                       (const int*)c->d_chain_cnt.p, (const int*)c->d_chain_ev.p, ringH, c->d_lev_pin.p);
+    hipLaunchKernelGGL(k_level_scan, dim3(1), dim3(1024), 0, cs, (const int*)c->d_lev_cnt.p, nlev, c->d_lev_start.p, c->d_lev_cursor.p);
+    HIPCHK(c, hipMemsetAsync(c->d_lev_cback.p, 0, nlev * sizeof(int32_t), cs));
+    hipLaunchKernelGGL(k_level_scatter, dim3(eb), dim3(256), 0, cs, (const int*)c->d_ht.p, (const int*)c->d_cr.p,
+                       (const int*)c->d_sp.p, (const int*)c->d_op.p, (const int*)c->d_seq.p, (int)a, (int)k, hmin,
+                       (const int*)c->d_lev_start.p, c->d_lev_cursor.p, c->d_lev_cback.p, c->d_desc.p, ringH, np,
+                       (const unsigned char*)c->d_lev_pin.p, c->d_lev_pos.p);
+    // pinned events in front of every level (the front cursors' exclusive scan), then the children's descriptors
+    hipLaunchKernelGGL(k_level_scan, dim3(1), dim3(1024), 0, cs, (const int*)c->d_lev_cursor.p, nlev, c->d_lev_pinbase.p, c->d_lev_cback.p);
+    hipLaunchKernelGGL(k_level_patch, dim3(eb), dim3(256), 0, cs, (const int*)c->d_ht.p, (const int*)c->d_cr.p, (const int*)c->d_op.p,
+                       (const int*)c->d_seq.p, (int)a, (int)k, hmin, (const int*)c->d_lev_start.p, (const int*)c->d_lev_pinbase.p,
+                       c->d_desc.p, ringH, np, (const int*)c->d_chain_start.p, (const int*)c->d_chain_cnt.p, (const int*)c->d_chain_ev.p,
+                       (const int*)c->d_lev_pos.p);
+    c->ctr.kernel_launches += 5;
+    *scs = span_begin(c, cs);
+    return launch_cansee<NW>(c, nlev, a);
+}
+
+// ---- phase: every can_see sweep of the call, enqueued on the sweep stream; behind sweep i its event and, in a gated call,
+// the stage the round loop may advance to
+template <int NW>
+int enqueue_sweeps(sw_ctx* c, DivideCall& d) {
+    hipStream_t cs = c->stream_cs;
+    for (int i = 0; i < d.S; ++i) {
+        const int64_t a = d.cut[i], k = d.cut[i + 1] - d.cut[i];
         Span scs{};
-        if (preswept) {
+        if (d.preswept) {
             scs = span_begin(c, cs);
-        } else if (flow && c->chunk_plan[i].G >= 2) {
+        } else if (d.flow && c->chunk_plan[i].G >= 2) {
             scs = span_begin(c, cs);
             CHK(launch_cansee_chunks<NW>(c, i));
-        } else if (flow) {
+        } else if (d.flow) {
             scs = span_begin(c, cs);
             CHK(launch_cansee_flow<NW>(c, i, a));
         } else {
-            HIPCHK(c, hipMemsetAsync(c->d_lev_cnt.p, 0, nlevs[i] * sizeof(int32_t), cs));
-            HIPCHK(c, hipMemsetAsync(c->d_lev_pin.p, 0, (size_t)k, cs));
-            const int eb = (int)((k + 255) / 256);
-            const int ringH = cansee_cfg(np, c->ring_H_req).H;
-            hipLaunchKernelGGL(k_level_hist, dim3(eb), dim3(256), 0, cs, (const int*)c->d_ht.p, (int)a, (int)k, hmins[i], c->d_lev_cnt.p,
-                               (const int*)c->d_cr.p, (const int*)c->d_op.p, (const int*)c->d_seq.p, (const int*)c->d_chain_start.p,
-                               (const int*)c->d_chain_cnt.p, (const int*)c->d_chain_ev.p, ringH, c->d_lev_pin.p);
-            hipLaunchKernelGGL(k_level_scan, dim3(1), dim3(1024), 0, cs, (const int*)c->d_lev_cnt.p, nlevs[i], c->d_lev_start.p, c->d_lev_cursor.p);
-            HIPCHK(c, hipMemsetAsync(c->d_lev_cback.p, 0, nlevs[i] * sizeof(int32_t), cs));
-            hipLaunchKernelGGL(k_level_scatter, dim3(eb), dim3(256), 0, cs, (const int*)c->d_ht.p, (const int*)c->d_cr.p,
-                               (const int*)c->d_sp.p, (const int*)c->d_op.p, (const int*)c->d_seq.p, (int)a, (int)k, hmins[i],
-                               (const int*)c->d_lev_start.p, c->d_lev_cursor.p, c->d_lev_cback.p, c->d_desc.p, ringH, np,
-                               (const unsigned char*)c->d_lev_pin.p, c->d_lev_pos.p);
-            // pinned events in front of every level (the front cursors' exclusive scan), then the children's descriptors
-            hipLaunchKernelGGL(k_level_scan, dim3(1), dim3(1024), 0, cs, (const int*)c->d_lev_cursor.p, nlevs[i], c->d_lev_pinbase.p, c->d_lev_cback.p);
-            hipLaunchKernelGGL(k_level_patch, dim3(eb), dim3(256), 0, cs, (const int*)c->d_ht.p, (const int*)c->d_cr.p, (const int*)c->d_op.p,
-                               (const int*)c->d_seq.p, (int)a, (int)k, hmins[i], (const int*)c->d_lev_start.p, (const int*)c->d_lev_pinbase.p,
-                               c->d_desc.p, ringH, np, (const int*)c->d_chain_start.p, (const int*)c->d_chain_cnt.p, (const int*)c->d_chain_ev.p,
-                               (const int*)c->d_lev_pos.p);
-            c->ctr.kernel_launches += 2;
-            c->ctr.kernel_launches += 3;
-            scs = span_begin(c, cs);
-            CHK(launch_cansee<NW>(c, nlevs[i], a));
+            CHK(launch_cansee_levels<NW>(c, a, k, d.hmins[i], d.nlevs[i], &scs));
         }
         span_end(c, scs, cs);
-        if (c->profiling) cansee_spans.push_back(scs);
-        if (gated && !c->gate_lag) { hipLaunchKernelGGL(k_set_stage, dim3(1), dim3(64), 0, cs, d_gate, i + 1); c->ctr.kernel_launches++; }
+        if (c->profiling) d.cansee_spans.push_back(scs);
+        if (d.gated && !c->gate_lag) { hipLaunchKernelGGL(k_set_stage, dim3(1), dim3(64), 0, cs, loop_gate(c), i + 1); c->ctr.kernel_launches++; }
         HIPCHK(c, hipEventRecord(c->cs_events[i], cs));
     }
-    if (c->profiling) (void)hipEventRecord(cs_t1, cs);
-    clk.mark(&c->stage_us[0]);
+    if (c->profiling) (void)hipEventRecord(d.cs_t1, cs);
+    return SW_OK;
+}
 
-    if (bounds_pending) HIPCHK(c, hipEventSynchronize(c->ev_bounds));
-    // ---- round loops, one per sub-batch, each over the events visible so far
-    CHK(ensure_rounds(c, std::max(c->R, 1) + c->BATCH + 4));
-    Span sp_rl = span_begin(c);
-    hipEvent_t fin_t0 = nullptr;
-    float tally_ms = 0.f;
-    int tally_launches = 0;
-    // members' visible chain lengths before this call and after every sub-batch: rows of the cut table
-    std::vector<int32_t> clen_prev(bounds_h.begin(), bounds_h.begin() + np), clen(np, 0);
-    bool aux_armed = false;
-    std::function<int()> pending_aux = []() -> int { return SW_OK; };
-    // start round of sub-batch i's loop = the smallest front round among the members it adds events to; a member's first event
-    // (swirld.py:195-198) opens round 0 for it: lo[0][m], chain position 0, uploaded in front of the loop
-    auto start_round = [&](int i, bool* row0_dirty) -> int {
-        int r_start = 0x7fffffff;
-        *row0_dirty = false;
-        std::copy(bounds_h.begin() + (size_t)(i + 1) * np, bounds_h.begin() + (size_t)(i + 2) * np, clen.begin());
-        for (int m = 0; m < n; ++m) {
-            if (clen[m] > clen_prev[m]) {  // member touched by this sub-batch
-                if (c->front[m] < 0) {     // its root (swirld.py:195-198): lo[0][m], chain position 0
-                    c->lo0_h[m] = c->first_ev[m];
-                    c->front[m] = 0;
-                    *row0_dirty = true;
-                }
-                r_start = std::min(r_start, c->front[m]);
+// ---- round loops: what a loop needs in front of it and leaves behind it
+
+// In front of a loop that adds the events up to sub-batch i.  Its start round = the smallest front round among the members
+// it adds events to; a member's first event (swirld.py:195-198) opens round 0 for it: lo[0][m], chain position 0, uploaded
+// in front of the loop.  Mutates c->front / c->lo0_h and fills d.clen from row i + 1 of the cut table (d.clen_prev is the
+// row the loop before it ended at).  On the main stream: the wait for sweep `i_sweep`, then row 0 of the round table and the
+// members' front rounds if a root is among the events.
+int begin_loop(sw_ctx* c, DivideCall& d, int i, int i_sweep, int* r_start_out) {
+    const int np = c->npad;
+    int r_start = 0x7fffffff;
+    bool row0_dirty = false;
+    std::copy(c->bounds_stage.begin() + (size_t)(i + 1) * np, c->bounds_stage.begin() + (size_t)(i + 2) * np, d.clen.begin());
+    for (int m = 0; m < c->n; ++m) {
+        if (d.clen[m] > d.clen_prev[m]) {  // member touched by this sub-batch
+            if (c->front[m] < 0) {         // its root (swirld.py:195-198): lo[0][m], chain position 0
+                c->lo0_h[m] = c->first_ev[m];
+                c->front[m] = 0;
+                row0_dirty = true;
             }
+            r_start = std::min(r_start, c->front[m]);
         }
-        if (r_start == 0x7fffffff) r_start = std::max(c->R - 1, 0);
-        return r_start;
-    };
-    auto upload_row0 = [&]() -> int {
+    }
+    *r_start_out = r_start == 0x7fffffff ? std::max(c->R - 1, 0) : r_start;
+    HIPCHK(c, hipStreamWaitEvent(c->stream, c->cs_events[i_sweep], 0));
+    if (row0_dirty) {
         HIPCHK(c, hipMemcpyAsync(c->d_lo.p, c->lo0_h.data(), np * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
         std::copy(c->front.begin(), c->front.end(), c->front_dev.begin());
         HIPCHK(c, hipMemcpyAsync(c->d_front.p, c->front_dev.data(), np * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-        return SW_OK;
-    };
-    // what follows a finished loop i (its state is in c->h_rb): the chunk counters of its sweep, the host mirror of the front rounds,
-    // and the finalize / witness-row / voter-mask launches of its sub-batch, armed here and enqueued behind the next loop's shot
-    auto chunk_check = [&](int i) {
-        if (c->chunk_plan[i].G >= 2) {
-            // the sweep of this sub-batch is complete (the loop waited for it) and its counters came back with the
-            // loop state: provisional entries per chunk, entries the repair changed.  (A loop never reports SW_OK
-            // without at least one read-back behind a shot that waited for cs_events[i]: h_rb is this sub-batch's or a later one.)
-            const unsigned* pv = reinterpret_cast<const unsigned*>(c->h_rb + ((unsigned char*)c->d_prov - c->d_rb));
-            const sw_ctx::ChunkPlan& pl = c->chunk_plan[i];
-            for (int k = 1; k < pl.G; ++k) {
-                const unsigned cnt = pv[(size_t)i * SW_MAX_CHUNKS + k];
-                const int64_t len = pl.a[k + 1] - pl.a[k];
-                c->ctr.chunk_provisional += cnt;
-                if (cnt > (unsigned)std::min<int64_t>((len * c->n) / (32 * (c->chunk_cfg == 1 ? 2 : 4)), 0x7fffffff)) {
-                    c->ctr.chunk_resweeps++;
-                    c->chunks_off = true;   // this hashgraph has members silent for longer than the halo: sweep unchunked from now on
-                }
-            }
-            c->ctr.chunk_repaired += pv[(size_t)SW_PROV_ROWS * SW_MAX_CHUNKS + i];
+    }
+    d.clk.mark(&c->stage_us[1]);
+    return SW_OK;
+}
+
+// the chunk counters of sub-batch i's sweep, from the read-back slot read last
+void chunk_check(sw_ctx* c, int i) {
+    const sw_ctx::ChunkPlan& pl = c->chunk_plan[i];
+    if (pl.G < 2) return;
+    // the sweep of this sub-batch is complete (the loop waited for it) and its counters came back with the
+    // loop state: provisional entries per chunk, entries the repair changed.  (A loop never reports SW_OK
+    // without at least one read-back behind a shot that waited for cs_events[i]: h_rb is this sub-batch's or a later one.)
+    const unsigned* pv = reinterpret_cast<const unsigned*>(c->h_rb + ((unsigned char*)c->d_prov - c->d_rb));
+    for (int k = 1; k < pl.G; ++k) {
+        const unsigned cnt = pv[(size_t)i * SW_MAX_CHUNKS + k];
+        const int64_t len = pl.a[k + 1] - pl.a[k];
+        c->ctr.chunk_provisional += cnt;
+        if (cnt > (unsigned)std::min<int64_t>((len * c->n) / (32 * (c->chunk_cfg == 1 ? 2 : 4)), 0x7fffffff)) {
+            c->ctr.chunk_resweeps++;
+            c->chunks_off = true;   // this hashgraph has members silent for longer than the halo: sweep unchunked from now on
         }
-    };
-    auto after_loop = [&](int i, int r_start, int64_t fin_from, hipEvent_t loop_done) -> int {
-        chunk_check(i);
-        // host mirror of the per-member front round (kept by the resolve kernel, read back with the loop state)
-        const int R = c->R;
-        for (int m = 0; m < n; ++m) c->front[m] = std::max(c->front[m], c->front_dev[m]);
-        clen_prev.swap(clen);
-        clk.mark(&c->stage_us[3]);
-        // The rounds of every event below `limit` are final now (later sub-batches only add lo
-        // entries that compare greater than every existing event), so their round numbers,
-        // sees-masks, witness rows and voter masks are produced on a third stream, overlapping the
-        // round loop of the next sub-batch — and ENQUEUED behind that loop's first shot (they must wait for
-        // this loop's kernels, which the aux stream learns from an event recorded behind them).
-        CHK(ensure_rounds(c, R + 2));
-        const int64_t a0 = fin_from, k0 = cut[i + 1] - fin_from;   // (the early part of the last sub-batch is done)
-        const int rs_ = r_start, i_ = i;
-        aux_armed = true;
-        const int S_ = S;
-        pending_aux = [c, np, R, a0, k0, rs_, i_, S_, loop_done, &fin_t0, &aux_armed]() -> int {
-            if (!aux_armed) return SW_OK;
-            aux_armed = false;
-            hipStream_t ax = c->stream_aux;
-            HIPCHK(c, hipStreamWaitEvent(ax, loop_done, 0));
-            if (i_ == 0 && c->profiling) { fin_t0 = next_event(c); (void)hipEventRecord(fin_t0, ax); }
-            // (a finalize that runs beside the next round loop is throttled: fewer workgroups, less pressure on the loop's gathers;
-            // the last one has nothing to hide behind and takes the whole GPU)
-            const int blocks = (int)std::min<int64_t>((k0 + 3) / 4, i_ == S_ - 1 ? 8192 : c->fin_blocks);
-            CHK(launch_finalize<NW>(c, ax, a0, k0, R, blocks));
-            const int total = (R - rs_) * np;
-            if (total > 0)
-                hipLaunchKernelGGL(k_witness_table, dim3((total + 255) / 256), dim3(256), 0, ax,
-                                   (const int*)c->d_lo.p, R, rs_, np, c->d_wit.p);
-            c->ctr.kernel_launches += 1;
-            return launch_voter_masks<NW>(c, rs_, R, ax);
-        };
-        clk.mark(&c->stage_us[4]);
-        return SW_OK;
-    };
-    // ---- the gated loop (SW_GATED=1): ONE round loop over the whole call.  The sweep stream publishes how many sub-batches it
-    // has swept (k_set_stage) and the resolve step latches that one iteration late: no seam between sub-batches (host round
-    // trip, read-back, k_loop_init, first-shot logic), no round searched twice, a member at the end of its visible chain waits
-    // in its round.  The predicted iterations of the whole call go out in pieces of about one sub-batch, each read back into
-    // its own pinned slot: the host waits for the previous piece while the next one runs, and finalizes the events below the
-    // band of the round in progress beside the loop; witness rows and voter masks follow the loop, as the last sub-batch's did.
-    auto run_gated = [&]() -> int {
-        bool row0_dirty = false;
-        const int r_start = start_round(S - 1, &row0_dirty);   // (clen_prev is row 0: every member the call adds events to)
-        HIPCHK(c, hipStreamWaitEvent(c->stream, c->cs_events[0], 0));
-        if (row0_dirty) CHK(upload_row0());
-        clk.mark(&c->stage_us[1]);
-        const bool dbg_t = c->debug_timing;
-        const auto dbg_t0 = std::chrono::steady_clock::now();
-        const int64_t dbg_it0 = c->ctr.round_iterations;
-        if (dbg_t) (void)hipStreamSynchronize(c->stream);   // separates "waiting for the first sweep" from the loop itself
-        const auto dbg_t1 = std::chrono::steady_clock::now();
-        hipLaunchKernelGGL(k_loop_init, dim3(1), dim3(std::min(2 * np, 1024)), 0, c->stream, loop_bufs(c), np, r_start,
-                           (int)cut[1], c->NEARCAP, (const int*)(c->d_bounds.p + np), c->d_chain_len.p, c->eval_src,
-                           c->fin_band ? (int)first : 0x7fffffff, (int)std::min<int64_t>(c->ctr.round_iterations - c->dbg_iter_base, 0x7fffffff),
-                           S, (const int*)c->d_bounds.p, (const long long*)c->d_cuts.p);
-        c->eval_src = 0;
-        c->ctr.kernel_launches++;
-        std::vector<Span> tally_spans, resolve_spans;
-        std::vector<Span>* tsp = c->profiling ? &tally_spans : nullptr;
-        std::vector<Span>* rsp = c->profiling ? &resolve_spans : nullptr;
-        const int total = predict_shot(c, K, true);
-        const int P = std::min(S, SW_PROV_ROWS);
-        CHK(ensure_rounds(c, c->R + total + 8));
-        RState st{};
-        int64_t fin_from = first;
-        int launched = 0;
-        auto enqueue_piece = [&](int j, int n_it) -> int {
-            CHK(launch_iterations<NW>(c, n_it, tsp, rsp));
-            launched += n_it;
-            HIPCHK(c, hipGetLastError());
-            HIPCHK(c, hipMemcpyAsync(c->h_rb_all + (size_t)j * c->rb_bytes, c->d_rb, c->rb_bytes, hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(c, hipEventRecord(c->rb_events[j], c->stream));
-            return SW_OK;
-        };
-        // read-back slot j: loop state, sweep error flag, front rounds, chunk counters
-        auto take = [&](int j) -> int {
-            HIPCHK(c, hipEventSynchronize(c->rb_events[j]));
-            c->h_rb = c->h_rb_all + (size_t)j * c->rb_bytes;
-            memcpy(&st, c->h_rb, sizeof st);
-            int ferr = 0;
-            memcpy(&ferr, c->h_rb + 2 * sizeof(RState), sizeof ferr);
-            if (ferr) return fail(c, SW_EIO, "can_see sweep gave up polling (code %d): internal protocol error", ferr);
-            if (st.err) return fail(c, SW_ERANGE, "round table capacity exceeded (internal)");
-            return SW_OK;
-        };
-        // events below the band of the round in progress have their final round (rows 0 .. st.r of the table are final: a
-        // round commits only when every member has its next-round event or is exhausted at the last stage)
-        auto early_fin = [&](int j) -> int {
-            const int64_t upto = std::min<int64_t>(std::min(st.mlo, st.N), first + K);
-            if (!c->fin_band || st.done || st.iter <= 0 || upto < fin_from + 16384) return SW_OK;
-            HIPCHK(c, hipStreamWaitEvent(c->stream_aux, c->rb_events[j], 0));
-            if (c->profiling && !fin_t0) { fin_t0 = next_event(c); (void)hipEventRecord(fin_t0, c->stream_aux); }
-            CHK(launch_finalize<NW>(c, c->stream_aux, fin_from, upto - fin_from, st.r + 1, c->fin_blocks));
-            fin_from = upto;
-            return SW_OK;
-        };
-        const int piece = std::max(2, (total / P) & ~1);
-        int left = total, j = 0;
-        bool taken_last = false;
-        // SW_GATE_LAG (test hook): the stage schedule fixed by the ORDER OF LAUNCHES on the loop stream instead of by the race
-        // with the sweep stream.  Pieces of exactly `lag` iterations; behind each the loop stream waits for the sweeps of the
-        // next `gate_step` sub-batches and publishes them itself with the same k_set_stage: iteration t loads
-        // vis = min(S, 1 + (t / lag) * gate_step).  Nothing on the device waits for `vis`, every publication is enqueued
-        // behind a sweep already in the queue, and the iteration bound below ends a loop that does not finish.  The pinned
-        // slots are reused in turn (the host is one piece behind, as below).
-        if (const int lag = c->gate_lag; lag > 0) {
-            left = 0;
-            taken_last = true;
-            int pub = 1;   // (stage 1 is the loop's own start: k_loop_init)
-            const int64_t bound = (int64_t)c->max_height + 2 + c->N / c->K + 4096 + total + (int64_t)lag * S;
-            for (;; ++j) {
-                if ((int64_t)launched > bound)
-                    return fail(c, SW_EIO, "round loop did not terminate after %d iterations (r=%d, SW_GATE_LAG=%d)", launched, st.r, lag);
-                CHK(ensure_rounds(c, c->R + launched + lag + 4));
-                CHK(enqueue_piece(j % SW_PROV_ROWS, lag));
-                if (pub < S) {
-                    const int v = std::min(S, pub + c->gate_step);
-                    for (int i = pub; i < v; ++i) HIPCHK(c, hipStreamWaitEvent(c->stream, c->cs_events[i], 0));
-                    hipLaunchKernelGGL(k_set_stage, dim3(1), dim3(64), 0, c->stream, d_gate, v);
-                    c->ctr.kernel_launches++;
-                    pub = v;
-                }
-                if (j > 0) {
-                    CHK(take((j - 1) % SW_PROV_ROWS));
-                    if (st.done) break;
-                    CHK(early_fin((j - 1) % SW_PROV_ROWS));
-                }
-            }
-        }
-        for (; left > 0 && j < P; ++j) {
-            const int n_it = j == P - 1 ? left : std::min(left, piece);
-            CHK(enqueue_piece(j, n_it));
-            left -= n_it;
-            if (j > 0) {   // (the GPU has piece j queued behind the one the host waits for)
-                CHK(take(j - 1));
-                if (st.done) { taken_last = true; break; }
-                CHK(early_fin(j - 1));
-            }
-        }
-        if (!taken_last) CHK(take(j - 1));
-        // top-ups as in run_round_loop, one read-back each
-        while (!st.done) {
-            if ((int64_t)launched > (int64_t)c->max_height + 2 + c->N / c->K + 4096 + total)
-                return fail(c, SW_EIO, "round loop did not terminate after %d iterations (r=%d)", launched, st.r);
-            const int shot = launched < 8 ? 2 : (launched < 48 ? 8 : 4);
-            CHK(ensure_rounds(c, c->R + launched + shot + 4));
-            CHK(enqueue_piece(0, shot));
-            CHK(take(0));
-        }
-        if (K >= 4096 && !c->gate_lag) {   // (first-shot history is for real schedules)
-            c->gstat_iters += st.iter;
-            c->gstat_events += K;
-        }
-        c->eval_src = st.iter & 1;
-        c->R = st.max_round + 1;
-        memcpy(c->front_dev.data(), c->h_rb + 256, np * sizeof(int32_t));
-        if (c->unit_stake && c->tally_impl == 2) {
-            const int32_t* tc = reinterpret_cast<const int32_t*>(c->h_rb + ((unsigned char*)c->d_treecnt - c->d_rb));
-            for (int m = 0; m < np; ++m) c->ctr.tally_evals += tc[m];
-        } else
-        c->ctr.tally_evals += (int64_t)st.evals;
-        c->ctr.far_hops += (int64_t)st.far_hops;
-        c->ctr.round_iterations += st.iter;   // (every iteration the loop executed; those that waited for the sweep also in gated_idle_iterations)
+    }
+    c->ctr.chunk_repaired += pv[(size_t)SW_PROV_ROWS * SW_MAX_CHUNKS + i];
+}
+
+// what follows a finished loop i (its state is in c->h_rb): the chunk counters of its sweep — the gated loop's: of every
+// sweep, all complete since the loop ended at the last stage, all against the slot read last —, the host mirror of the
+// front rounds, and the tail of its sub-batch, armed here and enqueued by the next flush_tail
+int after_loop(sw_ctx* c, DivideCall& d, int i, int r_start) {
+    d.clk.mark(&c->stage_us[2]);
+    HIPCHK(c, hipEventRecord(c->ev_loop_done, c->stream));
+    for (int k = d.gated ? 0 : i; k <= i; ++k) chunk_check(c, k);
+    // host mirror of the per-member front round (kept by the resolve kernel, read back with the loop state)
+    for (int m = 0; m < c->n; ++m) c->front[m] = std::max(c->front[m], c->front_dev[m]);
+    d.clen_prev.swap(d.clen);
+    d.clk.mark(&c->stage_us[3]);
+    CHK(ensure_rounds(c, c->R + 2));
+    // (the early part of the sub-batch, below fin_from, is done)
+    d.tail = DeferredTail{true, i, r_start, c->R, d.fin_from, d.cut[i + 1] - d.fin_from, c->ev_loop_done};
+    d.clk.mark(&c->stage_us[4]);
+    return SW_OK;
+}
+
+// the armed tail, if any, goes to the aux stream: round numbers and sees-masks of the sub-batch's remaining events, its
+// witness rows, its voter masks.  Called behind the first shot of the next loop — host work that is off the critical path:
+// the GPU is already busy with that shot — and once more at the end of the call, for the last sub-batch's.
+template <int NW>
+int flush_tail(sw_ctx* c, DivideCall& d) {
+    DeferredTail& t = d.tail;
+    if (!t.armed) return SW_OK;
+    t.armed = false;
+    const int np = c->npad;
+    hipStream_t ax = c->stream_aux;
+    HIPCHK(c, hipStreamWaitEvent(ax, t.loop_done, 0));
+    if (t.i == 0 && c->profiling) { d.fin_t0 = next_event(c); (void)hipEventRecord(d.fin_t0, ax); }
+    // (a finalize that runs beside the next round loop is throttled: fewer workgroups, less pressure on the loop's gathers;
+    // the last one has nothing to hide behind and takes the whole GPU)
+    const int blocks = (int)std::min<int64_t>((t.k0 + 3) / 4, t.i == d.S - 1 ? 8192 : c->fin_blocks);
+    CHK(launch_finalize<NW>(c, ax, t.a0, t.k0, t.R, blocks));
+    const int total = (t.R - t.r_start) * np;
+    if (total > 0)
+        hipLaunchKernelGGL(k_witness_table, dim3((total + 255) / 256), dim3(256), 0, ax,
+                           (const int*)c->d_lo.p, t.R, t.r_start, np, c->d_wit.p);
+    c->ctr.kernel_launches += 1;
+    return launch_voter_masks<NW>(c, t.r_start, t.R, ax);
+}
+
+// ---- round loops: the mechanics both drivers share
+
+// one round loop as the host follows it
+struct LoopRun {
+    RState st{};        // the loop state read back last
+    int launched = 0;   // iterations enqueued
+    int pieces = 0;     // gated loop: pieces enqueued in front of the top-ups (SW_DEBUG_TIMING)
+    bool spans = false; // profiling: a span around every kernel of the loop (plain launches, no graphs)
+    std::vector<Span> tally_spans, resolve_spans;
+    // SW_DEBUG_TIMING: when the loop's set-up was enqueued, when the stream had drained the wait for the sweep in front of it
+    std::chrono::steady_clock::time_point t_wait, t_loop;
+    int64_t iters_before = 0;
+    double waited_ms() const { return std::chrono::duration<double, std::milli>(t_loop - t_wait).count(); }
+    double loop_ms() const { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_loop).count(); }
+};
+
+// the loop's k_loop_init on the main stream.  `fin_from`: the band pass writes the rounds of events from this one on
+// (SW_FIN_BAND; none without it); `stages` > 0: the gated loop over that many rows of the cut table
+void loop_start(sw_ctx* c, LoopRun& L, bool timed, int r_start, int64_t limit, const int32_t* visible_len, int64_t fin_from, int stages) {
+    L.t_wait = std::chrono::steady_clock::now();
+    L.iters_before = c->ctr.round_iterations;
+    if (timed) (void)hipStreamSynchronize(c->stream);   // separates "waiting for the sweep" from the loop itself
+    L.t_loop = std::chrono::steady_clock::now();
+    const int np = c->npad;
+    hipLaunchKernelGGL(k_loop_init, dim3(1), dim3(std::min(2 * np, 1024)), 0, c->stream, loop_bufs(c), np, r_start,
+                       (int)limit, c->NEARCAP, (const int*)visible_len, c->d_chain_len.p, c->eval_src,
+                       (int)std::min<int64_t>(c->fin_band ? fin_from : 0x7fffffff, 0x7fffffff),
+                       (int)std::min<int64_t>(c->ctr.round_iterations - c->dbg_iter_base, 0x7fffffff),
+                       stages, stages ? (const int*)c->d_bounds.p : (const int*)nullptr, stages ? (const long long*)c->d_cuts.p : (const long long*)nullptr);
+    c->eval_src = 0;
+    c->ctr.kernel_launches++;
+}
+
+// pinned read-back slot j of the call; -1: the slot that was read last
+unsigned char* rb_slot(sw_ctx* c, int j) { return j < 0 ? c->h_rb : c->h_rb_all + (size_t)j * c->rb_bytes; }
+
+// `n_it` more iterations on the main stream and behind them loop state, sweep error flag, the members' front rounds,
+// tree-tally and chunk counters: ONE copy into pinned slot j, its event recorded behind the copy (j >= 0)
+template <int NW>
+int enqueue_shot(sw_ctx* c, LoopRun& L, int n_it, int j) {
+    CHK(launch_iterations<NW>(c, n_it, L.spans ? &L.tally_spans : nullptr, L.spans ? &L.resolve_spans : nullptr));
+    L.launched += n_it;
+    if (c->split_failed) { c->poisoned = true; return fail(c, SW_EIO, "split round loop: a linked context did not arrive at iteration %lld (sw_split_link: every part calls sw_divide_rounds)", c->split_iter); }
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(rb_slot(c, j), c->d_rb, c->rb_bytes, hipMemcpyDeviceToHost, c->stream));
+    if (j >= 0) HIPCHK(c, hipEventRecord(c->rb_events[j], c->stream));
+    return SW_OK;
+}
+
+// wait for slot j (its event; j < 0: the main stream) and decode it.  The front rounds are copied at every read-back;
+// nothing reads front_dev before the loop has ended (after_loop), so the copies before the last one are only spare work.
+int take_read_back(sw_ctx* c, LoopRun& L, int j) {
+    if (j >= 0) HIPCHK(c, hipEventSynchronize(c->rb_events[j]));
+    else HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->h_rb = rb_slot(c, j);
+    memcpy(&L.st, c->h_rb, sizeof L.st);
+    int ferr = 0;
+    memcpy(&ferr, c->h_rb + 2 * sizeof(RState), sizeof ferr);
+    memcpy(c->front_dev.data(), c->h_rb + 256, c->npad * sizeof(int32_t));
+    if (ferr) return fail(c, SW_EIO, "can_see sweep gave up polling (code %d): internal protocol error", ferr);
+    if (L.st.err) return fail(c, SW_ERANGE, "round table capacity exceeded (internal)");
+    return SW_OK;
+}
+
+// rounds <= DAG height + 1, retries <= N / K: anything beyond that is a bug, not work.  `slack`: iterations the caller
+// enqueues whatever the loop reports (a gated loop's predicted total, the SW_GATE_LAG schedule's forced waits)
+int check_terminates(sw_ctx* c, const LoopRun& L, int64_t slack, int lag = 0) {
+    if ((int64_t)L.launched <= (int64_t)c->max_height + 2 + c->N / c->K + 4096 + slack) return SW_OK;
+    if (lag) return fail(c, SW_EIO, "round loop did not terminate after %d iterations (r=%d, SW_GATE_LAG=%d)", L.launched, L.st.r, lag);
+    return fail(c, SW_EIO, "round loop did not terminate after %d iterations (r=%d)", L.launched, L.st.r);
+}
+
+// short top-ups behind the predicted iterations, until the loop reports done
+inline int top_up_shot(int launched) { return launched < 8 ? 2 : (launched < 48 ? 8 : 4); }
+
+// Early finalize beside a running loop, from a read-back `st` of it: the events below the band of the round in progress,
+// [d.fin_from, upto), have their final round (round <= st.r - 1; rows 0 .. st.r of the table are committed and final: a round
+// commits only when every member has its next-round event or is exhausted at the last stage).  `slot_read`: the event the
+// aux stream waits for, if the host has not waited for the main stream itself.
+template <int NW>
+int early_finalize(sw_ctx* c, DivideCall& d, const RState& st, int64_t upto, hipEvent_t slot_read) {
+    if (st.iter <= 0 || upto < d.fin_from + 16384) return SW_OK;
+    if (slot_read) {
+        HIPCHK(c, hipStreamWaitEvent(c->stream_aux, slot_read, 0));
+        if (c->profiling && !d.fin_t0) { d.fin_t0 = next_event(c); (void)hipEventRecord(d.fin_t0, c->stream_aux); }
+    }
+    CHK(ensure_rounds(c, st.r + 2));   // (never grows in the gated loop: run_gated has ensured the rows of every iteration it enqueues)
+    CHK(launch_finalize<NW>(c, c->stream_aux, d.fin_from, upto - d.fin_from, st.r + 1, c->fin_blocks));
+    d.fin_from = upto;
+    return SW_OK;
+}
+
+// the books of a finished loop over `n_events` new events (its last read-back is in c->h_rb)
+void account_loop(sw_ctx* c, DivideCall& d, const LoopRun& L, int64_t n_events, bool gated) {
+    const RState& st = L.st;
+    // keep the rate estimate to runs where it means something (and, gated, to real schedules)
+    if (n_events >= 4096 && !(gated && c->gate_lag)) {
+        (gated ? c->gstat_iters : c->stat_iters) += st.iter;
+        (gated ? c->gstat_events : c->stat_events) += n_events;
+    }
+    // the per-member exhaustion marks persist across runs; the next run reads half 0: its k_loop_init moves them there
+    // (two small device copies here sat in the gap between two sub-batches' loops)
+    c->eval_src = st.iter & 1;
+    c->R = st.max_round + 1;
+    if (c->unit_stake && c->tally_impl == 2) {   // the tree search counts the tallies it really evaluated (per member, read back with the state)
+        const int32_t* tc = reinterpret_cast<const int32_t*>(c->h_rb + ((unsigned char*)c->d_treecnt - c->d_rb));
+        for (int m = 0; m < c->npad; ++m) c->ctr.tally_evals += tc[m];
+    } else
+    c->ctr.tally_evals += (int64_t)st.evals;
+    c->ctr.far_hops += (int64_t)st.far_hops;
+    c->ctr.round_iterations += st.iter;   // (every iteration the loop executed; those of a gated loop that waited for the sweep also in gated_idle_iterations)
+    if (gated) {
         c->ctr.gated_calls += 1;
         c->ctr.gated_idle_iterations += st.idle;
-        c->ctr.band_events += (int64_t)st.band_events;
-        if (c->profiling) {
-            for (size_t i = 0; i < tally_spans.size() && (int)i < st.iter - 1; ++i) { tally_ms += span_ms(tally_spans[i]); ++tally_launches; }
-            for (size_t i = 0; i < resolve_spans.size() && (int)i < st.iter; ++i) { c->tm.resolve_ms += span_ms(resolve_spans[i]); c->tm.resolve_launches++; }
-        }
-        if (dbg_t) {
-            const auto dbg_t2 = std::chrono::steady_clock::now();
-            const double w = std::chrono::duration<double, std::milli>(dbg_t1 - dbg_t0).count();
-            const double l = std::chrono::duration<double, std::milli>(dbg_t2 - dbg_t1).count();
-            fprintf(stderr, "[sw] gated loop: %d sub-batches, %lld events, waited %.3f ms for the first sweep, loop %.3f ms, %lld iterations + %d waiting, %d launched in %d pieces\n",
-                    S, (long long)K, w, l, (long long)(c->ctr.round_iterations - dbg_it0 - st.idle), st.idle, launched, j);
-        }
-        clk.mark(&c->stage_us[2]);
-        for (int i = 0; i < S - 1; ++i) chunk_check(i);   // (every sweep is complete: the loop ended at the last stage)
-        HIPCHK(c, hipEventRecord(c->ev_loop_done, c->stream));
-        return after_loop(S - 1, r_start, fin_from, c->ev_loop_done);
-    };
-    if (gated) CHK(run_gated());
-    for (int i = 0; i < S && !gated; ++i) {
-        const int64_t limit = cut[i + 1];
-        bool row0_dirty = false;
-        const int r_start = start_round(i, &row0_dirty);
-        HIPCHK(c, hipStreamWaitEvent(c->stream, c->cs_events[i], 0));
-        if (row0_dirty) CHK(upload_row0());
-        clk.mark(&c->stage_us[1]);
-        const bool dbg_t = c->debug_timing && K >= 65536;
-        const auto dbg_t0 = std::chrono::steady_clock::now();
-        const int64_t dbg_it0 = c->ctr.round_iterations;
-        if (dbg_t) (void)hipStreamSynchronize(c->stream);  // separates "waiting for the sweep" from the loop itself
-        const auto dbg_t1 = std::chrono::steady_clock::now();
-        // the last sub-batch has no later loop to hide its finalize behind: most of it runs beside the end of its own loop
-        int64_t fin_from = cut[i];
-        const std::function<int(const RState&)> early_fin = [c, np, &fin_from, limit, &pending_aux](const RState& st) -> int {
-            CHK(pending_aux());   // (the previous sub-batch's launches go first: same stream, same order as without the early part)
-            const int64_t upto = std::min<int64_t>(st.mlo, limit);
-            if (st.iter <= 0 || upto < fin_from + 16384) return SW_OK;
-            // events below the band of round st.r: round <= st.r - 1, rows 0 .. st.r of the table are committed and final
-            CHK(ensure_rounds(c, st.r + 2));
-            const int64_t k1 = upto - fin_from;
-            CHK(launch_finalize<NW>(c, c->stream_aux, fin_from, k1, st.r + 1, c->fin_blocks));
-            fin_from = upto;
-            return SW_OK;
-        };
-        const bool split_fin = i == S - 1 && cut[i + 1] - cut[i] >= 65536;
-        CHK(run_round_loop<NW>(c, r_start, limit, cut[i + 1] - cut[i], c->d_bounds.p + (size_t)(i + 1) * np, &tally_ms, &tally_launches, &pending_aux,
-                               split_fin ? &early_fin : nullptr, c->fin_band ? cut[i] : 0x7fffffff));
-        CHK(pending_aux());   // (a loop that returned before its first shot — never — would have left it undone)
-        if (dbg_t) {
-            const auto dbg_t2 = std::chrono::steady_clock::now();
-            const double w = std::chrono::duration<double, std::milli>(dbg_t1 - dbg_t0).count();
-            const double l = std::chrono::duration<double, std::milli>(dbg_t2 - dbg_t1).count();
-            const int64_t its = c->ctr.round_iterations - dbg_it0;
-            fprintf(stderr, "[sw] sub-batch %d: %lld events, waited %.3f ms for the sweep, loop %.3f ms, %lld iterations (%.1f us each)\n",
-                    i, (long long)(cut[i + 1] - cut[i]), w, l, (long long)its, its ? l * 1e3 / (double)its : 0.0);
-        }
-        clk.mark(&c->stage_us[2]);
-        HIPCHK(c, hipEventRecord(c->ev_loop_done, c->stream));
-        CHK(after_loop(i, r_start, fin_from, c->ev_loop_done));
     }
-    CHK(pending_aux());   // the last sub-batch's
-    span_end(c, sp_rl);
+    c->ctr.band_events += (int64_t)st.band_events;
+    if (c->profiling) {
+        float ms = 0.f;
+        int cnt = 0;
+        // only the launches that did work (iterations before `done`)
+        for (size_t i = 0; i < L.tally_spans.size() && (int)i < st.iter - 1; ++i) { ms += span_ms(L.tally_spans[i]); ++cnt; }
+        d.tally_ms += ms;
+        d.tally_launches += cnt;
+        for (size_t i = 0; i < L.resolve_spans.size() && (int)i < st.iter; ++i) { c->tm.resolve_ms += span_ms(L.resolve_spans[i]); c->tm.resolve_launches++; }
+    }
+}
 
-    const int R = c->R;
+// ---- driver: one round loop per sub-batch, over the events visible behind sweep i.  First shot: the predicted number of
+// iterations (predict_shot), then short top-ups until the loop reports done; the host waits for every shot.
+template <int NW>
+int run_round_loop(sw_ctx* c, DivideCall& d, int i) {
+    const int np = c->npad;
+    const int64_t limit = d.cut[i + 1], n_new_events = d.cut[i + 1] - d.cut[i];
+    int r_start = 0;
+    CHK(begin_loop(c, d, i, i, &r_start));
+    const bool dbg_t = c->debug_timing && d.K >= 65536;
+    LoopRun L;
+    L.spans = c->profiling && !c->split;
+    d.fin_from = d.cut[i];
+    loop_start(c, L, dbg_t, r_start, limit, c->d_bounds.p + (size_t)(i + 1) * np, d.cut[i], 0);
+    int shot = predict_shot(c, n_new_events);
+    // SW_MID_PCT (the last sub-batch of a large call has no later loop to hide its finalize behind): the first shot stops
+    // `mid_pct` % of the way, the host looks at the loop state once and finalizes the events below the band of the round in
+    // progress beside the rest of the loop instead of behind it; the rest of the prediction follows
+    int rest = 0;
+    if (i == d.S - 1 && n_new_events >= 65536 && shot >= 64 && c->mid_pct > 0) {
+        const int head = std::max(2, (int)((int64_t)shot * c->mid_pct / 100) & ~1);
+        rest = std::max(2, (shot - head) & ~1);
+        shot = head;
+    }
+    for (;;) {
+        CHK(ensure_rounds(c, c->R + L.launched + shot + 4));
+        CHK(enqueue_shot<NW>(c, L, shot, -1));
+        if (L.launched == shot) CHK(flush_tail<NW>(c, d));   // the previous sub-batch's, behind this one's first shot
+        CHK(take_read_back(c, L, -1));
+        if (L.st.done) break;
+        CHK(check_terminates(c, L, 0));
+        if (rest) {
+            CHK(flush_tail<NW>(c, d));   // (the previous sub-batch's launches go first: same stream, same order as without the early part)
+            CHK(early_finalize<NW>(c, d, L.st, std::min<int64_t>(L.st.mlo, limit), nullptr));
+            shot = rest;
+            rest = 0;
+        } else
+        shot = top_up_shot(L.launched);
+    }
+    account_loop(c, d, L, n_new_events, false);
+    if (dbg_t) {
+        const double l = L.loop_ms();
+        const int64_t its = c->ctr.round_iterations - L.iters_before;
+        fprintf(stderr, "[sw] sub-batch %d: %lld events, waited %.3f ms for the sweep, loop %.3f ms, %lld iterations (%.1f us each)\n",
+                i, (long long)n_new_events, L.waited_ms(), l, (long long)its, its ? l * 1e3 / (double)its : 0.0);
+    }
+    return after_loop(c, d, i, r_start);
+}
+
+// ---- driver: the gated loop (SW_GATED=1): ONE round loop over the whole call.  The sweep stream publishes how many sub-batches it
+// has swept (k_set_stage) and the resolve step latches that one iteration late: no seam between sub-batches (host round
+// trip, read-back, k_loop_init, first-shot logic), no round searched twice, a member at the end of its visible chain waits
+// in its round.  The predicted iterations of the whole call go out in pieces of about one sub-batch, each read back into
+// its own pinned slot: the host waits for the previous piece while the next one runs, and finalizes the events below the
+// band of the round in progress beside the loop; witness rows and voter masks follow the loop, as the last sub-batch's did.
+
+// the piece read back into slot j, with the loop still running behind it: decode, then the early finalize (the aux stream
+// waits for that read-back)
+template <int NW>
+int take_piece(sw_ctx* c, DivideCall& d, LoopRun& L, int j) {
+    CHK(take_read_back(c, L, j));
+    const RState& st = L.st;
+    if (!c->fin_band || st.done) return SW_OK;
+    return early_finalize<NW>(c, d, st, std::min<int64_t>(std::min(st.mlo, st.N), d.first + d.K), c->rb_events[j]);
+}
+
+// the schedule of a gated loop: `total` predicted iterations in P pieces, the host one piece behind the GPU; then top-ups,
+// one read-back each
+template <int NW>
+int gated_schedule(sw_ctx* c, DivideCall& d, LoopRun& L, int total) {
+    const int P = std::min(d.S, SW_PROV_ROWS);
+    const int piece = std::max(2, (total / P) & ~1);
+    int left = total, j = 0;
+    bool taken_last = false;
+    for (; left > 0 && j < P; ++j) {
+        const int n_it = j == P - 1 ? left : std::min(left, piece);
+        CHK(enqueue_shot<NW>(c, L, n_it, j));
+        left -= n_it;
+        if (j > 0) {   // (the GPU has piece j queued behind the one the host waits for)
+            CHK(take_piece<NW>(c, d, L, j - 1));
+            if (L.st.done) { taken_last = true; break; }
+        }
+    }
+    L.pieces = j;
+    if (!taken_last) CHK(take_read_back(c, L, j - 1));
+    while (!L.st.done) {
+        CHK(check_terminates(c, L, total));
+        const int shot = top_up_shot(L.launched);
+        CHK(ensure_rounds(c, c->R + L.launched + shot + 4));
+        CHK(enqueue_shot<NW>(c, L, shot, 0));
+        CHK(take_read_back(c, L, 0));
+    }
+    return SW_OK;
+}
+
+// SW_GATE_LAG (test hook): the stage schedule fixed by the ORDER OF LAUNCHES on the loop stream instead of by the race
+// with the sweep stream.  Pieces of exactly `lag` iterations; behind each the loop stream waits for the sweeps of the
+// next `gate_step` sub-batches and publishes them itself with the same k_set_stage: iteration t loads
+// vis = min(S, 1 + (t / lag) * gate_step).  Nothing on the device waits for `vis`, every publication is enqueued
+// behind a sweep already in the queue, and the iteration bound ends a loop that does not finish.  The pinned
+// slots are reused in turn (the host is one piece behind, as in gated_schedule).
+template <int NW>
+int gated_schedule_lag(sw_ctx* c, DivideCall& d, LoopRun& L, int total) {
+    const int lag = c->gate_lag, S = d.S;
+    int pub = 1;   // (stage 1 is the loop's own start: k_loop_init)
+    for (int j = 0;; ++j) {
+        CHK(check_terminates(c, L, total + (int64_t)lag * S, lag));
+        CHK(ensure_rounds(c, c->R + L.launched + lag + 4));
+        CHK(enqueue_shot<NW>(c, L, lag, j % SW_PROV_ROWS));
+        if (pub < S) {
+            const int v = std::min(S, pub + c->gate_step);
+            for (int i = pub; i < v; ++i) HIPCHK(c, hipStreamWaitEvent(c->stream, c->cs_events[i], 0));
+            hipLaunchKernelGGL(k_set_stage, dim3(1), dim3(64), 0, c->stream, loop_gate(c), v);
+            c->ctr.kernel_launches++;
+            pub = v;
+        }
+        if (j > 0) {
+            CHK(take_piece<NW>(c, d, L, (j - 1) % SW_PROV_ROWS));
+            L.pieces = j;
+            if (L.st.done) return SW_OK;
+        }
+    }
+}
+
+template <int NW>
+int run_gated(sw_ctx* c, DivideCall& d) {
+    const int np = c->npad, S = d.S;
+    int r_start = 0;
+    CHK(begin_loop(c, d, S - 1, 0, &r_start));   // (clen_prev is row 0: every member the call adds events to; the loop starts behind the first sweep)
+    LoopRun L;
+    L.spans = c->profiling;
+    d.fin_from = d.first;
+    loop_start(c, L, c->debug_timing, r_start, d.cut[1], c->d_bounds.p + np, d.first, S);
+    const int total = predict_shot(c, d.K, true);
+    CHK(ensure_rounds(c, c->R + total + 8));
+    if (c->gate_lag > 0) CHK(gated_schedule_lag<NW>(c, d, L, total));
+    else CHK(gated_schedule<NW>(c, d, L, total));
+    account_loop(c, d, L, d.K, true);
+    if (c->debug_timing) {
+        fprintf(stderr, "[sw] gated loop: %d sub-batches, %lld events, waited %.3f ms for the first sweep, loop %.3f ms, %lld iterations + %d waiting, %d launched in %d pieces\n",
+                S, (long long)d.K, L.waited_ms(), L.loop_ms(), (long long)(c->ctr.round_iterations - L.iters_before - L.st.idle), L.st.idle, L.launched, L.pieces);
+    }
+    return after_loop(c, d, S - 1, r_start);   // one tail for the whole call
+}
+
+// ---- phase: the three streams join, the books of the call
+int finish_call(sw_ctx* c, DivideCall& d) {
+    const int np = c->npad, S = d.S, R = c->R;
+    const int64_t first = d.first, K = d.K;
     hipEvent_t fin_t1 = nullptr;
     if (c->profiling) { fin_t1 = next_event(c); (void)hipEventRecord(fin_t1, c->stream_aux); }
     // Everything later calls enqueue goes to the main stream (getters, decide_fame, find_order): it
@@ -1811,15 +1884,15 @@ int do_divide(sw_ctx* c, int64_t first, int64_t K) {
     HIPCHK(c, hipEventRecord(c->ev_cs_done, c->stream_cs));
     HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_aux_done, 0));
     HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_cs_done, 0));
-    span_end(c, sp_total);
+    span_end(c, d.sp_total);
     if (c->profiling || c->debug_timing) {
         HIPCHK(c, hipStreamSynchronize(c->stream_aux));
         HIPCHK(c, hipStreamSynchronize(c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream_cs));
     }
     HIPCHK(c, hipGetLastError());
-    std::copy(bounds_h.begin() + (size_t)S * np, bounds_h.begin() + (size_t)(S + 1) * np, c->divided_cnt.begin());
-    clk.mark(&c->stage_us[5]);
+    std::copy(c->bounds_stage.begin() + (size_t)S * np, c->bounds_stage.begin() + (size_t)(S + 1) * np, c->divided_cnt.begin());
+    d.clk.mark(&c->stage_us[5]);
     c->sw_dirty_from = std::max(R, 1);  // voter masks are up to date
     if (first + K == c->N) std::copy(c->head.begin(), c->head.end(), c->divided_head.begin());
     else for (int64_t e = first; e < first + K; ++e) c->divided_head[c->cr[e]] = (int32_t)e;
@@ -1828,18 +1901,49 @@ int do_divide(sw_ctx* c, int64_t first, int64_t K) {
     c->ctr.rounds = R;
     if (c->profiling) {
         float ms = 0.f;
-        if (cs_t0 && cs_t1) (void)hipEventElapsedTime(&ms, cs_t0, cs_t1);
+        if (d.cs_t0 && d.cs_t1) (void)hipEventElapsedTime(&ms, d.cs_t0, d.cs_t1);
         c->tm.can_see_ms = ms;   // on its own stream: overlaps rounds_ms
-        c->tm.rounds_ms = span_ms(sp_rl);
-        c->tm.tally_ms = tally_ms;
-        c->tm.tally_launches = tally_launches;
-        { float fm = 0.f; if (fin_t0 && fin_t1) (void)hipEventElapsedTime(&fm, fin_t0, fin_t1); c->tm.finalize_ms = fm; }  // aux stream span (overlaps)
-        c->tm.total_ms = span_ms(sp_total);
+        c->tm.rounds_ms = span_ms(d.sp_rl);
+        c->tm.tally_ms = d.tally_ms;
+        c->tm.tally_launches = d.tally_launches;
+        { float fm = 0.f; if (d.fin_t0 && fin_t1) (void)hipEventElapsedTime(&fm, d.fin_t0, fin_t1); c->tm.finalize_ms = fm; }  // aux stream span (overlaps)
+        c->tm.total_ms = span_ms(d.sp_total);
         c->tm.cansee_kernel_ms = 0.f;
-        c->tm.cansee_launches = (int32_t)cansee_spans.size();
-        for (const Span& s_ : cansee_spans) c->tm.cansee_kernel_ms += span_ms(s_);
+        c->tm.cansee_launches = (int32_t)d.cansee_spans.size();
+        for (const Span& s_ : d.cansee_spans) c->tm.cansee_kernel_ms += span_ms(s_);
     }
     return SW_OK;
+}
+
+template <int NW>
+int do_divide(sw_ctx* c, int64_t first, int64_t K) {
+    const int np = c->npad;
+    c->ev_used = 0;
+    DivideCall d(c, first, K);
+    c->stage_calls += 1;
+    d.sp_total = span_begin(c);
+    plan_cuts(c, d);
+    choose_tally(c, d);
+    CHK(test_preswept(c, d));
+    CHK(size_level_tables(c, d));
+    // ---- sweep stream: every can_see sweep of the call, behind the tables it reads
+    CHK(open_sweep_stream(c, d));
+    CHK(build_bounds(c, d));
+    CHK(plan_chunks(c, d));
+    CHK(enqueue_sweeps<NW>(c, d));
+    d.clk.mark(&c->stage_us[0]);
+
+    // ---- main stream: the round loops, each over the events visible so far; aux stream: the tails behind them
+    if (d.bounds_pending) HIPCHK(c, hipEventSynchronize(c->ev_bounds));
+    CHK(ensure_rounds(c, std::max(c->R, 1) + c->BATCH + 4));
+    d.sp_rl = span_begin(c);
+    d.clen_prev.assign(c->bounds_stage.begin(), c->bounds_stage.begin() + np);
+    d.clen.assign(np, 0);
+    if (d.gated) CHK(run_gated<NW>(c, d));
+    else for (int i = 0; i < d.S; ++i) CHK(run_round_loop<NW>(c, d, i));
+    CHK(flush_tail<NW>(c, d));   // the last sub-batch's
+    span_end(c, d.sp_rl);
+    return finish_call(c, d);
 }
 
 // first round not in `consensus` (swirld.py:226-228)
@@ -2571,11 +2675,9 @@ int sw_create(int n_members, const uint64_t* stake, int coin_period, int device,
         CHIP(hipHostMalloc((void**)&c->h_rb_all, c->rb_bytes * SW_PROV_ROWS, hipHostMallocDefault));
         c->h_rb = c->h_rb_all;
         for (int i = 0; i < SW_PROV_ROWS; ++i) {
-            hipEvent_t e1, e2;
+            hipEvent_t e1;
             CHIP(hipEventCreateWithFlags(&e1, hipEventDisableTiming));
             c->rb_events.push_back(e1);
-            CHIP(hipEventCreateWithFlags(&e2, hipEventDisableTiming));
-            c->shot_events.push_back(e2);
         }
         c->d_state = reinterpret_cast<RState*>(c->d_rb);
         c->d_flow_err = reinterpret_cast<int*>(c->d_rb + 2 * sizeof(RState));
@@ -2669,7 +2771,6 @@ int sw_destroy(sw_ctx* c) {
     if (c->d_rb) (void)hipFree(c->d_rb);
     if (c->h_rb_all) (void)hipHostFree(c->h_rb_all);
     for (hipEvent_t e : c->rb_events) (void)hipEventDestroy(e);
-    for (hipEvent_t e : c->shot_events) (void)hipEventDestroy(e);
     if (c->h_fame) (void)hipHostFree(c->h_fame);
     if (c->d_err) (void)hipFree(c->d_err);
     dfree(c->d_ord_rounds); dfree(c->d_fwm); dfree(c->d_ordat); dfree(c->d_rowsum); dfree(c->d_grp); dfree(c->d_oblk);

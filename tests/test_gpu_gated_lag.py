@@ -136,7 +136,7 @@ def oracles(request, pkg):
 
 
 def cut_plan(K, env, pipe=5):
-    """The event limits of the sub-batches of a divide_rounds call over events [0, K) — do_divide's plan: SW_CUTS fractions,
+    """The event limits of the sub-batches of a divide_rounds call over events [0, K) — plan_cuts' plan (csrc/swirld_hip.hip): SW_CUTS fractions,
     else a head of K / 16 and five graduated parts, every boundary rounded down to a multiple of 4096."""
     cut = [0]
     if "SW_CUTS" in env and K >= 65536:
