@@ -80,6 +80,45 @@ int sw_append_events(sw_ctx* ctx, int64_t K, const int32_t* creator, const int32
 int64_t sw_num_events(const sw_ctx* ctx);
 
 /*
+ * sw_append_events for K events that are ALREADY IN DEVICE MEMORY (batched signature checks, a torch pipeline, a
+ * generator kernel, a peer's events arriving by RCCL): same meaning, same state afterwards — every getter and every
+ * later call behaves as if the same arrays had gone through sw_append_events.  All arrays lie in memory of the
+ * context's device (`d_t`, `d_sig64` may be NULL: zeros are stored); a host pointer, or memory of another device, is
+ * SW_EINVAL before anything is launched.  `user_stream` is a hipStream_t or NULL (the null stream), as for
+ * sw_import_rows: the context's stream waits, on the device, for what has been enqueued there so far.  On return the
+ * caller may reuse or free the arrays.
+ *
+ * The device path (ingest.hip.h) validates the batch, ranks every event in its creator's chain, builds the per-member
+ * tables and the chain pool and computes the heights (swirld.py:117-120) on the device; it reads back one verdict
+ * word, the per-member tables and 8 B per event (creator, chain position).  The heights kernel runs behind the call;
+ * whoever needs heights waits for it, and the full host mirror of parents and heights is downloaded only for
+ * sw_get_height, the gossip getters, a later small append or the exact path.
+ *
+ * Atomic on rejection like sw_append_events (nothing stored, context usable), with the same code for the same
+ * defect: SW_EINVAL for creator out of range, one parent only, a parent index not earlier than the event (indices at
+ * or beyond the end of the batch included), self-parent by another member, other-parent by the same member;
+ * sw_last_error names the event.  With several defects in one batch the device path reports the LOWEST offending
+ * event, and for it the first failing check in the order just given.  (The bulk host path differs there: its host
+ * loop runs before its other-parent kernel, so any defect of the loop — or a fork — wins over an other-parent defect
+ * whatever the index.)
+ *
+ * What falls back: the batch is copied to the host and handed to sw_append_events when the context is on the exact
+ * path, the table is windowed (sw_set_window), the batch is not bulk-sized (bulk: K >= 8192, or the first append, or
+ * 8 K >= events stored — small appends keep the host mirrors incremental), or the device validation finds a FORK
+ * (self-parent by the same creator but not its latest event, or a second root).  In the fork case nothing has been
+ * committed, so the host path decides as ever: exact path with sw_set_forks(ctx, 1), SW_ENOTSUP and nothing stored
+ * with sw_set_forks(ctx, 0).
+ *
+ * sw_get_ingest_stats: batches / events the device path committed, batches that fell back (rejected pointer checks do
+ * not count), and the events whose height the sequential host loop computed (0 for device-appended events) — since
+ * sw_create.  Any pointer may be NULL.
+ */
+int sw_append_events_device(sw_ctx* ctx, int64_t K, const int32_t* d_creator, const int32_t* d_self_parent,
+                            const int32_t* d_other_parent, const double* d_t, const uint8_t* d_sig64, void* user_stream);
+int sw_get_ingest_stats(sw_ctx* ctx, int64_t* device_batches, int64_t* device_events, int64_t* fallback_batches,
+                        int64_t* host_height_events);
+
+/*
  * Node.divide_rounds(events) (swirld.py:187-222) for the K events [first, first+K):
  * fills can_see rows, round numbers and the witness table.  `first` must equal the
  * number of events already divided (the reference processes every new event exactly

@@ -23,6 +23,7 @@
 #define SW_RANGE_SLOTS 16 // event ranges swept by sw_cansee_range between two rewinds
 #include "crypto.hip.h"
 #include "exact.hip.h"
+#include "ingest.hip.h"
 
 namespace {
 
@@ -145,6 +146,16 @@ struct sw_ctx {
     size_t h_pin_cap = 0;
     int max_height = 0;
     int64_t N = 0, cap = 0, divided = 0;
+    // device-side ingest (sw_append_events_device; ingest.hip.h)
+    DBuf<int32_t> d_ing_tab;      // [4 + 3 npad]: verdict word (64 bits), pad; then [nev | head | first] of the members
+    DBuf<int32_t> d_ing_hist;     // [tiles][npad] creators per tile, then chain position of each member at the head of each tile
+    DBuf<int32_t> d_ht_stat;      // k_ingest_heights: [error, largest height, {min, max} per 4096-event block of the batch]
+    std::vector<int32_t> ing_stage;   // host staging of d_ing_tab (persistent: uploaded and read back without a copy of a local)
+    hipEvent_t ev_ht = nullptr;   // the heights kernel of the last device append (it runs on stream_io, behind the call)
+    bool ht_pending = false;      // ... has not been waited for yet: d_ht, max_height, blk_hmin / blk_hmax lack its events
+    int64_t ht_first = 0, ht_K = 0;   // ... which are these
+    int64_t ht_dev_upto = 0;      // events below this index and beyond the host mirror (sp.size()) have their height in d_ht
+    int64_t st_dev_batches = 0, st_dev_events = 0, st_fallback = 0, st_host_ht = 0;   // sw_get_ingest_stats
 
     // device: events
     DBuf<int32_t> d_cr, d_sp, d_op, d_ht, d_seq, d_round, d_L, d_chain_ev;
@@ -509,8 +520,11 @@ int vm_map_scratch(sw_ctx* c) {
     return SW_OK;
 }
 
+int heights_ready(sw_ctx* c);
+
 int ensure_events(sw_ctx* c, int64_t need) {
     if (need <= c->cap) return SW_OK;
+    CHK(heights_ready(c));   // (the event arrays move: a device append's heights kernel may still be writing d_ht)
     int64_t nc = c->cap ? c->cap : 0;
     if (nc == 0) nc = need;
     while (nc < need) nc = nc + nc / 2 + 1024;
@@ -652,17 +666,48 @@ int rebuild_chains(sw_ctx* c, const std::vector<int32_t>& cnt, int64_t n_events)
 // ---- lazily fetched host mirrors: the device arrays are the source of truth -------------------
 // self / other parents and heights (swirld.py:117-120) of all events: needed by sw_get_height and
 // by the level-bucketed can_see kernels only
+// The heights kernel of a device append runs behind the call (stream_io).  Whoever reads d_ht, max_height or the
+// block spans, or moves the event arrays, waits for it here and folds its read-back into the host tables.
+int heights_ready(sw_ctx* c) {
+    if (!c->ht_pending) return SW_OK;
+    c->ht_pending = false;
+    const int64_t blk0 = c->ht_first >> 12, nblk = ((c->ht_first + c->ht_K - 1) >> 12) - blk0 + 1;
+    std::vector<int32_t> st((size_t)(2 + 2 * nblk));
+    hipError_t e_ = hipEventSynchronize(c->ev_ht);
+    if (e_ == hipSuccess) e_ = hipMemcpy(st.data(), c->d_ht_stat.p, st.size() * sizeof(int32_t), hipMemcpyDeviceToHost);
+    if (e_ != hipSuccess) { c->poisoned = true; return fail(c, SW_EIO, "heights of a device append: %s", hipGetErrorString(e_)); }
+    if (st[0] != 0) {
+        c->poisoned = true;
+        return fail(c, SW_EIO, "heights of a device append: a tile did not settle within its trip bound (internal)");
+    }
+    c->max_height = std::max(c->max_height, st[1]);
+    c->blk_hmin.resize((size_t)(blk0 + nblk), 0x7fffffff);
+    c->blk_hmax.resize((size_t)(blk0 + nblk), -1);
+    for (int64_t b = 0; b < nblk; ++b) {
+        c->blk_hmin[blk0 + b] = std::min(c->blk_hmin[blk0 + b], st[2 + 2 * b]);
+        c->blk_hmax[blk0 + b] = std::max(c->blk_hmax[blk0 + b], st[3 + 2 * b]);
+    }
+    return SW_OK;
+}
+
 int ensure_dag_h(sw_ctx* c) {
+    CHK(heights_ready(c));
     const int64_t have = (int64_t)c->sp.size();
     if (have >= c->N) return SW_OK;
     const int64_t K = c->N - have;
+    // events [have, dev) were appended from device memory: their heights are in d_ht already and are downloaded;
+    // those behind came through a bulk host append, and the host loop below computes theirs
+    const int64_t dev = std::min(std::max(c->ht_dev_upto, have), c->N);
     c->sp.resize(c->N); c->op.resize(c->N); c->ht.resize(c->N);
     HIPCHK(c, hipMemcpyAsync(c->sp.data() + have, c->d_sp.p + have, (size_t)K * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(c->op.data() + have, c->d_op.p + have, (size_t)K * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    if (dev > have) HIPCHK(c, hipMemcpyAsync(c->ht.data() + have, c->d_ht.p + have, (size_t)(dev - have) * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->blk_hmin.resize((size_t)((c->N + 4095) >> 12), 0x7fffffff);
     c->blk_hmax.resize((size_t)((c->N + 4095) >> 12), -1);
-    for (int64_t e = have; e < c->N; ++e) {
+    if (dev >= c->N) return SW_OK;
+    c->st_host_ht += c->N - dev;
+    for (int64_t e = dev; e < c->N; ++e) {
         const int32_t s_ = c->sp[e], o_ = c->op[e];
         const int32_t h = s_ < 0 ? 0 : std::max(c->ht[s_], c->ht[o_]) + 1;  // swirld.py:117-120
         c->ht[e] = h;
@@ -670,7 +715,7 @@ int ensure_dag_h(sw_ctx* c) {
         c->blk_hmin[e >> 12] = std::min(c->blk_hmin[e >> 12], h);
         c->blk_hmax[e >> 12] = std::max(c->blk_hmax[e >> 12], h);
     }
-    HIPCHK(c, hipMemcpyAsync(c->d_ht.p + have, c->ht.data() + have, (size_t)K * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->d_ht.p + dev, c->ht.data() + dev, (size_t)(c->N - dev) * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return SW_OK;
 }
@@ -1182,23 +1227,56 @@ int launch_voter_masks(sw_ctx* c, int r0, int R, hipStream_t strm) {
     return SW_OK;
 }
 
+// Heights of the 4096-event blocks that hold a cut, for events the host mirror lacks (heights_for_spans).
+struct EdgeHeights {
+    std::vector<int64_t> start;               // first event of each fetched piece
+    std::vector<std::vector<int32_t>> h;
+    int32_t at(int64_t e) const {
+        for (size_t i = 0; i < start.size(); ++i)
+            if (e >= start[i] && e < start[i] + (int64_t)h[i].size()) return h[i][(size_t)(e - start[i])];
+        return 0;   // (not reached: every partial block beyond the mirror has been fetched)
+    }
+};
+
 // height span of the events [a, b): from the ingest-time block index, edges by scanning
-void height_span(const sw_ctx* c, int64_t a, int64_t b, int* hmin, int* hmax) {
+void height_span(const sw_ctx* c, int64_t a, int64_t b, int* hmin, int* hmax, const EdgeHeights& edge) {
     int lo = 0x7fffffff, hi = -1;
     int64_t e = a;
+    const int64_t have = (int64_t)c->ht.size();
     while (e < b) {
         if ((e & 4095) == 0 && e + 4096 <= b) {
             lo = std::min(lo, c->blk_hmin[e >> 12]);
             hi = std::max(hi, c->blk_hmax[e >> 12]);
             e += 4096;
         } else {
-            lo = std::min(lo, c->ht[e]);
-            hi = std::max(hi, c->ht[e]);
+            const int32_t h = e < have ? c->ht[e] : edge.at(e);
+            lo = std::min(lo, h);
+            hi = std::max(hi, h);
             ++e;
         }
     }
     *hmin = lo;
     *hmax = hi;
+}
+
+// What the level sweep's sizing reads on the host.  Events appended from device memory have their heights in d_ht and
+// their block spans in blk_hmin / blk_hmax without the full host mirror: when every event beyond the mirror is such an
+// event, only the blocks that hold a cut are fetched; otherwise the mirror is completed (ensure_dag_h).
+int heights_for_spans(sw_ctx* c, const std::vector<int64_t>& cut, EdgeHeights& edge) {
+    CHK(heights_ready(c));
+    const int64_t have = (int64_t)c->sp.size();
+    if (have >= c->N) return SW_OK;
+    if (c->ht_dev_upto < c->N) return ensure_dag_h(c);
+    for (size_t i = 0; i < cut.size(); ++i) {
+        const int64_t x = cut[i];
+        const int64_t a = std::max<int64_t>(x & ~(int64_t)4095, have), b = std::min<int64_t>((x | (int64_t)4095) + 1, c->N);
+        if ((x & 4095) == 0 || b <= a) continue;
+        edge.start.push_back(a);
+        edge.h.emplace_back((size_t)(b - a));
+        HIPCHK(c, hipMemcpyAsync(edge.h.back().data(), c->d_ht.p + a, (size_t)(b - a) * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return SW_OK;
 }
 
 // host-side stage clock of sw_divide_rounds (SW_DEBUG_TIMING=1: averages printed by sw_destroy)
@@ -1329,10 +1407,11 @@ int size_level_tables(sw_ctx* c, DivideCall& d) {
     if (d.flow || d.preswept) return SW_OK;
     int max_nlev = 1;
     int64_t max_k = 1;
-    CHK(ensure_dag_h(c));  // the level-bucketed kernels need the heights (swirld.py:117-120)
+    EdgeHeights edge;
+    CHK(heights_for_spans(c, d.cut, edge));  // the level-bucketed kernels need the heights (swirld.py:117-120)
     for (int i = 0; i < d.S; ++i) {
         int hmax;
-        height_span(c, d.cut[i], d.cut[i + 1], &d.hmins[i], &hmax);
+        height_span(c, d.cut[i], d.cut[i + 1], &d.hmins[i], &hmax, edge);
         d.nlevs[i] = hmax - d.hmins[i] + 1;
         max_nlev = std::max(max_nlev, d.nlevs[i]);
         max_k = std::max(max_k, d.cut[i + 1] - d.cut[i]);
@@ -2796,6 +2875,8 @@ int sw_destroy(sw_ctx* c) {
     for (auto e : c->cs_events) (void)hipEventDestroy(e);
     if (c->stream_io) { (void)hipStreamSynchronize(c->stream_io); (void)hipStreamDestroy(c->stream_io); }
     if (c->ev_payload) (void)hipEventDestroy(c->ev_payload);
+    if (c->ev_ht) (void)hipEventDestroy(c->ev_ht);
+    dfree(c->d_ing_tab); dfree(c->d_ing_hist); dfree(c->d_ht_stat);
     if (c->ev_aux_done) (void)hipEventDestroy(c->ev_aux_done);
     if (c->ev_cs_done) (void)hipEventDestroy(c->ev_cs_done);
     if (c->ev_main_mark) (void)hipEventDestroy(c->ev_main_mark);
@@ -3186,6 +3267,7 @@ int sw_append_events(sw_ctx* c, int64_t K, const int32_t* creator, const int32_t
     if (K < 0 || (K > 0 && (!creator || !self_parent || !other_parent))) return fail(c, SW_EINVAL, "NULL event arrays");
     if (K == 0) return SW_OK;
     if (c->N + K > 0x7ffffff0ll) return fail(c, SW_ERANGE, "more than 2^31 events");
+    CHK(heights_ready(c));   // (a device append's heights kernel may still run: the event arrays may move below)
     if (c->exact) return append_exact(c, K, creator, self_parent, other_parent, t, sig64);
     const int64_t N0 = c->N;
     const int n = c->n;
@@ -3322,6 +3404,187 @@ int sw_append_events(sw_ctx* c, int64_t K, const int32_t* creator, const int32_t
     PHIP(hipStreamSynchronize(c->stream));  // caller buffers may be released on return (bulk payload: staged copy)
 #undef PCHK
 #undef PHIP
+    return SW_OK;
+}
+
+// ---- sw_append_events_device: the same K events from device memory ------------------------------------------------
+namespace {
+
+// device memory of the context's device?  (For plain host memory the query itself fails on ROCm: that is the answer,
+// and the error is cleared so that it does not surface in a later check.)
+bool on_ctx_device(const sw_ctx* c, const void* p, size_t bytes) {
+    const char* ends[2] = {(const char*)p, (const char*)p + (bytes ? bytes - 1 : 0)};
+    for (const char* q : ends) {
+        hipPointerAttribute_t at;
+        if (hipPointerGetAttributes(&at, q) != hipSuccess) { (void)hipGetLastError(); return false; }
+        if (at.type != hipMemoryTypeDevice || at.device != c->device) return false;
+    }
+    return true;
+}
+
+// Everything outside the bulk fork-free fast path: the batch goes to the host and through sw_append_events.
+int ingest_fallback(sw_ctx* c, int64_t K, const int32_t* d_creator, const int32_t* d_self_parent, const int32_t* d_other_parent,
+                    const double* d_t, const uint8_t* d_sig64, hipStream_t us) {
+    c->st_fallback++;
+    std::vector<int32_t> cr((size_t)K), sp((size_t)K), op((size_t)K);
+    std::vector<double> t(d_t ? (size_t)K : 0);
+    std::vector<uint8_t> sig(d_sig64 ? (size_t)K * 64 : 0);
+    const size_t b4 = (size_t)K * sizeof(int32_t);
+    HIPCHK(c, hipMemcpyAsync(cr.data(), d_creator, b4, hipMemcpyDeviceToHost, us));
+    HIPCHK(c, hipMemcpyAsync(sp.data(), d_self_parent, b4, hipMemcpyDeviceToHost, us));
+    HIPCHK(c, hipMemcpyAsync(op.data(), d_other_parent, b4, hipMemcpyDeviceToHost, us));
+    if (d_t) HIPCHK(c, hipMemcpyAsync(t.data(), d_t, (size_t)K * 8, hipMemcpyDeviceToHost, us));
+    if (d_sig64) HIPCHK(c, hipMemcpyAsync(sig.data(), d_sig64, (size_t)K * 64, hipMemcpyDeviceToHost, us));
+    HIPCHK(c, hipStreamSynchronize(us));
+    return sw_append_events(c, K, cr.data(), sp.data(), op.data(), d_t ? t.data() : nullptr, d_sig64 ? sig.data() : nullptr);
+}
+
+}  // namespace
+
+int sw_append_events_device(sw_ctx* c, int64_t K, const int32_t* d_creator, const int32_t* d_self_parent,
+                            const int32_t* d_other_parent, const double* d_t, const uint8_t* d_sig64, void* user_stream) {
+    if (!c) return SW_EINVAL;
+    if (c->poisoned) return fail(c, SW_EIO, "context unusable after an earlier device failure");
+    if (K < 0 || (K > 0 && (!d_creator || !d_self_parent || !d_other_parent))) return fail(c, SW_EINVAL, "NULL event arrays");
+    if (K == 0) return SW_OK;
+    if (c->N + K > 0x7ffffff0ll) return fail(c, SW_ERANGE, "more than 2^31 events");
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t b4 = (size_t)K * sizeof(int32_t);
+    if (!on_ctx_device(c, d_creator, b4) || !on_ctx_device(c, d_self_parent, b4) || !on_ctx_device(c, d_other_parent, b4) ||
+        (d_t && !on_ctx_device(c, d_t, (size_t)K * 8)) || (d_sig64 && !on_ctx_device(c, d_sig64, (size_t)K * 64)))
+        return fail(c, SW_EINVAL, "sw_append_events_device: every array must lie in memory of device %d (a host pointer, or another device's)", c->device);
+    hipStream_t us = (hipStream_t)user_stream;
+    const int64_t N0 = c->N;
+    const int n = c->n, np = c->npad;
+    const bool bulk = K >= 8192 || c->chain_cap.empty() || K * 8 >= N0;   // (sw_append_events' predicate)
+    if (c->exact || c->vm.active || !bulk || np > ing::MAX_KEYS)
+        return ingest_fallback(c, K, d_creator, d_self_parent, d_other_parent, d_t, d_sig64, us);
+    // heights of the events so far must be on the device (a bulk HOST append leaves them to ensure_dag_h)
+    CHK(heights_ready(c));
+    if ((int64_t)c->sp.size() < N0 && c->ht_dev_upto < N0) CHK(ensure_dag_h(c));
+    // ---- allocations (nothing committed)
+    CHK(ensure_events(c, N0 + K));
+    const int tiles = (int)((K + ing::TILE - 1) / ing::TILE);
+    const int64_t blk0 = N0 >> 12, nblk = ((N0 + K - 1) >> 12) - blk0 + 1;
+    CHK(dgrow(c, c->d_ing_tab, (size_t)4 + 3 * np, 0));
+    CHK(dgrow(c, c->d_ing_hist, (size_t)tiles * np, 0));
+    CHK(dgrow(c, c->d_ht_stat, (size_t)(2 + 2 * nblk), 0));
+    // (the pinned staging buffer may still feed the payload upload of an earlier bulk host append)
+    if (c->payload_pending) { HIPCHK(c, hipEventSynchronize(c->ev_payload)); c->payload_pending = false; }
+    if ((size_t)K * 8 > c->h_pin_cap) {
+        if (c->h_pin) (void)hipHostFree(c->h_pin);
+        c->h_pin = nullptr; c->h_pin_cap = 0;
+        if (hipHostMalloc((void**)&c->h_pin, (size_t)K * 8, hipHostMallocDefault) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(c, SW_ENOMEM, "hipHostMalloc(%zu bytes) for the ingest read-back buffer failed", (size_t)K * 8);
+        }
+        c->h_pin_cap = (size_t)K * 8;
+    }
+    if (!c->ev_user) HIPCHK(c, hipEventCreateWithFlags(&c->ev_user, hipEventDisableTiming));
+    if (!c->ev_ht) HIPCHK(c, hipEventCreateWithFlags(&c->ev_ht, hipEventDisableTiming));
+    // ---- the context's stream waits for what the caller enqueued; parent arrays to the (uncommitted) tail
+    HIPCHK(c, hipEventRecord(c->ev_user, us));
+    HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_user, 0));
+    HIPCHK(c, hipMemcpyAsync(c->d_cr.p + N0, d_creator, b4, hipMemcpyDeviceToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->d_sp.p + N0, d_self_parent, b4, hipMemcpyDeviceToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->d_op.p + N0, d_other_parent, b4, hipMemcpyDeviceToDevice, c->stream));
+    // ---- verdict word and per-member tables [nev | head | first]
+    std::vector<int32_t>& tab = c->ing_stage;
+    tab.assign((size_t)4 + 3 * np, 0);
+    const unsigned long long none = ing::V_NONE;
+    memcpy(tab.data(), &none, sizeof none);
+    for (int m = 0; m < np; ++m) {
+        tab[4 + m] = m < n ? c->nev[m] : 0;
+        tab[4 + np + m] = m < n ? c->head[m] : -1;
+        tab[4 + 2 * np + m] = (m < n && c->first_ev[m] >= 0) ? c->first_ev[m] : 0x7fffffff;
+    }
+    HIPCHK(c, hipMemcpyAsync(c->d_ing_tab.p, tab.data(), tab.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    unsigned long long* d_v = (unsigned long long*)c->d_ing_tab.p;
+    int* d_tab = c->d_ing_tab.p + 4;
+    int nbits = 0;
+    while ((1 << nbits) < np) ++nbits;
+    const dim3 ev_grid((unsigned)((K + 255) / 256));
+    hipLaunchKernelGGL(ing::k_ingest_local, ev_grid, dim3(256), 0, c->stream, c->d_cr.p, (const int*)c->d_sp.p, (const int*)c->d_op.p,
+                       (int)N0, (int)K, n, d_v);
+    hipLaunchKernelGGL(ing::k_ingest_hist, dim3(tiles), dim3(ing::THREADS), 0, c->stream, (const int*)c->d_cr.p, (int)N0, (int)K, np,
+                       c->d_ing_hist.p, d_tab);
+    hipLaunchKernelGGL(ing::k_ingest_scan, dim3((np + 63) / 64), dim3(64), 0, c->stream, c->d_ing_hist.p, tiles, np, d_tab);
+    hipLaunchKernelGGL(ing::k_ingest_rank, dim3(tiles), dim3(ing::THREADS), 0, c->stream, (const int*)c->d_cr.p, (int)N0, (int)K, np, nbits,
+                       (const int*)c->d_ing_hist.p, c->d_seq.p);
+    hipLaunchKernelGGL(ing::k_ingest_links, ev_grid, dim3(256), 0, c->stream, (const int*)c->d_cr.p, (const int*)c->d_sp.p,
+                       (const int*)c->d_op.p, (const int*)c->d_seq.p, (int)N0, (int)K, d_v);
+    c->ctr.kernel_launches += 5;
+    HIPCHK(c, hipGetLastError());
+    // ---- one read-back: verdict and tables; the always-complete host mirrors (creator, chain position) ride along
+    int32_t* pin_cr = (int32_t*)c->h_pin;
+    int32_t* pin_seq = pin_cr + K;
+    HIPCHK(c, hipMemcpyAsync(tab.data(), c->d_ing_tab.p, tab.size() * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(pin_cr, c->d_cr.p + N0, b4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(pin_seq, c->d_seq.p + N0, b4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    unsigned long long v;
+    memcpy(&v, tab.data(), sizeof v);
+    if (v != ing::V_NONE) {
+        const long long e = (long long)(v >> 8);
+        switch ((int)(v & 0xff)) {
+            case ing::V_CREATOR: return fail(c, SW_EINVAL, "event %lld: creator out of range", e);
+            case ing::V_ARITY: return fail(c, SW_EINVAL, "event %lld: must have 0 or 2 parents", e);
+            case ing::V_ORDER: return fail(c, SW_EINVAL, "event %lld: parent index not earlier (not a topological order)", e);
+            case ing::V_SELF: return fail(c, SW_EINVAL, "event %lld: self-parent is by another member", e);
+            case ing::V_OTHER: return fail(c, SW_EINVAL, "event %lld: other-parent is by the same member", e);
+            default:   // a fork: nothing is committed, the host path decides (exact path, or SW_ENOTSUP)
+                return ingest_fallback(c, K, d_creator, d_self_parent, d_other_parent, d_t, d_sig64, us);
+        }
+    }
+    // ---- commit.  From here on a device failure leaves the context inconsistent: it is poisoned.
+#define PCHK(expr) do { int rc_ = (expr); if (rc_ != SW_OK) { c->poisoned = true; return rc_; } } while (0)
+#define PHIP(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { c->poisoned = true; \
+        return fail(c, SW_EIO, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); } } while (0)
+    c->cr.insert(c->cr.end(), pin_cr, pin_cr + K);
+    c->seq_h.insert(c->seq_h.end(), pin_seq, pin_seq + K);
+    std::vector<int32_t> nev_t(c->nev);
+    for (int m = 0; m < n; ++m) {
+        nev_t[m] = tab[4 + m];
+        c->head[m] = tab[4 + np + m];
+        c->first_ev[m] = tab[4 + 2 * np + m] == 0x7fffffff ? -1 : tab[4 + 2 * np + m];
+    }
+    c->N = N0 + K;
+    // payload: device to device on the context's stream (done when the call returns)
+    if (d_t) PHIP(hipMemcpyAsync(c->d_t.p + N0, d_t, (size_t)K * 8, hipMemcpyDeviceToDevice, c->stream));
+    else PHIP(hipMemsetAsync(c->d_t.p + N0, 0, (size_t)K * 8, c->stream));
+    if (d_sig64) PHIP(hipMemcpyAsync(c->d_sig.p + (size_t)N0 * 64, d_sig64, (size_t)K * 64, hipMemcpyDeviceToDevice, c->stream));
+    else PHIP(hipMemsetAsync(c->d_sig.p + (size_t)N0 * 64, 0, (size_t)K * 64, c->stream));
+    hipLaunchKernelGGL(k_coin_bits, ev_grid, dim3(256), 0, c->stream, (const unsigned char*)c->d_sig.p, (int)N0, (int)K, c->d_coin.p);
+    c->ctr.kernel_launches++;
+    PHIP(hipMemsetAsync(c->d_round.p + N0, 0xff, b4, c->stream));
+    // heights: behind the call, on the payload stream (the parent arrays are in place: the stream was drained above)
+    std::vector<int32_t> st0((size_t)(2 + 2 * nblk));
+    st0[0] = 0; st0[1] = -1;
+    for (int64_t b = 0; b < nblk; ++b) { st0[2 + 2 * b] = 0x7fffffff; st0[3 + 2 * b] = -1; }
+    PHIP(hipMemcpy(c->d_ht_stat.p, st0.data(), st0.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(ing::k_ingest_heights, dim3(1), dim3(ing::HT_TILE), 0, c->stream_io, (const int*)c->d_sp.p, (const int*)c->d_op.p,
+                       c->d_ht.p, (int)N0, (int)K, (int)blk0, c->d_ht_stat.p);
+    c->ctr.kernel_launches++;
+    PHIP(hipGetLastError());
+    PHIP(hipEventRecord(c->ev_ht, c->stream_io));
+    c->ht_pending = true; c->ht_first = N0; c->ht_K = K; c->ht_dev_upto = N0 + K;
+    PCHK(rebuild_chains(c, nev_t, c->N));
+    c->nev.swap(nev_t);
+    PHIP(hipStreamSynchronize(c->stream));  // the caller's arrays may be reused or freed on return
+    // ... and the caller's stream may not overwrite them before the copies above are done (they are: drained)
+    c->st_dev_batches++;
+    c->st_dev_events += K;
+#undef PCHK
+#undef PHIP
+    return SW_OK;
+}
+
+int sw_get_ingest_stats(sw_ctx* c, int64_t* device_batches, int64_t* device_events, int64_t* fallback_batches, int64_t* host_height_events) {
+    if (!c) return SW_EINVAL;
+    if (device_batches) *device_batches = c->st_dev_batches;
+    if (device_events) *device_events = c->st_dev_events;
+    if (fallback_batches) *fallback_batches = c->st_fallback;
+    if (host_height_events) *host_height_events = c->st_host_ht;
     return SW_OK;
 }
 
@@ -3784,6 +4047,8 @@ int sw_reset(sw_ctx* c) {
     c->pool_h_valid = true;
     if (c->stream_io) HIPCHK(c, hipStreamSynchronize(c->stream_io));  // a payload upload may still be writing t / sig
     c->payload_pending = false;
+    c->ht_pending = false;   // (the heights kernel of a device append ran there too)
+    c->ht_dev_upto = 0;
     c->exact = false;  // (a fresh hashgraph starts on the fast path again)
     c->chunks_off = false;  // ... and with the chunked sweep
     return SW_OK;

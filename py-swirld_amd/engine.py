@@ -13,6 +13,26 @@ def _p(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
+def _dev_ptr(a):
+    """(address, length or None) of an array in device memory: an integer address, an object with data_ptr()
+    (a torch tensor) or with __cuda_array_interface__."""
+    if a is None:
+        return None, None
+    if isinstance(a, (int, np.integer)):
+        return int(a), None
+    if hasattr(a, "data_ptr"):
+        ptr = int(a.data_ptr())
+    elif hasattr(a, "__cuda_array_interface__"):
+        ptr = int(a.__cuda_array_interface__["data"][0])
+    else:
+        raise TypeError("expected a device address, or an object with data_ptr() / __cuda_array_interface__ "
+                        "(got %s; host arrays go through append_events)" % type(a).__name__)
+    try:
+        return ptr, len(a)
+    except TypeError:
+        return ptr, None
+
+
 class Hashgraph:
     def __init__(self, n_members, stake=None, coin_period=6, device=0):
         self._L = _lib.load()
@@ -67,6 +87,32 @@ class Hashgraph:
         t = None if t is None else np.ascontiguousarray(t, np.float64)
         sig = None if sig is None else np.ascontiguousarray(sig, np.uint8).reshape(K, 64)
         self._chk(self._L.sw_append_events(self._h, K, _p(creator), _p(sp), _p(op), _p(t), _p(sig)))
+
+    def append_events_device(self, creator, self_parent, other_parent, t=None, sig=None, stream=0, count=None):
+        """append_events for arrays that lie in DEVICE memory (int32 creator / parents, float64 t, K x 64 uint8 sig):
+        each one an integer address or an object with data_ptr() (torch) or __cuda_array_interface__.  K comes from
+        `creator`'s length where it has one, else from `count`.  `stream` (a raw hipStream_t) has the arrays' producers
+        enqueued; the library waits for them on the device.  Batches outside the bulk fork-free fast path fall back
+        to the host path inside the library (ingest_stats() counts them)."""
+        ptrs = [_dev_ptr(a) for a in (creator, self_parent, other_parent, t, sig)]
+        K = count if count is not None else ptrs[0][1]
+        if K is None:
+            raise ValueError("the number of events is not known: pass count=")
+        K = int(K)
+        for (_, ln), what in zip(ptrs[:4], ("creator", "self_parent", "other_parent", "t")):
+            if ln is not None and ln != K:
+                raise ValueError("%s holds %d entries, expected %d" % (what, ln, K))
+        if ptrs[4][1] is not None and ptrs[4][1] not in (K, 64 * K):
+            raise ValueError("sig holds %d entries, expected %d x 64 bytes" % (ptrs[4][1], K))
+        args = [C.c_void_p(q) if q else None for q, _ in ptrs]
+        self._chk(self._L.sw_append_events_device(self._h, K, *args, C.c_void_p(int(stream))))
+
+    def ingest_stats(self):
+        """Counters of append_events_device since the context was created: batches and events the device path
+        committed, batches that fell back to the host path, events whose height the host loop computed."""
+        v = [C.c_int64() for _ in range(4)]
+        self._chk(self._L.sw_get_ingest_stats(self._h, *[C.byref(x) for x in v]))
+        return dict(zip(("device_batches", "device_events", "fallback_batches", "host_height_events"), (int(x.value) for x in v)))
 
     @property
     def num_events(self):
