@@ -119,6 +119,65 @@ int sw_get_ingest_stats(sw_ctx* ctx, int64_t* device_batches, int64_t* device_ev
                         int64_t* host_height_events);
 
 /*
+ * Events by ID (Node.sync swirld.py:130-136, node.py).  A peer's sync payload names events by their 32-byte
+ * ids (BLAKE2b-256 of the pickled event) and their parents by id, in no particular order, events the receiver already has
+ * included.  The context can learn the ids of its events — an ID INDEX, allocated on first use: 32 bytes per event in dense
+ * order, and a device hash table id -> dense index (open addressing, power-of-two capacity, load <= 1/2, rebuilt when it
+ * grows; keyed by the first 64-bit word of the id, a hit confirmed on all 32 bytes; every probe loop is bounded by the
+ * capacity, ids being attacker-chosen) — and then takes a whole payload addressed by id.
+ * sw_rewind keeps the ids (the events stay), sw_reset forgets them.  The index is COMPLETE when every stored event has an
+ * id (an empty context counts as complete).
+ *
+ * sw_set_event_ids     ids of the stored events [first, first + K) (how events appended by index get theirs).  `first` must
+ *                      equal the number of events that have ids already.  SW_EINVAL, nothing stored, when an id is already
+ *                      present or occurs twice in the call.
+ * sw_get_event_ids     the ids of [first, first + K); SW_ERANGE beyond the events that have ids.
+ * sw_lookup_event_ids  index_out[i] = dense index of id i, or -1 (looked up on the device).
+ *
+ * sw_ingest_payload_device   Node.sync's loop over K events in ANY order, on the device: known ids are recognised, the rest
+ *   is validated, ordered topologically and appended; invalid events are DROPPED and the rest is stored (the reference's
+ *   behaviour, swirld.py:135 — unlike sw_append_events_device the call is not atomic per batch).  Needs a complete index
+ *   (SW_ENOTSUP and nothing stored otherwise).  All d_* arrays lie in memory of the context's device (checked like
+ *   sw_append_events_device's; a host pointer is SW_EINVAL before any launch); the three id arrays must be 8-byte aligned
+ *   (SW_EINVAL).  Per event: d_id32 its id; d_sp_id32 / d_op_id32 the parents' ids (ignored when the arity is 0); d_arity
+ *   (uint8) the number of parents claimed, len(ev.p); d_creator a dense member index; d_ok (uint8, NULL = all 1) 1 when
+ *   signature and hash were verified (what sw_crypto_verify_batch wrote, ANDed with the caller's hash comparison); d_t,
+ *   d_sig64 nullable as for sw_append_events_device; user_stream as there.  d_index_out: K int32 in device memory;
+ *   *n_stored (host): the events stored.  index_out[i] is
+ *     an index <  the event count before the call   the id is stored already (nothing is stored again)
+ *     an index >= the event count before the call   stored by this call at that dense index
+ *     -2  a later copy of an id that occurs earlier in this payload (the lowest position counts)
+ *     -3  d_ok is 0                       -4  creator outside [0, n)          -5  arity neither 0 nor 2
+ *     -6  a parent that is neither stored nor accepted in this call (children of dropped events, unknown ids, cycles)
+ *     -7  self-parent by another member   -8  other-parent by the same member
+ *   (several defects: the first in this order).  Acceptance runs in WAVES: wave 0 accepts the locally valid events whose
+ *   parents are both stored, and the locally valid roots; wave w those whose parents are all stored or accepted in waves
+ *   < w, at least one in wave w - 1; the call ends with the first wave that accepts nothing (at most accepted + 1 waves,
+ *   driven from the host in batches of launches with one read-back of per-wave counts; no kernel waits for another
+ *   workgroup).  The accepted set is what Node.sync's loop stores under any topological order of the payload.  Accepted
+ *   events get the dense indices (count before) + rank, rank sorting by (wave, payload position): a topological order that
+ *   keeps every member's chain in chain order.  They then go through the body of sw_append_events_device — same bulk
+ *   predicate, fallbacks and fork handling (exact path under sw_set_forks(1); SW_ENOTSUP under sw_set_forks(0)); the ids
+ *   are committed only after the append has succeeded.  If it fails, context and index are unchanged, *n_stored is 0 and
+ *   index_out is unspecified.
+ * sw_ingest_payload    the same with every array (and index_out) in HOST memory: staged into context scratch on the
+ *   context's stream, same device code.
+ * sw_get_payload_stats payload calls so far, waves and accepted events of the most recent one, rebuilds of the id table
+ *   since sw_create, and — under sw_set_profiling — the host time in ms of the most recent call's phases: phase_ms[4] =
+ *   resolve, waves, sort + gather, append + id commit.  Any pointer may be NULL.
+ */
+int sw_set_event_ids(sw_ctx* ctx, int64_t first, int64_t K, const uint8_t* id32);
+int sw_get_event_ids(sw_ctx* ctx, int64_t first, int64_t K, uint8_t* out);
+int sw_lookup_event_ids(sw_ctx* ctx, int64_t K, const uint8_t* id32, int32_t* index_out);
+int sw_ingest_payload_device(sw_ctx* ctx, int64_t K, const uint8_t* d_id32, const uint8_t* d_sp_id32, const uint8_t* d_op_id32,
+                             const uint8_t* d_arity, const int32_t* d_creator, const uint8_t* d_ok, const double* d_t,
+                             const uint8_t* d_sig64, void* user_stream, int32_t* d_index_out, int64_t* n_stored);
+int sw_ingest_payload(sw_ctx* ctx, int64_t K, const uint8_t* id32, const uint8_t* sp_id32, const uint8_t* op_id32,
+                      const uint8_t* arity, const int32_t* creator, const uint8_t* ok, const double* t, const uint8_t* sig64,
+                      int32_t* index_out, int64_t* n_stored);
+int sw_get_payload_stats(sw_ctx* ctx, int64_t* calls, int64_t* waves, int64_t* accepted, int64_t* table_rebuilds, double* phase_ms);
+
+/*
  * Node.divide_rounds(events) (swirld.py:187-222) for the K events [first, first+K):
  * fills can_see rows, round numbers and the witness table.  `first` must equal the
  * number of events already divided (the reference processes every new event exactly

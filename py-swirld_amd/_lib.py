@@ -46,6 +46,12 @@ SIGNATURES = {
     "sw_num_events": (C.c_int64, [_P]),
     "sw_append_events_device": (C.c_int, [_P, C.c_int64, _P, _P, _P, _P, _P, _P]),
     "sw_get_ingest_stats": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "sw_set_event_ids": (C.c_int, [_P, C.c_int64, C.c_int64, _P]),
+    "sw_get_event_ids": (C.c_int, [_P, C.c_int64, C.c_int64, _P]),
+    "sw_lookup_event_ids": (C.c_int, [_P, C.c_int64, _P, _P]),
+    "sw_ingest_payload_device": (C.c_int, [_P, C.c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.POINTER(C.c_int64)]),
+    "sw_ingest_payload": (C.c_int, [_P, C.c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.POINTER(C.c_int64)]),
+    "sw_get_payload_stats": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), _P]),
     "sw_divide_rounds": (C.c_int, [_P, C.c_int64, C.c_int64]),
     "sw_decide_fame": (C.c_int, [_P, _P, C.c_int, C.POINTER(C.c_int)]),
     "sw_decide_fame_partial": (C.c_int, [_P, C.c_int, C.c_int, _P, _P, C.c_int, C.POINTER(C.c_int)]),

@@ -24,6 +24,7 @@
 #include "crypto.hip.h"
 #include "exact.hip.h"
 #include "ingest.hip.h"
+#include "resolve.hip.h"
 
 namespace {
 
@@ -156,6 +157,17 @@ struct sw_ctx {
     int64_t ht_first = 0, ht_K = 0;   // ... which are these
     int64_t ht_dev_upto = 0;      // events below this index and beyond the host mirror (sp.size()) have their height in d_ht
     int64_t st_dev_batches = 0, st_dev_events = 0, st_fallback = 0, st_host_ht = 0;   // sw_get_ingest_stats
+    // id index (sw_set_event_ids, sw_ingest_payload[_device]; resolve.hip.h): allocated on first use
+    DBuf<unsigned char> d_id;     // 32 B per event that has an id, in dense order
+    DBuf<int32_t> d_idtab;        // id -> dense index: 1 << idtab_log slots, load <= 1/2, rebuilt from d_id when it grows
+    int idtab_log = 0;            // (0: no table yet)
+    int64_t n_ids = 0;            // events [0, n_ids) have ids; the index is COMPLETE when n_ids == N
+    DBuf<int32_t> d_idflag;       // [4] duplicate flag of an insert
+    DBuf<unsigned char> d_pl;     // scratch of a payload call
+    DBuf<unsigned char> d_pl_in;  // ... and the staged arrays of the host-array forms
+    int32_t* h_plcnt = nullptr;   // pinned: per-wave counts of one batch of waves
+    int64_t pl_calls = 0, pl_waves = 0, pl_accepted = 0, pl_rebuilds = 0;   // sw_get_payload_stats (waves, accepted: the last call's)
+    double pl_ms[4] = {0, 0, 0, 0};   // ... host time of its phases under sw_set_profiling: resolve, waves, sort + gather, append + commit
 
     // device: events
     DBuf<int32_t> d_cr, d_sp, d_op, d_ht, d_seq, d_round, d_L, d_chain_ev;
@@ -2877,6 +2889,8 @@ int sw_destroy(sw_ctx* c) {
     if (c->ev_payload) (void)hipEventDestroy(c->ev_payload);
     if (c->ev_ht) (void)hipEventDestroy(c->ev_ht);
     dfree(c->d_ing_tab); dfree(c->d_ing_hist); dfree(c->d_ht_stat);
+    dfree(c->d_id); dfree(c->d_idtab); dfree(c->d_idflag); dfree(c->d_pl); dfree(c->d_pl_in);
+    if (c->h_plcnt) (void)hipHostFree(c->h_plcnt);
     if (c->ev_aux_done) (void)hipEventDestroy(c->ev_aux_done);
     if (c->ev_cs_done) (void)hipEventDestroy(c->ev_cs_done);
     if (c->ev_main_mark) (void)hipEventDestroy(c->ev_main_mark);
@@ -3441,6 +3455,9 @@ int ingest_fallback(sw_ctx* c, int64_t K, const int32_t* d_creator, const int32_
 
 }  // namespace
 
+static int append_device_body(sw_ctx* c, int64_t K, const int32_t* d_creator, const int32_t* d_self_parent, const int32_t* d_other_parent,
+                              const double* d_t, const uint8_t* d_sig64, hipStream_t us);
+
 int sw_append_events_device(sw_ctx* c, int64_t K, const int32_t* d_creator, const int32_t* d_self_parent,
                             const int32_t* d_other_parent, const double* d_t, const uint8_t* d_sig64, void* user_stream) {
     if (!c) return SW_EINVAL;
@@ -3453,7 +3470,14 @@ int sw_append_events_device(sw_ctx* c, int64_t K, const int32_t* d_creator, cons
     if (!on_ctx_device(c, d_creator, b4) || !on_ctx_device(c, d_self_parent, b4) || !on_ctx_device(c, d_other_parent, b4) ||
         (d_t && !on_ctx_device(c, d_t, (size_t)K * 8)) || (d_sig64 && !on_ctx_device(c, d_sig64, (size_t)K * 64)))
         return fail(c, SW_EINVAL, "sw_append_events_device: every array must lie in memory of device %d (a host pointer, or another device's)", c->device);
-    hipStream_t us = (hipStream_t)user_stream;
+    return append_device_body(c, K, d_creator, d_self_parent, d_other_parent, d_t, d_sig64, (hipStream_t)user_stream);
+}
+
+// The call itself, behind the argument checks: K > 0 events in memory of the context's device, produced on `us`.
+// (Also the last step of sw_ingest_payload[_device], with `us` the context's own stream.)
+static int append_device_body(sw_ctx* c, int64_t K, const int32_t* d_creator, const int32_t* d_self_parent, const int32_t* d_other_parent,
+                              const double* d_t, const uint8_t* d_sig64, hipStream_t us) {
+    const size_t b4 = (size_t)K * sizeof(int32_t);
     const int64_t N0 = c->N;
     const int n = c->n, np = c->npad;
     const bool bulk = K >= 8192 || c->chain_cap.empty() || K * 8 >= N0;   // (sw_append_events' predicate)
@@ -3585,6 +3609,308 @@ int sw_get_ingest_stats(sw_ctx* c, int64_t* device_batches, int64_t* device_even
     if (device_events) *device_events = c->st_dev_events;
     if (fallback_batches) *fallback_batches = c->st_fallback;
     if (host_height_events) *host_height_events = c->st_host_ht;
+    return SW_OK;
+}
+
+// ---- id index and payload ingest by event id (resolve.hip.h) ------------------------------------------------------
+}  // extern "C"
+namespace {
+
+constexpr int PL_WAVE_BATCH = 32;   // waves launched between two read-backs of their counts
+
+// (re)build the table from the ids the context holds
+int idtab_rebuild(sw_ctx* c) {
+    HIPCHK(c, hipMemsetAsync(c->d_idtab.p, 0xff, sizeof(int32_t) << c->idtab_log, c->stream));
+    if (c->n_ids) {
+        hipLaunchKernelGGL(rsv::k_tab_insert, dim3((unsigned)((c->n_ids + 255) / 256)), dim3(256), 0, c->stream, c->d_idtab.p, c->idtab_log,
+                           (const unsigned char*)c->d_id.p, 0, (int)c->n_ids, (int*)nullptr);
+        c->ctr.kernel_launches++;
+        HIPCHK(c, hipGetLastError());
+    }
+    c->pl_rebuilds++;
+    return SW_OK;
+}
+
+// room for `count` ids: the id array (contents kept) and a table of load <= 1/2
+int idindex_reserve(sw_ctx* c, int64_t count) {
+    CHK(dgrow(c, c->d_id, (size_t)count * 32, (size_t)c->n_ids * 32));
+    CHK(dgrow(c, c->d_idflag, 4, 0));
+    int lg = 10;
+    while ((1ll << lg) < 2 * count) ++lg;
+    if (lg <= c->idtab_log) return SW_OK;
+    CHK(dgrow(c, c->d_idtab, (size_t)1 << lg, 0));
+    c->idtab_log = lg;
+    return idtab_rebuild(c);
+}
+
+// insert the ids of the events [first, first + K) (already in d_id); *flag = 0 fine, 1 an id was present or twice, 2 table full
+int idtab_insert(sw_ctx* c, int64_t first, int64_t K, int* flag) {
+    HIPCHK(c, hipMemsetAsync(c->d_idflag.p, 0, sizeof(int32_t), c->stream));
+    hipLaunchKernelGGL(rsv::k_tab_insert, dim3((unsigned)((K + 255) / 256)), dim3(256), 0, c->stream, c->d_idtab.p, c->idtab_log,
+                       (const unsigned char*)c->d_id.p, (int)first, (int)K, c->d_idflag.p);
+    c->ctr.kernel_launches++;
+    HIPCHK(c, hipGetLastError());
+    int32_t f = 0;
+    HIPCHK(c, hipMemcpyAsync(&f, c->d_idflag.p, sizeof f, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    *flag = f;
+    return SW_OK;
+}
+
+struct Carve {   // consecutive 256-byte aligned pieces of one allocation
+    size_t off = 0;
+    size_t take(size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; }
+};
+
+double ms_since(std::chrono::steady_clock::time_point t0) {
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+
+// The payload call behind the argument checks.  Every array lies in device memory; d_out too.
+int payload_core(sw_ctx* c, int64_t K, const uint8_t* d_id32, const uint8_t* d_sp_id32, const uint8_t* d_op_id32, const uint8_t* d_arity,
+                 const int32_t* d_creator, const uint8_t* d_ok, const double* d_t, const uint8_t* d_sig64, hipStream_t us, int32_t* d_out,
+                 int64_t* n_stored) {
+    const int64_t N0 = c->N;
+    const bool prof = c->profiling;
+    auto t0 = std::chrono::steady_clock::now();
+    // ---- allocations (nothing committed): ids and table for every event of the payload, scratch
+    CHK(idindex_reserve(c, N0 + K));
+    int llog = 4;
+    while ((1ll << llog) < 2 * K) ++llog;
+    const size_t nctr = (size_t)K + PL_WAVE_BATCH + 2;
+    const size_t tiles0 = (size_t)((K + ing::TILE - 1) / ing::TILE);
+    Carve cv;
+    const size_t o_lslots = cv.take(sizeof(int32_t) << llog), o_wave = cv.take((size_t)K * 4), o_pr = cv.take((size_t)K * 8);
+    const size_t o_la = cv.take((size_t)K * 4), o_lb = cv.take((size_t)K * 4), o_pend = cv.take(nctr * 4), o_acc = cv.take(nctr * 4);
+    const size_t o_key = cv.take((size_t)K * 4), o_seq = cv.take((size_t)K * 4), o_oa = cv.take((size_t)K * 4), o_ob = cv.take((size_t)K * 4);
+    const size_t o_rank = cv.take((size_t)K * 4), o_hist = cv.take(tiles0 * 1024 * 4), o_tab = cv.take(3 * 1024 * 4), o_base = cv.take(1024 * 4);
+    const size_t o_gcr = cv.take((size_t)K * 4), o_gsp = cv.take((size_t)K * 4), o_gop = cv.take((size_t)K * 4);
+    const size_t o_gt = cv.take(d_t ? (size_t)K * 8 : 0), o_gsig = cv.take(d_sig64 ? (size_t)K * 64 : 0);
+    CHK(dgrow(c, c->d_pl, cv.off, 0));
+    unsigned char* B = c->d_pl.p;
+    int* lslots = (int*)(B + o_lslots); int* wave = (int*)(B + o_wave); int* pr = (int*)(B + o_pr);
+    int* lst[2] = {(int*)(B + o_la), (int*)(B + o_lb)};
+    int* pend = (int*)(B + o_pend); int* acc = (int*)(B + o_acc);
+    int* key = (int*)(B + o_key); int* seq = (int*)(B + o_seq); int* ord[2] = {(int*)(B + o_oa), (int*)(B + o_ob)};
+    int* rank_of = (int*)(B + o_rank); int* hist = (int*)(B + o_hist); int* tab = (int*)(B + o_tab); int* base = (int*)(B + o_base);
+    int* g_cr = (int*)(B + o_gcr); int* g_sp = (int*)(B + o_gsp); int* g_op = (int*)(B + o_gop);
+    double* g_t = d_t ? (double*)(B + o_gt) : nullptr;
+    unsigned char* g_sig = d_sig64 ? B + o_gsig : nullptr;
+    if (!c->h_plcnt && hipHostMalloc((void**)&c->h_plcnt, (2 * PL_WAVE_BATCH + 2) * sizeof(int32_t), hipHostMallocDefault) != hipSuccess) {
+        (void)hipGetLastError();
+        c->h_plcnt = nullptr;
+        return fail(c, SW_ENOMEM, "hipHostMalloc for the wave counts failed");
+    }
+    if (!c->ev_user) HIPCHK(c, hipEventCreateWithFlags(&c->ev_user, hipEventDisableTiming));
+    HIPCHK(c, hipEventRecord(c->ev_user, us));
+    HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_user, 0));
+    // ---- resolve: the payload's own table (lowest position of every id), local checks, parent references
+    const dim3 ev_grid((unsigned)((K + 255) / 256));
+    HIPCHK(c, hipMemsetAsync(lslots, 0xff, sizeof(int32_t) << llog, c->stream));
+    HIPCHK(c, hipMemsetAsync(pend, 0, (o_acc - o_pend) + nctr * 4, c->stream));   // (pend and acc are neighbours)
+    hipLaunchKernelGGL(rsv::k_tab_insert, ev_grid, dim3(256), 0, c->stream, lslots, llog, (const unsigned char*)d_id32, 0, (int)K, (int*)nullptr);
+    hipLaunchKernelGGL(rsv::k_pl_local, ev_grid, dim3(256), 0, c->stream, (const int*)c->d_idtab.p, N0 ? c->idtab_log : 0,
+                       (const unsigned char*)c->d_id.p, (const int*)lslots, llog, (const unsigned char*)d_id32, (const unsigned char*)d_sp_id32,
+                       (const unsigned char*)d_op_id32, (const unsigned char*)d_arity, (const int*)d_creator, (const unsigned char*)d_ok, (int)K, c->n,
+                       (int*)d_out, wave, pr, lst[0], pend);
+    c->ctr.kernel_launches += 2;
+    HIPCHK(c, hipGetLastError());
+    if (prof) { HIPCHK(c, hipStreamSynchronize(c->stream)); c->pl_ms[0] = ms_since(t0); t0 = std::chrono::steady_clock::now(); }
+    // ---- waves: batches of launches, one read-back of their counts each; ends with the first wave that accepts nothing
+    int64_t W = -1, A = 0, ub = K;
+    for (int64_t w0 = 0; W < 0; w0 += PL_WAVE_BATCH) {
+        if (w0 > K + 1) return fail(c, SW_EIO, "payload waves did not end after %lld waves (internal error)", (long long)w0);
+        const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((ub + 255) / 256, 2048));
+        for (int64_t w = w0; w < w0 + PL_WAVE_BATCH; ++w)
+            hipLaunchKernelGGL(rsv::k_pl_wave, dim3(grid), dim3(256), 0, c->stream, (int)w, (const int*)lst[w & 1], (const int*)(pend + w), lst[(w + 1) & 1],
+                               pend + w + 1, acc + w, (const int*)pr, (const int*)d_creator, (const int*)c->d_cr.p, wave, (int*)d_out);
+        c->ctr.kernel_launches += PL_WAVE_BATCH;
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipMemcpyAsync(c->h_plcnt, pend + w0, (PL_WAVE_BATCH + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(c->h_plcnt + PL_WAVE_BATCH + 1, acc + w0, PL_WAVE_BATCH * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        for (int j = 0; j < PL_WAVE_BATCH; ++j) {
+            const int a = c->h_plcnt[PL_WAVE_BATCH + 1 + j];
+            if (a == 0) { W = w0 + j; break; }
+            A += a;
+        }
+        ub = c->h_plcnt[PL_WAVE_BATCH];
+    }
+    hipLaunchKernelGGL(rsv::k_pl_leftover, ev_grid, dim3(256), 0, c->stream, (const int*)wave, (int)K, (int*)d_out);
+    c->ctr.kernel_launches++;
+    c->pl_waves = W;
+    c->pl_accepted = A;
+    c->pl_calls++;
+    if (prof) { HIPCHK(c, hipStreamSynchronize(c->stream)); c->pl_ms[1] = ms_since(t0); t0 = std::chrono::steady_clock::now(); }
+    c->pl_ms[2] = c->pl_ms[3] = 0;
+    if (A == 0) {
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        return SW_OK;
+    }
+    // ---- dense order: stable sort of the accepted events by wave, LSD in passes of 10 bits through the stable-rank
+    // kernels of ingest.hip.h (keys < 1024; an event that was not accepted has key -1 and drops out in pass 0)
+    int passes = 1;
+    while (passes < 4 && ((W - 1) >> (10 * passes)) > 0) ++passes;
+    const int* cur = nullptr;
+    for (int p = 0; p < passes; ++p) {
+        const int64_t cnt = p == 0 ? K : A;
+        const int tiles = (int)((cnt + ing::TILE - 1) / ing::TILE);
+        const dim3 g((unsigned)((cnt + 255) / 256));
+        int* dst = ord[p & 1];
+        HIPCHK(c, hipMemsetAsync(tab, 0, 3 * 1024 * sizeof(int32_t), c->stream));
+        hipLaunchKernelGGL(rsv::k_pl_keys, g, dim3(256), 0, c->stream, (const int*)wave, cur, (int)cnt, 10 * p, key);
+        hipLaunchKernelGGL(ing::k_ingest_hist, dim3(tiles), dim3(ing::THREADS), 0, c->stream, (const int*)key, 0, (int)cnt, 1024, hist, tab);
+        hipLaunchKernelGGL(ing::k_ingest_scan, dim3(1024 / 64), dim3(64), 0, c->stream, hist, tiles, 1024, tab);
+        hipLaunchKernelGGL(ing::k_ingest_rank, dim3(tiles), dim3(ing::THREADS), 0, c->stream, (const int*)key, 0, (int)cnt, 1024, 10, (const int*)hist, seq);
+        hipLaunchKernelGGL(rsv::k_pl_bases, dim3(1), dim3(1024), 0, c->stream, (const int*)tab, base);
+        hipLaunchKernelGGL(rsv::k_pl_scatter, g, dim3(256), 0, c->stream, (const int*)key, (const int*)seq, (const int*)base, cur, (int)cnt, dst);
+        c->ctr.kernel_launches += 6;
+        HIPCHK(c, hipGetLastError());
+        cur = dst;
+    }
+    const dim3 a_grid((unsigned)((A + 255) / 256));
+    hipLaunchKernelGGL(rsv::k_pl_ranks, a_grid, dim3(256), 0, c->stream, cur, (int)A, (int)N0, rank_of, (int*)d_out);
+    hipLaunchKernelGGL(rsv::k_pl_gather, a_grid, dim3(256), 0, c->stream, cur, (int)A, (int)N0, (const int*)rank_of, (const int*)pr, (const int*)d_creator,
+                       (const unsigned char*)d_id32, d_t, g_cr, g_sp, g_op, g_t, c->d_id.p + (size_t)N0 * 32);
+    if (d_sig64)
+        hipLaunchKernelGGL(rsv::k_pl_gather_sig, dim3((unsigned)((A * 16 + 255) / 256)), dim3(256), 0, c->stream, cur, (int)A, (const unsigned char*)d_sig64, g_sig);
+    c->ctr.kernel_launches += 3;
+    HIPCHK(c, hipGetLastError());
+    if (prof) { HIPCHK(c, hipStreamSynchronize(c->stream)); c->pl_ms[2] = ms_since(t0); t0 = std::chrono::steady_clock::now(); }
+    // ---- append (bulk device path or its fallbacks; atomic), then — only then — the ids
+    CHK(append_device_body(c, A, g_cr, g_sp, g_op, g_t, g_sig, c->stream));
+    int flag = 0;
+    const int rc = idtab_insert(c, N0, A, &flag);
+    if (rc != SW_OK || flag != 0) {
+        c->poisoned = true;
+        return rc != SW_OK ? rc : fail(c, SW_EIO, "id table insert after the append reported %d (internal error)", flag);
+    }
+    c->n_ids = N0 + A;
+    *n_stored = A;
+    if (prof) c->pl_ms[3] = ms_since(t0);
+    return SW_OK;
+}
+
+int payload_args(sw_ctx* c, int64_t K, const void* id, const void* sp, const void* op, const void* ar, const void* cr, const void* out,
+                 int64_t* n_stored, const char* what) {
+    if (c->poisoned) return fail(c, SW_EIO, "context unusable after an earlier device failure");
+    if (!n_stored) return fail(c, SW_EINVAL, "%s: n_stored is NULL", what);
+    *n_stored = 0;
+    if (K < 0 || (K > 0 && (!id || !sp || !op || !ar || !cr || !out))) return fail(c, SW_EINVAL, "%s: NULL payload arrays", what);
+    if (K > 0x3fffffffll || c->N + K > 0x7ffffff0ll) return fail(c, SW_ERANGE, "%s: more than 2^31 events", what);
+    if (c->n_ids != c->N)
+        return fail(c, SW_ENOTSUP, "%s: %lld of the %lld stored events have no id (sw_set_event_ids first)", what, (long long)(c->N - c->n_ids), (long long)c->N);
+    return SW_OK;
+}
+
+}  // namespace
+extern "C" {
+
+int sw_set_event_ids(sw_ctx* c, int64_t first, int64_t K, const uint8_t* id32) {
+    if (!c) return SW_EINVAL;
+    if (c->poisoned) return fail(c, SW_EIO, "context unusable after an earlier device failure");
+    if (K < 0 || (K > 0 && !id32)) return fail(c, SW_EINVAL, "sw_set_event_ids: NULL ids");
+    if (first != c->n_ids) return fail(c, SW_EINVAL, "sw_set_event_ids must continue at event %lld (got %lld): ids are contiguous from 0", (long long)c->n_ids, (long long)first);
+    if (first + K > c->N) return fail(c, SW_ERANGE, "events [%lld, %lld) outside the stored hashgraph", (long long)first, (long long)(first + K));
+    if (K == 0) return SW_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    CHK(idindex_reserve(c, first + K));
+    HIPCHK(c, hipMemcpyAsync(c->d_id.p + (size_t)first * 32, id32, (size_t)K * 32, hipMemcpyHostToDevice, c->stream));
+    int flag = 0;
+    CHK(idtab_insert(c, first, K, &flag));
+    if (flag != 0) {
+        CHK(idtab_rebuild(c));   // (the table as it was: from the ids below `first`)
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (flag == 1) return fail(c, SW_EINVAL, "sw_set_event_ids: an id is already present, or occurs twice in the call");
+        return fail(c, SW_EIO, "sw_set_event_ids: id table full (internal error)");
+    }
+    c->n_ids = first + K;
+    return SW_OK;
+}
+
+int sw_get_event_ids(sw_ctx* c, int64_t first, int64_t K, uint8_t* out) {
+    if (!c) return SW_EINVAL;
+    if (first < 0 || K < 0 || first + K > c->n_ids) return fail(c, SW_ERANGE, "events [%lld, %lld) beyond the %lld events that have ids", (long long)first, (long long)(first + K), (long long)c->n_ids);
+    if (K == 0) return SW_OK;
+    if (!out) return fail(c, SW_EINVAL, "sw_get_event_ids: NULL output");
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipMemcpyAsync(out, c->d_id.p + (size_t)first * 32, (size_t)K * 32, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return SW_OK;
+}
+
+int sw_lookup_event_ids(sw_ctx* c, int64_t K, const uint8_t* id32, int32_t* index_out) {
+    if (!c) return SW_EINVAL;
+    if (c->poisoned) return fail(c, SW_EIO, "context unusable after an earlier device failure");
+    if (K < 0 || K > 0x3fffffffll || (K > 0 && (!id32 || !index_out))) return fail(c, SW_EINVAL, "sw_lookup_event_ids: NULL arrays");
+    if (K == 0) return SW_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    Carve cv;
+    const size_t o_id = cv.take((size_t)K * 32), o_out = cv.take((size_t)K * 4);
+    CHK(dgrow(c, c->d_pl_in, cv.off, 0));
+    unsigned char* B = c->d_pl_in.p;
+    HIPCHK(c, hipMemcpyAsync(B + o_id, id32, (size_t)K * 32, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(rsv::k_tab_lookup, dim3((unsigned)((K + 255) / 256)), dim3(256), 0, c->stream, (const int*)c->d_idtab.p, c->n_ids ? c->idtab_log : 0,
+                       (const unsigned char*)c->d_id.p, (const unsigned char*)(B + o_id), (int)K, (int*)(B + o_out));
+    c->ctr.kernel_launches++;
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(index_out, B + o_out, (size_t)K * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return SW_OK;
+}
+
+int sw_ingest_payload_device(sw_ctx* c, int64_t K, const uint8_t* d_id32, const uint8_t* d_sp_id32, const uint8_t* d_op_id32, const uint8_t* d_arity,
+                             const int32_t* d_creator, const uint8_t* d_ok, const double* d_t, const uint8_t* d_sig64, void* user_stream,
+                             int32_t* d_index_out, int64_t* n_stored) {
+    if (!c) return SW_EINVAL;
+    CHK(payload_args(c, K, d_id32, d_sp_id32, d_op_id32, d_arity, d_creator, d_index_out, n_stored, "sw_ingest_payload_device"));
+    if (K == 0) return SW_OK;
+    if (((uintptr_t)d_id32 | (uintptr_t)d_sp_id32 | (uintptr_t)d_op_id32) & 7)
+        return fail(c, SW_EINVAL, "sw_ingest_payload_device: the id arrays must be 8-byte aligned");
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t k = (size_t)K;
+    if (!on_ctx_device(c, d_id32, k * 32) || !on_ctx_device(c, d_sp_id32, k * 32) || !on_ctx_device(c, d_op_id32, k * 32) ||
+        !on_ctx_device(c, d_arity, k) || !on_ctx_device(c, d_creator, k * 4) || !on_ctx_device(c, d_index_out, k * 4) ||
+        (d_ok && !on_ctx_device(c, d_ok, k)) || (d_t && !on_ctx_device(c, d_t, k * 8)) || (d_sig64 && !on_ctx_device(c, d_sig64, k * 64)))
+        return fail(c, SW_EINVAL, "sw_ingest_payload_device: every array must lie in memory of device %d (a host pointer, or another device's)", c->device);
+    return payload_core(c, K, d_id32, d_sp_id32, d_op_id32, d_arity, d_creator, d_ok, d_t, d_sig64, (hipStream_t)user_stream, d_index_out, n_stored);
+}
+
+int sw_ingest_payload(sw_ctx* c, int64_t K, const uint8_t* id32, const uint8_t* sp_id32, const uint8_t* op_id32, const uint8_t* arity,
+                      const int32_t* creator, const uint8_t* ok, const double* t, const uint8_t* sig64, int32_t* index_out, int64_t* n_stored) {
+    if (!c) return SW_EINVAL;
+    CHK(payload_args(c, K, id32, sp_id32, op_id32, arity, creator, index_out, n_stored, "sw_ingest_payload"));
+    if (K == 0) return SW_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t k = (size_t)K;
+    Carve cv;
+    const size_t o_id = cv.take(k * 32), o_sp = cv.take(k * 32), o_op = cv.take(k * 32), o_ar = cv.take(k), o_cr = cv.take(k * 4);
+    const size_t o_ok = cv.take(ok ? k : 0), o_t = cv.take(t ? k * 8 : 0), o_sig = cv.take(sig64 ? k * 64 : 0), o_out = cv.take(k * 4);
+    CHK(dgrow(c, c->d_pl_in, cv.off, 0));
+    unsigned char* B = c->d_pl_in.p;
+    HIPCHK(c, hipMemcpyAsync(B + o_id, id32, k * 32, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(B + o_sp, sp_id32, k * 32, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(B + o_op, op_id32, k * 32, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(B + o_ar, arity, k, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(B + o_cr, creator, k * 4, hipMemcpyHostToDevice, c->stream));
+    if (ok) HIPCHK(c, hipMemcpyAsync(B + o_ok, ok, k, hipMemcpyHostToDevice, c->stream));
+    if (t) HIPCHK(c, hipMemcpyAsync(B + o_t, t, k * 8, hipMemcpyHostToDevice, c->stream));
+    if (sig64) HIPCHK(c, hipMemcpyAsync(B + o_sig, sig64, k * 64, hipMemcpyHostToDevice, c->stream));
+    const int rc = payload_core(c, K, B + o_id, B + o_sp, B + o_op, B + o_ar, (const int32_t*)(B + o_cr), ok ? B + o_ok : nullptr,
+                                t ? (const double*)(B + o_t) : nullptr, sig64 ? B + o_sig : nullptr, c->stream, (int32_t*)(B + o_out), n_stored);
+    if (rc != SW_OK) return rc;
+    HIPCHK(c, hipMemcpyAsync(index_out, B + o_out, k * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return SW_OK;
+}
+
+int sw_get_payload_stats(sw_ctx* c, int64_t* calls, int64_t* waves, int64_t* accepted, int64_t* table_rebuilds, double* phase_ms) {
+    if (!c) return SW_EINVAL;
+    if (calls) *calls = c->pl_calls;
+    if (waves) *waves = c->pl_waves;
+    if (accepted) *accepted = c->pl_accepted;
+    if (table_rebuilds) *table_rebuilds = c->pl_rebuilds;
+    if (phase_ms) for (int i = 0; i < 4; ++i) phase_ms[i] = c->pl_ms[i];
     return SW_OK;
 }
 
@@ -4049,6 +4375,8 @@ int sw_reset(sw_ctx* c) {
     c->payload_pending = false;
     c->ht_pending = false;   // (the heights kernel of a device append ran there too)
     c->ht_dev_upto = 0;
+    c->n_ids = 0;   // the ids go with the events (the table keeps its size and is emptied)
+    if (c->idtab_log) HIPCHK(c, hipMemsetAsync(c->d_idtab.p, 0xff, sizeof(int32_t) << c->idtab_log, c->stream));
     c->exact = false;  // (a fresh hashgraph starts on the fast path again)
     c->chunks_off = false;  // ... and with the chunked sweep
     return SW_OK;

@@ -114,6 +114,81 @@ class Hashgraph:
         self._chk(self._L.sw_get_ingest_stats(self._h, *[C.byref(x) for x in v]))
         return dict(zip(("device_batches", "device_events", "fallback_batches", "host_height_events"), (int(x.value) for x in v)))
 
+    # ---- events by id (Node.sync, swirld.py:130-136): the id index and whole payloads addressed by id ----
+    @staticmethod
+    def _ids(a, K=None):
+        a = np.ascontiguousarray(a, np.uint8).reshape(-1, 32)
+        if K is not None and a.shape[0] != K:
+            raise ValueError("expected %d ids of 32 bytes, got %d" % (K, a.shape[0]))
+        return a
+
+    def set_event_ids(self, first, ids):
+        """Attach the 32-byte ids `ids` (K x 32 uint8) to the stored events [first, first + K); `first` must be the number
+        of events that have ids already.  SW_EINVAL when an id is already present or occurs twice."""
+        ids = self._ids(ids)
+        self._chk(self._L.sw_set_event_ids(self._h, int(first), ids.shape[0], _p(ids)))
+
+    def event_ids(self, first=0, K=None):
+        """The ids of the events [first, first + K) as a K x 32 uint8 array (K None: every event from `first` on)."""
+        if K is None:
+            K = self.num_events - first
+        out = np.empty((max(int(K), 0), 32), np.uint8)
+        self._chk(self._L.sw_get_event_ids(self._h, int(first), int(K), _p(out)))
+        return out
+
+    def lookup_event_ids(self, ids):
+        """Dense index of every id, -1 where the context does not hold it (looked up on the device)."""
+        ids = self._ids(ids)
+        out = np.empty(ids.shape[0], np.int32)
+        self._chk(self._L.sw_lookup_event_ids(self._h, ids.shape[0], _p(ids), _p(out)))
+        return out
+
+    def ingest_payload(self, ids, sp_ids, op_ids, arity, creator, ok=None, t=None, sig=None):
+        """A sync payload addressed by id, host arrays in any order (sw_ingest_payload): known ids are recognised, invalid
+        events dropped, the rest ordered topologically and appended.  Returns (index_out, n_stored): per event its dense
+        index or a reject code -2 .. -8 (include/swirld_hip.h)."""
+        ids = self._ids(ids)
+        K = ids.shape[0]
+        sp_ids, op_ids = self._ids(sp_ids, K), self._ids(op_ids, K)
+        arity = np.ascontiguousarray(arity, np.uint8)
+        creator = np.ascontiguousarray(creator, np.int32)
+        if arity.shape != (K,) or creator.shape != (K,):
+            raise ValueError("arity / creator must have one entry per event")
+        ok = None if ok is None else np.ascontiguousarray(ok, np.uint8).reshape(K)
+        t = None if t is None else np.ascontiguousarray(t, np.float64).reshape(K)
+        sig = None if sig is None else np.ascontiguousarray(sig, np.uint8).reshape(K, 64)
+        out = np.empty(K, np.int32)
+        n_stored = C.c_int64()
+        self._chk(self._L.sw_ingest_payload(self._h, K, _p(ids), _p(sp_ids), _p(op_ids), _p(arity), _p(creator), _p(ok), _p(t), _p(sig),
+                                            _p(out), C.byref(n_stored)))
+        return out, int(n_stored.value)
+
+    def ingest_payload_device(self, ids, sp_ids, op_ids, arity, creator, ok=None, t=None, sig=None, index_out=None, stream=0, count=None):
+        """ingest_payload for arrays in DEVICE memory (addresses, or objects with data_ptr() / __cuda_array_interface__;
+        the id arrays 8-byte aligned).  `index_out` (required): K int32 in device memory, where the answer is left.
+        Returns (index_out as given, n_stored)."""
+        if index_out is None:
+            raise ValueError("index_out (K int32 in device memory) is required")
+        ptrs = [_dev_ptr(a) for a in (ids, sp_ids, op_ids, arity, creator, ok, t, sig, index_out)]
+        K = count if count is not None else ptrs[3][1]
+        if K is None:
+            raise ValueError("the number of events is not known: pass count=")
+        K = int(K)
+        args = [C.c_void_p(q) if q else None for q, _ in ptrs]
+        n_stored = C.c_int64()
+        self._chk(self._L.sw_ingest_payload_device(self._h, K, *args[:8], C.c_void_p(int(stream)), args[8], C.byref(n_stored)))
+        return index_out, int(n_stored.value)
+
+    def payload_stats(self):
+        """Payload calls so far, waves / accepted events of the most recent one, id-table rebuilds, and (under
+        set_profiling) the host milliseconds of its phases: resolve, waves, sort, append."""
+        v = [C.c_int64() for _ in range(4)]
+        ms = (C.c_double * 4)()
+        self._chk(self._L.sw_get_payload_stats(self._h, *[C.byref(x) for x in v], ms))
+        d = dict(zip(("calls", "waves", "accepted", "table_rebuilds"), (int(x.value) for x in v)))
+        d.update(zip(("resolve_ms", "waves_ms", "sort_ms", "append_ms"), (float(x) for x in ms)))
+        return d
+
     @property
     def num_events(self):
         return int(self._L.sw_num_events(self._h))

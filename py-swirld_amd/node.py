@@ -233,6 +233,12 @@ class Node:
     # §8f N3) for sync payloads of at least this many events; smaller payloads go through libsodium on
     # the host (one signature costs a GPU thread ~1-2 ms of latency, a CPU core ~60 us).  None = never.
     device_crypto_threshold = 512
+    # Whole sync payloads resolved, ordered, validated and appended on the GPU (sw_ingest_payload: the id index of the
+    # context, csrc/resolve.hip.h) instead of toposort + one is_valid_event / add_event per event on the host, for payloads
+    # of at least this many unknown events.  Only with accept_forks=True (the device call stores forks as the reference
+    # does; dropping them is the host loop's job).  The stored SET is the host loop's; the order events are added in is
+    # (acceptance wave, position in the payload) instead of the toposort's — both topological.  None = never.
+    device_payload_threshold = None
 
     def __init__(self, kp, network, n_nodes, stake, device=0, accept_forks=True):
         self.pk, self.sk = kp
@@ -270,6 +276,8 @@ class Node:
         self._chains = [[] for _ in range(n_nodes)]  # per member: its events in self-parent order (hashes)
         self._pending = []    # (creator, self_parent, other_parent, t, sig) not yet uploaded
         self._uploaded = 0
+        self._dev_ids = 0     # events whose id the device context knows (device_payload_threshold)
+        self._device_payloads = 0
         self._divided = 0
         self._device = device
         self._dev = Hashgraph(n_nodes, [stake[pk] for pk in self._members], coin_period=C, device=device)
@@ -354,6 +362,12 @@ class Node:
 
     def add_event(self, h, ev):
         """Store an event (swirld.py:114-120); it is uploaded with the next divide_rounds."""
+        self._add_event_host(h, ev)
+        sp, op = (self._index[ev.p[0]], self._index[ev.p[1]]) if ev.p else (-1, -1)
+        self._pending.append((self._mindex[ev.c], sp, op, float(ev.t), ev.s))
+
+    def _add_event_host(self, h, ev):
+        """The host side of add_event: every dict and list of this view (the device side is _pending, or a payload call)."""
         self.hg[h] = ev
         if ev.c in self._chain_head and self._chain_head[ev.c] != (ev.p[0] if ev.p else None):
             # a fork of member ev.c: everything of it above the forked self-parent may be on a branch a peer lacks
@@ -365,8 +379,6 @@ class Node:
         self._index[h] = len(self._ids)
         self._ids.append(h)
         self._chains[self._mindex[ev.c]].append(h)
-        sp, op = (self._index[ev.p[0]], self._index[ev.p[1]]) if ev.p else (-1, -1)
-        self._pending.append((self._mindex[ev.c], sp, op, float(ev.t), ev.s))
 
     def _known_heights(self):
         """{member pk -> height of the newest event of that member my head can see}: what a
@@ -384,10 +396,14 @@ class Node:
         reply = crypto.sign_open(self.network[pk](self.pk, request), pk)
         remote_head, remote_hg = loads(reply)
         unknown = remote_hg.keys() - self.hg.keys()
-        new = tuple(toposort(unknown, lambda u: remote_hg[u].p))
         thr = self.device_crypto_threshold
         if not crypto.HAVE_SODIUM:  # stand-in signatures are keyed hashes: the device verifier (real Ed25519) would refuse all of them
             thr = None
+        dthr = self.device_payload_threshold
+        if dthr is not None and self.accept_forks and len(unknown) >= max(dthr, 1):
+            added = self._sync_payload_device(list(unknown), remote_hg, thr)
+            return self._sync_finish(added, remote_head, remote_hg, payload)
+        new = tuple(toposort(unknown, lambda u: remote_hg[u].p))
         pre = self._batch_crypto(new, remote_hg) if thr is not None and len(new) >= thr else {}
         # Only what was actually stored is returned (main() hands it to divide_rounds): the reference
         # returns the rejected ids too and then fails on them (swirld.py:134-146, 326), and references an
@@ -397,6 +413,58 @@ class Node:
             if self.is_valid_event(eid, remote_hg[eid], pre.get(eid)):
                 self.add_event(eid, remote_hg[eid])
                 added.append(eid)
+        return self._sync_finish(added, remote_head, remote_hg, payload)
+
+    def _sync_payload_device(self, eids, remote_hg, crypto_thr):
+        """The unknown events of a sync payload, in any order, through Hashgraph.ingest_payload; returns the ids stored,
+        in the order they were added."""
+        self._flush()
+        if self._dev_ids < len(self._ids):   # events added one by one since the last payload: the context learns their ids
+            self._dev.set_event_ids(self._dev_ids, np.frombuffer(b"".join(self._ids[self._dev_ids:]), np.uint8).reshape(-1, 32))
+            self._dev_ids = len(self._ids)
+        is32 = lambda x: isinstance(x, (bytes, bytearray)) and len(x) == 32
+        eids = [e for e in eids if is32(e)]   # (anything else cannot be the BLAKE2b-256 of an event)
+        K = len(eids)
+        if K == 0:
+            return []
+        pre = self._batch_crypto(eids, remote_hg) if crypto_thr is not None and K >= crypto_thr else None
+        ids = np.frombuffer(b"".join(bytes(e) for e in eids), np.uint8).reshape(K, 32)
+        par = np.zeros((2, K, 32), np.uint8)
+        arity = np.zeros(K, np.uint8)
+        creator = np.full(K, -1, np.int32)
+        ok = np.zeros(K, np.uint8)
+        t = np.zeros(K, np.float64)
+        sig = np.zeros((K, 64), np.uint8)
+        for i, eid in enumerate(eids):
+            ev = remote_hg[eid]
+            try:
+                good = isinstance(ev.p, tuple) and all(is32(p) for p in ev.p) and isinstance(ev.s, (bytes, bytearray)) and len(ev.s) == 64
+                if good:
+                    t[i] = float(ev.t)
+                    sig[i] = np.frombuffer(bytes(ev.s), np.uint8)
+                    arity[i] = min(len(ev.p), 255)
+                    if len(ev.p) == 2:
+                        par[0, i] = np.frombuffer(bytes(ev.p[0]), np.uint8)
+                        par[1, i] = np.frombuffer(bytes(ev.p[1]), np.uint8)
+                    creator[i] = self._mindex.get(ev.c, -1)
+                    sig_ok, hid = pre[eid] if pre is not None else (self._signature_ok(ev), crypto.generichash(dumps(ev)))
+                    ok[i] = bool(sig_ok) and hid == eid
+            except Exception:  # noqa: BLE001  (a malformed event is an invalid event)
+                ok[i] = 0
+        n_before = len(self._ids)
+        out, n_stored = self._dev.ingest_payload(ids, par[0], par[1], arity, creator, ok, t, sig)
+        self._device_payloads += 1
+        added = []
+        for j in np.argsort(out, kind="stable")[K - n_stored:] if n_stored else ():
+            eid = eids[int(j)]
+            assert out[j] == len(self._ids) >= n_before
+            self._add_event_host(eid, remote_hg[eid])
+            added.append(eid)
+        self._uploaded += n_stored
+        self._dev_ids = len(self._ids)
+        return added
+
+    def _sync_finish(self, added, remote_head, remote_hg, payload):
         if remote_head in remote_hg and self.is_valid_event(remote_head, remote_hg[remote_head]):
             h, ev = self.new_event(payload, (self.head, remote_head))
             assert self.is_valid_event(h, ev)
