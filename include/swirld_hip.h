@@ -321,6 +321,60 @@ int sw_sync_diff(sw_ctx* ctx, int64_t head_event, const int32_t* known_height, i
 int sw_get_chain_events(sw_ctx* ctx, int member, int32_t p0, int32_t p1, int32_t* out);
 
 /*
+ * Answering a sync ON THE DEVICE (Node.ask_sync swirld.py:148-161 and the asking half of Node.sync,
+ * swirld.py:125-136; kernels in csrc/gossip.hip.h).  The events sw_sync_diff names leave the answering context as the arrays
+ * sw_ingest_payload_device takes, so that a payload goes from one context's device memory into another's — or into a send
+ * buffer — without a host copy of any event.
+ *
+ * sw_get_known_heights_device   sw_get_known_heights with the answer left in device memory: d_out holds n_members int32 (not
+ *   the padded row: nothing is written behind them) in memory of the context's device (SW_EINVAL otherwise); `user_stream`
+ *   (a hipStream_t or NULL, the null stream) is made to wait for the result.
+ *
+ * sw_export_payload_device   exports exactly the events sw_sync_diff(head_event, known_height) names; *n_out (host) is that
+ *   call's n_events.  ORDER: member-major — member 0's range first — and chain order inside a member: with off[m] the
+ *   exclusive prefix sum of the range lengths, slot s of member m is the event at chain position pos_first[m] + (s - off[m]).
+ *   This order is NOT topological: ordering is the ingest's job.  PER SLOT: d_id32 the event's id; d_sp_id32 / d_op_id32 its
+ *   parents' ids (32 zero bytes each for a root); d_arity (uint8) 2, or 0 for a root; d_creator the dense member index; d_t,
+ *   d_sig64 (either may be NULL: not exported) bit-exact copies of what was appended; d_event (may be NULL) the dense index
+ *   of the event in THIS context.  d_known_height: n_members int32 in device memory, negative = member unknown to the
+ *   asker; NULL = the asker knows nobody.  The heights are the asker's claim: they are compared with stored heights and
+ *   never used as an index.  Every array must lie in memory of the context's device, the three id arrays and d_sig64
+ *   16-byte aligned: SW_EINVAL before anything is launched.
+ *   CAPACITY: `cap` is the number of events the arrays can take.  If the diff is larger the call returns SW_ERANGE with
+ *   *n_out = the number required and writes nothing; cap = 0 with all arrays NULL is how to ask for the size.
+ *   STREAMS: as for sw_export_rows — the context's stream first waits, on the device, for what `user_stream` has enqueued so
+ *   far (the producer of d_known_height), and `user_stream` is then made to wait for the gather: an ingest enqueued on it, or
+ *   given it as its user_stream, reads complete arrays.  The call synchronises once, to read the count.
+ *   NEEDS a complete id index (SW_ENOTSUP otherwise; sw_set_event_ids), the fast path (SW_ENOTSUP on the exact, forked
+ *   path), a divided, resident head (SW_ERANGE); SW_EIO on a poisoned context.  Works with the windowed table wherever
+ *   sw_sync_diff does.  READ-ONLY: no getter and no later call answers differently afterwards (counters.kernel_launches
+ *   moves).
+ * sw_export_payload    the same with every array in HOST memory: gathered into context scratch by the same device code,
+ *   then copied out.
+ *
+ * sw_sync_pull   the reference's sync without the new event (swirld.py:125-136) between two contexts on ONE device: dst
+ *   computes its known heights at dst_head, src computes ranges, count and the gather (into scratch src owns) at src_head,
+ *   dst ingests through the body of sw_ingest_payload_device, its stream ordered behind src's; nothing but the count
+ *   crosses to the host.  *n_sent = the events exported, *n_stored = the events dst stored: its events [count before, count
+ *   before + n_stored), whose ids sw_get_event_ids gives.  Preconditions of both halves; contexts on different devices:
+ *   SW_ENOTSUP; dst == src, or differing member counts: SW_EINVAL (same members and stake are the caller's business).  The
+ *   error message is left in dst.
+ *
+ * sw_get_export_stats   export calls (sw_sync_pull counts for its src) and events exported since sw_create, and — under
+ *   sw_set_profiling — the host time in ms of the most recent call's phases: phase_ms[2] = ranges + count, gather.  Any
+ *   pointer may be NULL.
+ */
+int sw_get_known_heights_device(sw_ctx* ctx, int64_t head_event, int32_t* d_out, void* user_stream);
+int sw_export_payload_device(sw_ctx* ctx, int64_t head_event, const int32_t* d_known_height, int64_t cap,
+                             uint8_t* d_id32, uint8_t* d_sp_id32, uint8_t* d_op_id32, uint8_t* d_arity, int32_t* d_creator,
+                             double* d_t, uint8_t* d_sig64, int32_t* d_event, void* user_stream, int64_t* n_out);
+int sw_export_payload(sw_ctx* ctx, int64_t head_event, const int32_t* known_height, int64_t cap,
+                      uint8_t* id32, uint8_t* sp_id32, uint8_t* op_id32, uint8_t* arity, int32_t* creator,
+                      double* t, uint8_t* sig64, int32_t* event, int64_t* n_out);
+int sw_sync_pull(sw_ctx* dst, int64_t dst_head, sw_ctx* src, int64_t src_head, int64_t* n_sent, int64_t* n_stored);
+int sw_get_export_stats(sw_ctx* ctx, int64_t* calls, int64_t* events, double* phase_ms);
+
+/*
  * Ingest-side crypto in batches — what Node.is_valid_event spends its time in
  * (swirld.py:99-103), stateless, one GPU thread per message; message i = msgs[msg_off[i] .. msg_off[i+1]).
  * sw_crypto_verify_batch: ok[i] = 1 iff libsodium's crypto_sign_verify_detached(sig_i, msg_i, pk_i)

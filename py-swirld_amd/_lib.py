@@ -79,6 +79,11 @@ SIGNATURES = {
     "sw_get_known_heights": (C.c_int, [_P, C.c_int64, _P]),
     "sw_sync_diff": (C.c_int, [_P, C.c_int64, _P, _P, _P, C.POINTER(C.c_int64)]),
     "sw_get_chain_events": (C.c_int, [_P, C.c_int, C.c_int32, C.c_int32, _P]),
+    "sw_get_known_heights_device": (C.c_int, [_P, C.c_int64, _P, _P]),
+    "sw_export_payload_device": (C.c_int, [_P, C.c_int64, _P, C.c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.POINTER(C.c_int64)]),
+    "sw_export_payload": (C.c_int, [_P, C.c_int64, _P, C.c_int64, _P, _P, _P, _P, _P, _P, _P, _P, C.POINTER(C.c_int64)]),
+    "sw_sync_pull": (C.c_int, [_P, C.c_int64, _P, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "sw_get_export_stats": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), _P]),
     "sw_crypto_verify_batch": (C.c_int, [C.c_int, C.c_int64, _P, _P, _P, _P, _P]),
     "sw_crypto_hash_batch": (C.c_int, [C.c_int, C.c_int64, _P, _P, _P]),
     "sw_num_ordered": (C.c_int, [_P, C.POINTER(C.c_int64)]),

@@ -25,6 +25,7 @@
 #include "exact.hip.h"
 #include "ingest.hip.h"
 #include "resolve.hip.h"
+#include "gossip.hip.h"
 
 namespace {
 
@@ -168,6 +169,12 @@ struct sw_ctx {
     int32_t* h_plcnt = nullptr;   // pinned: per-wave counts of one batch of waves
     int64_t pl_calls = 0, pl_waves = 0, pl_accepted = 0, pl_rebuilds = 0;   // sw_get_payload_stats (waves, accepted: the last call's)
     double pl_ms[4] = {0, 0, 0, 0};   // ... host time of its phases under sw_set_profiling: resolve, waves, sort + gather, append + commit
+    // answering a sync on the device (sw_export_payload[_device], sw_sync_pull; gossip.hip.h)
+    DBuf<int32_t> d_xp;           // [2: the total, 64 bits][npad + 1: offsets of the members' ranges][npad: chain pool base per member]
+    DBuf<unsigned char> d_xp_out; // the exported arrays of the host-array form and of sw_sync_pull
+    int64_t xp_calls = 0, xp_events = 0;   // sw_get_export_stats
+    double xp_ms[2] = {0, 0};     // ... host time of the most recent call's phases under sw_set_profiling: ranges + count, gather
+    int export_lanes = 16;        // SW_EXPORT_LANES (measurement knob, read at sw_create): lanes of a wave that share one output slot — 4, 8 or 16
 
     // device: events
     DBuf<int32_t> d_cr, d_sp, d_op, d_ht, d_seq, d_round, d_L, d_chain_ev;
@@ -2704,6 +2711,7 @@ int sw_create(int n_members, const uint64_t* stake, int coin_period, int device,
         if (hipMalloc(&c->d_flow_dbg, 8 * sizeof(u64)) != hipSuccess) c->d_flow_dbg = nullptr;
         else (void)hipMemset(c->d_flow_dbg, 0, 8 * sizeof(u64));
     }
+    if (const char* e_ = getenv("SW_EXPORT_LANES")) { const int g = atoi(e_); if (g == 4 || g == 8) c->export_lanes = g; }
     if (getenv("SW_DEBUG_CLOCKS")) {  // diagnostics: phase stamps of the round-loop kernels
         c->dbg_minor = atoi(getenv("SW_DEBUG_CLOCKS")) >= 2 ? 0 : 1;
         if (atoi(getenv("SW_DEBUG_CLOCKS")) == 3) {
@@ -2890,6 +2898,7 @@ int sw_destroy(sw_ctx* c) {
     if (c->ev_ht) (void)hipEventDestroy(c->ev_ht);
     dfree(c->d_ing_tab); dfree(c->d_ing_hist); dfree(c->d_ht_stat);
     dfree(c->d_id); dfree(c->d_idtab); dfree(c->d_idflag); dfree(c->d_pl); dfree(c->d_pl_in);
+    dfree(c->d_xp); dfree(c->d_xp_out);
     if (c->h_plcnt) (void)hipHostFree(c->h_plcnt);
     if (c->ev_aux_done) (void)hipEventDestroy(c->ev_aux_done);
     if (c->ev_cs_done) (void)hipEventDestroy(c->ev_cs_done);
@@ -4705,6 +4714,250 @@ int sw_get_chain_events(sw_ctx* c, int member, int32_t p0, int32_t p1, int32_t* 
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipMemcpyAsync(out, c->d_chain_ev.p + c->chain_start_h[member] + p0, (size_t)(p1 - p0) * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
+    return SW_OK;
+}
+
+// ---- answering a sync on the device (gossip.hip.h): the diff of sw_sync_diff as the arrays a payload call takes ---------
+}  // extern "C"
+namespace {
+
+struct ExportArrays { uint8_t *id, *sp_id, *op_id, *arity; int32_t* creator; double* t; uint8_t* sig; int32_t* event; };
+
+// what both forms and sw_sync_pull ask of the answering context
+int export_pre(sw_ctx* c, int64_t head, const char* what) {
+    if (c->poisoned) return fail(c, SW_EIO, "context unusable after an earlier device failure");
+    if (c->exact) return fail(c, SW_ENOTSUP, "%s is not available on the exact (forked-hashgraph) path", what);
+    if (c->n_ids != c->N)
+        return fail(c, SW_ENOTSUP, "%s: %lld of the %lld stored events have no id (sw_set_event_ids first)", what, (long long)(c->N - c->n_ids), (long long)c->N);
+    if (head < c->first_resident || head >= c->divided) return fail(c, SW_ERANGE, "%s: head %lld is not a divided, resident event", what, (long long)head);
+    return SW_OK;
+}
+
+// d_ht complete on the device.  sw_sync_diff and sw_get_known_heights call ensure_dag_h for this, which also fills the host
+// mirrors of parents and heights; nothing here reads those mirrors, so the download is skipped when the device already holds
+// every height: events appended from device memory have theirs in d_ht once heights_ready has waited for the kernel
+// (ht_dev_upto), and only a bulk HOST append leaves heights to ensure_dag_h's loop — the test append_device_body makes.
+int heights_on_device(sw_ctx* c) {
+    CHK(heights_ready(c));
+    if ((int64_t)c->sp.size() < c->N && c->ht_dev_upto < c->N) CHK(ensure_dag_h(c));
+    return SW_OK;
+}
+
+// k_sync_diff, the offsets and the count, on the context's stream; ONE synchronisation, for the count.  `known` (n int32,
+// may be NULL: nobody known) is copied with `kind`; it is compared with heights and never used as an index.
+int export_ranges(sw_ctx* c, int64_t head, const int32_t* known, hipMemcpyKind kind, int64_t* total) {
+    CHK(heights_on_device(c));
+    const int np = c->npad, n = c->n;
+    CHK(dgrow(c, c->d_q, (size_t)3 * np, 0));
+    CHK(dgrow(c, c->d_xp, (size_t)2 * np + 8, 0));
+    if (c->payload_pending) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_payload, 0));   // timestamps / signatures of a bulk host append
+    HIPCHK(c, hipMemsetAsync(c->d_q.p, 0xff, (size_t)np * sizeof(int32_t), c->stream));
+    if (known) HIPCHK(c, hipMemcpyAsync(c->d_q.p, known, (size_t)n * sizeof(int32_t), kind, c->stream));
+    hipLaunchKernelGGL(k_sync_diff, dim3(1), dim3(np), 0, c->stream, (const int*)c->d_L.p, (const int*)c->d_ht.p, (const int*)c->d_seq.p,
+                       (const int*)c->d_cr.p, (const int*)c->d_chain_start.p, (const int*)c->d_chain_ev.p, (const int*)c->d_q.p,
+                       (int)head, np, c->d_q.p + np, c->d_q.p + 2 * np);
+    hipLaunchKernelGGL(gsp::k_export_offsets, dim3(1), dim3(gsp::SCAN_THREADS), 0, c->stream, (const int*)(c->d_q.p + np), (const int*)(c->d_q.p + 2 * np),
+                       (const int*)c->d_chain_start.p, n, c->d_xp.p + 2, c->d_xp.p + 2 + np + 1, (long long*)c->d_xp.p);
+    c->ctr.kernel_launches += 2;
+    HIPCHK(c, hipGetLastError());
+    long long tot = 0;
+    HIPCHK(c, hipMemcpyAsync(&tot, c->d_xp.p, sizeof tot, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (tot < 1 || tot > c->N) return fail(c, SW_EIO, "export: the ranges hold %lld events of %lld (internal error)", tot, (long long)c->N);
+    *total = tot;
+    return SW_OK;
+}
+
+// the gather of `total` slots behind export_ranges, on the context's stream (asynchronous)
+int export_gather(sw_ctx* c, int64_t total, const ExportArrays& o) {
+    const int np = c->npad;
+    gsp::ExportIn in{c->d_xp.p + 2, c->d_xp.p + 2 + np + 1, c->d_chain_ev.p, c->d_sp.p, c->d_op.p, c->d_id.p, c->d_sig.p, (const unsigned long long*)c->d_t.p};
+    gsp::ExportOut out{o.id, o.sp_id, o.op_id, o.arity, o.creator, (unsigned long long*)o.t, o.sig, o.event};
+    const int G = c->export_lanes;
+    const size_t lds = (size_t)(2 * c->n + 1) * sizeof(int);   // off[n + 1] | base[n]
+    const dim3 grid((unsigned)std::min<int64_t>(2048, (total * G + gsp::GATHER_THREADS - 1) / gsp::GATHER_THREADS)), block(gsp::GATHER_THREADS);
+    if (G == 4) hipLaunchKernelGGL(gsp::k_export_gather<4>, grid, block, lds, c->stream, in, out, c->n, (int)total);
+    else if (G == 8) hipLaunchKernelGGL(gsp::k_export_gather<8>, grid, block, lds, c->stream, in, out, c->n, (int)total);
+    else hipLaunchKernelGGL(gsp::k_export_gather<16>, grid, block, lds, c->stream, in, out, c->n, (int)total);
+    c->ctr.kernel_launches++;
+    HIPCHK(c, hipGetLastError());
+    return SW_OK;
+}
+
+// the exported arrays for `total` events inside d_xp_out
+int export_scratch(sw_ctx* c, int64_t total, bool with_t, bool with_sig, bool with_event, ExportArrays* o) {
+    const size_t k = (size_t)total;
+    Carve cv;
+    const size_t o_id = cv.take(k * 32), o_sp = cv.take(k * 32), o_op = cv.take(k * 32), o_ar = cv.take(k), o_cr = cv.take(k * 4);
+    const size_t o_t = cv.take(with_t ? k * 8 : 0), o_sig = cv.take(with_sig ? k * 64 : 0), o_ev = cv.take(with_event ? k * 4 : 0);
+    CHK(dgrow(c, c->d_xp_out, cv.off, 0));
+    unsigned char* B = c->d_xp_out.p;
+    *o = ExportArrays{B + o_id, B + o_sp, B + o_op, B + o_ar, (int32_t*)(B + o_cr), with_t ? (double*)(B + o_t) : nullptr,
+                      with_sig ? B + o_sig : nullptr, with_event ? (int32_t*)(B + o_ev) : nullptr};
+    return SW_OK;
+}
+
+}  // namespace
+extern "C" {
+
+int sw_get_known_heights_device(sw_ctx* c, int64_t head_event, int32_t* d_out, void* user_stream) {
+    if (!c || !d_out) return SW_EINVAL;
+    if (head_event < c->first_resident || head_event >= c->divided) return fail(c, SW_ERANGE, "head %lld is not a divided, resident event", (long long)head_event);
+    HIPCHK(c, hipSetDevice(c->device));
+    if (!on_ctx_device(c, d_out, (size_t)c->n * sizeof(int32_t)))
+        return fail(c, SW_EINVAL, "sw_get_known_heights_device: the output must lie in memory of device %d (a host pointer, or another device's)", c->device);
+    CHK(heights_on_device(c));
+    const int np = c->npad;
+    CHK(dgrow(c, c->d_q, (size_t)3 * np, 0));
+    if (!c->ev_user) HIPCHK(c, hipEventCreateWithFlags(&c->ev_user, hipEventDisableTiming));
+    hipStream_t us = (hipStream_t)user_stream;
+    HIPCHK(c, hipEventRecord(c->ev_user, us));            // (the output may still be read by what the caller enqueued earlier)
+    HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_user, 0));
+    hipLaunchKernelGGL(k_known_heights, dim3(1), dim3(np), 0, c->stream, (const int*)c->d_L.p, (const int*)c->d_ht.p, (int)head_event, np, c->d_q.p);
+    c->ctr.kernel_launches++;
+    HIPCHK(c, hipGetLastError());
+    // n entries, not npad: the caller's array ends there
+    HIPCHK(c, hipMemcpyAsync(d_out, c->d_q.p, (size_t)c->n * sizeof(int32_t), hipMemcpyDeviceToDevice, c->stream));
+    HIPCHK(c, hipEventRecord(c->ev_user, c->stream));
+    HIPCHK(c, hipStreamWaitEvent(us, c->ev_user, 0));
+    return SW_OK;
+}
+
+int sw_export_payload_device(sw_ctx* c, int64_t head_event, const int32_t* d_known_height, int64_t cap, uint8_t* d_id32, uint8_t* d_sp_id32,
+                             uint8_t* d_op_id32, uint8_t* d_arity, int32_t* d_creator, double* d_t, uint8_t* d_sig64, int32_t* d_event,
+                             void* user_stream, int64_t* n_out) {
+    if (!c) return SW_EINVAL;
+    if (!n_out) return fail(c, SW_EINVAL, "sw_export_payload_device: n_out is NULL");
+    *n_out = 0;
+    CHK(export_pre(c, head_event, "sw_export_payload_device"));
+    if (cap < 0 || (cap > 0 && (!d_id32 || !d_sp_id32 || !d_op_id32 || !d_arity || !d_creator)))
+        return fail(c, SW_EINVAL, "sw_export_payload_device: NULL output arrays (capacity %lld)", (long long)cap);
+    if (((uintptr_t)d_id32 | (uintptr_t)d_sp_id32 | (uintptr_t)d_op_id32 | (uintptr_t)d_sig64) & 15)
+        return fail(c, SW_EINVAL, "sw_export_payload_device: the id arrays and the signatures must be 16-byte aligned");
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t k = (size_t)cap;
+    bool on = !d_known_height || on_ctx_device(c, d_known_height, (size_t)c->n * sizeof(int32_t));
+    if (cap > 0)
+        on = on && on_ctx_device(c, d_id32, k * 32) && on_ctx_device(c, d_sp_id32, k * 32) && on_ctx_device(c, d_op_id32, k * 32) &&
+             on_ctx_device(c, d_arity, k) && on_ctx_device(c, d_creator, k * 4) && (!d_t || on_ctx_device(c, d_t, k * 8)) &&
+             (!d_sig64 || on_ctx_device(c, d_sig64, k * 64)) && (!d_event || on_ctx_device(c, d_event, k * 4));
+    if (!on) return fail(c, SW_EINVAL, "sw_export_payload_device: every array must lie in memory of device %d (a host pointer, or another device's)", c->device);
+    const bool prof = c->profiling;
+    auto t0 = std::chrono::steady_clock::now();
+    if (!c->ev_user) HIPCHK(c, hipEventCreateWithFlags(&c->ev_user, hipEventDisableTiming));
+    hipStream_t us = (hipStream_t)user_stream;
+    HIPCHK(c, hipEventRecord(c->ev_user, us));            // the producer of d_known_height; earlier readers of the output arrays
+    HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_user, 0));
+    int64_t total = 0;
+    CHK(export_ranges(c, head_event, d_known_height, hipMemcpyDeviceToDevice, &total));
+    *n_out = total;
+    c->xp_ms[0] = prof ? ms_since(t0) : 0;
+    c->xp_ms[1] = 0;
+    if (total > cap) return fail(c, SW_ERANGE, "sw_export_payload_device: %lld events to export, capacity %lld (nothing written)", (long long)total, (long long)cap);
+    t0 = std::chrono::steady_clock::now();
+    CHK(export_gather(c, total, ExportArrays{d_id32, d_sp_id32, d_op_id32, d_arity, d_creator, d_t, d_sig64, d_event}));
+    HIPCHK(c, hipEventRecord(c->ev_user, c->stream));     // whatever the caller enqueues next reads complete arrays
+    HIPCHK(c, hipStreamWaitEvent(us, c->ev_user, 0));
+    if (prof) { HIPCHK(c, hipStreamSynchronize(c->stream)); c->xp_ms[1] = ms_since(t0); }
+    c->xp_calls++;
+    c->xp_events += total;
+    return SW_OK;
+}
+
+int sw_export_payload(sw_ctx* c, int64_t head_event, const int32_t* known_height, int64_t cap, uint8_t* id32, uint8_t* sp_id32, uint8_t* op_id32,
+                      uint8_t* arity, int32_t* creator, double* t, uint8_t* sig64, int32_t* event, int64_t* n_out) {
+    if (!c) return SW_EINVAL;
+    if (!n_out) return fail(c, SW_EINVAL, "sw_export_payload: n_out is NULL");
+    *n_out = 0;
+    CHK(export_pre(c, head_event, "sw_export_payload"));
+    if (cap < 0 || (cap > 0 && (!id32 || !sp_id32 || !op_id32 || !arity || !creator)))
+        return fail(c, SW_EINVAL, "sw_export_payload: NULL output arrays (capacity %lld)", (long long)cap);
+    HIPCHK(c, hipSetDevice(c->device));
+    const bool prof = c->profiling;
+    auto t0 = std::chrono::steady_clock::now();
+    int64_t total = 0;
+    CHK(export_ranges(c, head_event, known_height, hipMemcpyHostToDevice, &total));
+    *n_out = total;
+    c->xp_ms[0] = prof ? ms_since(t0) : 0;
+    c->xp_ms[1] = 0;
+    if (total > cap) return fail(c, SW_ERANGE, "sw_export_payload: %lld events to export, capacity %lld (nothing written)", (long long)total, (long long)cap);
+    t0 = std::chrono::steady_clock::now();
+    ExportArrays d{};
+    CHK(export_scratch(c, total, t != nullptr, sig64 != nullptr, event != nullptr, &d));
+    CHK(export_gather(c, total, d));
+    const size_t k = (size_t)total;
+    HIPCHK(c, hipMemcpyAsync(id32, d.id, k * 32, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(sp_id32, d.sp_id, k * 32, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(op_id32, d.op_id, k * 32, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(arity, d.arity, k, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(creator, d.creator, k * 4, hipMemcpyDeviceToHost, c->stream));
+    if (t) HIPCHK(c, hipMemcpyAsync(t, d.t, k * 8, hipMemcpyDeviceToHost, c->stream));
+    if (sig64) HIPCHK(c, hipMemcpyAsync(sig64, d.sig, k * 64, hipMemcpyDeviceToHost, c->stream));
+    if (event) HIPCHK(c, hipMemcpyAsync(event, d.event, k * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (prof) c->xp_ms[1] = ms_since(t0);
+    c->xp_calls++;
+    c->xp_events += total;
+    return SW_OK;
+}
+
+int sw_sync_pull(sw_ctx* dst, int64_t dst_head, sw_ctx* src, int64_t src_head, int64_t* n_sent, int64_t* n_stored) {
+    if (!dst || !src) return SW_EINVAL;
+    if (n_sent) *n_sent = 0;
+    if (n_stored) *n_stored = 0;
+    if (dst == src) return fail(dst, SW_EINVAL, "sw_sync_pull: a context cannot pull from itself");
+    if (dst->device != src->device) return fail(dst, SW_ENOTSUP, "sw_sync_pull: the contexts live on devices %d and %d (same device only)", dst->device, src->device);
+    if (dst->n != src->n) return fail(dst, SW_EINVAL, "sw_sync_pull: %d members here, %d at the peer", dst->n, src->n);
+    if (dst->poisoned) return fail(dst, SW_EIO, "context unusable after an earlier device failure");
+    if (dst->n_ids != dst->N)
+        return fail(dst, SW_ENOTSUP, "sw_sync_pull: %lld of the %lld stored events have no id (sw_set_event_ids first)", (long long)(dst->N - dst->n_ids), (long long)dst->N);
+    if (dst_head < dst->first_resident || dst_head >= dst->divided) return fail(dst, SW_ERANGE, "sw_sync_pull: head %lld is not a divided, resident event", (long long)dst_head);
+    if (const int rc = export_pre(src, src_head, "sw_sync_pull (peer)"); rc != SW_OK) { dst->err = src->err; return rc; }
+    HIPCHK(dst, hipSetDevice(dst->device));
+    // ---- 1. what dst knows at its head (swirld.py:125-126), left in its own scratch; src's stream waits for it
+    CHK(heights_on_device(dst));
+    const int np = dst->npad;
+    CHK(dgrow(dst, dst->d_q, (size_t)3 * np, 0));
+    if (!dst->ev_user) HIPCHK(dst, hipEventCreateWithFlags(&dst->ev_user, hipEventDisableTiming));
+    hipLaunchKernelGGL(k_known_heights, dim3(1), dim3(np), 0, dst->stream, (const int*)dst->d_L.p, (const int*)dst->d_ht.p, (int)dst_head, np, dst->d_q.p);
+    dst->ctr.kernel_launches++;
+    HIPCHK(dst, hipGetLastError());
+    HIPCHK(dst, hipEventRecord(dst->ev_user, dst->stream));
+    HIPCHK(dst, hipStreamWaitEvent(src->stream, dst->ev_user, 0));
+    // ---- 2. src: ranges, count (its one synchronisation: dst's heights have been consumed by then), gather into its own scratch
+    const bool prof = src->profiling;
+    auto t0 = std::chrono::steady_clock::now();
+    int64_t total = 0;
+    if (const int rc = export_ranges(src, src_head, dst->d_q.p, hipMemcpyDeviceToDevice, &total); rc != SW_OK) { dst->err = src->err; return rc; }
+    src->xp_ms[0] = prof ? ms_since(t0) : 0;
+    src->xp_ms[1] = 0;
+    if (total > 0x3fffffffll || dst->N + total > 0x7ffffff0ll) return fail(dst, SW_ERANGE, "sw_sync_pull: more than 2^31 events");
+    t0 = std::chrono::steady_clock::now();
+    ExportArrays d{};
+    int rc = export_scratch(src, total, true, true, false, &d);
+    if (rc == SW_OK) rc = export_gather(src, total, d);
+    if (rc != SW_OK) { dst->err = src->err; return rc; }
+    if (prof) { HIPCHK(src, hipStreamSynchronize(src->stream)); src->xp_ms[1] = ms_since(t0); }
+    src->xp_calls++;
+    src->xp_events += total;
+    if (n_sent) *n_sent = total;
+    // ---- 3. dst ingests (Node.sync's loop, swirld.py:130-136), its stream ordered behind src's
+    CHK(dgrow(dst, dst->d_pl_in, (size_t)total * sizeof(int32_t), 0));
+    int64_t stored = 0;
+    rc = payload_core(dst, total, d.id, d.sp_id, d.op_id, d.arity, d.creator, nullptr, d.t, d.sig, src->stream, (int32_t*)dst->d_pl_in.p, &stored);
+    // src's scratch is free again only once dst has read it
+    const hipError_t drained = hipStreamSynchronize(dst->stream);
+    if (rc != SW_OK) return rc;
+    HIPCHK(dst, drained);
+    if (n_stored) *n_stored = stored;
+    return SW_OK;
+}
+
+int sw_get_export_stats(sw_ctx* c, int64_t* calls, int64_t* events, double* phase_ms) {
+    if (!c) return SW_EINVAL;
+    if (calls) *calls = c->xp_calls;
+    if (events) *events = c->xp_events;
+    if (phase_ms) for (int i = 0; i < 2; ++i) phase_ms[i] = c->xp_ms[i];
     return SW_OK;
 }
 

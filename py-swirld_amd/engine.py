@@ -369,6 +369,72 @@ class Hashgraph:
         self._chk(self._L.sw_get_chain_events(self._h, int(member), int(p0), int(p1), _p(out)))
         return out
 
+    # ---- answering a sync on the device (Node.ask_sync, swirld.py:148-161; csrc/gossip.hip.h) ----
+    def known_heights_device(self, head, out, stream=0):
+        """known_heights(head) left in DEVICE memory: `out` holds n int32 (an address, or an object with data_ptr() /
+        __cuda_array_interface__); `stream` (a raw hipStream_t) is made to wait for it.  Returns `out`."""
+        ptr, ln = _dev_ptr(out)
+        if ln is not None and ln < self.n:
+            raise ValueError("out holds %d entries, expected %d" % (ln, self.n))
+        self._chk(self._L.sw_get_known_heights_device(self._h, int(head), C.c_void_p(ptr), C.c_void_p(int(stream))))
+        return out
+
+    def export_payload_device(self, head, known, cap, ids, sp_ids, op_ids, arity, creator, t=None, sig=None, event=None, stream=0):
+        """The events sync_diff(head, known) names, written to DEVICE arrays in the layout ingest_payload_device takes
+        (member-major, chain order inside a member; include/swirld_hip.h).  `known`: n int32 in device memory, or None (the
+        asker knows nobody).  `cap`: events the arrays can take; a larger diff raises SwirldHipError with code -34 and writes
+        nothing (export_size gives the size).  The id arrays and `sig` 16-byte aligned.  `stream` has the producer of `known`
+        enqueued and is made to wait for the arrays.  Returns the number of events exported."""
+        ptrs = [_dev_ptr(a)[0] for a in (known, ids, sp_ids, op_ids, arity, creator, t, sig, event)]
+        a = [C.c_void_p(q) if q else None for q in ptrs]
+        n_out = C.c_int64()
+        self._chk(self._L.sw_export_payload_device(self._h, int(head), a[0], int(cap), *a[1:], C.c_void_p(int(stream)), C.byref(n_out)))
+        return int(n_out.value)
+
+    def export_size(self, head, known=None, stream=0):
+        """Number of events export_payload_device(head, known, ...) would write (`known` in device memory, or None)."""
+        kp = _dev_ptr(known)[0]
+        n_out = C.c_int64()
+        rc = self._L.sw_export_payload_device(self._h, int(head), C.c_void_p(kp) if kp else None, 0, *([None] * 8),
+                                              C.c_void_p(int(stream)), C.byref(n_out))
+        if rc != -34:      # (a diff is never empty — the head is always sent — so the size query answers SW_ERANGE)
+            self._chk(rc)
+        return int(n_out.value)
+
+    def export_payload(self, head, known=None):
+        """The same into fresh numpy arrays: a dict with ids, sp_ids, op_ids (K x 32 uint8), arity (uint8), creator (int32),
+        t (float64), sig (K x 64 uint8) and event (int32, the dense indices here).  `known`: n heights (host), None = nobody."""
+        kn = None if known is None else np.ascontiguousarray(known, np.int32)
+        if kn is not None and kn.shape != (self.n,):
+            raise ValueError("known must have one height per member")
+        n_out = C.c_int64()
+        rc = self._L.sw_export_payload(self._h, int(head), _p(kn), 0, *([None] * 8), C.byref(n_out))
+        if rc != -34:
+            self._chk(rc)
+        K = int(n_out.value)
+        d = dict(ids=np.empty((K, 32), np.uint8), sp_ids=np.empty((K, 32), np.uint8), op_ids=np.empty((K, 32), np.uint8),
+                 arity=np.empty(K, np.uint8), creator=np.empty(K, np.int32), t=np.empty(K, np.float64),
+                 sig=np.empty((K, 64), np.uint8), event=np.empty(K, np.int32))
+        self._chk(self._L.sw_export_payload(self._h, int(head), _p(kn), K, *[_p(d[k]) for k in ("ids", "sp_ids", "op_ids", "arity", "creator", "t", "sig", "event")],
+                                            C.byref(n_out)))
+        return d
+
+    def pull_from(self, peer, peer_head, my_head):
+        """Node.sync without the new event (swirld.py:125-136) against `peer`, a Hashgraph on the same device: my known
+        heights at `my_head` -> the peer's diff at `peer_head` -> my ingest, all in device memory.  Returns (n_sent,
+        n_stored); my new events are the last n_stored ones, their ids event_ids(num_events - n_stored)."""
+        a, b = C.c_int64(), C.c_int64()
+        self._chk(self._L.sw_sync_pull(self._h, int(my_head), peer._h, int(peer_head), C.byref(a), C.byref(b)))
+        return int(a.value), int(b.value)
+
+    def export_stats(self):
+        """Export calls and events exported since the context was created, and (under set_profiling) the host
+        milliseconds of the most recent call's phases: ranges + count, gather."""
+        v = [C.c_int64() for _ in range(2)]
+        ms = (C.c_double * 2)()
+        self._chk(self._L.sw_get_export_stats(self._h, *[C.byref(x) for x in v], ms))
+        return dict(calls=int(v[0].value), events=int(v[1].value), ranges_ms=float(ms[0]), gather_ms=float(ms[1]))
+
     def transactions(self):
         n = C.c_int64()
         self._chk(self._L.sw_num_ordered(self._h, C.byref(n)))
