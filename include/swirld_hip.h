@@ -375,6 +375,47 @@ int sw_sync_pull(sw_ctx* dst, int64_t dst_head, sw_ctx* src, int64_t src_head, i
 int sw_get_export_stats(sw_ctx* ctx, int64_t* calls, int64_t* events, double* phase_ms);
 
 /*
+ * What find_order decides per event, kept (Node.find_order swirld.py:283-309; kernels in csrc/consensus.hip.h).  The
+ * reference computes, for every event x it orders, the ROUND RECEIVED r (swirld.py:283: the first decided round whose famous
+ * witnesses all see x) and the CONSENSUS TIMESTAMP ts[x] (swirld.py:305: .5 * (first + second) of the middle of the sorted
+ * times at which the creators of those witnesses first saw x), sorts by them (swirld.py:306) and drops them: its Node keeps
+ * neither.  Here every sw_find_order call on the fast path leaves both in per-event tables on the device, and its part of
+ * the order in a device copy of `transactions`; sw_rewind / sw_reset empty them with the order.
+ *
+ * sw_get_round_received   swirld.py:283-309: out[i] = round received of event first + i, -1 = not ordered yet.
+ * sw_get_consensus_time   swirld.py:283-309: out[i] = consensus timestamp of event first + i, bit for bit the double
+ *   swirld.py:305 computes; a quiet NaN = not ordered yet.  Both: [first, first + K) inside [0, sw_num_events), SW_ERANGE
+ *   otherwise; out NULL or K = 0: nothing to do.  One small kernel into context scratch and one copy back.
+ *
+ * sw_export_ordered_device   swirld.py:283-309 as a stream: positions [first, first + K) of the order (the indices of
+ *   sw_get_transactions), per position p the dense index of the event (d_event), its id (d_id32, 32 B), its creator's member
+ *   index (d_creator), its round received (d_round_received) and its consensus timestamp (d_time) — non-decreasing in
+ *   (round received, timestamp) along p, as swirld.py:306-309 appends them.  Every array may be NULL: not wanted.
+ *   [first, first + K) inside [0, sw_num_ordered): SW_ERANGE otherwise, nothing written.  d_id32 non-NULL NEEDS a complete
+ *   id index (SW_ENOTSUP otherwise; sw_set_event_ids) and 16-byte alignment (SW_EINVAL); every array must lie in memory of
+ *   the context's device (SW_EINVAL before anything is launched).
+ *   STREAMS: as for sw_export_payload_device — the context's stream first waits, on the device, for what `user_stream` (a
+ *   hipStream_t or NULL, the null stream) has enqueued so far, and `user_stream` is then made to wait for the gather: what
+ *   the caller enqueues on it next reads complete arrays.  No host synchronisation.
+ * sw_export_ordered   swirld.py:283-309, the same with every array in HOST memory: gathered into context scratch by the same
+ *   device code, then copied out.
+ *   All four: the fast path only (SW_ENOTSUP on the exact, forked path); SW_EIO on a poisoned context; SW_EINVAL for a NULL
+ *   context.  READ-ONLY: no getter and no later call answers differently afterwards (counters.kernel_launches and the
+ *   statistics below move).
+ *
+ * sw_get_consensus_stats   swirld.py:283-309 has no counterpart: sw_find_order calls that recorded events and the events
+ *   they recorded, export calls (both forms) and the positions they exported, since sw_create.  Any pointer may be NULL.
+ */
+int sw_get_round_received(sw_ctx* ctx, int64_t first, int64_t K, int32_t* out);
+int sw_get_consensus_time(sw_ctx* ctx, int64_t first, int64_t K, double* out);
+int sw_export_ordered_device(sw_ctx* ctx, int64_t first, int64_t K, int32_t* d_event, uint8_t* d_id32, int32_t* d_creator,
+                             int32_t* d_round_received, double* d_time, void* user_stream);
+int sw_export_ordered(sw_ctx* ctx, int64_t first, int64_t K, int32_t* event, uint8_t* id32, int32_t* creator,
+                      int32_t* round_received, double* time);
+int sw_get_consensus_stats(sw_ctx* ctx, int64_t* record_calls, int64_t* recorded_events, int64_t* export_calls,
+                           int64_t* exported_events);
+
+/*
  * Ingest-side crypto in batches — what Node.is_valid_event spends its time in
  * (swirld.py:99-103), stateless, one GPU thread per message; message i = msgs[msg_off[i] .. msg_off[i+1]).
  * sw_crypto_verify_batch: ok[i] = 1 iff libsodium's crypto_sign_verify_detached(sig_i, msg_i, pk_i)

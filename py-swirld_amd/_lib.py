@@ -84,6 +84,11 @@ SIGNATURES = {
     "sw_export_payload": (C.c_int, [_P, C.c_int64, _P, C.c_int64, _P, _P, _P, _P, _P, _P, _P, _P, C.POINTER(C.c_int64)]),
     "sw_sync_pull": (C.c_int, [_P, C.c_int64, _P, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "sw_get_export_stats": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), _P]),
+    "sw_get_round_received": (C.c_int, [_P, C.c_int64, C.c_int64, _P]),
+    "sw_get_consensus_time": (C.c_int, [_P, C.c_int64, C.c_int64, _P]),
+    "sw_export_ordered_device": (C.c_int, [_P, C.c_int64, C.c_int64, _P, _P, _P, _P, _P, _P]),
+    "sw_export_ordered": (C.c_int, [_P, C.c_int64, C.c_int64, _P, _P, _P, _P, _P]),
+    "sw_get_consensus_stats": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "sw_crypto_verify_batch": (C.c_int, [C.c_int, C.c_int64, _P, _P, _P, _P, _P]),
     "sw_crypto_hash_batch": (C.c_int, [C.c_int, C.c_int64, _P, _P, _P]),
     "sw_num_ordered": (C.c_int, [_P, C.POINTER(C.c_int64)]),

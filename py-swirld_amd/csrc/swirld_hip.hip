@@ -26,6 +26,7 @@
 #include "ingest.hip.h"
 #include "resolve.hip.h"
 #include "gossip.hip.h"
+#include "consensus.hip.h"
 
 namespace {
 
@@ -175,6 +176,15 @@ struct sw_ctx {
     int64_t xp_calls = 0, xp_events = 0;   // sw_get_export_stats
     double xp_ms[2] = {0, 0};     // ... host time of the most recent call's phases under sw_set_profiling: ranges + count, gather
     int export_lanes = 16;        // SW_EXPORT_LANES (measurement knob, read at sw_create): lanes of a wave that share one output slot — 4, 8 or 16
+    // what find_order decided per event, kept (sw_get_round_received, sw_get_consensus_time, sw_export_ordered[_device];
+    // consensus.hip.h): allocated by the first find_order call that orders something
+    DBuf<int32_t> d_rr;           // per event: round received (swirld.py:283); entries of events that are not ordered are unspecified
+    DBuf<double> d_cts;           // per event: consensus timestamp (swirld.py:305); likewise
+    DBuf<int32_t> d_tx;           // device copy of `transactions` ...
+    int64_t tx_len = 0;           // ... and its length (0 again after sw_rewind / sw_reset)
+    DBuf<int32_t> d_cs_ordpos;    // npad: the ordered prefixes as of now, uploaded by a getter (d_ordpos holds those at the head of the last call)
+    DBuf<unsigned char> d_cs_out; // the arrays of the host-array forms
+    int64_t cs_record_calls = 0, cs_recorded = 0, cs_export_calls = 0, cs_exported = 0;   // sw_get_consensus_stats
 
     // device: events
     DBuf<int32_t> d_cr, d_sp, d_op, d_ht, d_seq, d_round, d_L, d_chain_ev;
@@ -2247,6 +2257,47 @@ int ensure_order_stage(sw_ctx* c, size_t ints) {
     return SW_OK;
 }
 
+// ---- round received and consensus timestamp of the ordered events, kept on the device (consensus.hip.h) ----
+// room for `tx_total` ordered events and for every stored event's two values; earlier records survive a growth
+int consensus_reserve(sw_ctx* c, size_t tx_total) {
+    const size_t ev = (size_t)std::max<int64_t>(c->cap, c->N);
+    CHK(dgrow(c, c->d_rr, ev, c->d_rr.cap));
+    CHK(dgrow(c, c->d_cts, ev, c->d_cts.cap));
+    CHK(dgrow(c, c->d_tx, tx_total, (size_t)c->tx_len));
+    return SW_OK;
+}
+
+// The end of a find_order call that keeps its result: the two values of its n_acc events into the per-event tables, its part
+// of the order behind d_tx[tx_at).  Enqueued on c->stream behind the call's last synchronisation and NOT waited for: the next
+// find_order call synchronises c->stream (its lap "tables") before any of its side streams writes d_acc_ev, d_acc_ri, d_ts or
+// d_sorted again, a dgrow of one of them drains the device, and every reader of the tables runs on c->stream.  Only a call
+// with host-sorted rounds (rare) waits: their slices come from `sorted`, pinned memory the next call may move.
+int consensus_record(sw_ctx* c, int64_t n_acc, size_t tx_at, int nr, const long long* acc_off, const int32_t* hostflag, const int32_t* sorted) {
+    auto run = [&]() -> int {
+        hipLaunchKernelGGL(cns::k_consensus_record, dim3((unsigned)((n_acc + cns::THREADS - 1) / cns::THREADS)), dim3(cns::THREADS), 0, c->stream,
+                           (const int*)c->d_acc_ev.p, (const int*)c->d_acc_ri.p, (const int*)c->d_ord_rounds.p, (const unsigned long long*)c->d_ts.p,
+                           (long long)n_acc, c->d_rr.p, (unsigned long long*)c->d_cts.p);
+        c->ctr.kernel_launches++;
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipMemcpyAsync(c->d_tx.p + tx_at, c->d_sorted.p, (size_t)n_acc * sizeof(int32_t), hipMemcpyDeviceToDevice, c->stream));
+        bool patched = false;
+        for (int i = 0; i < nr; ++i) {
+            const int64_t len = acc_off[i + 1] - acc_off[i];
+            if (!hostflag[i] || !len) continue;
+            HIPCHK(c, hipMemcpyAsync(c->d_tx.p + tx_at + acc_off[i], sorted + acc_off[i], (size_t)len * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+            patched = true;
+        }
+        if (patched) HIPCHK(c, hipStreamSynchronize(c->stream));
+        return SW_OK;
+    };
+    const int rc = run();
+    if (rc != SW_OK) { c->poisoned = true; return rc; }   // (the host's order is extended, the device's is not)
+    c->tx_len = (int64_t)tx_at + n_acc;
+    c->cs_record_calls++;
+    c->cs_recorded += n_acc;
+    return SW_OK;
+}
+
 constexpr int order_tile(int NW) { return NW <= 8 ? 16 : 8; }   // positions per tile of k_order_median: 16 KB of LDS at 256 members (8 workgroups per CU)
 
 template <int NW>
@@ -2335,6 +2386,7 @@ int do_find_order(sw_ctx* c, std::vector<int32_t> rounds, int32_t* out_events, i
         CHK(dgrow(c, c->d_white, (size_t)nr * 64, 0));
         CHK(dgrow(c, c->d_sorted, n_acc, 0));
         CHK(dgrow(c, c->d_hostflag, nr, 0));
+        CHK(consensus_reserve(c, tx_at + (size_t)n_acc));
         // rounds too large for the LDS sort: the same network over global scratch, one workgroup per such round (behind everything else)
         std::vector<int32_t> big_ri;
         std::vector<long long> big_off{0};
@@ -2570,6 +2622,7 @@ int do_find_order(sw_ctx* c, std::vector<int32_t> rounds, int32_t* out_events, i
     }
     if (out_events && n_acc && !(copied_early_ok && !any_host_sorted)) memcpy(out_events, sorted, (size_t)std::min<int64_t>(n_acc, cap) * sizeof(int32_t));
     lap("sort");
+    if (n_acc) CHK(consensus_record(c, n_acc, tx_at, nr, acc_off, hostflag, sorted));   // (the call keeps its result from here on, SW_ERANGE below included)
     std::copy(h_ordnew, h_ordnew + n, c->ord_pos.begin());
     CHK(window_evict(c));
     if (n_out) *n_out = produced;
@@ -2899,6 +2952,7 @@ int sw_destroy(sw_ctx* c) {
     dfree(c->d_ing_tab); dfree(c->d_ing_hist); dfree(c->d_ht_stat);
     dfree(c->d_id); dfree(c->d_idtab); dfree(c->d_idflag); dfree(c->d_pl); dfree(c->d_pl_in);
     dfree(c->d_xp); dfree(c->d_xp_out);
+    dfree(c->d_rr); dfree(c->d_cts); dfree(c->d_tx); dfree(c->d_cs_ordpos); dfree(c->d_cs_out);
     if (c->h_plcnt) (void)hipHostFree(c->h_plcnt);
     if (c->ev_aux_done) (void)hipEventDestroy(c->ev_aux_done);
     if (c->ev_cs_done) (void)hipEventDestroy(c->ev_cs_done);
@@ -4359,6 +4413,7 @@ int sw_rewind(sw_ctx* c) {
     c->sw_dirty_from = 1;
     c->dbg_iter_base = c->ctr.round_iterations;   // (the phase stamps of the loop kernels count from the rewind)
     c->transactions.clear();
+    c->tx_len = 0;   // (d_rr / d_cts need nothing: no event is inside an ordered prefix any more)
     std::fill(c->ord_pos.begin(), c->ord_pos.end(), 0);
     if (c->exact) CHK(exact_rewind(c));
     return SW_OK;
@@ -4971,6 +5026,136 @@ int sw_get_transactions(sw_ctx* c, int64_t first, int64_t K, int32_t* out) {
     if (!c || !out) return SW_EINVAL;
     if (first < 0 || K < 0 || first + K > (int64_t)c->transactions.size()) return fail(c, SW_ERANGE, "range outside the ordered events");
     for (int64_t i = 0; i < K; ++i) out[i] = c->transactions[first + i];
+    return SW_OK;
+}
+
+// ---- round received and consensus timestamp (consensus.hip.h; swirld.py:283-309) ----------------------------------------
+}  // extern "C"
+namespace {
+
+int consensus_pre(sw_ctx* c, const char* what) {
+    if (c->poisoned) return fail(c, SW_EIO, "context unusable after an earlier device failure");
+    if (c->exact) return fail(c, SW_ENOTSUP, "%s is not available on the exact (forked-hashgraph) path", what);
+    return SW_OK;
+}
+
+// both per-event getters: k_consensus_events into context scratch, the wanted array(s) back, one synchronisation
+int consensus_events(sw_ctx* c, const char* what, int64_t first, int64_t K, int32_t* rr_out, double* cts_out) {
+    CHK(consensus_pre(c, what));
+    if (first < 0 || K < 0 || first + K > c->N)
+        return fail(c, SW_ERANGE, "%s: range [%lld, %lld) outside [0, %lld)", what, (long long)first, (long long)(first + K), (long long)c->N);
+    if (!K || (!rr_out && !cts_out)) return SW_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    const int np = c->npad;
+    Carve cv;
+    const size_t o_rr = cv.take(rr_out ? (size_t)K * 4 : 0), o_cts = cv.take(cts_out ? (size_t)K * 8 : 0);
+    CHK(dgrow(c, c->d_cs_out, cv.off, 0));
+    CHK(dgrow(c, c->d_cs_ordpos, np, 0));
+    // (a pageable source: staged before the call returns; every entry below n is written, the kernel reads no other)
+    HIPCHK(c, hipMemcpyAsync(c->d_cs_ordpos.p, c->ord_pos.data(), (size_t)c->n * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    int32_t* d_rr_out = rr_out ? (int32_t*)(c->d_cs_out.p + o_rr) : nullptr;
+    unsigned long long* d_cts_out = cts_out ? (unsigned long long*)(c->d_cs_out.p + o_cts) : nullptr;
+    const unsigned grid = (unsigned)std::min<int64_t>(4096, (K + cns::THREADS - 1) / cns::THREADS);
+    hipLaunchKernelGGL(cns::k_consensus_events, dim3(grid), dim3(cns::THREADS), 0, c->stream, (long long)first, (long long)K, (const int*)c->d_seq.p,
+                       (const int*)c->d_cr.p, (const int*)c->d_cs_ordpos.p, (const int*)c->d_rr.p, (const unsigned long long*)c->d_cts.p, d_rr_out, d_cts_out);
+    c->ctr.kernel_launches++;
+    HIPCHK(c, hipGetLastError());
+    if (rr_out) HIPCHK(c, hipMemcpyAsync(rr_out, d_rr_out, (size_t)K * 4, hipMemcpyDeviceToHost, c->stream));
+    if (cts_out) HIPCHK(c, hipMemcpyAsync(cts_out, d_cts_out, (size_t)K * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return SW_OK;
+}
+
+struct OrderedArrays { int32_t* event; uint8_t* id; int32_t* creator; int32_t* rr; double* t; };
+
+// what both export forms check before anything is enqueued
+int ordered_pre(sw_ctx* c, const char* what, int64_t first, int64_t K, bool want_ids) {
+    CHK(consensus_pre(c, what));
+    if (first < 0 || K < 0 || first + K > c->tx_len)
+        return fail(c, SW_ERANGE, "%s: positions [%lld, %lld) outside the %lld ordered events (nothing written)", what, (long long)first, (long long)(first + K), (long long)c->tx_len);
+    if (want_ids && c->n_ids != c->N)
+        return fail(c, SW_ENOTSUP, "%s: %lld of the %lld stored events have no id (sw_set_event_ids first, or pass no id array)", what, (long long)(c->N - c->n_ids), (long long)c->N);
+    return SW_OK;
+}
+
+// the gather of K > 0 positions on the context's stream (asynchronous)
+int ordered_gather(sw_ctx* c, int64_t first, int64_t K, const OrderedArrays& o) {
+    cns::OrderedIn in{c->d_tx.p, c->d_id.p, c->d_cr.p, c->d_rr.p, (const unsigned long long*)c->d_cts.p};
+    cns::OrderedOut out{o.event, o.id, o.creator, o.rr, (unsigned long long*)o.t};
+    constexpr int G = cns::GATHER_LANES;
+    const dim3 grid((unsigned)std::min<int64_t>(2048, (K * G + cns::THREADS - 1) / cns::THREADS)), block(cns::THREADS);
+    hipLaunchKernelGGL(cns::k_ordered_gather<G>, grid, block, 0, c->stream, in, out, (long long)first, (long long)K);
+    c->ctr.kernel_launches++;
+    HIPCHK(c, hipGetLastError());
+    c->cs_export_calls++;
+    c->cs_exported += K;
+    return SW_OK;
+}
+
+}  // namespace
+extern "C" {
+
+int sw_get_round_received(sw_ctx* c, int64_t first, int64_t K, int32_t* out) {
+    if (!c) return SW_EINVAL;
+    return consensus_events(c, "sw_get_round_received", first, K, out, nullptr);
+}
+
+int sw_get_consensus_time(sw_ctx* c, int64_t first, int64_t K, double* out) {
+    if (!c) return SW_EINVAL;
+    return consensus_events(c, "sw_get_consensus_time", first, K, nullptr, out);
+}
+
+int sw_export_ordered_device(sw_ctx* c, int64_t first, int64_t K, int32_t* d_event, uint8_t* d_id32, int32_t* d_creator,
+                             int32_t* d_round_received, double* d_time, void* user_stream) {
+    if (!c) return SW_EINVAL;
+    CHK(ordered_pre(c, "sw_export_ordered_device", first, K, d_id32 != nullptr));
+    if ((uintptr_t)d_id32 & 15) return fail(c, SW_EINVAL, "sw_export_ordered_device: the id array must be 16-byte aligned");
+    if (!K || (!d_event && !d_id32 && !d_creator && !d_round_received && !d_time)) return SW_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t k = (size_t)K;
+    const bool on = (!d_event || on_ctx_device(c, d_event, k * 4)) && (!d_id32 || on_ctx_device(c, d_id32, k * 32)) &&
+                    (!d_creator || on_ctx_device(c, d_creator, k * 4)) && (!d_round_received || on_ctx_device(c, d_round_received, k * 4)) &&
+                    (!d_time || on_ctx_device(c, d_time, k * 8));
+    if (!on) return fail(c, SW_EINVAL, "sw_export_ordered_device: every array must lie in memory of device %d (a host pointer, or another device's)", c->device);
+    if (!c->ev_user) HIPCHK(c, hipEventCreateWithFlags(&c->ev_user, hipEventDisableTiming));
+    hipStream_t us = (hipStream_t)user_stream;
+    HIPCHK(c, hipEventRecord(c->ev_user, us));            // earlier readers of the output arrays
+    HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_user, 0));
+    CHK(ordered_gather(c, first, K, OrderedArrays{d_event, d_id32, d_creator, d_round_received, d_time}));
+    HIPCHK(c, hipEventRecord(c->ev_user, c->stream));     // whatever the caller enqueues next reads complete arrays
+    HIPCHK(c, hipStreamWaitEvent(us, c->ev_user, 0));
+    return SW_OK;
+}
+
+int sw_export_ordered(sw_ctx* c, int64_t first, int64_t K, int32_t* event, uint8_t* id32, int32_t* creator, int32_t* round_received, double* time) {
+    if (!c) return SW_EINVAL;
+    CHK(ordered_pre(c, "sw_export_ordered", first, K, id32 != nullptr));
+    if (!K || (!event && !id32 && !creator && !round_received && !time)) return SW_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t k = (size_t)K;
+    Carve cv;
+    const size_t o_ev = cv.take(event ? k * 4 : 0), o_id = cv.take(id32 ? k * 32 : 0), o_cr = cv.take(creator ? k * 4 : 0),
+                 o_rr = cv.take(round_received ? k * 4 : 0), o_t = cv.take(time ? k * 8 : 0);
+    CHK(dgrow(c, c->d_cs_out, cv.off, 0));
+    unsigned char* B = c->d_cs_out.p;
+    const OrderedArrays d{event ? (int32_t*)(B + o_ev) : nullptr, id32 ? B + o_id : nullptr, creator ? (int32_t*)(B + o_cr) : nullptr,
+                          round_received ? (int32_t*)(B + o_rr) : nullptr, time ? (double*)(B + o_t) : nullptr};
+    CHK(ordered_gather(c, first, K, d));
+    if (event) HIPCHK(c, hipMemcpyAsync(event, d.event, k * 4, hipMemcpyDeviceToHost, c->stream));
+    if (id32) HIPCHK(c, hipMemcpyAsync(id32, d.id, k * 32, hipMemcpyDeviceToHost, c->stream));
+    if (creator) HIPCHK(c, hipMemcpyAsync(creator, d.creator, k * 4, hipMemcpyDeviceToHost, c->stream));
+    if (round_received) HIPCHK(c, hipMemcpyAsync(round_received, d.rr, k * 4, hipMemcpyDeviceToHost, c->stream));
+    if (time) HIPCHK(c, hipMemcpyAsync(time, d.t, k * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return SW_OK;
+}
+
+int sw_get_consensus_stats(sw_ctx* c, int64_t* record_calls, int64_t* recorded_events, int64_t* export_calls, int64_t* exported_events) {
+    if (!c) return SW_EINVAL;
+    if (record_calls) *record_calls = c->cs_record_calls;
+    if (recorded_events) *recorded_events = c->cs_recorded;
+    if (export_calls) *export_calls = c->cs_export_calls;
+    if (exported_events) *exported_events = c->cs_exported;
     return SW_OK;
 }
 

@@ -442,6 +442,65 @@ class Hashgraph:
         self._chk(self._L.sw_get_transactions(self._h, 0, n.value, _p(out)))
         return out
 
+    # ---- what find_order decided per event (swirld.py:283-309; csrc/consensus.hip.h) ----
+    @property
+    def num_ordered(self):
+        n = C.c_int64()
+        self._chk(self._L.sw_num_ordered(self._h, C.byref(n)))
+        return int(n.value)
+
+    def round_received(self, first=0, K=None):
+        """Round received of the events [first, first + K) (swirld.py:283), -1 = not ordered yet."""
+        K = self.num_events - first if K is None else K
+        out = np.empty(max(K, 0), np.int32)
+        self._chk(self._L.sw_get_round_received(self._h, int(first), int(K), _p(out)))
+        return out
+
+    def consensus_time(self, first=0, K=None):
+        """Consensus timestamp of the events [first, first + K) (swirld.py:305, bit for bit), NaN = not ordered yet."""
+        K = self.num_events - first if K is None else K
+        out = np.empty(max(K, 0), np.float64)
+        self._chk(self._L.sw_get_consensus_time(self._h, int(first), int(K), _p(out)))
+        return out
+
+    def export_ordered(self, first=0, K=None, ids=None):
+        """Positions [first, first + K) of the order as numpy arrays: a dict with event (int32, the dense indices: a slice of
+        transactions()), creator (int32), round_received (int32), time (float64) and — `ids` True, or None [default] and the id index
+        complete — ids (K x 32 uint8)."""
+        K = self.num_ordered - first if K is None else K
+        k = max(int(K), 0)
+        d = dict(event=np.empty(k, np.int32), creator=np.empty(k, np.int32), round_received=np.empty(k, np.int32), time=np.empty(k, np.float64))
+        for with_ids in ((True, False) if ids is None else (bool(ids),)):
+            i32 = np.empty((k, 32), np.uint8) if with_ids else None
+            rc = self._L.sw_export_ordered(self._h, int(first), int(K), _p(d["event"]), _p(i32), _p(d["creator"]), _p(d["round_received"]), _p(d["time"]))
+            if not (rc == -95 and with_ids and ids is None):    # (no complete id index: the same without ids)
+                break
+        self._chk(rc)
+        if with_ids:
+            d["ids"] = i32
+        return d
+
+    def export_ordered_device(self, first, K, event=None, ids=None, creator=None, round_received=None, time=None, stream=0):
+        """Positions [first, first + K) of the order written to DEVICE arrays (addresses, or objects with data_ptr() /
+        __cuda_array_interface__, e.g. torch tensors): event, creator, round_received int32, time float64, ids K x 32 uint8
+        and 16-byte aligned; None = not wanted.  `stream` (a raw hipStream_t) is made to wait for the arrays; there is no
+        host synchronisation.  Returns K."""
+        a = []
+        for what, arr in (("event", event), ("ids", ids), ("creator", creator), ("round_received", round_received), ("time", time)):
+            ptr, ln = _dev_ptr(arr)
+            if ln is not None and ln < K:
+                raise ValueError("%s holds %d entries, expected %d" % (what, ln, K))
+            a.append(C.c_void_p(ptr) if ptr else None)
+        self._chk(self._L.sw_export_ordered_device(self._h, int(first), int(K), *a, C.c_void_p(int(stream))))
+        return int(K)
+
+    def consensus_stats(self):
+        """find_order calls that recorded events and the events they recorded, export_ordered[_device] calls and the
+        positions they exported, since the context was created."""
+        v = [C.c_int64() for _ in range(4)]
+        self._chk(self._L.sw_get_consensus_stats(self._h, *[C.byref(x) for x in v]))
+        return dict(zip(("record_calls", "recorded_events", "export_calls", "exported_events"), (int(x.value) for x in v)))
+
     # ---- measurement ----
     def counters(self):
         c = Counters()

@@ -135,6 +135,28 @@ class _FamousView(Mapping):
         return len(self._dict())
 
 
+class _ConsensusView(Mapping):
+    """Node.round_received / Node.consensus_time: {event hash -> round received (swirld.py:283) / consensus timestamp
+    (swirld.py:305)} of exactly the events of Node.transactions, in that order.  The reference computes both inside
+    find_order and drops them; here they stay on the device (csrc/consensus.hip.h).  On a context that stored a forked
+    event (exact path) the view raises NotImplementedError with the library's message."""
+
+    def __init__(self, node, which):
+        self._n, self._k = node, which
+
+    def __getitem__(self, h):
+        vals = self._n._consensus_values()[self._k]
+        return vals[self._n.idx[h]].item()      # (KeyError for an event that is not ordered, or not known)
+
+    def __iter__(self):
+        self._n._consensus_values()
+        return iter(self._n.transactions)
+
+    def __len__(self):
+        self._n._consensus_values()
+        return len(self._n.transactions)
+
+
 class VotesUnavailable(LookupError):
     """Node.votes is not kept in this state: the context stored a forked event (the exact path keeps two
     vote layers, not the history: sw_get_vote -> SW_ENOTSUP) or fame was committed from a partitioned
@@ -291,6 +313,9 @@ class Node:
         self.witnesses = _WitnessView(self)
         self.famous = _FamousView(self)
         self.votes = _VotesView(self)
+        self._cons_cache = (np.zeros(0, np.int32), np.zeros(0, np.float64))
+        self.round_received = _ConsensusView(self, 0)
+        self.consensus_time = _ConsensusView(self, 1)
 
         # the node's own root event (swirld.py:75-80)
         h, ev = self.new_event(None, ())
@@ -598,6 +623,23 @@ class Node:
         if have < self._divided:
             self._round_cache = np.concatenate([self._round_cache, self._dev.rounds(have, self._divided - have)])
         return self._round_cache
+
+    def _consensus_values(self):
+        """(round received, consensus time) by position of Node.transactions; the positions added since the last look
+        are fetched in one range of events."""
+        if self._dev.exact:
+            try:
+                self._dev.round_received(0, 0)
+            except SwirldHipError as exc:
+                raise NotImplementedError(str(exc)) from None
+            raise NotImplementedError("round received / consensus time are not kept on the exact (forked-hashgraph) path")
+        have, n = self._cons_cache[0].shape[0], len(self.transactions)
+        if have < n:
+            ev = np.array([self._index[h] for h in self.transactions[have:]], np.int64)
+            lo, hi = int(ev.min()), int(ev.max()) + 1
+            rr, ct = self._dev.round_received(lo, hi - lo), self._dev.consensus_time(lo, hi - lo)
+            self._cons_cache = (np.concatenate([self._cons_cache[0], rr[ev - lo]]), np.concatenate([self._cons_cache[1], ct[ev - lo]]))
+        return self._cons_cache
 
     def _witness_table(self):
         if self._wit_cache is None:
