@@ -2237,7 +2237,11 @@ int window_evict(sw_ctx* c) {
     return SW_OK;
 }
 
-// pinned staging of a find_order call: [rounds: nr][ordpos: npad][OrderInfo init][read-back block = the layout of d_oblk][hostflag: nr]
+// ==== sw_find_order, host side ====================================================================
+// do_find_order (at the end of this section) calls the phases below in order; DESIGN.md §5 maps every phase to its
+// function, to the stream it enqueues on and to what the host waits for.
+
+// pinned staging of a find_order call (laid out by stage_order_call)
 int ensure_order_host(sw_ctx* c, size_t bytes) {
     if (bytes <= c->h_ord_cap) return SW_OK;
     if (c->h_ord) { HIPCHK(c, hipDeviceSynchronize()); (void)hipHostFree(c->h_ord); c->h_ord = nullptr; c->h_ord_cap = 0; }
@@ -2267,30 +2271,31 @@ int consensus_reserve(sw_ctx* c, size_t tx_total) {
     return SW_OK;
 }
 
+int consensus_record_enqueue(sw_ctx* c, int64_t n_acc, size_t tx_at, int nr, const long long* acc_off, const int32_t* hostflag, const int32_t* sorted) {
+    hipLaunchKernelGGL(cns::k_consensus_record, dim3((unsigned)((n_acc + cns::THREADS - 1) / cns::THREADS)), dim3(cns::THREADS), 0, c->stream,
+                       (const int*)c->d_acc_ev.p, (const int*)c->d_acc_ri.p, (const int*)c->d_ord_rounds.p, (const unsigned long long*)c->d_ts.p,
+                       (long long)n_acc, c->d_rr.p, (unsigned long long*)c->d_cts.p);
+    c->ctr.kernel_launches++;
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(c->d_tx.p + tx_at, c->d_sorted.p, (size_t)n_acc * sizeof(int32_t), hipMemcpyDeviceToDevice, c->stream));
+    bool patched = false;
+    for (int i = 0; i < nr; ++i) {
+        const int64_t len = acc_off[i + 1] - acc_off[i];
+        if (!hostflag[i] || !len) continue;
+        HIPCHK(c, hipMemcpyAsync(c->d_tx.p + tx_at + acc_off[i], sorted + acc_off[i], (size_t)len * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+        patched = true;
+    }
+    if (patched) HIPCHK(c, hipStreamSynchronize(c->stream));
+    return SW_OK;
+}
+
 // The end of a find_order call that keeps its result: the two values of its n_acc events into the per-event tables, its part
 // of the order behind d_tx[tx_at).  Enqueued on c->stream behind the call's last synchronisation and NOT waited for: the next
 // find_order call synchronises c->stream (its lap "tables") before any of its side streams writes d_acc_ev, d_acc_ri, d_ts or
 // d_sorted again, a dgrow of one of them drains the device, and every reader of the tables runs on c->stream.  Only a call
 // with host-sorted rounds (rare) waits: their slices come from `sorted`, pinned memory the next call may move.
 int consensus_record(sw_ctx* c, int64_t n_acc, size_t tx_at, int nr, const long long* acc_off, const int32_t* hostflag, const int32_t* sorted) {
-    auto run = [&]() -> int {
-        hipLaunchKernelGGL(cns::k_consensus_record, dim3((unsigned)((n_acc + cns::THREADS - 1) / cns::THREADS)), dim3(cns::THREADS), 0, c->stream,
-                           (const int*)c->d_acc_ev.p, (const int*)c->d_acc_ri.p, (const int*)c->d_ord_rounds.p, (const unsigned long long*)c->d_ts.p,
-                           (long long)n_acc, c->d_rr.p, (unsigned long long*)c->d_cts.p);
-        c->ctr.kernel_launches++;
-        HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipMemcpyAsync(c->d_tx.p + tx_at, c->d_sorted.p, (size_t)n_acc * sizeof(int32_t), hipMemcpyDeviceToDevice, c->stream));
-        bool patched = false;
-        for (int i = 0; i < nr; ++i) {
-            const int64_t len = acc_off[i + 1] - acc_off[i];
-            if (!hostflag[i] || !len) continue;
-            HIPCHK(c, hipMemcpyAsync(c->d_tx.p + tx_at + acc_off[i], sorted + acc_off[i], (size_t)len * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-            patched = true;
-        }
-        if (patched) HIPCHK(c, hipStreamSynchronize(c->stream));
-        return SW_OK;
-    };
-    const int rc = run();
+    const int rc = consensus_record_enqueue(c, n_acc, tx_at, nr, acc_off, hostflag, sorted);
     if (rc != SW_OK) { c->poisoned = true; return rc; }   // (the host's order is extended, the device's is not)
     c->tx_len = (int64_t)tx_at + n_acc;
     c->cs_record_calls++;
@@ -2299,335 +2304,512 @@ int consensus_record(sw_ctx* c, int64_t n_acc, size_t tx_at, int nr, const long 
 }
 
 constexpr int order_tile(int NW) { return NW <= 8 ? 16 : 8; }   // positions per tile of k_order_median: 16 KB of LDS at 256 members (8 workgroups per CU)
+constexpr int order_cw(int NW) { return NW >= 4 ? 256 : 64 * NW; }   // columns per workgroup of k_order_walk
 
-template <int NW>
-int do_find_order(sw_ctx* c, std::vector<int32_t> rounds, int32_t* out_events, int64_t cap, int64_t* n_out) {
-    const int np = c->npad, n = c->n;
-    const bool dbg = getenv("SW_DEBUG_TIMING") != nullptr;
-    auto T0 = std::chrono::steady_clock::now();
-    auto lap = [&](const char* what) {
-        if (!dbg) return;
+// the SW_ORDER_* switches of one call (read per call: the tests force either path between two calls of one process)
+struct OrderKnobs {
+    int64_t bulk_min;   // SW_ORDER_BULK: events from which a call takes the first-descendant table (0 = never) [16384]
+    int64_t slab_mb;    // SW_ORDER_SLAB_MB: table per group [256 per 256 columns: 4 groups per 1 M events — 128 and 512 are both 0.15-0.3 ms slower, profiles/r06_measured_and_dropped.txt]
+    int S;              // SW_ORDER_S: stretches per (member, column group) of the walk [enough for 1024 workgroups], 1..64
+    bool one_stream;    // SW_ORDER_ONE_STREAM: one slab, everything on the main stream
+    bool sort_inline;   // SW_ORDER_SORT_INLINE: a group's sort behind its samples, on their stream
+    bool late_copy;     // SW_ORDER_LATE_COPY: the caller's copy in one piece at the end
+    bool host;          // SW_ORDER_HOST: test hook: every round sorted by the host
+    bool big_host;      // SW_ORDER_BIG_HOST: test hook: oversize rounds to the host, as before round 4
+    bool timing;        // SW_DEBUG_TIMING: the laps below
+};
+
+OrderKnobs read_order_knobs(const sw_ctx* c) {
+    OrderKnobs k;
+    const char* e;
+    k.bulk_min = (e = getenv("SW_ORDER_BULK")) ? atoll(e) : 16384;
+    k.slab_mb = (e = getenv("SW_ORDER_SLAB_MB")) ? atoll(e) : 256 * std::max(1, c->nw / 4);
+    const int wgs = c->n * (c->npad / order_cw(c->nw));   // workgroups of the walk per stretch
+    k.S = std::min(std::max((e = getenv("SW_ORDER_S")) ? atoi(e) : (1024 + wgs - 1) / wgs, 1), 64);
+    k.one_stream = getenv("SW_ORDER_ONE_STREAM") != nullptr;
+    k.sort_inline = getenv("SW_ORDER_SORT_INLINE") != nullptr;
+    k.late_copy = getenv("SW_ORDER_LATE_COPY") != nullptr;
+    k.host = getenv("SW_ORDER_HOST") != nullptr;
+    k.big_host = getenv("SW_ORDER_BIG_HOST") != nullptr;
+    k.timing = getenv("SW_DEBUG_TIMING") != nullptr;
+    return k;
+}
+
+// host laps of one call under SW_DEBUG_TIMING, each behind a synchronisation of the main stream (profiles/order_laps.py)
+struct OrderLaps {
+    bool on;
+    std::chrono::steady_clock::time_point last = std::chrono::steady_clock::now();
+    void lap(sw_ctx* c, const char* what, hipStream_t side = nullptr) {   // side: a side stream to wait for first
+        if (!on) return;
+        if (side) (void)hipStreamSynchronize(side);
         (void)hipStreamSynchronize(c->stream);
-        auto t = std::chrono::steady_clock::now();
-        fprintf(stderr, "[find_order] %-10s %8.3f ms\n", what, std::chrono::duration<double, std::milli>(t - T0).count());
-        T0 = t;
-    };
-    std::sort(rounds.begin(), rounds.end());  // sorted(new_c), swirld.py:283
+        const auto t = std::chrono::steady_clock::now();
+        fprintf(stderr, "[find_order] %-10s %8.3f ms\n", what, std::chrono::duration<double, std::milli>(t - last).count());
+        last = t;
+    }
+};
+
+// The read-back block of a call, d_oblk on the device and its image in the pinned block: [OrderInfo][ord_new: npad ints]
+// [acc_off: nr + 1 long long], fetched with ONE copy (and its OrderInfo once more at the end of the call).
+struct OrderBlock {
+    OrderInfo* info = nullptr;
+    int32_t* ordnew = nullptr;       // members' ordered prefixes behind this call
+    long long* acc_off = nullptr;    // [nr + 1] first ordered event of every round entry
+    OrderBlock() = default;
+    OrderBlock(void* base, int np) : info(static_cast<OrderInfo*>(base)), ordnew(reinterpret_cast<int32_t*>(info + 1)), acc_off(reinterpret_cast<long long*>(ordnew + np)) {}
+    static size_t bytes(int np, int nr) { return sizeof(OrderInfo) + (size_t)np * 4 + ((size_t)nr + 1) * 8; }
+};
+static_assert(sizeof(OrderInfo) % 8 == 0, "acc_off follows OrderInfo and an even number of ints");
+
+struct OrderSpan { int i0, i1; };   // the round entries [i0, i1) of a group
+
+// one sw_find_order call: what its phases hand on to each other (buffers that outlive the call stay in sw_ctx)
+struct OrderCall {
+    const OrderKnobs k;
+    const std::vector<int32_t> rounds;   // sorted, unique: the round entries
+    const int nr;
+    int32_t* const out_events;           // the caller's array (may be NULL) and its capacity
+    const int64_t cap;
+    // views into the pinned block (stage_order_call)
+    int32_t *h_rounds = nullptr, *h_ordpos = nullptr, *hostflag = nullptr;   // hostflag[i]: the host sorts round entry i
+    OrderInfo* h_init = nullptr;
+    OrderBlock h;                        // the read-back block
+    // views into d_oblk, d_seg, d_fwm
+    OrderBlock d;
+    int32_t *d_seg_start = nullptr, *d_seg_len = nullptr, *d_seg_off = nullptr, *d_fwseq = nullptr;
+    int64_t n_acc = 0;                   // events the call orders
+    size_t tx_at = 0;                    // ... behind this many of earlier calls
+    int32_t* sorted = nullptr;           // transactions + tx_at: the device-sorted order lands in place
+    // rounds too large for the LDS sort (plan_order_sorts)
+    std::vector<int32_t> big_ri;
+    std::vector<long long> big_off{0};
+    bool fetch_early = false;            // every sort is followed by the copy of its part of the order to the host
+    bool bulk = false;                   // the first-descendant table (else one search per (event, famous witness))
+    // groups and slabs of a bulk call (plan_order_groups)
+    std::vector<OrderSpan> groups;
+    int64_t stride = 0;                  // entries between two members' planes of a slab
+    bool two = false;                    // two slabs, side streams
+    hipStream_t s1 = nullptr;            // the stream of the table's consumers
+    hipStream_t tail = nullptr;          // the stream the last kernels of the call are on
+    bool copied_early = false;           // out_events already holds the order as the device sorted it
+    bool any_host_sorted = false;        // the host re-sorted rounds of it
+    std::vector<int32_t> acc_ev;         // host copies, fetched only for the rounds the host has to sort
+    std::vector<double> ts;
+    std::vector<unsigned char> white_h;
+    int64_t produced = 0;
+    OrderLaps clk;
+    OrderCall(sw_ctx* c, std::vector<int32_t>&& rounds_, int32_t* out_events_, int64_t cap_)
+        : k(read_order_knobs(c)), rounds(std::move(rounds_)), nr((int)rounds.size()), out_events(out_events_), cap(cap_), tx_at(c->transactions.size()), tail(c->stream), clk{k.timing} {}
+};
+
+// the call's part of `transactions`: from its growth (order_reserve) on, every return that does not keep the call's result
+// gives it back, so that sw_num_ordered, sw_get_transactions, ord_pos and the device's tables go on agreeing.  The device is
+// drained first: after a HIP error in the middle of the groups, copies into that part may still be in flight on the sort
+// streams, and the next call may grow (and move) the array.
+struct OrderRollback {
+    sw_ctx* c;
+    const OrderCall& o;
+    bool armed;
+    ~OrderRollback() { if (armed) { (void)hipDeviceSynchronize(); c->transactions.resize(o.tx_at); } }
+};
+
+// ---- phase: the rounds argument, shared with exact_order: sorted(new_c), swirld.py:283, every round once and known
+int order_rounds_arg(sw_ctx* c, std::vector<int32_t>& rounds) {
+    std::sort(rounds.begin(), rounds.end());
     rounds.erase(std::unique(rounds.begin(), rounds.end()), rounds.end());
-    const int nr = (int)rounds.size();
-    if (nr == 0) return SW_OK;
-    if (c->payload_pending) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_payload, 0));  // timestamps / signatures of a bulk append
-    if (rounds.front() < 0 || rounds.back() >= c->R)
+    if (!rounds.empty() && (rounds.front() < 0 || rounds.back() >= c->R))
         return fail(c, SW_ERANGE, "find_order: round outside [0, %d) (KeyError in the reference)", c->R);
+    return SW_OK;
+}
+
+// ---- phase: staging and the table buffers.  The pinned block is [rounds: nr][ordpos: npad][OrderInfo init][read-back block]
+// [hostflag: nr], every part on a 64-byte boundary; this function alone knows the offsets.  The tables of
+// the call are all on the device: f_w (:284), q (:288-293), ordered prefixes per entry, segment offsets.
+int stage_order_call(sw_ctx* c, OrderCall& o) {
+    const int np = c->npad, nr = o.nr;
     if ((int64_t)(nr + 1) * np >= (1ll << 31)) return fail(c, SW_ERANGE, "find_order: %d rounds x %d columns exceed 2^31 table entries", nr, np);
-    // ---- tables of the call, all on the device: f_w (:284), q (:288-293), ordered prefixes per entry, segment offsets ----
-    // device block read back with ONE copy: [OrderInfo][ord_new: npad ints][acc_off: nr + 1 long long]
-    const size_t oblk_ll = sizeof(OrderInfo) / 8 + (size_t)np / 2 + (size_t)nr + 1;
-    const size_t h_rounds_off = 0, h_ordpos_off = ((size_t)nr * 4 + 63) & ~(size_t)63, h_init_off = h_ordpos_off + (size_t)np * 4,
-                 h_blk_off = h_init_off + 64, h_flag_off = h_blk_off + ((oblk_ll * 8 + 63) & ~(size_t)63);
-    CHK(ensure_order_host(c, h_flag_off + (size_t)nr * 4));
-    int32_t* h_rounds = reinterpret_cast<int32_t*>(c->h_ord + h_rounds_off);
-    int32_t* h_ordpos = reinterpret_cast<int32_t*>(c->h_ord + h_ordpos_off);
-    OrderInfo* h_init = reinterpret_cast<OrderInfo*>(c->h_ord + h_init_off);
-    const OrderInfo* h_info = reinterpret_cast<const OrderInfo*>(c->h_ord + h_blk_off);
-    const int32_t* h_ordnew = reinterpret_cast<const int32_t*>(c->h_ord + h_blk_off + sizeof(OrderInfo));
-    const long long* acc_off = reinterpret_cast<const long long*>(c->h_ord + h_blk_off + sizeof(OrderInfo) + (size_t)np * 4);
-    int32_t* hostflag = reinterpret_cast<int32_t*>(c->h_ord + h_flag_off);
-    std::copy(rounds.begin(), rounds.end(), h_rounds);
-    std::fill(h_ordpos, h_ordpos + np, 0);
-    std::copy(c->ord_pos.begin(), c->ord_pos.end(), h_ordpos);
-    *h_init = OrderInfo{0, 0x7fffffff, 0, {0, 0, 0, 0}};
+    const size_t blk = OrderBlock::bytes(np, nr);
+    const size_t ordpos_off = ((size_t)nr * 4 + 63) & ~(size_t)63, init_off = ordpos_off + (size_t)np * 4, blk_off = init_off + 64,
+                 flag_off = blk_off + ((blk + 63) & ~(size_t)63);
+    CHK(ensure_order_host(c, flag_off + (size_t)nr * 4));
+    o.h_rounds = reinterpret_cast<int32_t*>(c->h_ord);
+    o.h_ordpos = reinterpret_cast<int32_t*>(c->h_ord + ordpos_off);
+    o.h_init = reinterpret_cast<OrderInfo*>(c->h_ord + init_off);
+    o.h = OrderBlock(c->h_ord + blk_off, np);
+    o.hostflag = reinterpret_cast<int32_t*>(c->h_ord + flag_off);
+    std::copy(o.rounds.begin(), o.rounds.end(), o.h_rounds);
+    std::fill(o.h_ordpos, o.h_ordpos + np, 0);
+    std::copy(c->ord_pos.begin(), c->ord_pos.end(), o.h_ordpos);
+    *o.h_init = OrderInfo{0, 0x7fffffff, 0, {0, 0, 0, 0}};
     CHK(dgrow(c, c->d_ord_rounds, nr, 0));
     CHK(dgrow(c, c->d_fwm, (size_t)2 * nr * np, 0));   // [famous witness | its chain position] per (entry, member)
     CHK(dgrow(c, c->d_q, (size_t)nr * np, 0));
     CHK(dgrow(c, c->d_ordat, (size_t)(nr + 1) * np, 0));
     CHK(dgrow(c, c->d_seg, (size_t)3 * nr * np, 0));
     CHK(dgrow(c, c->d_rowsum, nr, 0));
-    CHK(dgrow(c, c->d_oblk, oblk_ll, 0));
+    CHK(dgrow(c, c->d_oblk, blk / 8, 0));
     CHK(dgrow(c, c->d_ordpos, np, 0));
-    OrderInfo* d_info = reinterpret_cast<OrderInfo*>(c->d_oblk.p);
-    int32_t* d_ordnew = reinterpret_cast<int32_t*>(c->d_oblk.p) + sizeof(OrderInfo) / 4;
-    long long* d_acc_off = c->d_oblk.p + sizeof(OrderInfo) / 8 + np / 2;
-    int32_t *d_seg_start = c->d_seg.p, *d_seg_len = c->d_seg.p + (size_t)nr * np, *d_seg_off = c->d_seg.p + (size_t)2 * nr * np;
-    HIPCHK(c, hipMemcpyAsync(c->d_ord_rounds.p, h_rounds, (size_t)nr * 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(c->d_ordpos.p, h_ordpos, (size_t)np * 4, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(d_info, h_init, sizeof(OrderInfo), hipMemcpyHostToDevice, c->stream));
-    int32_t* d_fwseq = c->d_fwm.p + (size_t)nr * np;
+    o.d = OrderBlock(c->d_oblk.p, np);
+    o.d_seg_start = c->d_seg.p; o.d_seg_len = c->d_seg.p + (size_t)nr * np; o.d_seg_off = c->d_seg.p + (size_t)2 * nr * np;
+    o.d_fwseq = c->d_fwm.p + (size_t)nr * np;
+    HIPCHK(c, hipMemcpyAsync(c->d_ord_rounds.p, o.h_rounds, (size_t)nr * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->d_ordpos.p, o.h_ordpos, (size_t)np * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(o.d.info, o.h_init, sizeof(OrderInfo), hipMemcpyHostToDevice, c->stream));
+    return SW_OK;
+}
+
+// ---- phase: the tables.  Five kernels, ONE read-back (events per entry, error words, new prefixes) and the first of the
+// call's two synchronisations: all the host sees before it sizes the bulk kernels.
+template <int NW>
+int order_tables(sw_ctx* c, OrderCall& o) {
+    const int np = c->npad, n = c->n, nr = o.nr;
     hipLaunchKernelGGL(k_order_prep, dim3(nr), dim3(np), 0, c->stream, (const int*)c->d_ord_rounds.p, (const int*)c->d_wit.p,
-                       (const signed char*)c->d_fam.p, (const int*)c->d_seq.p, n, np, c->d_fwm.p, d_fwseq, d_info);
+                       (const signed char*)c->d_fam.p, (const int*)c->d_seq.p, n, np, c->d_fwm.p, o.d_fwseq, o.d.info);
     hipLaunchKernelGGL(k_order_bounds<NW>, dim3(nr, NW), dim3(64 * NW), 0, c->stream, (const int*)c->d_fwm.p, (const int*)c->d_L.p,
                        (const int*)c->d_seq.p, (const uint32_t*)c->d_stake.p, c->tot, (const int*)c->d_chain_start.p,
                        (const int*)c->d_chain_cnt.p, (const int*)c->d_chain_ev.p, n, (int)(c->N - 1), c->d_q.p);
     hipLaunchKernelGGL(k_order_runmax, dim3(1), dim3(np), 0, c->stream, (const int*)c->d_q.p, (const int*)c->d_ordpos.p, nr, np,
-                       c->d_ordat.p, d_seg_start, d_seg_len, d_ordnew);
-    hipLaunchKernelGGL(k_order_rowscan, dim3(nr), dim3(np), 0, c->stream, (const int*)d_seg_len, np, d_seg_off, c->d_rowsum.p);
-    hipLaunchKernelGGL(k_order_offsets, dim3(1), dim3(1024), 0, c->stream, (const int*)c->d_rowsum.p, nr, d_acc_off, d_info);
+                       c->d_ordat.p, o.d_seg_start, o.d_seg_len, o.d.ordnew);
+    hipLaunchKernelGGL(k_order_rowscan, dim3(nr), dim3(np), 0, c->stream, (const int*)o.d_seg_len, np, o.d_seg_off, c->d_rowsum.p);
+    hipLaunchKernelGGL(k_order_offsets, dim3(1), dim3(1024), 0, c->stream, (const int*)c->d_rowsum.p, nr, o.d.acc_off, o.d.info);
     c->ctr.kernel_launches += 5;
-    HIPCHK(c, hipMemcpyAsync(c->h_ord + h_blk_off, c->d_oblk.p, oblk_ll * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(o.h.info, o.d.info, OrderBlock::bytes(np, nr), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     HIPCHK(c, hipGetLastError());
-    lap("tables");
-    if (h_info->undecided_ri != 0x7fffffff)
-        return fail(c, SW_EINVAL, "find_order: round %d has an undecided witness (KeyError on self.famous[w], swirld.py:284)", rounds[h_info->undecided_ri]);
-    const int64_t n_acc = h_info->n_acc;
-    if (n_acc > 0x7ffffff0ll) return fail(c, SW_ERANGE, "find_order: more than 2^31 events in one call");
-    std::vector<int32_t> acc_ev;   // host copy: fetched only for the rounds the host has to sort
-    std::vector<double> ts;        // (host copy of the timestamps: only for rounds the host sorts)
-    std::vector<unsigned char> white_h;
-    std::fill(hostflag, hostflag + nr, 0);
-    const size_t tx_at = c->transactions.size();
-    if (!c->transactions.resize(tx_at + (size_t)n_acc)) return fail(c, SW_ENOMEM, "pinned host memory for the ordered events");   // the device-sorted order lands in place
-    int32_t* sorted = c->transactions.data() + tx_at;
-    bool copied_early_ok = false, any_host_sorted = false;   // out_events already holds the order / the host re-sorted rounds of it
-    if (n_acc) {
-        CHK(dgrow(c, c->d_acc_ev, n_acc, 0));
-        CHK(dgrow(c, c->d_acc_ri, n_acc, 0));
-        CHK(dgrow(c, c->d_ts, n_acc, 0));
-        CHK(dgrow(c, c->d_white, (size_t)nr * 64, 0));
-        CHK(dgrow(c, c->d_sorted, n_acc, 0));
-        CHK(dgrow(c, c->d_hostflag, nr, 0));
-        CHK(consensus_reserve(c, tx_at + (size_t)n_acc));
-        // rounds too large for the LDS sort: the same network over global scratch, one workgroup per such round (behind everything else)
-        std::vector<int32_t> big_ri;
-        std::vector<long long> big_off{0};
-        for (int i = 0; i < nr; ++i) {
-            const int64_t len = acc_off[i + 1] - acc_off[i];
-            if (len <= SORT_CAP || getenv("SW_ORDER_BIG_HOST")) continue;   // (test hook: oversize rounds to the host, as before round 4)
-            int64_t m = 1;
-            while (m < len) m <<= 1;
-            big_ri.push_back(i);
-            big_off.push_back(big_off.back() + m);
-        }
-        // device sort of the round entries [i0, i1) by (ts, first 8 whitened key bytes), then their part of the order to the host
-        auto sort_and_fetch = [&](hipStream_t st, int i0, int i1, bool fetch) -> int {
-            hipLaunchKernelGGL(k_order_sort, dim3(i1 - i0), dim3(1024), 0, st, (const int*)c->d_acc_ev.p,
-                               (const long long*)d_acc_off, (const double*)c->d_ts.p, (const unsigned char*)c->d_sig.p,
-                               (const unsigned char*)c->d_white.p, i0, c->d_sorted.p, c->d_hostflag.p);
-            c->ctr.kernel_launches++;
-            const int64_t a0 = acc_off[i0], na = acc_off[i1] - a0;
-            if (fetch && na) HIPCHK(c, hipMemcpyAsync(sorted + a0, c->d_sorted.p + a0, na * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-            return SW_OK;
-        };
-        const bool fetch_early = big_ri.empty();   // (oversize rounds are sorted last: then the whole order travels at the end)
-        // what only the consumers of the table need (the ordered events round-major, the whitening keys, cleared flags): enqueued
-        // on THEIR stream, beside the first walk
-        auto consumer_preamble = [&](hipStream_t st) -> int {
-            HIPCHK(c, hipMemsetAsync(c->d_hostflag.p, 0, nr * sizeof(int32_t), st));
-            hipLaunchKernelGGL(k_order_segments, dim3((unsigned)(((size_t)nr * np + 255) / 256)), dim3(256), 0, st, (const int*)d_seg_start,
-                               (const int*)d_seg_len, (const int*)d_seg_off, (const long long*)d_acc_off, (const int*)c->d_chain_start.p,
-                               (const int*)c->d_chain_ev.p, np, nr * np, c->d_acc_ev.p, c->d_acc_ri.p);
-            hipLaunchKernelGGL(k_order_white, dim3(nr), dim3(1024), 0, st, (const int*)c->d_fwm.p, n, np,
-                               (const unsigned char*)c->d_sig.p, c->d_white.p);
-            c->ctr.kernel_launches += 2;
-            return SW_OK;
-        };
-        // A call that orders many events: the first-descendant table (k_order_walk) instead of one binary search per
-        // (event, famous witness) pair.  Same samples, by construction and by test (SW_ORDER_BULK=<events> moves the
-        // threshold, 0 = never).
-        const int64_t bulk_min = getenv("SW_ORDER_BULK") ? atoll(getenv("SW_ORDER_BULK")) : 16384;   // (read per call: the tests force either path)
-        // Beyond 512 members every call takes the table: the search kernel's 16-word instance keeps ~90 wave masks alive around
-        // its divergent chain searches, the compiler spills them, and the timestamps came back wrong AND different from run
-        // to run (1024 members x 100 k events, profiles/r06_order_search_16_words.txt) — it is not built.
-        const bool bulk = NW > 8 || (bulk_min > 0 && n_acc >= bulk_min);
-        hipStream_t tail = c->stream;   // the stream the last kernels of the call are on
-        if (bulk) {
-            // The table is built for GROUPS of consecutive round entries whose events fit SW_ORDER_SLAB_MB [256 per 256 columns: 4 groups per 1 M events — 128 and 512 are both 0.15-0.3 ms slower, profiles/r06_measured_and_dropped.txt]
-            // of table — a slab that stays allocated instead of one table as large as the can_see rows of everything the call
-            // orders — and there are TWO slabs: the samples, the sort and the read-back of group g run on a second stream
-            // beside the walk of group g + 1 (the walk is bound by its stores, the samples by their selection loops).
-            constexpr int P = order_tile(NW);
-            const int64_t slab_mb = getenv("SW_ORDER_SLAB_MB") ? atoll(getenv("SW_ORDER_SLAB_MB")) : 256 * std::max(1, NW / 4);
-            const int64_t pad = (int64_t)P * np;   // every chain rounds its positions up to whole tiles
-            const int64_t slab_pos = std::max<int64_t>(2 * pad, (slab_mb << 20) / ((int64_t)n * 4));
-            struct Group { int i0, i1; };
-            std::vector<Group> groups;
-            int64_t stride = 0;
-            for (int i0 = 0; i0 < nr;) {
-                int i1 = i0 + 1;
-                while (i1 < nr && acc_off[i1 + 1] - acc_off[i0] + pad <= slab_pos) ++i1;
-                if (acc_off[i1] > acc_off[i0]) { groups.push_back({i0, i1}); stride = std::max<int64_t>(stride, acc_off[i1] - acc_off[i0] + pad); }
-                i0 = i1;
-            }
-            // the planes of the members sit `stride` entries apart and are read / written at the same offsets at the same
-            // time: 4 KB x odd + 256 B between them, so that they spread over the memory channels whatever the interleaving
-            // granule (a power of two — 131 072 entries for a full slab — put all 256 planes' lines on one channel)
-            stride = (((stride + 1023) >> 10) | 1) * 1024 + 64;
-            const bool two = groups.size() > 1 && !getenv("SW_ORDER_ONE_STREAM");
-            CHK(dgrow(c, c->d_fd, (size_t)stride * n * (two ? 2 : 1), 0));
-            CHK(dgrow(c, c->d_grp, (OrderGroup::ints(np) + 2) * std::max<size_t>(groups.size(), 1), 0));
-            int32_t* d_gbounds = c->d_grp.p + OrderGroup::ints(np) * groups.size();
-            CHK(ensure_order_stage(c, groups.size() * 2));
-            for (size_t gi = 0; gi < groups.size(); ++gi) { c->h_ord_stage[2 * gi] = groups[gi].i0; c->h_ord_stage[2 * gi + 1] = groups[gi].i1; }
-            HIPCHK(c, hipMemcpyAsync(d_gbounds, c->h_ord_stage, groups.size() * 2 * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-            hipLaunchKernelGGL(k_order_group, dim3((unsigned)groups.size()), dim3(np), 0, c->stream, (const int*)c->d_ordat.p, (const int*)c->d_fwm.p,
-                               (const int*)c->d_chain_start.p, (const int*)c->d_chain_cnt.p, (const int*)c->d_chain_ev.p, (const int*)d_gbounds, n, np, P, c->d_grp.p);
-            c->ctr.kernel_launches++;
-            constexpr int CW = NW >= 4 ? 256 : 64 * NW;
-            const int ncg = np / CW;
-            int S = getenv("SW_ORDER_S") ? atoi(getenv("SW_ORDER_S")) : (1024 + n * ncg - 1) / (n * ncg);
-            S = std::min(std::max(S, 1), 64);
-            if (two) {
-                if (!c->stream_ord) HIPCHK(c, hipStreamCreateWithFlags(&c->stream_ord, hipStreamNonBlocking));
-                for (auto& st : c->stream_srt) if (!st) HIPCHK(c, hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
-                while (c->ord_events.size() < 3 * groups.size() + 3) {
-                    hipEvent_t e;
-                    HIPCHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-                    c->ord_events.push_back(e);
-                }
-            }
-            hipStream_t s1 = two ? c->stream_ord : c->stream;
-            lap("group");
-            CHK(consumer_preamble(s1));   // (the tables it reads are complete: the host has waited for them)
-            if (dbg) { (void)hipStreamSynchronize(s1); lap("preamble"); }
-            {   // timestamps in chain order from the position in front of every member's first unordered event on
-                CHK(dgrow(c, c->d_tch, c->d_chain_ev.cap, 0));
-                int longest = 1;
-                for (int m = 0; m < n; ++m) longest = std::max(longest, c->nev[m] - c->ord_pos[m] + 1);
-                hipLaunchKernelGGL(k_order_tchain, dim3(n, (unsigned)std::min(64, (longest + 255) / 256)), dim3(256), 0, s1, (const int*)c->d_chain_start.p,
-                                   (const int*)c->d_chain_cnt.p, (const int*)c->d_chain_ev.p, (const int*)c->d_ordpos.p, (const double*)c->d_t.p, c->d_tch.p);
-                c->ctr.kernel_launches++;
-            }
-            for (size_t gi = 0; gi < groups.size(); ++gi) {
-                const Group& g = groups[gi];
-                int* grp = c->d_grp.p + OrderGroup::ints(np) * gi;
-                int* fd = c->d_fd.p + (two && (gi & 1) ? (size_t)stride * n : 0);
-                const int64_t a0 = acc_off[g.i0], na = acc_off[g.i1] - a0;
-                if (two && gi >= 2) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ord_events[3 * (gi - 2) + 1], 0));   // the slab's last reader
-                hipLaunchKernelGGL(k_order_walk<CW>, dim3((unsigned)((size_t)n * ncg * S)), dim3(CW), 0, c->stream, (const int*)c->d_L.p,
-                                   (const int*)c->d_seq.p, (const int*)c->d_chain_start.p, (const int*)c->d_chain_ev.p, (const int*)c->d_ordat.p,
-                                   g.i0, g.i1, (const int*)grp, np, S, P, (long long)stride, fd);
-                if (dbg) { (void)hipStreamSynchronize(s1); lap("walk"); }
-                if (two) {
-                    HIPCHK(c, hipEventRecord(c->ord_events[3 * gi], c->stream));
-                    HIPCHK(c, hipStreamWaitEvent(s1, c->ord_events[3 * gi], 0));
-                }
-                hipLaunchKernelGGL((k_order_median<NW, P>), dim3((unsigned)(na / P + n)), dim3(256), 0, s1, (const int*)fd,
-                                   (long long)stride, (const int*)grp, (const int*)c->d_ordat.p, g.i0, g.i1, n, (const int*)d_fwseq,
-                                   (const long long*)d_acc_off, (const int*)d_seg_off, (const int*)c->d_chain_start.p, (const double*)c->d_tch.p,
-                                   c->d_ts.p, d_info);
-                if (dbg) { (void)hipStreamSynchronize(s1); lap("median"); }
-                hipStream_t s2 = s1;
-                if (two) {
-                    HIPCHK(c, hipEventRecord(c->ord_events[3 * gi + 1], s1));
-                    if (!getenv("SW_ORDER_SORT_INLINE")) {
-                        s2 = c->stream_srt[gi & 1];
-                        HIPCHK(c, hipStreamWaitEvent(s2, c->ord_events[3 * gi + 1], 0));
-                    }
-                }
-                c->ctr.kernel_launches += 2;
-                CHK(sort_and_fetch(s2, g.i0, g.i1, fetch_early));
-                if (two && fetch_early) HIPCHK(c, hipEventRecord(c->ord_events[3 * gi + 2], s2));
-            }
-            // (round entries that order nothing keep their zeroed flag and have nothing to sort)
-            if (two) {   // the side streams join the main one
-                hipStream_t side[3] = {c->stream_ord, c->stream_srt[0], c->stream_srt[1]};
-                for (int k = 0; k < 3; ++k) {
-                    hipEvent_t e = c->ord_events[3 * groups.size() + k];
-                    HIPCHK(c, hipEventRecord(e, side[k]));
-                    HIPCHK(c, hipStreamWaitEvent(c->stream, e, 0));
-                }
-            }
-            if (two && fetch_early && out_events && !getenv("SW_ORDER_HOST") && !getenv("SW_ORDER_LATE_COPY")) {
-                // the caller's copy of the order, group by group as it arrives, while the device works on the later groups
-                for (size_t gi = 0; gi < groups.size(); ++gi) {
-                    HIPCHK(c, hipEventSynchronize(c->ord_events[3 * gi + 2]));
-                    const int64_t a0 = acc_off[groups[gi].i0], a1 = std::min<int64_t>(acc_off[groups[gi].i1], cap);
-                    if (a1 > a0) memcpy(out_events + a0, sorted + a0, (size_t)(a1 - a0) * sizeof(int32_t));
-                }
-                copied_early_ok = true;
-            }
-            lap("walk+median");
-        } else {
-            CHK(consumer_preamble(c->stream));
-            if constexpr (NW <= 8) {
-                hipLaunchKernelGGL(k_order_times<NW>, dim3((unsigned)((n_acc + 3) / 4)), dim3(256), 0, c->stream,
-                                   (const int*)c->d_acc_ev.p, (const int*)c->d_acc_ri.p, (int)n_acc, (const int*)c->d_fwm.p,
-                                   (const int*)c->d_L.p, (const int*)c->d_cr.p, (const int*)c->d_seq.p,
-                                   (const double*)c->d_t.p, (const int*)c->d_chain_start.p, (const int*)c->d_chain_ev.p,
-                                   (const int*)c->d_ordpos.p, c->d_ts.p, d_info);
-                c->ctr.kernel_launches++;
-            }
-            CHK(sort_and_fetch(c->stream, 0, nr, fetch_early));
-        }
-        if (!big_ri.empty()) {
-            CHK(dgrow(c, c->d_big_ri, big_ri.size(), 0));
-            CHK(dgrow(c, c->d_big_off, big_off.size(), 0));
-            CHK(dgrow(c, c->d_sk_ts, (size_t)big_off.back(), 0));
-            CHK(dgrow(c, c->d_sk_k8, (size_t)big_off.back(), 0));
-            CHK(dgrow(c, c->d_sk_ev, (size_t)big_off.back(), 0));
-            // (pageable sources: the copies are staged before the call returns)
-            HIPCHK(c, hipMemcpyAsync(c->d_big_ri.p, big_ri.data(), big_ri.size() * sizeof(int32_t), hipMemcpyHostToDevice, tail));
-            HIPCHK(c, hipMemcpyAsync(c->d_big_off.p, big_off.data(), big_off.size() * sizeof(long long), hipMemcpyHostToDevice, tail));
-            hipLaunchKernelGGL(k_order_sort_big, dim3((unsigned)big_ri.size()), dim3(1024), 0, tail, (const int*)c->d_big_ri.p,
-                               (const long long*)c->d_big_off.p, (const int*)c->d_acc_ev.p, (const long long*)d_acc_off,
-                               (const double*)c->d_ts.p, (const unsigned char*)c->d_sig.p, (const unsigned char*)c->d_white.p,
-                               c->d_sk_ts.p, c->d_sk_k8.p, c->d_sk_ev.p, c->d_sorted.p, c->d_hostflag.p);
-            c->ctr.kernel_launches++;
-            HIPCHK(c, hipMemcpyAsync(sorted, c->d_sorted.p, n_acc * sizeof(int32_t), hipMemcpyDeviceToHost, tail));
-        }
-        lap("sort kernels");
-        HIPCHK(c, hipMemcpyAsync(c->h_ord + h_blk_off, d_info, sizeof(OrderInfo), hipMemcpyDeviceToHost, tail));
-        HIPCHK(c, hipMemcpyAsync(hostflag, c->d_hostflag.p, nr * sizeof(int32_t), hipMemcpyDeviceToHost, tail));
-        HIPCHK(c, hipStreamSynchronize(tail));
-        HIPCHK(c, hipGetLastError());
-        if (h_info->index_err) {
-            c->transactions.resize(tx_at);   // nothing of this call is kept
-            return fail(c, SW_ERANGE, "find_order: an event is seen by a single famous witness (IndexError at swirld.py:305)");
-        }
-        bool any_flag = false;
-        if (getenv("SW_ORDER_HOST")) std::fill(hostflag, hostflag + nr, 1);  // test hook: host sort
-        for (int i = 0; i < nr; ++i) { any_flag = any_flag || hostflag[i]; c->ctr.order_rounds_host_sorted += hostflag[i] ? 1 : 0; }
-        any_host_sorted = any_flag;
-        if (any_flag) {  // rare: oversize round or a (ts, 8-byte key) tie: the host needs ts, the whitening keys and the signatures
-            acc_ev.resize((size_t)n_acc);
-            ts.resize((size_t)n_acc);
-            white_h.resize((size_t)nr * 64);
-            HIPCHK(c, hipMemcpyAsync(ts.data(), c->d_ts.p, n_acc * sizeof(double), hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(c, hipMemcpyAsync(acc_ev.data(), c->d_acc_ev.p, n_acc * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(c, hipMemcpyAsync(white_h.data(), c->d_white.p, white_h.size(), hipMemcpyDeviceToHost, c->stream));
-            HIPCHK(c, hipStreamSynchronize(c->stream));
-            CHK(ensure_sig_h(c));
+    o.clk.lap(c, "tables");
+    if (o.h.info->undecided_ri != 0x7fffffff)
+        return fail(c, SW_EINVAL, "find_order: round %d has an undecided witness (KeyError on self.famous[w], swirld.py:284)", o.rounds[o.h.info->undecided_ri]);
+    o.n_acc = o.h.info->n_acc;
+    if (o.n_acc > 0x7ffffff0ll) return fail(c, SW_ERANGE, "find_order: more than 2^31 events in one call");
+    return SW_OK;
+}
+
+// ---- phase: room for the call's events: its part of `transactions` (from here on OrderRollback gives it back), the
+// per-event buffers, the consensus tables
+int order_reserve(sw_ctx* c, OrderCall& o) {
+    const int nr = o.nr;
+    const int64_t n_acc = o.n_acc;
+    std::fill(o.hostflag, o.hostflag + nr, 0);
+    if (!c->transactions.resize(o.tx_at + (size_t)n_acc)) return fail(c, SW_ENOMEM, "pinned host memory for the ordered events");   // the device-sorted order lands in place
+    o.sorted = c->transactions.data() + o.tx_at;
+    if (!n_acc) return SW_OK;
+    CHK(dgrow(c, c->d_acc_ev, n_acc, 0));
+    CHK(dgrow(c, c->d_acc_ri, n_acc, 0));
+    CHK(dgrow(c, c->d_ts, n_acc, 0));
+    CHK(dgrow(c, c->d_white, (size_t)nr * 64, 0));
+    CHK(dgrow(c, c->d_sorted, n_acc, 0));
+    CHK(dgrow(c, c->d_hostflag, nr, 0));
+    CHK(consensus_reserve(c, o.tx_at + (size_t)n_acc));
+    return SW_OK;
+}
+
+// ---- phase: which sorts, which samples
+void plan_order_sorts(const sw_ctx* c, OrderCall& o) {
+    // rounds too large for the LDS sort: the same network over global scratch, one workgroup per such round (behind everything else)
+    for (int i = 0; i < o.nr; ++i) {
+        const int64_t len = o.h.acc_off[i + 1] - o.h.acc_off[i];
+        if (len <= SORT_CAP || o.k.big_host) continue;
+        int64_t m = 1;
+        while (m < len) m <<= 1;
+        o.big_ri.push_back(i);
+        o.big_off.push_back(o.big_off.back() + m);
+    }
+    o.fetch_early = o.big_ri.empty();   // (oversize rounds are sorted last: then the whole order travels at the end)
+    // A call that orders many events: the first-descendant table (k_order_walk) instead of one binary search per
+    // (event, famous witness) pair.  Same samples, by construction and by test (SW_ORDER_BULK=<events> moves the
+    // threshold, 0 = never).
+    // Beyond 512 members every call takes the table: the search kernel's 16-word instance keeps ~90 wave masks alive around
+    // its divergent chain searches, the compiler spills them, and the timestamps came back wrong AND different from run
+    // to run (1024 members x 100 k events, profiles/r06_order_search_16_words.txt) — it is not built.
+    o.bulk = c->nw > 8 || (o.k.bulk_min > 0 && o.n_acc >= o.k.bulk_min);
+}
+
+// ---- phase: groups and slabs of a bulk call.
+// The table is built for GROUPS of consecutive round entries whose events fit SW_ORDER_SLAB_MB
+// of table — a slab that stays allocated instead of one table as large as the can_see rows of everything the call
+// orders — and there are TWO slabs: the samples, the sort and the read-back of group g run on a second stream
+// beside the walk of group g + 1 (the walk is bound by its stores, the samples by their selection loops).
+int plan_order_groups(sw_ctx* c, OrderCall& o) {
+    const int np = c->npad, n = c->n, nr = o.nr, P = order_tile(c->nw);
+    const long long* acc_off = o.h.acc_off;
+    const int64_t pad = (int64_t)P * np;   // every chain rounds its positions up to whole tiles
+    const int64_t slab_pos = std::max<int64_t>(2 * pad, (o.k.slab_mb << 20) / ((int64_t)n * 4));
+    int64_t stride = 0;
+    for (int i0 = 0; i0 < nr;) {
+        int i1 = i0 + 1;
+        while (i1 < nr && acc_off[i1 + 1] - acc_off[i0] + pad <= slab_pos) ++i1;
+        if (acc_off[i1] > acc_off[i0]) { o.groups.push_back({i0, i1}); stride = std::max<int64_t>(stride, acc_off[i1] - acc_off[i0] + pad); }
+        i0 = i1;
+    }
+    // the planes of the members sit `stride` entries apart and are read / written at the same offsets at the same
+    // time: 4 KB x odd + 256 B between them, so that they spread over the memory channels whatever the interleaving
+    // granule (a power of two — 131 072 entries for a full slab — put all 256 planes' lines on one channel)
+    o.stride = (((stride + 1023) >> 10) | 1) * 1024 + 64;
+    const size_t ng = o.groups.size();
+    o.two = ng > 1 && !o.k.one_stream;
+    CHK(dgrow(c, c->d_fd, (size_t)o.stride * n * (o.two ? 2 : 1), 0));
+    CHK(dgrow(c, c->d_grp, (OrderGroup::ints(np) + 2) * std::max<size_t>(ng, 1), 0));
+    int32_t* d_gbounds = c->d_grp.p + OrderGroup::ints(np) * ng;
+    CHK(ensure_order_stage(c, ng * 2));
+    for (size_t gi = 0; gi < ng; ++gi) { c->h_ord_stage[2 * gi] = o.groups[gi].i0; c->h_ord_stage[2 * gi + 1] = o.groups[gi].i1; }
+    HIPCHK(c, hipMemcpyAsync(d_gbounds, c->h_ord_stage, ng * 2 * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(k_order_group, dim3((unsigned)ng), dim3(np), 0, c->stream, (const int*)c->d_ordat.p, (const int*)c->d_fwm.p,
+                       (const int*)c->d_chain_start.p, (const int*)c->d_chain_cnt.p, (const int*)c->d_chain_ev.p, (const int*)d_gbounds, n, np, P, c->d_grp.p);
+    c->ctr.kernel_launches++;
+    if (o.two) {
+        if (!c->stream_ord) HIPCHK(c, hipStreamCreateWithFlags(&c->stream_ord, hipStreamNonBlocking));
+        for (auto& st : c->stream_srt) if (!st) HIPCHK(c, hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+        while (c->ord_events.size() < 3 * ng + 3) {   // per group: table walked / table consumed / order on the host; then the ends of the three side streams
+            hipEvent_t e;
+            HIPCHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+            c->ord_events.push_back(e);
         }
     }
-    lap("read-back");
-    // final order inside each round: (consensus timestamp, whitened signature), swirld.py:306
+    o.s1 = o.two ? c->stream_ord : c->stream;
+    return SW_OK;
+}
+
+// ---- phase: what only the consumers of the table need (the ordered events round-major, the whitening keys, cleared flags):
+// enqueued on THEIR stream, beside the first walk (the tables it reads are complete: the host has waited for them)
+int consumer_preamble(sw_ctx* c, const OrderCall& o, hipStream_t st) {
+    const int np = c->npad, nr = o.nr;
+    HIPCHK(c, hipMemsetAsync(c->d_hostflag.p, 0, nr * sizeof(int32_t), st));
+    hipLaunchKernelGGL(k_order_segments, dim3((unsigned)(((size_t)nr * np + 255) / 256)), dim3(256), 0, st, (const int*)o.d_seg_start,
+                       (const int*)o.d_seg_len, (const int*)o.d_seg_off, (const long long*)o.d.acc_off, (const int*)c->d_chain_start.p,
+                       (const int*)c->d_chain_ev.p, np, nr * np, c->d_acc_ev.p, c->d_acc_ri.p);
+    hipLaunchKernelGGL(k_order_white, dim3(nr), dim3(1024), 0, st, (const int*)c->d_fwm.p, c->n, np,
+                       (const unsigned char*)c->d_sig.p, c->d_white.p);
+    c->ctr.kernel_launches += 2;
+    return SW_OK;
+}
+
+// ... and, for the samples of a bulk call, the timestamps in chain order from the position in front of every member's first
+// unordered event on
+int enqueue_tchain(sw_ctx* c, const OrderCall& o) {
+    const int n = c->n;
+    CHK(dgrow(c, c->d_tch, c->d_chain_ev.cap, 0));
+    int longest = 1;
+    for (int m = 0; m < n; ++m) longest = std::max(longest, c->nev[m] - c->ord_pos[m] + 1);
+    hipLaunchKernelGGL(k_order_tchain, dim3(n, (unsigned)std::min(64, (longest + 255) / 256)), dim3(256), 0, o.s1, (const int*)c->d_chain_start.p,
+                       (const int*)c->d_chain_cnt.p, (const int*)c->d_chain_ev.p, (const int*)c->d_ordpos.p, (const double*)c->d_t.p, c->d_tch.p);
+    c->ctr.kernel_launches++;
+    return SW_OK;
+}
+
+// device sort of the round entries [i0, i1) by (ts, first 8 whitened key bytes), then their part of the order to the host
+int sort_and_fetch(sw_ctx* c, const OrderCall& o, hipStream_t st, int i0, int i1) {
+    hipLaunchKernelGGL(k_order_sort, dim3(i1 - i0), dim3(1024), 0, st, (const int*)c->d_acc_ev.p,
+                       (const long long*)o.d.acc_off, (const double*)c->d_ts.p, (const unsigned char*)c->d_sig.p,
+                       (const unsigned char*)c->d_white.p, i0, c->d_sorted.p, c->d_hostflag.p);
+    c->ctr.kernel_launches++;
+    const int64_t a0 = o.h.acc_off[i0], na = o.h.acc_off[i1] - a0;
+    if (o.fetch_early && na) HIPCHK(c, hipMemcpyAsync(o.sorted + a0, c->d_sorted.p + a0, na * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    return SW_OK;
+}
+
+// ---- phase: one group: its walk on the main stream into the slab of its parity, its samples on s1, its sort and the
+// read-back of its part of the order on a sort stream of its parity.  Events 3 gi / 3 gi + 1 / 3 gi + 2: table walked /
+// table consumed / order on the host.
+template <int NW>
+int enqueue_group(sw_ctx* c, OrderCall& o, size_t gi) {
+    constexpr int P = order_tile(NW), CW = order_cw(NW);
+    const int np = c->npad, n = c->n, ncg = np / CW, S = o.k.S;
+    const OrderSpan& g = o.groups[gi];
+    const bool two = o.two;
+    hipStream_t s1 = o.s1;
+    int* grp = c->d_grp.p + OrderGroup::ints(np) * gi;
+    int* fd = c->d_fd.p + (two && (gi & 1) ? (size_t)o.stride * n : 0);
+    const int64_t na = o.h.acc_off[g.i1] - o.h.acc_off[g.i0];
+    if (two && gi >= 2) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ord_events[3 * (gi - 2) + 1], 0));   // the slab's last reader
+    hipLaunchKernelGGL(k_order_walk<CW>, dim3((unsigned)((size_t)n * ncg * S)), dim3(CW), 0, c->stream, (const int*)c->d_L.p,
+                       (const int*)c->d_seq.p, (const int*)c->d_chain_start.p, (const int*)c->d_chain_ev.p, (const int*)c->d_ordat.p,
+                       g.i0, g.i1, (const int*)grp, np, S, P, (long long)o.stride, fd);
+    o.clk.lap(c, "walk", s1);
+    if (two) {
+        HIPCHK(c, hipEventRecord(c->ord_events[3 * gi], c->stream));
+        HIPCHK(c, hipStreamWaitEvent(s1, c->ord_events[3 * gi], 0));
+    }
+    hipLaunchKernelGGL((k_order_median<NW, P>), dim3((unsigned)(na / P + n)), dim3(256), 0, s1, (const int*)fd,
+                       (long long)o.stride, (const int*)grp, (const int*)c->d_ordat.p, g.i0, g.i1, n, (const int*)o.d_fwseq,
+                       (const long long*)o.d.acc_off, (const int*)o.d_seg_off, (const int*)c->d_chain_start.p, (const double*)c->d_tch.p,
+                       c->d_ts.p, o.d.info);
+    o.clk.lap(c, "median", s1);
+    hipStream_t s2 = s1;
+    if (two) {
+        HIPCHK(c, hipEventRecord(c->ord_events[3 * gi + 1], s1));
+        if (!o.k.sort_inline) {
+            s2 = c->stream_srt[gi & 1];
+            HIPCHK(c, hipStreamWaitEvent(s2, c->ord_events[3 * gi + 1], 0));
+        }
+    }
+    c->ctr.kernel_launches += 2;
+    CHK(sort_and_fetch(c, o, s2, g.i0, g.i1));
+    if (two && o.fetch_early) HIPCHK(c, hipEventRecord(c->ord_events[3 * gi + 2], s2));
+    return SW_OK;
+}
+
+// ---- phase: the side streams join the main one (round entries that order nothing keep their zeroed flag and have nothing to
+// sort), then the early copy to the caller
+int join_and_copy_early(sw_ctx* c, OrderCall& o) {
+    if (!o.two) return SW_OK;
+    hipStream_t side[3] = {c->stream_ord, c->stream_srt[0], c->stream_srt[1]};
+    for (int k = 0; k < 3; ++k) {
+        hipEvent_t e = c->ord_events[3 * o.groups.size() + k];
+        HIPCHK(c, hipEventRecord(e, side[k]));
+        HIPCHK(c, hipStreamWaitEvent(c->stream, e, 0));
+    }
+    // the caller's copy of the order, group by group as it arrives, while the device works on the later groups
+    if (!(o.fetch_early && o.out_events && !o.k.host && !o.k.late_copy)) return SW_OK;
+    for (size_t gi = 0; gi < o.groups.size(); ++gi) {
+        HIPCHK(c, hipEventSynchronize(c->ord_events[3 * gi + 2]));
+        const int64_t a0 = o.h.acc_off[o.groups[gi].i0], a1 = std::min<int64_t>(o.h.acc_off[o.groups[gi].i1], o.cap);
+        if (a1 > a0) memcpy(o.out_events + a0, o.sorted + a0, (size_t)(a1 - a0) * sizeof(int32_t));
+    }
+    o.copied_early = true;
+    return SW_OK;
+}
+
+// ---- phase: a small call: one search per (event, famous witness) pair and one sort, all on the main stream
+template <int NW>
+int order_small_call(sw_ctx* c, const OrderCall& o) {
+    CHK(consumer_preamble(c, o, c->stream));
+    if constexpr (NW <= 8) {
+        hipLaunchKernelGGL(k_order_times<NW>, dim3((unsigned)((o.n_acc + 3) / 4)), dim3(256), 0, c->stream,
+                           (const int*)c->d_acc_ev.p, (const int*)c->d_acc_ri.p, (int)o.n_acc, (const int*)c->d_fwm.p,
+                           (const int*)c->d_L.p, (const int*)c->d_cr.p, (const int*)c->d_seq.p,
+                           (const double*)c->d_t.p, (const int*)c->d_chain_start.p, (const int*)c->d_chain_ev.p,
+                           (const int*)c->d_ordpos.p, c->d_ts.p, o.d.info);
+        c->ctr.kernel_launches++;
+    }
+    return sort_and_fetch(c, o, c->stream, 0, o.nr);
+}
+
+// ---- phase: the oversize rounds, sorted over global scratch behind everything else; then the whole order travels at once
+int sort_big_rounds(sw_ctx* c, const OrderCall& o) {
+    if (o.big_ri.empty()) return SW_OK;
+    CHK(dgrow(c, c->d_big_ri, o.big_ri.size(), 0));
+    CHK(dgrow(c, c->d_big_off, o.big_off.size(), 0));
+    CHK(dgrow(c, c->d_sk_ts, (size_t)o.big_off.back(), 0));
+    CHK(dgrow(c, c->d_sk_k8, (size_t)o.big_off.back(), 0));
+    CHK(dgrow(c, c->d_sk_ev, (size_t)o.big_off.back(), 0));
+    // (pageable sources: the copies are staged before the call returns)
+    HIPCHK(c, hipMemcpyAsync(c->d_big_ri.p, o.big_ri.data(), o.big_ri.size() * sizeof(int32_t), hipMemcpyHostToDevice, o.tail));
+    HIPCHK(c, hipMemcpyAsync(c->d_big_off.p, o.big_off.data(), o.big_off.size() * sizeof(long long), hipMemcpyHostToDevice, o.tail));
+    hipLaunchKernelGGL(k_order_sort_big, dim3((unsigned)o.big_ri.size()), dim3(1024), 0, o.tail, (const int*)c->d_big_ri.p,
+                       (const long long*)c->d_big_off.p, (const int*)c->d_acc_ev.p, (const long long*)o.d.acc_off,
+                       (const double*)c->d_ts.p, (const unsigned char*)c->d_sig.p, (const unsigned char*)c->d_white.p,
+                       c->d_sk_ts.p, c->d_sk_k8.p, c->d_sk_ev.p, c->d_sorted.p, c->d_hostflag.p);
+    c->ctr.kernel_launches++;
+    HIPCHK(c, hipMemcpyAsync(o.sorted, c->d_sorted.p, o.n_acc * sizeof(int32_t), hipMemcpyDeviceToHost, o.tail));
+    return SW_OK;
+}
+
+// ---- phase: the final read-back and the second of the call's two synchronisations: OrderInfo again (the samples' error
+// word), the rounds the device left to the host; only for those a third one, behind the copies their host sort needs
+int order_read_back(sw_ctx* c, OrderCall& o) {
+    const int nr = o.nr;
+    HIPCHK(c, hipMemcpyAsync(o.h.info, o.d.info, sizeof(OrderInfo), hipMemcpyDeviceToHost, o.tail));
+    HIPCHK(c, hipMemcpyAsync(o.hostflag, c->d_hostflag.p, nr * sizeof(int32_t), hipMemcpyDeviceToHost, o.tail));
+    HIPCHK(c, hipStreamSynchronize(o.tail));
+    HIPCHK(c, hipGetLastError());
+    if (o.h.info->index_err)   // (nothing of this call is kept)
+        return fail(c, SW_ERANGE, "find_order: an event is seen by a single famous witness (IndexError at swirld.py:305)");
+    if (o.k.host) std::fill(o.hostflag, o.hostflag + nr, 1);  // test hook: host sort
+    for (int i = 0; i < nr; ++i) { o.any_host_sorted = o.any_host_sorted || o.hostflag[i]; c->ctr.order_rounds_host_sorted += o.hostflag[i] ? 1 : 0; }
+    if (!o.any_host_sorted) return SW_OK;
+    // rare: oversize round or a (ts, 8-byte key) tie: the host needs ts, the whitening keys and the signatures
+    o.acc_ev.resize((size_t)o.n_acc);
+    o.ts.resize((size_t)o.n_acc);
+    o.white_h.resize((size_t)nr * 64);
+    HIPCHK(c, hipMemcpyAsync(o.ts.data(), c->d_ts.p, o.n_acc * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(o.acc_ev.data(), c->d_acc_ev.p, o.n_acc * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(o.white_h.data(), c->d_white.p, o.white_h.size(), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    CHK(ensure_sig_h(c));
+    return SW_OK;
+}
+
+// ---- phase: the final order inside each round the device left to the host: (consensus timestamp, whitened signature), swirld.py:306
+void host_sort_rounds(const sw_ctx* c, OrderCall& o) {
     struct Item { double ts; uint64_t k8; int32_t ev; };
-    int64_t produced = 0;
+    const unsigned char* sig = c->sig_h.data();
     std::vector<Item> items;
-    for (int i = 0; i < nr; ++i) {
-        if (!n_acc || !hostflag[i]) {  // sorted on the device: already in `transactions`
-            produced += acc_off[i + 1] - acc_off[i];
+    for (int i = 0; i < o.nr; ++i) {
+        if (!o.n_acc || !o.hostflag[i]) {  // sorted on the device: already in `transactions`
+            o.produced += o.h.acc_off[i + 1] - o.h.acc_off[i];
             continue;
         }
-        const unsigned char* white = white_h.data() + (size_t)i * 64;  // swirld.py:285
+        const unsigned char* white = o.white_h.data() + (size_t)i * 64;  // swirld.py:285
         items.clear();
-        for (int64_t a = acc_off[i]; a < acc_off[i + 1]; ++a) {
-            Item it{ts[a], 0, acc_ev[a]};
-            const unsigned char* sg = c->sig_h.data() + (size_t)acc_ev[a] * 64;
+        for (int64_t a = o.h.acc_off[i]; a < o.h.acc_off[i + 1]; ++a) {
+            Item it{o.ts[a], 0, o.acc_ev[a]};
+            const unsigned char* sg = sig + (size_t)o.acc_ev[a] * 64;
             for (int b = 0; b < 8; ++b) it.k8 = (it.k8 << 8) | (unsigned char)(white[b] ^ sg[b]);
             items.push_back(it);
         }
-        std::sort(items.begin(), items.end(), [&](const Item& x, const Item& y) {
+        std::sort(items.begin(), items.end(), [sig, white](const Item& x, const Item& y) {
             if (x.ts != y.ts) return x.ts < y.ts;
             if (x.k8 != y.k8) return x.k8 < y.k8;
-            const unsigned char* sx = c->sig_h.data() + (size_t)x.ev * 64;
-            const unsigned char* sy = c->sig_h.data() + (size_t)y.ev * 64;
+            const unsigned char* sx = sig + (size_t)x.ev * 64;
+            const unsigned char* sy = sig + (size_t)y.ev * 64;
             for (int b = 8; b < 64; ++b) {
                 const unsigned char kx = white[b] ^ sx[b], ky = white[b] ^ sy[b];
                 if (kx != ky) return kx < ky;
             }
             return x.ev < y.ev;
         });
-        for (const Item& it : items) sorted[produced++] = it.ev;   // swirld.py:307-309
+        for (const Item& it : items) o.sorted[o.produced++] = it.ev;   // swirld.py:307-309
     }
-    if (out_events && n_acc && !(copied_early_ok && !any_host_sorted)) memcpy(out_events, sorted, (size_t)std::min<int64_t>(n_acc, cap) * sizeof(int32_t));
-    lap("sort");
-    if (n_acc) CHK(consensus_record(c, n_acc, tx_at, nr, acc_off, hostflag, sorted));   // (the call keeps its result from here on, SW_ERANGE below included)
-    std::copy(h_ordnew, h_ordnew + n, c->ord_pos.begin());
+}
+
+// ---- phase: the end of a call, which keeps its result from here on (SW_ERANGE for a short out_events included; a failure inside
+// consensus_record poisons the context instead): the caller's copy in one piece, the device's copy of the order and its
+// two values per event, the members' ordered prefixes, the window.  Who copies the order to the caller: join_and_copy_early, group
+// by group, when the call has two slabs, no oversize round and neither SW_ORDER_HOST nor SW_ORDER_LATE_COPY; the copy here
+// otherwise — and AGAIN after an early copy when the host re-sorted a round, which the early copy took as the device left it.
+int finish_order(sw_ctx* c, OrderCall& o, int64_t* n_out) {
+    if (o.out_events && o.n_acc && !(o.copied_early && !o.any_host_sorted)) memcpy(o.out_events, o.sorted, (size_t)std::min<int64_t>(o.n_acc, o.cap) * sizeof(int32_t));
+    o.clk.lap(c, "sort");
+    if (o.n_acc) CHK(consensus_record(c, o.n_acc, o.tx_at, o.nr, o.h.acc_off, o.hostflag, o.sorted));
+    std::copy(o.h.ordnew, o.h.ordnew + c->n, c->ord_pos.begin());
     CHK(window_evict(c));
-    if (n_out) *n_out = produced;
-    if (produced > cap) return fail(c, SW_ERANGE, "find_order: out_events capacity %lld < %lld", (long long)cap, (long long)produced);
+    if (n_out) *n_out = o.produced;
+    if (o.produced > o.cap) return fail(c, SW_ERANGE, "find_order: out_events capacity %lld < %lld", (long long)o.cap, (long long)o.produced);
     return SW_OK;
+}
+
+template <int NW>
+int do_find_order(sw_ctx* c, std::vector<int32_t> rounds, int32_t* out_events, int64_t cap, int64_t* n_out) {
+    if (rounds.empty()) return SW_OK;
+    if (c->payload_pending) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_payload, 0));  // timestamps / signatures of a bulk append
+    CHK(order_rounds_arg(c, rounds));
+    OrderCall o(c, std::move(rounds), out_events, cap);
+    CHK(stage_order_call(c, o));
+    CHK(order_tables<NW>(c, o));
+    OrderRollback undo{c, o, true};
+    CHK(order_reserve(c, o));
+    if (o.n_acc) {
+        plan_order_sorts(c, o);
+        if (o.bulk) {
+            CHK(plan_order_groups(c, o));
+            o.clk.lap(c, "group");
+            CHK(consumer_preamble(c, o, o.s1));
+            o.clk.lap(c, "preamble", o.s1);
+            CHK(enqueue_tchain(c, o));
+            for (size_t gi = 0; gi < o.groups.size(); ++gi) CHK(enqueue_group<NW>(c, o, gi));
+            CHK(join_and_copy_early(c, o));
+            o.clk.lap(c, "walk+median");
+        } else {
+            CHK(order_small_call<NW>(c, o));
+        }
+        CHK(sort_big_rounds(c, o));
+        o.clk.lap(c, "sort kernels");
+        CHK(order_read_back(c, o));
+    }
+    o.clk.lap(c, "read-back");
+    host_sort_rounds(c, o);
+    undo.armed = false;
+    return finish_order(c, o, n_out);
 }
 
 
@@ -3188,12 +3370,9 @@ int exact_fame(sw_ctx* c, int32_t* new_rounds, int cap, int* n_new) {
 }
 
 int exact_order(sw_ctx* c, std::vector<int32_t> rounds, int32_t* out_events, int64_t cap, int64_t* n_out) {
-    std::sort(rounds.begin(), rounds.end());  // sorted(new_c), swirld.py:283
-    rounds.erase(std::unique(rounds.begin(), rounds.end()), rounds.end());
+    CHK(order_rounds_arg(c, rounds));
     const int nr = (int)rounds.size();
     if (nr == 0) return SW_OK;
-    if (rounds.front() < 0 || rounds.back() >= c->R)
-        return fail(c, SW_ERANGE, "find_order: round outside [0, %d) (KeyError in the reference)", c->R);
     CHK(exact_grow(c));
     CHK(dgrow(c, c->x_rounds, nr, 0));
     HIPCHK(c, hipMemcpyAsync(c->x_rounds.p, rounds.data(), (size_t)nr * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));

@@ -36,6 +36,7 @@ def test_argument_errors(pkg):
     assert list(h.decide_fame()) == []
     assert code(pkg, h.find_order, [0]) == -22                    # round 0 undecided (KeyError)
     assert code(pkg, h.find_order, [7]) == -34
+    assert h.num_ordered == 0 and len(h.transactions()) == 0      # a failed find_order keeps nothing
     assert list(h.find_order([])) == []
     assert h.vote(0, 0, 0, 1) == -1
     # the context is still usable

@@ -138,3 +138,37 @@ def test_rounds_larger_than_the_lds_sort(pkg, monkeypatch, big_host):
     hs = h.counters()["order_rounds_host_sorted"]
     assert (hs > 0) if big_host else (hs == 0)
     h.close()
+
+
+@pytest.mark.parametrize("bulk", ["1", "0"])   # the table / the searches
+def test_short_out_events_keeps_the_order(pkg, monkeypatch, bulk):
+    """sw_find_order with an out_events shorter than what the call orders: SW_ERANGE with the full count in n_out, and the
+    call KEEPS its result — sw_num_ordered and sw_get_transactions hold the oracle's whole order, and the next call goes on
+    from there."""
+    import ctypes as C
+    from oracle.oracle import Oracle
+    monkeypatch.setenv("SW_ORDER_BULK", bulk)
+    n, N, N2 = 16, 4000, 6000
+    cr, sp, op, t, sig = pkg.synth_hashgraph(n, N2, 95)
+    o, h = Oracle(n), pkg.Hashgraph(n)
+    for d in (o, h):
+        d.append_events(cr[:N], sp[:N], op[:N], t[:N], sig[:N])
+        d.divide_rounds(0, N)
+    nco, nch = o.decide_fame(), h.decide_fame()
+    assert list(nco) == list(nch)
+    exp = np.asarray(o.find_order(nco))
+    cap = len(exp) // 2
+    assert cap > 100
+    rounds = np.ascontiguousarray(sorted(int(r) for r in nch), np.int32)
+    out, n_out = np.full(cap, -1, np.int32), C.c_int64(-1)
+    rc = h._L.sw_find_order(h._h, rounds.ctypes.data_as(C.c_void_p), len(rounds), out.ctypes.data_as(C.c_void_p), cap, C.byref(n_out))
+    assert rc == -34 and n_out.value == len(exp)          # SW_ERANGE
+    assert h.num_ordered == len(exp) and np.array_equal(h.transactions(), exp)
+    for d in (o, h):
+        d.append_events(cr[N:], sp[N:], op[N:], t[N:], sig[N:])
+        d.divide_rounds(N, N2 - N)
+    nco, nch = o.decide_fame(), h.decide_fame()
+    assert list(nco) == list(nch) and len(nch) > 0
+    assert list(h.find_order(nch)) == list(o.find_order(nco))
+    assert np.array_equal(h.transactions(), o.transactions) and h.num_ordered == len(o.transactions)
+    h.close()

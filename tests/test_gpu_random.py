@@ -70,8 +70,10 @@ def test_random_shapes(pkg, monkeypatch, seed):
         try:
             exp = list(o.find_order(nco))
         except Exception:  # IndexError of swirld.py:305 (single seeing witness, weighted stakes)
+            before = h.transactions()
             with pytest.raises(pkg.SwirldHipError):
                 h.find_order(nch)
+            assert h.num_ordered == len(before) and np.array_equal(h.transactions(), before)   # a failed call keeps nothing
             return
         assert list(h.find_order(nch)) == exp
     assert np.array_equal(h.rounds(), o.round)
