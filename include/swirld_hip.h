@@ -141,7 +141,8 @@ int sw_get_ingest_stats(sw_ctx* ctx, int64_t* device_batches, int64_t* device_ev
  *   sw_append_events_device's; a host pointer is SW_EINVAL before any launch); the three id arrays must be 8-byte aligned
  *   (SW_EINVAL).  Per event: d_id32 its id; d_sp_id32 / d_op_id32 the parents' ids (ignored when the arity is 0); d_arity
  *   (uint8) the number of parents claimed, len(ev.p); d_creator a dense member index; d_ok (uint8, NULL = all 1) 1 when
- *   signature and hash were verified (what sw_crypto_verify_batch wrote, ANDed with the caller's hash comparison); d_t,
+ *   signature and hash were verified (what sw_validate_payload_device left, or what sw_crypto_verify_batch wrote ANDed
+ *   with the caller's hash comparison); d_t,
  *   d_sig64 nullable as for sw_append_events_device; user_stream as there.  d_index_out: K int32 in device memory;
  *   *n_stored (host): the events stored.  index_out[i] is
  *     an index <  the event count before the call   the id is stored already (nothing is stored again)
@@ -429,6 +430,54 @@ int sw_get_consensus_stats(sw_ctx* ctx, int64_t* record_calls, int64_t* recorded
 int sw_crypto_verify_batch(int device, int64_t K, const uint8_t* msgs, const int64_t* msg_off,
                            const uint8_t* sig64, const uint8_t* pk32, uint8_t* ok);
 int sw_crypto_hash_batch(int device, int64_t K, const uint8_t* msgs, const int64_t* msg_off, uint8_t* out32);
+
+/*
+ * Validating a payload ON THE DEVICE against the member keys (the crypto of Node.is_valid_event, swirld.py:97-103; kernels
+ * in csrc/validate.hip.h).  A hashgraph's members are fixed, so the context keeps a table of fixed-base
+ * multiples of every member's key (48 KB per member) and a verification is 128 table additions and one inversion.  The
+ * verdicts are left in device memory: they are the d_ok sw_ingest_payload_device takes.
+ *
+ * sw_set_member_keys   pk32: n_members * 32 bytes in HOST memory, key m the Ed25519 public key of member m.  Builds the
+ *   table on the device (one kernel, one synchronisation).  A key libsodium 1.0.18 refuses (non-canonical, small order, not
+ *   on the curve) makes its member UNUSABLE: every event of that member is invalid; *n_unusable (may be NULL) counts them.
+ *   Keys survive sw_rewind and sw_reset; setting keys again rebuilds the table.
+ * sw_get_member_keys   the keys as set and one byte per member, 1 = usable (either pointer may be NULL).  SW_ENOTSUP when no
+ *   keys are set.
+ *
+ * sw_validate_payload_device   K events, every array in memory of the context's device (a host pointer: SW_EINVAL before
+ *   anything is launched).  Event i was signed over d_msgs[d_msg_off[i] .. d_msg_off[i+1]) (dumps(ev[:-1]), swirld.py:99) with
+ *   signature d_sig64 + 64 i by member d_creator[i]; its id d_id32 + 32 i is the hash of d_whole[d_whole_off[i] ..
+ *   d_whole_off[i+1]) (dumps(ev), swirld.py:103).  d_whole, d_whole_off, whole_bytes all NULL / 0: no id check (d_id32 is
+ *   then ignored).  msg_bytes / whole_bytes are the lengths of the two byte buffers; the offset arrays hold K + 1 entries.
+ *   d_ok[i] = 1 iff  creator i is in [0, n_members) and its key is usable,  [off[i], off[i+1]) of both buffers is
+ *   non-negative, non-decreasing and inside the buffer (the offsets derive from a peer's bytes: nothing outside the buffers
+ *   is ever read),  libsodium 1.0.18's crypto_sign_verify_detached(sig_i, msg_i, pk[creator_i]) would return 0,  and — with
+ *   the id check — BLAKE2b-256(whole_i) equals id_i.  Otherwise 0.  d_id32 and the offsets must be 8-byte aligned.
+ *   STREAMS: as for sw_export_payload_device — the context's stream first waits, on the device, for what `user_stream` (a
+ *   hipStream_t or NULL, the null stream) has enqueued so far, and `user_stream` is then made to wait for the verdicts: an
+ *   ingest enqueued on it, or given it as its user_stream, reads a complete d_ok.  No allocation, no copy and no host
+ *   synchronisation.  K = 0 is a no-op.
+ *   SW_ENOTSUP when no keys are set; SW_EIO on a poisoned context.  Works on the exact (forked) path and with the windowed
+ *   table: it touches no hashgraph state.  READ-ONLY: no getter and no later call answers differently afterwards
+ *   (counters.kernel_launches and the statistics below move).
+ * sw_validate_payload   the same with every array, and ok, in HOST memory: staged into context scratch, judged by the same
+ *   kernel, copied back.
+ *
+ * sw_get_validate_stats   validation calls and the events they judged since sw_create, the events accepted (counted by the
+ *   host-array form only: the device form never reads its verdicts), table builds, and — under sw_set_profiling — the host
+ *   time in ms of the last table build and of the last validation: phase_ms[2].  Any pointer may be NULL.
+ */
+int sw_set_member_keys(sw_ctx* ctx, const uint8_t* pk32, int32_t* n_unusable);
+int sw_get_member_keys(sw_ctx* ctx, uint8_t* pk32_out, uint8_t* usable_out);
+int sw_validate_payload_device(sw_ctx* ctx, int64_t K, const uint8_t* d_msgs, const int64_t* d_msg_off, int64_t msg_bytes,
+                               const uint8_t* d_whole, const int64_t* d_whole_off, int64_t whole_bytes,
+                               const uint8_t* d_sig64, const int32_t* d_creator, const uint8_t* d_id32, uint8_t* d_ok,
+                               void* user_stream);
+int sw_validate_payload(sw_ctx* ctx, int64_t K, const uint8_t* msgs, const int64_t* msg_off, int64_t msg_bytes,
+                        const uint8_t* whole, const int64_t* whole_off, int64_t whole_bytes,
+                        const uint8_t* sig64, const int32_t* creator, const uint8_t* id32, uint8_t* ok);
+int sw_get_validate_stats(sw_ctx* ctx, int64_t* calls, int64_t* events, int64_t* accepted, int64_t* table_builds,
+                          double* phase_ms);
 
 /* Exact work counters of the calls so far: used by bench.py's roofline. */
 typedef struct sw_counters {

@@ -91,7 +91,12 @@ SIGNATURES = {
     "sw_get_consensus_stats": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "sw_crypto_verify_batch": (C.c_int, [C.c_int, C.c_int64, _P, _P, _P, _P, _P]),
     "sw_crypto_hash_batch": (C.c_int, [C.c_int, C.c_int64, _P, _P, _P]),
-    "sw_num_ordered": (C.c_int, [_P, C.POINTER(C.c_int64)]),
+    "sw_set_member_keys": (C.c_int, [_P, _P, C.POINTER(C.c_int32)]),
+    "sw_get_member_keys": (C.c_int, [_P, _P, _P]),
+    "sw_validate_payload_device": (C.c_int, [_P, C.c_int64, _P, _P, C.c_int64, _P, _P, C.c_int64, _P, _P, _P, _P, _P]),
+    "sw_validate_payload": (C.c_int, [_P, C.c_int64, _P, _P, C.c_int64, _P, _P, C.c_int64, _P, _P, _P, _P]),
+    "sw_get_validate_stats": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), _P]),
+    "sw_num_ordered":(C.c_int, [_P, C.POINTER(C.c_int64)]),
     "sw_get_transactions": (C.c_int, [_P, C.c_int64, C.c_int64, _P]),
     "sw_get_counters": (C.c_int, [_P, C.POINTER(Counters)]),
     "sw_get_counters_sized": (C.c_int, [_P, _P, C.c_size_t]),

@@ -22,6 +22,7 @@
 #define SW_PROV_ROWS 16   // sub-batches of one divide_rounds call that can be swept in chunks
 #define SW_RANGE_SLOTS 16 // event ranges swept by sw_cansee_range between two rewinds
 #include "crypto.hip.h"
+#include "validate.hip.h"
 #include "exact.hip.h"
 #include "ingest.hip.h"
 #include "resolve.hip.h"
@@ -185,6 +186,14 @@ struct sw_ctx {
     DBuf<int32_t> d_cs_ordpos;    // npad: the ordered prefixes as of now, uploaded by a getter (d_ordpos holds those at the head of the last call)
     DBuf<unsigned char> d_cs_out; // the arrays of the host-array forms
     int64_t cs_record_calls = 0, cs_recorded = 0, cs_export_calls = 0, cs_exported = 0;   // sw_get_consensus_stats
+    // validation of payloads against the member keys (sw_set_member_keys, sw_validate_payload[_device]; validate.hip.h):
+    // nothing here belongs to the hashgraph, so sw_rewind / sw_reset leave it alone
+    std::vector<uint8_t> vkeys, vusable;   // host copies: n x 32 key bytes, n flags (empty: no keys set)
+    DBuf<unsigned char> d_vkeys;  // [n x 32 key bytes][n usable flags]
+    DBuf<unsigned char> d_vtab;   // (n + 1) rows of swv::ROW entries: the members' multiples of -A, then the base point's
+    DBuf<unsigned char> d_v_in;   // the staged arrays of the host-array form
+    int64_t v_calls = 0, v_events = 0, v_accepted = 0, v_builds = 0;   // sw_get_validate_stats
+    double v_ms[2] = {0, 0};      // ... host time under sw_set_profiling: the last table build, the last validation
 
     // device: events
     DBuf<int32_t> d_cr, d_sp, d_op, d_ht, d_seq, d_round, d_L, d_chain_ev;
@@ -3135,6 +3144,7 @@ int sw_destroy(sw_ctx* c) {
     dfree(c->d_id); dfree(c->d_idtab); dfree(c->d_idflag); dfree(c->d_pl); dfree(c->d_pl_in);
     dfree(c->d_xp); dfree(c->d_xp_out);
     dfree(c->d_rr); dfree(c->d_cts); dfree(c->d_tx); dfree(c->d_cs_ordpos); dfree(c->d_cs_out);
+    dfree(c->d_vkeys); dfree(c->d_vtab); dfree(c->d_v_in);
     if (c->h_plcnt) (void)hipHostFree(c->h_plcnt);
     if (c->ev_aux_done) (void)hipEventDestroy(c->ev_aux_done);
     if (c->ev_cs_done) (void)hipEventDestroy(c->ev_cs_done);
@@ -5397,6 +5407,162 @@ int sw_synchronize(sw_ctx* c) {
     if (!c) return SW_EINVAL;
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));
+    return SW_OK;
+}
+
+// ---- validation of payloads against the member keys (validate.hip.h) ---------------------------------
+}  // extern "C"
+
+namespace {
+
+// the launch behind the argument checks, on the context's stream: every array in device memory
+int validate_launch(sw_ctx* c, int64_t K, const swv::Payload& p, uint8_t* d_ok) {
+    const int n = c->n;
+    const unsigned blocks = (unsigned)((K + 63) / 64);
+    hipLaunchKernelGGL(swv::k_validate_payload, dim3(blocks), dim3(64), 0, c->stream, p, (long long)K, n, (const uint8_t*)c->d_vkeys.p,
+                       (const uint8_t*)c->d_vkeys.p + (size_t)n * 32, (const swv::niels*)c->d_vtab.p, d_ok);
+    c->ctr.kernel_launches++;
+    HIPCHK(c, hipGetLastError());
+    return SW_OK;
+}
+
+int validate_pre(sw_ctx* c, int64_t K, const void* msgs, const void* msg_off, int64_t msg_bytes, const void* whole, const void* whole_off,
+                 int64_t whole_bytes, const void* sig, const void* creator, const void* id, const void* ok, const char* what) {
+    if (c->poisoned) return fail(c, SW_EIO, "context unusable after an earlier device failure");
+    if (c->vkeys.empty()) return fail(c, SW_ENOTSUP, "%s: no member keys (sw_set_member_keys first)", what);
+    if (K < 0 || msg_bytes < 0 || whole_bytes < 0) return fail(c, SW_EINVAL, "%s: negative count or length", what);
+    if (K > 0x7fffffff) return fail(c, SW_ERANGE, "%s: more than 2^31 events", what);
+    if (K > 0 && (!msg_off || !sig || !creator || !ok || (msg_bytes > 0 && !msgs))) return fail(c, SW_EINVAL, "%s: NULL arrays", what);
+    const bool any_whole = whole || whole_off || whole_bytes;
+    if (K > 0 && any_whole && (!whole_off || !id || (whole_bytes > 0 && !whole)))
+        return fail(c, SW_EINVAL, "%s: the id check needs whole, whole_off and id32 (or none of the three)", what);
+    return SW_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int sw_set_member_keys(sw_ctx* c, const uint8_t* pk32, int32_t* n_unusable) {
+    if (!c) return SW_EINVAL;
+    if (n_unusable) *n_unusable = 0;
+    if (c->poisoned) return fail(c, SW_EIO, "context unusable after an earlier device failure");
+    if (!pk32) return fail(c, SW_EINVAL, "sw_set_member_keys: NULL keys");
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t n = (size_t)c->n;
+    const auto t0 = std::chrono::steady_clock::now();
+    CHK(dgrow(c, c->d_vkeys, n * 33, 0));
+    CHK(dgrow(c, c->d_vtab, (n + 1) * swv::ROW * sizeof(swv::niels), 0));
+    // (an earlier validation may still be reading the old table on this stream: the build is ordered behind it)
+    std::vector<uint8_t> keys(pk32, pk32 + n * 32), usable(n);
+    HIPCHK(c, hipMemcpyAsync(c->d_vkeys.p, keys.data(), n * 32, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(swv::k_validate_table, dim3((unsigned)n + 1), dim3(swv::POSITIONS), 0, c->stream, (const uint8_t*)c->d_vkeys.p, (int)n,
+                       (swv::niels*)c->d_vtab.p, (uint8_t*)c->d_vkeys.p + n * 32);
+    c->ctr.kernel_launches++;
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(usable.data(), c->d_vkeys.p + n * 32, n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->vkeys.swap(keys);
+    c->vusable.swap(usable);
+    c->v_builds++;
+    c->v_ms[0] = c->profiling ? ms_since(t0) : 0;
+    int32_t bad = 0;
+    for (uint8_t u : c->vusable) bad += !u;
+    if (n_unusable) *n_unusable = bad;
+    return SW_OK;
+}
+
+int sw_get_member_keys(sw_ctx* c, uint8_t* pk32_out, uint8_t* usable_out) {
+    if (!c) return SW_EINVAL;
+    if (c->vkeys.empty()) return fail(c, SW_ENOTSUP, "sw_get_member_keys: no member keys (sw_set_member_keys first)");
+    if (pk32_out) memcpy(pk32_out, c->vkeys.data(), c->vkeys.size());
+    if (usable_out) memcpy(usable_out, c->vusable.data(), c->vusable.size());
+    return SW_OK;
+}
+
+int sw_validate_payload_device(sw_ctx* c, int64_t K, const uint8_t* d_msgs, const int64_t* d_msg_off, int64_t msg_bytes, const uint8_t* d_whole,
+                               const int64_t* d_whole_off, int64_t whole_bytes, const uint8_t* d_sig64, const int32_t* d_creator,
+                               const uint8_t* d_id32, uint8_t* d_ok, void* user_stream) {
+    if (!c) return SW_EINVAL;
+    CHK(validate_pre(c, K, d_msgs, d_msg_off, msg_bytes, d_whole, d_whole_off, whole_bytes, d_sig64, d_creator, d_id32, d_ok, "sw_validate_payload_device"));
+    if (K == 0) return SW_OK;
+    if ((uintptr_t)d_id32 & 7) return fail(c, SW_EINVAL, "sw_validate_payload_device: the id array must be 8-byte aligned");
+    if (((uintptr_t)d_msg_off | (uintptr_t)d_whole_off) & 7) return fail(c, SW_EINVAL, "sw_validate_payload_device: the offsets must be 8-byte aligned");
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t k = (size_t)K;
+    const bool idchk = d_whole_off != nullptr;
+    if (!on_ctx_device(c, d_msg_off, (k + 1) * 8) || (msg_bytes > 0 && !on_ctx_device(c, d_msgs, (size_t)msg_bytes)) ||
+        !on_ctx_device(c, d_sig64, k * 64) || !on_ctx_device(c, d_creator, k * 4) || !on_ctx_device(c, d_ok, k) ||
+        (idchk && (!on_ctx_device(c, d_whole_off, (k + 1) * 8) || !on_ctx_device(c, d_id32, k * 32) ||
+                   (whole_bytes > 0 && !on_ctx_device(c, d_whole, (size_t)whole_bytes)))))
+        return fail(c, SW_EINVAL, "sw_validate_payload_device: every array must lie in memory of device %d (a host pointer, or another device's)", c->device);
+    const bool prof = c->profiling;
+    const auto t0 = std::chrono::steady_clock::now();
+    if (!c->ev_user) HIPCHK(c, hipEventCreateWithFlags(&c->ev_user, hipEventDisableTiming));
+    hipStream_t us = (hipStream_t)user_stream;
+    HIPCHK(c, hipEventRecord(c->ev_user, us));            // the producers of the arrays; earlier readers of d_ok
+    HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_user, 0));
+    // (a zero-length buffer may be NULL: the kernel then only forms pointers it never reads through; `whole` non-NULL is
+    // what selects the id check there)
+    const uint8_t* anchor = (const uint8_t*)c->d_vkeys.p;
+    const swv::Payload p{d_msgs ? d_msgs : anchor, (const long long*)d_msg_off, (long long)msg_bytes, idchk ? (d_whole ? d_whole : anchor) : nullptr,
+                         (const long long*)d_whole_off, (long long)whole_bytes, d_sig64, d_creator, d_id32};
+    CHK(validate_launch(c, K, p, d_ok));
+    HIPCHK(c, hipEventRecord(c->ev_user, c->stream));     // whatever the caller enqueues next reads a complete d_ok
+    HIPCHK(c, hipStreamWaitEvent(us, c->ev_user, 0));
+    c->v_ms[1] = 0;
+    if (prof) { HIPCHK(c, hipStreamSynchronize(c->stream)); c->v_ms[1] = ms_since(t0); }
+    c->v_calls++;
+    c->v_events += K;
+    return SW_OK;
+}
+
+int sw_validate_payload(sw_ctx* c, int64_t K, const uint8_t* msgs, const int64_t* msg_off, int64_t msg_bytes, const uint8_t* whole,
+                        const int64_t* whole_off, int64_t whole_bytes, const uint8_t* sig64, const int32_t* creator, const uint8_t* id32, uint8_t* ok) {
+    if (!c) return SW_EINVAL;
+    CHK(validate_pre(c, K, msgs, msg_off, msg_bytes, whole, whole_off, whole_bytes, sig64, creator, id32, ok, "sw_validate_payload"));
+    if (K == 0) return SW_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    const bool prof = c->profiling;
+    const auto t0 = std::chrono::steady_clock::now();
+    const size_t k = (size_t)K, mb = (size_t)msg_bytes, wb = (size_t)whole_bytes;
+    const bool idchk = whole_off != nullptr;
+    Carve cv;
+    const size_t o_moff = cv.take((k + 1) * 8), o_m = cv.take(mb), o_woff = cv.take(idchk ? (k + 1) * 8 : 0), o_w = cv.take(idchk ? wb : 0);
+    const size_t o_sig = cv.take(k * 64), o_cr = cv.take(k * 4), o_id = cv.take(idchk ? k * 32 : 0), o_ok = cv.take(k);
+    CHK(dgrow(c, c->d_v_in, cv.off + 256, 0));
+    unsigned char* B = c->d_v_in.p;
+    HIPCHK(c, hipMemcpyAsync(B + o_moff, msg_off, (k + 1) * 8, hipMemcpyHostToDevice, c->stream));
+    if (mb) HIPCHK(c, hipMemcpyAsync(B + o_m, msgs, mb, hipMemcpyHostToDevice, c->stream));
+    if (idchk) {
+        HIPCHK(c, hipMemcpyAsync(B + o_woff, whole_off, (k + 1) * 8, hipMemcpyHostToDevice, c->stream));
+        if (wb) HIPCHK(c, hipMemcpyAsync(B + o_w, whole, wb, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(B + o_id, id32, k * 32, hipMemcpyHostToDevice, c->stream));
+    }
+    HIPCHK(c, hipMemcpyAsync(B + o_sig, sig64, k * 64, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(B + o_cr, creator, k * 4, hipMemcpyHostToDevice, c->stream));
+    const swv::Payload p{B + o_m, (const long long*)(B + o_moff), (long long)msg_bytes, idchk ? B + o_w : nullptr,
+                         idchk ? (const long long*)(B + o_woff) : nullptr, (long long)whole_bytes, B + o_sig, (const int32_t*)(B + o_cr),
+                         idchk ? B + o_id : nullptr};
+    CHK(validate_launch(c, K, p, B + o_ok));
+    HIPCHK(c, hipMemcpyAsync(ok, B + o_ok, k, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->v_ms[1] = prof ? ms_since(t0) : 0;
+    int64_t acc = 0;
+    for (size_t i = 0; i < k; ++i) acc += ok[i] != 0;
+    c->v_calls++;
+    c->v_events += K;
+    c->v_accepted += acc;
+    return SW_OK;
+}
+
+int sw_get_validate_stats(sw_ctx* c, int64_t* calls, int64_t* events, int64_t* accepted, int64_t* table_builds, double* phase_ms) {
+    if (!c) return SW_EINVAL;
+    if (calls) *calls = c->v_calls;
+    if (events) *events = c->v_events;
+    if (accepted) *accepted = c->v_accepted;
+    if (table_builds) *table_builds = c->v_builds;
+    if (phase_ms) for (int i = 0; i < 2; ++i) phase_ms[i] = c->v_ms[i];
     return SW_OK;
 }
 

@@ -189,6 +189,88 @@ class Hashgraph:
         d.update(zip(("resolve_ms", "waves_ms", "sort_ms", "append_ms"), (float(x) for x in ms)))
         return d
 
+    # ---- validation against the member keys (the crypto of Node.is_valid_event, swirld.py:97-103) ----
+    def set_member_keys(self, keys):
+        """The members' Ed25519 public keys (n x 32 uint8, or n byte strings): builds the fixed-base table on the device
+        (sw_set_member_keys).  Returns the number of keys libsodium would refuse; their members' events are all invalid."""
+        if isinstance(keys, (list, tuple)):
+            keys = np.frombuffer(b"".join(bytes(k) for k in keys), np.uint8)
+        keys = np.ascontiguousarray(keys, np.uint8).reshape(-1)
+        if keys.shape[0] != 32 * self.n:
+            raise ValueError("expected %d keys of 32 bytes" % self.n)
+        bad = C.c_int32()
+        self._chk(self._L.sw_set_member_keys(self._h, _p(keys), C.byref(bad)))
+        return int(bad.value)
+
+    def member_keys(self):
+        """(keys n x 32 uint8, usable n bool) as set by set_member_keys."""
+        keys, usable = np.empty((self.n, 32), np.uint8), np.empty(self.n, np.uint8)
+        self._chk(self._L.sw_get_member_keys(self._h, _p(keys), _p(usable)))
+        return keys, usable.astype(bool)
+
+    @staticmethod
+    def _pack(items):
+        """(bytes as uint8 array, int64 offsets) of a list of byte strings; arrays (data, off) pass through."""
+        if isinstance(items, tuple) and len(items) == 2 and isinstance(items[1], np.ndarray):
+            return np.ascontiguousarray(items[0], np.uint8).reshape(-1), np.ascontiguousarray(items[1], np.int64)
+        off = np.zeros(len(items) + 1, np.int64)
+        if len(items):
+            np.cumsum([len(m) for m in items], out=off[1:])
+        return np.frombuffer(b"".join(items), np.uint8), off
+
+    def validate_payload(self, msgs, sig, creator, whole=None, ids=None):
+        """Verdicts of K events, host arrays in and a bool array out (sw_validate_payload).  msgs / whole: lists of byte
+        strings, or (uint8 data, int64 offsets of K + 1 entries); msgs[i] is what event i's signature sig[i] (K x 64) by
+        member creator[i] covers, whole[i] what its id ids[i] (K x 32) is the BLAKE2b-256 of (whole None: no id check)."""
+        data, off = self._pack(msgs)
+        K = off.shape[0] - 1
+        sig = np.ascontiguousarray(sig, np.uint8).reshape(K, 64)
+        creator = np.ascontiguousarray(creator, np.int32)
+        if creator.shape != (K,):
+            raise ValueError("creator must have one entry per event")
+        wdata = woff = None
+        wbytes = 0
+        if whole is not None:
+            wdata, woff = self._pack(whole)
+            if woff.shape[0] != K + 1:
+                raise ValueError("whole must have one entry per event")
+            ids = self._ids(ids, K)
+            wbytes = wdata.shape[0]
+            if wbytes == 0:
+                wdata = np.zeros(1, np.uint8)
+        if data.shape[0] == 0:
+            data = np.zeros(1, np.uint8)
+        ok = np.zeros(K, np.uint8)
+        self._chk(self._L.sw_validate_payload(self._h, K, _p(data), _p(off), int(off[-1]) if K else 0, _p(wdata), _p(woff), wbytes,
+                                              _p(sig), _p(creator), _p(ids) if whole is not None else None, _p(ok)))
+        return ok.astype(bool)
+
+    def validate_payload_device(self, msgs, msg_off, msg_bytes, sig, creator, ok, whole=None, whole_off=None, whole_bytes=0, ids=None,
+                                stream=0, count=None):
+        """validate_payload for arrays in DEVICE memory (addresses, or objects with data_ptr() / __cuda_array_interface__):
+        uint8 msgs of msg_bytes bytes, int64 msg_off (K + 1), K x 64 uint8 sig, int32 creator, and — for the id check —
+        whole / whole_off / whole_bytes and K x 32 uint8 ids (8-byte aligned).  `ok` (K uint8 in device memory) receives
+        the verdicts, complete for whatever is enqueued on `stream` afterwards — an ingest_payload_device(ok=ok,
+        stream=stream) in particular.  K comes from `creator`'s length where it has one, else from `count`.  Returns `ok`."""
+        ptrs = [_dev_ptr(a) for a in (msgs, msg_off, whole, whole_off, sig, creator, ids, ok)]
+        K = count if count is not None else ptrs[5][1]
+        if K is None:
+            raise ValueError("the number of events is not known: pass count=")
+        a = [C.c_void_p(q) if q else None for q, _ in ptrs]
+        self._chk(self._L.sw_validate_payload_device(self._h, int(K), a[0], a[1], int(msg_bytes), a[2], a[3], int(whole_bytes),
+                                                     a[4], a[5], a[6], a[7], C.c_void_p(int(stream))))
+        return ok
+
+    def validate_stats(self):
+        """Validation calls and events judged so far, events accepted (host form only), table builds, and (under
+        set_profiling) the host milliseconds of the last table build and of the last validation."""
+        v = [C.c_int64() for _ in range(4)]
+        ms = (C.c_double * 2)()
+        self._chk(self._L.sw_get_validate_stats(self._h, *[C.byref(x) for x in v], ms))
+        d = dict(zip(("calls", "events", "accepted", "table_builds"), (int(x.value) for x in v)))
+        d.update(zip(("table_ms", "validate_ms"), (float(x) for x in ms)))
+        return d
+
     @property
     def num_events(self):
         return int(self._L.sw_num_events(self._h))

@@ -261,6 +261,11 @@ class Node:
     # does; dropping them is the host loop's job).  The stored SET is the host loop's; the order events are added in is
     # (acceptance wave, position in the payload) instead of the toposort's — both topological.  None = never.
     device_payload_threshold = None
+    # The crypto of is_valid_event for a whole payload in ONE device call against the members' keys (sw_validate_payload: the
+    # fixed-base table of csrc/validate.hip.h; signature by the creator's key AND id in one verdict), for payloads of at
+    # least this many events; it then takes the place of the two stateless batches above.  The node hands its members' keys
+    # to the context on first use.  None = never.
+    device_validate_threshold = None
 
     def __init__(self, kp, network, n_nodes, stake, device=0, accept_forks=True):
         self.pk, self.sk = kp
@@ -300,6 +305,7 @@ class Node:
         self._uploaded = 0
         self._dev_ids = 0     # events whose id the device context knows (device_payload_threshold)
         self._device_payloads = 0
+        self._keys_on_device = False   # the context has the members' keys (device_validate_threshold)
         self._divided = 0
         self._device = device
         self._dev = Hashgraph(n_nodes, [stake[pk] for pk in self._members], coin_period=C, device=device)
@@ -385,6 +391,36 @@ class Node:
         ids = hash_batch(whole, device=self._device)
         return {eid: (bool(ok[i]) and good[i], ids[i]) for i, eid in enumerate(eids)}
 
+    def _batch_validate(self, eids, events):
+        """{event id -> (valid, id)} for a whole sync payload from ONE device call (Hashgraph.validate_payload): valid =
+        signed by its creator, a member, and hashing to its id.  dumps(ev[:-1]) and dumps(ev) are packed once; malformed
+        events (wrong types or lengths) are simply invalid."""
+        if not self._keys_on_device:
+            self._dev.set_member_keys([bytes(pk) for pk in self._members])
+            self._keys_on_device = True
+        is_b = lambda x, n: isinstance(x, (bytes, bytearray)) and len(x) == n
+        msgs, whole, sigs, ids, good = [], [], [], [], []
+        creator = np.full(len(eids), -1, np.int32)
+        for i, eid in enumerate(eids):
+            ev = events[eid]
+            wf = is_b(ev.s, 64) and is_b(ev.c, 32) and is_b(eid, 32)
+            good.append(wf)
+            msgs.append(dumps(ev[:-1]))
+            whole.append(dumps(ev))
+            sigs.append(bytes(ev.s) if wf else b"\0" * 64)
+            ids.append(bytes(eid) if wf else b"\0" * 32)
+            if wf:
+                creator[i] = self._mindex.get(bytes(ev.c), -1)
+        ok = self._dev.validate_payload(msgs, np.frombuffer(b"".join(sigs), np.uint8), creator, whole=whole,
+                                        ids=np.frombuffer(b"".join(ids), np.uint8))
+        return {eid: ((True, eid) if ok[i] and good[i] else (False, None)) for i, eid in enumerate(eids)}
+
+    def _validate_threshold(self):
+        """device_validate_threshold where the device verifier applies: real Ed25519 keys of 32 bytes."""
+        if not crypto.HAVE_SODIUM or not all(isinstance(pk, (bytes, bytearray)) and len(pk) == 32 for pk in self._members):
+            return None
+        return self.device_validate_threshold
+
     def add_event(self, h, ev):
         """Store an event (swirld.py:114-120); it is uploaded with the next divide_rounds."""
         self._add_event_host(h, ev)
@@ -424,12 +460,16 @@ class Node:
         thr = self.device_crypto_threshold
         if not crypto.HAVE_SODIUM:  # stand-in signatures are keyed hashes: the device verifier (real Ed25519) would refuse all of them
             thr = None
+        vthr = self._validate_threshold()
         dthr = self.device_payload_threshold
         if dthr is not None and self.accept_forks and len(unknown) >= max(dthr, 1):
-            added = self._sync_payload_device(list(unknown), remote_hg, thr)
+            added = self._sync_payload_device(list(unknown), remote_hg, thr, vthr)
             return self._sync_finish(added, remote_head, remote_hg, payload)
         new = tuple(toposort(unknown, lambda u: remote_hg[u].p))
-        pre = self._batch_crypto(new, remote_hg) if thr is not None and len(new) >= thr else {}
+        if vthr is not None and len(new) >= max(vthr, 1):
+            pre = self._batch_validate(new, remote_hg)
+        else:
+            pre = self._batch_crypto(new, remote_hg) if thr is not None and len(new) >= thr else {}
         # Only what was actually stored is returned (main() hands it to divide_rounds): the reference
         # returns the rejected ids too and then fails on them (swirld.py:134-146, 326), and references an
         # unbound `h` when the remote head itself is rejected; here a bad payload costs the step, not the node.
@@ -440,7 +480,7 @@ class Node:
                 added.append(eid)
         return self._sync_finish(added, remote_head, remote_hg, payload)
 
-    def _sync_payload_device(self, eids, remote_hg, crypto_thr):
+    def _sync_payload_device(self, eids, remote_hg, crypto_thr, validate_thr=None):
         """The unknown events of a sync payload, in any order, through Hashgraph.ingest_payload; returns the ids stored,
         in the order they were added."""
         self._flush()
@@ -452,7 +492,10 @@ class Node:
         K = len(eids)
         if K == 0:
             return []
-        pre = self._batch_crypto(eids, remote_hg) if crypto_thr is not None and K >= crypto_thr else None
+        if validate_thr is not None and K >= validate_thr:
+            pre = self._batch_validate(eids, remote_hg)
+        else:
+            pre = self._batch_crypto(eids, remote_hg) if crypto_thr is not None and K >= crypto_thr else None
         ids = np.frombuffer(b"".join(bytes(e) for e in eids), np.uint8).reshape(K, 32)
         par = np.zeros((2, K, 32), np.uint8)
         arity = np.zeros(K, np.uint8)
