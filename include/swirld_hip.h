@@ -479,6 +479,72 @@ int sw_validate_payload(sw_ctx* ctx, int64_t K, const uint8_t* msgs, const int64
 int sw_get_validate_stats(sw_ctx* ctx, int64_t* calls, int64_t* events, int64_t* accepted, int64_t* table_builds,
                           double* phase_ms);
 
+/*
+ * The signed bytes of events, built ON THE DEVICE (kernels in csrc/pack.hip.h): the two byte streams
+ * sw_validate_payload_device reads — dumps(ev[:-1]), what the signature covers (swirld.py:99), and dumps(ev), what the id
+ * is the hash of (swirld.py:95, :103) — from the arrays sw_export_payload_device writes.  For parents () or two 32-byte
+ * ids, a float timestamp, a 32-byte creator key, a 64-byte signature and data None or a bytes object of at most 60 000
+ * bytes, pickle protocol 4 writes a fixed template of one frame without memo reads (tests/model_pack.py); these calls
+ * write exactly those bytes.
+ *
+ * sw_set_event_class / sw_get_event_class   module and qualified name of the Event class (Event.__module__,
+ *   Event.__qualname__): they are part of dumps(ev) and so of every id.  NUL-terminated UTF-8 of 1 .. 255 bytes each, else
+ *   SW_EINVAL; default "swirld", "Event".  The getter's buffers hold 256 bytes each (either may be NULL).  The setting
+ *   survives sw_rewind and sw_reset.
+ * sw_pack_bound   upper bounds of the two streams for ANY K events with data_bytes bytes of data between them (host
+ *   arithmetic: 137 K + data_bytes, and (214 + len(module) + len(qualname)) K + data_bytes).
+ *
+ * sw_pack_events_device   K events, every array in memory of the context's device (a host pointer: SW_EINVAL before
+ *   anything is launched).  In: d_sp_id32, d_op_id32, d_arity, d_creator, d_t, d_sig64 as sw_export_payload_device writes
+ *   them (the parents' ids are read only where the arity is 2); the creator's key bytes come from the context
+ *   (sw_set_member_keys; SW_ENOTSUP without).  Data: d_data, d_data_off, data_bytes and d_data_none all NULL / 0 means
+ *   every event's data is None; otherwise event i's data is d_data[d_data_off[i] .. d_data_off[i+1]) (K + 1 int64 offsets,
+ *   an empty range is b''), and d_data_none (uint8 per event, may be NULL) nonzero marks None.
+ *   Out: d_msgs / d_msg_off and d_whole / d_whole_off — bytes and K + 1 int64 offsets each, in the form
+ *   sw_validate_payload_device takes; the totals are off[K].  Bytes at and beyond off[K] are not written.  d_encodable
+ *   (uint8 per event, may be NULL): 0 for an event that has no such bytes — an arity that is neither 0 nor 2, a creator
+ *   outside [0, n_members), a data range that is negative, decreasing, beyond data_bytes or longer than 60 000.  Such an
+ *   event has length 0 in both streams and nothing is read for it (the offsets may derive from a peer's bytes: nothing
+ *   outside [0, data_bytes) is ever read).  Its verdict from sw_validate_payload_device is 0.
+ *   msg_cap / whole_cap: the capacities of d_msgs / d_whole; below sw_pack_bound's values: SW_ERANGE, before any launch.
+ *   The two byte streams, d_sig64 and the id arrays must be 16-byte aligned, offsets and timestamps 8-byte aligned
+ *   (SW_EINVAL).  STREAMS: as for sw_validate_payload_device — the context's stream first waits for what `user_stream` has
+ *   enqueued so far, and `user_stream` is then made to wait for the result.  No allocation beyond growing context
+ *   scratch, no copy of an array (the first call after sw_create or sw_set_event_class uploads the class header, at most
+ *   518 bytes) and no host synchronisation.  K = 0 is a no-op that writes off[0] = 0.  SW_EIO on a poisoned context.
+ *   READ-ONLY with respect to the hashgraph: it works on the exact path and with the windowed table, and no getter and
+ *   no later call answers differently afterwards (counters.kernel_launches and the statistics below move).
+ * sw_pack_events   the same with every array in HOST memory, staged through context scratch; *msg_bytes / *whole_bytes
+ *   (may be NULL) receive the totals.
+ *
+ * sw_sync_pull_validated   sw_sync_pull with is_valid_event's crypto in the middle (swirld.py:97-103): after src's gather,
+ *   dst — on its stream, behind src's — packs the exported arrays into scratch of its own, validates them with ITS OWN
+ *   member keys and event class (id check on), ANDs the verdicts with the encodable flags and ingests with that as d_ok.
+ *   *n_valid: the events that passed, counted on the device and read at the call's final drain.  Preconditions: those of
+ *   sw_sync_pull, and keys set in dst (SW_ENOTSUP, nothing stored).  The context does NOT store event data: the bytes are
+ *   built with data None, so events that src's members signed with other data fail the id check and are rejected one by
+ *   one, with their descendants.  Carrying data through ingest and export is a later change.
+ *
+ * sw_get_pack_stats   pack calls (sw_sync_pull_validated's included) and the events they encoded since sw_create, the
+ *   bytes written (counted by the host-array form only: the device form never reads its totals), and — under
+ *   sw_set_profiling — the host time in ms of the last call's lengths-and-scan and of its two writers: phase_ms[2].
+ */
+int sw_set_event_class(sw_ctx* ctx, const char* module, const char* qualname);
+int sw_get_event_class(sw_ctx* ctx, char* module_out, char* qualname_out);
+int sw_pack_bound(sw_ctx* ctx, int64_t K, int64_t data_bytes, int64_t* msg_bytes, int64_t* whole_bytes);
+int sw_pack_events_device(sw_ctx* ctx, int64_t K, const uint8_t* d_sp_id32, const uint8_t* d_op_id32, const uint8_t* d_arity,
+                          const int32_t* d_creator, const double* d_t, const uint8_t* d_sig64, const uint8_t* d_data,
+                          const int64_t* d_data_off, int64_t data_bytes, const uint8_t* d_data_none, uint8_t* d_msgs,
+                          int64_t* d_msg_off, int64_t msg_cap, uint8_t* d_whole, int64_t* d_whole_off, int64_t whole_cap,
+                          uint8_t* d_encodable, void* user_stream);
+int sw_pack_events(sw_ctx* ctx, int64_t K, const uint8_t* sp_id32, const uint8_t* op_id32, const uint8_t* arity,
+                   const int32_t* creator, const double* t, const uint8_t* sig64, const uint8_t* data, const int64_t* data_off,
+                   int64_t data_bytes, const uint8_t* data_none, uint8_t* msgs, int64_t* msg_off, int64_t msg_cap, uint8_t* whole,
+                   int64_t* whole_off, int64_t whole_cap, uint8_t* encodable, int64_t* msg_bytes, int64_t* whole_bytes);
+int sw_sync_pull_validated(sw_ctx* dst, int64_t dst_head, sw_ctx* src, int64_t src_head, int64_t* n_sent, int64_t* n_valid,
+                           int64_t* n_stored);
+int sw_get_pack_stats(sw_ctx* ctx, int64_t* calls, int64_t* events, int64_t* bytes, double* phase_ms);
+
 /* Exact work counters of the calls so far: used by bench.py's roofline. */
 typedef struct sw_counters {
     int64_t events_divided;      /* events through divide_rounds                          */

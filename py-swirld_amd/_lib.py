@@ -96,6 +96,14 @@ SIGNATURES = {
     "sw_validate_payload_device": (C.c_int, [_P, C.c_int64, _P, _P, C.c_int64, _P, _P, C.c_int64, _P, _P, _P, _P, _P]),
     "sw_validate_payload": (C.c_int, [_P, C.c_int64, _P, _P, C.c_int64, _P, _P, C.c_int64, _P, _P, _P, _P]),
     "sw_get_validate_stats": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), _P]),
+    "sw_set_event_class": (C.c_int, [_P, C.c_char_p, C.c_char_p]),
+    "sw_get_event_class": (C.c_int, [_P, _P, _P]),
+    "sw_pack_bound": (C.c_int, [_P, C.c_int64, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "sw_pack_events_device": (C.c_int, [_P, C.c_int64, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int64, _P, _P, _P, C.c_int64, _P, _P, C.c_int64, _P, _P]),
+    "sw_pack_events": (C.c_int, [_P, C.c_int64, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int64, _P, _P, _P, C.c_int64, _P, _P, C.c_int64, _P,
+                                 C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "sw_sync_pull_validated": (C.c_int, [_P, C.c_int64, _P, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "sw_get_pack_stats": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), _P]),
     "sw_num_ordered":(C.c_int, [_P, C.POINTER(C.c_int64)]),
     "sw_get_transactions": (C.c_int, [_P, C.c_int64, C.c_int64, _P]),
     "sw_get_counters": (C.c_int, [_P, C.POINTER(Counters)]),

@@ -23,6 +23,7 @@
 #define SW_RANGE_SLOTS 16 // event ranges swept by sw_cansee_range between two rewinds
 #include "crypto.hip.h"
 #include "validate.hip.h"
+#include "pack.hip.h"
 #include "exact.hip.h"
 #include "ingest.hip.h"
 #include "resolve.hip.h"
@@ -194,6 +195,18 @@ struct sw_ctx {
     DBuf<unsigned char> d_v_in;   // the staged arrays of the host-array form
     int64_t v_calls = 0, v_events = 0, v_accepted = 0, v_builds = 0;   // sw_get_validate_stats
     double v_ms[2] = {0, 0};      // ... host time under sw_set_profiling: the last table build, the last validation
+    // the signed bytes of events built on the device (sw_pack_events[_device], sw_sync_pull_validated; pack.hip.h): like the
+    // keys, a setting and scratch that sw_rewind / sw_reset leave alone
+    std::string pk_mod = "swirld", pk_qual = "Event";   // module and qualified name of the Event class (sw_set_event_class)
+    bool pk_hdr_stale = true;     // d_pk_hdr does not hold the class header of pk_mod / pk_qual yet
+    std::vector<uint8_t> pk_hdr;  // host copy of the header as uploaded (it must outlive the asynchronous copy)
+    DBuf<unsigned char> d_pk_hdr; // the class header of the whole stream (pck::HDR_MAX bytes)
+    DBuf<unsigned char> d_pk;     // tile sums of the scan
+    DBuf<unsigned char> d_pk_in;  // the staged arrays and streams of the host-array form
+    DBuf<unsigned char> d_pk_out; // sw_sync_pull_validated: offsets, streams, flags, verdicts, the count
+    int32_t* h_pkcnt = nullptr;   // pinned: the count of valid events of sw_sync_pull_validated
+    int64_t pk_calls = 0, pk_events = 0, pk_bytes = 0;   // sw_get_pack_stats
+    double pk_ms[2] = {0, 0};     // ... host time under sw_set_profiling: lengths and scan, the two writers
 
     // device: events
     DBuf<int32_t> d_cr, d_sp, d_op, d_ht, d_seq, d_round, d_L, d_chain_ev;
@@ -3145,6 +3158,8 @@ int sw_destroy(sw_ctx* c) {
     dfree(c->d_xp); dfree(c->d_xp_out);
     dfree(c->d_rr); dfree(c->d_cts); dfree(c->d_tx); dfree(c->d_cs_ordpos); dfree(c->d_cs_out);
     dfree(c->d_vkeys); dfree(c->d_vtab); dfree(c->d_v_in);
+    dfree(c->d_pk_hdr); dfree(c->d_pk); dfree(c->d_pk_in); dfree(c->d_pk_out);
+    if (c->h_pkcnt) (void)hipHostFree(c->h_pkcnt);
     if (c->h_plcnt) (void)hipHostFree(c->h_plcnt);
     if (c->ev_aux_done) (void)hipEventDestroy(c->ev_aux_done);
     if (c->ev_cs_done) (void)hipEventDestroy(c->ev_cs_done);
@@ -5563,6 +5578,350 @@ int sw_get_validate_stats(sw_ctx* c, int64_t* calls, int64_t* events, int64_t* a
     if (accepted) *accepted = c->v_accepted;
     if (table_builds) *table_builds = c->v_builds;
     if (phase_ms) for (int i = 0; i < 2; ++i) phase_ms[i] = c->v_ms[i];
+    return SW_OK;
+}
+
+// ---- the signed bytes of events built on the device (pack.hip.h) ---------------------------------------
+}  // extern "C"
+
+namespace {
+
+struct PackArrays {   // what a pack call reads and writes, every array in device memory
+    const uint8_t *sp_id, *op_id, *arity;
+    const int32_t* creator;
+    const double* t;
+    const uint8_t *sig, *data;
+    const int64_t* data_off;
+    int64_t data_bytes;
+    const uint8_t* data_none;
+    uint8_t* msgs;
+    int64_t* msg_off;
+    uint8_t* whole;
+    int64_t* whole_off;
+    uint8_t* enc;
+};
+
+bool utf8_name(const char* s) {   // 1 .. 255 bytes of well-formed UTF-8
+    if (!s) return false;
+    const size_t len = strlen(s);
+    if (len < 1 || len > (size_t)pck::MAX_NAME) return false;
+    const unsigned char* p = (const unsigned char*)s;
+    for (size_t i = 0; i < len;) {
+        const unsigned b = p[i];
+        int more;
+        unsigned cp;
+        if (b < 0x80) { ++i; continue; }
+        else if (b >= 0xc2 && b <= 0xdf) { more = 1; cp = b & 0x1f; }
+        else if (b >= 0xe0 && b <= 0xef) { more = 2; cp = b & 0x0f; }
+        else if (b >= 0xf0 && b <= 0xf4) { more = 3; cp = b & 0x07; }
+        else return false;
+        if (i + more >= len) return false;
+        for (int k = 1; k <= more; ++k) {
+            if ((p[i + k] & 0xc0) != 0x80) return false;
+            cp = (cp << 6) | (p[i + k] & 0x3f);
+        }
+        if ((more == 2 && cp < 0x800) || (more == 3 && cp < 0x10000) || cp > 0x10ffff || (cp >= 0xd800 && cp <= 0xdfff)) return false;
+        i += more + 1;
+    }
+    return true;
+}
+
+int pack_hdr_len(const sw_ctx* c) { return (int)(c->pk_mod.size() + c->pk_qual.size() + 8); }
+
+void pack_bound(const sw_ctx* c, int64_t K, int64_t data_bytes, int64_t* msg, int64_t* whole) {
+    *msg = K * pck::MSG_MAX + data_bytes;
+    *whole = K * (pck::WHOLE_MAX + pack_hdr_len(c)) + data_bytes;
+}
+
+// the class header of the whole stream in device memory (after sw_create and after sw_set_event_class: one small copy)
+int pack_header(sw_ctx* c) {
+    if (!c->pk_hdr_stale) return SW_OK;
+    CHK(dgrow(c, c->d_pk_hdr, (size_t)pck::HDR_MAX + 248, 0));
+    std::vector<uint8_t>& h = c->pk_hdr;
+    h.clear();
+    for (const std::string* s : {&c->pk_mod, &c->pk_qual}) {
+        h.push_back(0x8c);
+        h.push_back((uint8_t)s->size());
+        h.insert(h.end(), s->begin(), s->end());
+        h.push_back(0x94);
+    }
+    h.push_back(0x93);
+    h.push_back(0x94);
+    HIPCHK(c, hipMemcpyAsync(c->d_pk_hdr.p, h.data(), h.size(), hipMemcpyHostToDevice, c->stream));
+    c->pk_hdr_stale = false;
+    return SW_OK;
+}
+
+// the six launches behind the argument checks, on the context's stream.  bound_*: sw_pack_bound's values (the host does
+// not know the totals: the writers' grids come from the bounds).
+int pack_launch(sw_ctx* c, int64_t K, const PackArrays& a, int64_t bound_msg, int64_t bound_whole) {
+    const bool prof = c->profiling;
+    auto t0 = std::chrono::steady_clock::now();
+    CHK(pack_header(c));
+    const int64_t tiles = (K + pck::TILE - 1) / pck::TILE;
+    CHK(dgrow(c, c->d_pk, (size_t)(2 * tiles) * sizeof(int64_t) + 256, 0));
+    pck::i64* tsum = (pck::i64*)c->d_pk.p;
+    const pck::PackIn in{a.sp_id, a.op_id, a.arity, a.creator, (const pck::u64*)a.t, a.sig, a.data, (const pck::i64*)a.data_off,
+                         (pck::i64)a.data_bytes, a.data_none, (const unsigned char*)c->d_vkeys.p, (const unsigned char*)c->d_pk_hdr.p,
+                         pack_hdr_len(c), c->n};
+    pck::i64* moff = (pck::i64*)a.msg_off;
+    pck::i64* woff = (pck::i64*)a.whole_off;
+    hipLaunchKernelGGL(pck::k_pack_lengths, dim3((unsigned)((K + 255) / 256)), dim3(256), 0, c->stream, in, (pck::i64)K, moff, woff, a.enc);
+    hipLaunchKernelGGL(pck::k_pack_tile_sums, dim3((unsigned)tiles, 2), dim3(pck::SCAN_THREADS), 0, c->stream, (pck::i64)K, (pck::i64)tiles,
+                       (const pck::i64*)moff, (const pck::i64*)woff, tsum);
+    hipLaunchKernelGGL(pck::k_pack_scan_sums, dim3(2), dim3(pck::SCAN_THREADS), 0, c->stream, (pck::i64)K, (pck::i64)tiles, moff, woff, tsum);
+    hipLaunchKernelGGL(pck::k_pack_offsets, dim3((unsigned)tiles, 2), dim3(pck::SCAN_THREADS), 0, c->stream, (pck::i64)K, (pck::i64)tiles, moff, woff,
+                       (const pck::i64*)tsum);
+    c->ctr.kernel_launches += 4;
+    HIPCHK(c, hipGetLastError());
+    if (prof) { HIPCHK(c, hipStreamSynchronize(c->stream)); c->pk_ms[0] = ms_since(t0); t0 = std::chrono::steady_clock::now(); }
+    for (int w = 0; w < 2; ++w) {
+        const int64_t chunks = ((w ? bound_whole : bound_msg) + 15) / 16;
+        const int64_t blocks = std::max<int64_t>(1, std::min<int64_t>(4096, (chunks + pck::WRITE_THREADS - 1) / pck::WRITE_THREADS));
+        const int64_t trips = (chunks + blocks * pck::WRITE_THREADS - 1) / (blocks * pck::WRITE_THREADS);
+        if (w) hipLaunchKernelGGL(pck::k_pack_write<true>, dim3((unsigned)blocks), dim3(pck::WRITE_THREADS), 0, c->stream, in, (pck::i64)K,
+                                  (const pck::i64*)woff, a.whole, (pck::i64)trips);
+        else hipLaunchKernelGGL(pck::k_pack_write<false>, dim3((unsigned)blocks), dim3(pck::WRITE_THREADS), 0, c->stream, in, (pck::i64)K,
+                                (const pck::i64*)moff, a.msgs, (pck::i64)trips);
+    }
+    c->ctr.kernel_launches += 2;
+    HIPCHK(c, hipGetLastError());
+    c->pk_ms[0] = prof ? c->pk_ms[0] : 0;
+    c->pk_ms[1] = 0;
+    if (prof) { HIPCHK(c, hipStreamSynchronize(c->stream)); c->pk_ms[1] = ms_since(t0); }
+    c->pk_calls++;
+    c->pk_events += K;
+    return SW_OK;
+}
+
+// what both forms check before anything else; the bounds come back
+int pack_pre(sw_ctx* c, int64_t K, const void* sp, const void* op, const void* arity, const void* creator, const void* t, const void* sig,
+             const void* data, const void* data_off, int64_t data_bytes, const void* data_none, const void* msgs, const void* msg_off,
+             int64_t msg_cap, const void* whole, const void* whole_off, int64_t whole_cap, int64_t* bm, int64_t* bw, const char* what) {
+    if (c->poisoned) return fail(c, SW_EIO, "context unusable after an earlier device failure");
+    if (c->vkeys.empty()) return fail(c, SW_ENOTSUP, "%s: no member keys (sw_set_member_keys first)", what);
+    if (K < 0 || data_bytes < 0 || msg_cap < 0 || whole_cap < 0) return fail(c, SW_EINVAL, "%s: negative count, length or capacity", what);
+    if (K > 0x7fffffff) return fail(c, SW_ERANGE, "%s: more than 2^31 events", what);
+    if (!msg_off || !whole_off) return fail(c, SW_EINVAL, "%s: NULL offset arrays", what);
+    if (K > 0 && (!sp || !op || !arity || !creator || !t || !sig || !msgs || !whole)) return fail(c, SW_EINVAL, "%s: NULL arrays", what);
+    if (!data_off && (data || data_bytes || data_none)) return fail(c, SW_EINVAL, "%s: data needs its offsets (or none of data, offsets, length, flags)", what);
+    if (data_off && data_bytes > 0 && !data) return fail(c, SW_EINVAL, "%s: %lld data bytes and a NULL buffer", what, (long long)data_bytes);
+    pack_bound(c, K, data_bytes, bm, bw);
+    if (msg_cap < *bm || whole_cap < *bw)
+        return fail(c, SW_ERANGE, "%s: capacities %lld / %lld below sw_pack_bound's %lld / %lld (nothing written)", what, (long long)msg_cap,
+                    (long long)whole_cap, (long long)*bm, (long long)*bw);
+    return SW_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int sw_set_event_class(sw_ctx* c, const char* module, const char* qualname) {
+    if (!c) return SW_EINVAL;
+    if (!utf8_name(module) || !utf8_name(qualname)) return fail(c, SW_EINVAL, "sw_set_event_class: module and qualified name must be 1 .. 255 bytes of UTF-8");
+    if (c->pk_mod == module && c->pk_qual == qualname) return SW_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    HIPCHK(c, hipStreamSynchronize(c->stream));   // a pack call may still be reading the old header
+    c->pk_mod = module;
+    c->pk_qual = qualname;
+    c->pk_hdr_stale = true;
+    return SW_OK;
+}
+
+int sw_get_event_class(sw_ctx* c, char* module_out, char* qualname_out) {
+    if (!c) return SW_EINVAL;
+    if (module_out) memcpy(module_out, c->pk_mod.c_str(), c->pk_mod.size() + 1);
+    if (qualname_out) memcpy(qualname_out, c->pk_qual.c_str(), c->pk_qual.size() + 1);
+    return SW_OK;
+}
+
+int sw_pack_bound(sw_ctx* c, int64_t K, int64_t data_bytes, int64_t* msg_bytes, int64_t* whole_bytes) {
+    if (!c) return SW_EINVAL;
+    if (K < 0 || data_bytes < 0) return fail(c, SW_EINVAL, "sw_pack_bound: negative count or length");
+    if (K > 0x7fffffff) return fail(c, SW_ERANGE, "sw_pack_bound: more than 2^31 events");
+    int64_t m = 0, w = 0;
+    pack_bound(c, K, data_bytes, &m, &w);
+    if (msg_bytes) *msg_bytes = m;
+    if (whole_bytes) *whole_bytes = w;
+    return SW_OK;
+}
+
+int sw_pack_events_device(sw_ctx* c, int64_t K, const uint8_t* d_sp_id32, const uint8_t* d_op_id32, const uint8_t* d_arity, const int32_t* d_creator,
+                          const double* d_t, const uint8_t* d_sig64, const uint8_t* d_data, const int64_t* d_data_off, int64_t data_bytes,
+                          const uint8_t* d_data_none, uint8_t* d_msgs, int64_t* d_msg_off, int64_t msg_cap, uint8_t* d_whole, int64_t* d_whole_off,
+                          int64_t whole_cap, uint8_t* d_encodable, void* user_stream) {
+    if (!c) return SW_EINVAL;
+    const char* what = "sw_pack_events_device";
+    int64_t bm = 0, bw = 0;
+    CHK(pack_pre(c, K, d_sp_id32, d_op_id32, d_arity, d_creator, d_t, d_sig64, d_data, d_data_off, data_bytes, d_data_none, d_msgs, d_msg_off, msg_cap,
+                 d_whole, d_whole_off, whole_cap, &bm, &bw, what));
+    if (((uintptr_t)d_msgs | (uintptr_t)d_whole | (uintptr_t)d_sig64 | (uintptr_t)d_sp_id32 | (uintptr_t)d_op_id32) & 15)
+        return fail(c, SW_EINVAL, "%s: the byte streams, the signatures and the id arrays must be 16-byte aligned", what);
+    if (((uintptr_t)d_msg_off | (uintptr_t)d_whole_off | (uintptr_t)d_data_off | (uintptr_t)d_t) & 7)
+        return fail(c, SW_EINVAL, "%s: the offsets and the timestamps must be 8-byte aligned", what);
+    if ((uintptr_t)d_creator & 3) return fail(c, SW_EINVAL, "%s: the creators must be 4-byte aligned", what);
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t k = (size_t)K;
+    bool on = on_ctx_device(c, d_msg_off, (k + 1) * 8) && on_ctx_device(c, d_whole_off, (k + 1) * 8);
+    if (K > 0)
+        on = on && on_ctx_device(c, d_sp_id32, k * 32) && on_ctx_device(c, d_op_id32, k * 32) && on_ctx_device(c, d_arity, k) &&
+             on_ctx_device(c, d_creator, k * 4) && on_ctx_device(c, d_t, k * 8) && on_ctx_device(c, d_sig64, k * 64) &&
+             on_ctx_device(c, d_msgs, (size_t)msg_cap) && on_ctx_device(c, d_whole, (size_t)whole_cap) &&
+             (!d_encodable || on_ctx_device(c, d_encodable, k)) && (!d_data_off || on_ctx_device(c, d_data_off, (k + 1) * 8)) &&
+             (!d_data || data_bytes == 0 || on_ctx_device(c, d_data, (size_t)data_bytes)) && (!d_data_none || on_ctx_device(c, d_data_none, k));
+    if (!on) return fail(c, SW_EINVAL, "%s: every array must lie in memory of device %d (a host pointer, or another device's)", what, c->device);
+    if (!c->ev_user) HIPCHK(c, hipEventCreateWithFlags(&c->ev_user, hipEventDisableTiming));
+    hipStream_t us = (hipStream_t)user_stream;
+    HIPCHK(c, hipEventRecord(c->ev_user, us));            // the producers of the arrays; earlier readers of the outputs
+    HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_user, 0));
+    if (K == 0) {
+        HIPCHK(c, hipMemsetAsync(d_msg_off, 0, 8, c->stream));
+        HIPCHK(c, hipMemsetAsync(d_whole_off, 0, 8, c->stream));
+    } else {
+        CHK(pack_launch(c, K, PackArrays{d_sp_id32, d_op_id32, d_arity, d_creator, d_t, d_sig64, d_data, d_data_off, data_bytes, d_data_none, d_msgs,
+                                         d_msg_off, d_whole, d_whole_off, d_encodable}, bm, bw));
+    }
+    HIPCHK(c, hipEventRecord(c->ev_user, c->stream));     // whatever the caller enqueues next reads complete streams
+    HIPCHK(c, hipStreamWaitEvent(us, c->ev_user, 0));
+    return SW_OK;
+}
+
+int sw_pack_events(sw_ctx* c, int64_t K, const uint8_t* sp_id32, const uint8_t* op_id32, const uint8_t* arity, const int32_t* creator, const double* t,
+                   const uint8_t* sig64, const uint8_t* data, const int64_t* data_off, int64_t data_bytes, const uint8_t* data_none, uint8_t* msgs,
+                   int64_t* msg_off, int64_t msg_cap, uint8_t* whole, int64_t* whole_off, int64_t whole_cap, uint8_t* encodable, int64_t* msg_bytes,
+                   int64_t* whole_bytes) {
+    if (!c) return SW_EINVAL;
+    if (msg_bytes) *msg_bytes = 0;
+    if (whole_bytes) *whole_bytes = 0;
+    int64_t bm = 0, bw = 0;
+    CHK(pack_pre(c, K, sp_id32, op_id32, arity, creator, t, sig64, data, data_off, data_bytes, data_none, msgs, msg_off, msg_cap, whole, whole_off,
+                 whole_cap, &bm, &bw, "sw_pack_events"));
+    msg_off[0] = whole_off[0] = 0;
+    if (K == 0) return SW_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t k = (size_t)K, db = (size_t)data_bytes;
+    Carve cv;
+    const size_t o_sp = cv.take(k * 32), o_op = cv.take(k * 32), o_ar = cv.take(k), o_cr = cv.take(k * 4), o_t = cv.take(k * 8), o_sig = cv.take(k * 64);
+    const size_t o_doff = cv.take(data_off ? (k + 1) * 8 : 0), o_d = cv.take(db), o_dn = cv.take(data_none ? k : 0);
+    const size_t o_moff = cv.take((k + 1) * 8), o_woff = cv.take((k + 1) * 8), o_m = cv.take((size_t)bm), o_w = cv.take((size_t)bw), o_enc = cv.take(k);
+    CHK(dgrow(c, c->d_pk_in, cv.off + 256, 0));
+    unsigned char* B = c->d_pk_in.p;
+    const struct { size_t o; const void* src; size_t bytes; } up[] = {
+        {o_sp, sp_id32, k * 32}, {o_op, op_id32, k * 32}, {o_ar, arity, k}, {o_cr, creator, k * 4}, {o_t, t, k * 8}, {o_sig, sig64, k * 64},
+        {o_doff, data_off, data_off ? (k + 1) * 8 : 0}, {o_d, data, db}, {o_dn, data_none, data_none ? k : 0}};
+    for (const auto& u : up)
+        if (u.bytes) HIPCHK(c, hipMemcpyAsync(B + u.o, u.src, u.bytes, hipMemcpyHostToDevice, c->stream));
+    CHK(pack_launch(c, K, PackArrays{B + o_sp, B + o_op, B + o_ar, (const int32_t*)(B + o_cr), (const double*)(B + o_t), B + o_sig,
+                                     data_off ? B + o_d : nullptr, data_off ? (const int64_t*)(B + o_doff) : nullptr, data_bytes,
+                                     data_none ? B + o_dn : nullptr, B + o_m, (int64_t*)(B + o_moff), B + o_w, (int64_t*)(B + o_woff), B + o_enc}, bm, bw));
+    HIPCHK(c, hipMemcpyAsync(msg_off, B + o_moff, (k + 1) * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(whole_off, B + o_woff, (k + 1) * 8, hipMemcpyDeviceToHost, c->stream));
+    if (encodable) HIPCHK(c, hipMemcpyAsync(encodable, B + o_enc, k, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const int64_t tm = msg_off[K], tw = whole_off[K];
+    if (tm < 0 || tm > bm || tw < 0 || tw > bw) return fail(c, SW_EIO, "sw_pack_events: totals %lld / %lld outside the bounds (internal error)", (long long)tm, (long long)tw);
+    if (tm) HIPCHK(c, hipMemcpyAsync(msgs, B + o_m, (size_t)tm, hipMemcpyDeviceToHost, c->stream));
+    if (tw) HIPCHK(c, hipMemcpyAsync(whole, B + o_w, (size_t)tw, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->pk_bytes += tm + tw;
+    if (msg_bytes) *msg_bytes = tm;
+    if (whole_bytes) *whole_bytes = tw;
+    return SW_OK;
+}
+
+int sw_sync_pull_validated(sw_ctx* dst, int64_t dst_head, sw_ctx* src, int64_t src_head, int64_t* n_sent, int64_t* n_valid, int64_t* n_stored) {
+    if (!dst || !src) return SW_EINVAL;
+    const char* what = "sw_sync_pull_validated";
+    if (n_sent) *n_sent = 0;
+    if (n_valid) *n_valid = 0;
+    if (n_stored) *n_stored = 0;
+    if (dst == src) return fail(dst, SW_EINVAL, "%s: a context cannot pull from itself", what);
+    if (dst->device != src->device) return fail(dst, SW_ENOTSUP, "%s: the contexts live on devices %d and %d (same device only)", what, dst->device, src->device);
+    if (dst->n != src->n) return fail(dst, SW_EINVAL, "%s: %d members here, %d at the peer", what, dst->n, src->n);
+    if (dst->poisoned) return fail(dst, SW_EIO, "context unusable after an earlier device failure");
+    if (dst->vkeys.empty()) return fail(dst, SW_ENOTSUP, "%s: no member keys (sw_set_member_keys first)", what);
+    if (dst->n_ids != dst->N)
+        return fail(dst, SW_ENOTSUP, "%s: %lld of the %lld stored events have no id (sw_set_event_ids first)", what, (long long)(dst->N - dst->n_ids), (long long)dst->N);
+    if (dst_head < dst->first_resident || dst_head >= dst->divided) return fail(dst, SW_ERANGE, "%s: head %lld is not a divided, resident event", what, (long long)dst_head);
+    if (const int rc = export_pre(src, src_head, "sw_sync_pull_validated (peer)"); rc != SW_OK) { dst->err = src->err; return rc; }
+    HIPCHK(dst, hipSetDevice(dst->device));
+    if (!dst->h_pkcnt && hipHostMalloc((void**)&dst->h_pkcnt, sizeof(int32_t), hipHostMallocDefault) != hipSuccess) {
+        (void)hipGetLastError();
+        dst->h_pkcnt = nullptr;
+        return fail(dst, SW_ENOMEM, "hipHostMalloc for the count of valid events failed");
+    }
+    // ---- 1. and 2. as in sw_sync_pull: dst's known heights, src's ranges, count and gather
+    CHK(heights_on_device(dst));
+    const int np = dst->npad;
+    CHK(dgrow(dst, dst->d_q, (size_t)3 * np, 0));
+    if (!dst->ev_user) HIPCHK(dst, hipEventCreateWithFlags(&dst->ev_user, hipEventDisableTiming));
+    hipLaunchKernelGGL(k_known_heights, dim3(1), dim3(np), 0, dst->stream, (const int*)dst->d_L.p, (const int*)dst->d_ht.p, (int)dst_head, np, dst->d_q.p);
+    dst->ctr.kernel_launches++;
+    HIPCHK(dst, hipGetLastError());
+    HIPCHK(dst, hipEventRecord(dst->ev_user, dst->stream));
+    HIPCHK(dst, hipStreamWaitEvent(src->stream, dst->ev_user, 0));
+    const bool prof = src->profiling;
+    auto t0 = std::chrono::steady_clock::now();
+    int64_t total = 0;
+    if (const int rc = export_ranges(src, src_head, dst->d_q.p, hipMemcpyDeviceToDevice, &total); rc != SW_OK) { dst->err = src->err; return rc; }
+    src->xp_ms[0] = prof ? ms_since(t0) : 0;
+    src->xp_ms[1] = 0;
+    if (total > 0x3fffffffll || dst->N + total > 0x7ffffff0ll) return fail(dst, SW_ERANGE, "%s: more than 2^31 events", what);
+    t0 = std::chrono::steady_clock::now();
+    ExportArrays d{};
+    int rc = export_scratch(src, total, true, true, false, &d);
+    if (rc == SW_OK) rc = export_gather(src, total, d);
+    if (rc != SW_OK) { dst->err = src->err; return rc; }
+    if (prof) { HIPCHK(src, hipStreamSynchronize(src->stream)); src->xp_ms[1] = ms_since(t0); }
+    src->xp_calls++;
+    src->xp_events += total;
+    if (n_sent) *n_sent = total;
+    // ---- 3. dst, its stream ordered behind src's: the signed bytes (data None: the context stores no event data), the
+    // verdicts by dst's OWN keys and event class, ANDed with the encodable flags and counted
+    const size_t k = (size_t)total;
+    int64_t bm = 0, bw = 0;
+    pack_bound(dst, total, 0, &bm, &bw);
+    Carve cv;
+    const size_t o_moff = cv.take((k + 1) * 8), o_woff = cv.take((k + 1) * 8), o_m = cv.take((size_t)bm), o_w = cv.take((size_t)bw);
+    const size_t o_enc = cv.take(k), o_ok = cv.take(k), o_cnt = cv.take(sizeof(int32_t));
+    CHK(dgrow(dst, dst->d_pk_out, cv.off + 256, 0));
+    CHK(dgrow(dst, dst->d_pl_in, k * sizeof(int32_t), 0));
+    unsigned char* B = dst->d_pk_out.p;
+    HIPCHK(dst, hipEventRecord(dst->ev_user, src->stream));
+    HIPCHK(dst, hipStreamWaitEvent(dst->stream, dst->ev_user, 0));
+    HIPCHK(dst, hipMemsetAsync(B + o_cnt, 0, sizeof(int32_t), dst->stream));
+    rc = pack_launch(dst, total, PackArrays{d.sp_id, d.op_id, d.arity, d.creator, d.t, d.sig, nullptr, nullptr, 0, nullptr, B + o_m, (int64_t*)(B + o_moff),
+                                            B + o_w, (int64_t*)(B + o_woff), B + o_enc}, bm, bw);
+    if (rc == SW_OK) {
+        const swv::Payload p{B + o_m, (const long long*)(B + o_moff), (long long)bm, B + o_w, (const long long*)(B + o_woff), (long long)bw, d.sig, d.creator, d.id};
+        rc = validate_launch(dst, total, p, B + o_ok);
+    }
+    if (rc != SW_OK) { (void)hipStreamSynchronize(dst->stream); return rc; }   // (src's scratch is free again only once dst has read it)
+    dst->v_calls++;
+    dst->v_events += total;
+    hipLaunchKernelGGL(pck::k_pack_and_count, dim3((unsigned)std::min<int64_t>(1024, (total + 255) / 256)), dim3(256), 0, dst->stream, (pck::i64)total,
+                       B + o_ok, (const unsigned char*)(B + o_enc), (int*)(B + o_cnt));
+    dst->ctr.kernel_launches++;
+    HIPCHK(dst, hipGetLastError());
+    HIPCHK(dst, hipMemcpyAsync(dst->h_pkcnt, B + o_cnt, sizeof(int32_t), hipMemcpyDeviceToHost, dst->stream));
+    // ---- 4. dst ingests what is valid (Node.sync's loop, swirld.py:130-136)
+    int64_t stored = 0;
+    rc = payload_core(dst, total, d.id, d.sp_id, d.op_id, d.arity, d.creator, B + o_ok, d.t, d.sig, src->stream, (int32_t*)dst->d_pl_in.p, &stored);
+    const hipError_t drained = hipStreamSynchronize(dst->stream);
+    if (rc != SW_OK) return rc;
+    HIPCHK(dst, drained);
+    if (n_valid) *n_valid = *dst->h_pkcnt;
+    if (n_stored) *n_stored = stored;
+    return SW_OK;
+}
+
+int sw_get_pack_stats(sw_ctx* c, int64_t* calls, int64_t* events, int64_t* bytes, double* phase_ms) {
+    if (!c) return SW_EINVAL;
+    if (calls) *calls = c->pk_calls;
+    if (events) *events = c->pk_events;
+    if (bytes) *bytes = c->pk_bytes;
+    if (phase_ms) for (int i = 0; i < 2; ++i) phase_ms[i] = c->pk_ms[i];
     return SW_OK;
 }
 

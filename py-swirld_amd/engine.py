@@ -501,13 +501,102 @@ class Hashgraph:
                                             C.byref(n_out)))
         return d
 
-    def pull_from(self, peer, peer_head, my_head):
+    def pull_from(self, peer, peer_head, my_head, validate=False):
         """Node.sync without the new event (swirld.py:125-136) against `peer`, a Hashgraph on the same device: my known
         heights at `my_head` -> the peer's diff at `peer_head` -> my ingest, all in device memory.  Returns (n_sent,
-        n_stored); my new events are the last n_stored ones, their ids event_ids(num_events - n_stored)."""
+        n_stored); my new events are the last n_stored ones, their ids event_ids(num_events - n_stored).
+        validate=True puts is_valid_event's crypto in the middle (sw_sync_pull_validated): the signed bytes of the peer's
+        events are built on the device, judged by MY member keys and event class, and only valid events are ingested;
+        returns (n_sent, n_valid, n_stored).  Needs set_member_keys; the bytes are built with data None."""
         a, b = C.c_int64(), C.c_int64()
+        if validate:
+            v = C.c_int64()
+            self._chk(self._L.sw_sync_pull_validated(self._h, int(my_head), peer._h, int(peer_head), C.byref(a), C.byref(v), C.byref(b)))
+            return int(a.value), int(v.value), int(b.value)
         self._chk(self._L.sw_sync_pull(self._h, int(my_head), peer._h, int(peer_head), C.byref(a), C.byref(b)))
         return int(a.value), int(b.value)
+
+    # ---- the signed bytes of events built on the device (dumps(ev[:-1]), dumps(ev), swirld.py:95-103; csrc/pack.hip.h) ----
+    def set_event_class(self, module, qualname):
+        """Module and qualified name of the Event class (Event.__module__, Event.__qualname__): part of dumps(ev) and so of
+        every id.  1 .. 255 bytes of UTF-8 each; default "swirld", "Event"."""
+        self._chk(self._L.sw_set_event_class(self._h, module.encode("utf-8"), qualname.encode("utf-8")))
+
+    def event_class(self):
+        m, q = C.create_string_buffer(256), C.create_string_buffer(256)
+        self._chk(self._L.sw_get_event_class(self._h, m, q))
+        return m.value.decode("utf-8"), q.value.decode("utf-8")
+
+    def pack_bound(self, K, data_bytes=0):
+        """(msg_bytes, whole_bytes): upper bounds of the two streams for any K events with data_bytes bytes of data."""
+        m, w = C.c_int64(), C.c_int64()
+        self._chk(self._L.sw_pack_bound(self._h, int(K), int(data_bytes), C.byref(m), C.byref(w)))
+        return int(m.value), int(w.value)
+
+    def pack_events(self, sp_ids, op_ids, arity, creator, t, sig, data=None, data_off=None, data_none=None):
+        """dumps(ev[:-1]) and dumps(ev) of K events from host arrays (sw_pack_events): sp_ids / op_ids K x 32 uint8 (read
+        where arity is 2), arity uint8, creator int32 (dense member index; the key bytes are set_member_keys'), t float64,
+        sig K x 64 uint8; data (uint8) / data_off (K + 1 int64) / data_none (uint8 per event) or None: every data None.
+        Returns (msgs, msg_off, whole, whole_off, encodable): uint8 bytes and int64 offsets as validate_payload takes them
+        as (data, offsets) pairs, and a bool per event — False: the event has no such bytes and length 0 in both."""
+        arity = np.ascontiguousarray(arity, np.uint8)
+        K = arity.shape[0]
+        sp_ids, op_ids = self._ids(sp_ids, K), self._ids(op_ids, K)
+        creator = np.ascontiguousarray(creator, np.int32)
+        t = np.ascontiguousarray(t, np.float64)
+        sig = np.ascontiguousarray(sig, np.uint8).reshape(K, 64)
+        if creator.shape != (K,) or t.shape != (K,):
+            raise ValueError("creator and t must have one entry per event")
+        nbytes = 0
+        if data_off is not None:
+            data_off = np.ascontiguousarray(data_off, np.int64)
+            if data_off.shape != (K + 1,):
+                raise ValueError("data_off must have K + 1 entries")
+            data = np.zeros(0, np.uint8) if data is None else np.ascontiguousarray(data, np.uint8).reshape(-1)
+            nbytes = data.shape[0]
+            if nbytes == 0:
+                data = None
+            if data_none is not None:
+                data_none = np.ascontiguousarray(data_none, np.uint8)
+                if data_none.shape != (K,):
+                    raise ValueError("data_none must have one entry per event")
+        elif data is not None or data_none is not None:
+            raise ValueError("data needs data_off")
+        bm, bw = self.pack_bound(K, nbytes)
+        msgs, whole = np.empty(max(bm, 1), np.uint8), np.empty(max(bw, 1), np.uint8)
+        moff, woff = np.empty(K + 1, np.int64), np.empty(K + 1, np.int64)
+        enc = np.zeros(K, np.uint8)
+        tm, tw = C.c_int64(), C.c_int64()
+        self._chk(self._L.sw_pack_events(self._h, K, _p(sp_ids), _p(op_ids), _p(arity), _p(creator), _p(t), _p(sig), _p(data), _p(data_off),
+                                         nbytes, _p(data_none), _p(msgs), _p(moff), bm, _p(whole), _p(woff), bw, _p(enc),
+                                         C.byref(tm), C.byref(tw)))
+        return msgs[:tm.value], moff, whole[:tw.value], woff, enc.astype(bool)
+
+    def pack_events_device(self, sp_ids, op_ids, arity, creator, t, sig, msgs, msg_off, msg_cap, whole, whole_off, whole_cap,
+                           encodable=None, data=None, data_off=None, data_bytes=0, data_none=None, stream=0, count=None):
+        """pack_events for arrays in DEVICE memory (addresses, or objects with data_ptr() / __cuda_array_interface__), as
+        export_payload_device writes them.  msgs / whole (uint8, msg_cap / whole_cap bytes, at least pack_bound's, 16-byte
+        aligned) and msg_off / whole_off (K + 1 int64) receive the streams in the form validate_payload_device takes;
+        `encodable` (K uint8, optional) the flags.  Complete for whatever is enqueued on `stream` afterwards; nothing is
+        read back.  K comes from `creator`'s length where it has one, else from `count`."""
+        ptrs = [_dev_ptr(a) for a in (sp_ids, op_ids, arity, creator, t, sig, data, data_off, data_none, msgs, msg_off, whole, whole_off,
+                                      encodable)]
+        K = count if count is not None else ptrs[3][1]
+        if K is None:
+            raise ValueError("the number of events is not known: pass count=")
+        a = [C.c_void_p(q) if q else None for q, _ in ptrs]
+        self._chk(self._L.sw_pack_events_device(self._h, int(K), a[0], a[1], a[2], a[3], a[4], a[5], a[6], a[7], int(data_bytes), a[8],
+                                                a[9], a[10], int(msg_cap), a[11], a[12], int(whole_cap), a[13], C.c_void_p(int(stream))))
+
+    def pack_stats(self):
+        """Pack calls and events encoded so far, bytes written (host form only), and (under set_profiling) the host
+        milliseconds of the last call's lengths-and-scan and of its two writers."""
+        v = [C.c_int64() for _ in range(3)]
+        ms = (C.c_double * 2)()
+        self._chk(self._L.sw_get_pack_stats(self._h, *[C.byref(x) for x in v], ms))
+        d = dict(zip(("calls", "events", "bytes"), (int(x.value) for x in v)))
+        d.update(zip(("scan_ms", "write_ms"), (float(x) for x in ms)))
+        return d
 
     def export_stats(self):
         """Export calls and events exported since the context was created, and (under set_profiling) the host

@@ -305,7 +305,8 @@ class Node:
         self._uploaded = 0
         self._dev_ids = 0     # events whose id the device context knows (device_payload_threshold)
         self._device_payloads = 0
-        self._keys_on_device = False   # the context has the members' keys (device_validate_threshold)
+        self._keys_on_device = False   # the context has the members' keys and the Event class (device_validate_threshold)
+        self._plain_payloads = 0       # payloads whose signed bytes the device built (_batch_validate_plain)
         self._divided = 0
         self._device = device
         self._dev = Hashgraph(n_nodes, [stake[pk] for pk in self._members], coin_period=C, device=device)
@@ -397,7 +398,10 @@ class Node:
         events (wrong types or lengths) are simply invalid."""
         if not self._keys_on_device:
             self._dev.set_member_keys([bytes(pk) for pk in self._members])
+            self._dev.set_event_class(Event.__module__, Event.__qualname__)
             self._keys_on_device = True
+        if all(self._is_plain(eid, events[eid]) for eid in eids):
+            return self._batch_validate_plain(eids, events)
         is_b = lambda x, n: isinstance(x, (bytes, bytearray)) and len(x) == n
         msgs, whole, sigs, ids, good = [], [], [], [], []
         creator = np.full(len(eids), -1, np.int32)
@@ -414,6 +418,46 @@ class Node:
         ok = self._dev.validate_payload(msgs, np.frombuffer(b"".join(sigs), np.uint8), creator, whole=whole,
                                         ids=np.frombuffer(b"".join(ids), np.uint8))
         return {eid: ((True, eid) if ok[i] and good[i] else (False, None)) for i, eid in enumerate(eids)}
+
+    @staticmethod
+    def _is_plain(eid, ev):
+        """True when dumps(ev[:-1]) and dumps(ev) are the fixed template Hashgraph.pack_events writes (csrc/pack.hip.h): an
+        Event with data None, a float timestamp, parents () or two 32-byte ids, and creator key, signature and id of exactly
+        type bytes and 32, 64 and 32 bytes.  No two fields may be ONE object: pickle would write the second as a memo read."""
+        is_b = lambda x, n: type(x) is bytes and len(x) == n
+        if type(ev) is not Event or ev.d is not None or type(ev.t) is not float or type(ev.p) is not tuple:
+            return False
+        if not (is_b(ev.c, 32) and is_b(ev.s, 64) and is_b(eid, 32)):
+            return False
+        if len(ev.p) == 0:
+            return True
+        return (len(ev.p) == 2 and is_b(ev.p[0], 32) and is_b(ev.p[1], 32)
+                and ev.p[0] is not ev.p[1] and ev.p[0] is not ev.c and ev.p[1] is not ev.c)
+
+    @staticmethod
+    def _payload_arrays(eids, events, mindex):
+        """The arrays Hashgraph.pack_events / validate_payload take, for a payload of plain events: parents' ids, arity,
+        creator (dense index, -1 for a non-member), timestamp, signature, id."""
+        K = len(eids)
+        evs = [events[eid] for eid in eids]
+        zero = b"\0" * 32
+        sp = np.frombuffer(b"".join(ev.p[0] if ev.p else zero for ev in evs), np.uint8).reshape(K, 32)
+        op = np.frombuffer(b"".join(ev.p[1] if ev.p else zero for ev in evs), np.uint8).reshape(K, 32)
+        arity = np.fromiter((len(ev.p) for ev in evs), np.uint8, K)
+        creator = np.fromiter((mindex.get(ev.c, -1) for ev in evs), np.int32, K)
+        t = np.fromiter((ev.t for ev in evs), np.float64, K)
+        sig = np.frombuffer(b"".join(ev.s for ev in evs), np.uint8).reshape(K, 64)
+        ids = np.frombuffer(b"".join(eids), np.uint8).reshape(K, 32)
+        return sp, op, arity, creator, t, sig, ids
+
+    def _batch_validate_plain(self, eids, events):
+        """_batch_validate for plain events (_is_plain): no dumps per event — the arrays go to the device, which builds the
+        signed bytes itself (Hashgraph.pack_events) and judges them (Hashgraph.validate_payload)."""
+        sp, op, arity, creator, t, sig, ids = self._payload_arrays(eids, events, self._mindex)
+        msgs, moff, whole, woff, enc = self._dev.pack_events(sp, op, arity, creator, t, sig)
+        ok = self._dev.validate_payload((msgs, moff), sig, creator, whole=(whole, woff), ids=ids)
+        self._plain_payloads += 1
+        return {eid: ((True, eid) if ok[i] and enc[i] else (False, None)) for i, eid in enumerate(eids)}
 
     def _validate_threshold(self):
         """device_validate_threshold where the device verifier applies: real Ed25519 keys of 32 bytes."""
