@@ -523,7 +523,7 @@ int sw_get_validate_stats(sw_ctx* ctx, int64_t* calls, int64_t* events, int64_t*
  *   *n_valid: the events that passed, counted on the device and read at the call's final drain.  Preconditions: those of
  *   sw_sync_pull, and keys set in dst (SW_ENOTSUP, nothing stored).  The context does NOT store event data: the bytes are
  *   built with data None, so events that src's members signed with other data fail the id check and are rejected one by
- *   one, with their descendants.  Carrying data through ingest and export is a later change.
+ *   one, with their descendants.  sw_sync_pull_data (below) is the pull for hashgraphs whose events carry data.
  *
  * sw_get_pack_stats   pack calls (sw_sync_pull_validated's included) and the events they encoded since sw_create, the
  *   bytes written (counted by the host-array form only: the device form never reads its totals), and — under
@@ -544,6 +544,87 @@ int sw_pack_events(sw_ctx* ctx, int64_t K, const uint8_t* sp_id32, const uint8_t
 int sw_sync_pull_validated(sw_ctx* dst, int64_t dst_head, sw_ctx* src, int64_t src_head, int64_t* n_sent, int64_t* n_valid,
                            int64_t* n_stored);
 int sw_get_pack_stats(sw_ctx* ctx, int64_t* calls, int64_t* events, int64_t* bytes, double* phase_ms);
+
+/*
+ * The DATA of events kept on the device (kernels in csrc/data.hip.h): Event.d, the transaction an event
+ * carries (swirld.py:30, :82-95) — a bytes object of 0 .. 60 000 bytes, or None, per event.  It is part of what is signed
+ * and of what the id is the hash of.  A context keeps it in one byte arena with int64 offsets and one None flag per event,
+ * allocated on first use and grown geometrically; the layout is that of sw_pack_events_device's data arguments.  The store
+ * is COMPLETE when every stored event has an entry (an empty context counts), the semantics of the id index: events
+ * appended by index (sw_append_events[_device], sw_ingest_payload[_device], sw_sync_pull[_validated]) get NO entry, and the
+ * store stays incomplete until sw_set_event_data has caught up.  sw_rewind keeps the data (the events stay), sw_reset
+ * forgets it.  The store is independent of the voting state: it works on the exact path and with the windowed table.
+ * OUT OF SCOPE: the data of rows the window has evicted is NOT evicted, and data that is neither None nor bytes cannot
+ * be stored (a caller stores None for it and keeps the object itself).
+ *
+ * sw_set_event_data   the data of the stored events [first, first + K), host arrays: event first + i has
+ *   data[data_off[i] .. data_off[i+1]) (K + 1 int64 offsets; an empty range is b''), data_none (uint8 per event, may be
+ *   NULL) nonzero marks None whatever the range.  data, data_off, data_none all NULL (data_bytes 0): every event is None.
+ *   `first` must equal the number of events that have data (SW_EINVAL); first + K beyond the stored events: SW_ERANGE.  An
+ *   offset that is negative, decreasing, beyond data_bytes, or a length above 60 000: SW_EINVAL, nothing stored.
+ * sw_set_event_data_device   the same from memory of the context's device (a host pointer: SW_EINVAL before anything is
+ *   launched; d_data_off 8-byte aligned), with the stream contract of sw_pack_events_device.  The offsets are checked on
+ *   the device; the call synchronises once, to read the byte total and the verdict.
+ * sw_get_event_data   the entries of [first, first + K) (beyond the events that have data: SW_ERANGE): K + 1 offsets
+ *   rebased to 0, the bytes, the None flags (a None entry has an empty range).  *n_bytes receives the bytes required;
+ *   cap below that: SW_ERANGE, nothing written.
+ * sw_gather_event_data_device   the data of K events named by DENSE INDEX in d_event (int32, device memory), in the order
+ *   given, repeats allowed: d_data_off receives K + 1 int64 offsets from 0, d_data the bytes back to back, d_data_none the
+ *   flags.  This turns the d_event array of sw_export_payload_device, or of sw_export_ordered_device, into the payloads of
+ *   a sync answer or of the consensus stream.  An index outside [0, events that have data): SW_ERANGE, nothing written.
+ *   The call synchronises once, to read the byte total and the bad-index count; *n_bytes receives the total; cap (the
+ *   capacity of d_data) below it: SW_ERANGE, nothing written; cap = 0 with the three arrays NULL asks for the size
+ *   (SW_OK when it is 0).  d_data 16-byte aligned, d_data_off 8-byte aligned, every array in memory of the context's
+ *   device: SW_EINVAL before any launch.  Streams as above.  READ-ONLY with respect to every getter (kernel_launches and
+ *   the statistics below move).
+ * sw_gather_event_data   the same with host arrays, staged through context scratch.
+ * sw_ingest_payload_data_device   sw_ingest_payload_device whose accepted events bring their data: the four data
+ *   arguments as for sw_pack_events_device, one range per payload event.  Needs a complete id index AND a complete data
+ *   store (SW_ENOTSUP, nothing stored).  An event whose range is negative, decreasing, beyond data_bytes or longer than
+ *   60 000 is not valid: its d_index_out is -3 (its descendants' -6), the rule sw_pack_events_device's d_encodable states.
+ *   The data of the events stored by the call is appended in dense-index order.  Memory for the whole payload is reserved
+ *   before anything is committed; behind the commit a failure leaves the context poisoned (SW_EIO from then on), as a
+ *   failed id-table insert does.  The buffers may derive from a peer's bytes: no byte outside [0, data_bytes) is read and
+ *   no offset is followed before it is checked.  The ranges of a peer may OVERLAP (offsets that jump back across a rejected
+ *   event): when the usable ranges together hold more than data_bytes bytes the whole payload is refused, SW_EINVAL,
+ *   nothing stored — so what is appended never exceeds what was reserved.  A usable range is required of EVERY event,
+ *   also of one whose d_data_none flag is set (the flag decides between None and the range's bytes, it does not excuse an
+ *   unusable range; sw_set_event_data and sw_pack_events_device's d_encodable judge the same way).
+ *   STREAMS: as for sw_ingest_payload_device — the context's stream first waits for what `user_stream` has enqueued so
+ *   far; the call synchronises with the host before it returns (after the fold, inside the ingest, and after the copy of
+ *   the data), so on return every array, the data arrays included, may be reused or freed, and d_index_out is complete.
+ * sw_ingest_payload_data   the same with host arrays.
+ * sw_sync_pull_data   sw_sync_pull (validate = 0) or sw_sync_pull_validated (validate != 0) for events WITH data: src
+ *   gathers the data of the exported events into its scratch, beside the other arrays (one more synchronisation of src's
+ *   stream, for the byte total); with `validate`, dst packs the signed bytes with that data, validates with its own keys,
+ *   ANDs the encodable flags, and ingests through the data ingest.  Needs complete data stores on both sides
+ *   (SW_ENOTSUP).  Only the event count and the byte total cross to the host.  *n_valid is written only with `validate`.
+ * sw_get_data_stats   events that have data, arena bytes in use, store calls (set and ingest), gather calls (sw_sync_pull_data's
+ *   included), bytes gathered, and — under sw_set_profiling — the host time in ms of the last call's lengths + scan and of
+ *   its copy: phase_ms[2].  Any pointer may be NULL.
+ */
+int sw_set_event_data(sw_ctx* ctx, int64_t first, int64_t K, const uint8_t* data, const int64_t* data_off, int64_t data_bytes,
+                      const uint8_t* data_none);
+int sw_set_event_data_device(sw_ctx* ctx, int64_t first, int64_t K, const uint8_t* d_data, const int64_t* d_data_off,
+                             int64_t data_bytes, const uint8_t* d_data_none, void* user_stream);
+int sw_get_event_data(sw_ctx* ctx, int64_t first, int64_t K, int64_t cap, uint8_t* data, int64_t* data_off, uint8_t* data_none,
+                      int64_t* n_bytes);
+int sw_gather_event_data_device(sw_ctx* ctx, int64_t K, const int32_t* d_event, int64_t cap, uint8_t* d_data, int64_t* d_data_off,
+                                uint8_t* d_data_none, void* user_stream, int64_t* n_bytes);
+int sw_gather_event_data(sw_ctx* ctx, int64_t K, const int32_t* event, int64_t cap, uint8_t* data, int64_t* data_off,
+                         uint8_t* data_none, int64_t* n_bytes);
+int sw_ingest_payload_data_device(sw_ctx* ctx, int64_t K, const uint8_t* d_id32, const uint8_t* d_sp_id32, const uint8_t* d_op_id32,
+                                  const uint8_t* d_arity, const int32_t* d_creator, const uint8_t* d_ok, const double* d_t,
+                                  const uint8_t* d_sig64, void* user_stream, int32_t* d_index_out, int64_t* n_stored,
+                                  const uint8_t* d_data, const int64_t* d_data_off, int64_t data_bytes, const uint8_t* d_data_none);
+int sw_ingest_payload_data(sw_ctx* ctx, int64_t K, const uint8_t* id32, const uint8_t* sp_id32, const uint8_t* op_id32,
+                           const uint8_t* arity, const int32_t* creator, const uint8_t* ok, const double* t, const uint8_t* sig64,
+                           int32_t* index_out, int64_t* n_stored, const uint8_t* data, const int64_t* data_off, int64_t data_bytes,
+                           const uint8_t* data_none);
+int sw_sync_pull_data(sw_ctx* dst, int64_t dst_head, sw_ctx* src, int64_t src_head, int validate, int64_t* n_sent, int64_t* n_valid,
+                      int64_t* n_stored);
+int sw_get_data_stats(sw_ctx* ctx, int64_t* events, int64_t* bytes, int64_t* store_calls, int64_t* gather_calls,
+                      int64_t* gather_bytes, double* phase_ms);
 
 /* Exact work counters of the calls so far: used by bench.py's roofline. */
 typedef struct sw_counters {

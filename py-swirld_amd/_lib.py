@@ -104,6 +104,15 @@ SIGNATURES = {
                                  C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "sw_sync_pull_validated": (C.c_int, [_P, C.c_int64, _P, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "sw_get_pack_stats": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), _P]),
+    "sw_set_event_data": (C.c_int, [_P, C.c_int64, C.c_int64, _P, _P, C.c_int64, _P]),
+    "sw_set_event_data_device": (C.c_int, [_P, C.c_int64, C.c_int64, _P, _P, C.c_int64, _P, _P]),
+    "sw_get_event_data": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int64, _P, _P, _P, C.POINTER(C.c_int64)]),
+    "sw_gather_event_data_device": (C.c_int, [_P, C.c_int64, _P, C.c_int64, _P, _P, _P, _P, C.POINTER(C.c_int64)]),
+    "sw_gather_event_data": (C.c_int, [_P, C.c_int64, _P, C.c_int64, _P, _P, _P, C.POINTER(C.c_int64)]),
+    "sw_ingest_payload_data_device": (C.c_int, [_P, C.c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.POINTER(C.c_int64), _P, _P, C.c_int64, _P]),
+    "sw_ingest_payload_data": (C.c_int, [_P, C.c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.POINTER(C.c_int64), _P, _P, C.c_int64, _P]),
+    "sw_sync_pull_data": (C.c_int, [_P, C.c_int64, _P, C.c_int64, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "sw_get_data_stats": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), _P]),
     "sw_num_ordered":(C.c_int, [_P, C.POINTER(C.c_int64)]),
     "sw_get_transactions": (C.c_int, [_P, C.c_int64, C.c_int64, _P]),
     "sw_get_counters": (C.c_int, [_P, C.POINTER(Counters)]),

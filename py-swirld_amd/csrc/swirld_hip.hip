@@ -24,6 +24,7 @@
 #include "crypto.hip.h"
 #include "validate.hip.h"
 #include "pack.hip.h"
+#include "data.hip.h"
 #include "exact.hip.h"
 #include "ingest.hip.h"
 #include "resolve.hip.h"
@@ -207,6 +208,18 @@ struct sw_ctx {
     int32_t* h_pkcnt = nullptr;   // pinned: the count of valid events of sw_sync_pull_validated
     int64_t pk_calls = 0, pk_events = 0, pk_bytes = 0;   // sw_get_pack_stats
     double pk_ms[2] = {0, 0};     // ... host time under sw_set_profiling: lengths and scan, the two writers
+    // the data of events (sw_set_event_data[_device], sw_gather_event_data[_device], sw_ingest_payload_data[_device],
+    // sw_sync_pull_data; data.hip.h): allocated on first use; sw_rewind keeps it (the events stay), sw_reset forgets it
+    DBuf<unsigned char> d_data;   // the arena: 256-byte aligned, at least dat::SLACK readable bytes behind data_used
+    DBuf<long long> d_data_off;   // [n_data + 1] absolute offsets into the arena, contiguous; [0] = 0
+    DBuf<unsigned char> d_data_none;   // per event that has data: nonzero = None
+    int64_t n_data = 0;           // events [0, n_data) have data; the store is COMPLETE when n_data == N
+    int64_t data_used = 0;        // bytes of the arena in use
+    DBuf<unsigned char> d_dt;     // scratch of a call: scanned offsets + the bad-slot count, none flags, tile sums, slots, folded ok
+    DBuf<unsigned char> d_dt_in;  // the staged arrays of the host-array forms
+    DBuf<unsigned char> d_dt_out; // the gathered data: of the host-array gather, and of sw_sync_pull_data's exported events (in the answering context)
+    int64_t dt_store_calls = 0, dt_gather_calls = 0, dt_gather_bytes = 0;   // sw_get_data_stats
+    double dt_ms[2] = {0, 0};     // ... host time under sw_set_profiling: lengths + scan, the copy
 
     // device: events
     DBuf<int32_t> d_cr, d_sp, d_op, d_ht, d_seq, d_round, d_L, d_chain_ev;
@@ -3159,6 +3172,7 @@ int sw_destroy(sw_ctx* c) {
     dfree(c->d_rr); dfree(c->d_cts); dfree(c->d_tx); dfree(c->d_cs_ordpos); dfree(c->d_cs_out);
     dfree(c->d_vkeys); dfree(c->d_vtab); dfree(c->d_v_in);
     dfree(c->d_pk_hdr); dfree(c->d_pk); dfree(c->d_pk_in); dfree(c->d_pk_out);
+    dfree(c->d_data); dfree(c->d_data_off); dfree(c->d_data_none); dfree(c->d_dt); dfree(c->d_dt_in); dfree(c->d_dt_out);
     if (c->h_pkcnt) (void)hipHostFree(c->h_pkcnt);
     if (c->h_plcnt) (void)hipHostFree(c->h_plcnt);
     if (c->ev_aux_done) (void)hipEventDestroy(c->ev_aux_done);
@@ -4644,6 +4658,8 @@ int sw_reset(sw_ctx* c) {
     c->ht_pending = false;   // (the heights kernel of a device append ran there too)
     c->ht_dev_upto = 0;
     c->n_ids = 0;   // the ids go with the events (the table keeps its size and is emptied)
+    c->n_data = 0;  // ... and so does their data (the arena keeps its size)
+    c->data_used = 0;
     if (c->idtab_log) HIPCHK(c, hipMemsetAsync(c->d_idtab.p, 0xff, sizeof(int32_t) << c->idtab_log, c->stream));
     c->exact = false;  // (a fresh hashgraph starts on the fast path again)
     c->chunks_off = false;  // ... and with the chunked sweep
@@ -5922,6 +5938,514 @@ int sw_get_pack_stats(sw_ctx* c, int64_t* calls, int64_t* events, int64_t* bytes
     if (events) *events = c->pk_events;
     if (bytes) *bytes = c->pk_bytes;
     if (phase_ms) for (int i = 0; i < 2; ++i) phase_ms[i] = c->pk_ms[i];
+    return SW_OK;
+}
+
+// ---- the data of events kept on the device (data.hip.h) -------------------------------------------------
+}  // extern "C"
+
+namespace {
+
+struct DataPlan {   // the scratch of one call inside d_dt
+    dat::i64* off;            // [K + 1] lengths, then scanned offsets; [K + 1]: the bad-slot count (low 32 bits)
+    unsigned char* none;      // [K]
+    dat::i64* tsum;           // tile sums of the scan
+    int* slot;                // [slots] dense rank -> payload position (ingest append)
+    unsigned char* ok;        // [oks] the folded verdicts (ingest)
+};
+
+int data_scratch(sw_ctx* c, int64_t K, int64_t slots, int64_t oks, DataPlan* p) {
+    const size_t k = (size_t)K, tiles = (k + pck::TILE - 1) / pck::TILE;
+    Carve cv;
+    const size_t o_off = cv.take((k + 2) * 8), o_none = cv.take(k), o_ts = cv.take((tiles + 1) * 8), o_slot = cv.take((size_t)slots * 4), o_ok = cv.take((size_t)oks);
+    CHK(dgrow(c, c->d_dt, cv.off + 256, 0));
+    unsigned char* B = c->d_dt.p;
+    *p = DataPlan{(dat::i64*)(B + o_off), B + o_none, (dat::i64*)(B + o_ts), (int*)(B + o_slot), B + o_ok};
+    return SW_OK;
+}
+
+// room for the data of `events` events in `bytes` bytes (contents kept): arena with its slack, offsets, flags
+int data_reserve(sw_ctx* c, int64_t events, int64_t bytes) {
+    CHK(dgrow(c, c->d_data, (size_t)bytes + dat::SLACK + 256, (size_t)c->data_used));
+    CHK(dgrow(c, c->d_data_off, (size_t)events + 1, c->d_data_off.p ? (size_t)c->n_data + 1 : 0));
+    CHK(dgrow(c, c->d_data_none, (size_t)events + 256, (size_t)c->n_data));
+    return SW_OK;
+}
+
+// lengths, scan, and the read-back of the byte total and the bad-slot count: ONE synchronisation
+int data_plan(sw_ctx* c, int64_t K, const dat::SegIn& in, const DataPlan& p, int64_t* total, int64_t* bad) {
+    const auto t0 = std::chrono::steady_clock::now();
+    HIPCHK(c, hipMemsetAsync(p.off + K, 0, 16, c->stream));   // off[K] (K = 0: the total) and the count
+    if (K > 0) {
+        const int64_t tiles = (K + pck::TILE - 1) / pck::TILE;
+        hipLaunchKernelGGL(dat::k_data_lengths, dim3((unsigned)((K + 255) / 256)), dim3(256), 0, c->stream, in, (dat::i64)K, p.off, p.none, (int*)(p.off + K + 1));
+        hipLaunchKernelGGL(pck::k_pack_tile_sums, dim3((unsigned)tiles, 1), dim3(pck::SCAN_THREADS), 0, c->stream, (pck::i64)K, (pck::i64)tiles,
+                           (const pck::i64*)p.off, (const pck::i64*)p.off, p.tsum);
+        hipLaunchKernelGGL(pck::k_pack_scan_sums, dim3(1), dim3(pck::SCAN_THREADS), 0, c->stream, (pck::i64)K, (pck::i64)tiles, p.off, p.off, p.tsum);
+        hipLaunchKernelGGL(pck::k_pack_offsets, dim3((unsigned)tiles, 1), dim3(pck::SCAN_THREADS), 0, c->stream, (pck::i64)K, (pck::i64)tiles, p.off, p.off,
+                           (const pck::i64*)p.tsum);
+        c->ctr.kernel_launches += 4;
+        HIPCHK(c, hipGetLastError());
+    }
+    long long rb[2] = {0, 0};
+    HIPCHK(c, hipMemcpyAsync(rb, p.off + K, sizeof rb, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    *total = rb[0];
+    *bad = rb[1] & 0xffffffffll;
+    c->dt_ms[0] = c->profiling ? ms_since(t0) : 0;
+    c->dt_ms[1] = 0;
+    return SW_OK;
+}
+
+// the copy of `total` bytes to dst + dst_base (the destination holds dst_base + total bytes at least), and the offsets
+// (plus `base`) and flags to where they stay; asynchronous
+int data_copy(sw_ctx* c, int64_t K, const dat::SegIn& in, const DataPlan& p, int64_t total, unsigned char* dst, int64_t dst_base, int64_t base,
+              int64_t* off_out, unsigned char* none_out) {
+    const auto t0 = std::chrono::steady_clock::now();
+    if (total > 0) {
+        const int64_t chunks = ((dst_base & 15) + total + 15) / 16;
+        const int64_t blocks = std::max<int64_t>(1, std::min<int64_t>(4096, (chunks + dat::WRITE_THREADS - 1) / dat::WRITE_THREADS));
+        const int64_t trips = (chunks + blocks * dat::WRITE_THREADS - 1) / (blocks * dat::WRITE_THREADS);
+        hipLaunchKernelGGL(dat::k_data_copy, dim3((unsigned)blocks), dim3(dat::WRITE_THREADS), 0, c->stream, in, (dat::i64)K, (const dat::i64*)p.off, dst,
+                           (dat::i64)dst_base, (dat::i64)trips);
+        c->ctr.kernel_launches++;
+    }
+    hipLaunchKernelGGL(dat::k_data_store_off, dim3((unsigned)((K + 256) / 256)), dim3(256), 0, c->stream, (dat::i64)K, (const dat::i64*)p.off, (dat::i64)base,
+                       (dat::i64*)off_out, (const unsigned char*)p.none, none_out);
+    c->ctr.kernel_launches++;
+    HIPCHK(c, hipGetLastError());
+    if (c->profiling) { HIPCHK(c, hipStreamSynchronize(c->stream)); c->dt_ms[1] = ms_since(t0); }
+    return SW_OK;
+}
+
+// what both forms of sw_set_event_data check first
+int data_set_args(sw_ctx* c, int64_t first, int64_t K, const void* data, const void* data_off, int64_t data_bytes, const void* data_none, const char* what) {
+    if (c->poisoned) return fail(c, SW_EIO, "context unusable after an earlier device failure");
+    if (K < 0 || data_bytes < 0) return fail(c, SW_EINVAL, "%s: negative count or length", what);
+    if (first != c->n_data) return fail(c, SW_EINVAL, "%s must continue at event %lld (got %lld): data is contiguous from 0", what, (long long)c->n_data, (long long)first);
+    if (first + K > c->N) return fail(c, SW_ERANGE, "%s: events [%lld, %lld) outside the stored hashgraph", what, (long long)first, (long long)(first + K));
+    if (!data_off && (data || data_bytes || data_none)) return fail(c, SW_EINVAL, "%s: data needs its offsets (or none of data, offsets, length, flags)", what);
+    if (data_off && data_bytes > 0 && !data) return fail(c, SW_EINVAL, "%s: %lld data bytes and a NULL buffer", what, (long long)data_bytes);
+    return SW_OK;
+}
+
+// the store call behind the argument checks: every array in device memory and visible to the context's stream
+int data_set_body(sw_ctx* c, int64_t K, const uint8_t* d_data, const int64_t* d_off, int64_t data_bytes, const uint8_t* d_none, const char* what) {
+    DataPlan p{};
+    CHK(data_scratch(c, K, 0, 0, &p));
+    const dat::SegIn in{d_data, (const dat::i64*)d_off, d_none, nullptr, (dat::i64)K, (dat::i64)data_bytes, 0};
+    int64_t total = 0, bad = 0;
+    CHK(data_plan(c, K, in, p, &total, &bad));
+    if (bad) return fail(c, SW_EINVAL, "%s: %lld events with offsets that are negative, decreasing, beyond the %lld data bytes, or a length above %d (nothing stored)",
+                         what, (long long)bad, (long long)data_bytes, dat::MAX_DATA);
+    if (total < 0 || total > data_bytes) return fail(c, SW_EIO, "%s: %lld bytes from a buffer of %lld (internal error)", what, (long long)total, (long long)data_bytes);
+    CHK(data_reserve(c, c->n_data + K, c->data_used + total));
+    CHK(data_copy(c, K, in, p, total, c->d_data.p, c->data_used, c->data_used, (int64_t*)c->d_data_off.p + c->n_data, c->d_data_none.p + c->n_data));
+    c->n_data += K;
+    c->data_used += total;
+    c->dt_store_calls++;
+    return SW_OK;
+}
+
+int data_gather_args(sw_ctx* c, int64_t K, const void* event, int64_t cap, const void* data, const void* off, const void* none, int64_t* n_bytes, bool* query, const char* what) {
+    if (!n_bytes) return fail(c, SW_EINVAL, "%s: n_bytes is NULL", what);
+    *n_bytes = 0;
+    if (c->poisoned) return fail(c, SW_EIO, "context unusable after an earlier device failure");
+    if (K < 0 || cap < 0) return fail(c, SW_EINVAL, "%s: negative count or capacity", what);
+    if (K > 0x7fffffff) return fail(c, SW_ERANGE, "%s: more than 2^31 events", what);
+    if (K > 0 && !event) return fail(c, SW_EINVAL, "%s: NULL event indices", what);
+    *query = cap == 0 && !data && !off && !none;
+    if (!*query && (!off || (K > 0 && !none) || (cap > 0 && !data))) return fail(c, SW_EINVAL, "%s: NULL output arrays (capacity %lld)", what, (long long)cap);
+    if (K > 0 && c->n_data == 0) return fail(c, SW_ERANGE, "%s: no event has data (nothing written)", what);
+    return SW_OK;
+}
+
+// the gather behind the argument checks, in two steps: lengths, scan and the refusals (one synchronisation) ...
+int data_gather_plan(sw_ctx* c, int64_t K, const int32_t* d_event, int64_t cap, int64_t* n_bytes, DataPlan* p, dat::SegIn* in, const char* what) {
+    CHK(data_scratch(c, K, 0, 0, p));
+    *in = dat::SegIn{c->d_data.p, (const dat::i64*)c->d_data_off.p, c->d_data_none.p, d_event, (dat::i64)c->n_data, (dat::i64)c->data_used, 1};
+    int64_t total = 0, bad = 0;
+    CHK(data_plan(c, K, *in, *p, &total, &bad));
+    if (bad) return fail(c, SW_ERANGE, "%s: %lld indices outside the %lld events that have data (nothing written)", what, (long long)bad, (long long)c->n_data);
+    *n_bytes = total;
+    if (total > cap) return fail(c, SW_ERANGE, "%s: %lld bytes to gather, capacity %lld (nothing written)", what, (long long)total, (long long)cap);
+    return SW_OK;
+}
+// ... and the copy into device arrays that hold *n_bytes bytes, K + 1 offsets and K flags
+int data_gather_copy(sw_ctx* c, int64_t K, const DataPlan& p, const dat::SegIn& in, int64_t total, uint8_t* d_data, int64_t* d_off, uint8_t* d_none) {
+    CHK(data_copy(c, K, in, p, total, d_data, 0, 0, d_off, d_none));
+    c->dt_gather_calls++;
+    c->dt_gather_bytes += total;
+    return SW_OK;
+}
+
+int data_payload_args(sw_ctx* c, const void* data, const void* data_off, int64_t data_bytes, const void* data_none, const char* what) {
+    if (c->n_data != c->N)
+        return fail(c, SW_ENOTSUP, "%s: %lld of the %lld stored events have no data entry (sw_set_event_data first)", what, (long long)(c->N - c->n_data), (long long)c->N);
+    if (data_bytes < 0) return fail(c, SW_EINVAL, "%s: negative data length", what);
+    if (!data_off && (data || data_bytes || data_none)) return fail(c, SW_EINVAL, "%s: data needs its offsets (or none of data, offsets, length, flags)", what);
+    if (data_off && data_bytes > 0 && !data) return fail(c, SW_EINVAL, "%s: %lld data bytes and a NULL buffer", what, (long long)data_bytes);
+    return SW_OK;
+}
+
+// payload_core whose accepted events bring their data.  Everything that can be refused or can run out of memory in the
+// ordinary case comes first; behind payload_core's commit a failure poisons the context.
+int ingest_data_core(sw_ctx* c, int64_t K, const uint8_t* d_id32, const uint8_t* d_sp_id32, const uint8_t* d_op_id32, const uint8_t* d_arity,
+                     const int32_t* d_creator, const uint8_t* d_ok, const double* d_t, const uint8_t* d_sig64, const uint8_t* d_data, const int64_t* d_off,
+                     int64_t data_bytes, const uint8_t* d_none, hipStream_t us, int32_t* d_out, int64_t* n_stored) {
+    const int64_t N0 = c->N;
+    DataPlan p{};
+    CHK(data_scratch(c, K, K, K, &p));
+    CHK(data_reserve(c, N0 + K, c->data_used + data_bytes));
+    if (!c->ev_user) HIPCHK(c, hipEventCreateWithFlags(&c->ev_user, hipEventDisableTiming));
+    HIPCHK(c, hipEventRecord(c->ev_user, us));
+    HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_user, 0));
+    // an event whose data range cannot be used is not valid (-3): pack's d_encodable rule, folded into a copy of d_ok
+    // The lengths of the ranges that stay ok are summed: ranges of a peer may overlap (offsets that jump back across a
+    // rejected event), and the append could then outgrow the reservation behind the commit.  Such a payload is refused whole.
+    dat::u64* d_sum = (dat::u64*)(p.off + K + 1);
+    HIPCHK(c, hipMemsetAsync(d_sum, 0, sizeof(dat::u64), c->stream));
+    hipLaunchKernelGGL(dat::k_data_fold_ok, dim3((unsigned)((K + 255) / 256)), dim3(256), 0, c->stream, (dat::i64)K, d_ok, (const dat::i64*)d_off,
+                       (dat::i64)data_bytes, p.ok, d_sum);
+    c->ctr.kernel_launches++;
+    HIPCHK(c, hipGetLastError());
+    unsigned long long usable = 0;
+    HIPCHK(c, hipMemcpyAsync(&usable, d_sum, sizeof usable, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (usable > (unsigned long long)data_bytes)
+        return fail(c, SW_EINVAL, "the usable data ranges of the payload hold %llu bytes, its buffer %lld: ranges overlap (nothing stored)", usable,
+                    (long long)data_bytes);
+    CHK(payload_core(c, K, d_id32, d_sp_id32, d_op_id32, d_arity, d_creator, p.ok, d_t, d_sig64, c->stream, d_out, n_stored));
+    const int64_t A = *n_stored;
+    if (A == 0) return SW_OK;
+    // ---- committed: the data of the new events, in dense order (slot r = the payload position of the event with index N0 + r)
+    const auto after = [&]() -> int {
+        HIPCHK(c, hipMemsetAsync(p.slot, 0x7f, (size_t)A * sizeof(int32_t), c->stream));
+        hipLaunchKernelGGL(dat::k_data_slots, dim3((unsigned)((K + 255) / 256)), dim3(256), 0, c->stream, (dat::i64)K, (const int*)d_out, (int)N0, (dat::i64)A, p.slot);
+        c->ctr.kernel_launches++;
+        const dat::SegIn in{d_data, (const dat::i64*)d_off, d_none, p.slot, (dat::i64)K, (dat::i64)data_bytes, 0};
+        int64_t total = 0, bad = 0;
+        CHK(data_plan(c, A, in, p, &total, &bad));
+        if (bad || total < 0 || total > data_bytes)   // (the stored events' ranges are among the usable ones, summed above)
+            return fail(c, SW_EIO, "data of the accepted events: %lld bad slots, %lld bytes of %lld (internal error)", (long long)bad, (long long)total, (long long)data_bytes);
+        CHK(data_copy(c, A, in, p, total, c->d_data.p, c->data_used, c->data_used, (int64_t*)c->d_data_off.p + N0, c->d_data_none.p + N0));
+        HIPCHK(c, hipStreamSynchronize(c->stream));   // the copy has read the caller's arrays: on return they may be reused or freed
+        c->n_data = N0 + A;
+        c->data_used += total;
+        c->dt_store_calls++;
+        return SW_OK;
+    };
+    const int rc = after();
+    if (rc != SW_OK) c->poisoned = true;
+    return rc;
+}
+
+}  // namespace
+
+extern "C" {
+
+int sw_set_event_data_device(sw_ctx* c, int64_t first, int64_t K, const uint8_t* d_data, const int64_t* d_data_off, int64_t data_bytes,
+                             const uint8_t* d_data_none, void* user_stream) {
+    if (!c) return SW_EINVAL;
+    const char* what = "sw_set_event_data_device";
+    CHK(data_set_args(c, first, K, d_data, d_data_off, data_bytes, d_data_none, what));
+    if ((uintptr_t)d_data_off & 7) return fail(c, SW_EINVAL, "%s: the offsets must be 8-byte aligned", what);
+    if (K == 0) return SW_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t k = (size_t)K;
+    if ((d_data_off && !on_ctx_device(c, d_data_off, (k + 1) * 8)) || (d_data && data_bytes > 0 && !on_ctx_device(c, d_data, (size_t)data_bytes)) ||
+        (d_data_none && !on_ctx_device(c, d_data_none, k)))
+        return fail(c, SW_EINVAL, "%s: every array must lie in memory of device %d (a host pointer, or another device's)", what, c->device);
+    if (!c->ev_user) HIPCHK(c, hipEventCreateWithFlags(&c->ev_user, hipEventDisableTiming));
+    hipStream_t us = (hipStream_t)user_stream;
+    HIPCHK(c, hipEventRecord(c->ev_user, us));
+    HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_user, 0));
+    CHK(data_set_body(c, K, d_data, d_data_off, data_bytes, d_data_none, what));
+    HIPCHK(c, hipEventRecord(c->ev_user, c->stream));     // the caller may reuse its arrays behind this
+    HIPCHK(c, hipStreamWaitEvent(us, c->ev_user, 0));
+    return SW_OK;
+}
+
+int sw_set_event_data(sw_ctx* c, int64_t first, int64_t K, const uint8_t* data, const int64_t* data_off, int64_t data_bytes, const uint8_t* data_none) {
+    if (!c) return SW_EINVAL;
+    const char* what = "sw_set_event_data";
+    CHK(data_set_args(c, first, K, data, data_off, data_bytes, data_none, what));
+    if (K == 0) return SW_OK;
+    if (data_off)
+        for (int64_t i = 0; i < K; ++i) {
+            const int64_t a = data_off[i], b = data_off[i + 1];
+            if (a < 0 || b < a || b > data_bytes || b - a > dat::MAX_DATA)
+                return fail(c, SW_EINVAL, "%s: event %lld has the data range [%lld, %lld) of %lld bytes (at most %d each; nothing stored)", what,
+                            (long long)(first + i), (long long)a, (long long)b, (long long)data_bytes, dat::MAX_DATA);
+        }
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t k = (size_t)K, db = (size_t)data_bytes;
+    Carve cv;
+    const size_t o_off = cv.take(data_off ? (k + 1) * 8 : 0), o_d = cv.take(db), o_n = cv.take(data_none ? k : 0);
+    CHK(dgrow(c, c->d_dt_in, cv.off + 256, 0));
+    unsigned char* B = c->d_dt_in.p;
+    if (data_off) HIPCHK(c, hipMemcpyAsync(B + o_off, data_off, (k + 1) * 8, hipMemcpyHostToDevice, c->stream));
+    if (db) HIPCHK(c, hipMemcpyAsync(B + o_d, data, db, hipMemcpyHostToDevice, c->stream));
+    if (data_none) HIPCHK(c, hipMemcpyAsync(B + o_n, data_none, k, hipMemcpyHostToDevice, c->stream));
+    return data_set_body(c, K, data_off ? B + o_d : nullptr, data_off ? (const int64_t*)(B + o_off) : nullptr, data_bytes, data_none ? B + o_n : nullptr, what);
+}
+
+int sw_get_event_data(sw_ctx* c, int64_t first, int64_t K, int64_t cap, uint8_t* data, int64_t* data_off, uint8_t* data_none, int64_t* n_bytes) {
+    if (!c) return SW_EINVAL;
+    if (!n_bytes) return fail(c, SW_EINVAL, "sw_get_event_data: n_bytes is NULL");
+    *n_bytes = 0;
+    if (first < 0 || K < 0 || first + K > c->n_data)
+        return fail(c, SW_ERANGE, "events [%lld, %lld) beyond the %lld events that have data", (long long)first, (long long)(first + K), (long long)c->n_data);
+    if (cap < 0) return fail(c, SW_EINVAL, "sw_get_event_data: negative capacity");
+    if (K == 0) { if (data_off) data_off[0] = 0; return SW_OK; }
+    HIPCHK(c, hipSetDevice(c->device));
+    std::vector<int64_t> off((size_t)K + 1);
+    HIPCHK(c, hipMemcpyAsync(off.data(), c->d_data_off.p + first, ((size_t)K + 1) * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    const int64_t a = off[0], bytes = off[(size_t)K] - a;
+    if (a < 0 || bytes < 0 || off[(size_t)K] > c->data_used) return fail(c, SW_EIO, "sw_get_event_data: stored offsets [%lld, %lld) (internal error)", (long long)a, (long long)off[(size_t)K]);
+    *n_bytes = bytes;
+    if (bytes > cap) return fail(c, SW_ERANGE, "sw_get_event_data: %lld bytes, capacity %lld (nothing written)", (long long)bytes, (long long)cap);
+    if (!data_off || !data_none || (bytes > 0 && !data)) return fail(c, SW_EINVAL, "sw_get_event_data: NULL output arrays");
+    if (bytes) HIPCHK(c, hipMemcpyAsync(data, c->d_data.p + a, (size_t)bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(data_none, c->d_data_none.p + first, (size_t)K, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    for (int64_t i = 0; i <= K; ++i) data_off[i] = off[(size_t)i] - a;
+    return SW_OK;
+}
+
+int sw_gather_event_data_device(sw_ctx* c, int64_t K, const int32_t* d_event, int64_t cap, uint8_t* d_data, int64_t* d_data_off, uint8_t* d_data_none,
+                                void* user_stream, int64_t* n_bytes) {
+    if (!c) return SW_EINVAL;
+    const char* what = "sw_gather_event_data_device";
+    bool query = false;
+    CHK(data_gather_args(c, K, d_event, cap, d_data, d_data_off, d_data_none, n_bytes, &query, what));
+    if ((uintptr_t)d_data & 15) return fail(c, SW_EINVAL, "%s: the data buffer must be 16-byte aligned", what);
+    if (((uintptr_t)d_data_off & 7) || ((uintptr_t)d_event & 3)) return fail(c, SW_EINVAL, "%s: the offsets must be 8-byte aligned, the indices 4-byte aligned", what);
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t k = (size_t)K;
+    bool on = K == 0 || on_ctx_device(c, d_event, k * 4);
+    if (!query) on = on && on_ctx_device(c, d_data_off, (k + 1) * 8) && (K == 0 || on_ctx_device(c, d_data_none, k)) && (cap == 0 || on_ctx_device(c, d_data, (size_t)cap));
+    if (!on) return fail(c, SW_EINVAL, "%s: every array must lie in memory of device %d (a host pointer, or another device's)", what, c->device);
+    if (!c->ev_user) HIPCHK(c, hipEventCreateWithFlags(&c->ev_user, hipEventDisableTiming));
+    hipStream_t us = (hipStream_t)user_stream;
+    HIPCHK(c, hipEventRecord(c->ev_user, us));            // the producer of d_event; earlier readers of the outputs
+    HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_user, 0));
+    DataPlan p{};
+    dat::SegIn in{};
+    CHK(data_gather_plan(c, K, d_event, cap, n_bytes, &p, &in, what));
+    if (!query) CHK(data_gather_copy(c, K, p, in, *n_bytes, d_data, d_data_off, d_data_none));
+    HIPCHK(c, hipEventRecord(c->ev_user, c->stream));     // whatever the caller enqueues next reads complete arrays
+    HIPCHK(c, hipStreamWaitEvent(us, c->ev_user, 0));
+    return SW_OK;
+}
+
+int sw_gather_event_data(sw_ctx* c, int64_t K, const int32_t* event, int64_t cap, uint8_t* data, int64_t* data_off, uint8_t* data_none, int64_t* n_bytes) {
+    if (!c) return SW_EINVAL;
+    const char* what = "sw_gather_event_data";
+    bool query = false;
+    CHK(data_gather_args(c, K, event, cap, data, data_off, data_none, n_bytes, &query, what));
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t k = (size_t)K;
+    CHK(dgrow(c, c->d_dt_in, k * 4 + 256, 0));
+    if (K) HIPCHK(c, hipMemcpyAsync(c->d_dt_in.p, event, k * 4, hipMemcpyHostToDevice, c->stream));
+    DataPlan p{};
+    dat::SegIn in{};
+    CHK(data_gather_plan(c, K, (const int32_t*)c->d_dt_in.p, cap, n_bytes, &p, &in, what));
+    if (query) return SW_OK;
+    Carve cv;   // the outputs, sized from the total (not from the caller's capacity)
+    const size_t o_off = cv.take((k + 1) * 8), o_n = cv.take(k), o_d = cv.take((size_t)*n_bytes + 16);
+    CHK(dgrow(c, c->d_dt_out, cv.off + 256, 0));
+    unsigned char* B = c->d_dt_out.p;
+    CHK(data_gather_copy(c, K, p, in, *n_bytes, B + o_d, (int64_t*)(B + o_off), B + o_n));
+    HIPCHK(c, hipMemcpyAsync(data_off, B + o_off, (k + 1) * 8, hipMemcpyDeviceToHost, c->stream));
+    if (K) HIPCHK(c, hipMemcpyAsync(data_none, B + o_n, k, hipMemcpyDeviceToHost, c->stream));
+    if (*n_bytes) HIPCHK(c, hipMemcpyAsync(data, B + o_d, (size_t)*n_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return SW_OK;
+}
+
+int sw_ingest_payload_data_device(sw_ctx* c, int64_t K, const uint8_t* d_id32, const uint8_t* d_sp_id32, const uint8_t* d_op_id32, const uint8_t* d_arity,
+                                  const int32_t* d_creator, const uint8_t* d_ok, const double* d_t, const uint8_t* d_sig64, void* user_stream,
+                                  int32_t* d_index_out, int64_t* n_stored, const uint8_t* d_data, const int64_t* d_data_off, int64_t data_bytes,
+                                  const uint8_t* d_data_none) {
+    if (!c) return SW_EINVAL;
+    const char* what = "sw_ingest_payload_data_device";
+    CHK(payload_args(c, K, d_id32, d_sp_id32, d_op_id32, d_arity, d_creator, d_index_out, n_stored, what));
+    CHK(data_payload_args(c, d_data, d_data_off, data_bytes, d_data_none, what));
+    if (K == 0) return SW_OK;
+    if (((uintptr_t)d_id32 | (uintptr_t)d_sp_id32 | (uintptr_t)d_op_id32 | (uintptr_t)d_data_off) & 7)
+        return fail(c, SW_EINVAL, "%s: the id arrays and the data offsets must be 8-byte aligned", what);
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t k = (size_t)K;
+    if (!on_ctx_device(c, d_id32, k * 32) || !on_ctx_device(c, d_sp_id32, k * 32) || !on_ctx_device(c, d_op_id32, k * 32) ||
+        !on_ctx_device(c, d_arity, k) || !on_ctx_device(c, d_creator, k * 4) || !on_ctx_device(c, d_index_out, k * 4) ||
+        (d_ok && !on_ctx_device(c, d_ok, k)) || (d_t && !on_ctx_device(c, d_t, k * 8)) || (d_sig64 && !on_ctx_device(c, d_sig64, k * 64)) ||
+        (d_data_off && !on_ctx_device(c, d_data_off, (k + 1) * 8)) || (d_data && data_bytes > 0 && !on_ctx_device(c, d_data, (size_t)data_bytes)) ||
+        (d_data_none && !on_ctx_device(c, d_data_none, k)))
+        return fail(c, SW_EINVAL, "%s: every array must lie in memory of device %d (a host pointer, or another device's)", what, c->device);
+    return ingest_data_core(c, K, d_id32, d_sp_id32, d_op_id32, d_arity, d_creator, d_ok, d_t, d_sig64, d_data, d_data_off, data_bytes, d_data_none,
+                            (hipStream_t)user_stream, d_index_out, n_stored);
+}
+
+int sw_ingest_payload_data(sw_ctx* c, int64_t K, const uint8_t* id32, const uint8_t* sp_id32, const uint8_t* op_id32, const uint8_t* arity,
+                           const int32_t* creator, const uint8_t* ok, const double* t, const uint8_t* sig64, int32_t* index_out, int64_t* n_stored,
+                           const uint8_t* data, const int64_t* data_off, int64_t data_bytes, const uint8_t* data_none) {
+    if (!c) return SW_EINVAL;
+    const char* what = "sw_ingest_payload_data";
+    CHK(payload_args(c, K, id32, sp_id32, op_id32, arity, creator, index_out, n_stored, what));
+    CHK(data_payload_args(c, data, data_off, data_bytes, data_none, what));
+    if (K == 0) return SW_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t k = (size_t)K, db = (size_t)data_bytes;
+    Carve cv;
+    const size_t o_id = cv.take(k * 32), o_sp = cv.take(k * 32), o_op = cv.take(k * 32), o_ar = cv.take(k), o_cr = cv.take(k * 4);
+    const size_t o_ok = cv.take(ok ? k : 0), o_t = cv.take(t ? k * 8 : 0), o_sig = cv.take(sig64 ? k * 64 : 0), o_out = cv.take(k * 4);
+    const size_t o_doff = cv.take(data_off ? (k + 1) * 8 : 0), o_d = cv.take(db), o_dn = cv.take(data_none ? k : 0);
+    CHK(dgrow(c, c->d_dt_in, cv.off + 256, 0));
+    unsigned char* B = c->d_dt_in.p;
+    const struct { size_t o; const void* src; size_t bytes; } up[] = {
+        {o_id, id32, k * 32}, {o_sp, sp_id32, k * 32}, {o_op, op_id32, k * 32}, {o_ar, arity, k}, {o_cr, creator, k * 4}, {o_ok, ok, ok ? k : 0},
+        {o_t, t, t ? k * 8 : 0}, {o_sig, sig64, sig64 ? k * 64 : 0}, {o_doff, data_off, data_off ? (k + 1) * 8 : 0}, {o_d, data, db},
+        {o_dn, data_none, data_none ? k : 0}};
+    for (const auto& u : up)
+        if (u.bytes) HIPCHK(c, hipMemcpyAsync(B + u.o, u.src, u.bytes, hipMemcpyHostToDevice, c->stream));
+    const int rc = ingest_data_core(c, K, B + o_id, B + o_sp, B + o_op, B + o_ar, (const int32_t*)(B + o_cr), ok ? B + o_ok : nullptr,
+                                    t ? (const double*)(B + o_t) : nullptr, sig64 ? B + o_sig : nullptr, data_off ? B + o_d : nullptr,
+                                    data_off ? (const int64_t*)(B + o_doff) : nullptr, data_bytes, data_none ? B + o_dn : nullptr, c->stream,
+                                    (int32_t*)(B + o_out), n_stored);
+    if (rc != SW_OK) return rc;
+    HIPCHK(c, hipMemcpyAsync(index_out, B + o_out, k * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return SW_OK;
+}
+
+int sw_sync_pull_data(sw_ctx* dst, int64_t dst_head, sw_ctx* src, int64_t src_head, int validate, int64_t* n_sent, int64_t* n_valid, int64_t* n_stored) {
+    if (!dst || !src) return SW_EINVAL;
+    const char* what = "sw_sync_pull_data";
+    if (n_sent) *n_sent = 0;
+    if (n_valid) *n_valid = 0;
+    if (n_stored) *n_stored = 0;
+    if (dst == src) return fail(dst, SW_EINVAL, "%s: a context cannot pull from itself", what);
+    if (dst->device != src->device) return fail(dst, SW_ENOTSUP, "%s: the contexts live on devices %d and %d (same device only)", what, dst->device, src->device);
+    if (dst->n != src->n) return fail(dst, SW_EINVAL, "%s: %d members here, %d at the peer", what, dst->n, src->n);
+    if (dst->poisoned) return fail(dst, SW_EIO, "context unusable after an earlier device failure");
+    if (validate && dst->vkeys.empty()) return fail(dst, SW_ENOTSUP, "%s: no member keys (sw_set_member_keys first)", what);
+    if (dst->n_ids != dst->N)
+        return fail(dst, SW_ENOTSUP, "%s: %lld of the %lld stored events have no id (sw_set_event_ids first)", what, (long long)(dst->N - dst->n_ids), (long long)dst->N);
+    if (dst->n_data != dst->N)
+        return fail(dst, SW_ENOTSUP, "%s: %lld of the %lld stored events have no data entry (sw_set_event_data first)", what, (long long)(dst->N - dst->n_data), (long long)dst->N);
+    if (dst_head < dst->first_resident || dst_head >= dst->divided) return fail(dst, SW_ERANGE, "%s: head %lld is not a divided, resident event", what, (long long)dst_head);
+    if (const int rc = export_pre(src, src_head, "sw_sync_pull_data (peer)"); rc != SW_OK) { dst->err = src->err; return rc; }
+    if (src->n_data != src->N)
+        return fail(dst, SW_ENOTSUP, "%s: %lld of the peer's %lld stored events have no data entry (sw_set_event_data first)", what, (long long)(src->N - src->n_data), (long long)src->N);
+    HIPCHK(dst, hipSetDevice(dst->device));
+    if (validate && !dst->h_pkcnt && hipHostMalloc((void**)&dst->h_pkcnt, sizeof(int32_t), hipHostMallocDefault) != hipSuccess) {
+        (void)hipGetLastError();
+        dst->h_pkcnt = nullptr;
+        return fail(dst, SW_ENOMEM, "hipHostMalloc for the count of valid events failed");
+    }
+    // ---- 1. and 2. as in sw_sync_pull: dst's known heights, src's ranges, count and gather (with the dense indices)
+    CHK(heights_on_device(dst));
+    const int np = dst->npad;
+    CHK(dgrow(dst, dst->d_q, (size_t)3 * np, 0));
+    if (!dst->ev_user) HIPCHK(dst, hipEventCreateWithFlags(&dst->ev_user, hipEventDisableTiming));
+    hipLaunchKernelGGL(k_known_heights, dim3(1), dim3(np), 0, dst->stream, (const int*)dst->d_L.p, (const int*)dst->d_ht.p, (int)dst_head, np, dst->d_q.p);
+    dst->ctr.kernel_launches++;
+    HIPCHK(dst, hipGetLastError());
+    HIPCHK(dst, hipEventRecord(dst->ev_user, dst->stream));
+    HIPCHK(dst, hipStreamWaitEvent(src->stream, dst->ev_user, 0));
+    const bool prof = src->profiling;
+    auto t0 = std::chrono::steady_clock::now();
+    int64_t total = 0;
+    if (const int rc = export_ranges(src, src_head, dst->d_q.p, hipMemcpyDeviceToDevice, &total); rc != SW_OK) { dst->err = src->err; return rc; }
+    src->xp_ms[0] = prof ? ms_since(t0) : 0;
+    src->xp_ms[1] = 0;
+    if (total > 0x3fffffffll || dst->N + total > 0x7ffffff0ll) return fail(dst, SW_ERANGE, "%s: more than 2^31 events", what);
+    t0 = std::chrono::steady_clock::now();
+    ExportArrays d{};
+    int rc = export_scratch(src, total, true, true, true, &d);
+    if (rc == SW_OK) rc = export_gather(src, total, d);
+    if (rc != SW_OK) { dst->err = src->err; return rc; }
+    if (prof) { HIPCHK(src, hipStreamSynchronize(src->stream)); src->xp_ms[1] = ms_since(t0); }
+    src->xp_calls++;
+    src->xp_events += total;
+    if (n_sent) *n_sent = total;
+    // ---- 3. src: the data of those events beside the other arrays (its second synchronisation: the byte total)
+    const size_t k = (size_t)total;
+    DataPlan sp{};
+    int64_t dbytes = 0, bad = 0;
+    const dat::SegIn sin{src->d_data.p, (const dat::i64*)src->d_data_off.p, src->d_data_none.p, d.event, (dat::i64)src->n_data, (dat::i64)src->data_used, 1};
+    rc = data_scratch(src, total, 0, 0, &sp);
+    if (rc == SW_OK) rc = data_plan(src, total, sin, sp, &dbytes, &bad);
+    if (rc == SW_OK && bad) rc = fail(src, SW_EIO, "%s: %lld exported events without data (internal error)", what, (long long)bad);
+    Carve sv;
+    const size_t s_d = sv.take((size_t)dbytes + 16), s_off = sv.take((k + 1) * 8), s_n = sv.take(k);
+    if (rc == SW_OK) rc = dgrow(src, src->d_dt_out, sv.off + 256, 0);
+    unsigned char* S = src->d_dt_out.p;
+    if (rc == SW_OK) rc = data_copy(src, total, sin, sp, dbytes, S + s_d, 0, 0, (int64_t*)(S + s_off), S + s_n);
+    if (rc != SW_OK) { dst->err = src->err; return rc; }
+    src->dt_gather_calls++;
+    src->dt_gather_bytes += dbytes;
+    const uint8_t* x_data = S + s_d;
+    const int64_t* x_off = (const int64_t*)(S + s_off);
+    const uint8_t* x_none = S + s_n;
+    CHK(dgrow(dst, dst->d_pl_in, k * sizeof(int32_t), 0));
+    int64_t stored = 0;
+    if (!validate) {
+        rc = ingest_data_core(dst, total, d.id, d.sp_id, d.op_id, d.arity, d.creator, nullptr, d.t, d.sig, x_data, x_off, dbytes, x_none, src->stream,
+                              (int32_t*)dst->d_pl_in.p, &stored);
+        const hipError_t drained = hipStreamSynchronize(dst->stream);   // src's scratch is free again only once dst has read it
+        if (rc != SW_OK) return rc;
+        HIPCHK(dst, drained);
+        if (n_stored) *n_stored = stored;
+        return SW_OK;
+    }
+    // ---- 4. dst, its stream ordered behind src's: the signed bytes WITH the data, the verdicts by dst's own keys and
+    // event class, ANDed with the encodable flags and counted
+    int64_t bm = 0, bw = 0;
+    pack_bound(dst, total, dbytes, &bm, &bw);
+    Carve cv;
+    const size_t o_moff = cv.take((k + 1) * 8), o_woff = cv.take((k + 1) * 8), o_m = cv.take((size_t)bm), o_w = cv.take((size_t)bw);
+    const size_t o_enc = cv.take(k), o_ok = cv.take(k), o_cnt = cv.take(sizeof(int32_t));
+    CHK(dgrow(dst, dst->d_pk_out, cv.off + 256, 0));
+    unsigned char* B = dst->d_pk_out.p;
+    HIPCHK(dst, hipEventRecord(dst->ev_user, src->stream));
+    HIPCHK(dst, hipStreamWaitEvent(dst->stream, dst->ev_user, 0));
+    HIPCHK(dst, hipMemsetAsync(B + o_cnt, 0, sizeof(int32_t), dst->stream));
+    rc = pack_launch(dst, total, PackArrays{d.sp_id, d.op_id, d.arity, d.creator, d.t, d.sig, x_data, x_off, dbytes, x_none, B + o_m, (int64_t*)(B + o_moff),
+                                            B + o_w, (int64_t*)(B + o_woff), B + o_enc}, bm, bw);
+    if (rc == SW_OK) {
+        const swv::Payload p{B + o_m, (const long long*)(B + o_moff), (long long)bm, B + o_w, (const long long*)(B + o_woff), (long long)bw, d.sig, d.creator, d.id};
+        rc = validate_launch(dst, total, p, B + o_ok);
+    }
+    if (rc != SW_OK) { (void)hipStreamSynchronize(dst->stream); return rc; }
+    dst->v_calls++;
+    dst->v_events += total;
+    hipLaunchKernelGGL(pck::k_pack_and_count, dim3((unsigned)std::min<int64_t>(1024, (total + 255) / 256)), dim3(256), 0, dst->stream, (pck::i64)total,
+                       B + o_ok, (const unsigned char*)(B + o_enc), (int*)(B + o_cnt));
+    dst->ctr.kernel_launches++;
+    HIPCHK(dst, hipGetLastError());
+    HIPCHK(dst, hipMemcpyAsync(dst->h_pkcnt, B + o_cnt, sizeof(int32_t), hipMemcpyDeviceToHost, dst->stream));
+    // ---- 5. dst ingests what is valid, with its data
+    rc = ingest_data_core(dst, total, d.id, d.sp_id, d.op_id, d.arity, d.creator, B + o_ok, d.t, d.sig, x_data, x_off, dbytes, x_none, src->stream,
+                          (int32_t*)dst->d_pl_in.p, &stored);
+    const hipError_t drained = hipStreamSynchronize(dst->stream);
+    if (rc != SW_OK) return rc;
+    HIPCHK(dst, drained);
+    if (n_valid) *n_valid = *dst->h_pkcnt;
+    if (n_stored) *n_stored = stored;
+    return SW_OK;
+}
+
+int sw_get_data_stats(sw_ctx* c, int64_t* events, int64_t* bytes, int64_t* store_calls, int64_t* gather_calls, int64_t* gather_bytes, double* phase_ms) {
+    if (!c) return SW_EINVAL;
+    if (events) *events = c->n_data;
+    if (bytes) *bytes = c->data_used;
+    if (store_calls) *store_calls = c->dt_store_calls;
+    if (gather_calls) *gather_calls = c->dt_gather_calls;
+    if (gather_bytes) *gather_bytes = c->dt_gather_bytes;
+    if (phase_ms) for (int i = 0; i < 2; ++i) phase_ms[i] = c->dt_ms[i];
     return SW_OK;
 }
 

@@ -143,10 +143,12 @@ class Hashgraph:
         self._chk(self._L.sw_lookup_event_ids(self._h, ids.shape[0], _p(ids), _p(out)))
         return out
 
-    def ingest_payload(self, ids, sp_ids, op_ids, arity, creator, ok=None, t=None, sig=None):
+    def ingest_payload(self, ids, sp_ids, op_ids, arity, creator, ok=None, t=None, sig=None, *, data=None, data_off=None, data_none=None):
         """A sync payload addressed by id, host arrays in any order (sw_ingest_payload): known ids are recognised, invalid
         events dropped, the rest ordered topologically and appended.  Returns (index_out, n_stored): per event its dense
-        index or a reject code -2 .. -8 (include/swirld_hip.h)."""
+        index or a reject code -2 .. -8 (include/swirld_hip.h).
+        data / data_off / data_none (as pack_events takes them; `data` may also be a list of bytes | None): the events bring
+        their data (sw_ingest_payload_data) — the data store must be complete, an event with an unusable range is -3."""
         ids = self._ids(ids)
         K = ids.shape[0]
         sp_ids, op_ids = self._ids(sp_ids, K), self._ids(op_ids, K)
@@ -159,14 +161,21 @@ class Hashgraph:
         sig = None if sig is None else np.ascontiguousarray(sig, np.uint8).reshape(K, 64)
         out = np.empty(K, np.int32)
         n_stored = C.c_int64()
+        if data is not None or data_off is not None or data_none is not None:
+            data, data_off, data_none, nbytes = self._data_arrays(K, data, data_off, data_none)
+            self._chk(self._L.sw_ingest_payload_data(self._h, K, _p(ids), _p(sp_ids), _p(op_ids), _p(arity), _p(creator), _p(ok), _p(t), _p(sig),
+                                                     _p(out), C.byref(n_stored), _p(data), _p(data_off), nbytes, _p(data_none)))
+            return out, int(n_stored.value)
         self._chk(self._L.sw_ingest_payload(self._h, K, _p(ids), _p(sp_ids), _p(op_ids), _p(arity), _p(creator), _p(ok), _p(t), _p(sig),
                                             _p(out), C.byref(n_stored)))
         return out, int(n_stored.value)
 
-    def ingest_payload_device(self, ids, sp_ids, op_ids, arity, creator, ok=None, t=None, sig=None, index_out=None, stream=0, count=None):
+    def ingest_payload_device(self, ids, sp_ids, op_ids, arity, creator, ok=None, t=None, sig=None, index_out=None, stream=0, count=None,
+                              *, data=None, data_off=None, data_bytes=0, data_none=None):
         """ingest_payload for arrays in DEVICE memory (addresses, or objects with data_ptr() / __cuda_array_interface__;
         the id arrays 8-byte aligned).  `index_out` (required): K int32 in device memory, where the answer is left.
-        Returns (index_out as given, n_stored)."""
+        Returns (index_out as given, n_stored).  data_off (K + 1 int64 in device memory) with data / data_bytes / data_none:
+        the events bring their data (sw_ingest_payload_data_device)."""
         if index_out is None:
             raise ValueError("index_out (K int32 in device memory) is required")
         ptrs = [_dev_ptr(a) for a in (ids, sp_ids, op_ids, arity, creator, ok, t, sig, index_out)]
@@ -176,6 +185,11 @@ class Hashgraph:
         K = int(K)
         args = [C.c_void_p(q) if q else None for q, _ in ptrs]
         n_stored = C.c_int64()
+        if data is not None or data_off is not None or data_none is not None:
+            dp = [C.c_void_p(q) if q else None for q in (_dev_ptr(a)[0] for a in (data, data_off, data_none))]
+            self._chk(self._L.sw_ingest_payload_data_device(self._h, K, *args[:8], C.c_void_p(int(stream)), args[8], C.byref(n_stored),
+                                                            dp[0], dp[1], int(data_bytes), dp[2]))
+            return index_out, int(n_stored.value)
         self._chk(self._L.sw_ingest_payload_device(self._h, K, *args[:8], C.c_void_p(int(stream)), args[8], C.byref(n_stored)))
         return index_out, int(n_stored.value)
 
@@ -187,6 +201,108 @@ class Hashgraph:
         self._chk(self._L.sw_get_payload_stats(self._h, *[C.byref(x) for x in v], ms))
         d = dict(zip(("calls", "waves", "accepted", "table_rebuilds"), (int(x.value) for x in v)))
         d.update(zip(("resolve_ms", "waves_ms", "sort_ms", "append_ms"), (float(x) for x in ms)))
+        return d
+
+    # ---- the data of events, Event.d (swirld.py:30, :82-95; csrc/data.hip.h) ----
+    @staticmethod
+    def pack_data(datas):
+        """A list of bytes | None as (data uint8, data_off int64 [K + 1], data_none uint8 [K])."""
+        none = np.fromiter((d is None for d in datas), np.uint8, len(datas))
+        lens = np.fromiter((0 if d is None else len(d) for d in datas), np.int64, len(datas))
+        off = np.zeros(len(datas) + 1, np.int64)
+        np.cumsum(lens, out=off[1:])
+        data = np.frombuffer(b"".join(d for d in datas if d is not None), np.uint8)
+        return data, off, none
+
+    @staticmethod
+    def unpack_data(data, data_off, data_none):
+        """The inverse: a list of bytes | None."""
+        raw = np.ascontiguousarray(data, np.uint8).tobytes()
+        return [None if data_none[i] else raw[int(data_off[i]):int(data_off[i + 1])] for i in range(len(data_none))]
+
+    def _data_arrays(self, K, data, data_off, data_none):
+        if data_off is None and data is not None and not isinstance(data, np.ndarray):
+            if data_none is not None:
+                raise ValueError("a list of bytes | None carries its own None flags")
+            data, data_off, data_none = self.pack_data(list(data))
+        if data_off is None:
+            if data is not None:
+                raise ValueError("data needs data_off")
+            data_off = np.zeros(K + 1, np.int64)       # (only None flags: every range empty)
+        data_off = np.ascontiguousarray(data_off, np.int64)
+        if data_off.shape != (K + 1,):
+            raise ValueError("data_off must have K + 1 entries (got %d for %d events)" % (data_off.shape[0], K))
+        data = np.zeros(0, np.uint8) if data is None else np.ascontiguousarray(data, np.uint8).reshape(-1)
+        nbytes = data.shape[0]
+        if data_none is not None:
+            data_none = np.ascontiguousarray(data_none, np.uint8)
+            if data_none.shape != (K,):
+                raise ValueError("data_none must have one entry per event")
+        return (data if nbytes else None), data_off, data_none, nbytes
+
+    def set_event_data(self, first, datas):
+        """The data of the stored events [first, first + K) (sw_set_event_data): `datas` is a list of bytes | None, or a
+        (data, data_off, data_none) triple as pack_events takes it.  `first` must be the number of events that have data."""
+        if isinstance(datas, tuple) and len(datas) == 3 and isinstance(datas[1], np.ndarray):
+            K = len(datas[1]) - 1
+            data, off, none, nbytes = self._data_arrays(K, *datas)
+        else:
+            datas = list(datas)
+            K = len(datas)
+            data, off, none, nbytes = self._data_arrays(K, datas, None, None)
+        self._chk(self._L.sw_set_event_data(self._h, int(first), K, _p(data), _p(off), nbytes, _p(none)))
+
+    def set_event_data_device(self, first, K, data=None, data_off=None, data_bytes=0, data_none=None, stream=0):
+        """set_event_data from DEVICE memory (sw_set_event_data_device); all of data, data_off, data_none None: every None."""
+        dp = [C.c_void_p(q) if q else None for q in (_dev_ptr(a)[0] for a in (data, data_off, data_none))]
+        self._chk(self._L.sw_set_event_data_device(self._h, int(first), int(K), dp[0], dp[1], int(data_bytes), dp[2], C.c_void_p(int(stream))))
+
+    def get_event_data(self, first=0, K=None):
+        """(data, data_off, data_none) of the events [first, first + K), offsets from 0 (K None: up to the last event that
+        has data)."""
+        if K is None:
+            K = self.data_stats()["events"] - first
+        k = max(int(K), 0)
+        off, none, nb = np.zeros(k + 1, np.int64), np.zeros(k, np.uint8), C.c_int64()
+        data = np.empty(0, np.uint8)
+        rc = self._L.sw_get_event_data(self._h, int(first), int(K), 0, None, _p(off), _p(none), C.byref(nb))
+        if rc == -34 and nb.value > 0:      # (the size: now with room)
+            data = np.empty(int(nb.value), np.uint8)
+            rc = self._L.sw_get_event_data(self._h, int(first), int(K), data.shape[0], _p(data), _p(off), _p(none), C.byref(nb))
+        self._chk(rc)
+        return data, off, none
+
+    def gather_event_data(self, events):
+        """(data, data_off, data_none) of the events named by dense index, in the order given, repeats allowed
+        (sw_gather_event_data) — e.g. export_ordered()["event"] or export_payload()["event"]."""
+        ev = np.ascontiguousarray(events, np.int32).reshape(-1)
+        K, nb = ev.shape[0], C.c_int64()
+        rc = self._L.sw_gather_event_data(self._h, K, _p(ev), 0, None, None, None, C.byref(nb))
+        if not (rc == -34 and nb.value > 0):
+            self._chk(rc)
+        data, off, none = np.empty(int(nb.value), np.uint8), np.zeros(K + 1, np.int64), np.zeros(K, np.uint8)
+        self._chk(self._L.sw_gather_event_data(self._h, K, _p(ev), data.shape[0], _p(data), _p(off), _p(none), C.byref(nb)))
+        return data, off, none
+
+    def gather_event_data_device(self, K, events, cap=0, data=None, data_off=None, data_none=None, stream=0):
+        """gather_event_data between DEVICE arrays (sw_gather_event_data_device): `events` K int32, data `cap` bytes and
+        16-byte aligned, data_off K + 1 int64, data_none K uint8.  Returns the byte total; with cap = 0 and no arrays it
+        only asks for it.  A total beyond `cap` raises SwirldHipError -34 and writes nothing."""
+        ptrs = [C.c_void_p(q) if q else None for q in (_dev_ptr(a)[0] for a in (events, data, data_off, data_none))]
+        nb = C.c_int64()
+        rc = self._L.sw_gather_event_data_device(self._h, int(K), ptrs[0], int(cap), ptrs[1], ptrs[2], ptrs[3], C.c_void_p(int(stream)), C.byref(nb))
+        if not (rc == -34 and cap == 0 and data is None and data_off is None and data_none is None and nb.value > 0):
+            self._chk(rc)
+        return int(nb.value)
+
+    def data_stats(self):
+        """Events that have data, arena bytes in use, store calls, gather calls, bytes gathered, and (under set_profiling)
+        the host milliseconds of the last call's lengths + scan and of its copy."""
+        v = [C.c_int64() for _ in range(5)]
+        ms = (C.c_double * 2)()
+        self._chk(self._L.sw_get_data_stats(self._h, *[C.byref(x) for x in v], ms))
+        d = dict(zip(("events", "bytes", "store_calls", "gather_calls", "gather_bytes"), (int(x.value) for x in v)))
+        d.update(zip(("scan_ms", "copy_ms"), (float(x) for x in ms)))
         return d
 
     # ---- validation against the member keys (the crypto of Node.is_valid_event, swirld.py:97-103) ----
@@ -483,9 +599,10 @@ class Hashgraph:
             self._chk(rc)
         return int(n_out.value)
 
-    def export_payload(self, head, known=None):
+    def export_payload(self, head, known=None, *, data=False):
         """The same into fresh numpy arrays: a dict with ids, sp_ids, op_ids (K x 32 uint8), arity (uint8), creator (int32),
-        t (float64), sig (K x 64 uint8) and event (int32, the dense indices here).  `known`: n heights (host), None = nobody."""
+        t (float64), sig (K x 64 uint8) and event (int32, the dense indices here).  `known`: n heights (host), None = nobody.
+        data=True adds data, data_off, data_none: the events' data, through gather_event_data."""
         kn = None if known is None else np.ascontiguousarray(known, np.int32)
         if kn is not None and kn.shape != (self.n,):
             raise ValueError("known must have one height per member")
@@ -499,16 +616,24 @@ class Hashgraph:
                  sig=np.empty((K, 64), np.uint8), event=np.empty(K, np.int32))
         self._chk(self._L.sw_export_payload(self._h, int(head), _p(kn), K, *[_p(d[k]) for k in ("ids", "sp_ids", "op_ids", "arity", "creator", "t", "sig", "event")],
                                             C.byref(n_out)))
+        if data:
+            d["data"], d["data_off"], d["data_none"] = self.gather_event_data(d["event"])
         return d
 
-    def pull_from(self, peer, peer_head, my_head, validate=False):
+    def pull_from(self, peer, peer_head, my_head, validate=False, *, data=False):
         """Node.sync without the new event (swirld.py:125-136) against `peer`, a Hashgraph on the same device: my known
         heights at `my_head` -> the peer's diff at `peer_head` -> my ingest, all in device memory.  Returns (n_sent,
         n_stored); my new events are the last n_stored ones, their ids event_ids(num_events - n_stored).
         validate=True puts is_valid_event's crypto in the middle (sw_sync_pull_validated): the signed bytes of the peer's
         events are built on the device, judged by MY member keys and event class, and only valid events are ingested;
-        returns (n_sent, n_valid, n_stored).  Needs set_member_keys; the bytes are built with data None."""
+        returns (n_sent, n_valid, n_stored).  Needs set_member_keys; the bytes are built with data None.
+        data=True (sw_sync_pull_data): the events travel WITH their data, from the peer's data store into mine, and with
+        validate=True the signed bytes are built with it; both data stores must be complete."""
         a, b = C.c_int64(), C.c_int64()
+        if data:
+            v = C.c_int64()
+            self._chk(self._L.sw_sync_pull_data(self._h, int(my_head), peer._h, int(peer_head), 1 if validate else 0, C.byref(a), C.byref(v), C.byref(b)))
+            return (int(a.value), int(v.value), int(b.value)) if validate else (int(a.value), int(b.value))
         if validate:
             v = C.c_int64()
             self._chk(self._L.sw_sync_pull_validated(self._h, int(my_head), peer._h, int(peer_head), C.byref(a), C.byref(v), C.byref(b)))
@@ -634,10 +759,10 @@ class Hashgraph:
         self._chk(self._L.sw_get_consensus_time(self._h, int(first), int(K), _p(out)))
         return out
 
-    def export_ordered(self, first=0, K=None, ids=None):
+    def export_ordered(self, first=0, K=None, ids=None, *, data=False):
         """Positions [first, first + K) of the order as numpy arrays: a dict with event (int32, the dense indices: a slice of
         transactions()), creator (int32), round_received (int32), time (float64) and — `ids` True, or None [default] and the id index
-        complete — ids (K x 32 uint8)."""
+        complete — ids (K x 32 uint8).  data=True adds data, data_off, data_none: the events' data, through gather_event_data."""
         K = self.num_ordered - first if K is None else K
         k = max(int(K), 0)
         d = dict(event=np.empty(k, np.int32), creator=np.empty(k, np.int32), round_received=np.empty(k, np.int32), time=np.empty(k, np.float64))
@@ -649,6 +774,8 @@ class Hashgraph:
         self._chk(rc)
         if with_ids:
             d["ids"] = i32
+        if data:
+            d["data"], d["data_off"], d["data_none"] = self.gather_event_data(d["event"])
         return d
 
     def export_ordered_device(self, first, K, event=None, ids=None, creator=None, round_received=None, time=None, stream=0):

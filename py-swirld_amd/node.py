@@ -30,6 +30,8 @@ from ._lib import SwirldHipError
 from .engine import Hashgraph
 from .hgutils import bfs, randrange, toposort
 
+_pack_data, _unpack_data = Hashgraph.pack_data, Hashgraph.unpack_data   # (list of bytes | None <-> data, offsets, None flags)
+
 C = 6  # coin-round period, swirld.py:17
 
 
@@ -266,6 +268,14 @@ class Node:
     # least this many events; it then takes the place of the two stateless batches above.  The node hands its members' keys
     # to the context on first use.  None = never.
     device_validate_threshold = None
+    # Event.d kept on the device beside the other fields (the data store of the context, csrc/data.hip.h).  False: every
+    # route is as without it.  True: before every divide_rounds the context's store is caught up with the data of the
+    # events it has not seen yet — the one place that covers every route by which events reach the device —, payloads
+    # whose events carry bytes of at most 60 000 bytes take _batch_validate's array route too, and ordered_data() reads
+    # the consensus stream's payloads back from the device.  An event whose d is neither None nor such bytes makes its
+    # payload fall back to the host routes, and the store holds None for it: hg[h].d stays the truth for such events.
+    device_data = False
+    MAX_DEVICE_DATA = 60000
 
     def __init__(self, kp, network, n_nodes, stake, device=0, accept_forks=True):
         self.pk, self.sk = kp
@@ -304,6 +314,7 @@ class Node:
         self._pending = []    # (creator, self_parent, other_parent, t, sig) not yet uploaded
         self._uploaded = 0
         self._dev_ids = 0     # events whose id the device context knows (device_payload_threshold)
+        self._dev_data = 0    # events whose data the device context holds (device_data)
         self._device_payloads = 0
         self._keys_on_device = False   # the context has the members' keys and the Event class (device_validate_threshold)
         self._plain_payloads = 0       # payloads whose signed bytes the device built (_batch_validate_plain)
@@ -402,6 +413,8 @@ class Node:
             self._keys_on_device = True
         if all(self._is_plain(eid, events[eid]) for eid in eids):
             return self._batch_validate_plain(eids, events)
+        if self.device_data and all(self._is_plain_or_data(eid, events[eid]) for eid in eids):
+            return self._batch_validate_plain(eids, events, with_data=True)
         is_b = lambda x, n: isinstance(x, (bytes, bytearray)) and len(x) == n
         msgs, whole, sigs, ids, good = [], [], [], [], []
         creator = np.full(len(eids), -1, np.int32)
@@ -434,6 +447,25 @@ class Node:
         return (len(ev.p) == 2 and is_b(ev.p[0], 32) and is_b(ev.p[1], 32)
                 and ev.p[0] is not ev.p[1] and ev.p[0] is not ev.c and ev.p[1] is not ev.c)
 
+    @classmethod
+    def _is_plain_or_data(cls, eid, ev):
+        """_is_plain, or the same shape with data of exactly type bytes and at most MAX_DEVICE_DATA bytes that is not the
+        same object as another field (pickle would write a memo read): what pack_events writes with its data arguments."""
+        if type(ev) is not Event:
+            return False
+        if ev.d is None:
+            return cls._is_plain(eid, ev)
+        if type(ev.d) is not bytes or len(ev.d) > cls.MAX_DEVICE_DATA or type(ev.p) is not tuple:
+            return False
+        if any(ev.d is x for x in (ev.c, ev.s) + ev.p):
+            return False
+        return cls._is_plain(eid, ev._replace(d=None))
+
+    @classmethod
+    def _storable_data(cls, d):
+        """What the device store holds for an event with data d: d itself, or None where it cannot hold it."""
+        return d if d is None or (type(d) is bytes and len(d) <= cls.MAX_DEVICE_DATA) else None
+
     @staticmethod
     def _payload_arrays(eids, events, mindex):
         """The arrays Hashgraph.pack_events / validate_payload take, for a payload of plain events: parents' ids, arity,
@@ -450,11 +482,16 @@ class Node:
         ids = np.frombuffer(b"".join(eids), np.uint8).reshape(K, 32)
         return sp, op, arity, creator, t, sig, ids
 
-    def _batch_validate_plain(self, eids, events):
-        """_batch_validate for plain events (_is_plain): no dumps per event — the arrays go to the device, which builds the
-        signed bytes itself (Hashgraph.pack_events) and judges them (Hashgraph.validate_payload)."""
+    def _batch_validate_plain(self, eids, events, with_data=False):
+        """_batch_validate for plain events (_is_plain; with_data: _is_plain_or_data): no dumps per event — the arrays go to
+        the device, which builds the signed bytes itself (Hashgraph.pack_events) and judges them
+        (Hashgraph.validate_payload)."""
         sp, op, arity, creator, t, sig, ids = self._payload_arrays(eids, events, self._mindex)
-        msgs, moff, whole, woff, enc = self._dev.pack_events(sp, op, arity, creator, t, sig)
+        if with_data:
+            data, data_off, data_none = _pack_data([events[eid].d for eid in eids])
+            msgs, moff, whole, woff, enc = self._dev.pack_events(sp, op, arity, creator, t, sig, data=data, data_off=data_off, data_none=data_none)
+        else:
+            msgs, moff, whole, woff, enc = self._dev.pack_events(sp, op, arity, creator, t, sig)
         ok = self._dev.validate_payload((msgs, moff), sig, creator, whole=(whole, woff), ids=ids)
         self._plain_payloads += 1
         return {eid: ((True, eid) if ok[i] and enc[i] else (False, None)) for i, eid in enumerate(eids)}
@@ -654,6 +691,23 @@ class Node:
             self._uploaded += len(self._pending)
             self._pending = []
 
+    def _catch_up_data(self):
+        """device_data: the context's data store learns the data of every event it has not seen yet, in one call."""
+        first = self._dev_data
+        if self.device_data and first < len(self._ids):
+            self._dev.set_event_data(first, [self._storable_data(self.hg[h].d) for h in self._ids[first:]])
+            self._dev_data = len(self._ids)
+
+    def ordered_data(self, first=0, K=None):
+        """[(event id, data)] of positions [first, first + K) of the consensus order (K None: to its end), the data read
+        from the device in one export_ordered(..., data=True).  Needs device_data; an event whose d the store cannot hold
+        (neither None nor bytes of at most MAX_DEVICE_DATA bytes) comes back as None."""
+        if not self.device_data:
+            raise RuntimeError("ordered_data needs Node.device_data = True")
+        o = self._dev.export_ordered(first, K, data=True)
+        datas = _unpack_data(o["data"], o["data_off"], o["data_none"])
+        return [(self._ids[int(e)], d) for e, d in zip(o["event"], datas)]
+
     def divide_rounds(self, events):
         """Assign rounds / witnesses / can_see rows to the new events (swirld.py:187-222).
         `events` must be the not-yet-divided events in the order they were added (which is
@@ -669,6 +723,7 @@ class Node:
                     raise KeyError(h)
             raise ValueError("divide_rounds expects the undivided events in the order they were added")
         self._flush()
+        self._catch_up_data()
         self._dev.divide_rounds(first, len(events))
         self._divided = first + len(events)
         self._wit_cache = None
