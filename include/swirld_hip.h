@@ -626,6 +626,70 @@ int sw_sync_pull_data(sw_ctx* dst, int64_t dst_head, sw_ctx* src, int64_t src_he
 int sw_get_data_stats(sw_ctx* ctx, int64_t* events, int64_t* bytes, int64_t* store_calls, int64_t* gather_calls,
                       int64_t* gather_bytes, double* phase_ms);
 
+/*
+ * CREATING signed events on the device (kernels in csrc/sign.hip.h): the producing half of Node.new_event
+ * (swirld.py:82-95) for K events at once — the Ed25519 signature over dumps((d, p, t, pk)) and the id
+ * crypto_generichash(dumps(ev)), bit for bit what libsodium, pickle and hashlib give, from the same index arrays
+ * sw_append_events takes.  An event's signed bytes hold its parents' ids and an id is the hash of bytes that hold the
+ * signature, so a batch is signed LEVEL by level: one launch per level, enqueued back to back.  Neither byte stream is
+ * materialised.  The signing keys are a setting of the context like the member keys: sw_rewind and sw_reset keep them,
+ * sw_set_member_keys called again drops them.  The secrets (clamped scalar and hash prefix per member) live in ONE device
+ * array and leave it through no getter.
+ *
+ * sw_set_signing_keys   the 32-byte Ed25519 seeds of K members (any subset; member[j] is a dense member index, its seed
+ *   the bytes seed32[32 j .. 32 j + 32)).  Needs sw_set_member_keys (SW_ENOTSUP).  The key pair is derived on the device as
+ *   crypto_sign_seed_keypair derives it; a seed whose public key differs from that member's key: SW_EINVAL, nothing
+ *   changed — as for a member out of range, with an unusable key, or given twice.  Members set by earlier calls keep
+ *   their keys.  The seeds pass through context scratch for the length of the call and are overwritten before it returns.
+ * sw_clear_signing_keys   overwrites the device copy with zeros; sw_destroy does the same.
+ * sw_get_signing_members   has_key[m] = 1 when the context holds member m's signing key: n bytes.
+ * sw_sign_events_device   READ-ONLY with respect to the hashgraph (kernel_launches and the statistics below move).  K
+ *   events in topological order as sw_append_events_device takes them: d_creator, d_self_parent, d_other_parent (int32), d_t
+ *   (float64).  Parent indices are DENSE indices in the numbering the append would give: an index below sw_num_events
+ *   names a stored event, an index at or above it the batch position index - sw_num_events; negative: none.  The four data
+ *   arguments are those of sw_pack_events_device.  Output: d_id32, d_sp_id32, d_op_id32 (32 bytes per event; the parents'
+ *   ids of a root are zeros), d_arity (0 or 2), d_sig64 — exactly the arrays sw_ingest_payload[_data]_device and
+ *   sw_pack_events_device take.  Needs member keys, signing keys and a complete id index (SW_ENOTSUP).  Structural defects
+ *   get the codes, and the lowest-offender rule, of sw_append_events_device, and are found before anything is signed; the
+ *   lowest offending event is named in sw_last_error.  A creator without a signing key, an unusable data range, or data
+ *   longer than 60 000 bytes: SW_EINVAL.  FORKS are not a defect here: signing is a pure function of the arrays.
+ *   Alignment: the id arrays and the signatures 16 bytes, d_t and d_data_off 8, the index arrays 4; every array in memory
+ *   of the context's device (a host pointer: SW_EINVAL before anything is launched).  STREAMS: as for
+ *   sw_pack_events_device; the call synchronises with the host ONCE, to read the verdict together with the number of
+ *   levels and the widest level (which size the launches).  K = 0 is a no-op.
+ * sw_sign_events   the same with host arrays, staged through context scratch.
+ * sw_create_events_device   the same inputs; signs into context scratch, then commits through the bodies of the ingest:
+ *   the append (sw_append_events_device's: its bulk predicate, fork handling and fallbacks), the id index, and — when the
+ *   data store is complete — the data append.  ATOMIC on rejection as sw_append_events_device is: memory for the ids
+ *   and the data is reserved first; two equal events in the batch, or one equal to a stored event, are refused
+ *   (SW_EINVAL: equal events have equal ids), as are data ranges that together hold more than data_bytes bytes.  Behind the
+ *   append a failure leaves the context poisoned, as in sw_ingest_payload_data.  *first_out receives the dense index of
+ *   the first created event (the K events get consecutive indices in the order given); d_id32 / d_sig64 (optional,
+ *   16-byte aligned) receive the batch's ids and signatures.  Afterwards the context is in the state
+ *   sw_ingest_payload_data would leave for the same, host-signed events.  Synchronises before it returns.
+ * sw_create_events   the same with host arrays.
+ * sw_get_sign_stats   sign calls (create calls included) and events signed so far, the levels of the last call, calls of
+ *   sw_set_signing_keys that changed the keys, and — under sw_set_profiling — the host time in ms of the last call's
+ *   levels + sort, signing, and commit: phase_ms[3].  Any pointer may be NULL.
+ */
+int sw_set_signing_keys(sw_ctx* ctx, int64_t K, const int32_t* member, const uint8_t* seed32);
+int sw_clear_signing_keys(sw_ctx* ctx);
+int sw_get_signing_members(sw_ctx* ctx, uint8_t* has_key);
+int sw_sign_events_device(sw_ctx* ctx, int64_t K, const int32_t* d_creator, const int32_t* d_self_parent, const int32_t* d_other_parent,
+                          const double* d_t, const uint8_t* d_data, const int64_t* d_data_off, int64_t data_bytes,
+                          const uint8_t* d_data_none, uint8_t* d_id32, uint8_t* d_sp_id32, uint8_t* d_op_id32, uint8_t* d_arity,
+                          uint8_t* d_sig64, void* user_stream);
+int sw_sign_events(sw_ctx* ctx, int64_t K, const int32_t* creator, const int32_t* self_parent, const int32_t* other_parent, const double* t,
+                   const uint8_t* data, const int64_t* data_off, int64_t data_bytes, const uint8_t* data_none, uint8_t* id32,
+                   uint8_t* sp_id32, uint8_t* op_id32, uint8_t* arity, uint8_t* sig64);
+int sw_create_events_device(sw_ctx* ctx, int64_t K, const int32_t* d_creator, const int32_t* d_self_parent, const int32_t* d_other_parent,
+                            const double* d_t, const uint8_t* d_data, const int64_t* d_data_off, int64_t data_bytes,
+                            const uint8_t* d_data_none, void* user_stream, int64_t* first_out, uint8_t* d_id32, uint8_t* d_sig64);
+int sw_create_events(sw_ctx* ctx, int64_t K, const int32_t* creator, const int32_t* self_parent, const int32_t* other_parent,
+                     const double* t, const uint8_t* data, const int64_t* data_off, int64_t data_bytes, const uint8_t* data_none,
+                     int64_t* first_out, uint8_t* id32, uint8_t* sig64);
+int sw_get_sign_stats(sw_ctx* ctx, int64_t* calls, int64_t* events, int64_t* levels, int64_t* key_sets, double* phase_ms);
+
 /* Exact work counters of the calls so far: used by bench.py's roofline. */
 typedef struct sw_counters {
     int64_t events_divided;      /* events through divide_rounds                          */

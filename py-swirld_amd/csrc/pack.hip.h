@@ -37,18 +37,21 @@
 #include <hip/hip_runtime.h>
 #endif
 
+#include "tmpl.hip.h"
+
 namespace pck {
 
-constexpr int MAX_DATA = 60000;        // above a 64 KiB frame the pickler splits frames
+// (the template's lengths and opcode groups: tmpl.hip.h, shared with the signer)
+constexpr int MAX_DATA = tpl::MAX_DATA;
 constexpr int MAX_NAME = 255;
 constexpr int HDR_MAX = 2 * MAX_NAME + 8;
 constexpr int SCAN_THREADS = 256;
 constexpr int SCAN_PER = 4;
 constexpr int TILE = SCAN_THREADS * SCAN_PER;   // events per tile of the scan
 constexpr int WRITE_THREADS = 256;              // chunks per workgroup and trip; also the entries of the offset tile
-constexpr int MSG_FIXED = 11 + 48;              // frame + '(' 'G' t 'C' 0x20 pk 0x94 't' 0x94 '.'
-constexpr int WHOLE_FIXED = 11 + 117;           // ... + 'C' 0x40 sig 0x94 and 0x81 0x94, without HDR
-constexpr int PARENTS = 72;
+constexpr int MSG_FIXED = tpl::MSG_FIXED;
+constexpr int WHOLE_FIXED = tpl::WHOLE_FIXED;
+constexpr int PARENTS = tpl::PARENTS;
 constexpr int MSG_MAX = MSG_FIXED + PARENTS + 6;       // per event, without its data bytes
 constexpr int WHOLE_MAX = WHOLE_FIXED + PARENTS + 6;   // ... and without HDR
 
@@ -82,7 +85,7 @@ __device__ __forceinline__ int data_len(const PackIn& in, i64 i) {
     if (in.data_none && in.data_none[i]) return -1;
     return (int)(b - a);
 }
-__device__ __forceinline__ int d_size(int dl) { return dl < 0 ? 1 : dl < 256 ? dl + 3 : dl + 6; }
+__device__ __forceinline__ int d_size(int dl) { return tpl::d_size(dl); }
 
 // ---- k_pack_lengths
 __device__ __forceinline__ void lengths(i64 i, i64 K, const PackIn& in, i64* msg_off, i64* whole_off, unsigned char* enc) {
@@ -204,7 +207,7 @@ __device__ __forceinline__ void load_event(const PackIn& in, i64 e, i64 len, Ev*
     v->ar = in.arity[e];
     v->dl = data_len(in, e);
     v->t = __builtin_bswap64(in.t[e]);   // most significant byte first
-    v->inner = (u64)(len - 11);
+    v->inner = (u64)(len - tpl::FRAME);
     v->sp = (const unsigned*)(in.sp_id + (size_t)e * 32);
     v->op = (const unsigned*)(in.op_id + (size_t)e * 32);
     v->sig = (const unsigned*)(in.sig + (size_t)e * 64);
@@ -217,20 +220,20 @@ __device__ __forceinline__ void load_event(const PackIn& in, i64 e, i64 len, Ev*
 // that 16 bytes of a stream hold few runs.
 template <bool WHOLE>
 __device__ __forceinline__ Run event_run(const Ev& v, const Tile* s, int hdr_len, int p) {
-    if (p < 3) return krun(0x950480ull, p, 3);
-    if (p < 11) return krun(v.inner, p - 3, 8);
-    p -= 11;
+    if (p < 3) return krun(tpl::K_FRAME, p, 3);
+    if (p < tpl::FRAME) return krun(v.inner, p - 3, 8);
+    p -= tpl::FRAME;
     if (WHOLE) {
         if (p < hdr_len) return brun(s->hdr, p, hdr_len);
         p -= hdr_len;
     }
     const bool root = v.ar == 0;
-    u64 A, B = root ? 0x4729ull : 0x2043ull;      // A: '(' and the head of D;  B: [0x94] and ")G" or "C\x20"
+    u64 A, B = root ? tpl::K_ROOT : tpl::K_ID;      // A: '(' and the head of D;  B: [0x94] and ")G" or "C\x20"
     int la, lb = 2;
-    if (v.dl < 0) { A = 0x4e28ull; la = 2; }
-    else if (v.dl < 256) { A = 0x4328ull | (u64)v.dl << 16; la = 3; }
-    else { A = 0x4228ull | (u64)v.dl << 16; la = 6; }
-    if (v.dl >= 0) { B = B << 8 | 0x94ull; lb = 3; }
+    if (v.dl < 0) { A = tpl::K_NONE; la = 2; }
+    else if (v.dl < 256) { A = tpl::K_BYTES8 | (u64)v.dl << 16; la = 3; }
+    else { A = tpl::K_BYTES32 | (u64)v.dl << 16; la = 6; }
+    if (v.dl >= 0) { B = B << 8 | tpl::K_MEMO; lb = 3; }
     if (v.dl <= 0) {
         if (p < la + lb) return krun(A | B << (8 * la), p, la + lb);
         p -= la + lb;
@@ -245,25 +248,25 @@ __device__ __forceinline__ Run event_run(const Ev& v, const Tile* s, int hdr_len
     if (!root) {
         if (p < 32) return frun(v.sp, p, 32);
         p -= 32;
-        if (p < 3) return krun(0x204394ull, p, 3);
+        if (p < 3) return krun(tpl::K_ID_NEXT, p, 3);
         p -= 3;
         if (p < 32) return frun(v.op, p, 32);
         p -= 32;
-        if (p < 4) return krun(0x47948694ull, p, 4);
+        if (p < 4) return krun(tpl::K_PARENTS_END, p, 4);
         p -= 4;
     }
     if (p < 8) return krun(v.t, p, 8);
     p -= 8;
-    if (p < 2) return krun(0x2043ull, p, 2);
+    if (p < 2) return krun(tpl::K_ID, p, 2);
     p -= 2;
     if (p < 32) return frun(v.pk, p, 32);
     p -= 32;
-    if (!WHOLE) return krun(0x2e947494ull, p, 4);
-    if (p < 3) return krun(0x404394ull, p, 3);
+    if (!WHOLE) return krun(tpl::K_MSG_END, p, 4);
+    if (p < 3) return krun(tpl::K_SIG, p, 3);
     p -= 3;
     if (p < 64) return frun(v.sig, p, 64);
     p -= 64;
-    return krun(0x2e9481947494ull, p, 6);
+    return krun(tpl::K_WHOLE_END, p, 6);
 }
 
 // m <= 8 bytes at ptr, lowest first, from the aligned dwords that hold them (no dword without a wanted byte is read)

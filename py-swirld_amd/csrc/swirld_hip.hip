@@ -24,6 +24,7 @@
 #include "crypto.hip.h"
 #include "validate.hip.h"
 #include "pack.hip.h"
+#include "sign.hip.h"
 #include "data.hip.h"
 #include "exact.hip.h"
 #include "ingest.hip.h"
@@ -220,6 +221,14 @@ struct sw_ctx {
     DBuf<unsigned char> d_dt_out; // the gathered data: of the host-array gather, and of sw_sync_pull_data's exported events (in the answering context)
     int64_t dt_store_calls = 0, dt_gather_calls = 0, dt_gather_bytes = 0;   // sw_get_data_stats
     double dt_ms[2] = {0, 0};     // ... host time under sw_set_profiling: lengths + scan, the copy
+    // creating signed events (sw_set_signing_keys, sw_sign_events[_device], sw_create_events[_device]; sign.hip.h): like the
+    // member keys a setting that sw_rewind / sw_reset leave alone; sw_set_member_keys drops it
+    std::vector<uint8_t> sg_has;  // n flags: the members this context may sign for (empty: no signing key set)
+    DBuf<unsigned char> d_sg_keys;   // [n secrets of 64 B][n flags]: the ONLY copy of the secrets, never read back
+    DBuf<unsigned char> d_sg;     // scratch of a call: verdict block, levels, level counts and offsets, cursors, sorted events
+    DBuf<unsigned char> d_sg_in;  // the staged arrays of the host-array forms; the signed arrays of sw_create_events
+    int64_t sg_calls = 0, sg_events = 0, sg_levels = 0, sg_keysets = 0;   // sw_get_sign_stats (levels: the last call's)
+    double sg_ms[3] = {0, 0, 0};  // ... host time under sw_set_profiling: levels + sort, signing, commit
 
     // device: events
     DBuf<int32_t> d_cr, d_sp, d_op, d_ht, d_seq, d_round, d_L, d_chain_ev;
@@ -3173,6 +3182,8 @@ int sw_destroy(sw_ctx* c) {
     dfree(c->d_vkeys); dfree(c->d_vtab); dfree(c->d_v_in);
     dfree(c->d_pk_hdr); dfree(c->d_pk); dfree(c->d_pk_in); dfree(c->d_pk_out);
     dfree(c->d_data); dfree(c->d_data_off); dfree(c->d_data_none); dfree(c->d_dt); dfree(c->d_dt_in); dfree(c->d_dt_out);
+    if (c->d_sg_keys.p) { (void)hipMemset(c->d_sg_keys.p, 0, c->d_sg_keys.cap); (void)hipDeviceSynchronize(); }   // the secrets do not outlive the context
+    dfree(c->d_sg_keys); dfree(c->d_sg); dfree(c->d_sg_in);
     if (c->h_pkcnt) (void)hipHostFree(c->h_pkcnt);
     if (c->h_plcnt) (void)hipHostFree(c->h_plcnt);
     if (c->ev_aux_done) (void)hipEventDestroy(c->ev_aux_done);
@@ -5457,6 +5468,15 @@ int validate_launch(sw_ctx* c, int64_t K, const swv::Payload& p, uint8_t* d_ok) 
     return SW_OK;
 }
 
+// the signing keys of the context, overwritten with zeros (sw_clear_signing_keys, sw_set_member_keys, sw_destroy)
+int sign_keys_clear(sw_ctx* c) {
+    c->sg_has.clear();
+    if (!c->d_sg_keys.p) return SW_OK;
+    HIPCHK(c, hipMemsetAsync(c->d_sg_keys.p, 0, c->d_sg_keys.cap, c->stream));   // (behind whatever still signs on this stream)
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return SW_OK;
+}
+
 int validate_pre(sw_ctx* c, int64_t K, const void* msgs, const void* msg_off, int64_t msg_bytes, const void* whole, const void* whole_off,
                  int64_t whole_bytes, const void* sig, const void* creator, const void* id, const void* ok, const char* what) {
     if (c->poisoned) return fail(c, SW_EIO, "context unusable after an earlier device failure");
@@ -5482,6 +5502,7 @@ int sw_set_member_keys(sw_ctx* c, const uint8_t* pk32, int32_t* n_unusable) {
     HIPCHK(c, hipSetDevice(c->device));
     const size_t n = (size_t)c->n;
     const auto t0 = std::chrono::steady_clock::now();
+    CHK(sign_keys_clear(c));   // signing keys belong to the member keys they were checked against
     CHK(dgrow(c, c->d_vkeys, n * 33, 0));
     CHK(dgrow(c, c->d_vtab, (n + 1) * swv::ROW * sizeof(swv::niels), 0));
     // (an earlier validation may still be reading the old table on this stream: the build is ordered behind it)
@@ -6446,6 +6467,405 @@ int sw_get_data_stats(sw_ctx* c, int64_t* events, int64_t* bytes, int64_t* store
     if (gather_calls) *gather_calls = c->dt_gather_calls;
     if (gather_bytes) *gather_bytes = c->dt_gather_bytes;
     if (phase_ms) for (int i = 0; i < 2; ++i) phase_ms[i] = c->dt_ms[i];
+    return SW_OK;
+}
+
+// ---- creating signed events on the device (sign.hip.h) -------------------------------------------------
+}  // extern "C"
+
+namespace {
+
+struct SignArrays {   // what a sign call reads and writes, every array in device memory
+    const int32_t *creator, *sp, *op;
+    const double* t;
+    const uint8_t* data;
+    const int64_t* data_off;
+    int64_t data_bytes;
+    const uint8_t* data_none;
+    uint8_t *id, *sp_id, *op_id, *arity, *sig;
+};
+
+// what every form checks before anything else
+int sign_pre(sw_ctx* c, int64_t K, const void* creator, const void* sp, const void* op, const void* t, const void* data, const void* data_off,
+             int64_t data_bytes, const void* data_none, const char* what) {
+    if (c->poisoned) return fail(c, SW_EIO, "context unusable after an earlier device failure");
+    if (c->vkeys.empty()) return fail(c, SW_ENOTSUP, "%s: no member keys (sw_set_member_keys first)", what);
+    if (c->sg_has.empty()) return fail(c, SW_ENOTSUP, "%s: no signing keys (sw_set_signing_keys first)", what);
+    if (c->n_ids != c->N)
+        return fail(c, SW_ENOTSUP, "%s: %lld of the %lld stored events have no id (sw_set_event_ids first)", what, (long long)(c->N - c->n_ids), (long long)c->N);
+    if (K < 0 || data_bytes < 0) return fail(c, SW_EINVAL, "%s: negative count or length", what);
+    if (K > 0x3fffffffll || c->N + K > 0x7ffffff0ll) return fail(c, SW_ERANGE, "%s: more than 2^31 events", what);
+    if (K > 0 && (!creator || !sp || !op || !t)) return fail(c, SW_EINVAL, "%s: NULL event arrays", what);
+    if (!data_off && (data || data_bytes || data_none)) return fail(c, SW_EINVAL, "%s: data needs its offsets (or none of data, offsets, length, flags)", what);
+    if (data_off && data_bytes > 0 && !data) return fail(c, SW_EINVAL, "%s: %lld data bytes and a NULL buffer", what, (long long)data_bytes);
+    return SW_OK;
+}
+
+// The call behind the argument checks, on the context's stream: checks and levels (ONE synchronisation: the verdict, the
+// level count and the widest level come back together), the sort by level, one launch per level.  Returns with the level
+// launches enqueued.  *usable: the data bytes of all ranges together (they may overlap).
+int sign_core(sw_ctx* c, int64_t K, const SignArrays& a, const char* what, int64_t* usable) {
+    const bool prof = c->profiling;
+    auto t0 = std::chrono::steady_clock::now();
+    c->sg_ms[0] = c->sg_ms[1] = c->sg_ms[2] = 0;
+    CHK(pack_header(c));
+    const size_t k = (size_t)K;
+    Carve cv;
+    const size_t o_blk = cv.take(256), o_lvl = cv.take(k * 4), o_cnt = cv.take((k + 2) * 8), o_cur = cv.take(k * 4), o_ev = cv.take(k * 4);
+    const size_t o_ts = cv.take(((k + pck::TILE - 1) / pck::TILE + 1) * 8);
+    CHK(dgrow(c, c->d_sg, cv.off + 256, 0));
+    unsigned char* B = c->d_sg.p;
+    unsigned long long* d_v = (unsigned long long*)(B + o_blk);   // [0] verdict, [1] data bytes, then stat[4] as ints
+    int* d_stat = (int*)(B + o_blk + 16);
+    int* lvl = (int*)(B + o_lvl);
+    pck::i64* cnt = (pck::i64*)(B + o_cnt);
+    int* cursor = (int*)(B + o_cur);
+    int* level_events = (int*)(B + o_ev);
+    pck::i64* tsum = (pck::i64*)(B + o_ts);
+    const int n = c->n;
+    const sws::SignIn in{a.creator, a.sp, a.op, (const sws::u64*)a.t, a.data, (const sws::i64*)a.data_off, (sws::i64)a.data_bytes, a.data_none,
+                         (const int*)c->d_cr.p, (const uint8_t*)c->d_id.p, (int)c->N, n, (const uint8_t*)c->d_vkeys.p,
+                         (const uint8_t*)c->d_sg_keys.p + (size_t)n * sizeof(sws::Secret), (const sws::Secret*)c->d_sg_keys.p,
+                         (const swv::niels*)c->d_vtab.p + (size_t)n * swv::ROW, (const uint8_t*)c->d_pk_hdr.p, pack_hdr_len(c)};
+    const sws::SignOut out{a.id, a.sp_id, a.op_id, a.arity, a.sig};
+    HIPCHK(c, hipMemsetAsync(B + o_blk, 0, 256, c->stream));
+    HIPCHK(c, hipMemsetAsync(B + o_blk, 0xff, 8, c->stream));   // ing::V_NONE
+    HIPCHK(c, hipMemsetAsync(cnt, 0, (k + 2) * 8, c->stream));
+    HIPCHK(c, hipMemsetAsync(cursor, 0, k * 4, c->stream));
+    const dim3 ev_grid((unsigned)((K + 255) / 256));
+    hipLaunchKernelGGL(sws::k_sign_check, ev_grid, dim3(256), 0, c->stream, in, (int)K, d_v, d_v + 1);
+    hipLaunchKernelGGL(sws::k_sign_levels, dim3(1), dim3(sws::LV_TILE), 0, c->stream, a.sp, a.op, (int)c->N, (int)K, lvl, (unsigned long long*)cnt, d_stat);
+    c->ctr.kernel_launches += 2;
+    HIPCHK(c, hipGetLastError());
+    unsigned long long rb[4] = {0, 0, 0, 0};
+    HIPCHK(c, hipMemcpyAsync(rb, B + o_blk, sizeof rb, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (rb[0] != ing::V_NONE) {
+        const long long e = (long long)(rb[0] >> 8);
+        switch ((int)(rb[0] & 0xff)) {
+            case ing::V_CREATOR: return fail(c, SW_EINVAL, "event %lld: creator out of range", e);
+            case ing::V_ARITY: return fail(c, SW_EINVAL, "event %lld: must have 0 or 2 parents", e);
+            case ing::V_ORDER: return fail(c, SW_EINVAL, "event %lld: parent index not earlier (not a topological order)", e);
+            case ing::V_SELF: return fail(c, SW_EINVAL, "event %lld: self-parent is by another member", e);
+            case ing::V_OTHER: return fail(c, SW_EINVAL, "event %lld: other-parent is by the same member", e);
+            case sws::V_NOKEY: return fail(c, SW_EINVAL, "event %lld: no signing key for its creator", e);
+            default: return fail(c, SW_EINVAL, "event %lld: data range negative, decreasing, beyond the %lld data bytes, or longer than %d", e,
+                                 (long long)a.data_bytes, tpl::MAX_DATA);
+        }
+    }
+    int stat[4];
+    memcpy(stat, rb + 2, sizeof stat);
+    const int nlev = stat[0], widest = stat[1];
+    if (stat[2] || nlev < 1 || nlev > K || widest < 1 || widest > K)
+        return fail(c, SW_EIO, "%s: %d levels, widest %d, flag %d for %lld events (internal error)", what, nlev, widest, stat[2], (long long)K);
+    *usable = (int64_t)rb[1];
+    // ---- the batch sorted by level: counts -> offsets (the scan of pack.hip.h), scatter
+    const int64_t tiles = (nlev + pck::TILE - 1) / pck::TILE;
+    hipLaunchKernelGGL(pck::k_pack_tile_sums, dim3((unsigned)tiles, 1), dim3(pck::SCAN_THREADS), 0, c->stream, (pck::i64)nlev, (pck::i64)tiles,
+                       (const pck::i64*)cnt, (const pck::i64*)cnt, tsum);
+    hipLaunchKernelGGL(pck::k_pack_scan_sums, dim3(1), dim3(pck::SCAN_THREADS), 0, c->stream, (pck::i64)nlev, (pck::i64)tiles, cnt, cnt, tsum);
+    hipLaunchKernelGGL(pck::k_pack_offsets, dim3((unsigned)tiles, 1), dim3(pck::SCAN_THREADS), 0, c->stream, (pck::i64)nlev, (pck::i64)tiles, cnt, cnt,
+                       (const pck::i64*)tsum);
+    hipLaunchKernelGGL(sws::k_sign_scatter, ev_grid, dim3(256), 0, c->stream, (int)K, (const int*)lvl, (const sws::i64*)cnt, cursor, level_events);
+    c->ctr.kernel_launches += 4;
+    HIPCHK(c, hipGetLastError());
+    if (prof) { HIPCHK(c, hipStreamSynchronize(c->stream)); c->sg_ms[0] = ms_since(t0); t0 = std::chrono::steady_clock::now(); }
+    // ---- one launch per level, back to back
+    const dim3 lv_grid((unsigned)((widest + 63) / 64));
+    for (int l = 0; l < nlev; ++l)
+        hipLaunchKernelGGL(sws::k_sign_level, lv_grid, dim3(64), 0, c->stream, in, out, (const sws::i64*)cnt, (const int*)level_events, l);
+    c->ctr.kernel_launches += nlev;
+    HIPCHK(c, hipGetLastError());
+    if (prof) { HIPCHK(c, hipStreamSynchronize(c->stream)); c->sg_ms[1] = ms_since(t0); }
+    c->sg_calls++;
+    c->sg_events += K;
+    c->sg_levels = nlev;
+    return SW_OK;
+}
+
+// the alignment and residency rules of the device forms (those of sw_pack_events_device); out arrays may be NULL (create)
+int sign_device_args(sw_ctx* c, int64_t K, const int32_t* cr, const int32_t* sp, const int32_t* op, const double* t, const uint8_t* data,
+                     const int64_t* data_off, int64_t data_bytes, const uint8_t* data_none, const uint8_t* id, const uint8_t* sp_id, const uint8_t* op_id,
+                     const uint8_t* arity, const uint8_t* sig, const char* what) {
+    if (((uintptr_t)id | (uintptr_t)sp_id | (uintptr_t)op_id | (uintptr_t)sig) & 15)
+        return fail(c, SW_EINVAL, "%s: the id arrays and the signatures must be 16-byte aligned", what);
+    if (((uintptr_t)data_off | (uintptr_t)t) & 7) return fail(c, SW_EINVAL, "%s: the offsets and the timestamps must be 8-byte aligned", what);
+    if (((uintptr_t)cr | (uintptr_t)sp | (uintptr_t)op) & 3) return fail(c, SW_EINVAL, "%s: the index arrays must be 4-byte aligned", what);
+    const size_t k = (size_t)K;
+    const bool on = on_ctx_device(c, cr, k * 4) && on_ctx_device(c, sp, k * 4) && on_ctx_device(c, op, k * 4) && on_ctx_device(c, t, k * 8) &&
+                    (!data_off || on_ctx_device(c, data_off, (k + 1) * 8)) && (!data || data_bytes == 0 || on_ctx_device(c, data, (size_t)data_bytes)) &&
+                    (!data_none || on_ctx_device(c, data_none, k)) && (!id || on_ctx_device(c, id, k * 32)) && (!sp_id || on_ctx_device(c, sp_id, k * 32)) &&
+                    (!op_id || on_ctx_device(c, op_id, k * 32)) && (!arity || on_ctx_device(c, arity, k)) && (!sig || on_ctx_device(c, sig, k * 64));
+    if (!on) return fail(c, SW_EINVAL, "%s: every array must lie in memory of device %d (a host pointer, or another device's)", what, c->device);
+    return SW_OK;
+}
+
+// the signed arrays of a create call at the front of d_sg_in (the host form stages its inputs behind `end`)
+struct CreateScratch { size_t id, sp, op, ar, sig, end; };
+CreateScratch create_scratch(size_t k) {
+    Carve cv;
+    CreateScratch s{};
+    s.id = cv.take(k * 32); s.sp = cv.take(k * 32); s.op = cv.take(k * 32); s.ar = cv.take(k); s.sig = cv.take(k * 64);
+    s.end = cv.off;
+    return s;
+}
+
+// sw_create_events behind the argument checks: every array in device memory and visible to the context's stream.
+// Everything that can be refused or can run out of memory comes first; behind the append a failure poisons the context.
+int create_core(sw_ctx* c, int64_t K, const int32_t* d_cr, const int32_t* d_sp, const int32_t* d_op, const double* d_t, const uint8_t* d_data,
+                const int64_t* d_off, int64_t data_bytes, const uint8_t* d_none, uint8_t* d_id_out, uint8_t* d_sig_out, const char* what) {
+    const int64_t N0 = c->N;
+    const bool with_data = c->n_data == N0;
+    const size_t k = (size_t)K;
+    // ---- reservations: ids and table, the data store, the signed arrays
+    CHK(idindex_reserve(c, N0 + K));
+    DataPlan p{};
+    if (with_data) {
+        CHK(data_scratch(c, K, 0, 0, &p));
+        CHK(data_reserve(c, N0 + K, c->data_used + data_bytes));
+    }
+    const CreateScratch L = create_scratch(k);
+    const size_t o_id = L.id, o_sp = L.sp, o_op = L.op, o_ar = L.ar, o_sig = L.sig;
+    CHK(dgrow(c, c->d_sg_in, L.end + 256, 0));
+    unsigned char* B = c->d_sg_in.p;
+    int64_t usable = 0;
+    CHK(sign_core(c, K, SignArrays{d_cr, d_sp, d_op, d_t, d_data, d_off, data_bytes, d_none, B + o_id, B + o_sp, B + o_op, B + o_ar, B + o_sig}, what, &usable));
+    if (with_data && usable > data_bytes)
+        return fail(c, SW_EINVAL, "%s: the data ranges hold %lld bytes, the buffer %lld: ranges overlap (nothing stored)", what, (long long)usable, (long long)data_bytes);
+    const auto t0 = std::chrono::steady_clock::now();
+    // ---- the ids into the (uncommitted) tail and the table: two equal events, or one that is stored already, show here
+    HIPCHK(c, hipMemcpyAsync(c->d_id.p + (size_t)N0 * 32, B + o_id, k * 32, hipMemcpyDeviceToDevice, c->stream));
+    int flag = 0;
+    CHK(idtab_insert(c, N0, K, &flag));
+    if (flag != 0) {
+        CHK(idtab_rebuild(c));   // (the table as it was)
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        if (flag == 1) return fail(c, SW_EINVAL, "%s: an event of the batch equals a stored event or another one of the batch (nothing stored)", what);
+        return fail(c, SW_EIO, "%s: id table full (internal error)", what);
+    }
+    // ---- append (bulk device path or its fallbacks; atomic)
+    const int rc = append_device_body(c, K, d_cr, d_sp, d_op, d_t, B + o_sig, c->stream);
+    if (rc != SW_OK) {
+        if (!c->poisoned) {
+            const std::string msg = c->err;
+            if (idtab_rebuild(c) != SW_OK || hipStreamSynchronize(c->stream) != hipSuccess) c->poisoned = true;
+            c->err = msg;
+        }
+        return rc;
+    }
+    c->n_ids = N0 + K;
+    // ---- committed
+    const auto after = [&]() -> int {
+        if (with_data) CHK(data_set_body(c, K, d_data, d_off, data_bytes, d_none, what));
+        if (d_id_out) HIPCHK(c, hipMemcpyAsync(d_id_out, B + o_id, k * 32, hipMemcpyDeviceToDevice, c->stream));
+        if (d_sig_out) HIPCHK(c, hipMemcpyAsync(d_sig_out, B + o_sig, k * 64, hipMemcpyDeviceToDevice, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));   // on return the caller's arrays may be reused or freed
+        return SW_OK;
+    };
+    const int rc2 = after();
+    if (rc2 != SW_OK) c->poisoned = true;
+    if (c->profiling) c->sg_ms[2] = ms_since(t0);
+    return rc2;
+}
+
+}  // namespace
+
+extern "C" {
+
+int sw_set_signing_keys(sw_ctx* c, int64_t K, const int32_t* member, const uint8_t* seed32) {
+    if (!c) return SW_EINVAL;
+    const char* what = "sw_set_signing_keys";
+    if (c->poisoned) return fail(c, SW_EIO, "context unusable after an earlier device failure");
+    if (c->vkeys.empty()) return fail(c, SW_ENOTSUP, "%s: no member keys (sw_set_member_keys first)", what);
+    if (K < 0 || K > c->n || (K > 0 && (!member || !seed32))) return fail(c, SW_EINVAL, "%s: bad count or NULL arrays", what);
+    if (K == 0) return SW_OK;
+    const size_t n = (size_t)c->n, k = (size_t)K;
+    std::vector<char> seen(n, 0);
+    for (int64_t j = 0; j < K; ++j) {
+        const int m = member[j];
+        if (m < 0 || m >= c->n) return fail(c, SW_EINVAL, "%s: member %d out of range", what, m);
+        if (!c->vusable[(size_t)m]) return fail(c, SW_EINVAL, "%s: member %d has an unusable key", what, m);
+        if (seen[(size_t)m]) return fail(c, SW_EINVAL, "%s: member %d given twice", what, m);
+        seen[(size_t)m] = 1;
+    }
+    HIPCHK(c, hipSetDevice(c->device));
+    if (!c->d_sg_keys.p) {
+        CHK(dgrow(c, c->d_sg_keys, n * (sizeof(sws::Secret) + 1), 0));
+        HIPCHK(c, hipMemsetAsync(c->d_sg_keys.p, 0, c->d_sg_keys.cap, c->stream));
+    }
+    Carve cv;
+    const size_t o_m = cv.take(k * 4), o_seed = cv.take(k * 32), o_ok = cv.take(k);
+    CHK(dgrow(c, c->d_sg, cv.off + 256, 0));
+    unsigned char* B = c->d_sg.p;
+    sws::Secret* secret = (sws::Secret*)c->d_sg_keys.p;
+    uint8_t* has = c->d_sg_keys.p + n * sizeof(sws::Secret);
+    const swv::niels* rowB = (const swv::niels*)c->d_vtab.p + n * swv::ROW;
+    std::vector<uint8_t> ok(k);
+    // the seeds pass through scratch for the length of this call, and are overwritten before it returns whatever happens
+    const auto run = [&]() -> int {
+        HIPCHK(c, hipMemcpyAsync(B + o_m, member, k * 4, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(B + o_seed, seed32, k * 32, hipMemcpyHostToDevice, c->stream));
+        const dim3 grid((unsigned)((K + 63) / 64));
+        hipLaunchKernelGGL(sws::k_sign_keys, grid, dim3(64), 0, c->stream, (int)K, (const int*)(B + o_m), (const uint8_t*)(B + o_seed),
+                           (const uint8_t*)c->d_vkeys.p, rowB, 0, secret, has, B + o_ok);
+        c->ctr.kernel_launches++;
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipMemcpyAsync(ok.data(), B + o_ok, k, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        for (int64_t j = 0; j < K; ++j)
+            if (!ok[(size_t)j]) return fail(c, SW_EINVAL, "%s: the seed given for member %d does not derive that member's key (nothing changed)", what, member[j]);
+        hipLaunchKernelGGL(sws::k_sign_keys, grid, dim3(64), 0, c->stream, (int)K, (const int*)(B + o_m), (const uint8_t*)(B + o_seed),
+                           (const uint8_t*)c->d_vkeys.p, rowB, 1, secret, has, B + o_ok);
+        c->ctr.kernel_launches++;
+        HIPCHK(c, hipGetLastError());
+        return SW_OK;
+    };
+    const int rc = run();
+    (void)hipMemsetAsync(B + o_seed, 0, k * 32, c->stream);
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (rc != SW_OK) return rc;
+    if (c->sg_has.empty()) c->sg_has.assign(n, 0);
+    for (int64_t j = 0; j < K; ++j) c->sg_has[(size_t)member[j]] = 1;
+    c->sg_keysets++;
+    return SW_OK;
+}
+
+int sw_clear_signing_keys(sw_ctx* c) {
+    if (!c) return SW_EINVAL;
+    HIPCHK(c, hipSetDevice(c->device));
+    return sign_keys_clear(c);
+}
+
+int sw_get_signing_members(sw_ctx* c, uint8_t* has_key) {
+    if (!c) return SW_EINVAL;
+    if (!has_key) return fail(c, SW_EINVAL, "sw_get_signing_members: NULL output");
+    for (int m = 0; m < c->n; ++m) has_key[m] = c->sg_has.empty() ? 0 : c->sg_has[(size_t)m];
+    return SW_OK;
+}
+
+int sw_sign_events_device(sw_ctx* c, int64_t K, const int32_t* d_creator, const int32_t* d_self_parent, const int32_t* d_other_parent, const double* d_t,
+                          const uint8_t* d_data, const int64_t* d_data_off, int64_t data_bytes, const uint8_t* d_data_none, uint8_t* d_id32,
+                          uint8_t* d_sp_id32, uint8_t* d_op_id32, uint8_t* d_arity, uint8_t* d_sig64, void* user_stream) {
+    if (!c) return SW_EINVAL;
+    const char* what = "sw_sign_events_device";
+    CHK(sign_pre(c, K, d_creator, d_self_parent, d_other_parent, d_t, d_data, d_data_off, data_bytes, d_data_none, what));
+    if (K == 0) return SW_OK;
+    if (!d_id32 || !d_sp_id32 || !d_op_id32 || !d_arity || !d_sig64) return fail(c, SW_EINVAL, "%s: NULL output arrays", what);
+    HIPCHK(c, hipSetDevice(c->device));
+    CHK(sign_device_args(c, K, d_creator, d_self_parent, d_other_parent, d_t, d_data, d_data_off, data_bytes, d_data_none, d_id32, d_sp_id32, d_op_id32,
+                         d_arity, d_sig64, what));
+    if (!c->ev_user) HIPCHK(c, hipEventCreateWithFlags(&c->ev_user, hipEventDisableTiming));
+    hipStream_t us = (hipStream_t)user_stream;
+    HIPCHK(c, hipEventRecord(c->ev_user, us));            // the producers of the arrays; earlier readers of the outputs
+    HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_user, 0));
+    int64_t usable = 0;
+    CHK(sign_core(c, K, SignArrays{d_creator, d_self_parent, d_other_parent, d_t, d_data, d_data_off, data_bytes, d_data_none, d_id32, d_sp_id32,
+                                   d_op_id32, d_arity, d_sig64}, what, &usable));
+    HIPCHK(c, hipEventRecord(c->ev_user, c->stream));     // whatever the caller enqueues next reads complete arrays
+    HIPCHK(c, hipStreamWaitEvent(us, c->ev_user, 0));
+    return SW_OK;
+}
+
+}  // extern "C"
+
+namespace {
+
+// the inputs of the host-array forms staged in d_sg_in behind `front` bytes; pointers into the staging come back
+struct SignStaged { const int32_t *cr, *sp, *op; const double* t; const uint8_t* data; const int64_t* off; const uint8_t* none; };
+int sign_stage(sw_ctx* c, int64_t K, size_t front, const int32_t* creator, const int32_t* sp, const int32_t* op, const double* t, const uint8_t* data,
+               const int64_t* data_off, int64_t data_bytes, const uint8_t* data_none, SignStaged* s) {
+    const size_t k = (size_t)K, db = (size_t)data_bytes;
+    Carve cv;
+    cv.off = front;
+    const size_t o_cr = cv.take(k * 4), o_sp = cv.take(k * 4), o_op = cv.take(k * 4), o_t = cv.take(k * 8);
+    const size_t o_doff = cv.take(data_off ? (k + 1) * 8 : 0), o_d = cv.take(db), o_dn = cv.take(data_none ? k : 0);
+    CHK(dgrow(c, c->d_sg_in, cv.off + 256, 0));
+    unsigned char* B = c->d_sg_in.p;
+    const struct { size_t o; const void* src; size_t bytes; } up[] = {
+        {o_cr, creator, k * 4}, {o_sp, sp, k * 4}, {o_op, op, k * 4}, {o_t, t, k * 8}, {o_doff, data_off, data_off ? (k + 1) * 8 : 0}, {o_d, data, db},
+        {o_dn, data_none, data_none ? k : 0}};
+    for (const auto& u : up)
+        if (u.bytes) HIPCHK(c, hipMemcpyAsync(B + u.o, u.src, u.bytes, hipMemcpyHostToDevice, c->stream));
+    *s = SignStaged{(const int32_t*)(B + o_cr), (const int32_t*)(B + o_sp), (const int32_t*)(B + o_op), (const double*)(B + o_t),
+                    data_off ? B + o_d : nullptr, data_off ? (const int64_t*)(B + o_doff) : nullptr, data_none ? B + o_dn : nullptr};
+    return SW_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int sw_sign_events(sw_ctx* c, int64_t K, const int32_t* creator, const int32_t* self_parent, const int32_t* other_parent, const double* t,
+                   const uint8_t* data, const int64_t* data_off, int64_t data_bytes, const uint8_t* data_none, uint8_t* id32, uint8_t* sp_id32,
+                   uint8_t* op_id32, uint8_t* arity, uint8_t* sig64) {
+    if (!c) return SW_EINVAL;
+    const char* what = "sw_sign_events";
+    CHK(sign_pre(c, K, creator, self_parent, other_parent, t, data, data_off, data_bytes, data_none, what));
+    if (K == 0) return SW_OK;
+    if (!id32 || !sp_id32 || !op_id32 || !arity || !sig64) return fail(c, SW_EINVAL, "%s: NULL output arrays", what);
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t k = (size_t)K;
+    Carve cv;
+    const size_t o_id = cv.take(k * 32), o_spid = cv.take(k * 32), o_opid = cv.take(k * 32), o_ar = cv.take(k), o_sig = cv.take(k * 64);
+    SignStaged s{};
+    CHK(sign_stage(c, K, cv.off, creator, self_parent, other_parent, t, data, data_off, data_bytes, data_none, &s));
+    unsigned char* B = c->d_sg_in.p;
+    int64_t usable = 0;
+    CHK(sign_core(c, K, SignArrays{s.cr, s.sp, s.op, s.t, s.data, s.off, data_bytes, s.none, B + o_id, B + o_spid, B + o_opid, B + o_ar, B + o_sig}, what, &usable));
+    HIPCHK(c, hipMemcpyAsync(id32, B + o_id, k * 32, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(sp_id32, B + o_spid, k * 32, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(op_id32, B + o_opid, k * 32, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(arity, B + o_ar, k, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(sig64, B + o_sig, k * 64, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return SW_OK;
+}
+
+int sw_create_events_device(sw_ctx* c, int64_t K, const int32_t* d_creator, const int32_t* d_self_parent, const int32_t* d_other_parent, const double* d_t,
+                            const uint8_t* d_data, const int64_t* d_data_off, int64_t data_bytes, const uint8_t* d_data_none, void* user_stream,
+                            int64_t* first_out, uint8_t* d_id32, uint8_t* d_sig64) {
+    if (!c) return SW_EINVAL;
+    const char* what = "sw_create_events_device";
+    CHK(sign_pre(c, K, d_creator, d_self_parent, d_other_parent, d_t, d_data, d_data_off, data_bytes, d_data_none, what));
+    if (first_out) *first_out = c->N;
+    if (K == 0) return SW_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    CHK(sign_device_args(c, K, d_creator, d_self_parent, d_other_parent, d_t, d_data, d_data_off, data_bytes, d_data_none, d_id32, nullptr, nullptr, nullptr,
+                         d_sig64, what));
+    if (!c->ev_user) HIPCHK(c, hipEventCreateWithFlags(&c->ev_user, hipEventDisableTiming));
+    HIPCHK(c, hipEventRecord(c->ev_user, (hipStream_t)user_stream));
+    HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_user, 0));
+    return create_core(c, K, d_creator, d_self_parent, d_other_parent, d_t, d_data, d_data_off, data_bytes, d_data_none, d_id32, d_sig64, what);
+}
+
+int sw_create_events(sw_ctx* c, int64_t K, const int32_t* creator, const int32_t* self_parent, const int32_t* other_parent, const double* t,
+                     const uint8_t* data, const int64_t* data_off, int64_t data_bytes, const uint8_t* data_none, int64_t* first_out, uint8_t* id32,
+                     uint8_t* sig64) {
+    if (!c) return SW_EINVAL;
+    const char* what = "sw_create_events";
+    CHK(sign_pre(c, K, creator, self_parent, other_parent, t, data, data_off, data_bytes, data_none, what));
+    if (first_out) *first_out = c->N;
+    if (K == 0) return SW_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t k = (size_t)K;
+    const CreateScratch L = create_scratch(k);
+    SignStaged s{};
+    CHK(sign_stage(c, K, L.end, creator, self_parent, other_parent, t, data, data_off, data_bytes, data_none, &s));
+    CHK(create_core(c, K, s.cr, s.sp, s.op, s.t, s.data, s.off, data_bytes, s.none, nullptr, nullptr, what));
+    const unsigned char* B = c->d_sg_in.p;   // (create_core found the buffer large enough: it has not moved)
+    if (id32) HIPCHK(c, hipMemcpyAsync(id32, B + L.id, k * 32, hipMemcpyDeviceToHost, c->stream));
+    if (sig64) HIPCHK(c, hipMemcpyAsync(sig64, B + L.sig, k * 64, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return SW_OK;
+}
+
+int sw_get_sign_stats(sw_ctx* c, int64_t* calls, int64_t* events, int64_t* levels, int64_t* key_sets, double* phase_ms) {
+    if (!c) return SW_EINVAL;
+    if (calls) *calls = c->sg_calls;
+    if (events) *events = c->sg_events;
+    if (levels) *levels = c->sg_levels;
+    if (key_sets) *key_sets = c->sg_keysets;
+    if (phase_ms) for (int i = 0; i < 3; ++i) phase_ms[i] = c->sg_ms[i];
     return SW_OK;
 }
 

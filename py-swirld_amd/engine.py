@@ -723,6 +723,100 @@ class Hashgraph:
         d.update(zip(("scan_ms", "write_ms"), (float(x) for x in ms)))
         return d
 
+    # ---- creating signed events (Node.new_event, swirld.py:82-95, for a batch; csrc/sign.hip.h) ----
+    def set_signing_seeds(self, members, seeds):
+        """The Ed25519 seeds (32 bytes each: K x 32 uint8, or K byte strings) of the members this context may sign for
+        (sw_set_signing_keys); any subset of the members, after set_member_keys.  A seed that does not derive its member's
+        key raises SwirldHipError -22 and changes nothing.  The secrets stay on the device."""
+        members = np.ascontiguousarray(members, np.int32).reshape(-1)
+        if isinstance(seeds, (list, tuple)):
+            seeds = np.frombuffer(b"".join(bytes(s) for s in seeds), np.uint8)
+        seeds = np.ascontiguousarray(seeds, np.uint8).reshape(-1)
+        if seeds.shape[0] != 32 * members.shape[0]:
+            raise ValueError("expected %d seeds of 32 bytes" % members.shape[0])
+        self._chk(self._L.sw_set_signing_keys(self._h, members.shape[0], _p(members), _p(seeds)))
+
+    def clear_signing_seeds(self):
+        """Overwrites the device copy of the signing keys with zeros (sw_clear_signing_keys)."""
+        self._chk(self._L.sw_clear_signing_keys(self._h))
+
+    def signing_members(self):
+        """One bool per member: does the context hold its signing key?"""
+        has = np.zeros(self.n, np.uint8)
+        self._chk(self._L.sw_get_signing_members(self._h, _p(has)))
+        return has.astype(bool)
+
+    def _event_arrays(self, creator, self_parent, other_parent, t):
+        creator = np.ascontiguousarray(creator, np.int32)
+        K = creator.shape[0]
+        sp, op = np.ascontiguousarray(self_parent, np.int32), np.ascontiguousarray(other_parent, np.int32)
+        t = np.ascontiguousarray(t, np.float64)
+        if sp.shape != (K,) or op.shape != (K,) or t.shape != (K,):
+            raise ValueError("creator, parents and t must have equal length")
+        return K, creator, sp, op, t
+
+    def sign_events(self, creator, self_parent, other_parent, t, data=None, data_off=None, data_none=None):
+        """Signatures and ids of K events in topological order, host arrays (sw_sign_events): creator / parents as
+        append_events takes them — a parent index below num_events names a stored event, one at or above it the batch
+        position index - num_events — t float64, data a list of bytes | None or (data, data_off, data_none) as pack_events
+        takes them.  Nothing is stored.  Returns a dict of ids, sp_ids, op_ids (K x 32 uint8), arity (uint8) and sig
+        (K x 64 uint8): the arrays ingest_payload and pack_events take."""
+        K, creator, sp, op, t = self._event_arrays(creator, self_parent, other_parent, t)
+        d, off, none, nbytes = (None, None, None, 0) if data is None and data_off is None and data_none is None else self._data_arrays(K, data, data_off, data_none)
+        out = dict(ids=np.zeros((K, 32), np.uint8), sp_ids=np.zeros((K, 32), np.uint8), op_ids=np.zeros((K, 32), np.uint8),
+                   arity=np.zeros(K, np.uint8), sig=np.zeros((K, 64), np.uint8))
+        self._chk(self._L.sw_sign_events(self._h, K, _p(creator), _p(sp), _p(op), _p(t), _p(d), _p(off), nbytes, _p(none), _p(out["ids"]),
+                                         _p(out["sp_ids"]), _p(out["op_ids"]), _p(out["arity"]), _p(out["sig"])))
+        return out
+
+    def sign_events_device(self, creator, self_parent, other_parent, t, ids, sp_ids, op_ids, arity, sig, data=None, data_off=None, data_bytes=0,
+                           data_none=None, stream=0, count=None):
+        """sign_events between arrays in DEVICE memory (sw_sign_events_device): ids / sp_ids / op_ids (K x 32 uint8) and sig
+        (K x 64 uint8) 16-byte aligned.  Complete for whatever is enqueued on `stream` afterwards; the call synchronises
+        once, for the number of levels.  K comes from `creator`'s length where it has one, else from `count`."""
+        ptrs = [_dev_ptr(a) for a in (creator, self_parent, other_parent, t, data, data_off, data_none, ids, sp_ids, op_ids, arity, sig)]
+        K = count if count is not None else ptrs[0][1]
+        if K is None:
+            raise ValueError("the number of events is not known: pass count=")
+        a = [C.c_void_p(q) if q else None for q, _ in ptrs]
+        self._chk(self._L.sw_sign_events_device(self._h, int(K), a[0], a[1], a[2], a[3], a[4], a[5], int(data_bytes), a[6], a[7], a[8], a[9], a[10], a[11],
+                                                C.c_void_p(int(stream))))
+
+    def create_events(self, creator, self_parent, other_parent, t, data=None, data_off=None, data_none=None, *, want_ids=False):
+        """sign_events, then the append, the id commit and (with a complete data store) the data append (sw_create_events):
+        afterwards the context is in the state ingest_payload(..., data=...) would leave for the same, host-signed events.
+        Atomic on rejection.  Returns the dense index of the first created event; with want_ids (first, ids, sig)."""
+        K, creator, sp, op, t = self._event_arrays(creator, self_parent, other_parent, t)
+        d, off, none, nbytes = (None, None, None, 0) if data is None and data_off is None and data_none is None else self._data_arrays(K, data, data_off, data_none)
+        first = C.c_int64()
+        ids, sig = (np.zeros((K, 32), np.uint8), np.zeros((K, 64), np.uint8)) if want_ids else (None, None)
+        self._chk(self._L.sw_create_events(self._h, K, _p(creator), _p(sp), _p(op), _p(t), _p(d), _p(off), nbytes, _p(none), C.byref(first), _p(ids), _p(sig)))
+        return (int(first.value), ids, sig) if want_ids else int(first.value)
+
+    def create_events_device(self, creator, self_parent, other_parent, t, data=None, data_off=None, data_bytes=0, data_none=None, ids=None, sig=None,
+                             stream=0, count=None):
+        """create_events from arrays in DEVICE memory (sw_create_events_device); ids / sig (optional, 16-byte aligned)
+        receive the batch's ids and signatures.  Returns the dense index of the first created event."""
+        ptrs = [_dev_ptr(a) for a in (creator, self_parent, other_parent, t, data, data_off, data_none, ids, sig)]
+        K = count if count is not None else ptrs[0][1]
+        if K is None:
+            raise ValueError("the number of events is not known: pass count=")
+        a = [C.c_void_p(q) if q else None for q, _ in ptrs]
+        first = C.c_int64()
+        self._chk(self._L.sw_create_events_device(self._h, int(K), a[0], a[1], a[2], a[3], a[4], a[5], int(data_bytes), a[6], C.c_void_p(int(stream)),
+                                                  C.byref(first), a[7], a[8]))
+        return int(first.value)
+
+    def sign_stats(self):
+        """Sign calls and events signed so far, the levels of the last call, key sets, and (under set_profiling) the host
+        milliseconds of the last call's levels + sort, signing and commit."""
+        v = [C.c_int64() for _ in range(4)]
+        ms = (C.c_double * 3)()
+        self._chk(self._L.sw_get_sign_stats(self._h, *[C.byref(x) for x in v], ms))
+        d = dict(zip(("calls", "events", "levels", "key_sets"), (int(x.value) for x in v)))
+        d.update(zip(("levels_ms", "sign_ms", "commit_ms"), (float(x) for x in ms)))
+        return d
+
     def export_stats(self):
         """Export calls and events exported since the context was created, and (under set_profiling) the host
         milliseconds of the most recent call's phases: ranges + count, gather."""
