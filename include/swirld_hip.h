@@ -627,6 +627,65 @@ int sw_get_data_stats(sw_ctx* ctx, int64_t* events, int64_t* bytes, int64_t* sto
                       int64_t* gather_bytes, double* phase_ms);
 
 /*
+ * Answering a sync BY THE PRUNED WALK, forked hashgraphs included (Node.ask_sync swirld.py:148-161; kernels in
+ * csrc/walk.hip.h).  sw_sync_diff describes the answer as one chain range per member and so stops at the
+ * first forked event; these calls run the reference's walk itself — a BFS from the head over the parents that does not
+ * descend below what the asker reported per member (swirld.py:154-161) — and work on the fast AND the exact path.  None of
+ * them changes what an existing call answers; in windowed mode (sw_set_window) all of them return SW_ENOTSUP.
+ *
+ * THE SET (swirld.py:154-161), for ANY heights: head_event is in; a parent p of an included event is in iff
+ * known[creator(p)] < 0 or height(p) > known[creator(p)]; nothing is reached through an excluded event.  `known`: n_members
+ * int32, negative = member unknown to the asker, NULL = the asker knows nobody.  `cap` (may be NULL): n_members int32, every
+ * entry >= -1, INT32_MAX = no cap; the walk prunes at min(known[c], cap[c]), so a cap of -1 sends everything of that member.
+ * Both are the asker's / caller's claim: compared with stored heights, never used as an index.  With real can_see heights
+ * on a fork-free hashgraph the set is sw_sync_diff's; with other heights it is a subset of it (sw_sync_diff's header).
+ * THE ORDER: ascending dense index — deterministic, and topological (parents have lower indices).
+ *
+ * sw_get_fork_trunks   the trunk rule of a forked member (one reported height cannot say which branch the asker holds):
+ *   trunk_out[c] (host, n_members) = the smallest height among the stored events of member c that are the self-parent of
+ *   at least two stored events; -1 if c has at least two roots; INT32_MAX if c has not forked (all INT32_MAX on a fork-free
+ *   context).  Passed as `cap`, it prunes a forked member's events at its earliest fork point.  Either path.
+ *
+ * sw_sync_walk   swirld.py:154-161: the set as dense indices, ascending, in events_out (host).  known, cap in host memory.
+ *   CAPACITY: cap_events is the number of entries events_out can take; a larger set returns SW_ERANGE with *n_out = the
+ *   number required and writes nothing; cap_events = 0 with events_out NULL asks for the size.  Needs NO id index.
+ *
+ * sw_export_walk_device   swirld.py:154-161, 76-95: the set as the arrays sw_ingest_payload_device takes, PER SLOT as
+ *   sw_export_payload_device writes them (id, parents' ids or 32 zero bytes each for a root, arity 2 or 0, creator, d_t,
+ *   d_sig64, d_event; the last three may be NULL), slot s holding the s-th event in ascending dense index.  d_known, d_cap
+ *   and every array in memory of the context's device, the three id arrays and d_sig64 16-byte aligned (SW_EINVAL before
+ *   anything is launched).  CAPACITY as above (cap_events = 0 with all arrays NULL asks for the size).  STREAMS as for
+ *   sw_export_payload_device: the context's stream first waits for what `user_stream` has enqueued, `user_stream` is made to
+ *   wait for the gather; the call synchronises once, to read the count.  NEEDS a complete id index (SW_ENOTSUP), a divided,
+ *   resident head (SW_ERANGE); SW_EIO on a poisoned context, and if the walk meets a table entry out of range (the context
+ *   is poisoned then).  READ-ONLY otherwise (counters.kernel_launches moves).
+ * sw_export_walk   the same with every array in HOST memory.
+ *
+ * sw_sync_pull_walk   swirld.py:125-136 between two contexts on ONE device, as sw_sync_pull_data, with src answering by the
+ *   walk: dst's known heights at dst_head, src's walk at src_head, then — validate != 0 — the signed bytes judged by dst's
+ *   keys (sw_sync_pull_validated), — data != 0 — the events' data from src's store into dst's (sw_sync_pull_data), and dst's
+ *   ingest.  use_trunks != 0: the walk is capped by SRC's fork trunks, which stay on the device — the answerer applies the
+ *   rule.  Either context may be on either path (an exact dst ingests through the host append).  *n_sent, *n_valid (written
+ *   only when validate != 0), *n_stored and the error codes as for sw_sync_pull_data.
+ *
+ * sw_get_walk_stats   walk calls and events named since sw_create, the levels of the most recent walk, and — under
+ *   sw_set_profiling — the host time in ms of the most recent call's phases: phase_ms[3] = walk + count, list, gather.  Any
+ *   pointer may be NULL.
+ */
+int sw_get_fork_trunks(sw_ctx* ctx, int32_t* trunk_out);
+int sw_sync_walk(sw_ctx* ctx, int64_t head_event, const int32_t* known, const int32_t* cap, int64_t cap_events,
+                 int32_t* events_out, int64_t* n_out);
+int sw_export_walk_device(sw_ctx* ctx, int64_t head_event, const int32_t* d_known, const int32_t* d_cap, int64_t cap_events,
+                          uint8_t* d_id32, uint8_t* d_sp_id32, uint8_t* d_op_id32, uint8_t* d_arity, int32_t* d_creator,
+                          double* d_t, uint8_t* d_sig64, int32_t* d_event, void* user_stream, int64_t* n_out);
+int sw_export_walk(sw_ctx* ctx, int64_t head_event, const int32_t* known, const int32_t* cap, int64_t cap_events,
+                   uint8_t* id32, uint8_t* sp_id32, uint8_t* op_id32, uint8_t* arity, int32_t* creator,
+                   double* t, uint8_t* sig64, int32_t* event, int64_t* n_out);
+int sw_sync_pull_walk(sw_ctx* dst, int64_t dst_head, sw_ctx* src, int64_t src_head, int use_trunks, int validate, int data,
+                      int64_t* n_sent, int64_t* n_valid, int64_t* n_stored);
+int sw_get_walk_stats(sw_ctx* ctx, int64_t* calls, int64_t* events, int64_t* levels, double* phase_ms);
+
+/*
  * CREATING signed events on the device (kernels in csrc/sign.hip.h): the producing half of Node.new_event
  * (swirld.py:82-95) for K events at once — the Ed25519 signature over dumps((d, p, t, pk)) and the id
  * crypto_generichash(dumps(ev)), bit for bit what libsodium, pickle and hashlib give, from the same index arrays

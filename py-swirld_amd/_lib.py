@@ -113,7 +113,14 @@ SIGNATURES = {
     "sw_ingest_payload_data": (C.c_int, [_P, C.c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.POINTER(C.c_int64), _P, _P, C.c_int64, _P]),
     "sw_sync_pull_data": (C.c_int, [_P, C.c_int64, _P, C.c_int64, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "sw_get_data_stats": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), _P]),
-    "sw_set_signing_keys": (C.c_int, [_P, C.c_int64, _P, _P]),
+    "sw_get_fork_trunks": (C.c_int, [_P, _P]),
+    "sw_sync_walk": (C.c_int, [_P, C.c_int64, _P, _P, C.c_int64, _P, C.POINTER(C.c_int64)]),
+    "sw_export_walk_device": (C.c_int, [_P, C.c_int64, _P, _P, C.c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.POINTER(C.c_int64)]),
+    "sw_export_walk": (C.c_int, [_P, C.c_int64, _P, _P, C.c_int64, _P, _P, _P, _P, _P, _P, _P, _P, C.POINTER(C.c_int64)]),
+    "sw_sync_pull_walk": (C.c_int, [_P, C.c_int64, _P, C.c_int64, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                                    C.POINTER(C.c_int64)]),
+    "sw_get_walk_stats": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), _P]),
+    "sw_set_signing_keys":(C.c_int, [_P, C.c_int64, _P, _P]),
     "sw_clear_signing_keys": (C.c_int, [_P]),
     "sw_get_signing_members": (C.c_int, [_P, _P]),
     "sw_sign_events_device": (C.c_int, [_P, C.c_int64, _P, _P, _P, _P, _P, _P, C.c_int64, _P, _P, _P, _P, _P, _P, _P]),

@@ -30,6 +30,7 @@
 #include "ingest.hip.h"
 #include "resolve.hip.h"
 #include "gossip.hip.h"
+#include "walk.hip.h"
 #include "consensus.hip.h"
 
 namespace {
@@ -180,6 +181,18 @@ struct sw_ctx {
     int64_t xp_calls = 0, xp_events = 0;   // sw_get_export_stats
     double xp_ms[2] = {0, 0};     // ... host time of the most recent call's phases under sw_set_profiling: ranges + count, gather
     int export_lanes = 16;        // SW_EXPORT_LANES (measurement knob, read at sw_create): lanes of a wave that share one output slot — 4, 8 or 16
+    // answering a sync by the pruned walk, forked hashgraphs included (sw_sync_walk, sw_export_walk[_device], sw_sync_pull_walk,
+    // sw_get_fork_trunks; walk.hip.h)
+    DBuf<int32_t> d_wk;           // [wlk::H_WORDS: the header][npad: the asker's heights][npad: the cap]
+    DBuf<unsigned> d_wk_bits;     // the visited bitmap: head + 1 bits
+    DBuf<int32_t> d_wk_q;         // the queue of the frontiers: head + 1 entries
+    DBuf<int32_t> d_wk_list;      // the ascending list: head + 1 entries
+    DBuf<int32_t> d_wk_trunk;     // [npad: trunk per member][npad: roots per member], as of wk_trunk_N events
+    DBuf<int32_t> d_wk_children;  // children per self-parent (scratch of k_fork_trunks)
+    int64_t wk_trunk_N = -1;      // events d_wk_trunk was computed from (-1: never; sw_reset forgets it)
+    int walk_threads = 1024;      // SW_WALK_THREADS (read at sw_create): workgroup size of k_walk_bfs, a multiple of 64 up to 1024
+    int64_t wk_calls = 0, wk_events = 0, wk_levels = 0;   // sw_get_walk_stats (levels: the last call's)
+    double wk_ms[3] = {0, 0, 0};  // ... host time of the most recent call's phases under sw_set_profiling: walk + count, list, gather
     // what find_order decided per event, kept (sw_get_round_received, sw_get_consensus_time, sw_export_ordered[_device];
     // consensus.hip.h): allocated by the first find_order call that orders something
     DBuf<int32_t> d_rr;           // per event: round received (swirld.py:283); entries of events that are not ordered are unspecified
@@ -2991,6 +3004,7 @@ int sw_create(int n_members, const uint64_t* stake, int coin_period, int device,
         else (void)hipMemset(c->d_flow_dbg, 0, 8 * sizeof(u64));
     }
     if (const char* e_ = getenv("SW_EXPORT_LANES")) { const int g = atoi(e_); if (g == 4 || g == 8) c->export_lanes = g; }
+    if (const char* e_ = getenv("SW_WALK_THREADS")) { const int w = atoi(e_); if (w >= 64 && w <= wlk::MAX_THREADS && w % 64 == 0) c->walk_threads = w; }
     if (getenv("SW_DEBUG_CLOCKS")) {  // diagnostics: phase stamps of the round-loop kernels
         c->dbg_minor = atoi(getenv("SW_DEBUG_CLOCKS")) >= 2 ? 0 : 1;
         if (atoi(getenv("SW_DEBUG_CLOCKS")) == 3) {
@@ -3178,6 +3192,7 @@ int sw_destroy(sw_ctx* c) {
     dfree(c->d_ing_tab); dfree(c->d_ing_hist); dfree(c->d_ht_stat);
     dfree(c->d_id); dfree(c->d_idtab); dfree(c->d_idflag); dfree(c->d_pl); dfree(c->d_pl_in);
     dfree(c->d_xp); dfree(c->d_xp_out);
+    dfree(c->d_wk); dfree(c->d_wk_bits); dfree(c->d_wk_q); dfree(c->d_wk_list); dfree(c->d_wk_trunk); dfree(c->d_wk_children);
     dfree(c->d_rr); dfree(c->d_cts); dfree(c->d_tx); dfree(c->d_cs_ordpos); dfree(c->d_cs_out);
     dfree(c->d_vkeys); dfree(c->d_vtab); dfree(c->d_v_in);
     dfree(c->d_pk_hdr); dfree(c->d_pk); dfree(c->d_pk_in); dfree(c->d_pk_out);
@@ -4671,6 +4686,7 @@ int sw_reset(sw_ctx* c) {
     c->n_ids = 0;   // the ids go with the events (the table keeps its size and is emptied)
     c->n_data = 0;  // ... and so does their data (the arena keeps its size)
     c->data_used = 0;
+    c->wk_trunk_N = -1;   // (the trunk heights were those of the forgotten events)
     if (c->idtab_log) HIPCHK(c, hipMemsetAsync(c->d_idtab.p, 0xff, sizeof(int32_t) << c->idtab_log, c->stream));
     c->exact = false;  // (a fresh hashgraph starts on the fast path again)
     c->chunks_off = false;  // ... and with the chunked sweep
@@ -5009,6 +5025,13 @@ namespace {
 
 struct ExportArrays { uint8_t *id, *sp_id, *op_id, *arity; int32_t* creator; double* t; uint8_t* sig; int32_t* event; };
 
+// the parts every sw_sync_pull* shares (defined behind the data store's functions, which the last of them needs)
+int pull_pre(sw_ctx* dst, int64_t dst_head, sw_ctx* src, bool validate, bool data, const char* what);
+int pull_begin(sw_ctx* dst, int64_t dst_head, sw_ctx* src, bool validate, bool data, const char* what);
+int pull_ranges(sw_ctx* dst, sw_ctx* src, int64_t src_head, bool with_event, const char* what, int64_t* total, ExportArrays* d);
+int pull_finish(sw_ctx* dst, sw_ctx* src, int64_t total, const ExportArrays& d, bool validate, bool data, const char* what, int64_t* n_valid,
+                int64_t* n_stored);
+
 // what both forms and sw_sync_pull ask of the answering context
 int export_pre(sw_ctx* c, int64_t head, const char* what) {
     if (c->poisoned) return fail(c, SW_EIO, "context unusable after an earlier device failure");
@@ -5191,52 +5214,18 @@ int sw_sync_pull(sw_ctx* dst, int64_t dst_head, sw_ctx* src, int64_t src_head, i
     if (!dst || !src) return SW_EINVAL;
     if (n_sent) *n_sent = 0;
     if (n_stored) *n_stored = 0;
-    if (dst == src) return fail(dst, SW_EINVAL, "sw_sync_pull: a context cannot pull from itself");
-    if (dst->device != src->device) return fail(dst, SW_ENOTSUP, "sw_sync_pull: the contexts live on devices %d and %d (same device only)", dst->device, src->device);
-    if (dst->n != src->n) return fail(dst, SW_EINVAL, "sw_sync_pull: %d members here, %d at the peer", dst->n, src->n);
-    if (dst->poisoned) return fail(dst, SW_EIO, "context unusable after an earlier device failure");
-    if (dst->n_ids != dst->N)
-        return fail(dst, SW_ENOTSUP, "sw_sync_pull: %lld of the %lld stored events have no id (sw_set_event_ids first)", (long long)(dst->N - dst->n_ids), (long long)dst->N);
-    if (dst_head < dst->first_resident || dst_head >= dst->divided) return fail(dst, SW_ERANGE, "sw_sync_pull: head %lld is not a divided, resident event", (long long)dst_head);
+    const char* what = "sw_sync_pull";
+    CHK(pull_pre(dst, dst_head, src, false, false, what));
     if (const int rc = export_pre(src, src_head, "sw_sync_pull (peer)"); rc != SW_OK) { dst->err = src->err; return rc; }
-    HIPCHK(dst, hipSetDevice(dst->device));
     // ---- 1. what dst knows at its head (swirld.py:125-126), left in its own scratch; src's stream waits for it
-    CHK(heights_on_device(dst));
-    const int np = dst->npad;
-    CHK(dgrow(dst, dst->d_q, (size_t)3 * np, 0));
-    if (!dst->ev_user) HIPCHK(dst, hipEventCreateWithFlags(&dst->ev_user, hipEventDisableTiming));
-    hipLaunchKernelGGL(k_known_heights, dim3(1), dim3(np), 0, dst->stream, (const int*)dst->d_L.p, (const int*)dst->d_ht.p, (int)dst_head, np, dst->d_q.p);
-    dst->ctr.kernel_launches++;
-    HIPCHK(dst, hipGetLastError());
-    HIPCHK(dst, hipEventRecord(dst->ev_user, dst->stream));
-    HIPCHK(dst, hipStreamWaitEvent(src->stream, dst->ev_user, 0));
+    CHK(pull_begin(dst, dst_head, src, false, false, what));
     // ---- 2. src: ranges, count (its one synchronisation: dst's heights have been consumed by then), gather into its own scratch
-    const bool prof = src->profiling;
-    auto t0 = std::chrono::steady_clock::now();
     int64_t total = 0;
-    if (const int rc = export_ranges(src, src_head, dst->d_q.p, hipMemcpyDeviceToDevice, &total); rc != SW_OK) { dst->err = src->err; return rc; }
-    src->xp_ms[0] = prof ? ms_since(t0) : 0;
-    src->xp_ms[1] = 0;
-    if (total > 0x3fffffffll || dst->N + total > 0x7ffffff0ll) return fail(dst, SW_ERANGE, "sw_sync_pull: more than 2^31 events");
-    t0 = std::chrono::steady_clock::now();
     ExportArrays d{};
-    int rc = export_scratch(src, total, true, true, false, &d);
-    if (rc == SW_OK) rc = export_gather(src, total, d);
-    if (rc != SW_OK) { dst->err = src->err; return rc; }
-    if (prof) { HIPCHK(src, hipStreamSynchronize(src->stream)); src->xp_ms[1] = ms_since(t0); }
-    src->xp_calls++;
-    src->xp_events += total;
+    CHK(pull_ranges(dst, src, src_head, false, what, &total, &d));
     if (n_sent) *n_sent = total;
     // ---- 3. dst ingests (Node.sync's loop, swirld.py:130-136), its stream ordered behind src's
-    CHK(dgrow(dst, dst->d_pl_in, (size_t)total * sizeof(int32_t), 0));
-    int64_t stored = 0;
-    rc = payload_core(dst, total, d.id, d.sp_id, d.op_id, d.arity, d.creator, nullptr, d.t, d.sig, src->stream, (int32_t*)dst->d_pl_in.p, &stored);
-    // src's scratch is free again only once dst has read it
-    const hipError_t drained = hipStreamSynchronize(dst->stream);
-    if (rc != SW_OK) return rc;
-    HIPCHK(dst, drained);
-    if (n_stored) *n_stored = stored;
-    return SW_OK;
+    return pull_finish(dst, src, total, d, false, false, what, nullptr, n_stored);
 }
 
 int sw_get_export_stats(sw_ctx* c, int64_t* calls, int64_t* events, double* phase_ms) {
@@ -5873,84 +5862,17 @@ int sw_sync_pull_validated(sw_ctx* dst, int64_t dst_head, sw_ctx* src, int64_t s
     if (n_sent) *n_sent = 0;
     if (n_valid) *n_valid = 0;
     if (n_stored) *n_stored = 0;
-    if (dst == src) return fail(dst, SW_EINVAL, "%s: a context cannot pull from itself", what);
-    if (dst->device != src->device) return fail(dst, SW_ENOTSUP, "%s: the contexts live on devices %d and %d (same device only)", what, dst->device, src->device);
-    if (dst->n != src->n) return fail(dst, SW_EINVAL, "%s: %d members here, %d at the peer", what, dst->n, src->n);
-    if (dst->poisoned) return fail(dst, SW_EIO, "context unusable after an earlier device failure");
-    if (dst->vkeys.empty()) return fail(dst, SW_ENOTSUP, "%s: no member keys (sw_set_member_keys first)", what);
-    if (dst->n_ids != dst->N)
-        return fail(dst, SW_ENOTSUP, "%s: %lld of the %lld stored events have no id (sw_set_event_ids first)", what, (long long)(dst->N - dst->n_ids), (long long)dst->N);
-    if (dst_head < dst->first_resident || dst_head >= dst->divided) return fail(dst, SW_ERANGE, "%s: head %lld is not a divided, resident event", what, (long long)dst_head);
+    CHK(pull_pre(dst, dst_head, src, true, false, what));
     if (const int rc = export_pre(src, src_head, "sw_sync_pull_validated (peer)"); rc != SW_OK) { dst->err = src->err; return rc; }
-    HIPCHK(dst, hipSetDevice(dst->device));
-    if (!dst->h_pkcnt && hipHostMalloc((void**)&dst->h_pkcnt, sizeof(int32_t), hipHostMallocDefault) != hipSuccess) {
-        (void)hipGetLastError();
-        dst->h_pkcnt = nullptr;
-        return fail(dst, SW_ENOMEM, "hipHostMalloc for the count of valid events failed");
-    }
     // ---- 1. and 2. as in sw_sync_pull: dst's known heights, src's ranges, count and gather
-    CHK(heights_on_device(dst));
-    const int np = dst->npad;
-    CHK(dgrow(dst, dst->d_q, (size_t)3 * np, 0));
-    if (!dst->ev_user) HIPCHK(dst, hipEventCreateWithFlags(&dst->ev_user, hipEventDisableTiming));
-    hipLaunchKernelGGL(k_known_heights, dim3(1), dim3(np), 0, dst->stream, (const int*)dst->d_L.p, (const int*)dst->d_ht.p, (int)dst_head, np, dst->d_q.p);
-    dst->ctr.kernel_launches++;
-    HIPCHK(dst, hipGetLastError());
-    HIPCHK(dst, hipEventRecord(dst->ev_user, dst->stream));
-    HIPCHK(dst, hipStreamWaitEvent(src->stream, dst->ev_user, 0));
-    const bool prof = src->profiling;
-    auto t0 = std::chrono::steady_clock::now();
+    CHK(pull_begin(dst, dst_head, src, true, false, what));
     int64_t total = 0;
-    if (const int rc = export_ranges(src, src_head, dst->d_q.p, hipMemcpyDeviceToDevice, &total); rc != SW_OK) { dst->err = src->err; return rc; }
-    src->xp_ms[0] = prof ? ms_since(t0) : 0;
-    src->xp_ms[1] = 0;
-    if (total > 0x3fffffffll || dst->N + total > 0x7ffffff0ll) return fail(dst, SW_ERANGE, "%s: more than 2^31 events", what);
-    t0 = std::chrono::steady_clock::now();
     ExportArrays d{};
-    int rc = export_scratch(src, total, true, true, false, &d);
-    if (rc == SW_OK) rc = export_gather(src, total, d);
-    if (rc != SW_OK) { dst->err = src->err; return rc; }
-    if (prof) { HIPCHK(src, hipStreamSynchronize(src->stream)); src->xp_ms[1] = ms_since(t0); }
-    src->xp_calls++;
-    src->xp_events += total;
+    CHK(pull_ranges(dst, src, src_head, false, what, &total, &d));
     if (n_sent) *n_sent = total;
-    // ---- 3. dst, its stream ordered behind src's: the signed bytes (data None: the context stores no event data), the
-    // verdicts by dst's OWN keys and event class, ANDed with the encodable flags and counted
-    const size_t k = (size_t)total;
-    int64_t bm = 0, bw = 0;
-    pack_bound(dst, total, 0, &bm, &bw);
-    Carve cv;
-    const size_t o_moff = cv.take((k + 1) * 8), o_woff = cv.take((k + 1) * 8), o_m = cv.take((size_t)bm), o_w = cv.take((size_t)bw);
-    const size_t o_enc = cv.take(k), o_ok = cv.take(k), o_cnt = cv.take(sizeof(int32_t));
-    CHK(dgrow(dst, dst->d_pk_out, cv.off + 256, 0));
-    CHK(dgrow(dst, dst->d_pl_in, k * sizeof(int32_t), 0));
-    unsigned char* B = dst->d_pk_out.p;
-    HIPCHK(dst, hipEventRecord(dst->ev_user, src->stream));
-    HIPCHK(dst, hipStreamWaitEvent(dst->stream, dst->ev_user, 0));
-    HIPCHK(dst, hipMemsetAsync(B + o_cnt, 0, sizeof(int32_t), dst->stream));
-    rc = pack_launch(dst, total, PackArrays{d.sp_id, d.op_id, d.arity, d.creator, d.t, d.sig, nullptr, nullptr, 0, nullptr, B + o_m, (int64_t*)(B + o_moff),
-                                            B + o_w, (int64_t*)(B + o_woff), B + o_enc}, bm, bw);
-    if (rc == SW_OK) {
-        const swv::Payload p{B + o_m, (const long long*)(B + o_moff), (long long)bm, B + o_w, (const long long*)(B + o_woff), (long long)bw, d.sig, d.creator, d.id};
-        rc = validate_launch(dst, total, p, B + o_ok);
-    }
-    if (rc != SW_OK) { (void)hipStreamSynchronize(dst->stream); return rc; }   // (src's scratch is free again only once dst has read it)
-    dst->v_calls++;
-    dst->v_events += total;
-    hipLaunchKernelGGL(pck::k_pack_and_count, dim3((unsigned)std::min<int64_t>(1024, (total + 255) / 256)), dim3(256), 0, dst->stream, (pck::i64)total,
-                       B + o_ok, (const unsigned char*)(B + o_enc), (int*)(B + o_cnt));
-    dst->ctr.kernel_launches++;
-    HIPCHK(dst, hipGetLastError());
-    HIPCHK(dst, hipMemcpyAsync(dst->h_pkcnt, B + o_cnt, sizeof(int32_t), hipMemcpyDeviceToHost, dst->stream));
-    // ---- 4. dst ingests what is valid (Node.sync's loop, swirld.py:130-136)
-    int64_t stored = 0;
-    rc = payload_core(dst, total, d.id, d.sp_id, d.op_id, d.arity, d.creator, B + o_ok, d.t, d.sig, src->stream, (int32_t*)dst->d_pl_in.p, &stored);
-    const hipError_t drained = hipStreamSynchronize(dst->stream);
-    if (rc != SW_OK) return rc;
-    HIPCHK(dst, drained);
-    if (n_valid) *n_valid = *dst->h_pkcnt;
-    if (n_stored) *n_stored = stored;
-    return SW_OK;
+    // ---- 3. and 4. dst, its stream ordered behind src's: the signed bytes (data None: the context stores no event data), the
+    // verdicts by dst's OWN keys and event class, and the ingest of what is valid (Node.sync's loop, swirld.py:130-136)
+    return pull_finish(dst, src, total, d, true, false, what, n_valid, n_stored);
 }
 
 int sw_get_pack_stats(sw_ctx* c, int64_t* calls, int64_t* events, int64_t* bytes, double* phase_ms) {
@@ -6341,12 +6263,12 @@ int sw_ingest_payload_data(sw_ctx* c, int64_t K, const uint8_t* id32, const uint
     return SW_OK;
 }
 
-int sw_sync_pull_data(sw_ctx* dst, int64_t dst_head, sw_ctx* src, int64_t src_head, int validate, int64_t* n_sent, int64_t* n_valid, int64_t* n_stored) {
-    if (!dst || !src) return SW_EINVAL;
-    const char* what = "sw_sync_pull_data";
-    if (n_sent) *n_sent = 0;
-    if (n_valid) *n_valid = 0;
-    if (n_stored) *n_stored = 0;
+}  // extern "C"
+namespace {
+
+// ---- the parts sw_sync_pull, sw_sync_pull_validated, sw_sync_pull_data and sw_sync_pull_walk share --------------------------
+// what they ask of the pulling context, and of the pair
+int pull_pre(sw_ctx* dst, int64_t dst_head, sw_ctx* src, bool validate, bool data, const char* what) {
     if (dst == src) return fail(dst, SW_EINVAL, "%s: a context cannot pull from itself", what);
     if (dst->device != src->device) return fail(dst, SW_ENOTSUP, "%s: the contexts live on devices %d and %d (same device only)", what, dst->device, src->device);
     if (dst->n != src->n) return fail(dst, SW_EINVAL, "%s: %d members here, %d at the peer", what, dst->n, src->n);
@@ -6354,11 +6276,16 @@ int sw_sync_pull_data(sw_ctx* dst, int64_t dst_head, sw_ctx* src, int64_t src_he
     if (validate && dst->vkeys.empty()) return fail(dst, SW_ENOTSUP, "%s: no member keys (sw_set_member_keys first)", what);
     if (dst->n_ids != dst->N)
         return fail(dst, SW_ENOTSUP, "%s: %lld of the %lld stored events have no id (sw_set_event_ids first)", what, (long long)(dst->N - dst->n_ids), (long long)dst->N);
-    if (dst->n_data != dst->N)
+    if (data && dst->n_data != dst->N)
         return fail(dst, SW_ENOTSUP, "%s: %lld of the %lld stored events have no data entry (sw_set_event_data first)", what, (long long)(dst->N - dst->n_data), (long long)dst->N);
     if (dst_head < dst->first_resident || dst_head >= dst->divided) return fail(dst, SW_ERANGE, "%s: head %lld is not a divided, resident event", what, (long long)dst_head);
-    if (const int rc = export_pre(src, src_head, "sw_sync_pull_data (peer)"); rc != SW_OK) { dst->err = src->err; return rc; }
-    if (src->n_data != src->N)
+    return SW_OK;
+}
+
+// behind the checks of the answering context: what dst knows at its head (swirld.py:125-126), left in its own scratch
+// (dst->d_q); src's stream waits for it
+int pull_begin(sw_ctx* dst, int64_t dst_head, sw_ctx* src, bool validate, bool data, const char* what) {
+    if (data && src->n_data != src->N)
         return fail(dst, SW_ENOTSUP, "%s: %lld of the peer's %lld stored events have no data entry (sw_set_event_data first)", what, (long long)(src->N - src->n_data), (long long)src->N);
     HIPCHK(dst, hipSetDevice(dst->device));
     if (validate && !dst->h_pkcnt && hipHostMalloc((void**)&dst->h_pkcnt, sizeof(int32_t), hipHostMallocDefault) != hipSuccess) {
@@ -6366,7 +6293,6 @@ int sw_sync_pull_data(sw_ctx* dst, int64_t dst_head, sw_ctx* src, int64_t src_he
         dst->h_pkcnt = nullptr;
         return fail(dst, SW_ENOMEM, "hipHostMalloc for the count of valid events failed");
     }
-    // ---- 1. and 2. as in sw_sync_pull: dst's known heights, src's ranges, count and gather (with the dense indices)
     CHK(heights_on_device(dst));
     const int np = dst->npad;
     CHK(dgrow(dst, dst->d_q, (size_t)3 * np, 0));
@@ -6376,6 +6302,12 @@ int sw_sync_pull_data(sw_ctx* dst, int64_t dst_head, sw_ctx* src, int64_t src_he
     HIPCHK(dst, hipGetLastError());
     HIPCHK(dst, hipEventRecord(dst->ev_user, dst->stream));
     HIPCHK(dst, hipStreamWaitEvent(src->stream, dst->ev_user, 0));
+    return SW_OK;
+}
+
+// src answers with the chain ranges of k_sync_diff: ranges, count (its one synchronisation: dst's heights have been consumed
+// by then), gather into its own scratch
+int pull_ranges(sw_ctx* dst, sw_ctx* src, int64_t src_head, bool with_event, const char* what, int64_t* total_out, ExportArrays* d) {
     const bool prof = src->profiling;
     auto t0 = std::chrono::steady_clock::now();
     int64_t total = 0;
@@ -6384,79 +6316,354 @@ int sw_sync_pull_data(sw_ctx* dst, int64_t dst_head, sw_ctx* src, int64_t src_he
     src->xp_ms[1] = 0;
     if (total > 0x3fffffffll || dst->N + total > 0x7ffffff0ll) return fail(dst, SW_ERANGE, "%s: more than 2^31 events", what);
     t0 = std::chrono::steady_clock::now();
-    ExportArrays d{};
-    int rc = export_scratch(src, total, true, true, true, &d);
-    if (rc == SW_OK) rc = export_gather(src, total, d);
+    int rc = export_scratch(src, total, true, true, with_event, d);
+    if (rc == SW_OK) rc = export_gather(src, total, *d);
     if (rc != SW_OK) { dst->err = src->err; return rc; }
     if (prof) { HIPCHK(src, hipStreamSynchronize(src->stream)); src->xp_ms[1] = ms_since(t0); }
     src->xp_calls++;
     src->xp_events += total;
-    if (n_sent) *n_sent = total;
-    // ---- 3. src: the data of those events beside the other arrays (its second synchronisation: the byte total)
+    *total_out = total;
+    return SW_OK;
+}
+
+// behind src's export of `total` events into `d` (its scratch, written on its stream):
+//   data      src gathers the data of those events beside the other arrays (its second synchronisation: the byte total)
+//   validate  dst, its stream ordered behind src's, builds the signed bytes (with the data, or with data None), judges them by
+//             its OWN keys and event class, ANDs the verdicts with the encodable flags and counts them
+//   then      dst ingests what is valid (Node.sync's loop, swirld.py:130-136), on the exact path through the host append
+int pull_finish(sw_ctx* dst, sw_ctx* src, int64_t total, const ExportArrays& d, bool validate, bool data, const char* what, int64_t* n_valid,
+                int64_t* n_stored) {
     const size_t k = (size_t)total;
-    DataPlan sp{};
-    int64_t dbytes = 0, bad = 0;
-    const dat::SegIn sin{src->d_data.p, (const dat::i64*)src->d_data_off.p, src->d_data_none.p, d.event, (dat::i64)src->n_data, (dat::i64)src->data_used, 1};
-    rc = data_scratch(src, total, 0, 0, &sp);
-    if (rc == SW_OK) rc = data_plan(src, total, sin, sp, &dbytes, &bad);
-    if (rc == SW_OK && bad) rc = fail(src, SW_EIO, "%s: %lld exported events without data (internal error)", what, (long long)bad);
-    Carve sv;
-    const size_t s_d = sv.take((size_t)dbytes + 16), s_off = sv.take((k + 1) * 8), s_n = sv.take(k);
-    if (rc == SW_OK) rc = dgrow(src, src->d_dt_out, sv.off + 256, 0);
-    unsigned char* S = src->d_dt_out.p;
-    if (rc == SW_OK) rc = data_copy(src, total, sin, sp, dbytes, S + s_d, 0, 0, (int64_t*)(S + s_off), S + s_n);
-    if (rc != SW_OK) { dst->err = src->err; return rc; }
-    src->dt_gather_calls++;
-    src->dt_gather_bytes += dbytes;
-    const uint8_t* x_data = S + s_d;
-    const int64_t* x_off = (const int64_t*)(S + s_off);
-    const uint8_t* x_none = S + s_n;
+    int rc = SW_OK;
+    int64_t dbytes = 0;
+    const uint8_t* x_data = nullptr;
+    const int64_t* x_off = nullptr;
+    const uint8_t* x_none = nullptr;
+    if (data) {
+        DataPlan sp{};
+        int64_t bad = 0;
+        const dat::SegIn sin{src->d_data.p, (const dat::i64*)src->d_data_off.p, src->d_data_none.p, d.event, (dat::i64)src->n_data, (dat::i64)src->data_used, 1};
+        rc = data_scratch(src, total, 0, 0, &sp);
+        if (rc == SW_OK) rc = data_plan(src, total, sin, sp, &dbytes, &bad);
+        if (rc == SW_OK && bad) rc = fail(src, SW_EIO, "%s: %lld exported events without data (internal error)", what, (long long)bad);
+        Carve sv;
+        const size_t s_d = sv.take((size_t)dbytes + 16), s_off = sv.take((k + 1) * 8), s_n = sv.take(k);
+        if (rc == SW_OK) rc = dgrow(src, src->d_dt_out, sv.off + 256, 0);
+        unsigned char* S = src->d_dt_out.p;
+        if (rc == SW_OK) rc = data_copy(src, total, sin, sp, dbytes, S + s_d, 0, 0, (int64_t*)(S + s_off), S + s_n);
+        if (rc != SW_OK) { dst->err = src->err; return rc; }
+        src->dt_gather_calls++;
+        src->dt_gather_bytes += dbytes;
+        x_data = S + s_d;
+        x_off = (const int64_t*)(S + s_off);
+        x_none = S + s_n;
+    }
     CHK(dgrow(dst, dst->d_pl_in, k * sizeof(int32_t), 0));
+    const uint8_t* ok = nullptr;
+    if (validate) {
+        int64_t bm = 0, bw = 0;
+        pack_bound(dst, total, dbytes, &bm, &bw);
+        Carve cv;
+        const size_t o_moff = cv.take((k + 1) * 8), o_woff = cv.take((k + 1) * 8), o_m = cv.take((size_t)bm), o_w = cv.take((size_t)bw);
+        const size_t o_enc = cv.take(k), o_ok = cv.take(k), o_cnt = cv.take(sizeof(int32_t));
+        CHK(dgrow(dst, dst->d_pk_out, cv.off + 256, 0));
+        unsigned char* B = dst->d_pk_out.p;
+        HIPCHK(dst, hipEventRecord(dst->ev_user, src->stream));
+        HIPCHK(dst, hipStreamWaitEvent(dst->stream, dst->ev_user, 0));
+        HIPCHK(dst, hipMemsetAsync(B + o_cnt, 0, sizeof(int32_t), dst->stream));
+        rc = pack_launch(dst, total, PackArrays{d.sp_id, d.op_id, d.arity, d.creator, d.t, d.sig, x_data, x_off, dbytes, x_none, B + o_m, (int64_t*)(B + o_moff),
+                                                B + o_w, (int64_t*)(B + o_woff), B + o_enc}, bm, bw);
+        if (rc == SW_OK) {
+            const swv::Payload p{B + o_m, (const long long*)(B + o_moff), (long long)bm, B + o_w, (const long long*)(B + o_woff), (long long)bw, d.sig, d.creator, d.id};
+            rc = validate_launch(dst, total, p, B + o_ok);
+        }
+        if (rc != SW_OK) { (void)hipStreamSynchronize(dst->stream); return rc; }   // (src's scratch is free again only once dst has read it)
+        dst->v_calls++;
+        dst->v_events += total;
+        hipLaunchKernelGGL(pck::k_pack_and_count, dim3((unsigned)std::min<int64_t>(1024, (total + 255) / 256)), dim3(256), 0, dst->stream, (pck::i64)total,
+                           B + o_ok, (const unsigned char*)(B + o_enc), (int*)(B + o_cnt));
+        dst->ctr.kernel_launches++;
+        HIPCHK(dst, hipGetLastError());
+        HIPCHK(dst, hipMemcpyAsync(dst->h_pkcnt, B + o_cnt, sizeof(int32_t), hipMemcpyDeviceToHost, dst->stream));
+        ok = B + o_ok;
+    }
     int64_t stored = 0;
-    if (!validate) {
-        rc = ingest_data_core(dst, total, d.id, d.sp_id, d.op_id, d.arity, d.creator, nullptr, d.t, d.sig, x_data, x_off, dbytes, x_none, src->stream,
+    if (data)
+        rc = ingest_data_core(dst, total, d.id, d.sp_id, d.op_id, d.arity, d.creator, ok, d.t, d.sig, x_data, x_off, dbytes, x_none, src->stream,
                               (int32_t*)dst->d_pl_in.p, &stored);
-        const hipError_t drained = hipStreamSynchronize(dst->stream);   // src's scratch is free again only once dst has read it
-        if (rc != SW_OK) return rc;
-        HIPCHK(dst, drained);
-        if (n_stored) *n_stored = stored;
-        return SW_OK;
-    }
-    // ---- 4. dst, its stream ordered behind src's: the signed bytes WITH the data, the verdicts by dst's own keys and
-    // event class, ANDed with the encodable flags and counted
-    int64_t bm = 0, bw = 0;
-    pack_bound(dst, total, dbytes, &bm, &bw);
-    Carve cv;
-    const size_t o_moff = cv.take((k + 1) * 8), o_woff = cv.take((k + 1) * 8), o_m = cv.take((size_t)bm), o_w = cv.take((size_t)bw);
-    const size_t o_enc = cv.take(k), o_ok = cv.take(k), o_cnt = cv.take(sizeof(int32_t));
-    CHK(dgrow(dst, dst->d_pk_out, cv.off + 256, 0));
-    unsigned char* B = dst->d_pk_out.p;
-    HIPCHK(dst, hipEventRecord(dst->ev_user, src->stream));
-    HIPCHK(dst, hipStreamWaitEvent(dst->stream, dst->ev_user, 0));
-    HIPCHK(dst, hipMemsetAsync(B + o_cnt, 0, sizeof(int32_t), dst->stream));
-    rc = pack_launch(dst, total, PackArrays{d.sp_id, d.op_id, d.arity, d.creator, d.t, d.sig, x_data, x_off, dbytes, x_none, B + o_m, (int64_t*)(B + o_moff),
-                                            B + o_w, (int64_t*)(B + o_woff), B + o_enc}, bm, bw);
-    if (rc == SW_OK) {
-        const swv::Payload p{B + o_m, (const long long*)(B + o_moff), (long long)bm, B + o_w, (const long long*)(B + o_woff), (long long)bw, d.sig, d.creator, d.id};
-        rc = validate_launch(dst, total, p, B + o_ok);
-    }
-    if (rc != SW_OK) { (void)hipStreamSynchronize(dst->stream); return rc; }
-    dst->v_calls++;
-    dst->v_events += total;
-    hipLaunchKernelGGL(pck::k_pack_and_count, dim3((unsigned)std::min<int64_t>(1024, (total + 255) / 256)), dim3(256), 0, dst->stream, (pck::i64)total,
-                       B + o_ok, (const unsigned char*)(B + o_enc), (int*)(B + o_cnt));
-    dst->ctr.kernel_launches++;
-    HIPCHK(dst, hipGetLastError());
-    HIPCHK(dst, hipMemcpyAsync(dst->h_pkcnt, B + o_cnt, sizeof(int32_t), hipMemcpyDeviceToHost, dst->stream));
-    // ---- 5. dst ingests what is valid, with its data
-    rc = ingest_data_core(dst, total, d.id, d.sp_id, d.op_id, d.arity, d.creator, B + o_ok, d.t, d.sig, x_data, x_off, dbytes, x_none, src->stream,
-                          (int32_t*)dst->d_pl_in.p, &stored);
-    const hipError_t drained = hipStreamSynchronize(dst->stream);
+    else
+        rc = payload_core(dst, total, d.id, d.sp_id, d.op_id, d.arity, d.creator, ok, d.t, d.sig, src->stream, (int32_t*)dst->d_pl_in.p, &stored);
+    const hipError_t drained = hipStreamSynchronize(dst->stream);   // src's scratch is free again only once dst has read it
     if (rc != SW_OK) return rc;
     HIPCHK(dst, drained);
-    if (n_valid) *n_valid = *dst->h_pkcnt;
+    if (validate && n_valid) *n_valid = *dst->h_pkcnt;
     if (n_stored) *n_stored = stored;
     return SW_OK;
+}
+
+// ---- answering a sync by the pruned walk (walk.hip.h) ------------------------------------------------------
+// what every walk call asks of the answering context: either path, but every can_see row resident
+int walk_pre(sw_ctx* c, int64_t head, bool need_ids, const char* what) {
+    if (c->poisoned) return fail(c, SW_EIO, "context unusable after an earlier device failure");
+    if (c->vm.active) return fail(c, SW_ENOTSUP, "%s is not available with the windowed table", what);
+    if (need_ids && c->n_ids != c->N)
+        return fail(c, SW_ENOTSUP, "%s: %lld of the %lld stored events have no id (sw_set_event_ids first)", what, (long long)(c->N - c->n_ids), (long long)c->N);
+    if (head < c->first_resident || head >= c->divided || head >= c->N)
+        return fail(c, SW_ERANGE, "%s: head %lld is not a divided, resident event", what, (long long)head);
+    return SW_OK;
+}
+
+// trunk[c] of every member as of the stored events, in d_wk_trunk, on the context's stream (asynchronous).  Recomputed only
+// when events have arrived since.
+int fork_trunks(sw_ctx* c) {
+    const int np = c->npad;
+    CHK(dgrow(c, c->d_wk_trunk, (size_t)2 * np, 0));
+    if (c->wk_trunk_N == c->N) return SW_OK;
+    CHK(heights_on_device(c));
+    const int64_t N = c->N;
+    if (N > 0) {
+        CHK(dgrow(c, c->d_wk_children, (size_t)N, 0));
+        HIPCHK(c, hipMemsetAsync(c->d_wk_children.p, 0, (size_t)N * sizeof(int32_t), c->stream));
+    }
+    HIPCHK(c, hipMemsetAsync(c->d_wk_trunk.p + np, 0, (size_t)np * sizeof(int32_t), c->stream));
+    CHK(fill_i32(c, c->d_wk_trunk.p, (size_t)np, wlk::NO_CAP));
+    if (N > 0) {
+        const unsigned blocks = (unsigned)std::min<int64_t>(2048, (N + wlk::TRUNK_THREADS - 1) / wlk::TRUNK_THREADS);
+        hipLaunchKernelGGL(wlk::k_fork_trunks, dim3(blocks), dim3(wlk::TRUNK_THREADS), 0, c->stream, (const int*)c->d_sp.p, (const int*)c->d_cr.p,
+                           (const int*)c->d_ht.p, c->n, (long long)N, c->d_wk_children.p, c->d_wk_trunk.p + np, c->d_wk_trunk.p);
+        c->ctr.kernel_launches++;
+        HIPCHK(c, hipGetLastError());
+    }
+    c->wk_trunk_N = N;
+    return SW_OK;
+}
+
+// k_walk_bfs, k_walk_list when the caller can take the events, and the header, on the context's stream; ONE synchronisation,
+// for the count.  `known` and `cap` (n int32 each, either may be NULL) are copied with `kind`; they are compared with heights
+// and never used as an index.  An error word from the walk poisons the context: its tables are not what they must be.
+int walk_run(sw_ctx* c, int64_t head, const int32_t* known, const int32_t* cap, hipMemcpyKind kind, bool with_list, int64_t* total) {
+    CHK(heights_on_device(c));
+    const int np = c->npad, n = c->n;
+    const size_t ev = (size_t)head + 1, words = (ev + 31) / 32;
+    CHK(dgrow(c, c->d_wk, (size_t)wlk::H_WORDS + 2 * (size_t)np, 0));
+    CHK(dgrow(c, c->d_wk_bits, words, 0));
+    CHK(dgrow(c, c->d_wk_q, ev, 0));
+    CHK(dgrow(c, c->d_wk_list, ev, 0));
+    if (c->payload_pending) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_payload, 0));   // timestamps / signatures of a bulk host append
+    int32_t* d_hdr = c->d_wk.p;
+    int32_t* d_known = d_hdr + wlk::H_WORDS;
+    int32_t* d_cap = d_known + np;
+    HIPCHK(c, hipMemsetAsync(d_hdr, 0, wlk::H_WORDS * sizeof(int32_t), c->stream));
+    if (known) HIPCHK(c, hipMemcpyAsync(d_known, known, (size_t)n * sizeof(int32_t), kind, c->stream));
+    if (cap) HIPCHK(c, hipMemcpyAsync(d_cap, cap, (size_t)n * sizeof(int32_t), kind, c->stream));
+    HIPCHK(c, hipMemsetAsync(c->d_wk_bits.p, 0, words * sizeof(unsigned), c->stream));
+    const bool prof = c->profiling;
+    auto t0 = std::chrono::steady_clock::now();
+    const wlk::WalkIn in{c->d_sp.p, c->d_op.p, c->d_cr.p, c->d_ht.p, n, (int)head};
+    const size_t lds = (size_t)(n + wlk::C_WORDS) * sizeof(int);
+    hipLaunchKernelGGL(wlk::k_walk_bfs, dim3(1), dim3(c->walk_threads), lds, c->stream, in, known ? (const int*)d_known : nullptr,
+                       cap ? (const int*)d_cap : nullptr, c->d_wk_bits.p, c->d_wk_q.p, d_hdr);
+    c->ctr.kernel_launches++;
+    HIPCHK(c, hipGetLastError());
+    c->wk_ms[0] = c->wk_ms[1] = c->wk_ms[2] = 0;
+    if (prof) { HIPCHK(c, hipStreamSynchronize(c->stream)); c->wk_ms[0] = ms_since(t0); t0 = std::chrono::steady_clock::now(); }
+    if (with_list) {
+        hipLaunchKernelGGL(wlk::k_walk_list, dim3(1), dim3(wlk::LIST_THREADS), 0, c->stream, (const unsigned*)c->d_wk_bits.p, (int)head, d_hdr, c->d_wk_list.p);
+        c->ctr.kernel_launches++;
+        HIPCHK(c, hipGetLastError());
+    }
+    int32_t hdr[wlk::H_WORDS] = {0};
+    HIPCHK(c, hipMemcpyAsync(hdr, d_hdr, sizeof hdr, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (prof) c->wk_ms[with_list ? 1 : 0] += ms_since(t0);
+    if (hdr[wlk::H_ERR] || hdr[wlk::H_COUNT] < 1 || hdr[wlk::H_COUNT] > head + 1) {
+        c->poisoned = true;
+        return fail(c, SW_EIO, "walk from head %lld: error %d after %d levels, %d events (a parent or creator table entry out of range, or the queue overran)",
+                    (long long)head, hdr[wlk::H_ERR], hdr[wlk::H_LEVELS], hdr[wlk::H_COUNT]);
+    }
+    c->wk_levels = hdr[wlk::H_LEVELS];
+    *total = hdr[wlk::H_COUNT];
+    return SW_OK;
+}
+
+// the gather of `total` slots behind walk_run's list, on the context's stream (asynchronous)
+int walk_gather(sw_ctx* c, int64_t total, const ExportArrays& o) {
+    const gsp::ExportIn in{nullptr, nullptr, nullptr, c->d_sp.p, c->d_op.p, c->d_id.p, c->d_sig.p, (const unsigned long long*)c->d_t.p};
+    const gsp::ExportOut out{o.id, o.sp_id, o.op_id, o.arity, o.creator, (unsigned long long*)o.t, o.sig, o.event};
+    const int G = c->export_lanes;
+    const dim3 grid((unsigned)std::min<int64_t>(2048, (total * G + wlk::GATHER_THREADS - 1) / wlk::GATHER_THREADS)), block(wlk::GATHER_THREADS);
+    const int* list = c->d_wk_list.p;
+    const int* cr = c->d_cr.p;
+    if (G == 4) hipLaunchKernelGGL(wlk::k_walk_gather<4>, grid, block, 0, c->stream, in, out, list, cr, (int)total);
+    else if (G == 8) hipLaunchKernelGGL(wlk::k_walk_gather<8>, grid, block, 0, c->stream, in, out, list, cr, (int)total);
+    else hipLaunchKernelGGL(wlk::k_walk_gather<16>, grid, block, 0, c->stream, in, out, list, cr, (int)total);
+    c->ctr.kernel_launches++;
+    HIPCHK(c, hipGetLastError());
+    return SW_OK;
+}
+
+}  // namespace
+extern "C" {
+
+int sw_get_fork_trunks(sw_ctx* c, int32_t* trunk_out) {
+    if (!c || !trunk_out) return SW_EINVAL;
+    if (c->poisoned) return fail(c, SW_EIO, "context unusable after an earlier device failure");
+    if (c->vm.active) return fail(c, SW_ENOTSUP, "sw_get_fork_trunks is not available with the windowed table");
+    HIPCHK(c, hipSetDevice(c->device));
+    CHK(fork_trunks(c));
+    std::vector<int32_t> tmp(c->npad);
+    HIPCHK(c, hipMemcpyAsync(tmp.data(), c->d_wk_trunk.p, (size_t)c->npad * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    std::copy(tmp.begin(), tmp.begin() + c->n, trunk_out);
+    return SW_OK;
+}
+
+int sw_sync_walk(sw_ctx* c, int64_t head, const int32_t* known, const int32_t* cap, int64_t cap_events, int32_t* events_out, int64_t* n_out) {
+    if (!c) return SW_EINVAL;
+    if (!n_out) return fail(c, SW_EINVAL, "sw_sync_walk: n_out is NULL");
+    *n_out = 0;
+    CHK(walk_pre(c, head, false, "sw_sync_walk"));
+    if (cap_events < 0 || (cap_events > 0 && !events_out)) return fail(c, SW_EINVAL, "sw_sync_walk: NULL output array (capacity %lld)", (long long)cap_events);
+    HIPCHK(c, hipSetDevice(c->device));
+    int64_t total = 0;
+    CHK(walk_run(c, head, known, cap, hipMemcpyHostToDevice, cap_events > 0, &total));
+    *n_out = total;
+    if (total > cap_events) return fail(c, SW_ERANGE, "sw_sync_walk: %lld events, capacity %lld (nothing written)", (long long)total, (long long)cap_events);
+    HIPCHK(c, hipMemcpyAsync(events_out, c->d_wk_list.p, (size_t)total * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->wk_calls++;
+    c->wk_events += total;
+    return SW_OK;
+}
+
+int sw_export_walk_device(sw_ctx* c, int64_t head, const int32_t* d_known, const int32_t* d_cap, int64_t cap_events, uint8_t* d_id32, uint8_t* d_sp_id32,
+                          uint8_t* d_op_id32, uint8_t* d_arity, int32_t* d_creator, double* d_t, uint8_t* d_sig64, int32_t* d_event, void* user_stream,
+                          int64_t* n_out) {
+    if (!c) return SW_EINVAL;
+    const char* what = "sw_export_walk_device";
+    if (!n_out) return fail(c, SW_EINVAL, "%s: n_out is NULL", what);
+    *n_out = 0;
+    CHK(walk_pre(c, head, true, what));
+    if (cap_events < 0 || (cap_events > 0 && (!d_id32 || !d_sp_id32 || !d_op_id32 || !d_arity || !d_creator)))
+        return fail(c, SW_EINVAL, "%s: NULL output arrays (capacity %lld)", what, (long long)cap_events);
+    if (((uintptr_t)d_id32 | (uintptr_t)d_sp_id32 | (uintptr_t)d_op_id32 | (uintptr_t)d_sig64) & 15)
+        return fail(c, SW_EINVAL, "%s: the id arrays and the signatures must be 16-byte aligned", what);
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t k = (size_t)cap_events;
+    bool on = (!d_known || on_ctx_device(c, d_known, (size_t)c->n * sizeof(int32_t))) && (!d_cap || on_ctx_device(c, d_cap, (size_t)c->n * sizeof(int32_t)));
+    if (cap_events > 0)
+        on = on && on_ctx_device(c, d_id32, k * 32) && on_ctx_device(c, d_sp_id32, k * 32) && on_ctx_device(c, d_op_id32, k * 32) &&
+             on_ctx_device(c, d_arity, k) && on_ctx_device(c, d_creator, k * 4) && (!d_t || on_ctx_device(c, d_t, k * 8)) &&
+             (!d_sig64 || on_ctx_device(c, d_sig64, k * 64)) && (!d_event || on_ctx_device(c, d_event, k * 4));
+    if (!on) return fail(c, SW_EINVAL, "%s: every array must lie in memory of device %d (a host pointer, or another device's)", what, c->device);
+    if (!c->ev_user) HIPCHK(c, hipEventCreateWithFlags(&c->ev_user, hipEventDisableTiming));
+    hipStream_t us = (hipStream_t)user_stream;
+    HIPCHK(c, hipEventRecord(c->ev_user, us));            // the producers of d_known and d_cap; earlier readers of the output arrays
+    HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_user, 0));
+    int64_t total = 0;
+    CHK(walk_run(c, head, d_known, d_cap, hipMemcpyDeviceToDevice, cap_events > 0, &total));
+    *n_out = total;
+    if (total > cap_events) return fail(c, SW_ERANGE, "%s: %lld events to export, capacity %lld (nothing written)", what, (long long)total, (long long)cap_events);
+    const auto t0 = std::chrono::steady_clock::now();
+    CHK(walk_gather(c, total, ExportArrays{d_id32, d_sp_id32, d_op_id32, d_arity, d_creator, d_t, d_sig64, d_event}));
+    HIPCHK(c, hipEventRecord(c->ev_user, c->stream));     // whatever the caller enqueues next reads complete arrays
+    HIPCHK(c, hipStreamWaitEvent(us, c->ev_user, 0));
+    if (c->profiling) { HIPCHK(c, hipStreamSynchronize(c->stream)); c->wk_ms[2] = ms_since(t0); }
+    c->wk_calls++;
+    c->wk_events += total;
+    return SW_OK;
+}
+
+int sw_export_walk(sw_ctx* c, int64_t head, const int32_t* known, const int32_t* cap, int64_t cap_events, uint8_t* id32, uint8_t* sp_id32, uint8_t* op_id32,
+                   uint8_t* arity, int32_t* creator, double* t, uint8_t* sig64, int32_t* event, int64_t* n_out) {
+    if (!c) return SW_EINVAL;
+    const char* what = "sw_export_walk";
+    if (!n_out) return fail(c, SW_EINVAL, "%s: n_out is NULL", what);
+    *n_out = 0;
+    CHK(walk_pre(c, head, true, what));
+    if (cap_events < 0 || (cap_events > 0 && (!id32 || !sp_id32 || !op_id32 || !arity || !creator)))
+        return fail(c, SW_EINVAL, "%s: NULL output arrays (capacity %lld)", what, (long long)cap_events);
+    HIPCHK(c, hipSetDevice(c->device));
+    int64_t total = 0;
+    CHK(walk_run(c, head, known, cap, hipMemcpyHostToDevice, cap_events > 0, &total));
+    *n_out = total;
+    if (total > cap_events) return fail(c, SW_ERANGE, "%s: %lld events to export, capacity %lld (nothing written)", what, (long long)total, (long long)cap_events);
+    const auto t0 = std::chrono::steady_clock::now();
+    ExportArrays d{};
+    CHK(export_scratch(c, total, t != nullptr, sig64 != nullptr, event != nullptr, &d));
+    CHK(walk_gather(c, total, d));
+    const size_t k = (size_t)total;
+    HIPCHK(c, hipMemcpyAsync(id32, d.id, k * 32, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(sp_id32, d.sp_id, k * 32, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(op_id32, d.op_id, k * 32, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(arity, d.arity, k, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(creator, d.creator, k * 4, hipMemcpyDeviceToHost, c->stream));
+    if (t) HIPCHK(c, hipMemcpyAsync(t, d.t, k * 8, hipMemcpyDeviceToHost, c->stream));
+    if (sig64) HIPCHK(c, hipMemcpyAsync(sig64, d.sig, k * 64, hipMemcpyDeviceToHost, c->stream));
+    if (event) HIPCHK(c, hipMemcpyAsync(event, d.event, k * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (c->profiling) c->wk_ms[2] = ms_since(t0);
+    c->wk_calls++;
+    c->wk_events += total;
+    return SW_OK;
+}
+
+int sw_sync_pull_walk(sw_ctx* dst, int64_t dst_head, sw_ctx* src, int64_t src_head, int use_trunks, int validate, int data, int64_t* n_sent,
+                      int64_t* n_valid, int64_t* n_stored) {
+    if (!dst || !src) return SW_EINVAL;
+    const char* what = "sw_sync_pull_walk";
+    if (n_sent) *n_sent = 0;
+    if (n_valid) *n_valid = 0;
+    if (n_stored) *n_stored = 0;
+    CHK(pull_pre(dst, dst_head, src, validate != 0, data != 0, what));
+    if (const int rc = walk_pre(src, src_head, true, "sw_sync_pull_walk (peer)"); rc != SW_OK) { dst->err = src->err; return rc; }
+    // ---- 1. what dst knows at its head, as in sw_sync_pull
+    CHK(pull_begin(dst, dst_head, src, validate != 0, data != 0, what));
+    // ---- 2. src: the trunk heights of its forked members (the answerer applies the rule, as Node.ask_sync does), the walk
+    // pruned at min(dst's heights, trunks), the count (its one synchronisation), list and gather into its own scratch
+    int64_t total = 0;
+    ExportArrays d{};
+    int rc = use_trunks ? fork_trunks(src) : SW_OK;
+    if (rc == SW_OK) rc = walk_run(src, src_head, dst->d_q.p, use_trunks ? src->d_wk_trunk.p : nullptr, hipMemcpyDeviceToDevice, true, &total);
+    if (rc != SW_OK) { dst->err = src->err; return rc; }
+    if (total > 0x3fffffffll || dst->N + total > 0x7ffffff0ll) return fail(dst, SW_ERANGE, "%s: more than 2^31 events", what);
+    const auto t0 = std::chrono::steady_clock::now();
+    rc = export_scratch(src, total, true, true, data != 0, &d);
+    if (rc == SW_OK) rc = walk_gather(src, total, d);
+    if (rc != SW_OK) { dst->err = src->err; return rc; }
+    if (src->profiling) { HIPCHK(src, hipStreamSynchronize(src->stream)); src->wk_ms[2] = ms_since(t0); }
+    src->wk_calls++;
+    src->wk_events += total;
+    if (n_sent) *n_sent = total;
+    // ---- 3. the rest as in sw_sync_pull_data / sw_sync_pull_validated / sw_sync_pull
+    return pull_finish(dst, src, total, d, validate != 0, data != 0, what, n_valid, n_stored);
+}
+
+int sw_get_walk_stats(sw_ctx* c, int64_t* calls, int64_t* events, int64_t* levels, double* phase_ms) {
+    if (!c) return SW_EINVAL;
+    if (calls) *calls = c->wk_calls;
+    if (events) *events = c->wk_events;
+    if (levels) *levels = c->wk_levels;
+    if (phase_ms) for (int i = 0; i < 3; ++i) phase_ms[i] = c->wk_ms[i];
+    return SW_OK;
+}
+
+int sw_sync_pull_data(sw_ctx* dst, int64_t dst_head, sw_ctx* src, int64_t src_head, int validate, int64_t* n_sent, int64_t* n_valid, int64_t* n_stored) {
+    if (!dst || !src) return SW_EINVAL;
+    const char* what = "sw_sync_pull_data";
+    if (n_sent) *n_sent = 0;
+    if (n_valid) *n_valid = 0;
+    if (n_stored) *n_stored = 0;
+    CHK(pull_pre(dst, dst_head, src, validate != 0, true, what));
+    if (const int rc = export_pre(src, src_head, "sw_sync_pull_data (peer)"); rc != SW_OK) { dst->err = src->err; return rc; }
+    // ---- 1. and 2. as in sw_sync_pull: dst's known heights, src's ranges, count and gather (with the dense indices)
+    CHK(pull_begin(dst, dst_head, src, validate != 0, true, what));
+    int64_t total = 0;
+    ExportArrays d{};
+    CHK(pull_ranges(dst, src, src_head, true, what, &total, &d));
+    if (n_sent) *n_sent = total;
+    // ---- 3. to 5.: src's data of those events, dst's verdicts on the signed bytes WITH the data, dst's ingest
+    return pull_finish(dst, src, total, d, validate != 0, true, what, n_valid, n_stored);
 }
 
 int sw_get_data_stats(sw_ctx* c, int64_t* events, int64_t* bytes, int64_t* store_calls, int64_t* gather_calls, int64_t* gather_bytes, double* phase_ms) {

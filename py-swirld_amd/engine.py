@@ -620,7 +620,81 @@ class Hashgraph:
             d["data"], d["data_off"], d["data_none"] = self.gather_event_data(d["event"])
         return d
 
-    def pull_from(self, peer, peer_head, my_head, validate=False, *, data=False):
+    # ---- answering a sync by the pruned walk, forked hashgraphs included (swirld.py:154-161; csrc/walk.hip.h) ----
+    def _heights_arg(self, a, what):
+        if a is None:
+            return None
+        a = np.ascontiguousarray(a, np.int32)
+        if a.shape != (self.n,):
+            raise ValueError("%s must have one entry per member" % what)
+        return a
+
+    def fork_trunks(self):
+        """Per member the height of its earliest fork point (the lowest event that is the self-parent of two stored events),
+        -1 for a member with two roots, INT32_MAX for a member that has not forked: what Node.ask_sync caps a forked
+        member's reported height with.  Either path."""
+        out = np.empty(self.n, np.int32)
+        self._chk(self._L.sw_get_fork_trunks(self._h, _p(out)))
+        return out
+
+    def sync_walk(self, head, known=None, cap=None):
+        """The events Node.ask_sync's BFS reaches from `head` (swirld.py:154-161) as dense indices, ascending: `head` itself,
+        and every parent p of a reached event with known[creator(p)] < 0 or height(p) > known[creator(p)].  `known`: n
+        heights (host), None = the asker knows nobody; `cap`: n heights, the walk prunes at min(known, cap) (fork_trunks()).
+        Fast and exact path; needs no id index."""
+        kn, cp = self._heights_arg(known, "known"), self._heights_arg(cap, "cap")
+        n_out = C.c_int64()
+        out = np.empty(max(int(head) + 1, 1), np.int32)      # (the walk names ancestors of the head: at most head + 1 events, so ONE call)
+        self._chk(self._L.sw_sync_walk(self._h, int(head), _p(kn), _p(cp), len(out), _p(out), C.byref(n_out)))
+        return out[:int(n_out.value)].copy()
+
+    def export_walk_device(self, head, known, cap, cap_events, ids, sp_ids, op_ids, arity, creator, t=None, sig=None, event=None, stream=0):
+        """The events of sync_walk(head, known, cap) written to DEVICE arrays in the layout ingest_payload_device takes, in
+        ascending dense index.  `known`, `cap`: n int32 in device memory, or None.  `cap_events`: events the arrays can take; a
+        larger set raises SwirldHipError with code -34 and writes nothing (walk_size gives the size).  Alignment and
+        streams as for export_payload_device.  Returns the number of events exported."""
+        ptrs = [_dev_ptr(a)[0] for a in (known, cap, ids, sp_ids, op_ids, arity, creator, t, sig, event)]
+        a = [C.c_void_p(q) if q else None for q in ptrs]
+        n_out = C.c_int64()
+        self._chk(self._L.sw_export_walk_device(self._h, int(head), a[0], a[1], int(cap_events), *a[2:], C.c_void_p(int(stream)), C.byref(n_out)))
+        return int(n_out.value)
+
+    def walk_size(self, head, known=None, cap=None, stream=0):
+        """Number of events export_walk_device(head, known, cap, ...) would write (`known`, `cap` in device memory, or None)."""
+        kp, cp = _dev_ptr(known)[0], _dev_ptr(cap)[0]
+        n_out = C.c_int64()
+        rc = self._L.sw_export_walk_device(self._h, int(head), C.c_void_p(kp) if kp else None, C.c_void_p(cp) if cp else None, 0, *([None] * 8),
+                                           C.c_void_p(int(stream)), C.byref(n_out))
+        if rc != -34:
+            self._chk(rc)
+        return int(n_out.value)
+
+    def export_walk(self, head, known=None, cap=None, *, data=False):
+        """export_payload's dict for the events of sync_walk(head, known, cap), in ascending dense index (host arrays)."""
+        kn, cp = self._heights_arg(known, "known"), self._heights_arg(cap, "cap")
+        n_out = C.c_int64()
+        rc = self._L.sw_export_walk(self._h, int(head), _p(kn), _p(cp), 0, *([None] * 8), C.byref(n_out))
+        if rc != -34:
+            self._chk(rc)
+        K = int(n_out.value)
+        d = dict(ids=np.empty((K, 32), np.uint8), sp_ids=np.empty((K, 32), np.uint8), op_ids=np.empty((K, 32), np.uint8),
+                 arity=np.empty(K, np.uint8), creator=np.empty(K, np.int32), t=np.empty(K, np.float64),
+                 sig=np.empty((K, 64), np.uint8), event=np.empty(K, np.int32))
+        self._chk(self._L.sw_export_walk(self._h, int(head), _p(kn), _p(cp), K,
+                                         *[_p(d[k]) for k in ("ids", "sp_ids", "op_ids", "arity", "creator", "t", "sig", "event")], C.byref(n_out)))
+        if data:
+            d["data"], d["data_off"], d["data_none"] = self.gather_event_data(d["event"])
+        return d
+
+    def walk_stats(self):
+        """Walk calls, events named, levels of the most recent walk, and (under set_profiling) the host milliseconds of the
+        most recent call's phases: walk + count, list, gather."""
+        a, b, lv = C.c_int64(), C.c_int64(), C.c_int64()
+        ms = (C.c_double * 3)()
+        self._chk(self._L.sw_get_walk_stats(self._h, C.byref(a), C.byref(b), C.byref(lv), ms))
+        return dict(calls=int(a.value), events=int(b.value), levels=int(lv.value), walk_ms=ms[0], list_ms=ms[1], gather_ms=ms[2])
+
+    def pull_from(self, peer, peer_head, my_head, validate=False, *, data=False, walk=False, trunks=False):
         """Node.sync without the new event (swirld.py:125-136) against `peer`, a Hashgraph on the same device: my known
         heights at `my_head` -> the peer's diff at `peer_head` -> my ingest, all in device memory.  Returns (n_sent,
         n_stored); my new events are the last n_stored ones, their ids event_ids(num_events - n_stored).
@@ -628,8 +702,18 @@ class Hashgraph:
         events are built on the device, judged by MY member keys and event class, and only valid events are ingested;
         returns (n_sent, n_valid, n_stored).  Needs set_member_keys; the bytes are built with data None.
         data=True (sw_sync_pull_data): the events travel WITH their data, from the peer's data store into mine, and with
-        validate=True the signed bytes are built with it; both data stores must be complete."""
+        validate=True the signed bytes are built with it; both data stores must be complete.
+        walk=True (sw_sync_pull_walk): the peer answers by the pruned walk instead of the chain ranges, so either side may
+        hold forks; trunks=True caps the walk by the PEER's fork_trunks(), which is how two contexts holding different
+        siblings of a fork exchange them.  validate and data mean the same."""
         a, b = C.c_int64(), C.c_int64()
+        if trunks and not walk:
+            raise ValueError("trunks=True needs walk=True")
+        if walk:
+            v = C.c_int64()
+            self._chk(self._L.sw_sync_pull_walk(self._h, int(my_head), peer._h, int(peer_head), 1 if trunks else 0, 1 if validate else 0,
+                                                1 if data else 0, C.byref(a), C.byref(v), C.byref(b)))
+            return (int(a.value), int(v.value), int(b.value)) if validate else (int(a.value), int(b.value))
         if data:
             v = C.c_int64()
             self._chk(self._L.sw_sync_pull_data(self._h, int(my_head), peer._h, int(peer_head), 1 if validate else 0, C.byref(a), C.byref(v), C.byref(b)))

@@ -253,6 +253,11 @@ class Node:
     # iteration order of a Python set (and with it the order concurrent events are added in) — so the
     # default keeps the BFS, which makes whole simulations reproduce the reference event for event.
     device_sync_diff = False
+    # ask_sync by the height-pruned walk ON THE DEVICE (Hashgraph.sync_walk, csrc/walk.hip.h): the BFS of swirld.py:154-161
+    # itself, with this node's trunk heights as the cap, so it also serves a context that has stored a fork (the exact path),
+    # where device_sync_diff falls back to the host.  Exactly the BFS's SET for any heights; the reply dict is filled in
+    # ascending dense index (a topological order) instead of BFS order.  Takes precedence over device_sync_diff.
+    device_sync_walk = False
     # Batched is_valid_event crypto on the GPU (sw_crypto_verify_batch / sw_crypto_hash_batch, SURVEY.md
     # §8f N3) for sync payloads of at least this many events; smaller payloads go through libsodium on
     # the host (one signature costs a GPU thread ~1-2 ms of latency, a CPU core ~60 us).  None = never.
@@ -626,6 +631,24 @@ class Node:
         """Answer a sync request with every event the asker cannot know yet: walk back from
         my head, not descending below what the asker reported per member (swirld.py:148-161)."""
         asker_heights = loads(crypto.sign_open(info, pk))
+        if (self.device_sync_walk and self._index[self.head] < self._divided
+                and all(isinstance(h, int) for h in asker_heights.values())):
+            # the BFS below on the device (Hashgraph.sync_walk), trunk rule included; the reply holds the same events, in
+            # ascending dense index instead of BFS order
+            known = np.full(self.n, -1, np.int32)
+            for creator, hgt in asker_heights.items():
+                c = self._mindex.get(creator)
+                if c is not None:
+                    known[c] = min(hgt, 0x7FFFFFFF) if hgt >= 0 else -1
+            cap = None
+            if self._trunk_height:
+                cap = np.full(self.n, 0x7FFFFFFF, np.int32)
+                for creator, th in self._trunk_height.items():
+                    cap[self._mindex[creator]] = th
+            subset = {}
+            for i in self._dev.sync_walk(self._index[self.head], known, cap).tolist():
+                subset[self._ids[i]] = self.hg[self._ids[i]]
+            return crypto.sign(dumps((self.head, subset)), self.sk)
         # (a context on the exact path — it has stored a fork — has no sw_sync_diff and `_chains` is no longer
         # one chain per member: the BFS below serves it, so a peer cannot break ask_sync by delivering a fork)
         if self.device_sync_diff and not self._dev.exact and self._index[self.head] < self._divided:
