@@ -686,6 +686,68 @@ int sw_sync_pull_walk(sw_ctx* dst, int64_t dst_head, sw_ctx* src, int64_t src_he
 int sw_get_walk_stats(sw_ctx* ctx, int64_t* calls, int64_t* events, int64_t* levels, double* phase_ms);
 
 /*
+ * The WIRE BYTES of a sync answer, built and parsed on the device (kernels in csrc/wire.hip.h).  The canonical
+ * form is a protocol-4 pickle without frames that any pickle.loads turns into (head, {id: Event(d, p, t, c, s)}), i.e. what
+ * Node.ask_sync pickles (swirld.py:166) and Node.sync unpickles (swirld.py:129); it carries a table of record offsets in a
+ * bytes object that is pushed and popped, so that one lane owns one record.  tests/model_wire.py states the layout.
+ *
+ * sw_pack_message_bound    upper bound of the message of any K events with data_bytes bytes of data.
+ * sw_pack_message_device   the message of K events from DEVICE arrays: those sw_export_walk_device and
+ *   sw_gather_event_data_device leave, plus the head's id (32 bytes).  d_msg (16-byte aligned, msg_cap >= the bound, else
+ *   SW_ERANGE) receives the bytes, *d_msg_len (device memory, 8-byte aligned) the length.  ONE event that cannot be encoded
+ *   (sw_pack_events_device's d_encodable rule) makes the message unbuildable: *d_msg_len is -1 and d_msg is not written.
+ *   Nothing at or beyond the message's end is written.  No host synchronisation; stream contract of sw_pack_events_device.
+ * sw_pack_message   the same with HOST arrays; *msg_bytes receives the length; an unencodable event is SW_EINVAL and named
+ *   in the message of sw_last_error; a message longer than msg_cap is SW_ERANGE with *msg_bytes set, nothing written.
+ * sw_unpack_message_device   the strict reader: the message (device memory, no alignment asked) is accepted only if it is
+ *   byte for byte what the writer produces for SOME arrays under this context's event class.  Every offset and length is
+ *   judged before it is followed.  SW_OK with *n_events = K and the arrays written (head, K events in the layout
+ *   sw_ingest_payload_data_device takes; creator -1 for a key of no member, the lowest index among equal keys; a root's
+ *   parent ids zero; d_data_off holds cap_events + 1 entries, d_data cap_data bytes, 16-byte aligned), or SW_OK with
+ *   *n_events = -1 for anything else (a framed pickle.dumps, another class, a flipped byte, truncation) and nothing promised
+ *   about the arrays.  SW_ERANGE when K exceeds cap_events (*n_events = K, *n_data_bytes = an upper bound of the data; nothing
+ *   written) or the data exceed cap_data (*n_data_bytes exact; no data written).  Synchronises twice: K, the verdict.
+ * sw_unpack_message   the same with HOST arrays.
+ * sw_export_message[_device]   walk, export, data gather (with_data; else every d is None) and message in one call, on the
+ *   fast or the exact path, `known` / `cap` as for sw_export_walk[_device].  The refusals of sw_export_walk; SW_ENOTSUP
+ *   without member keys, or with_data and an incomplete data store; SW_ERANGE with *msg_bytes set when msg_cap is too small.
+ * sw_ingest_message[_device]   unpack, then (validate) the signed bytes built and judged with THIS context's keys and event
+ *   class, ANDed with the encodable flags as in sw_sync_pull_validated, then sw_ingest_payload[_data]_device's ingest
+ *   (with_data keeps the data; the signed bytes are built with the data either way).  *n_events = -1 and nothing stored for a
+ *   message that is not canonical.  head32_out (32 bytes) and index_out (msg_bytes / 150 entries suffice; sw_ingest_payload's
+ *   codes) may be NULL.  Needs a complete id index, with_data a complete data store, validate member keys (SW_ENOTSUP).
+ * sw_get_wire_stats   writer calls, events and bytes (forms that know the length), reader calls, events, refused messages.
+ */
+int sw_pack_message_bound(sw_ctx* ctx, int64_t K, int64_t data_bytes, int64_t* msg_bytes);
+int sw_pack_message_device(sw_ctx* ctx, int64_t K, const uint8_t* d_head32, const uint8_t* d_id32, const uint8_t* d_sp_id32,
+                           const uint8_t* d_op_id32, const uint8_t* d_arity, const int32_t* d_creator, const double* d_t,
+                           const uint8_t* d_sig64, const uint8_t* d_data, const int64_t* d_data_off, int64_t data_bytes,
+                           const uint8_t* d_data_none, uint8_t* d_msg, int64_t msg_cap, int64_t* d_msg_len, void* user_stream);
+int sw_pack_message(sw_ctx* ctx, int64_t K, const uint8_t* head32, const uint8_t* id32, const uint8_t* sp_id32,
+                    const uint8_t* op_id32, const uint8_t* arity, const int32_t* creator, const double* t, const uint8_t* sig64,
+                    const uint8_t* data, const int64_t* data_off, int64_t data_bytes, const uint8_t* data_none, uint8_t* msg,
+                    int64_t msg_cap, int64_t* msg_bytes);
+int sw_unpack_message_device(sw_ctx* ctx, const uint8_t* d_msg, int64_t msg_bytes, int64_t cap_events, int64_t cap_data,
+                             uint8_t* d_head32, uint8_t* d_id32, uint8_t* d_sp_id32, uint8_t* d_op_id32, uint8_t* d_arity,
+                             int32_t* d_creator, double* d_t, uint8_t* d_sig64, uint8_t* d_data, int64_t* d_data_off,
+                             uint8_t* d_data_none, void* user_stream, int64_t* n_events, int64_t* n_data_bytes);
+int sw_unpack_message(sw_ctx* ctx, const uint8_t* msg, int64_t msg_bytes, int64_t cap_events, int64_t cap_data, uint8_t* head32,
+                      uint8_t* id32, uint8_t* sp_id32, uint8_t* op_id32, uint8_t* arity, int32_t* creator, double* t,
+                      uint8_t* sig64, uint8_t* data, int64_t* data_off, uint8_t* data_none, int64_t* n_events,
+                      int64_t* n_data_bytes);
+int sw_export_message_device(sw_ctx* ctx, int64_t head_event, const int32_t* d_known, const int32_t* d_cap, int with_data,
+                             uint8_t* d_msg, int64_t msg_cap, void* user_stream, int64_t* msg_bytes, int64_t* n_events);
+int sw_export_message(sw_ctx* ctx, int64_t head_event, const int32_t* known, const int32_t* cap, int with_data, uint8_t* msg,
+                      int64_t msg_cap, int64_t* msg_bytes, int64_t* n_events);
+int sw_ingest_message_device(sw_ctx* ctx, const uint8_t* d_msg, int64_t msg_bytes, int validate, int with_data,
+                             uint8_t* d_head32_out, int32_t* d_index_out, void* user_stream, int64_t* n_events, int64_t* n_valid,
+                             int64_t* n_stored);
+int sw_ingest_message(sw_ctx* ctx, const uint8_t* msg, int64_t msg_bytes, int validate, int with_data, uint8_t* head32_out,
+                      int32_t* index_out, int64_t* n_events, int64_t* n_valid, int64_t* n_stored);
+int sw_get_wire_stats(sw_ctx* ctx, int64_t* pack_calls, int64_t* pack_events, int64_t* pack_bytes, int64_t* unpack_calls,
+                      int64_t* unpack_events, int64_t* refused);
+
+/*
  * CREATING signed events on the device (kernels in csrc/sign.hip.h): the producing half of Node.new_event
  * (swirld.py:82-95) for K events at once — the Ed25519 signature over dumps((d, p, t, pk)) and the id
  * crypto_generichash(dumps(ev)), bit for bit what libsodium, pickle and hashlib give, from the same index arrays

@@ -120,6 +120,17 @@ SIGNATURES = {
     "sw_sync_pull_walk": (C.c_int, [_P, C.c_int64, _P, C.c_int64, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
                                     C.POINTER(C.c_int64)]),
     "sw_get_walk_stats": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), _P]),
+    # the wire bytes of a sync answer (csrc/wire.hip.h)
+    "sw_pack_message_bound": (C.c_int, [_P, C.c_int64, C.c_int64, C.POINTER(C.c_int64)]),
+    "sw_pack_message_device": (C.c_int, [_P, C.c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int64, _P, _P, C.c_int64, _P, _P]),
+    "sw_pack_message": (C.c_int, [_P, C.c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int64, _P, _P, C.c_int64, C.POINTER(C.c_int64)]),
+    "sw_unpack_message_device": (C.c_int, [_P, _P, C.c_int64, C.c_int64, C.c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "sw_unpack_message": (C.c_int, [_P, _P, C.c_int64, C.c_int64, C.c_int64, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "sw_export_message_device": (C.c_int, [_P, C.c_int64, _P, _P, C.c_int, _P, C.c_int64, _P, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "sw_export_message": (C.c_int, [_P, C.c_int64, _P, _P, C.c_int, _P, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "sw_ingest_message_device": (C.c_int, [_P, _P, C.c_int64, C.c_int, C.c_int, _P, _P, _P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "sw_ingest_message": (C.c_int, [_P, _P, C.c_int64, C.c_int, C.c_int, _P, _P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+    "sw_get_wire_stats": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "sw_set_signing_keys":(C.c_int, [_P, C.c_int64, _P, _P]),
     "sw_clear_signing_keys": (C.c_int, [_P]),
     "sw_get_signing_members": (C.c_int, [_P, _P]),

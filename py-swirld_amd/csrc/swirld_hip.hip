@@ -31,6 +31,7 @@
 #include "resolve.hip.h"
 #include "gossip.hip.h"
 #include "walk.hip.h"
+#include "wire.hip.h"
 #include "consensus.hip.h"
 
 namespace {
@@ -234,6 +235,18 @@ struct sw_ctx {
     DBuf<unsigned char> d_dt_out; // the gathered data: of the host-array gather, and of sw_sync_pull_data's exported events (in the answering context)
     int64_t dt_store_calls = 0, dt_gather_calls = 0, dt_gather_bytes = 0;   // sw_get_data_stats
     double dt_ms[2] = {0, 0};     // ... host time under sw_set_profiling: lengths + scan, the copy
+    // the wire bytes of a sync answer (sw_pack_message[_device], sw_unpack_message[_device], sw_export_message[_device],
+    // sw_ingest_message[_device]; wire.hip.h): settings derived from the event class and the member keys, and scratch
+    std::string wr_mod, wr_qual;  // the class d_wr_set's prefix was built for (empty: none yet)
+    std::vector<uint8_t> wr_pre;  // host copy of the bytes in front of the table's length field, as uploaded
+    std::vector<uint8_t> wr_keys, wr_skeys;   // the member keys the sorted table was built from; the sorted keys as uploaded
+    std::vector<int32_t> wr_sperm;            // ... and the member each belongs to
+    DBuf<unsigned char> d_wr_set; // [wir::PRE_MAX prefix][n x 32 sorted keys][n members][8 words: K, refusal flag, verdict, data bytes, length]
+    DBuf<unsigned char> d_wr;     // scratch of a call: record offsets, tile sums, the first unencodable event; data positions
+    DBuf<unsigned char> d_wr_in;  // the staged arrays and the message of the host-array forms
+    DBuf<unsigned char> d_wr_out; // the message of sw_export_message; the unpacked arrays of sw_ingest_message
+    int wire_blocks = 4096;       // SW_WIRE_BLOCKS (measurement and test knob, read at sw_create): the most workgroups of k_wire_write
+    int64_t wr_pack_calls = 0, wr_pack_events = 0, wr_pack_bytes = 0, wr_unpack_calls = 0, wr_unpack_events = 0, wr_refused = 0;   // sw_get_wire_stats
     // creating signed events (sw_set_signing_keys, sw_sign_events[_device], sw_create_events[_device]; sign.hip.h): like the
     // member keys a setting that sw_rewind / sw_reset leave alone; sw_set_member_keys drops it
     std::vector<uint8_t> sg_has;  // n flags: the members this context may sign for (empty: no signing key set)
@@ -3005,6 +3018,7 @@ int sw_create(int n_members, const uint64_t* stake, int coin_period, int device,
     }
     if (const char* e_ = getenv("SW_EXPORT_LANES")) { const int g = atoi(e_); if (g == 4 || g == 8) c->export_lanes = g; }
     if (const char* e_ = getenv("SW_WALK_THREADS")) { const int w = atoi(e_); if (w >= 64 && w <= wlk::MAX_THREADS && w % 64 == 0) c->walk_threads = w; }
+    if (const char* e_ = getenv("SW_WIRE_BLOCKS")) { const int w = atoi(e_); if (w >= 1 && w <= 4096) c->wire_blocks = w; }
     if (getenv("SW_DEBUG_CLOCKS")) {  // diagnostics: phase stamps of the round-loop kernels
         c->dbg_minor = atoi(getenv("SW_DEBUG_CLOCKS")) >= 2 ? 0 : 1;
         if (atoi(getenv("SW_DEBUG_CLOCKS")) == 3) {
@@ -3196,6 +3210,7 @@ int sw_destroy(sw_ctx* c) {
     dfree(c->d_rr); dfree(c->d_cts); dfree(c->d_tx); dfree(c->d_cs_ordpos); dfree(c->d_cs_out);
     dfree(c->d_vkeys); dfree(c->d_vtab); dfree(c->d_v_in);
     dfree(c->d_pk_hdr); dfree(c->d_pk); dfree(c->d_pk_in); dfree(c->d_pk_out);
+    dfree(c->d_wr_set); dfree(c->d_wr); dfree(c->d_wr_in); dfree(c->d_wr_out);
     dfree(c->d_data); dfree(c->d_data_off); dfree(c->d_data_none); dfree(c->d_dt); dfree(c->d_dt_in); dfree(c->d_dt_out);
     if (c->d_sg_keys.p) { (void)hipMemset(c->d_sg_keys.p, 0, c->d_sg_keys.cap); (void)hipDeviceSynchronize(); }   // the secrets do not outlive the context
     dfree(c->d_sg_keys); dfree(c->d_sg); dfree(c->d_sg_in);
@@ -6326,6 +6341,9 @@ int pull_ranges(sw_ctx* dst, sw_ctx* src, int64_t src_head, bool with_event, con
     return SW_OK;
 }
 
+int ingest_arrays(sw_ctx* dst, hipStream_t from, int64_t total, const ExportArrays& d, const uint8_t* x_data, const int64_t* x_off, int64_t dbytes,
+                  const uint8_t* x_none, bool validate, bool store_data, int64_t* n_valid, int64_t* n_stored);
+
 // behind src's export of `total` events into `d` (its scratch, written on its stream):
 //   data      src gathers the data of those events beside the other arrays (its second synchronisation: the byte total)
 //   validate  dst, its stream ordered behind src's, builds the signed bytes (with the data, or with data None), judges them by
@@ -6358,6 +6376,18 @@ int pull_finish(sw_ctx* dst, sw_ctx* src, int64_t total, const ExportArrays& d, 
         x_off = (const int64_t*)(S + s_off);
         x_none = S + s_n;
     }
+    return ingest_arrays(dst, src->stream, total, d, x_data, x_off, dbytes, x_none, validate, data, n_valid, n_stored);
+}
+
+// `total` events in device arrays written on stream `from` (the peer's, or dst's own), with or without data arrays:
+//   validate  dst, its stream ordered behind `from`, builds the signed bytes (with the data, or with data None), judges them by
+//             its OWN keys and event class, ANDs the verdicts with the encodable flags and counts them
+//   then      dst ingests what is valid (Node.sync's loop, swirld.py:130-136), keeping the data when `store_data`; the dense
+//             indices are left in dst->d_pl_in.  dst's stream is drained before the call returns.
+int ingest_arrays(sw_ctx* dst, hipStream_t from, int64_t total, const ExportArrays& d, const uint8_t* x_data, const int64_t* x_off, int64_t dbytes,
+                  const uint8_t* x_none, bool validate, bool store_data, int64_t* n_valid, int64_t* n_stored) {
+    const size_t k = (size_t)total;
+    int rc = SW_OK;
     CHK(dgrow(dst, dst->d_pl_in, k * sizeof(int32_t), 0));
     const uint8_t* ok = nullptr;
     if (validate) {
@@ -6368,7 +6398,7 @@ int pull_finish(sw_ctx* dst, sw_ctx* src, int64_t total, const ExportArrays& d, 
         const size_t o_enc = cv.take(k), o_ok = cv.take(k), o_cnt = cv.take(sizeof(int32_t));
         CHK(dgrow(dst, dst->d_pk_out, cv.off + 256, 0));
         unsigned char* B = dst->d_pk_out.p;
-        HIPCHK(dst, hipEventRecord(dst->ev_user, src->stream));
+        HIPCHK(dst, hipEventRecord(dst->ev_user, from));
         HIPCHK(dst, hipStreamWaitEvent(dst->stream, dst->ev_user, 0));
         HIPCHK(dst, hipMemsetAsync(B + o_cnt, 0, sizeof(int32_t), dst->stream));
         rc = pack_launch(dst, total, PackArrays{d.sp_id, d.op_id, d.arity, d.creator, d.t, d.sig, x_data, x_off, dbytes, x_none, B + o_m, (int64_t*)(B + o_moff),
@@ -6388,11 +6418,11 @@ int pull_finish(sw_ctx* dst, sw_ctx* src, int64_t total, const ExportArrays& d, 
         ok = B + o_ok;
     }
     int64_t stored = 0;
-    if (data)
-        rc = ingest_data_core(dst, total, d.id, d.sp_id, d.op_id, d.arity, d.creator, ok, d.t, d.sig, x_data, x_off, dbytes, x_none, src->stream,
+    if (store_data)
+        rc = ingest_data_core(dst, total, d.id, d.sp_id, d.op_id, d.arity, d.creator, ok, d.t, d.sig, x_data, x_off, dbytes, x_none, from,
                               (int32_t*)dst->d_pl_in.p, &stored);
     else
-        rc = payload_core(dst, total, d.id, d.sp_id, d.op_id, d.arity, d.creator, ok, d.t, d.sig, src->stream, (int32_t*)dst->d_pl_in.p, &stored);
+        rc = payload_core(dst, total, d.id, d.sp_id, d.op_id, d.arity, d.creator, ok, d.t, d.sig, from, (int32_t*)dst->d_pl_in.p, &stored);
     const hipError_t drained = hipStreamSynchronize(dst->stream);   // src's scratch is free again only once dst has read it
     if (rc != SW_OK) return rc;
     HIPCHK(dst, drained);
@@ -6674,6 +6704,544 @@ int sw_get_data_stats(sw_ctx* c, int64_t* events, int64_t* bytes, int64_t* store
     if (gather_calls) *gather_calls = c->dt_gather_calls;
     if (gather_bytes) *gather_bytes = c->dt_gather_bytes;
     if (phase_ms) for (int i = 0; i < 2; ++i) phase_ms[i] = c->dt_ms[i];
+    return SW_OK;
+}
+
+// ---- the wire bytes of a sync answer (wire.hip.h) -------------------------------------------------------
+}  // extern "C"
+namespace {
+
+struct WireArrays {   // what the message writer reads, every array in device memory
+    const uint8_t *head, *id, *sp_id, *op_id, *arity;
+    const int32_t* creator;
+    const double* t;
+    const uint8_t *sig, *data;
+    const int64_t* data_off;
+    int64_t data_bytes;
+    const uint8_t* data_none;
+};
+
+int wire_pre_len(const sw_ctx* c) { return (int)(c->pk_mod.size() + c->pk_qual.size() + 10); }
+int64_t wire_base(const sw_ctx* c, int64_t K) { return (int64_t)wire_pre_len(c) + 8 + 8 * (K + 1) + wir::HEAD_PART; }
+int64_t wire_bound(const sw_ctx* c, int64_t K, int64_t data_bytes) { return wire_base(c, K) + K * wir::REC_MAX + data_bytes + 3; }
+
+struct WireSet { unsigned char* pre; unsigned char* skeys; int32_t* sperm; wir::i64* res; };
+WireSet wire_set(const sw_ctx* c) {
+    Carve cv;
+    const size_t o_pre = cv.take(wir::PRE_MAX), o_keys = cv.take((size_t)c->n * 32), o_perm = cv.take((size_t)c->n * 4), o_res = cv.take(64);
+    unsigned char* B = c->d_wr_set.p;
+    return WireSet{B + o_pre, B + o_keys, (int32_t*)(B + o_perm), (wir::i64*)(B + o_res)};
+}
+
+// the prefix under the context's event class and the sorted key table, in device memory: rebuilt when either has changed
+int wire_settings(sw_ctx* c) {
+    CHK(dgrow(c, c->d_wr_set, (size_t)wir::PRE_MAX + (size_t)c->n * 36 + 4 * 256 + 64, 0));
+    const WireSet ws = wire_set(c);
+    const bool pre_stale = c->wr_mod != c->pk_mod || c->wr_qual != c->pk_qual, keys_stale = c->wr_keys != c->vkeys;
+    if (!pre_stale && !keys_stale) return SW_OK;
+    HIPCHK(c, hipStreamSynchronize(c->stream));   // an earlier call may still be reading the old settings, or copying them
+    if (pre_stale) {
+        std::vector<uint8_t>& h = c->wr_pre;
+        h.assign({0x80, 0x04});
+        for (const std::string* s : {&c->pk_mod, &c->pk_qual}) {
+            h.push_back(0x8c);
+            h.push_back((uint8_t)s->size());
+            h.insert(h.end(), s->begin(), s->end());
+        }
+        for (const uint8_t b : {0x93, 0x94, 0x30, 0x8e}) h.push_back(b);
+        HIPCHK(c, hipMemcpyAsync(ws.pre, h.data(), h.size(), hipMemcpyHostToDevice, c->stream));
+        c->wr_mod = c->pk_mod;
+        c->wr_qual = c->pk_qual;
+    }
+    if (keys_stale) {
+        const int n = c->vkeys.empty() ? 0 : c->n;
+        c->wr_skeys.assign((size_t)c->n * 32, 0);
+        c->wr_sperm.assign((size_t)c->n, -1);
+        if (n) {
+            wir::sort_keys(c->vkeys.data(), n, c->wr_skeys.data(), c->wr_sperm.data());
+            HIPCHK(c, hipMemcpyAsync(ws.skeys, c->wr_skeys.data(), (size_t)n * 32, hipMemcpyHostToDevice, c->stream));
+            HIPCHK(c, hipMemcpyAsync(ws.sperm, c->wr_sperm.data(), (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+        }
+        c->wr_keys = c->vkeys;
+    }
+    return SW_OK;
+}
+
+// pack.hip.h's scan of one stream of K lengths in place (off[K] = the total), on the context's stream
+void wire_scan(sw_ctx* c, int64_t K, pck::i64* off, pck::i64* tsum) {
+    const int64_t tiles = (K + pck::TILE - 1) / pck::TILE;
+    if (tiles) hipLaunchKernelGGL(pck::k_pack_tile_sums, dim3((unsigned)tiles, 1), dim3(pck::SCAN_THREADS), 0, c->stream, (pck::i64)K, (pck::i64)tiles,
+                                  (const pck::i64*)off, (const pck::i64*)off, tsum);
+    hipLaunchKernelGGL(pck::k_pack_scan_sums, dim3(1), dim3(pck::SCAN_THREADS), 0, c->stream, (pck::i64)K, (pck::i64)tiles, off, off, tsum);
+    if (tiles) hipLaunchKernelGGL(pck::k_pack_offsets, dim3((unsigned)tiles, 1), dim3(pck::SCAN_THREADS), 0, c->stream, (pck::i64)K, (pck::i64)tiles, off, off,
+                                  (const pck::i64*)tsum);
+    c->ctr.kernel_launches += tiles ? 3 : 1;
+}
+
+// the launches of the writer on the context's stream (asynchronous): d_msg holds `bound` = wire_bound(...) bytes at least,
+// *d_msg_len receives the length or -1, *d_bad_out (may be NULL) the first unencodable event
+int wire_pack_launch(sw_ctx* c, int64_t K, const WireArrays& a, uint8_t* d_msg, int64_t bound, int64_t* d_msg_len, unsigned long long** d_bad_out) {
+    CHK(wire_settings(c));
+    const int64_t tiles = (K + pck::TILE - 1) / pck::TILE;
+    Carve cv;
+    const size_t o_off = cv.take((size_t)(K + 1) * 8), o_ts = cv.take((size_t)(tiles + 1) * 8), o_bad = cv.take(8);
+    CHK(dgrow(c, c->d_wr, cv.off + 256, 0));
+    unsigned char* B = c->d_wr.p;
+    pck::i64* off = (pck::i64*)(B + o_off);
+    pck::u64* bad = (pck::u64*)(B + o_bad);
+    const WireSet ws = wire_set(c);
+    const wir::WireIn w{pck::PackIn{a.sp_id, a.op_id, a.arity, a.creator, (const pck::u64*)a.t, a.sig, a.data, (const pck::i64*)a.data_off, (pck::i64)a.data_bytes,
+                                    a.data_none, (const unsigned char*)c->d_vkeys.p, ws.pre, wire_pre_len(c), c->n},
+                        a.id, a.head};
+    HIPCHK(c, hipMemsetAsync(bad, 0xff, 8, c->stream));
+    if (K > 0) {
+        hipLaunchKernelGGL(wir::k_wire_lengths, dim3((unsigned)((K + 255) / 256)), dim3(256), 0, c->stream, w, (pck::i64)K, off, bad);
+        c->ctr.kernel_launches++;
+    }
+    wire_scan(c, K, off, (pck::i64*)(B + o_ts));
+    const int64_t chunks = (bound + 15) / 16;
+    const int64_t blocks = std::max<int64_t>(1, std::min<int64_t>(c->wire_blocks, (chunks + wir::WRITE_THREADS - 1) / wir::WRITE_THREADS));
+    const int64_t trips = (chunks + blocks * wir::WRITE_THREADS - 1) / (blocks * wir::WRITE_THREADS);
+    hipLaunchKernelGGL(wir::k_wire_write, dim3((unsigned)blocks), dim3(wir::WRITE_THREADS), 0, c->stream, w, (pck::i64)K, (const pck::i64*)off,
+                       (pck::i64)wire_base(c, K), (const pck::u64*)bad, d_msg, (pck::i64*)d_msg_len, (pck::i64)trips);
+    c->ctr.kernel_launches++;
+    HIPCHK(c, hipGetLastError());
+    if (d_bad_out) *d_bad_out = bad;
+    c->wr_pack_calls++;
+    c->wr_pack_events += K;
+    return SW_OK;
+}
+
+// what both forms of sw_pack_message check before anything else
+int wire_pack_pre(sw_ctx* c, int64_t K, const WireArrays& a, const void* msg, const char* what) {
+    if (c->poisoned) return fail(c, SW_EIO, "context unusable after an earlier device failure");
+    if (c->vkeys.empty()) return fail(c, SW_ENOTSUP, "%s: no member keys (sw_set_member_keys first)", what);
+    if (K < 0 || a.data_bytes < 0) return fail(c, SW_EINVAL, "%s: negative count or length", what);
+    if (K > 0x7fffffff) return fail(c, SW_ERANGE, "%s: more than 2^31 events", what);
+    if (!a.head || !msg) return fail(c, SW_EINVAL, "%s: NULL head or message buffer", what);
+    if (K > 0 && (!a.id || !a.sp_id || !a.op_id || !a.arity || !a.creator || !a.t || !a.sig)) return fail(c, SW_EINVAL, "%s: NULL arrays", what);
+    if (!a.data_off && (a.data || a.data_bytes || a.data_none)) return fail(c, SW_EINVAL, "%s: data needs its offsets (or none of data, offsets, length, flags)", what);
+    if (a.data_off && a.data_bytes > 0 && !a.data) return fail(c, SW_EINVAL, "%s: %lld data bytes and a NULL buffer", what, (long long)a.data_bytes);
+    return SW_OK;
+}
+
+struct WireOut {      // what the reader writes, every array in device memory
+    uint8_t *head, *id, *sp_id, *op_id, *arity;
+    int32_t* creator;
+    double* t;
+    uint8_t *sig, *data;
+    int64_t* data_off;
+    uint8_t* data_none;
+};
+
+// the reader on the context's stream: TWO synchronisations, for K behind the header and for the verdict with the data bytes.
+// *n_events: K, or -1 for a message that is not canonical; SW_ERANGE with the sizes that suffice when a capacity is too small.
+int wire_unpack_run(sw_ctx* c, const uint8_t* d_msg, int64_t msg_bytes, int64_t cap_events, int64_t cap_data, const WireOut& o, int64_t* n_events,
+                    int64_t* n_data, const char* what) {
+    *n_events = -1;
+    *n_data = 0;
+    CHK(wire_settings(c));
+    c->wr_unpack_calls++;
+    const int pre_len = wire_pre_len(c);
+    if (msg_bytes < pre_len + 8) { c->wr_refused++; return SW_OK; }
+    const WireSet ws = wire_set(c);
+    const wir::ReadIn in{d_msg, (wir::i64)msg_bytes, ws.pre, pre_len, ws.skeys, ws.sperm, c->vkeys.empty() ? 0 : c->n};
+    hipLaunchKernelGGL(wir::k_wire_header, dim3(1), dim3(256), 0, c->stream, in, ws.res);
+    c->ctr.kernel_launches++;
+    HIPCHK(c, hipGetLastError());
+    long long K = -1;
+    HIPCHK(c, hipMemcpyAsync(&K, ws.res, 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (K < 0) { c->wr_refused++; return SW_OK; }
+    if (K > cap_events) {
+        *n_events = K;
+        *n_data = msg_bytes - wire_base(c, K) - 3 - K * wir::REC_MIN;
+        return fail(c, SW_ERANGE, "%s: %lld events in the message, capacity %lld (at most %lld data bytes; nothing written)", what, K, (long long)cap_events,
+                    (long long)*n_data);
+    }
+    const int64_t tiles = (K + pck::TILE - 1) / pck::TILE;
+    Carve cv;
+    const size_t o_ts = cv.take((size_t)(tiles + 1) * 8), o_src = cv.take((size_t)K * 8);
+    CHK(dgrow(c, c->d_wr, cv.off + 256, 0));
+    unsigned char* B = c->d_wr.p;
+    const wir::ReadOut ro{o.head, o.id, o.sp_id, o.op_id, o.arity, o.creator, (wir::u64*)o.t, o.sig, (wir::i64*)o.data_off, o.data_none, (wir::i64*)(B + o_src)};
+    wir::i64* flag = ws.res + 1;
+    hipLaunchKernelGGL(wir::k_wire_table, dim3((unsigned)((K + 256) / 256)), dim3(256), 0, c->stream, in, (wir::i64)K, o.head, flag);
+    c->ctr.kernel_launches++;
+    if (K > 0) {
+        hipLaunchKernelGGL(wir::k_wire_records, dim3((unsigned)((K + 255) / 256)), dim3(256), 0, c->stream, in, (wir::i64)K, ro, flag);
+        c->ctr.kernel_launches++;
+    }
+    wire_scan(c, K, (pck::i64*)o.data_off, (pck::i64*)(B + o_ts));
+    const int64_t chunks = (cap_data + 15) / 16;
+    const int64_t blocks = std::max<int64_t>(1, std::min<int64_t>(4096, (chunks + 255) / 256));
+    hipLaunchKernelGGL(wir::k_wire_data, dim3((unsigned)blocks), dim3(256), 0, c->stream, d_msg, (wir::i64)K, ro, (wir::i64)cap_data, (const wir::i64*)flag, o.data,
+                       ws.res + 2);
+    c->ctr.kernel_launches++;
+    HIPCHK(c, hipGetLastError());
+    long long v[2] = {-1, 0};
+    HIPCHK(c, hipMemcpyAsync(v, ws.res + 2, 16, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (v[0] < 0) { c->wr_refused++; return SW_OK; }
+    *n_events = K;
+    *n_data = v[1];
+    if (v[1] > cap_data) return fail(c, SW_ERANGE, "%s: %lld data bytes in the message, capacity %lld (no data written)", what, v[1], (long long)cap_data);
+    c->wr_unpack_events += K;
+    return SW_OK;
+}
+
+int wire_unpack_pre(sw_ctx* c, const void* msg, int64_t msg_bytes, int64_t cap_events, int64_t cap_data, const WireOut& o, const void* n_events,
+                    const void* n_data, const char* what) {
+    if (!n_events || !n_data) return fail(c, SW_EINVAL, "%s: n_events or n_data_bytes is NULL", what);
+    if (c->poisoned) return fail(c, SW_EIO, "context unusable after an earlier device failure");
+    if (msg_bytes < 0 || cap_events < 0 || cap_data < 0) return fail(c, SW_EINVAL, "%s: negative length or capacity", what);
+    if (cap_events > 0x7fffffff) return fail(c, SW_ERANGE, "%s: more than 2^31 events", what);
+    if ((msg_bytes > 0 && !msg) || !o.head || !o.data_off) return fail(c, SW_EINVAL, "%s: NULL message, head or offsets", what);
+    if (cap_events > 0 && (!o.id || !o.sp_id || !o.op_id || !o.arity || !o.creator || !o.t || !o.sig || !o.data_none)) return fail(c, SW_EINVAL, "%s: NULL output arrays", what);
+    if (cap_data > 0 && !o.data) return fail(c, SW_EINVAL, "%s: NULL data buffer (capacity %lld)", what, (long long)cap_data);
+    return SW_OK;
+}
+
+// walk, export, data gather and the message of sw_export_message, left in d_wr_out (*d_msg, *len bytes; *K events)
+int wire_export_run(sw_ctx* c, int64_t head, const int32_t* known, const int32_t* cap, hipMemcpyKind kind, bool with_data, const char* what, uint8_t** d_msg,
+                    int64_t* len, int64_t* n_events) {
+    CHK(walk_pre(c, head, true, what));
+    if (c->vkeys.empty()) return fail(c, SW_ENOTSUP, "%s: no member keys (sw_set_member_keys first)", what);
+    if (with_data && c->n_data != c->N)
+        return fail(c, SW_ENOTSUP, "%s: %lld of the %lld stored events have no data entry (sw_set_event_data first)", what, (long long)(c->N - c->n_data), (long long)c->N);
+    int64_t total = 0;
+    CHK(walk_run(c, head, known, cap, kind, true, &total));
+    ExportArrays d{};
+    CHK(export_scratch(c, total, true, true, true, &d));
+    CHK(walk_gather(c, total, d));
+    c->wk_calls++;
+    c->wk_events += total;
+    const size_t k = (size_t)total;
+    int64_t dbytes = 0;
+    const uint8_t* x_data = nullptr;
+    const int64_t* x_off = nullptr;
+    const uint8_t* x_none = nullptr;
+    if (with_data) {
+        DataPlan sp{};
+        int64_t bad = 0;
+        const dat::SegIn sin{c->d_data.p, (const dat::i64*)c->d_data_off.p, c->d_data_none.p, d.event, (dat::i64)c->n_data, (dat::i64)c->data_used, 1};
+        CHK(data_scratch(c, total, 0, 0, &sp));
+        CHK(data_plan(c, total, sin, sp, &dbytes, &bad));
+        if (bad) return fail(c, SW_EIO, "%s: %lld exported events without data (internal error)", what, (long long)bad);
+        Carve sv;
+        const size_t s_d = sv.take((size_t)dbytes + 16), s_off = sv.take((k + 1) * 8), s_n = sv.take(k);
+        CHK(dgrow(c, c->d_dt_out, sv.off + 256, 0));
+        unsigned char* S = c->d_dt_out.p;
+        CHK(data_copy(c, total, sin, sp, dbytes, S + s_d, 0, 0, (int64_t*)(S + s_off), S + s_n));
+        c->dt_gather_calls++;
+        c->dt_gather_bytes += dbytes;
+        x_data = S + s_d;
+        x_off = (const int64_t*)(S + s_off);
+        x_none = S + s_n;
+    }
+    const int64_t bound = wire_bound(c, total, dbytes);
+    CHK(dgrow(c, c->d_wr_out, (size_t)bound + 256, 0));
+    CHK(wire_settings(c));
+    int64_t* d_len = (int64_t*)(wire_set(c).res + 4);
+    CHK(wire_pack_launch(c, total, WireArrays{c->d_id.p + (size_t)head * 32, d.id, d.sp_id, d.op_id, d.arity, d.creator, d.t, d.sig, x_data, x_off, dbytes, x_none},
+                         c->d_wr_out.p, bound, d_len, nullptr));
+    long long l = -1;
+    HIPCHK(c, hipMemcpyAsync(&l, d_len, 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (l < 0 || l > bound) return fail(c, SW_EIO, "%s: a stored event cannot be encoded (length %lld, bound %lld: internal error)", what, l, (long long)bound);
+    c->wr_pack_bytes += l;
+    *d_msg = c->d_wr_out.p;
+    *len = l;
+    *n_events = total;
+    return SW_OK;
+}
+
+// unpack, validate and ingest of sw_ingest_message: d_msg in device memory, visible to the context's stream.  The head is left
+// at *d_head, the dense indices in d_pl_in.
+int wire_ingest_run(sw_ctx* c, const uint8_t* d_msg, int64_t msg_bytes, bool validate, bool with_data, const char* what, uint8_t** d_head, int64_t* n_events,
+                    int64_t* n_valid, int64_t* n_stored) {
+    if (c->poisoned) return fail(c, SW_EIO, "context unusable after an earlier device failure");
+    if (validate && c->vkeys.empty()) return fail(c, SW_ENOTSUP, "%s: no member keys (sw_set_member_keys first)", what);
+    if (c->n_ids != c->N)
+        return fail(c, SW_ENOTSUP, "%s: %lld of the %lld stored events have no id (sw_set_event_ids first)", what, (long long)(c->N - c->n_ids), (long long)c->N);
+    if (with_data && c->n_data != c->N)
+        return fail(c, SW_ENOTSUP, "%s: %lld of the %lld stored events have no data entry (sw_set_event_data first)", what, (long long)(c->N - c->n_data), (long long)c->N);
+    if (validate && !c->h_pkcnt && hipHostMalloc((void**)&c->h_pkcnt, sizeof(int32_t), hipHostMallocDefault) != hipSuccess) {
+        (void)hipGetLastError();
+        c->h_pkcnt = nullptr;
+        return fail(c, SW_ENOMEM, "hipHostMalloc for the count of valid events failed");
+    }
+    if (!c->ev_user) HIPCHK(c, hipEventCreateWithFlags(&c->ev_user, hipEventDisableTiming));
+    const int64_t kcap = std::min<int64_t>(msg_bytes / wir::REC_MIN, 0x3fffffff), dcap = msg_bytes;
+    const size_t k = (size_t)kcap;
+    Carve cv;
+    const size_t o_head = cv.take(32), o_id = cv.take(k * 32), o_sp = cv.take(k * 32), o_op = cv.take(k * 32), o_ar = cv.take(k), o_cr = cv.take(k * 4);
+    const size_t o_t = cv.take(k * 8), o_sig = cv.take(k * 64), o_doff = cv.take((k + 1) * 8), o_dn = cv.take(k), o_d = cv.take((size_t)dcap + 16);
+    CHK(dgrow(c, c->d_wr_out, cv.off + 256, 0));
+    unsigned char* B = c->d_wr_out.p;
+    const WireOut o{B + o_head, B + o_id, B + o_sp, B + o_op, B + o_ar, (int32_t*)(B + o_cr), (double*)(B + o_t), B + o_sig, B + o_d, (int64_t*)(B + o_doff), B + o_dn};
+    int64_t K = -1, dbytes = 0;
+    CHK(wire_unpack_run(c, d_msg, msg_bytes, kcap, dcap, o, &K, &dbytes, what));
+    *n_events = K;
+    *d_head = o.head;
+    if (K < 0) return SW_OK;
+    if (c->N + K > 0x7ffffff0ll) return fail(c, SW_ERANGE, "%s: more than 2^31 events", what);
+    if (K == 0) return SW_OK;
+    const ExportArrays d{o.id, o.sp_id, o.op_id, o.arity, o.creator, o.t, o.sig, nullptr};
+    return ingest_arrays(c, c->stream, K, d, o.data, o.data_off, dbytes, o.data_none, validate, with_data, n_valid, n_stored);
+}
+
+}  // namespace
+extern "C" {
+
+int sw_pack_message_bound(sw_ctx* c, int64_t K, int64_t data_bytes, int64_t* msg_bytes) {
+    if (!c) return SW_EINVAL;
+    if (K < 0 || data_bytes < 0) return fail(c, SW_EINVAL, "sw_pack_message_bound: negative count or length");
+    if (K > 0x7fffffff) return fail(c, SW_ERANGE, "sw_pack_message_bound: more than 2^31 events");
+    if (msg_bytes) *msg_bytes = wire_bound(c, K, data_bytes);
+    return SW_OK;
+}
+
+int sw_pack_message_device(sw_ctx* c, int64_t K, const uint8_t* d_head32, const uint8_t* d_id32, const uint8_t* d_sp_id32, const uint8_t* d_op_id32,
+                           const uint8_t* d_arity, const int32_t* d_creator, const double* d_t, const uint8_t* d_sig64, const uint8_t* d_data,
+                           const int64_t* d_data_off, int64_t data_bytes, const uint8_t* d_data_none, uint8_t* d_msg, int64_t msg_cap, int64_t* d_msg_len,
+                           void* user_stream) {
+    if (!c) return SW_EINVAL;
+    const char* what = "sw_pack_message_device";
+    const WireArrays a{d_head32, d_id32, d_sp_id32, d_op_id32, d_arity, d_creator, d_t, d_sig64, d_data, d_data_off, data_bytes, d_data_none};
+    CHK(wire_pack_pre(c, K, a, d_msg, what));
+    if (!d_msg_len) return fail(c, SW_EINVAL, "%s: d_msg_len is NULL", what);
+    const int64_t bound = wire_bound(c, K, data_bytes);
+    if (msg_cap < bound) return fail(c, SW_ERANGE, "%s: capacity %lld below sw_pack_message_bound's %lld (nothing written)", what, (long long)msg_cap, (long long)bound);
+    if (((uintptr_t)d_msg | (uintptr_t)d_sig64 | (uintptr_t)d_id32 | (uintptr_t)d_sp_id32 | (uintptr_t)d_op_id32) & 15)
+        return fail(c, SW_EINVAL, "%s: the message, the signatures and the id arrays must be 16-byte aligned", what);
+    if (((uintptr_t)d_msg_len | (uintptr_t)d_data_off | (uintptr_t)d_t) & 7) return fail(c, SW_EINVAL, "%s: the length, the offsets and the timestamps must be 8-byte aligned", what);
+    if ((uintptr_t)d_creator & 3) return fail(c, SW_EINVAL, "%s: the creators must be 4-byte aligned", what);
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t k = (size_t)K;
+    bool on = on_ctx_device(c, d_head32, 32) && on_ctx_device(c, d_msg, (size_t)msg_cap) && on_ctx_device(c, d_msg_len, 8);
+    if (K > 0)
+        on = on && on_ctx_device(c, d_id32, k * 32) && on_ctx_device(c, d_sp_id32, k * 32) && on_ctx_device(c, d_op_id32, k * 32) && on_ctx_device(c, d_arity, k) &&
+             on_ctx_device(c, d_creator, k * 4) && on_ctx_device(c, d_t, k * 8) && on_ctx_device(c, d_sig64, k * 64) &&
+             (!d_data_off || on_ctx_device(c, d_data_off, (k + 1) * 8)) && (!d_data || data_bytes == 0 || on_ctx_device(c, d_data, (size_t)data_bytes)) &&
+             (!d_data_none || on_ctx_device(c, d_data_none, k));
+    if (!on) return fail(c, SW_EINVAL, "%s: every array must lie in memory of device %d (a host pointer, or another device's)", what, c->device);
+    if (!c->ev_user) HIPCHK(c, hipEventCreateWithFlags(&c->ev_user, hipEventDisableTiming));
+    hipStream_t us = (hipStream_t)user_stream;
+    HIPCHK(c, hipEventRecord(c->ev_user, us));
+    HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_user, 0));
+    CHK(wire_pack_launch(c, K, a, d_msg, bound, d_msg_len, nullptr));
+    HIPCHK(c, hipEventRecord(c->ev_user, c->stream));
+    HIPCHK(c, hipStreamWaitEvent(us, c->ev_user, 0));
+    return SW_OK;
+}
+
+int sw_pack_message(sw_ctx* c, int64_t K, const uint8_t* head32, const uint8_t* id32, const uint8_t* sp_id32, const uint8_t* op_id32, const uint8_t* arity,
+                    const int32_t* creator, const double* t, const uint8_t* sig64, const uint8_t* data, const int64_t* data_off, int64_t data_bytes,
+                    const uint8_t* data_none, uint8_t* msg, int64_t msg_cap, int64_t* msg_bytes) {
+    if (!c) return SW_EINVAL;
+    const char* what = "sw_pack_message";
+    if (!msg_bytes) return fail(c, SW_EINVAL, "%s: msg_bytes is NULL", what);
+    *msg_bytes = 0;
+    CHK(wire_pack_pre(c, K, WireArrays{head32, id32, sp_id32, op_id32, arity, creator, t, sig64, data, data_off, data_bytes, data_none}, msg, what));
+    if (msg_cap < 0) return fail(c, SW_EINVAL, "%s: negative capacity", what);
+    HIPCHK(c, hipSetDevice(c->device));
+    const int64_t bound = wire_bound(c, K, data_bytes);
+    const size_t k = (size_t)K, db = (size_t)data_bytes;
+    Carve cv;
+    const size_t o_head = cv.take(32), o_id = cv.take(k * 32), o_sp = cv.take(k * 32), o_op = cv.take(k * 32), o_ar = cv.take(k), o_cr = cv.take(k * 4), o_t = cv.take(k * 8);
+    const size_t o_sig = cv.take(k * 64), o_doff = cv.take(data_off ? (k + 1) * 8 : 0), o_d = cv.take(db), o_dn = cv.take(data_none ? k : 0);
+    const size_t o_len = cv.take(8), o_m = cv.take((size_t)bound);
+    CHK(dgrow(c, c->d_wr_in, cv.off + 256, 0));
+    unsigned char* B = c->d_wr_in.p;
+    const struct { size_t o; const void* src; size_t bytes; } up[] = {
+        {o_head, head32, 32}, {o_id, id32, k * 32}, {o_sp, sp_id32, k * 32}, {o_op, op_id32, k * 32}, {o_ar, arity, k}, {o_cr, creator, k * 4}, {o_t, t, k * 8},
+        {o_sig, sig64, k * 64}, {o_doff, data_off, data_off ? (k + 1) * 8 : 0}, {o_d, data, db}, {o_dn, data_none, data_none ? k : 0}};
+    for (const auto& u : up)
+        if (u.bytes) HIPCHK(c, hipMemcpyAsync(B + u.o, u.src, u.bytes, hipMemcpyHostToDevice, c->stream));
+    unsigned long long* d_bad = nullptr;
+    CHK(wire_pack_launch(c, K, WireArrays{B + o_head, B + o_id, B + o_sp, B + o_op, B + o_ar, (const int32_t*)(B + o_cr), (const double*)(B + o_t), B + o_sig,
+                                          data_off ? B + o_d : nullptr, data_off ? (const int64_t*)(B + o_doff) : nullptr, data_bytes,
+                                          data_none ? B + o_dn : nullptr}, B + o_m, bound, (int64_t*)(B + o_len), &d_bad));
+    long long len = -1;
+    unsigned long long bad = 0;
+    HIPCHK(c, hipMemcpyAsync(&len, B + o_len, 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(&bad, d_bad, 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (len < 0)
+        return fail(c, SW_EINVAL, "%s: event %llu cannot be encoded (arity not 0 or 2, creator outside the %d members, or a data range that is unusable or longer than %d): no message",
+                    what, bad, c->n, wir::MAX_DATA);
+    if (len > bound) return fail(c, SW_EIO, "%s: length %lld beyond the bound %lld (internal error)", what, len, (long long)bound);
+    *msg_bytes = len;
+    if (len > msg_cap) return fail(c, SW_ERANGE, "%s: the message has %lld bytes, capacity %lld (nothing written)", what, len, (long long)msg_cap);
+    HIPCHK(c, hipMemcpyAsync(msg, B + o_m, (size_t)len, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    c->wr_pack_bytes += len;
+    return SW_OK;
+}
+
+int sw_unpack_message_device(sw_ctx* c, const uint8_t* d_msg, int64_t msg_bytes, int64_t cap_events, int64_t cap_data, uint8_t* d_head32, uint8_t* d_id32,
+                             uint8_t* d_sp_id32, uint8_t* d_op_id32, uint8_t* d_arity, int32_t* d_creator, double* d_t, uint8_t* d_sig64, uint8_t* d_data,
+                             int64_t* d_data_off, uint8_t* d_data_none, void* user_stream, int64_t* n_events, int64_t* n_data_bytes) {
+    if (!c) return SW_EINVAL;
+    const char* what = "sw_unpack_message_device";
+    const WireOut o{d_head32, d_id32, d_sp_id32, d_op_id32, d_arity, d_creator, d_t, d_sig64, d_data, d_data_off, d_data_none};
+    CHK(wire_unpack_pre(c, d_msg, msg_bytes, cap_events, cap_data, o, n_events, n_data_bytes, what));
+    *n_events = -1;
+    *n_data_bytes = 0;
+    if ((uintptr_t)d_data & 15) return fail(c, SW_EINVAL, "%s: the data buffer must be 16-byte aligned", what);
+    if (((uintptr_t)d_data_off | (uintptr_t)d_t) & 7) return fail(c, SW_EINVAL, "%s: the offsets and the timestamps must be 8-byte aligned", what);
+    if ((uintptr_t)d_creator & 3) return fail(c, SW_EINVAL, "%s: the creators must be 4-byte aligned", what);
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t k = (size_t)cap_events;
+    bool on = (msg_bytes == 0 || on_ctx_device(c, d_msg, (size_t)msg_bytes)) && on_ctx_device(c, d_head32, 32) && on_ctx_device(c, d_data_off, (k + 1) * 8) &&
+              (cap_data == 0 || on_ctx_device(c, d_data, (size_t)cap_data));
+    if (cap_events > 0)
+        on = on && on_ctx_device(c, d_id32, k * 32) && on_ctx_device(c, d_sp_id32, k * 32) && on_ctx_device(c, d_op_id32, k * 32) && on_ctx_device(c, d_arity, k) &&
+             on_ctx_device(c, d_creator, k * 4) && on_ctx_device(c, d_t, k * 8) && on_ctx_device(c, d_sig64, k * 64) && on_ctx_device(c, d_data_none, k);
+    if (!on) return fail(c, SW_EINVAL, "%s: every array must lie in memory of device %d (a host pointer, or another device's)", what, c->device);
+    if (!c->ev_user) HIPCHK(c, hipEventCreateWithFlags(&c->ev_user, hipEventDisableTiming));
+    hipStream_t us = (hipStream_t)user_stream;
+    HIPCHK(c, hipEventRecord(c->ev_user, us));
+    HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_user, 0));
+    const int rc = wire_unpack_run(c, d_msg, msg_bytes, cap_events, cap_data, o, n_events, n_data_bytes, what);
+    HIPCHK(c, hipEventRecord(c->ev_user, c->stream));
+    HIPCHK(c, hipStreamWaitEvent(us, c->ev_user, 0));
+    return rc;
+}
+
+int sw_unpack_message(sw_ctx* c, const uint8_t* msg, int64_t msg_bytes, int64_t cap_events, int64_t cap_data, uint8_t* head32, uint8_t* id32, uint8_t* sp_id32,
+                      uint8_t* op_id32, uint8_t* arity, int32_t* creator, double* t, uint8_t* sig64, uint8_t* data, int64_t* data_off, uint8_t* data_none,
+                      int64_t* n_events, int64_t* n_data_bytes) {
+    if (!c) return SW_EINVAL;
+    const char* what = "sw_unpack_message";
+    CHK(wire_unpack_pre(c, msg, msg_bytes, cap_events, cap_data, WireOut{head32, id32, sp_id32, op_id32, arity, creator, t, sig64, data, data_off, data_none},
+                        n_events, n_data_bytes, what));
+    *n_events = -1;
+    *n_data_bytes = 0;
+    HIPCHK(c, hipSetDevice(c->device));
+    // no more events or data bytes than the message can hold need room on the device
+    const int64_t ke = std::min<int64_t>(cap_events, msg_bytes / wir::REC_MIN), kd = std::min<int64_t>(cap_data, msg_bytes);
+    const size_t k = (size_t)ke;
+    Carve cv;
+    const size_t o_msg = cv.take((size_t)msg_bytes), o_head = cv.take(32), o_id = cv.take(k * 32), o_sp = cv.take(k * 32), o_op = cv.take(k * 32), o_ar = cv.take(k);
+    const size_t o_cr = cv.take(k * 4), o_t = cv.take(k * 8), o_sig = cv.take(k * 64), o_doff = cv.take((k + 1) * 8), o_dn = cv.take(k), o_d = cv.take((size_t)kd + 16);
+    CHK(dgrow(c, c->d_wr_in, cv.off + 256, 0));
+    unsigned char* B = c->d_wr_in.p;
+    if (msg_bytes) HIPCHK(c, hipMemcpyAsync(B + o_msg, msg, (size_t)msg_bytes, hipMemcpyHostToDevice, c->stream));
+    const WireOut o{B + o_head, B + o_id, B + o_sp, B + o_op, B + o_ar, (int32_t*)(B + o_cr), (double*)(B + o_t), B + o_sig, B + o_d, (int64_t*)(B + o_doff), B + o_dn};
+    int64_t K = -1, nd = 0;
+    const int rc = wire_unpack_run(c, B + o_msg, msg_bytes, ke, kd, o, &K, &nd, what);
+    *n_events = K;
+    *n_data_bytes = nd;
+    if (rc != SW_OK || K < 0) return rc;
+    const size_t kk = (size_t)K;
+    const struct { void* dst; size_t o; size_t bytes; } down[] = {
+        {head32, o_head, 32}, {id32, o_id, kk * 32}, {sp_id32, o_sp, kk * 32}, {op_id32, o_op, kk * 32}, {arity, o_ar, kk}, {creator, o_cr, kk * 4}, {t, o_t, kk * 8},
+        {sig64, o_sig, kk * 64}, {data_off, o_doff, (kk + 1) * 8}, {data_none, o_dn, kk}, {data, o_d, (size_t)nd}};
+    for (const auto& u : down)
+        if (u.bytes) HIPCHK(c, hipMemcpyAsync(u.dst, B + u.o, u.bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return SW_OK;
+}
+
+int sw_export_message_device(sw_ctx* c, int64_t head_event, const int32_t* d_known, const int32_t* d_cap, int with_data, uint8_t* d_msg, int64_t msg_cap,
+                             void* user_stream, int64_t* msg_bytes, int64_t* n_events) {
+    if (!c) return SW_EINVAL;
+    const char* what = "sw_export_message_device";
+    if (!msg_bytes || !n_events) return fail(c, SW_EINVAL, "%s: msg_bytes or n_events is NULL", what);
+    *msg_bytes = *n_events = 0;
+    if (msg_cap < 0 || (msg_cap > 0 && !d_msg)) return fail(c, SW_EINVAL, "%s: NULL message buffer (capacity %lld)", what, (long long)msg_cap);
+    HIPCHK(c, hipSetDevice(c->device));
+    if ((d_known && !on_ctx_device(c, d_known, (size_t)c->n * 4)) || (d_cap && !on_ctx_device(c, d_cap, (size_t)c->n * 4)) ||
+        (msg_cap > 0 && !on_ctx_device(c, d_msg, (size_t)msg_cap)))
+        return fail(c, SW_EINVAL, "%s: every array must lie in memory of device %d (a host pointer, or another device's)", what, c->device);
+    if (!c->ev_user) HIPCHK(c, hipEventCreateWithFlags(&c->ev_user, hipEventDisableTiming));
+    hipStream_t us = (hipStream_t)user_stream;
+    HIPCHK(c, hipEventRecord(c->ev_user, us));
+    HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_user, 0));
+    uint8_t* m = nullptr;
+    CHK(wire_export_run(c, head_event, d_known, d_cap, hipMemcpyDeviceToDevice, with_data != 0, what, &m, msg_bytes, n_events));
+    if (*msg_bytes > msg_cap) return fail(c, SW_ERANGE, "%s: the message has %lld bytes, capacity %lld (nothing written)", what, (long long)*msg_bytes, (long long)msg_cap);
+    HIPCHK(c, hipMemcpyAsync(d_msg, m, (size_t)*msg_bytes, hipMemcpyDeviceToDevice, c->stream));
+    HIPCHK(c, hipEventRecord(c->ev_user, c->stream));
+    HIPCHK(c, hipStreamWaitEvent(us, c->ev_user, 0));
+    return SW_OK;
+}
+
+int sw_export_message(sw_ctx* c, int64_t head_event, const int32_t* known, const int32_t* cap, int with_data, uint8_t* msg, int64_t msg_cap, int64_t* msg_bytes,
+                      int64_t* n_events) {
+    if (!c) return SW_EINVAL;
+    const char* what = "sw_export_message";
+    if (!msg_bytes || !n_events) return fail(c, SW_EINVAL, "%s: msg_bytes or n_events is NULL", what);
+    *msg_bytes = *n_events = 0;
+    if (msg_cap < 0 || (msg_cap > 0 && !msg)) return fail(c, SW_EINVAL, "%s: NULL message buffer (capacity %lld)", what, (long long)msg_cap);
+    HIPCHK(c, hipSetDevice(c->device));
+    uint8_t* m = nullptr;
+    CHK(wire_export_run(c, head_event, known, cap, hipMemcpyHostToDevice, with_data != 0, what, &m, msg_bytes, n_events));
+    if (*msg_bytes > msg_cap) return fail(c, SW_ERANGE, "%s: the message has %lld bytes, capacity %lld (nothing written)", what, (long long)*msg_bytes, (long long)msg_cap);
+    HIPCHK(c, hipMemcpyAsync(msg, m, (size_t)*msg_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return SW_OK;
+}
+
+int sw_ingest_message_device(sw_ctx* c, const uint8_t* d_msg, int64_t msg_bytes, int validate, int with_data, uint8_t* d_head32_out, int32_t* d_index_out,
+                             void* user_stream, int64_t* n_events, int64_t* n_valid, int64_t* n_stored) {
+    if (!c) return SW_EINVAL;
+    const char* what = "sw_ingest_message_device";
+    if (!n_events) return fail(c, SW_EINVAL, "%s: n_events is NULL", what);
+    *n_events = -1;
+    if (n_valid) *n_valid = 0;
+    if (n_stored) *n_stored = 0;
+    if (msg_bytes < 0 || (msg_bytes > 0 && !d_msg)) return fail(c, SW_EINVAL, "%s: NULL message (%lld bytes)", what, (long long)msg_bytes);
+    HIPCHK(c, hipSetDevice(c->device));
+    const size_t kcap = (size_t)(msg_bytes / wir::REC_MIN);
+    if ((msg_bytes > 0 && !on_ctx_device(c, d_msg, (size_t)msg_bytes)) || (d_head32_out && !on_ctx_device(c, d_head32_out, 32)) ||
+        (d_index_out && kcap && !on_ctx_device(c, d_index_out, kcap * 4)))
+        return fail(c, SW_EINVAL, "%s: every array must lie in memory of device %d (a host pointer, or another device's)", what, c->device);
+    if (!c->ev_user) HIPCHK(c, hipEventCreateWithFlags(&c->ev_user, hipEventDisableTiming));
+    hipStream_t us = (hipStream_t)user_stream;
+    HIPCHK(c, hipEventRecord(c->ev_user, us));
+    HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_user, 0));
+    uint8_t* d_head = nullptr;
+    CHK(wire_ingest_run(c, d_msg, msg_bytes, validate != 0, with_data != 0, what, &d_head, n_events, n_valid, n_stored));
+    if (*n_events < 0) return SW_OK;
+    if (d_head32_out) HIPCHK(c, hipMemcpyAsync(d_head32_out, d_head, 32, hipMemcpyDeviceToDevice, c->stream));
+    if (d_index_out && *n_events > 0) HIPCHK(c, hipMemcpyAsync(d_index_out, c->d_pl_in.p, (size_t)*n_events * 4, hipMemcpyDeviceToDevice, c->stream));
+    HIPCHK(c, hipEventRecord(c->ev_user, c->stream));
+    HIPCHK(c, hipStreamWaitEvent(us, c->ev_user, 0));
+    return SW_OK;
+}
+
+int sw_ingest_message(sw_ctx* c, const uint8_t* msg, int64_t msg_bytes, int validate, int with_data, uint8_t* head32_out, int32_t* index_out, int64_t* n_events,
+                      int64_t* n_valid, int64_t* n_stored) {
+    if (!c) return SW_EINVAL;
+    const char* what = "sw_ingest_message";
+    if (!n_events) return fail(c, SW_EINVAL, "%s: n_events is NULL", what);
+    *n_events = -1;
+    if (n_valid) *n_valid = 0;
+    if (n_stored) *n_stored = 0;
+    if (msg_bytes < 0 || (msg_bytes > 0 && !msg)) return fail(c, SW_EINVAL, "%s: NULL message (%lld bytes)", what, (long long)msg_bytes);
+    HIPCHK(c, hipSetDevice(c->device));
+    CHK(dgrow(c, c->d_wr_in, (size_t)msg_bytes + 256, 0));
+    if (msg_bytes) HIPCHK(c, hipMemcpyAsync(c->d_wr_in.p, msg, (size_t)msg_bytes, hipMemcpyHostToDevice, c->stream));
+    uint8_t* d_head = nullptr;
+    CHK(wire_ingest_run(c, c->d_wr_in.p, msg_bytes, validate != 0, with_data != 0, what, &d_head, n_events, n_valid, n_stored));
+    if (*n_events < 0) return SW_OK;
+    if (head32_out) HIPCHK(c, hipMemcpyAsync(head32_out, d_head, 32, hipMemcpyDeviceToHost, c->stream));
+    if (index_out && *n_events > 0) HIPCHK(c, hipMemcpyAsync(index_out, c->d_pl_in.p, (size_t)*n_events * 4, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return SW_OK;
+}
+
+int sw_get_wire_stats(sw_ctx* c, int64_t* pack_calls, int64_t* pack_events, int64_t* pack_bytes, int64_t* unpack_calls, int64_t* unpack_events, int64_t* refused) {
+    if (!c) return SW_EINVAL;
+    if (pack_calls) *pack_calls = c->wr_pack_calls;
+    if (pack_events) *pack_events = c->wr_pack_events;
+    if (pack_bytes) *pack_bytes = c->wr_pack_bytes;
+    if (unpack_calls) *unpack_calls = c->wr_unpack_calls;
+    if (unpack_events) *unpack_events = c->wr_unpack_events;
+    if (refused) *refused = c->wr_refused;
     return SW_OK;
 }
 

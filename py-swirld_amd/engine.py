@@ -807,6 +807,152 @@ class Hashgraph:
         d.update(zip(("scan_ms", "write_ms"), (float(x) for x in ms)))
         return d
 
+    # ---- the wire bytes of a sync answer (dumps((head, subset)), swirld.py:166; loads, swirld.py:129; csrc/wire.hip.h) ----
+    def pack_message_bound(self, K, data_bytes=0):
+        """Upper bound of the message of any K events with data_bytes bytes of data."""
+        m = C.c_int64()
+        self._chk(self._L.sw_pack_message_bound(self._h, int(K), int(data_bytes), C.byref(m)))
+        return int(m.value)
+
+    def pack_message(self, head_id, ids, sp_ids, op_ids, arity, creator, t, sig, data=None, data_off=None, data_none=None):
+        """The canonical wire form of (head, {id: Event}) from host arrays (sw_pack_message), as bytes: any pickle.loads reads
+        it.  The arrays are pack_events' plus the ids and the head's id (32 bytes).  One event that cannot be encoded makes
+        the message unbuildable: SwirldHipError -22 names it."""
+        arity = np.ascontiguousarray(arity, np.uint8)
+        K = arity.shape[0]
+        head = self._ids(head_id, 1)
+        ids, sp_ids, op_ids = self._ids(ids, K), self._ids(sp_ids, K), self._ids(op_ids, K)
+        creator = np.ascontiguousarray(creator, np.int32)
+        t = np.ascontiguousarray(t, np.float64)
+        sig = np.ascontiguousarray(sig, np.uint8).reshape(K, 64)
+        if creator.shape != (K,) or t.shape != (K,):
+            raise ValueError("creator and t must have one entry per event")
+        nbytes = 0
+        if data_off is not None:
+            data_off = np.ascontiguousarray(data_off, np.int64)
+            if data_off.shape != (K + 1,):
+                raise ValueError("data_off must have K + 1 entries")
+            data = np.zeros(0, np.uint8) if data is None else np.ascontiguousarray(data, np.uint8).reshape(-1)
+            nbytes = data.shape[0]
+            if nbytes == 0:
+                data = None
+            if data_none is not None:
+                data_none = np.ascontiguousarray(data_none, np.uint8)
+                if data_none.shape != (K,):
+                    raise ValueError("data_none must have one entry per event")
+        elif data is not None or data_none is not None:
+            raise ValueError("data needs data_off")
+        cap = self.pack_message_bound(K, nbytes)
+        msg = np.empty(cap, np.uint8)
+        n = C.c_int64()
+        self._chk(self._L.sw_pack_message(self._h, K, _p(head), _p(ids), _p(sp_ids), _p(op_ids), _p(arity), _p(creator), _p(t), _p(sig), _p(data),
+                                          _p(data_off), nbytes, _p(data_none), _p(msg), cap, C.byref(n)))
+        return msg[:n.value].tobytes()
+
+    def pack_message_device(self, head_id, ids, sp_ids, op_ids, arity, creator, t, sig, msg, msg_cap, msg_len, data=None, data_off=None,
+                            data_bytes=0, data_none=None, stream=0, count=None):
+        """pack_message between DEVICE arrays (sw_pack_message_device), as export_walk_device and gather_event_data_device
+        leave them.  msg: uint8, msg_cap bytes (at least pack_message_bound's), 16-byte aligned; msg_len: one int64 that
+        receives the length, or -1 when an event cannot be encoded (msg is then not written).  Nothing is read back."""
+        ptrs = [_dev_ptr(a) for a in (head_id, ids, sp_ids, op_ids, arity, creator, t, sig, data, data_off, data_none, msg, msg_len)]
+        K = count if count is not None else ptrs[5][1]
+        if K is None:
+            raise ValueError("the number of events is not known: pass count=")
+        a = [C.c_void_p(q) if q else None for q, _ in ptrs]
+        self._chk(self._L.sw_pack_message_device(self._h, int(K), *a[:10], int(data_bytes), a[10], a[11], int(msg_cap), a[12], C.c_void_p(int(stream))))
+
+    def unpack_message(self, msg, cap_events=None, cap_data=None):
+        """The strict reader (sw_unpack_message): None for bytes that are not the canonical form under this context's event
+        class, else a dict of host arrays: head (32 uint8), ids / sp_ids / op_ids (K x 32), arity, creator (member index by
+        set_member_keys' table, -1 for a key of no member), t, sig (K x 64), data, data_off (K + 1), data_none.  Nothing of
+        `msg` is ever unpickled.  Capacities default to what a message of this length can hold; a smaller one that does not
+        suffice raises SwirldHipError -34."""
+        buf = np.frombuffer(bytes(msg), np.uint8)
+        nb = buf.shape[0]
+        ke = nb // 150 if cap_events is None else int(cap_events)
+        kd = nb if cap_data is None else int(cap_data)
+        d = dict(head=np.zeros(32, np.uint8), ids=np.zeros((ke, 32), np.uint8), sp_ids=np.zeros((ke, 32), np.uint8), op_ids=np.zeros((ke, 32), np.uint8),
+                 arity=np.zeros(ke, np.uint8), creator=np.zeros(ke, np.int32), t=np.zeros(ke, np.float64), sig=np.zeros((ke, 64), np.uint8),
+                 data=np.zeros(kd, np.uint8), data_off=np.zeros(ke + 1, np.int64), data_none=np.zeros(ke, np.uint8))
+        n, m = C.c_int64(), C.c_int64()
+        self._chk(self._L.sw_unpack_message(self._h, _p(buf) if nb else None, nb, ke, kd,
+                                            *[_p(d[k]) for k in ("head", "ids", "sp_ids", "op_ids", "arity", "creator", "t", "sig", "data", "data_off", "data_none")],
+                                            C.byref(n), C.byref(m)))
+        K = int(n.value)
+        if K < 0:
+            return None
+        out = {k: (v if k == "head" else v[:K]) for k, v in d.items()}
+        out["data_off"] = d["data_off"][:K + 1]
+        out["data"] = d["data"][:int(m.value)]
+        return out
+
+    def unpack_message_device(self, msg, msg_bytes, cap_events, cap_data, head_id, ids, sp_ids, op_ids, arity, creator, t, sig, data, data_off,
+                              data_none, stream=0):
+        """unpack_message between DEVICE arrays (sw_unpack_message_device): data 16-byte aligned, data_off cap_events + 1
+        entries.  Returns (n_events, n_data_bytes); n_events -1: not canonical, nothing promised about the arrays."""
+        a = [C.c_void_p(q) if q else None for q in (_dev_ptr(x)[0] for x in (msg, head_id, ids, sp_ids, op_ids, arity, creator, t, sig, data, data_off,
+                                                                               data_none))]
+        n, m = C.c_int64(), C.c_int64()
+        self._chk(self._L.sw_unpack_message_device(self._h, a[0], int(msg_bytes), int(cap_events), int(cap_data), *a[1:], C.c_void_p(int(stream)),
+                                                   C.byref(n), C.byref(m)))
+        return int(n.value), int(m.value)
+
+    def export_message(self, head, known=None, cap=None, *, data=True, want_count=False):
+        """Node.ask_sync's reply body for the events of sync_walk(head, known, cap), built on the device in one call
+        (sw_export_message): walk, export, data gather (data=False: every d is None) and the wire bytes.  Returns bytes."""
+        kn, cp = self._heights_arg(known, "known"), self._heights_arg(cap, "cap")
+        nb, ne = C.c_int64(), C.c_int64()
+        msg = getattr(self, "_wire_buf", None)      # kept between calls: a message that does not fit costs one more call, once
+        if msg is None:
+            msg = self._wire_buf = np.empty(1 << 20, np.uint8)
+        rc = self._L.sw_export_message(self._h, int(head), _p(kn), _p(cp), 1 if data else 0, _p(msg), msg.shape[0], C.byref(nb), C.byref(ne))
+        if rc == -34 and nb.value > msg.shape[0]:
+            msg = self._wire_buf = np.empty(int(nb.value) + int(nb.value) // 4, np.uint8)
+            rc = self._L.sw_export_message(self._h, int(head), _p(kn), _p(cp), 1 if data else 0, _p(msg), msg.shape[0], C.byref(nb), C.byref(ne))
+        self._chk(rc)
+        out = msg[:nb.value].tobytes()
+        return (out, int(ne.value)) if want_count else out
+
+    def export_message_device(self, head, known, cap, msg, msg_cap, *, data=True, stream=0):
+        """export_message into DEVICE memory (`known`, `cap`: n int32 in device memory, or None).  Returns (msg_bytes,
+        n_events); a message longer than msg_cap raises SwirldHipError -34 and writes nothing."""
+        a = [C.c_void_p(q) if q else None for q in (_dev_ptr(x)[0] for x in (known, cap, msg))]
+        nb, ne = C.c_int64(), C.c_int64()
+        self._chk(self._L.sw_export_message_device(self._h, int(head), a[0], a[1], 1 if data else 0, a[2], int(msg_cap), C.c_void_p(int(stream)),
+                                                   C.byref(nb), C.byref(ne)))
+        return int(nb.value), int(ne.value)
+
+    def ingest_message(self, msg, validate=True, *, data=True):
+        """Node.sync's intake of a reply body in the canonical wire form (sw_ingest_message): strict unpack, with `validate`
+        the signed bytes built and judged by my keys and event class, then ingest_payload (data=True keeps the data).
+        Returns None for bytes that are not canonical (nothing stored, nothing unpickled), else a dict: head (32 bytes),
+        index (ingest_payload's codes per event of the message), n_events, n_valid (validate only), n_stored."""
+        buf = np.frombuffer(bytes(msg), np.uint8)
+        nb = buf.shape[0]
+        head, index = np.zeros(32, np.uint8), np.zeros(nb // 150 + 1, np.int32)
+        ne, nv, ns = C.c_int64(), C.c_int64(), C.c_int64()
+        self._chk(self._L.sw_ingest_message(self._h, _p(buf) if nb else None, nb, 1 if validate else 0, 1 if data else 0, _p(head), _p(index),
+                                            C.byref(ne), C.byref(nv), C.byref(ns)))
+        K = int(ne.value)
+        if K < 0:
+            return None
+        return dict(head=head.tobytes(), index=index[:K].copy(), n_events=K, n_valid=int(nv.value) if validate else None, n_stored=int(ns.value))
+
+    def ingest_message_device(self, msg, msg_bytes, validate=True, *, data=True, head_id=None, index=None, stream=0):
+        """ingest_message for a message in DEVICE memory; head_id (32 uint8) and index (msg_bytes // 150 int32 at least) are
+        optional device arrays.  Returns (n_events, n_valid, n_stored); n_events -1: not canonical, nothing stored."""
+        a = [C.c_void_p(q) if q else None for q in (_dev_ptr(x)[0] for x in (msg, head_id, index))]
+        ne, nv, ns = C.c_int64(), C.c_int64(), C.c_int64()
+        self._chk(self._L.sw_ingest_message_device(self._h, a[0], int(msg_bytes), 1 if validate else 0, 1 if data else 0, a[1], a[2],
+                                                   C.c_void_p(int(stream)), C.byref(ne), C.byref(nv), C.byref(ns)))
+        return int(ne.value), int(nv.value), int(ns.value)
+
+    def wire_stats(self):
+        """Message writer calls, events and bytes (forms that know the length), reader calls, events, refused messages."""
+        v = [C.c_int64() for _ in range(6)]
+        self._chk(self._L.sw_get_wire_stats(self._h, *[C.byref(x) for x in v]))
+        return dict(zip(("pack_calls", "pack_events", "pack_bytes", "unpack_calls", "unpack_events", "refused"), (int(x.value) for x in v)))
+
     # ---- creating signed events (Node.new_event, swirld.py:82-95, for a batch; csrc/sign.hip.h) ----
     def set_signing_seeds(self, members, seeds):
         """The Ed25519 seeds (32 bytes each: K x 32 uint8, or K byte strings) of the members this context may sign for

@@ -49,6 +49,15 @@ def majority(it):
 Event = namedtuple("Event", "d p t c s")  # payload, parents, time, creator pk, signature
 
 
+def _wire_prefix(cls):
+    """The first bytes of the canonical wire form of a sync reply under the event class `cls` (csrc/wire.hip.h)."""
+    m, q = cls.__module__.encode("utf-8"), cls.__qualname__.encode("utf-8")
+    return b"\x80\x04\x8c" + bytes([len(m)]) + m + b"\x8c" + bytes([len(q)]) + q + b"\x93\x940\x8e"
+
+
+WIRE_PREFIX = _wire_prefix(Event)
+
+
 class _RoundView(Mapping):
     """Node.round: {event hash -> round number} (swirld.py:51-52)."""
 
@@ -281,6 +290,15 @@ class Node:
     # payload fall back to the host routes, and the store holds None for it: hg[h].d stays the truth for such events.
     device_data = False
     MAX_DEVICE_DATA = 60000
+    # The body of a sync reply built and parsed on the device (Hashgraph.export_message / unpack_message, csrc/wire.hip.h)
+    # instead of dumps((head, subset)) / loads(reply).  The canonical wire form is a pickle any peer's loads reads, so a
+    # node with the switch on talks to nodes without it.  ask_sync: under device_sync_walk's precondition, and only while
+    # every stored event has the shape the device can write (_is_plain_or_data) and the data store can be caught up
+    # (device_data, or every d None); otherwise the call takes the routes below.  sync: a reply that starts with the
+    # canonical header goes to the strict reader and NEVER to pickle.loads (a reply the reader refuses adds nothing); its
+    # arrays take _batch_validate_plain's pack + validate and ingest_payload, and Event objects are built for the stored
+    # events only.  Any other reply is unpickled as before.
+    device_wire = False
 
     def __init__(self, kp, network, n_nodes, stake, device=0, accept_forks=True):
         self.pk, self.sk = kp
@@ -320,6 +338,11 @@ class Node:
         self._uploaded = 0
         self._dev_ids = 0     # events whose id the device context knows (device_payload_threshold)
         self._dev_data = 0    # events whose data the device context holds (device_data)
+        self._wire_checked = 0         # stored events judged for device_wire so far: those the device cannot write, those with data
+        self._wire_unfit = 0
+        self._wire_with_data = 0
+        self._wire_replies = 0         # ask_sync replies built on the device; sync replies read by the strict reader
+        self._wire_intakes = 0
         self._device_payloads = 0
         self._keys_on_device = False   # the context has the members' keys and the Event class (device_validate_threshold)
         self._plain_payloads = 0       # payloads whose signed bytes the device built (_batch_validate_plain)
@@ -408,14 +431,18 @@ class Node:
         ids = hash_batch(whole, device=self._device)
         return {eid: (bool(ok[i]) and good[i], ids[i]) for i, eid in enumerate(eids)}
 
-    def _batch_validate(self, eids, events):
-        """{event id -> (valid, id)} for a whole sync payload from ONE device call (Hashgraph.validate_payload): valid =
-        signed by its creator, a member, and hashing to its id.  dumps(ev[:-1]) and dumps(ev) are packed once; malformed
-        events (wrong types or lengths) are simply invalid."""
+    def _ensure_keys(self):
+        """The context has the members' keys and the Event class from the first call on."""
         if not self._keys_on_device:
             self._dev.set_member_keys([bytes(pk) for pk in self._members])
             self._dev.set_event_class(Event.__module__, Event.__qualname__)
             self._keys_on_device = True
+
+    def _batch_validate(self, eids, events):
+        """{event id -> (valid, id)} for a whole sync payload from ONE device call (Hashgraph.validate_payload): valid =
+        signed by its creator, a member, and hashing to its id.  dumps(ev[:-1]) and dumps(ev) are packed once; malformed
+        events (wrong types or lengths) are simply invalid."""
+        self._ensure_keys()
         if all(self._is_plain(eid, events[eid]) for eid in eids):
             return self._batch_validate_plain(eids, events)
         if self.device_data and all(self._is_plain_or_data(eid, events[eid]) for eid in eids):
@@ -541,7 +568,13 @@ class Node:
         (swirld.py:122-146)."""
         request = crypto.sign(dumps(self._known_heights()), self.sk)
         reply = crypto.sign_open(self.network[pk](self.pk, request), pk)
+        if self.device_wire and bytes(reply[:len(WIRE_PREFIX)]) == WIRE_PREFIX:
+            return self._sync_wire(bytes(reply), payload)
         remote_head, remote_hg = loads(reply)
+        return self._sync_events(remote_head, remote_hg, payload)
+
+    def _sync_events(self, remote_head, remote_hg, payload):
+        """sync behind the reply's decoding: validate and store the unknown events of remote_hg, then the new event."""
         unknown = remote_hg.keys() - self.hg.keys()
         thr = self.device_crypto_threshold
         if not crypto.HAVE_SODIUM:  # stand-in signatures are keyed hashes: the device verifier (real Ed25519) would refuse all of them
@@ -569,10 +602,7 @@ class Node:
     def _sync_payload_device(self, eids, remote_hg, crypto_thr, validate_thr=None):
         """The unknown events of a sync payload, in any order, through Hashgraph.ingest_payload; returns the ids stored,
         in the order they were added."""
-        self._flush()
-        if self._dev_ids < len(self._ids):   # events added one by one since the last payload: the context learns their ids
-            self._dev.set_event_ids(self._dev_ids, np.frombuffer(b"".join(self._ids[self._dev_ids:]), np.uint8).reshape(-1, 32))
-            self._dev_ids = len(self._ids)
+        self._catch_up_ids()
         is32 = lambda x: isinstance(x, (bytes, bytearray)) and len(x) == 32
         eids = [e for e in eids if is32(e)]   # (anything else cannot be the BLAKE2b-256 of an event)
         K = len(eids)
@@ -618,6 +648,69 @@ class Node:
         self._dev_ids = len(self._ids)
         return added
 
+    def _catch_up_ids(self):
+        """The context holds every stored event, and learns the ids of those added one by one since the last payload."""
+        self._flush()
+        if self._dev_ids < len(self._ids):
+            self._dev.set_event_ids(self._dev_ids, np.frombuffer(b"".join(self._ids[self._dev_ids:]), np.uint8).reshape(-1, 32))
+            self._dev_ids = len(self._ids)
+
+    def _sync_wire(self, reply, payload):
+        """sync for a reply in the canonical wire form (device_wire): the strict reader on the device, no unpickling."""
+        self._ensure_keys()
+        u = self._dev.unpack_message(reply)
+        self._wire_intakes += 1
+        if u is None:         # the canonical header in front of something the writer never writes: nothing is taken from it
+            return ()
+        remote_head = u["head"].tobytes()
+        eids = [bytes(r) for r in u["ids"]]
+        unknown = [i for i, e in enumerate(eids) if e not in self.hg]
+        datas = _unpack_data(u["data"], u["data_off"], u["data_none"]) if not u["data_none"].all() else None
+
+        def event(i):
+            p = (u["sp_ids"][i].tobytes(), u["op_ids"][i].tobytes()) if u["arity"][i] else ()
+            c = int(u["creator"][i])
+            # (the key of no member: the event is invalid whatever stands here, and is never stored)
+            return Event(None if datas is None else datas[i], p, float(u["t"][i]), self._members[c] if c >= 0 else b"", u["sig"][i].tobytes())
+
+        remote_hg = {}
+        if remote_head in self.hg:
+            remote_hg[remote_head] = self.hg[remote_head]
+        if not (self._validate_threshold() is not None and self.accept_forks and (self.device_data or datas is None)):
+            # the array route does not apply: Event objects for the unknown events, then the host routes
+            for i in unknown:
+                remote_hg.setdefault(eids[i], event(i))
+            return self._sync_events(remote_head, remote_hg, payload)
+        added = []
+        if unknown:
+            self._catch_up_ids()
+            self._catch_up_data()
+            sel = np.asarray(unknown)
+            ids, sp, op, arity, creator, t, sig = (np.ascontiguousarray(u[k][sel]) for k in ("ids", "sp_ids", "op_ids", "arity", "creator", "t", "sig"))
+            kw = {}
+            if datas is not None:
+                lens = np.diff(u["data_off"])[sel]
+                off = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+                src = np.repeat(u["data_off"][:-1][sel] - off[:-1], lens) + np.arange(int(off[-1]))
+                kw = dict(data=np.ascontiguousarray(u["data"][src]), data_off=off, data_none=np.ascontiguousarray(u["data_none"][sel]))
+            msgs, moff, whole, woff, enc = self._dev.pack_events(sp, op, arity, creator, t, sig, **kw)
+            ok = self._dev.validate_payload((msgs, moff), sig, creator, whole=(whole, woff), ids=ids)
+            self._plain_payloads += 1
+            ok = (np.asarray(ok, bool) & np.asarray(enc, bool)).astype(np.uint8)
+            out, n_stored = self._dev.ingest_payload(ids, sp, op, arity, creator, ok, t, sig, **(kw if self.device_data else {}))
+            self._device_payloads += 1
+            for j in np.argsort(out, kind="stable")[len(unknown) - n_stored:] if n_stored else ():
+                i = unknown[int(j)]
+                assert out[j] == len(self._ids)
+                remote_hg[eids[i]] = event(i)
+                self._add_event_host(eids[i], remote_hg[eids[i]])
+                added.append(eids[i])
+            self._uploaded += n_stored
+            self._dev_ids = len(self._ids)
+            if self.device_data:
+                self._dev_data = len(self._ids)
+        return self._sync_finish(added, remote_head, remote_hg, payload)
+
     def _sync_finish(self, added, remote_head, remote_hg, payload):
         if remote_head in remote_hg and self.is_valid_event(remote_head, remote_hg[remote_head]):
             h, ev = self.new_event(payload, (self.head, remote_head))
@@ -631,7 +724,7 @@ class Node:
         """Answer a sync request with every event the asker cannot know yet: walk back from
         my head, not descending below what the asker reported per member (swirld.py:148-161)."""
         asker_heights = loads(crypto.sign_open(info, pk))
-        if (self.device_sync_walk and self._index[self.head] < self._divided
+        if ((self.device_wire or self.device_sync_walk) and self._index[self.head] < self._divided
                 and all(isinstance(h, int) for h in asker_heights.values())):
             # the BFS below on the device (Hashgraph.sync_walk), trunk rule included; the reply holds the same events, in
             # ascending dense index instead of BFS order
@@ -645,6 +738,12 @@ class Node:
                 cap = np.full(self.n, 0x7FFFFFFF, np.int32)
                 for creator, th in self._trunk_height.items():
                     cap[self._mindex[creator]] = th
+            if self.device_wire and self._wire_ready():
+                # ... and the reply's bytes with it (Hashgraph.export_message): no dict entry per event, no dumps
+                self._wire_replies += 1
+                return crypto.sign(self._dev.export_message(self._index[self.head], known, cap, data=self.device_data), self.sk)
+        if (self.device_sync_walk and self._index[self.head] < self._divided
+                and all(isinstance(h, int) for h in asker_heights.values())):
             subset = {}
             for i in self._dev.sync_walk(self._index[self.head], known, cap).tolist():
                 subset[self._ids[i]] = self.hg[self._ids[i]]
@@ -689,6 +788,24 @@ class Node:
         for eid in bfs((self.head,), missing_parents):
             subset[eid] = self.hg[eid]
         return crypto.sign(dumps((self.head, subset)), self.sk)
+
+    def _wire_ready(self):
+        """device_wire: every stored event is one the device can write, and ids, data store and keys are caught up."""
+        if not all(type(pk) is bytes and len(pk) == 32 for pk in self._members):
+            return False
+        for h in self._ids[self._wire_checked:]:
+            ev = self.hg[h]
+            if not self._is_plain_or_data(h, ev):
+                self._wire_unfit += 1
+            elif ev.d is not None:
+                self._wire_with_data += 1
+        self._wire_checked = len(self._ids)
+        if self._wire_unfit or (self._wire_with_data and not self.device_data):
+            return False
+        self._catch_up_ids()
+        self._catch_up_data()
+        self._ensure_keys()
+        return True
 
     def ancestors(self, c):
         """Self-parent chain of c, newest first (swirld.py:163-168)."""
