@@ -811,6 +811,69 @@ int sw_create_events(sw_ctx* ctx, int64_t K, const int32_t* creator, const int32
                      int64_t* first_out, uint8_t* id32, uint8_t* sig64);
 int sw_get_sign_stats(sw_ctx* ctx, int64_t* calls, int64_t* events, int64_t* levels, int64_t* key_sets, double* phase_ms);
 
+/*
+ * ONE event signed by one wavefront, and the GOSSIP TURN around it (kernels in csrc/turn.hip.h): what a
+ * node does per step (swirld.py:322-328, 125-146) — sync with a peer, create one event on its own head and the peer's,
+ * divide_rounds, decide_fame, find_order — as one call between two contexts of one GPU.  sw_create_events gives an event
+ * one lane; here the 64 lanes of a wave share the base-point multiplication of its signature (one radix-16 digit each, a
+ * butterfly of six complete additions).  Signature and id are bit for bit those of sw_sign_events.
+ *
+ * sw_create_event   one event of `member` at time t: both parents -1 a root, otherwise both stored events (dense indices).
+ *   data_len < 0: data None; otherwise data_len bytes at `data` (host memory; 0 .. 60 000).  Preconditions, verdicts,
+ *   refusal codes, commit order (ids, append, data when the store is complete) and atomicity are those of
+ *   sw_create_events with K = 1 for the same event, and the context is left in the state that call would leave.
+ *   *index_out, id32_out[32], sig64_out[64] (host memory, any may be NULL) receive the dense index, the id and the
+ *   signature.  Synchronises once for the verdict, then as the commit does.
+ * sw_gossip_turn   `dst` (the node of `member`, at its head dst_head) syncs with `src` (at its head src_head) and creates
+ *   the event (data, (dst_head, src_head's event), t, member).  DEFINED BY EQUIVALENCE: dst is left in the state of
+ *     1. sw_sync_pull_walk(dst, dst_head, src, src_head, SW_TURN_TRUNKS, SW_TURN_VALIDATE, SW_TURN_DATA, ..);
+ *     2. the index of src_head's id in dst's id index — looked up on the device; the created event's other parent reaches
+ *        the signer from device memory;
+ *     3. when that id is present: sw_create_event(dst, member, dst_head, that index, t, data, data_len, ..); when it is
+ *        absent (under SW_TURN_VALIDATE: dst rejected it, the reference's is_valid_event(remote_head) false) no event is
+ *        created, new_head = -1 and the call returns SW_OK;
+ *     4. unless SW_TURN_NO_CONSENSUS: sw_divide_rounds(dst, N_before, n_stored + created), sw_decide_fame into
+ *        new_rounds[cap_rounds], sw_find_order of those rounds;
+ *   and src is left untouched as those calls leave it.  REFUSALS are judged before anything is launched or stored:
+ *   SW_EINVAL for dst == src, differing member counts, dst_head not an event of `member` (swirld.py:86), src_head an event
+ *   of `member` (swirld.py:87), undivided events in dst, data_len above 60 000, unknown flag bits, a NULL or short result;
+ *   SW_ENOTSUP for no signing key of `member`, no member keys, an incomplete id index on either side, SW_TURN_DATA with
+ *   an incomplete data store on either side, a windowed context on either side, contexts on different devices.  Every
+ *   other refusal is that of the call it comes from.  A failure behind the pull keeps what the pull stored (as the
+ *   reference's sync does); result.stage says how far the turn got.  The head lookup and the event's verdict share one
+ *   read-back: the turn adds no synchronisation to those of the composed calls and saves the lookup's.
+ *   `result` receives min(result_bytes, sizeof(sw_turn_result)) bytes (fields are only ever appended; at least the
+ *   first 8 bytes must fit: SW_EINVAL).
+ * sw_get_turn_stats   sw_create_event calls, events the wave signed, sw_gossip_turn calls, launches that were stamped;
+ *   stamps[8]: under sw_set_profiling the signer's lane 0 stores wall_clock64() at its phase boundaries — entry, key and
+ *   prefix loaded, first SHA-512 + reduce, base multiplication, inversion + encode, second SHA-512 + reduce, sc_muladd,
+ *   BLAKE2b id — and these are the last stamped launch's; *tick_ns the length of a tick in ns.  Any pointer may be NULL.
+ */
+#define SW_TURN_VALIDATE      1   /* the pull validates against dst's member keys (sw_sync_pull_walk's `validate`)      */
+#define SW_TURN_DATA          2   /* events travel with their data into dst's data store (`data`)                       */
+#define SW_TURN_TRUNKS        4   /* src caps its walk by its fork trunks (`use_trunks`)                                */
+#define SW_TURN_NO_CONSENSUS  8   /* stop behind the created event: no divide_rounds, decide_fame, find_order           */
+/* sw_turn_result.stage: the last step that completed */
+#define SW_TURN_STAGE_NONE     0  /* refused, or the pull failed: nothing stored                                        */
+#define SW_TURN_STAGE_PULLED   1  /* the pull stored n_stored events                                                    */
+#define SW_TURN_STAGE_CREATED  2  /* ... and the event exists (or src_head is absent: new_head = -1)                    */
+#define SW_TURN_STAGE_DIVIDED  3
+#define SW_TURN_STAGE_FAME     4
+#define SW_TURN_STAGE_ORDERED  5  /* the whole turn                                                                     */
+typedef struct sw_turn_result {
+    int64_t n_sent, n_valid, n_stored;   /* of the pull (n_valid only under SW_TURN_VALIDATE)                           */
+    int64_t new_head;                    /* dense index of the created event in dst, or -1                              */
+    int64_t n_new_rounds;                /* rounds sw_decide_fame added to the consensus (written to new_rounds)        */
+    int64_t n_ordered;                   /* events ordered by this turn                                                 */
+    int64_t stage;
+} sw_turn_result;
+int sw_create_event(sw_ctx* ctx, int member, int64_t self_parent, int64_t other_parent, double t, const uint8_t* data,
+                    int64_t data_len, int64_t* index_out, uint8_t* id32_out, uint8_t* sig64_out);
+int sw_gossip_turn(sw_ctx* dst, int member, int64_t dst_head, sw_ctx* src, int64_t src_head, double t, const uint8_t* data,
+                   int64_t data_len, int flags, int32_t* new_rounds, int cap_rounds, void* result, size_t result_bytes);
+int sw_get_turn_stats(sw_ctx* ctx, int64_t* create_calls, int64_t* events, int64_t* turns, int64_t* stamped, uint64_t* stamps,
+                      double* tick_ns);
+
 /* Exact work counters of the calls so far: used by bench.py's roofline. */
 typedef struct sw_counters {
     int64_t events_divided;      /* events through divide_rounds                          */

@@ -27,6 +27,15 @@ class Counters(C.Structure):
         "gated_calls", "gated_idle_iterations")]
 
 
+# sw_gossip_turn's flags and stages (include/swirld_hip.h)
+SW_TURN_VALIDATE, SW_TURN_DATA, SW_TURN_TRUNKS, SW_TURN_NO_CONSENSUS = 1, 2, 4, 8
+SW_TURN_STAGE_NONE, SW_TURN_STAGE_PULLED, SW_TURN_STAGE_CREATED, SW_TURN_STAGE_DIVIDED, SW_TURN_STAGE_FAME, SW_TURN_STAGE_ORDERED = range(6)
+
+
+class TurnResult(C.Structure):
+    _fields_ = [(k, C.c_int64) for k in ("n_sent", "n_valid", "n_stored", "new_head", "n_new_rounds", "n_ordered", "stage")]
+
+
 class Timings(C.Structure):
     _fields_ = [("can_see_ms", C.c_float), ("rounds_ms", C.c_float), ("tally_ms", C.c_float),
                 ("tally_launches", C.c_int32), ("finalize_ms", C.c_float), ("fame_ms", C.c_float),
@@ -139,6 +148,11 @@ SIGNATURES = {
     "sw_create_events_device": (C.c_int, [_P, C.c_int64, _P, _P, _P, _P, _P, _P, C.c_int64, _P, _P, C.POINTER(C.c_int64), _P, _P]),
     "sw_create_events": (C.c_int, [_P, C.c_int64, _P, _P, _P, _P, _P, _P, C.c_int64, _P, C.POINTER(C.c_int64), _P, _P]),
     "sw_get_sign_stats": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), _P]),
+    # one event signed by one wavefront, and the gossip turn around it (csrc/turn.hip.h)
+    "sw_create_event": (C.c_int, [_P, C.c_int, C.c_int64, C.c_int64, C.c_double, _P, C.c_int64, C.POINTER(C.c_int64), _P, _P]),
+    "sw_gossip_turn": (C.c_int, [_P, C.c_int, C.c_int64, _P, C.c_int64, C.c_double, _P, C.c_int64, C.c_int, _P, C.c_int, _P, C.c_size_t]),
+    "sw_get_turn_stats": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64), _P,
+                                    C.POINTER(C.c_double)]),
     "sw_num_ordered":(C.c_int, [_P, C.POINTER(C.c_int64)]),
     "sw_get_transactions": (C.c_int, [_P, C.c_int64, C.c_int64, _P]),
     "sw_get_counters": (C.c_int, [_P, C.POINTER(Counters)]),

@@ -32,6 +32,7 @@
 #include "gossip.hip.h"
 #include "walk.hip.h"
 #include "wire.hip.h"
+#include "turn.hip.h"
 #include "consensus.hip.h"
 
 namespace {
@@ -255,6 +256,9 @@ struct sw_ctx {
     DBuf<unsigned char> d_sg_in;  // the staged arrays of the host-array forms; the signed arrays of sw_create_events
     int64_t sg_calls = 0, sg_events = 0, sg_levels = 0, sg_keysets = 0;   // sw_get_sign_stats (levels: the last call's)
     double sg_ms[3] = {0, 0, 0};  // ... host time under sw_set_profiling: levels + sort, signing, commit
+    // one event signed by one wavefront, and the gossip turn around it (sw_create_event, sw_gossip_turn; turn.hip.h)
+    int64_t tn_calls = 0, tn_events = 0, tn_turns = 0, tn_profiled = 0;   // sw_get_turn_stats: sw_create_event calls, events the wave signed, turns, stamped launches
+    unsigned long long tn_stamps[8] = {0};   // wall_clock64() at the phase boundaries of the last stamped launch (swt::ST_COUNT)
 
     // device: events
     DBuf<int32_t> d_cr, d_sp, d_op, d_ht, d_seq, d_round, d_L, d_chain_ev;
@@ -7385,10 +7389,77 @@ CreateScratch create_scratch(size_t k) {
     return s;
 }
 
+// ONE event signed by one wavefront (turn.hip.h) in place of sign_core's levels.
+struct OneSign {
+    const uint8_t* d_head_id = nullptr;   // in: the other parent is the stored event with THIS id (device memory), looked up on the device
+    bool absent = false;                  // out: ... and no stored event has it (nothing signed, nothing stored)
+};
+
+// The checks of sign_core for K = 1 and the signer behind them, on the context's stream; ONE synchronisation, which brings back
+// the verdict, the data bytes, the looked-up parent and (profiling) the signer's stamps together.  *d_op: where the other
+// parent's index lies in device memory (the caller's array, or the slot the lookup wrote).
+int sign_one_core(sw_ctx* c, SignArrays a, const char* what, int64_t* usable, OneSign* one, const int32_t** d_op) {
+    const bool prof = c->profiling;
+    const auto t0 = std::chrono::steady_clock::now();
+    c->sg_ms[0] = c->sg_ms[1] = c->sg_ms[2] = 0;
+    CHK(pack_header(c));
+    CHK(dgrow(c, c->d_sg, 512, 0));
+    unsigned char* B = c->d_sg.p;   // [0] verdict, [1] data bytes, [4] the looked-up parent (int), [8 .. 8 + ST_COUNT) stamps
+    unsigned long long* d_v = (unsigned long long*)B;
+    int32_t* d_slot = (int32_t*)(B + 32);
+    unsigned long long* d_stamps = d_v + 8;
+    HIPCHK(c, hipMemsetAsync(B, 0, 256, c->stream));
+    HIPCHK(c, hipMemsetAsync(B, 0xff, 8, c->stream));   // ing::V_NONE
+    if (one->d_head_id) {
+        hipLaunchKernelGGL(rsv::k_tab_lookup, dim3(1), dim3(64), 0, c->stream, (const int*)c->d_idtab.p, c->n_ids ? c->idtab_log : 0,
+                           (const unsigned char*)c->d_id.p, (const unsigned char*)one->d_head_id, 1, (int*)d_slot);
+        c->ctr.kernel_launches++;
+        a.op = d_slot;
+    }
+    *d_op = a.op;
+    const int n = c->n;
+    const sws::SignIn in{a.creator, a.sp, a.op, (const sws::u64*)a.t, a.data, (const sws::i64*)a.data_off, (sws::i64)a.data_bytes, a.data_none,
+                         (const int*)c->d_cr.p, (const uint8_t*)c->d_id.p, (int)c->N, n, (const uint8_t*)c->d_vkeys.p,
+                         (const uint8_t*)c->d_sg_keys.p + (size_t)n * sizeof(sws::Secret), (const sws::Secret*)c->d_sg_keys.p,
+                         (const swv::niels*)c->d_vtab.p + (size_t)n * swv::ROW, (const uint8_t*)c->d_pk_hdr.p, pack_hdr_len(c)};
+    const sws::SignOut out{a.id, a.sp_id, a.op_id, a.arity, a.sig};
+    hipLaunchKernelGGL(sws::k_sign_check, dim3(1), dim3(256), 0, c->stream, in, 1, d_v, d_v + 1);
+    if (prof) hipLaunchKernelGGL(swt::k_sign_one<true>, dim3(1), dim3(swt::LANES), 0, c->stream, in, out, (const unsigned long long*)d_v, d_stamps);
+    else hipLaunchKernelGGL(swt::k_sign_one<false>, dim3(1), dim3(swt::LANES), 0, c->stream, in, out, (const unsigned long long*)d_v, d_stamps);
+    c->ctr.kernel_launches += 2;
+    HIPCHK(c, hipGetLastError());
+    unsigned long long rb[8 + swt::ST_COUNT] = {0};
+    HIPCHK(c, hipMemcpyAsync(rb, B, sizeof rb, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    int32_t slot = 0;
+    memcpy(&slot, rb + 4, sizeof slot);
+    if (one->d_head_id && slot < 0) { one->absent = true; return SW_OK; }
+    if (rb[0] != ing::V_NONE) {
+        switch ((int)(rb[0] & 0xff)) {
+            case ing::V_CREATOR: return fail(c, SW_EINVAL, "%s: creator out of range", what);
+            case ing::V_ARITY: return fail(c, SW_EINVAL, "%s: an event must have 0 or 2 parents", what);
+            case ing::V_ORDER: return fail(c, SW_EINVAL, "%s: a parent is not a stored event", what);
+            case ing::V_SELF: return fail(c, SW_EINVAL, "%s: self-parent is by another member", what);
+            case ing::V_OTHER: return fail(c, SW_EINVAL, "%s: other-parent is by the same member", what);
+            case sws::V_NOKEY: return fail(c, SW_EINVAL, "%s: no signing key for its creator", what);
+            default: return fail(c, SW_EINVAL, "%s: data longer than %d bytes", what, tpl::MAX_DATA);
+        }
+    }
+    *usable = (int64_t)rb[1];
+    if (prof) {
+        c->sg_ms[1] = ms_since(t0);
+        memcpy(c->tn_stamps, rb + 8, sizeof c->tn_stamps);
+        c->tn_profiled++;
+    }
+    c->tn_events++;
+    return SW_OK;
+}
+
 // sw_create_events behind the argument checks: every array in device memory and visible to the context's stream.
 // Everything that can be refused or can run out of memory comes first; behind the append a failure poisons the context.
 int create_core(sw_ctx* c, int64_t K, const int32_t* d_cr, const int32_t* d_sp, const int32_t* d_op, const double* d_t, const uint8_t* d_data,
-                const int64_t* d_off, int64_t data_bytes, const uint8_t* d_none, uint8_t* d_id_out, uint8_t* d_sig_out, const char* what) {
+                const int64_t* d_off, int64_t data_bytes, const uint8_t* d_none, uint8_t* d_id_out, uint8_t* d_sig_out, const char* what,
+                OneSign* one = nullptr) {
     const int64_t N0 = c->N;
     const bool with_data = c->n_data == N0;
     const size_t k = (size_t)K;
@@ -7404,7 +7475,13 @@ int create_core(sw_ctx* c, int64_t K, const int32_t* d_cr, const int32_t* d_sp, 
     CHK(dgrow(c, c->d_sg_in, L.end + 256, 0));
     unsigned char* B = c->d_sg_in.p;
     int64_t usable = 0;
-    CHK(sign_core(c, K, SignArrays{d_cr, d_sp, d_op, d_t, d_data, d_off, data_bytes, d_none, B + o_id, B + o_sp, B + o_op, B + o_ar, B + o_sig}, what, &usable));
+    const SignArrays sa{d_cr, d_sp, d_op, d_t, d_data, d_off, data_bytes, d_none, B + o_id, B + o_sp, B + o_op, B + o_ar, B + o_sig};
+    if (one) {   // K == 1: the one-wave signer (turn.hip.h); the other parent may come from the id index, and be absent
+        CHK(sign_one_core(c, sa, what, &usable, one, &d_op));
+        if (one->absent) return SW_OK;
+    } else {
+        CHK(sign_core(c, K, sa, what, &usable));
+    }
     if (with_data && usable > data_bytes)
         return fail(c, SW_EINVAL, "%s: the data ranges hold %lld bytes, the buffer %lld: ranges overlap (nothing stored)", what, (long long)usable, (long long)data_bytes);
     const auto t0 = std::chrono::steady_clock::now();
@@ -7641,6 +7718,135 @@ int sw_get_sign_stats(sw_ctx* c, int64_t* calls, int64_t* events, int64_t* level
     if (levels) *levels = c->sg_levels;
     if (key_sets) *key_sets = c->sg_keysets;
     if (phase_ms) for (int i = 0; i < 3; ++i) phase_ms[i] = c->sg_ms[i];
+    return SW_OK;
+}
+
+// ---- one event signed by one wavefront, and the gossip turn around it (turn.hip.h) -----------------------
+}  // extern "C"
+
+namespace {
+
+// One event as host values -> the K = 1 arrays sw_create_events would stage -> create_core with the one-wave signer.  The
+// staged values live on this frame: the stream is drained before it is left, whatever happens.
+int create_one(sw_ctx* c, int member, int64_t sp, int64_t op, double t, const uint8_t* data, int64_t data_len, OneSign* one, uint8_t* id32_out,
+               uint8_t* sig64_out, const char* what) {
+    const auto narrow = [](int64_t v) { return v < 0 ? (int32_t)-1 : v > 0x7fffffff ? (int32_t)0x7fffffff : (int32_t)v; };
+    const int32_t cr = member, s = narrow(sp), o = narrow(op);
+    const int64_t nbytes = data_len > 0 ? data_len : 0;
+    const int64_t off[2] = {0, nbytes};
+    const uint8_t none = data_len < 0 ? 1 : 0;
+    if (data_len > 0 && !data) return fail(c, SW_EINVAL, "%s: %lld data bytes and a NULL buffer", what, (long long)data_len);
+    CHK(sign_pre(c, 1, &cr, &s, &o, &t, nbytes ? data : nullptr, off, nbytes, &none, what));
+    if (data_len > tpl::MAX_DATA) return fail(c, SW_EINVAL, "%s: data longer than %d bytes", what, tpl::MAX_DATA);
+    HIPCHK(c, hipSetDevice(c->device));
+    const CreateScratch L = create_scratch(1);
+    const auto run = [&]() -> int {
+        SignStaged st{};
+        CHK(sign_stage(c, 1, L.end, &cr, &s, &o, &t, nbytes ? data : nullptr, off, nbytes, &none, &st));
+        CHK(create_core(c, 1, st.cr, st.sp, st.op, st.t, st.data, st.off, nbytes, st.none, nullptr, nullptr, what, one));
+        if (one->absent) return SW_OK;
+        const unsigned char* B = c->d_sg_in.p;   // (create_core found the buffer large enough: it has not moved)
+        if (id32_out) HIPCHK(c, hipMemcpyAsync(id32_out, B + L.id, 32, hipMemcpyDeviceToHost, c->stream));
+        if (sig64_out) HIPCHK(c, hipMemcpyAsync(sig64_out, B + L.sig, 64, hipMemcpyDeviceToHost, c->stream));
+        if (id32_out || sig64_out) HIPCHK(c, hipStreamSynchronize(c->stream));
+        return SW_OK;
+    };
+    const int rc = run();
+    if (rc != SW_OK) (void)hipStreamSynchronize(c->stream);
+    return rc;
+}
+
+}  // namespace
+
+extern "C" {
+
+int sw_create_event(sw_ctx* c, int member, int64_t self_parent, int64_t other_parent, double t, const uint8_t* data, int64_t data_len,
+                    int64_t* index_out, uint8_t* id32_out, uint8_t* sig64_out) {
+    if (!c) return SW_EINVAL;
+    const int64_t N0 = c->N;
+    OneSign one;
+    CHK(create_one(c, member, self_parent, other_parent, t, data, data_len, &one, id32_out, sig64_out, "sw_create_event"));
+    if (index_out) *index_out = N0;
+    c->tn_calls++;
+    return SW_OK;
+}
+
+int sw_gossip_turn(sw_ctx* dst, int member, int64_t dst_head, sw_ctx* src, int64_t src_head, double t, const uint8_t* data, int64_t data_len,
+                   int flags, int32_t* new_rounds, int cap_rounds, void* result, size_t result_bytes) {
+    if (!dst || !src) return SW_EINVAL;
+    const char* what = "sw_gossip_turn";
+    if (!result || result_bytes < 8) return fail(dst, SW_EINVAL, "%s: NULL or short result", what);
+    sw_turn_result res{};
+    res.new_head = -1;
+    const auto put = [&]() { memcpy(result, &res, std::min(result_bytes, sizeof res)); };
+    put();
+    const bool validate = flags & SW_TURN_VALIDATE, with_data = flags & SW_TURN_DATA, trunks = flags & SW_TURN_TRUNKS;
+    const bool consensus = !(flags & SW_TURN_NO_CONSENSUS);
+    // ---- refusals: before anything is launched or stored
+    if (flags & ~(SW_TURN_VALIDATE | SW_TURN_DATA | SW_TURN_TRUNKS | SW_TURN_NO_CONSENSUS)) return fail(dst, SW_EINVAL, "%s: unknown flag bits in %d", what, flags);
+    if (dst == src) return fail(dst, SW_EINVAL, "%s: a context cannot gossip with itself", what);
+    if (dst->n != src->n) return fail(dst, SW_EINVAL, "%s: %d members here, %d at the peer", what, dst->n, src->n);
+    if (dst->poisoned || src->poisoned) return fail(dst, SW_EIO, "context unusable after an earlier device failure");
+    if (dst->vm.active || src->vm.active) return fail(dst, SW_ENOTSUP, "%s is not available with the windowed table", what);
+    if (dst->vkeys.empty()) return fail(dst, SW_ENOTSUP, "%s: no member keys (sw_set_member_keys first)", what);
+    if (member < 0 || member >= dst->n) return fail(dst, SW_EINVAL, "%s: member %d out of range", what, member);
+    if (dst->sg_has.empty() || !dst->sg_has[(size_t)member]) return fail(dst, SW_ENOTSUP, "%s: no signing key for member %d (sw_set_signing_keys first)", what, member);
+    if (dst->n_ids != dst->N || src->n_ids != src->N) return fail(dst, SW_ENOTSUP, "%s: the id index of %s is incomplete (sw_set_event_ids first)", what, dst->n_ids != dst->N ? "this context" : "the peer");
+    if (with_data && (dst->n_data != dst->N || src->n_data != src->N))
+        return fail(dst, SW_ENOTSUP, "%s: the data store of %s is incomplete (sw_set_event_data first)", what, dst->n_data != dst->N ? "this context" : "the peer");
+    if (dst->divided != dst->N) return fail(dst, SW_EINVAL, "%s: %lld undivided events (sw_divide_rounds first)", what, (long long)(dst->N - dst->divided));
+    if (dst_head < 0 || dst_head >= dst->N || dst->cr[(size_t)dst_head] != member)
+        return fail(dst, SW_EINVAL, "%s: head %lld is not an event of member %d (swirld.py:86)", what, (long long)dst_head, member);
+    if (src_head >= 0 && src_head < src->N && src->cr[(size_t)src_head] == member)
+        return fail(dst, SW_EINVAL, "%s: the peer's head %lld is an event of member %d itself (swirld.py:87)", what, (long long)src_head, member);
+    if (data_len > tpl::MAX_DATA) return fail(dst, SW_EINVAL, "%s: data longer than %d bytes", what, tpl::MAX_DATA);
+    if (data_len > 0 && !data) return fail(dst, SW_EINVAL, "%s: %lld data bytes and a NULL buffer", what, (long long)data_len);
+    if (consensus && (cap_rounds < 0 || (cap_rounds > 0 && !new_rounds))) return fail(dst, SW_EINVAL, "%s: NULL new_rounds (capacity %d)", what, cap_rounds);
+    CHK(pull_pre(dst, dst_head, src, validate, with_data, what));
+    if (const int rc = walk_pre(src, src_head, true, "sw_gossip_turn (peer)"); rc != SW_OK) { dst->err = src->err; return rc; }
+    // ---- 1. the pull (swirld.py:125-136)
+    const int64_t N_before = dst->N;
+    CHK(sw_sync_pull_walk(dst, dst_head, src, src_head, trunks, validate, with_data, &res.n_sent, &res.n_valid, &res.n_stored));
+    res.stage = SW_TURN_STAGE_PULLED;
+    put();
+    dst->tn_turns++;
+    // ---- 2. and 3. the new event on my head and the peer's, whose index comes from the id index on the device
+    OneSign one;
+    one.d_head_id = (const uint8_t*)src->d_id.p + (size_t)src_head * 32;
+    const int64_t N_pulled = dst->N;
+    CHK(create_one(dst, member, dst_head, -1, t, data, data_len, &one, nullptr, nullptr, what));
+    if (!one.absent) res.new_head = N_pulled;
+    res.stage = SW_TURN_STAGE_CREATED;
+    put();
+    if (!consensus) return SW_OK;
+    // ---- 4. divide_rounds, decide_fame, find_order (swirld.py:326-328)
+    CHK(sw_divide_rounds(dst, N_before, dst->N - N_before));
+    res.stage = SW_TURN_STAGE_DIVIDED;
+    put();
+    int n_new = 0;
+    CHK(sw_decide_fame(dst, new_rounds, cap_rounds, &n_new));
+    res.n_new_rounds = n_new;
+    res.stage = SW_TURN_STAGE_FAME;
+    put();
+    std::vector<int32_t> ordered((size_t)std::max<int64_t>(dst->N, 1));
+    CHK(sw_find_order(dst, new_rounds, n_new, ordered.data(), dst->N, &res.n_ordered));
+    res.stage = SW_TURN_STAGE_ORDERED;
+    put();
+    return SW_OK;
+}
+
+int sw_get_turn_stats(sw_ctx* c, int64_t* create_calls, int64_t* events, int64_t* turns, int64_t* stamped, uint64_t* stamps, double* tick_ns) {
+    if (!c) return SW_EINVAL;
+    if (create_calls) *create_calls = c->tn_calls;
+    if (events) *events = c->tn_events;
+    if (turns) *turns = c->tn_turns;
+    if (stamped) *stamped = c->tn_profiled;
+    if (stamps) for (int i = 0; i < swt::ST_COUNT; ++i) stamps[i] = c->tn_stamps[i];
+    if (tick_ns) {
+        int khz = 0;
+        if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, c->device) != hipSuccess || khz <= 0) { (void)hipGetLastError(); khz = 100000; }
+        *tick_ns = 1e6 / khz;
+    }
     return SW_OK;
 }
 

@@ -1,12 +1,16 @@
 """Array-in / array-out front end of the C-ABI: one `Hashgraph` = the voting state of
 one Node view, resident in HBM.  Mirrors the reference's hot-path methods
 (swirld.py:187-311) on dense event / member indices."""
+import collections
 import ctypes as C
 
 import numpy as np
 
 from . import _lib
 from ._lib import Counters, SwirldHipError, Timings
+
+# what Hashgraph.gossip_turn returns: sw_turn_result's fields and the rounds decide_fame added to the consensus
+TurnResult = collections.namedtuple("TurnResult", "n_sent n_valid n_stored new_head n_new_rounds n_ordered stage new_rounds")
 
 
 def _p(a):
@@ -1045,6 +1049,52 @@ class Hashgraph:
         self._chk(self._L.sw_get_sign_stats(self._h, *[C.byref(x) for x in v], ms))
         d = dict(zip(("calls", "events", "levels", "key_sets"), (int(x.value) for x in v)))
         d.update(zip(("levels_ms", "sign_ms", "commit_ms"), (float(x) for x in ms)))
+        return d
+
+    # ---- one event signed by one wavefront, and the gossip turn around it (swirld.py:82-95, 122-146, 322-328; csrc/turn.hip.h) ----
+    def create_event(self, member, self_parent, other_parent, t, data=None, *, want_ids=False):
+        """create_events for ONE event, whose signature the 64 lanes of a wave share (sw_create_event): member's event at time
+        t on the stored events self_parent / other_parent (both -1: a root), data bytes | None.  The same verdicts, the same
+        state afterwards.  Returns the event's dense index; with want_ids (index, id, sig) as 32 / 64 bytes."""
+        idx = C.c_int64()
+        eid, sig = (C.create_string_buffer(32), C.create_string_buffer(64)) if want_ids else (None, None)
+        raw = None if data is None else bytes(data)
+        self._chk(self._L.sw_create_event(self._h, int(member), int(self_parent), int(other_parent), float(t), raw, -1 if raw is None else len(raw),
+                                          C.byref(idx), eid, sig))
+        return (int(idx.value), eid.raw, sig.raw) if want_ids else int(idx.value)
+
+    def gossip_turn(self, peer, member, my_head, peer_head, t, data=None, *, validate=True, data_store=False, trunks=False, consensus=True):
+        """One step of a node (sw_gossip_turn; swirld.py:125-146, 324-328): pull what `peer` (a Hashgraph on the same device)
+        knows at peer_head beyond my_head by the pruned walk, create member's event (data, (my_head, peer_head's event), t)
+        — the other parent found in my id index on the device — then divide_rounds, decide_fame and find_order.  Leaves
+        this context as pull_from(walk=True, ...), create_event, divide_rounds, decide_fame, find_order would.  Returns a
+        TurnResult: n_sent, n_valid, n_stored, new_head (-1 when the peer's head did not arrive: no event), n_new_rounds,
+        n_ordered, stage, and new_rounds (the rounds decide_fame added to the consensus)."""
+        flags = ((_lib.SW_TURN_VALIDATE if validate else 0) | (_lib.SW_TURN_DATA if data_store else 0) | (_lib.SW_TURN_TRUNKS if trunks else 0) |
+                 (0 if consensus else _lib.SW_TURN_NO_CONSENSUS))
+        raw = None if data is None else bytes(data)
+        res = _lib.TurnResult()
+        # (a round is a function of an event's ancestry: what arrives has the peer's rounds, the new event at most one more)
+        cap = max(self.max_round, peer.max_round) + 3 if consensus else 0
+        rounds = np.empty(max(cap, 1), np.int32)
+        rc = self._L.sw_gossip_turn(self._h, int(member), int(my_head), peer._h, int(peer_head), float(t), raw, -1 if raw is None else len(raw), flags,
+                                    _p(rounds), cap, C.byref(res), C.sizeof(res))
+        self._chk(rc)
+        return TurnResult(*(int(getattr(res, k)) for k, _ in _lib.TurnResult._fields_), rounds[: res.n_new_rounds].copy())
+
+    def turn_stats(self):
+        """create_event calls, events the one-wave signer signed, gossip turns, stamped launches; under set_profiling the phase
+        lengths of the last stamped launch in microseconds (phase_us: load, hash1, base_mult, encode, hash2, muladd, id) and
+        the raw stamps."""
+        v = [C.c_int64() for _ in range(4)]
+        st = (C.c_uint64 * 8)()
+        tick = C.c_double()
+        self._chk(self._L.sw_get_turn_stats(self._h, *[C.byref(x) for x in v], st, C.byref(tick)))
+        d = dict(zip(("create_calls", "events", "turns", "stamped"), (int(x.value) for x in v)))
+        d["stamps"] = [int(x) for x in st]
+        d["tick_ns"] = float(tick.value)
+        names = ("load", "hash1", "base_mult", "encode", "hash2", "muladd", "id")
+        d["phase_us"] = {k: (d["stamps"][i + 1] - d["stamps"][i]) * d["tick_ns"] / 1e3 for i, k in enumerate(names)}
         return d
 
     def export_stats(self):
