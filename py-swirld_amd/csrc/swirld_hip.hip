@@ -12,12 +12,14 @@
 #include <cstdarg>
 #include <cstdio>
 #include <cstring>
+#include <initializer_list>
 #include <string>
 #include <thread>
 #include <type_traits>
 #include <vector>
 
 #include "../../include/swirld_hip.h"
+#include "entry_plan.h"
 #include "kernels.hip.h"
 #define SW_PROV_ROWS 16   // sub-batches of one divide_rounds call that can be swept in chunks
 #define SW_RANGE_SLOTS 16 // event ranges swept by sw_cansee_range between two rewinds
@@ -509,6 +511,95 @@ void dfree(DBuf<T>& b) {
     if (b.p) (void)hipFree(b.p);
     b.p = nullptr;
     b.cap = 0;
+}
+
+// ---- the entry protocol of the call forms (entry_plan.h) --------------------------------------------------------
+using entry::Arg;
+using entry::Carve;
+using entry::Stage;
+
+double ms_since(std::chrono::steady_clock::time_point t0) {
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+
+// device memory of the context's device?  (For plain host memory the query itself fails on ROCm: that is the answer,
+// and the error is cleared so that it does not surface in a later check.)
+bool on_ctx_device(const sw_ctx* c, const void* p, size_t bytes) {
+    const char* ends[2] = {(const char*)p, (const char*)p + (bytes ? bytes - 1 : 0)};
+    for (const char* q : ends) {
+        hipPointerAttribute_t at;
+        if (hipPointerGetAttributes(&at, q) != hipSuccess) { (void)hipGetLastError(); return false; }
+        if (at.type != hipMemoryTypeDevice || at.device != c->device) return false;
+    }
+    return true;
+}
+
+int misaligned(sw_ctx* c, const char* what, unsigned align) {
+    return fail(c, SW_EINVAL, "%s: an array that must be %u-byte aligned is not (ids, signatures and byte streams 16, offsets and timestamps 8, indices 4)",
+                what, align);
+}
+
+// The arrays of a device-array form, behind the form's *_pre checks: alignment, the context's device made current, residency.
+// A row that is NULL or empty is skipped (entry_plan.h).
+int device_args(sw_ctx* c, const char* what, std::initializer_list<Arg> rows) {
+    const int bad = entry::first_misaligned(rows.begin(), (int)rows.size());
+    if (bad >= 0) return misaligned(c, what, rows.begin()[bad].align);
+    HIPCHK(c, hipSetDevice(c->device));
+    for (const Arg& a : rows)
+        if (!entry::skipped(a) && !on_ctx_device(c, a.p, a.bytes))
+            return fail(c, SW_EINVAL, "%s: every array must lie in memory of device %d (a host pointer, or another device's)", what, c->device);
+    return SW_OK;
+}
+
+// A call between the caller's stream and one of ours: join() puts our stream behind what the caller has enqueued (the producers
+// of its arrays, earlier readers of its outputs); leave() puts the caller's stream behind what the call enqueued, so that
+// whatever it enqueues next reads complete arrays and may reuse its own.  A call that returns between the two, for whatever
+// reason, hands the caller's stream back all the same (the destructor, errors ignored and cleared: the call's own error stands).
+struct UserStream {
+    sw_ctx* c = nullptr;
+    hipStream_t user = nullptr, ours = nullptr;
+    bool joined = false;
+    int join(sw_ctx* ctx, hipStream_t user_stream, hipStream_t our_stream = nullptr) {
+        c = ctx;
+        user = user_stream;
+        ours = our_stream ? our_stream : ctx->stream;
+        if (!c->ev_user) HIPCHK(c, hipEventCreateWithFlags(&c->ev_user, hipEventDisableTiming));
+        HIPCHK(c, hipEventRecord(c->ev_user, user));
+        HIPCHK(c, hipStreamWaitEvent(ours, c->ev_user, 0));
+        joined = true;
+        return SW_OK;
+    }
+    int leave() {
+        joined = false;
+        HIPCHK(c, hipEventRecord(c->ev_user, ours));
+        HIPCHK(c, hipStreamWaitEvent(user, c->ev_user, 0));
+        return SW_OK;
+    }
+    void drained() { joined = false; }   // our stream has been synchronised: there is nothing left to wait for
+    ~UserStream() {
+        if (joined && (hipEventRecord(c->ev_user, ours) != hipSuccess || hipStreamWaitEvent(user, c->ev_user, 0) != hipSuccess)) (void)hipGetLastError();
+    }
+};
+
+// The staging buffer of a host-array form, grown to the plan, and the uploads on the context's stream ...
+int stage_up(sw_ctx* c, DBuf<unsigned char>& buf, const Stage& st, unsigned char** base) {
+    if (st.full) return fail(c, SW_EIO, "a staging plan of more than %d copies (internal error)", Stage::MAX_ROWS);
+    CHK(dgrow(c, buf, st.total() + 256, 0));
+    *base = buf.p;
+    for (int i = 0; i < st.n_up; ++i)
+        HIPCHK(c, hipMemcpyAsync(buf.p + st.up[i].off, st.up[i].src, st.up[i].bytes, hipMemcpyHostToDevice, c->stream));
+    return SW_OK;
+}
+// ... and the downloads with the ONE synchronisation behind them.  A row is brought back once: a second call brings what has
+// been sized (Stage::out_bytes) since the first.
+int stage_down(sw_ctx* c, Stage& st, const unsigned char* base) {
+    for (int i = 0; i < st.n_down; ++i) {
+        Stage::Copy& d = st.down[i];
+        if (d.bytes) HIPCHK(c, hipMemcpyAsync(d.dst, base + d.off, d.bytes, hipMemcpyDeviceToHost, c->stream));
+        d.bytes = 0;
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    return SW_OK;
 }
 
 int fill_i32(sw_ctx* c, int32_t* p, size_t n, int v) {
@@ -3750,18 +3841,6 @@ int sw_append_events(sw_ctx* c, int64_t K, const int32_t* creator, const int32_t
 // ---- sw_append_events_device: the same K events from device memory ------------------------------------------------
 namespace {
 
-// device memory of the context's device?  (For plain host memory the query itself fails on ROCm: that is the answer,
-// and the error is cleared so that it does not surface in a later check.)
-bool on_ctx_device(const sw_ctx* c, const void* p, size_t bytes) {
-    const char* ends[2] = {(const char*)p, (const char*)p + (bytes ? bytes - 1 : 0)};
-    for (const char* q : ends) {
-        hipPointerAttribute_t at;
-        if (hipPointerGetAttributes(&at, q) != hipSuccess) { (void)hipGetLastError(); return false; }
-        if (at.type != hipMemoryTypeDevice || at.device != c->device) return false;
-    }
-    return true;
-}
-
 // Everything outside the bulk fork-free fast path: the batch goes to the host and through sw_append_events.
 int ingest_fallback(sw_ctx* c, int64_t K, const int32_t* d_creator, const int32_t* d_self_parent, const int32_t* d_other_parent,
                     const double* d_t, const uint8_t* d_sig64, hipStream_t us) {
@@ -3791,11 +3870,8 @@ int sw_append_events_device(sw_ctx* c, int64_t K, const int32_t* d_creator, cons
     if (K < 0 || (K > 0 && (!d_creator || !d_self_parent || !d_other_parent))) return fail(c, SW_EINVAL, "NULL event arrays");
     if (K == 0) return SW_OK;
     if (c->N + K > 0x7ffffff0ll) return fail(c, SW_ERANGE, "more than 2^31 events");
-    HIPCHK(c, hipSetDevice(c->device));
-    const size_t b4 = (size_t)K * sizeof(int32_t);
-    if (!on_ctx_device(c, d_creator, b4) || !on_ctx_device(c, d_self_parent, b4) || !on_ctx_device(c, d_other_parent, b4) ||
-        (d_t && !on_ctx_device(c, d_t, (size_t)K * 8)) || (d_sig64 && !on_ctx_device(c, d_sig64, (size_t)K * 64)))
-        return fail(c, SW_EINVAL, "sw_append_events_device: every array must lie in memory of device %d (a host pointer, or another device's)", c->device);
+    const size_t k = (size_t)K;
+    CHK(device_args(c, "sw_append_events_device", {{d_creator, k * 4, 1}, {d_self_parent, k * 4, 1}, {d_other_parent, k * 4, 1}, {d_t, k * 8, 1}, {d_sig64, k * 64, 1}}));
     return append_device_body(c, K, d_creator, d_self_parent, d_other_parent, d_t, d_sig64, (hipStream_t)user_stream);
 }
 
@@ -3830,11 +3906,10 @@ static int append_device_body(sw_ctx* c, int64_t K, const int32_t* d_creator, co
         }
         c->h_pin_cap = (size_t)K * 8;
     }
-    if (!c->ev_user) HIPCHK(c, hipEventCreateWithFlags(&c->ev_user, hipEventDisableTiming));
     if (!c->ev_ht) HIPCHK(c, hipEventCreateWithFlags(&c->ev_ht, hipEventDisableTiming));
     // ---- the context's stream waits for what the caller enqueued; parent arrays to the (uncommitted) tail
-    HIPCHK(c, hipEventRecord(c->ev_user, us));
-    HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_user, 0));
+    UserStream bracket;
+    CHK(bracket.join(c, us));
     HIPCHK(c, hipMemcpyAsync(c->d_cr.p + N0, d_creator, b4, hipMemcpyDeviceToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(c->d_sp.p + N0, d_self_parent, b4, hipMemcpyDeviceToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(c->d_op.p + N0, d_other_parent, b4, hipMemcpyDeviceToDevice, c->stream));
@@ -3872,6 +3947,7 @@ static int append_device_body(sw_ctx* c, int64_t K, const int32_t* d_creator, co
     HIPCHK(c, hipMemcpyAsync(pin_cr, c->d_cr.p + N0, b4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(pin_seq, c->d_seq.p + N0, b4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
+    bracket.drained();   // (the commit below drains the stream again before it returns; a failure inside it poisons the context)
     unsigned long long v;
     memcpy(&v, tab.data(), sizeof v);
     if (v != ing::V_NONE) {
@@ -3983,15 +4059,6 @@ int idtab_insert(sw_ctx* c, int64_t first, int64_t K, int* flag) {
     return SW_OK;
 }
 
-struct Carve {   // consecutive 256-byte aligned pieces of one allocation
-    size_t off = 0;
-    size_t take(size_t bytes) { const size_t o = off; off += (bytes + 255) & ~(size_t)255; return o; }
-};
-
-double ms_since(std::chrono::steady_clock::time_point t0) {
-    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-}
-
 // The payload call behind the argument checks.  Every array lies in device memory; d_out too.
 int payload_core(sw_ctx* c, int64_t K, const uint8_t* d_id32, const uint8_t* d_sp_id32, const uint8_t* d_op_id32, const uint8_t* d_arity,
                  const int32_t* d_creator, const uint8_t* d_ok, const double* d_t, const uint8_t* d_sig64, hipStream_t us, int32_t* d_out,
@@ -4027,9 +4094,8 @@ int payload_core(sw_ctx* c, int64_t K, const uint8_t* d_id32, const uint8_t* d_s
         c->h_plcnt = nullptr;
         return fail(c, SW_ENOMEM, "hipHostMalloc for the wave counts failed");
     }
-    if (!c->ev_user) HIPCHK(c, hipEventCreateWithFlags(&c->ev_user, hipEventDisableTiming));
-    HIPCHK(c, hipEventRecord(c->ev_user, us));
-    HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_user, 0));
+    UserStream bracket;   // (left by the destructor on a failure; a success has drained the stream)
+    CHK(bracket.join(c, us));
     // ---- resolve: the payload's own table (lowest position of every id), local checks, parent references
     const dim3 ev_grid((unsigned)((K + 255) / 256));
     HIPCHK(c, hipMemsetAsync(lslots, 0xff, sizeof(int32_t) << llog, c->stream));
@@ -4071,6 +4137,7 @@ int payload_core(sw_ctx* c, int64_t K, const uint8_t* d_id32, const uint8_t* d_s
     c->pl_ms[2] = c->pl_ms[3] = 0;
     if (A == 0) {
         HIPCHK(c, hipStreamSynchronize(c->stream));
+        bracket.drained();
         return SW_OK;
     }
     // ---- dense order: stable sort of the accepted events by wave, LSD in passes of 10 bits through the stable-rank
@@ -4114,6 +4181,7 @@ int payload_core(sw_ctx* c, int64_t K, const uint8_t* d_id32, const uint8_t* d_s
     c->n_ids = N0 + A;
     *n_stored = A;
     if (prof) c->pl_ms[3] = ms_since(t0);
+    bracket.drained();   // (idtab_insert has synchronised)
     return SW_OK;
 }
 
@@ -4171,18 +4239,15 @@ int sw_lookup_event_ids(sw_ctx* c, int64_t K, const uint8_t* id32, int32_t* inde
     if (K < 0 || K > 0x3fffffffll || (K > 0 && (!id32 || !index_out))) return fail(c, SW_EINVAL, "sw_lookup_event_ids: NULL arrays");
     if (K == 0) return SW_OK;
     HIPCHK(c, hipSetDevice(c->device));
-    Carve cv;
-    const size_t o_id = cv.take((size_t)K * 32), o_out = cv.take((size_t)K * 4);
-    CHK(dgrow(c, c->d_pl_in, cv.off, 0));
-    unsigned char* B = c->d_pl_in.p;
-    HIPCHK(c, hipMemcpyAsync(B + o_id, id32, (size_t)K * 32, hipMemcpyHostToDevice, c->stream));
+    Stage st;
+    const size_t o_id = st.in(id32, (size_t)K * 32), o_out = st.out(index_out, (size_t)K * 4);
+    unsigned char* B = nullptr;
+    CHK(stage_up(c, c->d_pl_in, st, &B));
     hipLaunchKernelGGL(rsv::k_tab_lookup, dim3((unsigned)((K + 255) / 256)), dim3(256), 0, c->stream, (const int*)c->d_idtab.p, c->n_ids ? c->idtab_log : 0,
                        (const unsigned char*)c->d_id.p, (const unsigned char*)(B + o_id), (int)K, (int*)(B + o_out));
     c->ctr.kernel_launches++;
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(index_out, B + o_out, (size_t)K * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return SW_OK;
+    return stage_down(c, st, B);
 }
 
 int sw_ingest_payload_device(sw_ctx* c, int64_t K, const uint8_t* d_id32, const uint8_t* d_sp_id32, const uint8_t* d_op_id32, const uint8_t* d_arity,
@@ -4191,14 +4256,9 @@ int sw_ingest_payload_device(sw_ctx* c, int64_t K, const uint8_t* d_id32, const 
     if (!c) return SW_EINVAL;
     CHK(payload_args(c, K, d_id32, d_sp_id32, d_op_id32, d_arity, d_creator, d_index_out, n_stored, "sw_ingest_payload_device"));
     if (K == 0) return SW_OK;
-    if (((uintptr_t)d_id32 | (uintptr_t)d_sp_id32 | (uintptr_t)d_op_id32) & 7)
-        return fail(c, SW_EINVAL, "sw_ingest_payload_device: the id arrays must be 8-byte aligned");
-    HIPCHK(c, hipSetDevice(c->device));
     const size_t k = (size_t)K;
-    if (!on_ctx_device(c, d_id32, k * 32) || !on_ctx_device(c, d_sp_id32, k * 32) || !on_ctx_device(c, d_op_id32, k * 32) ||
-        !on_ctx_device(c, d_arity, k) || !on_ctx_device(c, d_creator, k * 4) || !on_ctx_device(c, d_index_out, k * 4) ||
-        (d_ok && !on_ctx_device(c, d_ok, k)) || (d_t && !on_ctx_device(c, d_t, k * 8)) || (d_sig64 && !on_ctx_device(c, d_sig64, k * 64)))
-        return fail(c, SW_EINVAL, "sw_ingest_payload_device: every array must lie in memory of device %d (a host pointer, or another device's)", c->device);
+    CHK(device_args(c, "sw_ingest_payload_device", {{d_id32, k * 32, 8}, {d_sp_id32, k * 32, 8}, {d_op_id32, k * 32, 8}, {d_arity, k, 1}, {d_creator, k * 4, 1},
+                                                    {d_index_out, k * 4, 1}, {d_ok, k, 1}, {d_t, k * 8, 1}, {d_sig64, k * 64, 1}}));
     return payload_core(c, K, d_id32, d_sp_id32, d_op_id32, d_arity, d_creator, d_ok, d_t, d_sig64, (hipStream_t)user_stream, d_index_out, n_stored);
 }
 
@@ -4209,25 +4269,14 @@ int sw_ingest_payload(sw_ctx* c, int64_t K, const uint8_t* id32, const uint8_t* 
     if (K == 0) return SW_OK;
     HIPCHK(c, hipSetDevice(c->device));
     const size_t k = (size_t)K;
-    Carve cv;
-    const size_t o_id = cv.take(k * 32), o_sp = cv.take(k * 32), o_op = cv.take(k * 32), o_ar = cv.take(k), o_cr = cv.take(k * 4);
-    const size_t o_ok = cv.take(ok ? k : 0), o_t = cv.take(t ? k * 8 : 0), o_sig = cv.take(sig64 ? k * 64 : 0), o_out = cv.take(k * 4);
-    CHK(dgrow(c, c->d_pl_in, cv.off, 0));
-    unsigned char* B = c->d_pl_in.p;
-    HIPCHK(c, hipMemcpyAsync(B + o_id, id32, k * 32, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(B + o_sp, sp_id32, k * 32, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(B + o_op, op_id32, k * 32, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(B + o_ar, arity, k, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(B + o_cr, creator, k * 4, hipMemcpyHostToDevice, c->stream));
-    if (ok) HIPCHK(c, hipMemcpyAsync(B + o_ok, ok, k, hipMemcpyHostToDevice, c->stream));
-    if (t) HIPCHK(c, hipMemcpyAsync(B + o_t, t, k * 8, hipMemcpyHostToDevice, c->stream));
-    if (sig64) HIPCHK(c, hipMemcpyAsync(B + o_sig, sig64, k * 64, hipMemcpyHostToDevice, c->stream));
-    const int rc = payload_core(c, K, B + o_id, B + o_sp, B + o_op, B + o_ar, (const int32_t*)(B + o_cr), ok ? B + o_ok : nullptr,
-                                t ? (const double*)(B + o_t) : nullptr, sig64 ? B + o_sig : nullptr, c->stream, (int32_t*)(B + o_out), n_stored);
-    if (rc != SW_OK) return rc;
-    HIPCHK(c, hipMemcpyAsync(index_out, B + o_out, k * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return SW_OK;
+    Stage st;
+    const size_t o_id = st.in(id32, k * 32), o_sp = st.in(sp_id32, k * 32), o_op = st.in(op_id32, k * 32), o_ar = st.in(arity, k), o_cr = st.in(creator, k * 4);
+    const size_t o_ok = st.in(ok, k), o_t = st.in(t, k * 8), o_sig = st.in(sig64, k * 64), o_out = st.out(index_out, k * 4);
+    unsigned char* B = nullptr;
+    CHK(stage_up(c, c->d_pl_in, st, &B));
+    CHK(payload_core(c, K, B + o_id, B + o_sp, B + o_op, B + o_ar, (const int32_t*)(B + o_cr), ok ? B + o_ok : nullptr,
+                     t ? (const double*)(B + o_t) : nullptr, sig64 ? B + o_sig : nullptr, c->stream, (int32_t*)(B + o_out), n_stored));
+    return stage_down(c, st, B);
 }
 
 int sw_get_payload_stats(sw_ctx* c, int64_t* calls, int64_t* waves, int64_t* accepted, int64_t* table_rebuilds, double* phase_ms) {
@@ -4363,7 +4412,7 @@ static int do_cansee_range(sw_ctx* c, int64_t first, int64_t K) {
         if (first < pr.second && first + K > pr.first) return fail(c, SW_EINVAL, "sw_cansee_range: rows [%lld, %lld) are present already", (long long)pr.first, (long long)pr.second);
     if (!c->d_rprov) {
         HIPCHK(c, hipMalloc((void**)&c->d_rprov, (size_t)SW_RANGE_SLOTS * (SW_MAX_CHUNKS + 1) * sizeof(unsigned)));
-        HIPCHK(c, hipEventCreateWithFlags(&c->ev_user, hipEventDisableTiming));
+        if (!c->ev_user) HIPCHK(c, hipEventCreateWithFlags(&c->ev_user, hipEventDisableTiming));   // (an earlier call may have made it)
     }
     if (c->d_L.cap < table_elems(c, c->cap)) return fail(c, SW_EIO, "the can_see table has no halo scratch rows (internal)");
     sw_ctx::RangeRec r;
@@ -4448,15 +4497,11 @@ int sw_export_rows(sw_ctx* c, int64_t first, int64_t K, void* dst_device, void* 
     for (const auto& pr : c->present) ok = ok || (first >= pr.first && first + K <= pr.second);
     if (!ok) return fail(c, SW_EINVAL, "sw_export_rows: the rows [%lld, %lld) have not been computed here", (long long)first, (long long)(first + K));
     HIPCHK(c, hipSetDevice(c->device));
-    if (!c->ev_user) HIPCHK(c, hipEventCreateWithFlags(&c->ev_user, hipEventDisableTiming));
-    hipStream_t cs = c->stream_cs, us = (hipStream_t)user_stream;
     // the destination may still be read by work the caller enqueued earlier (a previous collective)
-    HIPCHK(c, hipEventRecord(c->ev_user, us));
-    HIPCHK(c, hipStreamWaitEvent(cs, c->ev_user, 0));
-    HIPCHK(c, hipMemcpyAsync(dst_device, c->d_L.p + (size_t)first * c->npad, (size_t)K * c->npad * sizeof(int32_t), hipMemcpyDeviceToDevice, cs));
-    HIPCHK(c, hipEventRecord(c->ev_user, cs));
-    HIPCHK(c, hipStreamWaitEvent(us, c->ev_user, 0));
-    return SW_OK;
+    UserStream bracket;
+    CHK(bracket.join(c, (hipStream_t)user_stream, c->stream_cs));
+    HIPCHK(c, hipMemcpyAsync(dst_device, c->d_L.p + (size_t)first * c->npad, (size_t)K * c->npad * sizeof(int32_t), hipMemcpyDeviceToDevice, c->stream_cs));
+    return bracket.leave();
 }
 
 int sw_import_rows(sw_ctx* c, int64_t first, int64_t K, const void* src_device, void* user_stream) {
@@ -4466,13 +4511,10 @@ int sw_import_rows(sw_ctx* c, int64_t first, int64_t K, const void* src_device, 
         if (first < pr.second && first + K > pr.first) return fail(c, SW_EINVAL, "sw_import_rows: rows [%lld, %lld) are present already", (long long)pr.first, (long long)pr.second);
     HIPCHK(c, hipSetDevice(c->device));
     CHK(ensure_events(c, c->N));
-    if (!c->ev_user) HIPCHK(c, hipEventCreateWithFlags(&c->ev_user, hipEventDisableTiming));
-    hipStream_t cs = c->stream_cs, us = (hipStream_t)user_stream;
-    HIPCHK(c, hipEventRecord(c->ev_user, us));            // what the caller enqueued so far (the collective that fills src)
-    HIPCHK(c, hipStreamWaitEvent(cs, c->ev_user, 0));
-    HIPCHK(c, hipMemcpyAsync(c->d_L.p + (size_t)first * c->npad, src_device, (size_t)K * c->npad * sizeof(int32_t), hipMemcpyDeviceToDevice, cs));
-    HIPCHK(c, hipEventRecord(c->ev_user, cs));            // ... and the caller's stream may not reuse src before the copy is done
-    HIPCHK(c, hipStreamWaitEvent(us, c->ev_user, 0));
+    UserStream bracket;   // what the caller enqueued so far (the collective that fills src); it may not reuse src before the copy is done
+    CHK(bracket.join(c, (hipStream_t)user_stream, c->stream_cs));
+    HIPCHK(c, hipMemcpyAsync(c->d_L.p + (size_t)first * c->npad, src_device, (size_t)K * c->npad * sizeof(int32_t), hipMemcpyDeviceToDevice, c->stream_cs));
+    CHK(bracket.leave());
     mark_present(c, first, first + K);
     return SW_OK;
 }
@@ -5112,14 +5154,16 @@ int export_gather(sw_ctx* c, int64_t total, const ExportArrays& o) {
     return SW_OK;
 }
 
-// the exported arrays for `total` events inside d_xp_out
-int export_scratch(sw_ctx* c, int64_t total, bool with_t, bool with_sig, bool with_event, ExportArrays* o) {
+// the exported arrays for `total` events inside d_xp_out; with `st` and `host` (the host-array forms) stage_down(st, d_xp_out)
+// brings them to the caller's arrays
+int export_scratch(sw_ctx* c, int64_t total, bool with_t, bool with_sig, bool with_event, ExportArrays* o, Stage* st = nullptr, const ExportArrays& host = {}) {
     const size_t k = (size_t)total;
-    Carve cv;
-    const size_t o_id = cv.take(k * 32), o_sp = cv.take(k * 32), o_op = cv.take(k * 32), o_ar = cv.take(k), o_cr = cv.take(k * 4);
-    const size_t o_t = cv.take(with_t ? k * 8 : 0), o_sig = cv.take(with_sig ? k * 64 : 0), o_ev = cv.take(with_event ? k * 4 : 0);
-    CHK(dgrow(c, c->d_xp_out, cv.off, 0));
-    unsigned char* B = c->d_xp_out.p;
+    Stage own;
+    Stage& s = st ? *st : own;
+    const size_t o_id = s.out(host.id, k * 32), o_sp = s.out(host.sp_id, k * 32), o_op = s.out(host.op_id, k * 32), o_ar = s.out(host.arity, k), o_cr = s.out(host.creator, k * 4);
+    const size_t o_t = s.out(host.t, with_t ? k * 8 : 0), o_sig = s.out(host.sig, with_sig ? k * 64 : 0), o_ev = s.out(host.event, with_event ? k * 4 : 0);
+    unsigned char* B = nullptr;
+    CHK(stage_up(c, c->d_xp_out, s, &B));
     *o = ExportArrays{B + o_id, B + o_sp, B + o_op, B + o_ar, (int32_t*)(B + o_cr), with_t ? (double*)(B + o_t) : nullptr,
                       with_sig ? B + o_sig : nullptr, with_event ? (int32_t*)(B + o_ev) : nullptr};
     return SW_OK;
@@ -5131,24 +5175,18 @@ extern "C" {
 int sw_get_known_heights_device(sw_ctx* c, int64_t head_event, int32_t* d_out, void* user_stream) {
     if (!c || !d_out) return SW_EINVAL;
     if (head_event < c->first_resident || head_event >= c->divided) return fail(c, SW_ERANGE, "head %lld is not a divided, resident event", (long long)head_event);
-    HIPCHK(c, hipSetDevice(c->device));
-    if (!on_ctx_device(c, d_out, (size_t)c->n * sizeof(int32_t)))
-        return fail(c, SW_EINVAL, "sw_get_known_heights_device: the output must lie in memory of device %d (a host pointer, or another device's)", c->device);
+    CHK(device_args(c, "sw_get_known_heights_device", {{d_out, (size_t)c->n * sizeof(int32_t), 1}}));
     CHK(heights_on_device(c));
     const int np = c->npad;
     CHK(dgrow(c, c->d_q, (size_t)3 * np, 0));
-    if (!c->ev_user) HIPCHK(c, hipEventCreateWithFlags(&c->ev_user, hipEventDisableTiming));
-    hipStream_t us = (hipStream_t)user_stream;
-    HIPCHK(c, hipEventRecord(c->ev_user, us));            // (the output may still be read by what the caller enqueued earlier)
-    HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_user, 0));
+    UserStream bracket;   // (the output may still be read by what the caller enqueued earlier)
+    CHK(bracket.join(c, (hipStream_t)user_stream));
     hipLaunchKernelGGL(k_known_heights, dim3(1), dim3(np), 0, c->stream, (const int*)c->d_L.p, (const int*)c->d_ht.p, (int)head_event, np, c->d_q.p);
     c->ctr.kernel_launches++;
     HIPCHK(c, hipGetLastError());
     // n entries, not npad: the caller's array ends there
     HIPCHK(c, hipMemcpyAsync(d_out, c->d_q.p, (size_t)c->n * sizeof(int32_t), hipMemcpyDeviceToDevice, c->stream));
-    HIPCHK(c, hipEventRecord(c->ev_user, c->stream));
-    HIPCHK(c, hipStreamWaitEvent(us, c->ev_user, 0));
-    return SW_OK;
+    return bracket.leave();
 }
 
 int sw_export_payload_device(sw_ctx* c, int64_t head_event, const int32_t* d_known_height, int64_t cap, uint8_t* d_id32, uint8_t* d_sp_id32,
@@ -5160,22 +5198,16 @@ int sw_export_payload_device(sw_ctx* c, int64_t head_event, const int32_t* d_kno
     CHK(export_pre(c, head_event, "sw_export_payload_device"));
     if (cap < 0 || (cap > 0 && (!d_id32 || !d_sp_id32 || !d_op_id32 || !d_arity || !d_creator)))
         return fail(c, SW_EINVAL, "sw_export_payload_device: NULL output arrays (capacity %lld)", (long long)cap);
-    if (((uintptr_t)d_id32 | (uintptr_t)d_sp_id32 | (uintptr_t)d_op_id32 | (uintptr_t)d_sig64) & 15)
-        return fail(c, SW_EINVAL, "sw_export_payload_device: the id arrays and the signatures must be 16-byte aligned");
-    HIPCHK(c, hipSetDevice(c->device));
+    // (with capacity 0 the rows are empty and skipped: the alignment of whatever was passed is asked for all the same)
+    if (cap == 0 && (((uintptr_t)d_id32 | (uintptr_t)d_sp_id32 | (uintptr_t)d_op_id32 | (uintptr_t)d_sig64) & 15)) return misaligned(c, "sw_export_payload_device", 16);
     const size_t k = (size_t)cap;
-    bool on = !d_known_height || on_ctx_device(c, d_known_height, (size_t)c->n * sizeof(int32_t));
-    if (cap > 0)
-        on = on && on_ctx_device(c, d_id32, k * 32) && on_ctx_device(c, d_sp_id32, k * 32) && on_ctx_device(c, d_op_id32, k * 32) &&
-             on_ctx_device(c, d_arity, k) && on_ctx_device(c, d_creator, k * 4) && (!d_t || on_ctx_device(c, d_t, k * 8)) &&
-             (!d_sig64 || on_ctx_device(c, d_sig64, k * 64)) && (!d_event || on_ctx_device(c, d_event, k * 4));
-    if (!on) return fail(c, SW_EINVAL, "sw_export_payload_device: every array must lie in memory of device %d (a host pointer, or another device's)", c->device);
+    CHK(device_args(c, "sw_export_payload_device", {{d_id32, k * 32, 16}, {d_sp_id32, k * 32, 16}, {d_op_id32, k * 32, 16}, {d_sig64, k * 64, 16},
+                                                    {d_known_height, (size_t)c->n * sizeof(int32_t), 1}, {d_arity, k, 1}, {d_creator, k * 4, 1}, {d_t, k * 8, 1},
+                                                    {d_event, k * 4, 1}}));
     const bool prof = c->profiling;
     auto t0 = std::chrono::steady_clock::now();
-    if (!c->ev_user) HIPCHK(c, hipEventCreateWithFlags(&c->ev_user, hipEventDisableTiming));
-    hipStream_t us = (hipStream_t)user_stream;
-    HIPCHK(c, hipEventRecord(c->ev_user, us));            // the producer of d_known_height; earlier readers of the output arrays
-    HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_user, 0));
+    UserStream bracket;   // the producer of d_known_height; earlier readers of the output arrays
+    CHK(bracket.join(c, (hipStream_t)user_stream));
     int64_t total = 0;
     CHK(export_ranges(c, head_event, d_known_height, hipMemcpyDeviceToDevice, &total));
     *n_out = total;
@@ -5184,8 +5216,7 @@ int sw_export_payload_device(sw_ctx* c, int64_t head_event, const int32_t* d_kno
     if (total > cap) return fail(c, SW_ERANGE, "sw_export_payload_device: %lld events to export, capacity %lld (nothing written)", (long long)total, (long long)cap);
     t0 = std::chrono::steady_clock::now();
     CHK(export_gather(c, total, ExportArrays{d_id32, d_sp_id32, d_op_id32, d_arity, d_creator, d_t, d_sig64, d_event}));
-    HIPCHK(c, hipEventRecord(c->ev_user, c->stream));     // whatever the caller enqueues next reads complete arrays
-    HIPCHK(c, hipStreamWaitEvent(us, c->ev_user, 0));
+    CHK(bracket.leave());
     if (prof) { HIPCHK(c, hipStreamSynchronize(c->stream)); c->xp_ms[1] = ms_since(t0); }
     c->xp_calls++;
     c->xp_events += total;
@@ -5211,18 +5242,10 @@ int sw_export_payload(sw_ctx* c, int64_t head_event, const int32_t* known_height
     if (total > cap) return fail(c, SW_ERANGE, "sw_export_payload: %lld events to export, capacity %lld (nothing written)", (long long)total, (long long)cap);
     t0 = std::chrono::steady_clock::now();
     ExportArrays d{};
-    CHK(export_scratch(c, total, t != nullptr, sig64 != nullptr, event != nullptr, &d));
+    Stage st;
+    CHK(export_scratch(c, total, t != nullptr, sig64 != nullptr, event != nullptr, &d, &st, ExportArrays{id32, sp_id32, op_id32, arity, creator, t, sig64, event}));
     CHK(export_gather(c, total, d));
-    const size_t k = (size_t)total;
-    HIPCHK(c, hipMemcpyAsync(id32, d.id, k * 32, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(sp_id32, d.sp_id, k * 32, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(op_id32, d.op_id, k * 32, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(arity, d.arity, k, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(creator, d.creator, k * 4, hipMemcpyDeviceToHost, c->stream));
-    if (t) HIPCHK(c, hipMemcpyAsync(t, d.t, k * 8, hipMemcpyDeviceToHost, c->stream));
-    if (sig64) HIPCHK(c, hipMemcpyAsync(sig64, d.sig, k * 64, hipMemcpyDeviceToHost, c->stream));
-    if (event) HIPCHK(c, hipMemcpyAsync(event, d.event, k * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    CHK(stage_down(c, st, c->d_xp_out.p));
     if (prof) c->xp_ms[1] = ms_since(t0);
     c->xp_calls++;
     c->xp_events += total;
@@ -5286,23 +5309,21 @@ int consensus_events(sw_ctx* c, const char* what, int64_t first, int64_t K, int3
     if (!K || (!rr_out && !cts_out)) return SW_OK;
     HIPCHK(c, hipSetDevice(c->device));
     const int np = c->npad;
-    Carve cv;
-    const size_t o_rr = cv.take(rr_out ? (size_t)K * 4 : 0), o_cts = cv.take(cts_out ? (size_t)K * 8 : 0);
-    CHK(dgrow(c, c->d_cs_out, cv.off, 0));
+    Stage st;
+    const size_t o_rr = st.out_opt(rr_out, (size_t)K * 4), o_cts = st.out_opt(cts_out, (size_t)K * 8);
+    unsigned char* B = nullptr;
+    CHK(stage_up(c, c->d_cs_out, st, &B));
     CHK(dgrow(c, c->d_cs_ordpos, np, 0));
     // (a pageable source: staged before the call returns; every entry below n is written, the kernel reads no other)
     HIPCHK(c, hipMemcpyAsync(c->d_cs_ordpos.p, c->ord_pos.data(), (size_t)c->n * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-    int32_t* d_rr_out = rr_out ? (int32_t*)(c->d_cs_out.p + o_rr) : nullptr;
-    unsigned long long* d_cts_out = cts_out ? (unsigned long long*)(c->d_cs_out.p + o_cts) : nullptr;
+    int32_t* d_rr_out = rr_out ? (int32_t*)(B + o_rr) : nullptr;
+    unsigned long long* d_cts_out = cts_out ? (unsigned long long*)(B + o_cts) : nullptr;
     const unsigned grid = (unsigned)std::min<int64_t>(4096, (K + cns::THREADS - 1) / cns::THREADS);
     hipLaunchKernelGGL(cns::k_consensus_events, dim3(grid), dim3(cns::THREADS), 0, c->stream, (long long)first, (long long)K, (const int*)c->d_seq.p,
                        (const int*)c->d_cr.p, (const int*)c->d_cs_ordpos.p, (const int*)c->d_rr.p, (const unsigned long long*)c->d_cts.p, d_rr_out, d_cts_out);
     c->ctr.kernel_launches++;
     HIPCHK(c, hipGetLastError());
-    if (rr_out) HIPCHK(c, hipMemcpyAsync(rr_out, d_rr_out, (size_t)K * 4, hipMemcpyDeviceToHost, c->stream));
-    if (cts_out) HIPCHK(c, hipMemcpyAsync(cts_out, d_cts_out, (size_t)K * 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return SW_OK;
+    return stage_down(c, st, B);
 }
 
 struct OrderedArrays { int32_t* event; uint8_t* id; int32_t* creator; int32_t* rr; double* t; };
@@ -5348,22 +5369,14 @@ int sw_export_ordered_device(sw_ctx* c, int64_t first, int64_t K, int32_t* d_eve
                              int32_t* d_round_received, double* d_time, void* user_stream) {
     if (!c) return SW_EINVAL;
     CHK(ordered_pre(c, "sw_export_ordered_device", first, K, d_id32 != nullptr));
-    if ((uintptr_t)d_id32 & 15) return fail(c, SW_EINVAL, "sw_export_ordered_device: the id array must be 16-byte aligned");
+    if (!K && ((uintptr_t)d_id32 & 15)) return misaligned(c, "sw_export_ordered_device", 16);   // (asked for K = 0 too, where the row is skipped)
     if (!K || (!d_event && !d_id32 && !d_creator && !d_round_received && !d_time)) return SW_OK;
-    HIPCHK(c, hipSetDevice(c->device));
     const size_t k = (size_t)K;
-    const bool on = (!d_event || on_ctx_device(c, d_event, k * 4)) && (!d_id32 || on_ctx_device(c, d_id32, k * 32)) &&
-                    (!d_creator || on_ctx_device(c, d_creator, k * 4)) && (!d_round_received || on_ctx_device(c, d_round_received, k * 4)) &&
-                    (!d_time || on_ctx_device(c, d_time, k * 8));
-    if (!on) return fail(c, SW_EINVAL, "sw_export_ordered_device: every array must lie in memory of device %d (a host pointer, or another device's)", c->device);
-    if (!c->ev_user) HIPCHK(c, hipEventCreateWithFlags(&c->ev_user, hipEventDisableTiming));
-    hipStream_t us = (hipStream_t)user_stream;
-    HIPCHK(c, hipEventRecord(c->ev_user, us));            // earlier readers of the output arrays
-    HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_user, 0));
+    CHK(device_args(c, "sw_export_ordered_device", {{d_id32, k * 32, 16}, {d_event, k * 4, 1}, {d_creator, k * 4, 1}, {d_round_received, k * 4, 1}, {d_time, k * 8, 1}}));
+    UserStream bracket;   // earlier readers of the output arrays
+    CHK(bracket.join(c, (hipStream_t)user_stream));
     CHK(ordered_gather(c, first, K, OrderedArrays{d_event, d_id32, d_creator, d_round_received, d_time}));
-    HIPCHK(c, hipEventRecord(c->ev_user, c->stream));     // whatever the caller enqueues next reads complete arrays
-    HIPCHK(c, hipStreamWaitEvent(us, c->ev_user, 0));
-    return SW_OK;
+    return bracket.leave();
 }
 
 int sw_export_ordered(sw_ctx* c, int64_t first, int64_t K, int32_t* event, uint8_t* id32, int32_t* creator, int32_t* round_received, double* time) {
@@ -5372,21 +5385,15 @@ int sw_export_ordered(sw_ctx* c, int64_t first, int64_t K, int32_t* event, uint8
     if (!K || (!event && !id32 && !creator && !round_received && !time)) return SW_OK;
     HIPCHK(c, hipSetDevice(c->device));
     const size_t k = (size_t)K;
-    Carve cv;
-    const size_t o_ev = cv.take(event ? k * 4 : 0), o_id = cv.take(id32 ? k * 32 : 0), o_cr = cv.take(creator ? k * 4 : 0),
-                 o_rr = cv.take(round_received ? k * 4 : 0), o_t = cv.take(time ? k * 8 : 0);
-    CHK(dgrow(c, c->d_cs_out, cv.off, 0));
-    unsigned char* B = c->d_cs_out.p;
+    Stage st;
+    const size_t o_ev = st.out_opt(event, k * 4), o_id = st.out_opt(id32, k * 32), o_cr = st.out_opt(creator, k * 4),
+                 o_rr = st.out_opt(round_received, k * 4), o_t = st.out_opt(time, k * 8);
+    unsigned char* B = nullptr;
+    CHK(stage_up(c, c->d_cs_out, st, &B));
     const OrderedArrays d{event ? (int32_t*)(B + o_ev) : nullptr, id32 ? B + o_id : nullptr, creator ? (int32_t*)(B + o_cr) : nullptr,
                           round_received ? (int32_t*)(B + o_rr) : nullptr, time ? (double*)(B + o_t) : nullptr};
     CHK(ordered_gather(c, first, K, d));
-    if (event) HIPCHK(c, hipMemcpyAsync(event, d.event, k * 4, hipMemcpyDeviceToHost, c->stream));
-    if (id32) HIPCHK(c, hipMemcpyAsync(id32, d.id, k * 32, hipMemcpyDeviceToHost, c->stream));
-    if (creator) HIPCHK(c, hipMemcpyAsync(creator, d.creator, k * 4, hipMemcpyDeviceToHost, c->stream));
-    if (round_received) HIPCHK(c, hipMemcpyAsync(round_received, d.rr, k * 4, hipMemcpyDeviceToHost, c->stream));
-    if (time) HIPCHK(c, hipMemcpyAsync(time, d.t, k * 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return SW_OK;
+    return stage_down(c, st, B);
 }
 
 int sw_get_consensus_stats(sw_ctx* c, int64_t* record_calls, int64_t* recorded_events, int64_t* export_calls, int64_t* exported_events) {
@@ -5546,30 +5553,24 @@ int sw_validate_payload_device(sw_ctx* c, int64_t K, const uint8_t* d_msgs, cons
     if (!c) return SW_EINVAL;
     CHK(validate_pre(c, K, d_msgs, d_msg_off, msg_bytes, d_whole, d_whole_off, whole_bytes, d_sig64, d_creator, d_id32, d_ok, "sw_validate_payload_device"));
     if (K == 0) return SW_OK;
-    if ((uintptr_t)d_id32 & 7) return fail(c, SW_EINVAL, "sw_validate_payload_device: the id array must be 8-byte aligned");
-    if (((uintptr_t)d_msg_off | (uintptr_t)d_whole_off) & 7) return fail(c, SW_EINVAL, "sw_validate_payload_device: the offsets must be 8-byte aligned");
-    HIPCHK(c, hipSetDevice(c->device));
     const size_t k = (size_t)K;
     const bool idchk = d_whole_off != nullptr;
-    if (!on_ctx_device(c, d_msg_off, (k + 1) * 8) || (msg_bytes > 0 && !on_ctx_device(c, d_msgs, (size_t)msg_bytes)) ||
-        !on_ctx_device(c, d_sig64, k * 64) || !on_ctx_device(c, d_creator, k * 4) || !on_ctx_device(c, d_ok, k) ||
-        (idchk && (!on_ctx_device(c, d_whole_off, (k + 1) * 8) || !on_ctx_device(c, d_id32, k * 32) ||
-                   (whole_bytes > 0 && !on_ctx_device(c, d_whole, (size_t)whole_bytes)))))
-        return fail(c, SW_EINVAL, "sw_validate_payload_device: every array must lie in memory of device %d (a host pointer, or another device's)", c->device);
+    // (ids without an id check are never read: their row is skipped, and only their alignment is asked for, as it always was)
+    if (!idchk && ((uintptr_t)d_id32 & 7)) return misaligned(c, "sw_validate_payload_device", 8);
+    CHK(device_args(c, "sw_validate_payload_device", {{d_id32, idchk ? k * 32 : 0, 8}, {d_msg_off, (k + 1) * 8, 8}, {d_whole_off, (k + 1) * 8, 8},
+                                                      {d_msgs, (size_t)msg_bytes, 1}, {d_sig64, k * 64, 1}, {d_creator, k * 4, 1}, {d_ok, k, 1},
+                                                      {d_whole, idchk ? (size_t)whole_bytes : 0, 1}}));
     const bool prof = c->profiling;
     const auto t0 = std::chrono::steady_clock::now();
-    if (!c->ev_user) HIPCHK(c, hipEventCreateWithFlags(&c->ev_user, hipEventDisableTiming));
-    hipStream_t us = (hipStream_t)user_stream;
-    HIPCHK(c, hipEventRecord(c->ev_user, us));            // the producers of the arrays; earlier readers of d_ok
-    HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_user, 0));
+    UserStream bracket;   // the producers of the arrays; earlier readers of d_ok
+    CHK(bracket.join(c, (hipStream_t)user_stream));
     // (a zero-length buffer may be NULL: the kernel then only forms pointers it never reads through; `whole` non-NULL is
     // what selects the id check there)
     const uint8_t* anchor = (const uint8_t*)c->d_vkeys.p;
     const swv::Payload p{d_msgs ? d_msgs : anchor, (const long long*)d_msg_off, (long long)msg_bytes, idchk ? (d_whole ? d_whole : anchor) : nullptr,
                          (const long long*)d_whole_off, (long long)whole_bytes, d_sig64, d_creator, d_id32};
     CHK(validate_launch(c, K, p, d_ok));
-    HIPCHK(c, hipEventRecord(c->ev_user, c->stream));     // whatever the caller enqueues next reads a complete d_ok
-    HIPCHK(c, hipStreamWaitEvent(us, c->ev_user, 0));
+    CHK(bracket.leave());   // whatever the caller enqueues next reads a complete d_ok
     c->v_ms[1] = 0;
     if (prof) { HIPCHK(c, hipStreamSynchronize(c->stream)); c->v_ms[1] = ms_since(t0); }
     c->v_calls++;
@@ -5587,26 +5588,16 @@ int sw_validate_payload(sw_ctx* c, int64_t K, const uint8_t* msgs, const int64_t
     const auto t0 = std::chrono::steady_clock::now();
     const size_t k = (size_t)K, mb = (size_t)msg_bytes, wb = (size_t)whole_bytes;
     const bool idchk = whole_off != nullptr;
-    Carve cv;
-    const size_t o_moff = cv.take((k + 1) * 8), o_m = cv.take(mb), o_woff = cv.take(idchk ? (k + 1) * 8 : 0), o_w = cv.take(idchk ? wb : 0);
-    const size_t o_sig = cv.take(k * 64), o_cr = cv.take(k * 4), o_id = cv.take(idchk ? k * 32 : 0), o_ok = cv.take(k);
-    CHK(dgrow(c, c->d_v_in, cv.off + 256, 0));
-    unsigned char* B = c->d_v_in.p;
-    HIPCHK(c, hipMemcpyAsync(B + o_moff, msg_off, (k + 1) * 8, hipMemcpyHostToDevice, c->stream));
-    if (mb) HIPCHK(c, hipMemcpyAsync(B + o_m, msgs, mb, hipMemcpyHostToDevice, c->stream));
-    if (idchk) {
-        HIPCHK(c, hipMemcpyAsync(B + o_woff, whole_off, (k + 1) * 8, hipMemcpyHostToDevice, c->stream));
-        if (wb) HIPCHK(c, hipMemcpyAsync(B + o_w, whole, wb, hipMemcpyHostToDevice, c->stream));
-        HIPCHK(c, hipMemcpyAsync(B + o_id, id32, k * 32, hipMemcpyHostToDevice, c->stream));
-    }
-    HIPCHK(c, hipMemcpyAsync(B + o_sig, sig64, k * 64, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemcpyAsync(B + o_cr, creator, k * 4, hipMemcpyHostToDevice, c->stream));
+    Stage st;   // (an absent buffer takes no room: `whole` and `whole_off` come together or not at all, validate_pre)
+    const size_t o_moff = st.in(msg_off, (k + 1) * 8), o_m = st.in(msgs, mb), o_woff = st.in(whole_off, (k + 1) * 8), o_w = st.in(whole, wb);
+    const size_t o_sig = st.in(sig64, k * 64), o_cr = st.in(creator, k * 4), o_id = st.in(idchk ? id32 : nullptr, k * 32), o_ok = st.out(ok, k);
+    unsigned char* B = nullptr;
+    CHK(stage_up(c, c->d_v_in, st, &B));
     const swv::Payload p{B + o_m, (const long long*)(B + o_moff), (long long)msg_bytes, idchk ? B + o_w : nullptr,
                          idchk ? (const long long*)(B + o_woff) : nullptr, (long long)whole_bytes, B + o_sig, (const int32_t*)(B + o_cr),
                          idchk ? B + o_id : nullptr};
     CHK(validate_launch(c, K, p, B + o_ok));
-    HIPCHK(c, hipMemcpyAsync(ok, B + o_ok, k, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    CHK(stage_down(c, st, B));
     c->v_ms[1] = prof ? ms_since(t0) : 0;
     int64_t acc = 0;
     for (size_t i = 0; i < k; ++i) acc += ok[i] != 0;
@@ -5801,25 +5792,19 @@ int sw_pack_events_device(sw_ctx* c, int64_t K, const uint8_t* d_sp_id32, const 
     int64_t bm = 0, bw = 0;
     CHK(pack_pre(c, K, d_sp_id32, d_op_id32, d_arity, d_creator, d_t, d_sig64, d_data, d_data_off, data_bytes, d_data_none, d_msgs, d_msg_off, msg_cap,
                  d_whole, d_whole_off, whole_cap, &bm, &bw, what));
-    if (((uintptr_t)d_msgs | (uintptr_t)d_whole | (uintptr_t)d_sig64 | (uintptr_t)d_sp_id32 | (uintptr_t)d_op_id32) & 15)
-        return fail(c, SW_EINVAL, "%s: the byte streams, the signatures and the id arrays must be 16-byte aligned", what);
-    if (((uintptr_t)d_msg_off | (uintptr_t)d_whole_off | (uintptr_t)d_data_off | (uintptr_t)d_t) & 7)
-        return fail(c, SW_EINVAL, "%s: the offsets and the timestamps must be 8-byte aligned", what);
-    if ((uintptr_t)d_creator & 3) return fail(c, SW_EINVAL, "%s: the creators must be 4-byte aligned", what);
-    HIPCHK(c, hipSetDevice(c->device));
     const size_t k = (size_t)K;
-    bool on = on_ctx_device(c, d_msg_off, (k + 1) * 8) && on_ctx_device(c, d_whole_off, (k + 1) * 8);
-    if (K > 0)
-        on = on && on_ctx_device(c, d_sp_id32, k * 32) && on_ctx_device(c, d_op_id32, k * 32) && on_ctx_device(c, d_arity, k) &&
-             on_ctx_device(c, d_creator, k * 4) && on_ctx_device(c, d_t, k * 8) && on_ctx_device(c, d_sig64, k * 64) &&
-             on_ctx_device(c, d_msgs, (size_t)msg_cap) && on_ctx_device(c, d_whole, (size_t)whole_cap) &&
-             (!d_encodable || on_ctx_device(c, d_encodable, k)) && (!d_data_off || on_ctx_device(c, d_data_off, (k + 1) * 8)) &&
-             (!d_data || data_bytes == 0 || on_ctx_device(c, d_data, (size_t)data_bytes)) && (!d_data_none || on_ctx_device(c, d_data_none, k));
-    if (!on) return fail(c, SW_EINVAL, "%s: every array must lie in memory of device %d (a host pointer, or another device's)", what, c->device);
-    if (!c->ev_user) HIPCHK(c, hipEventCreateWithFlags(&c->ev_user, hipEventDisableTiming));
-    hipStream_t us = (hipStream_t)user_stream;
-    HIPCHK(c, hipEventRecord(c->ev_user, us));            // the producers of the arrays; earlier readers of the outputs
-    HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_user, 0));
+    if (K == 0) {   // (no event: only the two offset arrays are touched; the alignment of whatever else was passed is asked for all the same)
+        if (((uintptr_t)d_msgs | (uintptr_t)d_whole | (uintptr_t)d_sig64 | (uintptr_t)d_sp_id32 | (uintptr_t)d_op_id32) & 15) return misaligned(c, what, 16);
+        if (((uintptr_t)d_data_off | (uintptr_t)d_t) & 7) return misaligned(c, what, 8);
+        if ((uintptr_t)d_creator & 3) return misaligned(c, what, 4);
+    }
+    // (the two streams are empty rows when no event is packed, whatever their capacity)
+    CHK(device_args(c, what, {{d_msgs, K ? (size_t)msg_cap : 0, 16}, {d_whole, K ? (size_t)whole_cap : 0, 16}, {d_sig64, k * 64, 16}, {d_sp_id32, k * 32, 16},
+                              {d_op_id32, k * 32, 16}, {d_msg_off, (k + 1) * 8, 8}, {d_whole_off, (k + 1) * 8, 8}, {d_data_off, K ? (k + 1) * 8 : 0, 8},
+                              {d_t, k * 8, 8}, {d_creator, k * 4, 4}, {d_arity, k, 1}, {d_encodable, k, 1}, {d_data, K ? (size_t)data_bytes : 0, 1},
+                              {d_data_none, k, 1}}));
+    UserStream bracket;   // the producers of the arrays; earlier readers of the outputs
+    CHK(bracket.join(c, (hipStream_t)user_stream));
     if (K == 0) {
         HIPCHK(c, hipMemsetAsync(d_msg_off, 0, 8, c->stream));
         HIPCHK(c, hipMemsetAsync(d_whole_off, 0, 8, c->stream));
@@ -5827,9 +5812,7 @@ int sw_pack_events_device(sw_ctx* c, int64_t K, const uint8_t* d_sp_id32, const 
         CHK(pack_launch(c, K, PackArrays{d_sp_id32, d_op_id32, d_arity, d_creator, d_t, d_sig64, d_data, d_data_off, data_bytes, d_data_none, d_msgs,
                                          d_msg_off, d_whole, d_whole_off, d_encodable}, bm, bw));
     }
-    HIPCHK(c, hipEventRecord(c->ev_user, c->stream));     // whatever the caller enqueues next reads complete streams
-    HIPCHK(c, hipStreamWaitEvent(us, c->ev_user, 0));
-    return SW_OK;
+    return bracket.leave();   // whatever the caller enqueues next reads complete streams
 }
 
 int sw_pack_events(sw_ctx* c, int64_t K, const uint8_t* sp_id32, const uint8_t* op_id32, const uint8_t* arity, const int32_t* creator, const double* t,
@@ -5846,29 +5829,22 @@ int sw_pack_events(sw_ctx* c, int64_t K, const uint8_t* sp_id32, const uint8_t* 
     if (K == 0) return SW_OK;
     HIPCHK(c, hipSetDevice(c->device));
     const size_t k = (size_t)K, db = (size_t)data_bytes;
-    Carve cv;
-    const size_t o_sp = cv.take(k * 32), o_op = cv.take(k * 32), o_ar = cv.take(k), o_cr = cv.take(k * 4), o_t = cv.take(k * 8), o_sig = cv.take(k * 64);
-    const size_t o_doff = cv.take(data_off ? (k + 1) * 8 : 0), o_d = cv.take(db), o_dn = cv.take(data_none ? k : 0);
-    const size_t o_moff = cv.take((k + 1) * 8), o_woff = cv.take((k + 1) * 8), o_m = cv.take((size_t)bm), o_w = cv.take((size_t)bw), o_enc = cv.take(k);
-    CHK(dgrow(c, c->d_pk_in, cv.off + 256, 0));
-    unsigned char* B = c->d_pk_in.p;
-    const struct { size_t o; const void* src; size_t bytes; } up[] = {
-        {o_sp, sp_id32, k * 32}, {o_op, op_id32, k * 32}, {o_ar, arity, k}, {o_cr, creator, k * 4}, {o_t, t, k * 8}, {o_sig, sig64, k * 64},
-        {o_doff, data_off, data_off ? (k + 1) * 8 : 0}, {o_d, data, db}, {o_dn, data_none, data_none ? k : 0}};
-    for (const auto& u : up)
-        if (u.bytes) HIPCHK(c, hipMemcpyAsync(B + u.o, u.src, u.bytes, hipMemcpyHostToDevice, c->stream));
+    Stage st;   // (the two streams come back behind the offsets, by the totals those report)
+    const size_t o_sp = st.in(sp_id32, k * 32), o_op = st.in(op_id32, k * 32), o_ar = st.in(arity, k), o_cr = st.in(creator, k * 4), o_t = st.in(t, k * 8);
+    const size_t o_sig = st.in(sig64, k * 64), o_doff = st.in(data_off, (k + 1) * 8), o_d = st.in(data, db), o_dn = st.in(data_none, k);
+    const size_t o_moff = st.out(msg_off, (k + 1) * 8), o_woff = st.out(whole_off, (k + 1) * 8), o_m = st.out(msgs, (size_t)bm, 0), o_w = st.out(whole, (size_t)bw, 0);
+    const size_t o_enc = st.out(encodable, k);
+    unsigned char* B = nullptr;
+    CHK(stage_up(c, c->d_pk_in, st, &B));
     CHK(pack_launch(c, K, PackArrays{B + o_sp, B + o_op, B + o_ar, (const int32_t*)(B + o_cr), (const double*)(B + o_t), B + o_sig,
                                      data_off ? B + o_d : nullptr, data_off ? (const int64_t*)(B + o_doff) : nullptr, data_bytes,
                                      data_none ? B + o_dn : nullptr, B + o_m, (int64_t*)(B + o_moff), B + o_w, (int64_t*)(B + o_woff), B + o_enc}, bm, bw));
-    HIPCHK(c, hipMemcpyAsync(msg_off, B + o_moff, (k + 1) * 8, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(whole_off, B + o_woff, (k + 1) * 8, hipMemcpyDeviceToHost, c->stream));
-    if (encodable) HIPCHK(c, hipMemcpyAsync(encodable, B + o_enc, k, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    CHK(stage_down(c, st, B));
     const int64_t tm = msg_off[K], tw = whole_off[K];
     if (tm < 0 || tm > bm || tw < 0 || tw > bw) return fail(c, SW_EIO, "sw_pack_events: totals %lld / %lld outside the bounds (internal error)", (long long)tm, (long long)tw);
-    if (tm) HIPCHK(c, hipMemcpyAsync(msgs, B + o_m, (size_t)tm, hipMemcpyDeviceToHost, c->stream));
-    if (tw) HIPCHK(c, hipMemcpyAsync(whole, B + o_w, (size_t)tw, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    st.out_bytes(msgs, (size_t)tm);
+    st.out_bytes(whole, (size_t)tw);
+    CHK(stage_down(c, st, B));
     c->pk_bytes += tm + tw;
     if (msg_bytes) *msg_bytes = tm;
     if (whole_bytes) *whole_bytes = tw;
@@ -6059,9 +6035,8 @@ int ingest_data_core(sw_ctx* c, int64_t K, const uint8_t* d_id32, const uint8_t*
     DataPlan p{};
     CHK(data_scratch(c, K, K, K, &p));
     CHK(data_reserve(c, N0 + K, c->data_used + data_bytes));
-    if (!c->ev_user) HIPCHK(c, hipEventCreateWithFlags(&c->ev_user, hipEventDisableTiming));
-    HIPCHK(c, hipEventRecord(c->ev_user, us));
-    HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_user, 0));
+    UserStream bracket;   // (left by the destructor on a failure; a success has drained the stream)
+    CHK(bracket.join(c, us));
     // an event whose data range cannot be used is not valid (-3): pack's d_encodable rule, folded into a copy of d_ok
     // The lengths of the ranges that stay ok are summed: ranges of a peer may overlap (offsets that jump back across a
     // rejected event), and the append could then outgrow the reservation behind the commit.  Such a payload is refused whole.
@@ -6078,6 +6053,7 @@ int ingest_data_core(sw_ctx* c, int64_t K, const uint8_t* d_id32, const uint8_t*
         return fail(c, SW_EINVAL, "the usable data ranges of the payload hold %llu bytes, its buffer %lld: ranges overlap (nothing stored)", usable,
                     (long long)data_bytes);
     CHK(payload_core(c, K, d_id32, d_sp_id32, d_op_id32, d_arity, d_creator, p.ok, d_t, d_sig64, c->stream, d_out, n_stored));
+    bracket.drained();   // (by payload_core, and again by after() below)
     const int64_t A = *n_stored;
     if (A == 0) return SW_OK;
     // ---- committed: the data of the new events, in dense order (slot r = the payload position of the event with index N0 + r)
@@ -6111,21 +6087,13 @@ int sw_set_event_data_device(sw_ctx* c, int64_t first, int64_t K, const uint8_t*
     if (!c) return SW_EINVAL;
     const char* what = "sw_set_event_data_device";
     CHK(data_set_args(c, first, K, d_data, d_data_off, data_bytes, d_data_none, what));
-    if ((uintptr_t)d_data_off & 7) return fail(c, SW_EINVAL, "%s: the offsets must be 8-byte aligned", what);
-    if (K == 0) return SW_OK;
-    HIPCHK(c, hipSetDevice(c->device));
+    if (K == 0) return ((uintptr_t)d_data_off & 7) ? misaligned(c, what, 8) : SW_OK;   // (asked for K = 0 too)
     const size_t k = (size_t)K;
-    if ((d_data_off && !on_ctx_device(c, d_data_off, (k + 1) * 8)) || (d_data && data_bytes > 0 && !on_ctx_device(c, d_data, (size_t)data_bytes)) ||
-        (d_data_none && !on_ctx_device(c, d_data_none, k)))
-        return fail(c, SW_EINVAL, "%s: every array must lie in memory of device %d (a host pointer, or another device's)", what, c->device);
-    if (!c->ev_user) HIPCHK(c, hipEventCreateWithFlags(&c->ev_user, hipEventDisableTiming));
-    hipStream_t us = (hipStream_t)user_stream;
-    HIPCHK(c, hipEventRecord(c->ev_user, us));
-    HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_user, 0));
+    CHK(device_args(c, what, {{d_data_off, (k + 1) * 8, 8}, {d_data, (size_t)data_bytes, 1}, {d_data_none, k, 1}}));
+    UserStream bracket;
+    CHK(bracket.join(c, (hipStream_t)user_stream));
     CHK(data_set_body(c, K, d_data, d_data_off, data_bytes, d_data_none, what));
-    HIPCHK(c, hipEventRecord(c->ev_user, c->stream));     // the caller may reuse its arrays behind this
-    HIPCHK(c, hipStreamWaitEvent(us, c->ev_user, 0));
-    return SW_OK;
+    return bracket.leave();   // the caller may reuse its arrays behind this
 }
 
 int sw_set_event_data(sw_ctx* c, int64_t first, int64_t K, const uint8_t* data, const int64_t* data_off, int64_t data_bytes, const uint8_t* data_none) {
@@ -6141,14 +6109,11 @@ int sw_set_event_data(sw_ctx* c, int64_t first, int64_t K, const uint8_t* data, 
                             (long long)(first + i), (long long)a, (long long)b, (long long)data_bytes, dat::MAX_DATA);
         }
     HIPCHK(c, hipSetDevice(c->device));
-    const size_t k = (size_t)K, db = (size_t)data_bytes;
-    Carve cv;
-    const size_t o_off = cv.take(data_off ? (k + 1) * 8 : 0), o_d = cv.take(db), o_n = cv.take(data_none ? k : 0);
-    CHK(dgrow(c, c->d_dt_in, cv.off + 256, 0));
-    unsigned char* B = c->d_dt_in.p;
-    if (data_off) HIPCHK(c, hipMemcpyAsync(B + o_off, data_off, (k + 1) * 8, hipMemcpyHostToDevice, c->stream));
-    if (db) HIPCHK(c, hipMemcpyAsync(B + o_d, data, db, hipMemcpyHostToDevice, c->stream));
-    if (data_none) HIPCHK(c, hipMemcpyAsync(B + o_n, data_none, k, hipMemcpyHostToDevice, c->stream));
+    const size_t k = (size_t)K;
+    Stage st;
+    const size_t o_off = st.in(data_off, (k + 1) * 8), o_d = st.in(data, (size_t)data_bytes), o_n = st.in(data_none, k);
+    unsigned char* B = nullptr;
+    CHK(stage_up(c, c->d_dt_in, st, &B));
     return data_set_body(c, K, data_off ? B + o_d : nullptr, data_off ? (const int64_t*)(B + o_off) : nullptr, data_bytes, data_none ? B + o_n : nullptr, what);
 }
 
@@ -6182,24 +6147,18 @@ int sw_gather_event_data_device(sw_ctx* c, int64_t K, const int32_t* d_event, in
     const char* what = "sw_gather_event_data_device";
     bool query = false;
     CHK(data_gather_args(c, K, d_event, cap, d_data, d_data_off, d_data_none, n_bytes, &query, what));
-    if ((uintptr_t)d_data & 15) return fail(c, SW_EINVAL, "%s: the data buffer must be 16-byte aligned", what);
-    if (((uintptr_t)d_data_off & 7) || ((uintptr_t)d_event & 3)) return fail(c, SW_EINVAL, "%s: the offsets must be 8-byte aligned, the indices 4-byte aligned", what);
-    HIPCHK(c, hipSetDevice(c->device));
+    // (empty rows are skipped: the alignment of a data buffer of capacity 0 and of the indices of no event is asked for all the same)
+    if (cap == 0 && ((uintptr_t)d_data & 15)) return misaligned(c, what, 16);
+    if (K == 0 && ((uintptr_t)d_event & 3)) return misaligned(c, what, 4);
     const size_t k = (size_t)K;
-    bool on = K == 0 || on_ctx_device(c, d_event, k * 4);
-    if (!query) on = on && on_ctx_device(c, d_data_off, (k + 1) * 8) && (K == 0 || on_ctx_device(c, d_data_none, k)) && (cap == 0 || on_ctx_device(c, d_data, (size_t)cap));
-    if (!on) return fail(c, SW_EINVAL, "%s: every array must lie in memory of device %d (a host pointer, or another device's)", what, c->device);
-    if (!c->ev_user) HIPCHK(c, hipEventCreateWithFlags(&c->ev_user, hipEventDisableTiming));
-    hipStream_t us = (hipStream_t)user_stream;
-    HIPCHK(c, hipEventRecord(c->ev_user, us));            // the producer of d_event; earlier readers of the outputs
-    HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_user, 0));
+    CHK(device_args(c, what, {{d_data, (size_t)cap, 16}, {d_data_off, (k + 1) * 8, 8}, {d_event, k * 4, 4}, {d_data_none, k, 1}}));
+    UserStream bracket;   // the producer of d_event; earlier readers of the outputs
+    CHK(bracket.join(c, (hipStream_t)user_stream));
     DataPlan p{};
     dat::SegIn in{};
     CHK(data_gather_plan(c, K, d_event, cap, n_bytes, &p, &in, what));
     if (!query) CHK(data_gather_copy(c, K, p, in, *n_bytes, d_data, d_data_off, d_data_none));
-    HIPCHK(c, hipEventRecord(c->ev_user, c->stream));     // whatever the caller enqueues next reads complete arrays
-    HIPCHK(c, hipStreamWaitEvent(us, c->ev_user, 0));
-    return SW_OK;
+    return bracket.leave();   // whatever the caller enqueues next reads complete arrays
 }
 
 int sw_gather_event_data(sw_ctx* c, int64_t K, const int32_t* event, int64_t cap, uint8_t* data, int64_t* data_off, uint8_t* data_none, int64_t* n_bytes) {
@@ -6209,22 +6168,20 @@ int sw_gather_event_data(sw_ctx* c, int64_t K, const int32_t* event, int64_t cap
     CHK(data_gather_args(c, K, event, cap, data, data_off, data_none, n_bytes, &query, what));
     HIPCHK(c, hipSetDevice(c->device));
     const size_t k = (size_t)K;
-    CHK(dgrow(c, c->d_dt_in, k * 4 + 256, 0));
-    if (K) HIPCHK(c, hipMemcpyAsync(c->d_dt_in.p, event, k * 4, hipMemcpyHostToDevice, c->stream));
+    Stage si;
+    si.in(event, k * 4);
+    unsigned char* E = nullptr;
+    CHK(stage_up(c, c->d_dt_in, si, &E));
     DataPlan p{};
     dat::SegIn in{};
-    CHK(data_gather_plan(c, K, (const int32_t*)c->d_dt_in.p, cap, n_bytes, &p, &in, what));
+    CHK(data_gather_plan(c, K, (const int32_t*)E, cap, n_bytes, &p, &in, what));
     if (query) return SW_OK;
-    Carve cv;   // the outputs, sized from the total (not from the caller's capacity)
-    const size_t o_off = cv.take((k + 1) * 8), o_n = cv.take(k), o_d = cv.take((size_t)*n_bytes + 16);
-    CHK(dgrow(c, c->d_dt_out, cv.off + 256, 0));
-    unsigned char* B = c->d_dt_out.p;
+    Stage st;   // the outputs, sized from the total (not from the caller's capacity)
+    const size_t o_off = st.out(data_off, (k + 1) * 8), o_n = st.out(data_none, k), o_d = st.out(data, (size_t)*n_bytes + 16, (size_t)*n_bytes);
+    unsigned char* B = nullptr;
+    CHK(stage_up(c, c->d_dt_out, st, &B));
     CHK(data_gather_copy(c, K, p, in, *n_bytes, B + o_d, (int64_t*)(B + o_off), B + o_n));
-    HIPCHK(c, hipMemcpyAsync(data_off, B + o_off, (k + 1) * 8, hipMemcpyDeviceToHost, c->stream));
-    if (K) HIPCHK(c, hipMemcpyAsync(data_none, B + o_n, k, hipMemcpyDeviceToHost, c->stream));
-    if (*n_bytes) HIPCHK(c, hipMemcpyAsync(data, B + o_d, (size_t)*n_bytes, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return SW_OK;
+    return stage_down(c, st, B);
 }
 
 int sw_ingest_payload_data_device(sw_ctx* c, int64_t K, const uint8_t* d_id32, const uint8_t* d_sp_id32, const uint8_t* d_op_id32, const uint8_t* d_arity,
@@ -6236,16 +6193,9 @@ int sw_ingest_payload_data_device(sw_ctx* c, int64_t K, const uint8_t* d_id32, c
     CHK(payload_args(c, K, d_id32, d_sp_id32, d_op_id32, d_arity, d_creator, d_index_out, n_stored, what));
     CHK(data_payload_args(c, d_data, d_data_off, data_bytes, d_data_none, what));
     if (K == 0) return SW_OK;
-    if (((uintptr_t)d_id32 | (uintptr_t)d_sp_id32 | (uintptr_t)d_op_id32 | (uintptr_t)d_data_off) & 7)
-        return fail(c, SW_EINVAL, "%s: the id arrays and the data offsets must be 8-byte aligned", what);
-    HIPCHK(c, hipSetDevice(c->device));
     const size_t k = (size_t)K;
-    if (!on_ctx_device(c, d_id32, k * 32) || !on_ctx_device(c, d_sp_id32, k * 32) || !on_ctx_device(c, d_op_id32, k * 32) ||
-        !on_ctx_device(c, d_arity, k) || !on_ctx_device(c, d_creator, k * 4) || !on_ctx_device(c, d_index_out, k * 4) ||
-        (d_ok && !on_ctx_device(c, d_ok, k)) || (d_t && !on_ctx_device(c, d_t, k * 8)) || (d_sig64 && !on_ctx_device(c, d_sig64, k * 64)) ||
-        (d_data_off && !on_ctx_device(c, d_data_off, (k + 1) * 8)) || (d_data && data_bytes > 0 && !on_ctx_device(c, d_data, (size_t)data_bytes)) ||
-        (d_data_none && !on_ctx_device(c, d_data_none, k)))
-        return fail(c, SW_EINVAL, "%s: every array must lie in memory of device %d (a host pointer, or another device's)", what, c->device);
+    CHK(device_args(c, what, {{d_id32, k * 32, 8}, {d_sp_id32, k * 32, 8}, {d_op_id32, k * 32, 8}, {d_data_off, (k + 1) * 8, 8}, {d_arity, k, 1}, {d_creator, k * 4, 1},
+                              {d_index_out, k * 4, 1}, {d_ok, k, 1}, {d_t, k * 8, 1}, {d_sig64, k * 64, 1}, {d_data, (size_t)data_bytes, 1}, {d_data_none, k, 1}}));
     return ingest_data_core(c, K, d_id32, d_sp_id32, d_op_id32, d_arity, d_creator, d_ok, d_t, d_sig64, d_data, d_data_off, data_bytes, d_data_none,
                             (hipStream_t)user_stream, d_index_out, n_stored);
 }
@@ -6259,27 +6209,18 @@ int sw_ingest_payload_data(sw_ctx* c, int64_t K, const uint8_t* id32, const uint
     CHK(data_payload_args(c, data, data_off, data_bytes, data_none, what));
     if (K == 0) return SW_OK;
     HIPCHK(c, hipSetDevice(c->device));
-    const size_t k = (size_t)K, db = (size_t)data_bytes;
-    Carve cv;
-    const size_t o_id = cv.take(k * 32), o_sp = cv.take(k * 32), o_op = cv.take(k * 32), o_ar = cv.take(k), o_cr = cv.take(k * 4);
-    const size_t o_ok = cv.take(ok ? k : 0), o_t = cv.take(t ? k * 8 : 0), o_sig = cv.take(sig64 ? k * 64 : 0), o_out = cv.take(k * 4);
-    const size_t o_doff = cv.take(data_off ? (k + 1) * 8 : 0), o_d = cv.take(db), o_dn = cv.take(data_none ? k : 0);
-    CHK(dgrow(c, c->d_dt_in, cv.off + 256, 0));
-    unsigned char* B = c->d_dt_in.p;
-    const struct { size_t o; const void* src; size_t bytes; } up[] = {
-        {o_id, id32, k * 32}, {o_sp, sp_id32, k * 32}, {o_op, op_id32, k * 32}, {o_ar, arity, k}, {o_cr, creator, k * 4}, {o_ok, ok, ok ? k : 0},
-        {o_t, t, t ? k * 8 : 0}, {o_sig, sig64, sig64 ? k * 64 : 0}, {o_doff, data_off, data_off ? (k + 1) * 8 : 0}, {o_d, data, db},
-        {o_dn, data_none, data_none ? k : 0}};
-    for (const auto& u : up)
-        if (u.bytes) HIPCHK(c, hipMemcpyAsync(B + u.o, u.src, u.bytes, hipMemcpyHostToDevice, c->stream));
-    const int rc = ingest_data_core(c, K, B + o_id, B + o_sp, B + o_op, B + o_ar, (const int32_t*)(B + o_cr), ok ? B + o_ok : nullptr,
-                                    t ? (const double*)(B + o_t) : nullptr, sig64 ? B + o_sig : nullptr, data_off ? B + o_d : nullptr,
-                                    data_off ? (const int64_t*)(B + o_doff) : nullptr, data_bytes, data_none ? B + o_dn : nullptr, c->stream,
-                                    (int32_t*)(B + o_out), n_stored);
-    if (rc != SW_OK) return rc;
-    HIPCHK(c, hipMemcpyAsync(index_out, B + o_out, k * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return SW_OK;
+    const size_t k = (size_t)K;
+    Stage st;
+    const size_t o_id = st.in(id32, k * 32), o_sp = st.in(sp_id32, k * 32), o_op = st.in(op_id32, k * 32), o_ar = st.in(arity, k), o_cr = st.in(creator, k * 4);
+    const size_t o_ok = st.in(ok, k), o_t = st.in(t, k * 8), o_sig = st.in(sig64, k * 64), o_out = st.out(index_out, k * 4);
+    const size_t o_doff = st.in(data_off, (k + 1) * 8), o_d = st.in(data, (size_t)data_bytes), o_dn = st.in(data_none, k);
+    unsigned char* B = nullptr;
+    CHK(stage_up(c, c->d_dt_in, st, &B));
+    CHK(ingest_data_core(c, K, B + o_id, B + o_sp, B + o_op, B + o_ar, (const int32_t*)(B + o_cr), ok ? B + o_ok : nullptr,
+                         t ? (const double*)(B + o_t) : nullptr, sig64 ? B + o_sig : nullptr, data_off ? B + o_d : nullptr,
+                         data_off ? (const int64_t*)(B + o_doff) : nullptr, data_bytes, data_none ? B + o_dn : nullptr, c->stream,
+                         (int32_t*)(B + o_out), n_stored));
+    return stage_down(c, st, B);
 }
 
 }  // extern "C"
@@ -6319,6 +6260,8 @@ int pull_begin(sw_ctx* dst, int64_t dst_head, sw_ctx* src, bool validate, bool d
     hipLaunchKernelGGL(k_known_heights, dim3(1), dim3(np), 0, dst->stream, (const int*)dst->d_L.p, (const int*)dst->d_ht.p, (int)dst_head, np, dst->d_q.p);
     dst->ctr.kernel_launches++;
     HIPCHK(dst, hipGetLastError());
+    // (not a UserStream: no caller's stream here.  The PEER's stream is put behind ours, one way, and the answer comes back
+    // through ingest_arrays, which puts ours behind the peer's and drains it)
     HIPCHK(dst, hipEventRecord(dst->ev_user, dst->stream));
     HIPCHK(dst, hipStreamWaitEvent(src->stream, dst->ev_user, 0));
     return SW_OK;
@@ -6402,6 +6345,8 @@ int ingest_arrays(sw_ctx* dst, hipStream_t from, int64_t total, const ExportArra
         const size_t o_enc = cv.take(k), o_ok = cv.take(k), o_cnt = cv.take(sizeof(int32_t));
         CHK(dgrow(dst, dst->d_pk_out, cv.off + 256, 0));
         unsigned char* B = dst->d_pk_out.p;
+        // (not a UserStream: `from` is the peer's stream or our own, and nothing is handed back to it: our stream is drained
+        // before the call returns, which is what frees the peer's scratch)
         HIPCHK(dst, hipEventRecord(dst->ev_user, from));
         HIPCHK(dst, hipStreamWaitEvent(dst->stream, dst->ev_user, 0));
         HIPCHK(dst, hipMemsetAsync(B + o_cnt, 0, sizeof(int32_t), dst->stream));
@@ -6580,28 +6525,20 @@ int sw_export_walk_device(sw_ctx* c, int64_t head, const int32_t* d_known, const
     CHK(walk_pre(c, head, true, what));
     if (cap_events < 0 || (cap_events > 0 && (!d_id32 || !d_sp_id32 || !d_op_id32 || !d_arity || !d_creator)))
         return fail(c, SW_EINVAL, "%s: NULL output arrays (capacity %lld)", what, (long long)cap_events);
-    if (((uintptr_t)d_id32 | (uintptr_t)d_sp_id32 | (uintptr_t)d_op_id32 | (uintptr_t)d_sig64) & 15)
-        return fail(c, SW_EINVAL, "%s: the id arrays and the signatures must be 16-byte aligned", what);
-    HIPCHK(c, hipSetDevice(c->device));
-    const size_t k = (size_t)cap_events;
-    bool on = (!d_known || on_ctx_device(c, d_known, (size_t)c->n * sizeof(int32_t))) && (!d_cap || on_ctx_device(c, d_cap, (size_t)c->n * sizeof(int32_t)));
-    if (cap_events > 0)
-        on = on && on_ctx_device(c, d_id32, k * 32) && on_ctx_device(c, d_sp_id32, k * 32) && on_ctx_device(c, d_op_id32, k * 32) &&
-             on_ctx_device(c, d_arity, k) && on_ctx_device(c, d_creator, k * 4) && (!d_t || on_ctx_device(c, d_t, k * 8)) &&
-             (!d_sig64 || on_ctx_device(c, d_sig64, k * 64)) && (!d_event || on_ctx_device(c, d_event, k * 4));
-    if (!on) return fail(c, SW_EINVAL, "%s: every array must lie in memory of device %d (a host pointer, or another device's)", what, c->device);
-    if (!c->ev_user) HIPCHK(c, hipEventCreateWithFlags(&c->ev_user, hipEventDisableTiming));
-    hipStream_t us = (hipStream_t)user_stream;
-    HIPCHK(c, hipEventRecord(c->ev_user, us));            // the producers of d_known and d_cap; earlier readers of the output arrays
-    HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_user, 0));
+    // (with capacity 0 the rows are empty and skipped: the alignment of whatever was passed is asked for all the same)
+    if (cap_events == 0 && (((uintptr_t)d_id32 | (uintptr_t)d_sp_id32 | (uintptr_t)d_op_id32 | (uintptr_t)d_sig64) & 15)) return misaligned(c, what, 16);
+    const size_t k = (size_t)cap_events, nb = (size_t)c->n * sizeof(int32_t);
+    CHK(device_args(c, what, {{d_id32, k * 32, 16}, {d_sp_id32, k * 32, 16}, {d_op_id32, k * 32, 16}, {d_sig64, k * 64, 16}, {d_known, nb, 1}, {d_cap, nb, 1},
+                              {d_arity, k, 1}, {d_creator, k * 4, 1}, {d_t, k * 8, 1}, {d_event, k * 4, 1}}));
+    UserStream bracket;   // the producers of d_known and d_cap; earlier readers of the output arrays
+    CHK(bracket.join(c, (hipStream_t)user_stream));
     int64_t total = 0;
     CHK(walk_run(c, head, d_known, d_cap, hipMemcpyDeviceToDevice, cap_events > 0, &total));
     *n_out = total;
     if (total > cap_events) return fail(c, SW_ERANGE, "%s: %lld events to export, capacity %lld (nothing written)", what, (long long)total, (long long)cap_events);
     const auto t0 = std::chrono::steady_clock::now();
     CHK(walk_gather(c, total, ExportArrays{d_id32, d_sp_id32, d_op_id32, d_arity, d_creator, d_t, d_sig64, d_event}));
-    HIPCHK(c, hipEventRecord(c->ev_user, c->stream));     // whatever the caller enqueues next reads complete arrays
-    HIPCHK(c, hipStreamWaitEvent(us, c->ev_user, 0));
+    CHK(bracket.leave());   // whatever the caller enqueues next reads complete arrays
     if (c->profiling) { HIPCHK(c, hipStreamSynchronize(c->stream)); c->wk_ms[2] = ms_since(t0); }
     c->wk_calls++;
     c->wk_events += total;
@@ -6624,18 +6561,10 @@ int sw_export_walk(sw_ctx* c, int64_t head, const int32_t* known, const int32_t*
     if (total > cap_events) return fail(c, SW_ERANGE, "%s: %lld events to export, capacity %lld (nothing written)", what, (long long)total, (long long)cap_events);
     const auto t0 = std::chrono::steady_clock::now();
     ExportArrays d{};
-    CHK(export_scratch(c, total, t != nullptr, sig64 != nullptr, event != nullptr, &d));
+    Stage st;
+    CHK(export_scratch(c, total, t != nullptr, sig64 != nullptr, event != nullptr, &d, &st, ExportArrays{id32, sp_id32, op_id32, arity, creator, t, sig64, event}));
     CHK(walk_gather(c, total, d));
-    const size_t k = (size_t)total;
-    HIPCHK(c, hipMemcpyAsync(id32, d.id, k * 32, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(sp_id32, d.sp_id, k * 32, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(op_id32, d.op_id, k * 32, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(arity, d.arity, k, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(creator, d.creator, k * 4, hipMemcpyDeviceToHost, c->stream));
-    if (t) HIPCHK(c, hipMemcpyAsync(t, d.t, k * 8, hipMemcpyDeviceToHost, c->stream));
-    if (sig64) HIPCHK(c, hipMemcpyAsync(sig64, d.sig, k * 64, hipMemcpyDeviceToHost, c->stream));
-    if (event) HIPCHK(c, hipMemcpyAsync(event, d.event, k * 4, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    CHK(stage_down(c, st, c->d_xp_out.p));
     if (c->profiling) c->wk_ms[2] = ms_since(t0);
     c->wk_calls++;
     c->wk_events += total;
@@ -7017,27 +6946,20 @@ int sw_pack_message_device(sw_ctx* c, int64_t K, const uint8_t* d_head32, const 
     if (!d_msg_len) return fail(c, SW_EINVAL, "%s: d_msg_len is NULL", what);
     const int64_t bound = wire_bound(c, K, data_bytes);
     if (msg_cap < bound) return fail(c, SW_ERANGE, "%s: capacity %lld below sw_pack_message_bound's %lld (nothing written)", what, (long long)msg_cap, (long long)bound);
-    if (((uintptr_t)d_msg | (uintptr_t)d_sig64 | (uintptr_t)d_id32 | (uintptr_t)d_sp_id32 | (uintptr_t)d_op_id32) & 15)
-        return fail(c, SW_EINVAL, "%s: the message, the signatures and the id arrays must be 16-byte aligned", what);
-    if (((uintptr_t)d_msg_len | (uintptr_t)d_data_off | (uintptr_t)d_t) & 7) return fail(c, SW_EINVAL, "%s: the length, the offsets and the timestamps must be 8-byte aligned", what);
-    if ((uintptr_t)d_creator & 3) return fail(c, SW_EINVAL, "%s: the creators must be 4-byte aligned", what);
-    HIPCHK(c, hipSetDevice(c->device));
     const size_t k = (size_t)K;
-    bool on = on_ctx_device(c, d_head32, 32) && on_ctx_device(c, d_msg, (size_t)msg_cap) && on_ctx_device(c, d_msg_len, 8);
-    if (K > 0)
-        on = on && on_ctx_device(c, d_id32, k * 32) && on_ctx_device(c, d_sp_id32, k * 32) && on_ctx_device(c, d_op_id32, k * 32) && on_ctx_device(c, d_arity, k) &&
-             on_ctx_device(c, d_creator, k * 4) && on_ctx_device(c, d_t, k * 8) && on_ctx_device(c, d_sig64, k * 64) &&
-             (!d_data_off || on_ctx_device(c, d_data_off, (k + 1) * 8)) && (!d_data || data_bytes == 0 || on_ctx_device(c, d_data, (size_t)data_bytes)) &&
-             (!d_data_none || on_ctx_device(c, d_data_none, k));
-    if (!on) return fail(c, SW_EINVAL, "%s: every array must lie in memory of device %d (a host pointer, or another device's)", what, c->device);
-    if (!c->ev_user) HIPCHK(c, hipEventCreateWithFlags(&c->ev_user, hipEventDisableTiming));
-    hipStream_t us = (hipStream_t)user_stream;
-    HIPCHK(c, hipEventRecord(c->ev_user, us));
-    HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_user, 0));
+    if (K == 0) {   // (an empty message: the event arrays are empty rows; the alignment of whatever was passed is asked for all the same)
+        if (((uintptr_t)d_sig64 | (uintptr_t)d_id32 | (uintptr_t)d_sp_id32 | (uintptr_t)d_op_id32) & 15) return misaligned(c, what, 16);
+        if (((uintptr_t)d_data_off | (uintptr_t)d_t) & 7) return misaligned(c, what, 8);
+        if ((uintptr_t)d_creator & 3) return misaligned(c, what, 4);
+    }
+    // (the message buffer holds the bound at least, which is never 0)
+    CHK(device_args(c, what, {{d_msg, (size_t)msg_cap, 16}, {d_sig64, k * 64, 16}, {d_id32, k * 32, 16}, {d_sp_id32, k * 32, 16}, {d_op_id32, k * 32, 16},
+                              {d_msg_len, 8, 8}, {d_data_off, K ? (k + 1) * 8 : 0, 8}, {d_t, k * 8, 8}, {d_creator, k * 4, 4}, {d_head32, 32, 1}, {d_arity, k, 1},
+                              {d_data, K ? (size_t)data_bytes : 0, 1}, {d_data_none, k, 1}}));
+    UserStream bracket;
+    CHK(bracket.join(c, (hipStream_t)user_stream));
     CHK(wire_pack_launch(c, K, a, d_msg, bound, d_msg_len, nullptr));
-    HIPCHK(c, hipEventRecord(c->ev_user, c->stream));
-    HIPCHK(c, hipStreamWaitEvent(us, c->ev_user, 0));
-    return SW_OK;
+    return bracket.leave();
 }
 
 int sw_pack_message(sw_ctx* c, int64_t K, const uint8_t* head32, const uint8_t* id32, const uint8_t* sp_id32, const uint8_t* op_id32, const uint8_t* arity,
@@ -7051,18 +6973,13 @@ int sw_pack_message(sw_ctx* c, int64_t K, const uint8_t* head32, const uint8_t* 
     if (msg_cap < 0) return fail(c, SW_EINVAL, "%s: negative capacity", what);
     HIPCHK(c, hipSetDevice(c->device));
     const int64_t bound = wire_bound(c, K, data_bytes);
-    const size_t k = (size_t)K, db = (size_t)data_bytes;
-    Carve cv;
-    const size_t o_head = cv.take(32), o_id = cv.take(k * 32), o_sp = cv.take(k * 32), o_op = cv.take(k * 32), o_ar = cv.take(k), o_cr = cv.take(k * 4), o_t = cv.take(k * 8);
-    const size_t o_sig = cv.take(k * 64), o_doff = cv.take(data_off ? (k + 1) * 8 : 0), o_d = cv.take(db), o_dn = cv.take(data_none ? k : 0);
-    const size_t o_len = cv.take(8), o_m = cv.take((size_t)bound);
-    CHK(dgrow(c, c->d_wr_in, cv.off + 256, 0));
-    unsigned char* B = c->d_wr_in.p;
-    const struct { size_t o; const void* src; size_t bytes; } up[] = {
-        {o_head, head32, 32}, {o_id, id32, k * 32}, {o_sp, sp_id32, k * 32}, {o_op, op_id32, k * 32}, {o_ar, arity, k}, {o_cr, creator, k * 4}, {o_t, t, k * 8},
-        {o_sig, sig64, k * 64}, {o_doff, data_off, data_off ? (k + 1) * 8 : 0}, {o_d, data, db}, {o_dn, data_none, data_none ? k : 0}};
-    for (const auto& u : up)
-        if (u.bytes) HIPCHK(c, hipMemcpyAsync(B + u.o, u.src, u.bytes, hipMemcpyHostToDevice, c->stream));
+    const size_t k = (size_t)K;
+    Stage st;   // (the message comes back by the length the writer reports)
+    const size_t o_head = st.in(head32, 32), o_id = st.in(id32, k * 32), o_sp = st.in(sp_id32, k * 32), o_op = st.in(op_id32, k * 32), o_ar = st.in(arity, k);
+    const size_t o_cr = st.in(creator, k * 4), o_t = st.in(t, k * 8), o_sig = st.in(sig64, k * 64), o_doff = st.in(data_off, (k + 1) * 8);
+    const size_t o_d = st.in(data, (size_t)data_bytes), o_dn = st.in(data_none, k), o_len = st.scratch(8), o_m = st.out(msg, (size_t)bound, 0);
+    unsigned char* B = nullptr;
+    CHK(stage_up(c, c->d_wr_in, st, &B));
     unsigned long long* d_bad = nullptr;
     CHK(wire_pack_launch(c, K, WireArrays{B + o_head, B + o_id, B + o_sp, B + o_op, B + o_ar, (const int32_t*)(B + o_cr), (const double*)(B + o_t), B + o_sig,
                                           data_off ? B + o_d : nullptr, data_off ? (const int64_t*)(B + o_doff) : nullptr, data_bytes,
@@ -7078,8 +6995,8 @@ int sw_pack_message(sw_ctx* c, int64_t K, const uint8_t* head32, const uint8_t* 
     if (len > bound) return fail(c, SW_EIO, "%s: length %lld beyond the bound %lld (internal error)", what, len, (long long)bound);
     *msg_bytes = len;
     if (len > msg_cap) return fail(c, SW_ERANGE, "%s: the message has %lld bytes, capacity %lld (nothing written)", what, len, (long long)msg_cap);
-    HIPCHK(c, hipMemcpyAsync(msg, B + o_m, (size_t)len, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
+    st.out_bytes(msg, (size_t)len);
+    CHK(stage_down(c, st, B));
     c->wr_pack_bytes += len;
     return SW_OK;
 }
@@ -7093,25 +7010,18 @@ int sw_unpack_message_device(sw_ctx* c, const uint8_t* d_msg, int64_t msg_bytes,
     CHK(wire_unpack_pre(c, d_msg, msg_bytes, cap_events, cap_data, o, n_events, n_data_bytes, what));
     *n_events = -1;
     *n_data_bytes = 0;
-    if ((uintptr_t)d_data & 15) return fail(c, SW_EINVAL, "%s: the data buffer must be 16-byte aligned", what);
-    if (((uintptr_t)d_data_off | (uintptr_t)d_t) & 7) return fail(c, SW_EINVAL, "%s: the offsets and the timestamps must be 8-byte aligned", what);
-    if ((uintptr_t)d_creator & 3) return fail(c, SW_EINVAL, "%s: the creators must be 4-byte aligned", what);
-    HIPCHK(c, hipSetDevice(c->device));
+    // (empty rows are skipped: the alignment of a data buffer of capacity 0, and of the arrays of no event, is asked for all the same)
+    if (cap_data == 0 && ((uintptr_t)d_data & 15)) return misaligned(c, what, 16);
+    if (cap_events == 0 && ((uintptr_t)d_t & 7)) return misaligned(c, what, 8);
+    if (cap_events == 0 && ((uintptr_t)d_creator & 3)) return misaligned(c, what, 4);
     const size_t k = (size_t)cap_events;
-    bool on = (msg_bytes == 0 || on_ctx_device(c, d_msg, (size_t)msg_bytes)) && on_ctx_device(c, d_head32, 32) && on_ctx_device(c, d_data_off, (k + 1) * 8) &&
-              (cap_data == 0 || on_ctx_device(c, d_data, (size_t)cap_data));
-    if (cap_events > 0)
-        on = on && on_ctx_device(c, d_id32, k * 32) && on_ctx_device(c, d_sp_id32, k * 32) && on_ctx_device(c, d_op_id32, k * 32) && on_ctx_device(c, d_arity, k) &&
-             on_ctx_device(c, d_creator, k * 4) && on_ctx_device(c, d_t, k * 8) && on_ctx_device(c, d_sig64, k * 64) && on_ctx_device(c, d_data_none, k);
-    if (!on) return fail(c, SW_EINVAL, "%s: every array must lie in memory of device %d (a host pointer, or another device's)", what, c->device);
-    if (!c->ev_user) HIPCHK(c, hipEventCreateWithFlags(&c->ev_user, hipEventDisableTiming));
-    hipStream_t us = (hipStream_t)user_stream;
-    HIPCHK(c, hipEventRecord(c->ev_user, us));
-    HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_user, 0));
-    const int rc = wire_unpack_run(c, d_msg, msg_bytes, cap_events, cap_data, o, n_events, n_data_bytes, what);
-    HIPCHK(c, hipEventRecord(c->ev_user, c->stream));
-    HIPCHK(c, hipStreamWaitEvent(us, c->ev_user, 0));
-    return rc;
+    CHK(device_args(c, what, {{d_data, (size_t)cap_data, 16}, {d_data_off, (k + 1) * 8, 8}, {d_t, k * 8, 8}, {d_creator, k * 4, 4}, {d_msg, (size_t)msg_bytes, 1},
+                              {d_head32, 32, 1}, {d_id32, k * 32, 1}, {d_sp_id32, k * 32, 1}, {d_op_id32, k * 32, 1}, {d_arity, k, 1}, {d_sig64, k * 64, 1},
+                              {d_data_none, k, 1}}));
+    UserStream bracket;
+    CHK(bracket.join(c, (hipStream_t)user_stream));
+    CHK(wire_unpack_run(c, d_msg, msg_bytes, cap_events, cap_data, o, n_events, n_data_bytes, what));
+    return bracket.leave();
 }
 
 int sw_unpack_message(sw_ctx* c, const uint8_t* msg, int64_t msg_bytes, int64_t cap_events, int64_t cap_data, uint8_t* head32, uint8_t* id32, uint8_t* sp_id32,
@@ -7127,12 +7037,12 @@ int sw_unpack_message(sw_ctx* c, const uint8_t* msg, int64_t msg_bytes, int64_t 
     // no more events or data bytes than the message can hold need room on the device
     const int64_t ke = std::min<int64_t>(cap_events, msg_bytes / wir::REC_MIN), kd = std::min<int64_t>(cap_data, msg_bytes);
     const size_t k = (size_t)ke;
-    Carve cv;
-    const size_t o_msg = cv.take((size_t)msg_bytes), o_head = cv.take(32), o_id = cv.take(k * 32), o_sp = cv.take(k * 32), o_op = cv.take(k * 32), o_ar = cv.take(k);
-    const size_t o_cr = cv.take(k * 4), o_t = cv.take(k * 8), o_sig = cv.take(k * 64), o_doff = cv.take((k + 1) * 8), o_dn = cv.take(k), o_d = cv.take((size_t)kd + 16);
-    CHK(dgrow(c, c->d_wr_in, cv.off + 256, 0));
-    unsigned char* B = c->d_wr_in.p;
-    if (msg_bytes) HIPCHK(c, hipMemcpyAsync(B + o_msg, msg, (size_t)msg_bytes, hipMemcpyHostToDevice, c->stream));
+    Stage st;   // (every array comes back by the counts the reader reports)
+    const size_t o_msg = st.in(msg, (size_t)msg_bytes), o_head = st.out(head32, 32, 0), o_id = st.out(id32, k * 32, 0), o_sp = st.out(sp_id32, k * 32, 0);
+    const size_t o_op = st.out(op_id32, k * 32, 0), o_ar = st.out(arity, k, 0), o_cr = st.out(creator, k * 4, 0), o_t = st.out(t, k * 8, 0), o_sig = st.out(sig64, k * 64, 0);
+    const size_t o_doff = st.out(data_off, (k + 1) * 8, 0), o_dn = st.out(data_none, k, 0), o_d = st.out(data, (size_t)kd + 16, 0);
+    unsigned char* B = nullptr;
+    CHK(stage_up(c, c->d_wr_in, st, &B));
     const WireOut o{B + o_head, B + o_id, B + o_sp, B + o_op, B + o_ar, (int32_t*)(B + o_cr), (double*)(B + o_t), B + o_sig, B + o_d, (int64_t*)(B + o_doff), B + o_dn};
     int64_t K = -1, nd = 0;
     const int rc = wire_unpack_run(c, B + o_msg, msg_bytes, ke, kd, o, &K, &nd, what);
@@ -7140,13 +7050,10 @@ int sw_unpack_message(sw_ctx* c, const uint8_t* msg, int64_t msg_bytes, int64_t 
     *n_data_bytes = nd;
     if (rc != SW_OK || K < 0) return rc;
     const size_t kk = (size_t)K;
-    const struct { void* dst; size_t o; size_t bytes; } down[] = {
-        {head32, o_head, 32}, {id32, o_id, kk * 32}, {sp_id32, o_sp, kk * 32}, {op_id32, o_op, kk * 32}, {arity, o_ar, kk}, {creator, o_cr, kk * 4}, {t, o_t, kk * 8},
-        {sig64, o_sig, kk * 64}, {data_off, o_doff, (kk + 1) * 8}, {data_none, o_dn, kk}, {data, o_d, (size_t)nd}};
-    for (const auto& u : down)
-        if (u.bytes) HIPCHK(c, hipMemcpyAsync(u.dst, B + u.o, u.bytes, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return SW_OK;
+    st.out_bytes(head32, 32); st.out_bytes(id32, kk * 32); st.out_bytes(sp_id32, kk * 32); st.out_bytes(op_id32, kk * 32); st.out_bytes(arity, kk);
+    st.out_bytes(creator, kk * 4); st.out_bytes(t, kk * 8); st.out_bytes(sig64, kk * 64); st.out_bytes(data_off, (kk + 1) * 8); st.out_bytes(data_none, kk);
+    st.out_bytes(data, (size_t)nd);
+    return stage_down(c, st, B);
 }
 
 int sw_export_message_device(sw_ctx* c, int64_t head_event, const int32_t* d_known, const int32_t* d_cap, int with_data, uint8_t* d_msg, int64_t msg_cap,
@@ -7156,21 +7063,14 @@ int sw_export_message_device(sw_ctx* c, int64_t head_event, const int32_t* d_kno
     if (!msg_bytes || !n_events) return fail(c, SW_EINVAL, "%s: msg_bytes or n_events is NULL", what);
     *msg_bytes = *n_events = 0;
     if (msg_cap < 0 || (msg_cap > 0 && !d_msg)) return fail(c, SW_EINVAL, "%s: NULL message buffer (capacity %lld)", what, (long long)msg_cap);
-    HIPCHK(c, hipSetDevice(c->device));
-    if ((d_known && !on_ctx_device(c, d_known, (size_t)c->n * 4)) || (d_cap && !on_ctx_device(c, d_cap, (size_t)c->n * 4)) ||
-        (msg_cap > 0 && !on_ctx_device(c, d_msg, (size_t)msg_cap)))
-        return fail(c, SW_EINVAL, "%s: every array must lie in memory of device %d (a host pointer, or another device's)", what, c->device);
-    if (!c->ev_user) HIPCHK(c, hipEventCreateWithFlags(&c->ev_user, hipEventDisableTiming));
-    hipStream_t us = (hipStream_t)user_stream;
-    HIPCHK(c, hipEventRecord(c->ev_user, us));
-    HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_user, 0));
+    CHK(device_args(c, what, {{d_known, (size_t)c->n * 4, 1}, {d_cap, (size_t)c->n * 4, 1}, {d_msg, (size_t)msg_cap, 1}}));
+    UserStream bracket;
+    CHK(bracket.join(c, (hipStream_t)user_stream));
     uint8_t* m = nullptr;
     CHK(wire_export_run(c, head_event, d_known, d_cap, hipMemcpyDeviceToDevice, with_data != 0, what, &m, msg_bytes, n_events));
     if (*msg_bytes > msg_cap) return fail(c, SW_ERANGE, "%s: the message has %lld bytes, capacity %lld (nothing written)", what, (long long)*msg_bytes, (long long)msg_cap);
     HIPCHK(c, hipMemcpyAsync(d_msg, m, (size_t)*msg_bytes, hipMemcpyDeviceToDevice, c->stream));
-    HIPCHK(c, hipEventRecord(c->ev_user, c->stream));
-    HIPCHK(c, hipStreamWaitEvent(us, c->ev_user, 0));
-    return SW_OK;
+    return bracket.leave();
 }
 
 int sw_export_message(sw_ctx* c, int64_t head_event, const int32_t* known, const int32_t* cap, int with_data, uint8_t* msg, int64_t msg_cap, int64_t* msg_bytes,
@@ -7198,23 +7098,16 @@ int sw_ingest_message_device(sw_ctx* c, const uint8_t* d_msg, int64_t msg_bytes,
     if (n_valid) *n_valid = 0;
     if (n_stored) *n_stored = 0;
     if (msg_bytes < 0 || (msg_bytes > 0 && !d_msg)) return fail(c, SW_EINVAL, "%s: NULL message (%lld bytes)", what, (long long)msg_bytes);
-    HIPCHK(c, hipSetDevice(c->device));
     const size_t kcap = (size_t)(msg_bytes / wir::REC_MIN);
-    if ((msg_bytes > 0 && !on_ctx_device(c, d_msg, (size_t)msg_bytes)) || (d_head32_out && !on_ctx_device(c, d_head32_out, 32)) ||
-        (d_index_out && kcap && !on_ctx_device(c, d_index_out, kcap * 4)))
-        return fail(c, SW_EINVAL, "%s: every array must lie in memory of device %d (a host pointer, or another device's)", what, c->device);
-    if (!c->ev_user) HIPCHK(c, hipEventCreateWithFlags(&c->ev_user, hipEventDisableTiming));
-    hipStream_t us = (hipStream_t)user_stream;
-    HIPCHK(c, hipEventRecord(c->ev_user, us));
-    HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_user, 0));
+    CHK(device_args(c, what, {{d_msg, (size_t)msg_bytes, 1}, {d_head32_out, 32, 1}, {d_index_out, kcap * 4, 1}}));
+    UserStream bracket;
+    CHK(bracket.join(c, (hipStream_t)user_stream));
     uint8_t* d_head = nullptr;
     CHK(wire_ingest_run(c, d_msg, msg_bytes, validate != 0, with_data != 0, what, &d_head, n_events, n_valid, n_stored));
-    if (*n_events < 0) return SW_OK;
+    if (*n_events < 0) return bracket.leave();   // (a refused message: nothing is written, and the caller's stream is handed back)
     if (d_head32_out) HIPCHK(c, hipMemcpyAsync(d_head32_out, d_head, 32, hipMemcpyDeviceToDevice, c->stream));
     if (d_index_out && *n_events > 0) HIPCHK(c, hipMemcpyAsync(d_index_out, c->d_pl_in.p, (size_t)*n_events * 4, hipMemcpyDeviceToDevice, c->stream));
-    HIPCHK(c, hipEventRecord(c->ev_user, c->stream));
-    HIPCHK(c, hipStreamWaitEvent(us, c->ev_user, 0));
-    return SW_OK;
+    return bracket.leave();
 }
 
 int sw_ingest_message(sw_ctx* c, const uint8_t* msg, int64_t msg_bytes, int validate, int with_data, uint8_t* head32_out, int32_t* index_out, int64_t* n_events,
@@ -7366,17 +7259,9 @@ int sign_core(sw_ctx* c, int64_t K, const SignArrays& a, const char* what, int64
 int sign_device_args(sw_ctx* c, int64_t K, const int32_t* cr, const int32_t* sp, const int32_t* op, const double* t, const uint8_t* data,
                      const int64_t* data_off, int64_t data_bytes, const uint8_t* data_none, const uint8_t* id, const uint8_t* sp_id, const uint8_t* op_id,
                      const uint8_t* arity, const uint8_t* sig, const char* what) {
-    if (((uintptr_t)id | (uintptr_t)sp_id | (uintptr_t)op_id | (uintptr_t)sig) & 15)
-        return fail(c, SW_EINVAL, "%s: the id arrays and the signatures must be 16-byte aligned", what);
-    if (((uintptr_t)data_off | (uintptr_t)t) & 7) return fail(c, SW_EINVAL, "%s: the offsets and the timestamps must be 8-byte aligned", what);
-    if (((uintptr_t)cr | (uintptr_t)sp | (uintptr_t)op) & 3) return fail(c, SW_EINVAL, "%s: the index arrays must be 4-byte aligned", what);
-    const size_t k = (size_t)K;
-    const bool on = on_ctx_device(c, cr, k * 4) && on_ctx_device(c, sp, k * 4) && on_ctx_device(c, op, k * 4) && on_ctx_device(c, t, k * 8) &&
-                    (!data_off || on_ctx_device(c, data_off, (k + 1) * 8)) && (!data || data_bytes == 0 || on_ctx_device(c, data, (size_t)data_bytes)) &&
-                    (!data_none || on_ctx_device(c, data_none, k)) && (!id || on_ctx_device(c, id, k * 32)) && (!sp_id || on_ctx_device(c, sp_id, k * 32)) &&
-                    (!op_id || on_ctx_device(c, op_id, k * 32)) && (!arity || on_ctx_device(c, arity, k)) && (!sig || on_ctx_device(c, sig, k * 64));
-    if (!on) return fail(c, SW_EINVAL, "%s: every array must lie in memory of device %d (a host pointer, or another device's)", what, c->device);
-    return SW_OK;
+    const size_t k = (size_t)K;   // (K > 0: no row of an array that was passed is empty)
+    return device_args(c, what, {{id, k * 32, 16}, {sp_id, k * 32, 16}, {op_id, k * 32, 16}, {sig, k * 64, 16}, {data_off, (k + 1) * 8, 8}, {t, k * 8, 8},
+                                 {cr, k * 4, 4}, {sp, k * 4, 4}, {op, k * 4, 4}, {data, (size_t)data_bytes, 1}, {data_none, k, 1}, {arity, k, 1}});
 }
 
 // the signed arrays of a create call at the front of d_sg_in (the host form stages its inputs behind `end`)
@@ -7603,41 +7488,30 @@ int sw_sign_events_device(sw_ctx* c, int64_t K, const int32_t* d_creator, const 
     CHK(sign_pre(c, K, d_creator, d_self_parent, d_other_parent, d_t, d_data, d_data_off, data_bytes, d_data_none, what));
     if (K == 0) return SW_OK;
     if (!d_id32 || !d_sp_id32 || !d_op_id32 || !d_arity || !d_sig64) return fail(c, SW_EINVAL, "%s: NULL output arrays", what);
-    HIPCHK(c, hipSetDevice(c->device));
     CHK(sign_device_args(c, K, d_creator, d_self_parent, d_other_parent, d_t, d_data, d_data_off, data_bytes, d_data_none, d_id32, d_sp_id32, d_op_id32,
                          d_arity, d_sig64, what));
-    if (!c->ev_user) HIPCHK(c, hipEventCreateWithFlags(&c->ev_user, hipEventDisableTiming));
-    hipStream_t us = (hipStream_t)user_stream;
-    HIPCHK(c, hipEventRecord(c->ev_user, us));            // the producers of the arrays; earlier readers of the outputs
-    HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_user, 0));
+    UserStream bracket;   // the producers of the arrays; earlier readers of the outputs
+    CHK(bracket.join(c, (hipStream_t)user_stream));
     int64_t usable = 0;
     CHK(sign_core(c, K, SignArrays{d_creator, d_self_parent, d_other_parent, d_t, d_data, d_data_off, data_bytes, d_data_none, d_id32, d_sp_id32,
                                    d_op_id32, d_arity, d_sig64}, what, &usable));
-    HIPCHK(c, hipEventRecord(c->ev_user, c->stream));     // whatever the caller enqueues next reads complete arrays
-    HIPCHK(c, hipStreamWaitEvent(us, c->ev_user, 0));
-    return SW_OK;
+    return bracket.leave();   // whatever the caller enqueues next reads complete arrays
 }
 
 }  // extern "C"
 
 namespace {
 
-// the inputs of the host-array forms staged in d_sg_in behind `front` bytes; pointers into the staging come back
+// the inputs of the host-array forms staged in d_sg_in behind what `st` holds already (the signed arrays); pointers into the
+// staging come back
 struct SignStaged { const int32_t *cr, *sp, *op; const double* t; const uint8_t* data; const int64_t* off; const uint8_t* none; };
-int sign_stage(sw_ctx* c, int64_t K, size_t front, const int32_t* creator, const int32_t* sp, const int32_t* op, const double* t, const uint8_t* data,
+int sign_stage(sw_ctx* c, int64_t K, Stage& st, const int32_t* creator, const int32_t* sp, const int32_t* op, const double* t, const uint8_t* data,
                const int64_t* data_off, int64_t data_bytes, const uint8_t* data_none, SignStaged* s) {
-    const size_t k = (size_t)K, db = (size_t)data_bytes;
-    Carve cv;
-    cv.off = front;
-    const size_t o_cr = cv.take(k * 4), o_sp = cv.take(k * 4), o_op = cv.take(k * 4), o_t = cv.take(k * 8);
-    const size_t o_doff = cv.take(data_off ? (k + 1) * 8 : 0), o_d = cv.take(db), o_dn = cv.take(data_none ? k : 0);
-    CHK(dgrow(c, c->d_sg_in, cv.off + 256, 0));
-    unsigned char* B = c->d_sg_in.p;
-    const struct { size_t o; const void* src; size_t bytes; } up[] = {
-        {o_cr, creator, k * 4}, {o_sp, sp, k * 4}, {o_op, op, k * 4}, {o_t, t, k * 8}, {o_doff, data_off, data_off ? (k + 1) * 8 : 0}, {o_d, data, db},
-        {o_dn, data_none, data_none ? k : 0}};
-    for (const auto& u : up)
-        if (u.bytes) HIPCHK(c, hipMemcpyAsync(B + u.o, u.src, u.bytes, hipMemcpyHostToDevice, c->stream));
+    const size_t k = (size_t)K;
+    const size_t o_cr = st.in(creator, k * 4), o_sp = st.in(sp, k * 4), o_op = st.in(op, k * 4), o_t = st.in(t, k * 8);
+    const size_t o_doff = st.in(data_off, (k + 1) * 8), o_d = st.in(data, (size_t)data_bytes), o_dn = st.in(data_none, k);
+    unsigned char* B = nullptr;
+    CHK(stage_up(c, c->d_sg_in, st, &B));
     *s = SignStaged{(const int32_t*)(B + o_cr), (const int32_t*)(B + o_sp), (const int32_t*)(B + o_op), (const double*)(B + o_t),
                     data_off ? B + o_d : nullptr, data_off ? (const int64_t*)(B + o_doff) : nullptr, data_none ? B + o_dn : nullptr};
     return SW_OK;
@@ -7657,20 +7531,14 @@ int sw_sign_events(sw_ctx* c, int64_t K, const int32_t* creator, const int32_t* 
     if (!id32 || !sp_id32 || !op_id32 || !arity || !sig64) return fail(c, SW_EINVAL, "%s: NULL output arrays", what);
     HIPCHK(c, hipSetDevice(c->device));
     const size_t k = (size_t)K;
-    Carve cv;
-    const size_t o_id = cv.take(k * 32), o_spid = cv.take(k * 32), o_opid = cv.take(k * 32), o_ar = cv.take(k), o_sig = cv.take(k * 64);
+    Stage st;
+    const size_t o_id = st.out(id32, k * 32), o_spid = st.out(sp_id32, k * 32), o_opid = st.out(op_id32, k * 32), o_ar = st.out(arity, k), o_sig = st.out(sig64, k * 64);
     SignStaged s{};
-    CHK(sign_stage(c, K, cv.off, creator, self_parent, other_parent, t, data, data_off, data_bytes, data_none, &s));
+    CHK(sign_stage(c, K, st, creator, self_parent, other_parent, t, data, data_off, data_bytes, data_none, &s));
     unsigned char* B = c->d_sg_in.p;
     int64_t usable = 0;
     CHK(sign_core(c, K, SignArrays{s.cr, s.sp, s.op, s.t, s.data, s.off, data_bytes, s.none, B + o_id, B + o_spid, B + o_opid, B + o_ar, B + o_sig}, what, &usable));
-    HIPCHK(c, hipMemcpyAsync(id32, B + o_id, k * 32, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(sp_id32, B + o_spid, k * 32, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(op_id32, B + o_opid, k * 32, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(arity, B + o_ar, k, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(sig64, B + o_sig, k * 64, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    return SW_OK;
+    return stage_down(c, st, B);
 }
 
 int sw_create_events_device(sw_ctx* c, int64_t K, const int32_t* d_creator, const int32_t* d_self_parent, const int32_t* d_other_parent, const double* d_t,
@@ -7681,13 +7549,13 @@ int sw_create_events_device(sw_ctx* c, int64_t K, const int32_t* d_creator, cons
     CHK(sign_pre(c, K, d_creator, d_self_parent, d_other_parent, d_t, d_data, d_data_off, data_bytes, d_data_none, what));
     if (first_out) *first_out = c->N;
     if (K == 0) return SW_OK;
-    HIPCHK(c, hipSetDevice(c->device));
     CHK(sign_device_args(c, K, d_creator, d_self_parent, d_other_parent, d_t, d_data, d_data_off, data_bytes, d_data_none, d_id32, nullptr, nullptr, nullptr,
                          d_sig64, what));
-    if (!c->ev_user) HIPCHK(c, hipEventCreateWithFlags(&c->ev_user, hipEventDisableTiming));
-    HIPCHK(c, hipEventRecord(c->ev_user, (hipStream_t)user_stream));
-    HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_user, 0));
-    return create_core(c, K, d_creator, d_self_parent, d_other_parent, d_t, d_data, d_data_off, data_bytes, d_data_none, d_id32, d_sig64, what);
+    UserStream bracket;
+    CHK(bracket.join(c, (hipStream_t)user_stream));
+    CHK(create_core(c, K, d_creator, d_self_parent, d_other_parent, d_t, d_data, d_data_off, data_bytes, d_data_none, d_id32, d_sig64, what));
+    bracket.drained();   // (create_core synchronises the stream before a successful return: the join half is all this form needs)
+    return SW_OK;
 }
 
 int sw_create_events(sw_ctx* c, int64_t K, const int32_t* creator, const int32_t* self_parent, const int32_t* other_parent, const double* t,
@@ -7701,8 +7569,10 @@ int sw_create_events(sw_ctx* c, int64_t K, const int32_t* creator, const int32_t
     HIPCHK(c, hipSetDevice(c->device));
     const size_t k = (size_t)K;
     const CreateScratch L = create_scratch(k);
+    Stage st;
+    st.scratch(L.end);   // (the signed arrays, where create_core puts them)
     SignStaged s{};
-    CHK(sign_stage(c, K, L.end, creator, self_parent, other_parent, t, data, data_off, data_bytes, data_none, &s));
+    CHK(sign_stage(c, K, st, creator, self_parent, other_parent, t, data, data_off, data_bytes, data_none, &s));
     CHK(create_core(c, K, s.cr, s.sp, s.op, s.t, s.data, s.off, data_bytes, s.none, nullptr, nullptr, what));
     const unsigned char* B = c->d_sg_in.p;   // (create_core found the buffer large enough: it has not moved)
     if (id32) HIPCHK(c, hipMemcpyAsync(id32, B + L.id, k * 32, hipMemcpyDeviceToHost, c->stream));
@@ -7727,7 +7597,9 @@ int sw_get_sign_stats(sw_ctx* c, int64_t* calls, int64_t* events, int64_t* level
 namespace {
 
 // One event as host values -> the K = 1 arrays sw_create_events would stage -> create_core with the one-wave signer.  The
-// staged values live on this frame: the stream is drained before it is left, whatever happens.
+// staged values live on this frame: the stream is drained before it is left, whatever happens.  (sw_create_event and
+// sw_gossip_turn take no stream of the caller's: the only UserStream under them is the one inside the append, which joins the
+// context's stream with itself and drains it.)
 int create_one(sw_ctx* c, int member, int64_t sp, int64_t op, double t, const uint8_t* data, int64_t data_len, OneSign* one, uint8_t* id32_out,
                uint8_t* sig64_out, const char* what) {
     const auto narrow = [](int64_t v) { return v < 0 ? (int32_t)-1 : v > 0x7fffffff ? (int32_t)0x7fffffff : (int32_t)v; };
@@ -7741,8 +7613,10 @@ int create_one(sw_ctx* c, int member, int64_t sp, int64_t op, double t, const ui
     HIPCHK(c, hipSetDevice(c->device));
     const CreateScratch L = create_scratch(1);
     const auto run = [&]() -> int {
+        Stage plan;
+        plan.scratch(L.end);
         SignStaged st{};
-        CHK(sign_stage(c, 1, L.end, &cr, &s, &o, &t, nbytes ? data : nullptr, off, nbytes, &none, &st));
+        CHK(sign_stage(c, 1, plan, &cr, &s, &o, &t, nbytes ? data : nullptr, off, nbytes, &none, &st));
         CHK(create_core(c, 1, st.cr, st.sp, st.op, st.t, st.data, st.off, nbytes, st.none, nullptr, nullptr, what, one));
         if (one->absent) return SW_OK;
         const unsigned char* B = c->d_sg_in.p;   // (create_core found the buffer large enough: it has not moved)
