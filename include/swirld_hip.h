@@ -299,6 +299,40 @@ int sw_get_sees_mask(sw_ctx* ctx, int64_t first, int64_t K, uint64_t* out);
  * witness (rc, mc): -1 = no entry, 0/1 = vote (swirld.py:258-272).  Recomputed from the voter
  * masks with the semantics of one batch decide_fame() call; valid after sw_decide_fame. */
 int sw_get_vote(sw_ctx* ctx, int rv, int mv, int rc, int mc, int8_t* out);
+
+/*
+ * Node.votes IN BULK (swirld.py:60-61, 256-272; kernels in csrc/votes.hip.h): every entry of the voter
+ * rounds rv0 <= round(y) < rv1 as one table, computed on the device from the voter masks, the witness table, the coin bits,
+ * the stakes and the deciding call / voter of every witness.
+ *
+ * THE TABLE: one row per pair (voter witness y, candidate round rc) for which votes[y] holds at least one entry for a
+ * witness of round rc.  row_voter[row] = the dense index of y, row_cand_round[row] = rc; exists[row][j] and value[row][j],
+ * j < ceil(n_members / 64) little-endian words (the stride of sw_get_sees_mask), are member bitmasks: bit mc of exists is set
+ * iff votes[y][witnesses[rc][mc]] exists, bit mc of value is that entry's value (value is a subset of exists).  Rows are
+ * sorted by (round(y), y, rc) ascending.  Existence and value of every bit are what sw_get_vote(round(y), creator(y), rc,
+ * mc) answers on the same context; the comment above that function is the specification (tests/model_votes.py states the
+ * table in numpy).
+ * PRECONDITIONS as for sw_get_vote: SW_ENOTSUP on the exact path and after sw_commit_fame; SW_ERANGE for rv0 < 0 or rv1
+ * beyond the round table; SW_EINVAL when rv1 reaches rounds sw_decide_fame has not seen yet.  rv0 >= rv1: an empty table,
+ * SW_OK.  A windowed context is served (no can_see row is read).
+ * CAPACITY: *n_rows and *n_entries (host; the set bits of exists) are always written.  cap_rows < *n_rows returns
+ * SW_ERANGE and writes no array: cap_rows = 0 (arrays may be NULL) asks for the size.
+ * sw_export_votes_device   the four arrays in memory of the context's device (SW_EINVAL otherwise, before anything is
+ *   launched; d_exists and d_value 16-byte aligned).  STREAMS as for sw_export_payload_device: the context's stream first
+ *   waits for what `user_stream` has enqueued, `user_stream` is made to wait for the table.  The one host synchronisation
+ *   is the read-back of the two counts.
+ * sw_export_votes   the same with the arrays in HOST memory (written into context scratch by the same kernels, copied out).
+ * sw_get_votes_stats   calls, rows and entries exported since sw_create, election levels replayed for them, and — under
+ *   sw_set_profiling — the host time in ms of the most recent call's phases: phase_ms[2] = plan + existence + counts,
+ *   rows + values.  Any pointer may be NULL.
+ */
+int sw_export_votes_device(sw_ctx* ctx, int rv0, int rv1, int64_t cap_rows,
+                           int32_t* d_row_voter, int32_t* d_row_cand_round, uint64_t* d_exists, uint64_t* d_value,
+                           int64_t* n_rows, int64_t* n_entries, void* user_stream);
+int sw_export_votes(sw_ctx* ctx, int rv0, int rv1, int64_t cap_rows,
+                    int32_t* row_voter, int32_t* row_cand_round, uint64_t* exists, uint64_t* value,
+                    int64_t* n_rows, int64_t* n_entries);
+int sw_get_votes_stats(sw_ctx* ctx, int64_t* calls, int64_t* rows, int64_t* entries, int64_t* levels, double* phase_ms);
 /* Node.transactions / Node.idx: total ordered so far, and a slice of the order. */
 int sw_num_ordered(sw_ctx* ctx, int64_t* out);
 int sw_get_transactions(sw_ctx* ctx, int64_t first, int64_t K, int32_t* out);

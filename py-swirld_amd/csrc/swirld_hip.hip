@@ -36,6 +36,7 @@
 #include "wire.hip.h"
 #include "turn.hip.h"
 #include "consensus.hip.h"
+#include "votes.hip.h"
 
 namespace {
 
@@ -184,6 +185,15 @@ struct sw_ctx {
     DBuf<unsigned char> d_xp_out; // the exported arrays of the host-array form and of sw_sync_pull
     int64_t xp_calls = 0, xp_events = 0;   // sw_get_export_stats
     double xp_ms[2] = {0, 0};     // ... host time of the most recent call's phases under sw_set_profiling: ranges + count, gather
+    // Node.votes in bulk (csrc/votes.hip.h; sw_export_votes[_device])
+    struct VotesState {
+        DBuf<unsigned char> d_sched, d_plan, d_work, d_out;   // call schedule, per-call plan, scratch, the host form's table
+        int sched_calls = -1;               // number of decide_fame calls d_sched holds (-1: stale)
+        std::vector<unsigned char> sched_stage, plan_stage;   // persistent host staging: uploaded without a sync
+        DBuf<unsigned long long> d_cnt;     // vts::C_WORDS counters: rows and entries of the running call, levels replayed since sw_create
+        int64_t calls = 0, rows = 0, entries = 0;             // sw_get_votes_stats
+        double ms[2] = {0, 0};              // ... under sw_set_profiling: plan + existence + count, rows + values
+    } votes;
     int export_lanes = 16;        // SW_EXPORT_LANES (measurement knob, read at sw_create): lanes of a wave that share one output slot — 4, 8 or 16
     // answering a sync by the pruned walk, forked hashgraphs included (sw_sync_walk, sw_export_walk[_device], sw_sync_pull_walk,
     // sw_get_fork_trunks; walk.hip.h)
@@ -3301,6 +3311,7 @@ int sw_destroy(sw_ctx* c) {
     dfree(c->d_ing_tab); dfree(c->d_ing_hist); dfree(c->d_ht_stat);
     dfree(c->d_id); dfree(c->d_idtab); dfree(c->d_idflag); dfree(c->d_pl); dfree(c->d_pl_in);
     dfree(c->d_xp); dfree(c->d_xp_out);
+    dfree(c->votes.d_sched); dfree(c->votes.d_plan); dfree(c->votes.d_work); dfree(c->votes.d_out); dfree(c->votes.d_cnt);
     dfree(c->d_wk); dfree(c->d_wk_bits); dfree(c->d_wk_q); dfree(c->d_wk_list); dfree(c->d_wk_trunk); dfree(c->d_wk_children);
     dfree(c->d_rr); dfree(c->d_cts); dfree(c->d_tx); dfree(c->d_cs_ordpos); dfree(c->d_cs_out);
     dfree(c->d_vkeys); dfree(c->d_vtab); dfree(c->d_v_in);
@@ -4658,6 +4669,7 @@ int sw_rewind(sw_ctx* c) {
     HIPCHK(c, hipStreamSynchronize(c->stream_aux));
     const size_t rows = (size_t)c->Rcap * c->npad;
     c->fame_calls.clear();
+    c->votes.sched_calls = -1;
     c->votes_partial = false;
     c->eval_src = 0;
     std::fill(c->cons_call.begin(), c->cons_call.end(), -1);
@@ -5022,6 +5034,237 @@ int sw_get_vote(sw_ctx* c, int rv, int mv, int rc, int mc, int8_t* out) {
         }
         if (d == D) { *out = Vn[mv]; return SW_OK; }
         V.swap(Vn);
+    }
+    return SW_OK;
+}
+
+// ---- Node.votes in bulk (votes.hip.h): the table of sw_get_vote's answers for whole voter rounds ---------------------------
+}  // extern "C"
+namespace {
+
+struct VotesCall {
+    int rv0 = 0, rv1 = 0, rc0 = 0, nrv = 0;   // voter rounds [rv0, rv1) (rv0 >= 1), candidate rounds from rc0 on
+    long long pairs = 0;                      // (voter round, candidate round) pairs the call schedule allows
+    vts::Tables t{};
+    vts::Sched s{};
+    vts::Range g{};
+    vts::Work w{};
+};
+
+// sw_get_vote's preconditions for the whole range; *empty: nothing to export
+int votes_pre(sw_ctx* c, int rv0, int rv1, const char* what, bool* empty) {
+    *empty = true;
+    if (c->poisoned) return fail(c, SW_EIO, "context unusable after an earlier device failure");
+    if (c->exact) return fail(c, SW_ENOTSUP, "%s is not available on the exact (forked-hashgraph) path", what);
+    if (c->votes_partial) return fail(c, SW_ENOTSUP, "%s is not available after sw_commit_fame (the deciding voters of other parts' witnesses are not recorded)", what);
+    if (rv0 >= rv1) return SW_OK;
+    if (rv0 < 0 || rv1 > c->R) return fail(c, SW_ERANGE, "%s: voter rounds [%d, %d) outside the table of %d rounds", what, rv0, rv1, c->R);
+    const int seen = c->fame_calls.empty() ? 0 : c->fame_calls.back().R;
+    if (rv1 > seen || rv1 > c->Sw_rows || c->sw_dirty_from < rv1)
+        return fail(c, SW_EINVAL, "%s: votes are available after decide_fame has seen these rounds (%d so far)", what, seen);
+    *empty = rv1 <= 1;
+    return SW_OK;
+}
+
+// the call schedule on the device, uploaded when decide_fame has been called since
+int votes_schedule(sw_ctx* c, VotesCall& v) {
+    auto& vs = c->votes;
+    const int ncalls = (int)c->fame_calls.size(), R = ncalls ? c->fame_calls.back().R : 0;
+    Carve cv;
+    const size_t o_maxc = cv.take((size_t)ncalls * 4), o_cons = cv.take((size_t)R * 4), o_div = cv.take((size_t)ncalls * 8);
+    if (vs.sched_calls != ncalls) {
+        CHK(dgrow(c, vs.d_sched, cv.off + 256, 0));
+        vs.sched_stage.assign(cv.off, 0);
+        int32_t* maxc = (int32_t*)(vs.sched_stage.data() + o_maxc);
+        int32_t* cons = (int32_t*)(vs.sched_stage.data() + o_cons);
+        long long* div = (long long*)(vs.sched_stage.data() + o_div);
+        for (int i = 0; i < ncalls; ++i) { maxc[i] = c->fame_calls[i].max_c; div[i] = c->fame_calls[i].divided; }
+        for (int r = 0; r < R; ++r) cons[r] = c->cons_call[r];
+        HIPCHK(c, hipMemcpyAsync(vs.d_sched.p, vs.sched_stage.data(), cv.off, hipMemcpyHostToDevice, c->stream));
+        vs.sched_calls = ncalls;
+    }
+    v.s.call_maxc = (const int*)(vs.d_sched.p + o_maxc);
+    v.s.cons_call = (const int*)(vs.d_sched.p + o_cons);
+    v.s.call_div = (const long long*)(vs.d_sched.p + o_div);
+    v.s.ncalls = ncalls;
+    return SW_OK;
+}
+
+// Per voter round what the host knows (vts::plan_rounds: the calls that bound its entries, the lowest candidate round they
+// leave open), uploaded; the context's tables; and the call's scratch carved out of one allocation.
+int votes_plan(sw_ctx* c, VotesCall& v, int rv0, int rv1) {
+    auto& vs = c->votes;
+    const auto& calls = c->fame_calls;
+    const int ncalls = (int)calls.size(), np = c->npad;
+    v.rv0 = std::max(rv0, 1);
+    v.rv1 = rv1;
+    v.nrv = v.rv1 - v.rv0;
+    Carve cv;
+    const size_t o_lo = cv.take((size_t)v.nrv * 4), o_c1v = cv.take((size_t)v.nrv * 4), o_cf = cv.take((size_t)v.nrv * 4),
+                 o_q = cv.take((size_t)(v.nrv + 1) * 8);
+    vs.plan_stage.assign(cv.off, 0);
+    int32_t* lo = (int32_t*)(vs.plan_stage.data() + o_lo);
+    int32_t* c1v = (int32_t*)(vs.plan_stage.data() + o_c1v);
+    int32_t* cf = (int32_t*)(vs.plan_stage.data() + o_cf);
+    long long* q = (long long*)(vs.plan_stage.data() + o_q);
+    std::vector<vts::CallRec> recs(ncalls);
+    for (int i = 0; i < ncalls; ++i) recs[i] = vts::CallRec{calls[i].max_c, calls[i].R, (long long)calls[i].divided};
+    v.rc0 = vts::plan_rounds(recs.data(), ncalls, c->cons_call.data(), v.rv0, v.rv1, lo, c1v, cf, q);
+    v.pairs = q[v.nrv];
+    CHK(dgrow(c, vs.d_plan, cv.off + 256, 0));
+    HIPCHK(c, hipMemcpyAsync(vs.d_plan.p, vs.plan_stage.data(), cv.off, hipMemcpyHostToDevice, c->stream));
+    v.g = vts::Range{v.rv0, v.rv1, v.rc0, (const int*)(vs.d_plan.p + o_lo), (const int*)(vs.d_plan.p + o_c1v), (const int*)(vs.d_plan.p + o_cf),
+                     (const long long*)(vs.d_plan.p + o_q)};
+    v.t = vts::Tables{c->d_wit.p, (const vts::u64*)c->d_Sw.p, c->d_coin.p, c->d_stake.p, c->d_dec_call.p, c->d_dec_by.p, c->d_round.p, (long long)c->N,
+                      c->n, np, c->nw, (c->n + 63) / 64, c->coin_period, 2u * c->tot};
+    // scratch
+    const size_t NR = (size_t)(v.rv1 - v.rc0), V = (size_t)v.nrv * np;
+    Carve wc;
+    const size_t o_born = wc.take(NR * np * 4), o_rz = wc.take(NR * np * 4), o_order = wc.take(NR * np * 4), o_rank = wc.take(NR * np * 4),
+                 o_nwit = wc.take(NR * 4), o_hr = wc.take(NR * 4), o_hc = wc.take(NR * 4), o_lod = wc.take((size_t)v.nrv * 4),
+                 o_mask = wc.take((size_t)v.pairs * c->nw * 8), o_vrows = wc.take(V * 4), o_vent = wc.take(V * 8), o_voff = wc.take(V * 8);
+    CHK(dgrow(c, vs.d_work, wc.off + 256, 0));
+    if (!vs.d_cnt.p) {
+        CHK(dgrow(c, vs.d_cnt, vts::C_WORDS, 0));
+        HIPCHK(c, hipMemsetAsync(vs.d_cnt.p, 0, vts::C_WORDS * sizeof(unsigned long long), c->stream));
+    }
+    unsigned char* B = vs.d_work.p;
+    v.w = vts::Work{(int*)(B + o_born), (int*)(B + o_rz), (int*)(B + o_order), (int*)(B + o_rank), (int*)(B + o_nwit), (int*)(B + o_hr), (int*)(B + o_hc),
+                    (int*)(B + o_lod), (vts::u64*)(B + o_mask), (int*)(B + o_vrows), (long long*)(B + o_vent), (long long*)(B + o_voff), vs.d_cnt.p};
+    if (v.pairs) HIPCHK(c, hipMemsetAsync(B + o_mask, 0, (size_t)v.pairs * c->nw * 8, c->stream));
+    return SW_OK;
+}
+
+// existence: rows per voter, their scan, and the read-back of the two counts — the call's one synchronisation
+int votes_count(sw_ctx* c, VotesCall& v, int64_t* n_rows, int64_t* n_entries) {
+    const int np = c->npad;
+    const long long V = (long long)v.nrv * np;
+    const unsigned vblocks = (unsigned)((V + vts::COUNT_THREADS - 1) / vts::COUNT_THREADS);
+    hipLaunchKernelGGL(vts::k_votes_prep, dim3((unsigned)(v.rv1 - v.rc0)), dim3(np), 0, c->stream, v.t, v.s, v.g, v.w);
+    hipLaunchKernelGGL(vts::k_votes_lo, dim3((unsigned)((v.nrv + vts::COUNT_THREADS - 1) / vts::COUNT_THREADS)), dim3(vts::COUNT_THREADS), 0, c->stream, v.g, v.w);
+    hipLaunchKernelGGL(vts::k_votes_rows<false>, dim3(vblocks), dim3(vts::COUNT_THREADS), 0, c->stream, v.t, v.s, v.g, v.w, vts::Out{});
+    hipLaunchKernelGGL(vts::k_votes_scan, dim3(1), dim3(vts::SCAN_THREADS), 0, c->stream, v.w, V);
+    c->ctr.kernel_launches += 4;
+    HIPCHK(c, hipGetLastError());
+    unsigned long long cnt[2] = {0, 0};
+    HIPCHK(c, hipMemcpyAsync(cnt, c->votes.d_cnt.p, sizeof cnt, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    *n_rows = (int64_t)cnt[vts::C_ROWS];
+    *n_entries = (int64_t)cnt[vts::C_ENTRIES];
+    return SW_OK;
+}
+
+// the rows and their exists words, then the elections replayed for the values
+int votes_write(sw_ctx* c, VotesCall& v, const vts::Out& out) {
+    const int np = c->npad;
+    const long long V = (long long)v.nrv * np;
+    const unsigned vblocks = (unsigned)((V + vts::COUNT_THREADS - 1) / vts::COUNT_THREADS);
+    hipLaunchKernelGGL(vts::k_votes_rows<true>, dim3(vblocks), dim3(vts::COUNT_THREADS), 0, c->stream, v.t, v.s, v.g, v.w, out);
+    const unsigned blocks = (unsigned)(v.rv1 - 1 - v.rc0) * (unsigned)v.t.nwo;   // candidate rounds rc0 .. rv1 - 2
+    const size_t lds = ((size_t)64 * c->nw + np) * 8 + (size_t)np * 4 + 16;
+    if (blocks) {
+        if (c->unit_stake) hipLaunchKernelGGL(vts::k_votes_values<true>, dim3(blocks), dim3(np), lds, c->stream, v.t, v.g, v.w, out);
+        else hipLaunchKernelGGL(vts::k_votes_values<false>, dim3(blocks), dim3(np), lds, c->stream, v.t, v.g, v.w, out);
+    }
+    c->ctr.kernel_launches += 2;
+    HIPCHK(c, hipGetLastError());
+    return SW_OK;
+}
+
+void votes_account(sw_ctx* c, int64_t rows, int64_t entries) {
+    c->votes.calls++;
+    c->votes.rows += rows;
+    c->votes.entries += entries;
+}
+
+}  // namespace
+extern "C" {
+
+int sw_export_votes_device(sw_ctx* c, int rv0, int rv1, int64_t cap_rows, int32_t* d_row_voter, int32_t* d_row_cand_round, uint64_t* d_exists,
+                           uint64_t* d_value, int64_t* n_rows, int64_t* n_entries, void* user_stream) {
+    if (!c) return SW_EINVAL;
+    const char* what = "sw_export_votes_device";
+    if (!n_rows || !n_entries) return fail(c, SW_EINVAL, "%s: n_rows or n_entries is NULL", what);
+    *n_rows = *n_entries = 0;
+    bool empty = true;
+    CHK(votes_pre(c, rv0, rv1, what, &empty));
+    if (cap_rows < 0 || (cap_rows > 0 && (!d_row_voter || !d_row_cand_round || !d_exists || !d_value)))
+        return fail(c, SW_EINVAL, "%s: NULL output arrays (capacity %lld)", what, (long long)cap_rows);
+    // (with capacity 0 the rows are empty and skipped: the alignment of whatever was passed is asked for all the same)
+    if (cap_rows == 0 && (((uintptr_t)d_exists | (uintptr_t)d_value) & 15)) return misaligned(c, what, 16);
+    const size_t k = (size_t)cap_rows, nwo = (size_t)(c->n + 63) / 64;
+    CHK(device_args(c, what, {{d_exists, k * nwo * 8, 16}, {d_value, k * nwo * 8, 16}, {d_row_voter, k * 4, 4}, {d_row_cand_round, k * 4, 4}}));
+    if (empty) return SW_OK;
+    const bool prof = c->profiling;
+    auto t0 = std::chrono::steady_clock::now();
+    UserStream bracket;   // earlier readers of the output arrays
+    CHK(bracket.join(c, (hipStream_t)user_stream));
+    VotesCall v;
+    CHK(votes_schedule(c, v));
+    CHK(votes_plan(c, v, rv0, rv1));
+    CHK(votes_count(c, v, n_rows, n_entries));
+    c->votes.ms[0] = prof ? ms_since(t0) : 0;
+    c->votes.ms[1] = 0;
+    if (*n_rows > cap_rows) return fail(c, SW_ERANGE, "%s: %lld rows to export, capacity %lld (nothing written)", what, (long long)*n_rows, (long long)cap_rows);
+    t0 = std::chrono::steady_clock::now();
+    if (*n_rows) CHK(votes_write(c, v, vts::Out{d_row_voter, d_row_cand_round, (vts::u64*)d_exists, (vts::u64*)d_value}));
+    CHK(bracket.leave());
+    if (prof) { HIPCHK(c, hipStreamSynchronize(c->stream)); c->votes.ms[1] = ms_since(t0); }
+    votes_account(c, *n_rows, *n_entries);
+    return SW_OK;
+}
+
+int sw_export_votes(sw_ctx* c, int rv0, int rv1, int64_t cap_rows, int32_t* row_voter, int32_t* row_cand_round, uint64_t* exists, uint64_t* value,
+                    int64_t* n_rows, int64_t* n_entries) {
+    if (!c) return SW_EINVAL;
+    const char* what = "sw_export_votes";
+    if (!n_rows || !n_entries) return fail(c, SW_EINVAL, "%s: n_rows or n_entries is NULL", what);
+    *n_rows = *n_entries = 0;
+    bool empty = true;
+    CHK(votes_pre(c, rv0, rv1, what, &empty));
+    if (cap_rows < 0 || (cap_rows > 0 && (!row_voter || !row_cand_round || !exists || !value)))
+        return fail(c, SW_EINVAL, "%s: NULL output arrays (capacity %lld)", what, (long long)cap_rows);
+    if (empty) return SW_OK;
+    HIPCHK(c, hipSetDevice(c->device));
+    const bool prof = c->profiling;
+    auto t0 = std::chrono::steady_clock::now();
+    VotesCall v;
+    CHK(votes_schedule(c, v));
+    CHK(votes_plan(c, v, rv0, rv1));
+    CHK(votes_count(c, v, n_rows, n_entries));
+    c->votes.ms[0] = prof ? ms_since(t0) : 0;
+    c->votes.ms[1] = 0;
+    if (*n_rows > cap_rows) return fail(c, SW_ERANGE, "%s: %lld rows to export, capacity %lld (nothing written)", what, (long long)*n_rows, (long long)cap_rows);
+    t0 = std::chrono::steady_clock::now();
+    if (*n_rows) {
+        const size_t k = (size_t)*n_rows, nwo = (size_t)(c->n + 63) / 64;
+        Stage st;
+        const size_t o_ex = st.out(exists, k * nwo * 8), o_val = st.out(value, k * nwo * 8), o_rv = st.out(row_voter, k * 4), o_rc = st.out(row_cand_round, k * 4);
+        unsigned char* B = nullptr;
+        CHK(stage_up(c, c->votes.d_out, st, &B));
+        CHK(votes_write(c, v, vts::Out{(int*)(B + o_rv), (int*)(B + o_rc), (vts::u64*)(B + o_ex), (vts::u64*)(B + o_val)}));
+        CHK(stage_down(c, st, B));
+    }
+    if (prof) c->votes.ms[1] = ms_since(t0);
+    votes_account(c, *n_rows, *n_entries);
+    return SW_OK;
+}
+
+int sw_get_votes_stats(sw_ctx* c, int64_t* calls, int64_t* rows, int64_t* entries, int64_t* levels, double* phase_ms) {
+    if (!c) return SW_EINVAL;
+    if (calls) *calls = c->votes.calls;
+    if (rows) *rows = c->votes.rows;
+    if (entries) *entries = c->votes.entries;
+    if (phase_ms) for (int i = 0; i < 2; ++i) phase_ms[i] = c->votes.ms[i];
+    if (levels) {
+        *levels = 0;
+        if (c->votes.d_cnt.p) {
+            unsigned long long lv = 0;
+            HIPCHK(c, hipSetDevice(c->device));
+            HIPCHK(c, hipMemcpyAsync(&lv, c->votes.d_cnt.p + vts::C_LEVELS, sizeof lv, hipMemcpyDeviceToHost, c->stream));
+            HIPCHK(c, hipStreamSynchronize(c->stream));
+            *levels = (int64_t)lv;
+        }
     }
     return SW_OK;
 }

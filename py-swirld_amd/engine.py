@@ -548,6 +548,61 @@ class Hashgraph:
         self._chk(self._L.sw_get_vote(self._h, int(rv), int(mv), int(rc), int(mc), C.byref(v)))
         return int(v.value)
 
+    # ---- Node.votes in bulk (swirld.py:60-61, 256-272; csrc/votes.hip.h) ----
+    def export_votes_device(self, rv0, rv1, cap_rows, row_voter=None, row_cand_round=None, exists=None, value=None, stream=0):
+        """The votes table of the voter rounds [rv0, rv1) written to DEVICE arrays (include/swirld_hip.h): row_voter,
+        row_cand_round (int32 per row), exists, value (ceil(n / 64) uint64 per row, 16-byte aligned).  `cap_rows`: rows the
+        arrays can take; a larger table raises SwirldHipError with code -34 and writes nothing (cap_rows = 0 with no arrays:
+        the size query, which does not raise).  `stream` is made to wait for the arrays.  Returns (n_rows, n_entries)."""
+        a = [C.c_void_p(q) if q else None for q in (_dev_ptr(x)[0] for x in (row_voter, row_cand_round, exists, value))]
+        n_rows, n_entries = C.c_int64(), C.c_int64()
+        rc = self._L.sw_export_votes_device(self._h, int(rv0), int(rv1), int(cap_rows), *a, C.byref(n_rows), C.byref(n_entries), C.c_void_p(int(stream)))
+        if not (rc == -34 and int(cap_rows) == 0 and n_rows.value > 0):
+            self._chk(rc)
+        return int(n_rows.value), int(n_entries.value)
+
+    def export_votes(self, rv0=1, rv1=None):
+        """Node.votes of the voter rounds [rv0, rv1) (default: every round) as (row_voter, row_cand_round, exists, value):
+        one row per (voter witness y, candidate round rc) with an entry, sorted by (round(y), y, rc); bit mc of
+        exists[row] / value[row] (uint64 words, ceil(n / 64) per row): votes[y][witnesses[rc][mc]] exists / is True."""
+        rv1 = self.max_round + 1 if rv1 is None else int(rv1)
+        nwo = (self.n + 63) // 64
+        n_rows, n_entries = C.c_int64(), C.c_int64()
+        rc = self._L.sw_export_votes(self._h, int(rv0), rv1, 0, None, None, None, None, C.byref(n_rows), C.byref(n_entries))
+        if not (rc == -34 and n_rows.value > 0):
+            self._chk(rc)
+        K = int(n_rows.value)
+        out = (np.empty(K, np.int32), np.empty(K, np.int32), np.empty((K, nwo), np.uint64), np.empty((K, nwo), np.uint64))
+        if K:
+            self._chk(self._L.sw_export_votes(self._h, int(rv0), rv1, K, *[_p(a) for a in out], C.byref(n_rows), C.byref(n_entries)))
+        return out
+
+    def votes_triples(self, rv0=1, rv1=None):
+        """export_votes expanded to an int64 [K, 3] array of (y, x, v): voter, candidate (dense indices) and the vote, in row
+        order, candidates of a row by member index."""
+        row_voter, row_cand, exists, value = self.export_votes(rv0, rv1)
+        rows = len(row_voter)
+        bits = lambda w: np.unpackbits(np.ascontiguousarray(w.astype("<u8")).view(np.uint8).reshape(rows, -1), axis=1,  # noqa: E731
+                                       bitorder="little")[:, :self.n]
+        out = np.empty((0, 3), np.int64)
+        if rows:
+            ex = bits(exists)
+            i, mc = np.nonzero(ex)
+            wit = self.witnesses(0, int(row_cand.max()) + 1)
+            out = np.empty((len(i), 3), np.int64)
+            out[:, 0] = row_voter[i]
+            out[:, 1] = wit[row_cand[i], mc]
+            out[:, 2] = bits(value)[i, mc]
+        return out
+
+    def votes_stats(self):
+        """Bulk exports since the context was created: calls, rows and entries exported, election levels replayed, and under
+        set_profiling the host time of the most recent call's phases (plan + existence + counts, rows + values)."""
+        c = [C.c_int64() for _ in range(4)]
+        ms = (C.c_double * 2)()
+        self._chk(self._L.sw_get_votes_stats(self._h, *[C.byref(x) for x in c], ms))
+        return {"calls": c[0].value, "rows": c[1].value, "entries": c[2].value, "levels": c[3].value, "phase_ms": [ms[0], ms[1]]}
+
     # ---- gossip side from device state (N4) ----
     def known_heights(self, head_event):
         """{member -> height of the newest event of that member `head_event` sees} as an array, -1 absent

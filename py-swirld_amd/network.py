@@ -85,6 +85,14 @@ class DeviceNetwork:
         ids, ct = self._ids(i), self.ctx[i].consensus_time()
         return {ids[e]: float(ct[e]) for e in self.ctx[i].transactions()}
 
+    def votes(self, i):
+        """Node.votes of node i (swirld.py:60-61): {voter id: {candidate id: bool}}, the voters that hold an entry."""
+        ids = self._ids(i)
+        out = {}
+        for y, x, v in self.ctx[i].votes_triples().tolist():
+            out.setdefault(ids[y], {})[ids[x]] = bool(v)
+        return out
+
     def ordered_data(self, i):
         """The data of the ordered events, in order (bytes | None)."""
         tx = self.ctx[i].transactions()

@@ -213,10 +213,21 @@ class _VoterVotes(Mapping):
         nd = self._n
         rv, mv = self._slot(self._y)
         wit = nd._witness_table()
-        for rc in range(rv):
-            for mc in np.argsort(np.where(wit[rc] >= 0, wit[rc], np.iinfo(np.int32).max), kind="stable"):
-                if wit[rc, mc] >= 0 and self._vote(rv, mv, rc, int(mc)) >= 0:
-                    yield nd._ids[wit[rc, mc]]
+        if not hasattr(nd._dev, "export_votes"):   # a backend without the bulk export: entry by entry
+            for rc in range(rv):
+                for mc in np.argsort(np.where(wit[rc] >= 0, wit[rc], np.iinfo(np.int32).max), kind="stable"):
+                    if wit[rc, mc] >= 0 and self._vote(rv, mv, rc, int(mc)) >= 0:
+                        yield nd._ids[wit[rc, mc]]
+            return
+        # the bulk route: the rows of y in the table of its voter round, candidate rounds ascending, the candidates of a
+        # round in registration order (= ascending dense index)
+        row_voter, row_cand, exists, _ = nd._votes_round(rv)
+        y = nd._index[self._y]
+        for i in range(np.searchsorted(row_voter, y, "left"), np.searchsorted(row_voter, y, "right")):
+            rc = int(row_cand[i])
+            mcs = np.flatnonzero(np.unpackbits(exists[i].astype("<u8").view(np.uint8), bitorder="little")[:wit.shape[1]])
+            for e in np.sort(wit[rc, mcs]):
+                yield nd._ids[e]
 
     def __len__(self):
         return sum(1 for _ in self)
@@ -224,8 +235,8 @@ class _VoterVotes(Mapping):
 
 class _VotesView(Mapping):
     """Node.votes: {voter witness -> {candidate witness -> bool}} (swirld.py:60-61).  The GPU
-    elections keep votes as per-round member bitmasks; entries are recomputed on demand
-    (sw_get_vote) with the reference's full semantics, the decide_fame() call schedule included: a
+    elections keep votes as per-round member bitmasks; entries are recomputed on demand (one by
+    sw_get_vote, a voter's whole dict from the table of its round, sw_export_votes) with the reference's full semantics, the decide_fame() call schedule included: a
     voter has an entry for every candidate it evaluated, in whichever call, before that candidate
     was decided (Appendix A Q8/Q9)."""
 
@@ -353,6 +364,7 @@ class Node:
         self._round_cache = np.zeros(0, np.int32)
         self._wit_cache = None
         self._fam_cache = None
+        self._votes_cache = {}         # voter round -> its votes table (_votes_round)
 
         self.round = _RoundView(self)
         self.can_see = _CanSeeView(self)
@@ -867,6 +879,7 @@ class Node:
         self._dev.divide_rounds(first, len(events))
         self._divided = first + len(events)
         self._wit_cache = None
+        self._votes_cache = {}
 
     def decide_fame(self):
         """Run the witness elections; returns the set of newly decided rounds
@@ -874,6 +887,7 @@ class Node:
         new_c = {int(r) for r in self._dev.decide_fame()}
         self.consensus |= new_c
         self._fam_cache = None
+        self._votes_cache = {}
         return new_c
 
     def find_order(self, new_c):
@@ -922,6 +936,23 @@ class Node:
             rr, ct = self._dev.round_received(lo, hi - lo), self._dev.consensus_time(lo, hi - lo)
             self._cons_cache = (np.concatenate([self._cons_cache[0], rr[ev - lo]]), np.concatenate([self._cons_cache[1], ct[ev - lo]]))
         return self._cons_cache
+
+    def _votes_round(self, rv):
+        """The votes table of voter round rv (Hashgraph.export_votes(rv, rv + 1)), kept until the next divide_rounds or
+        decide_fame.  A round decide_fame has not seen yet holds no votes."""
+        t = self._votes_cache.get(rv)
+        if t is None:
+            try:
+                t = self._dev.export_votes(rv, rv + 1)
+            except SwirldHipError as exc:
+                if exc.code == -95:
+                    raise VotesUnavailable(str(exc)) from None
+                if exc.code != -22:
+                    raise
+                nwo = (self.n + 63) // 64
+                t = (np.empty(0, np.int32), np.empty(0, np.int32), np.empty((0, nwo), np.uint64), np.empty((0, nwo), np.uint64))
+            self._votes_cache[rv] = t
+        return t
 
     def _witness_table(self):
         if self._wit_cache is None:
