@@ -44,10 +44,12 @@ class Election:
         self.stake = g["stake"].astype(np.int64)
         self.tot2 = 2 * int(self.stake.sum())
         self.coin = g["sig"][:, 0] >> 7
-        self.V, self.strong, self.coined = [None], [None], [None]
+        self.unit = bool((self.stake == 1).all())
+        self.V, self.strong, self.coined, self.by_stake = [None], [None], [None], [None]
 
     def level(self, d):
-        """(vote, supermajority, coin branch taken): bool [voter member][candidate member]"""
+        """(vote, supermajority, coin branch taken): bool [voter member][candidate member]; by_stake[d] beside them: the
+        entries whose majority or supermajority by STAKE is not what a count of the same voters gives"""
         while len(self.V) <= d:
             k = len(self.V)
             wit = self.g["witnesses"][self.rc + k]
@@ -57,12 +59,22 @@ class Election:
                 self.V.append(Sk.copy())                           # x in s (swirld.py:258)
                 self.strong.append(np.zeros_like(Sk))
                 self.coined.append(np.zeros_like(Sk))
+                self.by_stake.append(np.zeros_like(Sk))
                 continue
             w = Sk * self.stake[None, :]                           # [voter][member]
             yes = w @ self.V[k - 1].astype(np.int64)               # [voter][candidate]
             no = w.sum(axis=1)[:, None] - yes
             vote = ~(no > yes)                                     # majority(): a tie is True (swirld.py:24-27)
             strong = 3 * np.where(vote, yes, no) > self.tot2
+            by_stake = np.zeros_like(vote)
+            if not self.unit:                                      # the same tally with every voter weighing 1, against 2 n / 3
+                heads = Sk.astype(np.int64)
+                yes_h = heads @ self.V[k - 1].astype(np.int64)
+                no_h = heads.sum(axis=1)[:, None] - yes_h
+                vote_h = ~(no_h > yes_h)
+                strong_h = 3 * np.where(vote_h, yes_h, no_h) > 2 * len(self.stake)
+                by_stake = ((vote != vote_h) | (strong != strong_h)) & has[:, None]
+            self.by_stake.append(by_stake)
             coined = np.zeros_like(vote)
             if k % COIN_PERIOD == 0:
                 coined = ~strong & has[:, None]
@@ -74,7 +86,8 @@ class Election:
 
 
 def model_votes(g, new_c=None):
-    """-> dict(row_voter, row_cand_round, exists [rows][nwo] uint64, value, n_entries, n_coin, n_weighted, and the
+    """-> dict(row_voter, row_cand_round, exists [rows][nwo] uint64, value, n_entries, n_coin, n_weighted, n_by_stake (the
+    evaluated entries whose outcome by stake differs from a head count of the same voters), and the
     tables the library keeps beside the hashgraph: dec_call, dec_by, calls, cons_call, S).
     new_c: per call the rounds the reference put into `consensus` (default: the golden's record)."""
     wit, rnd = g["witnesses"], g["round"]
@@ -91,7 +104,7 @@ def model_votes(g, new_c=None):
     dec_call = np.full((R, n), -1, np.int32)  # per witness slot the call and the voter that decided it (what the library records)
     dec_by = np.full((R, n), -1, np.int32)
     calls = []                               # (max_c, rounds, events divided) per call
-    n_coin = n_weighted = 0
+    n_coin = n_weighted = n_by_stake = 0
     for call, (_, divided) in enumerate(g["batches"]):
         reg = (wit >= 0) & (wit < divided)   # the witnesses this call knows
         max_c = 0
@@ -117,6 +130,8 @@ def model_votes(g, new_c=None):
                         el = elections[r] = Election(g, S, r)
                     V, strong, coined = el.level(d)
                     stored = und
+                    if d > 1:
+                        n_by_stake += int((und & el.by_stake[d][mv]).sum())
                     if d > 1 and d % COIN_PERIOD != 0:
                         decided = und & strong[mv]
                         if decided.any():
@@ -144,6 +159,7 @@ def model_votes(g, new_c=None):
         ex[i, :n], va[i, :n] = rows[k]
     return {"row_voter": np.array([k[0] for k in keys], np.int32), "row_cand_round": np.array([k[1] for k in keys], np.int32),
             "exists": pack_words(ex), "value": pack_words(va), "n_entries": int(ex.sum()), "n_coin": n_coin, "n_weighted": n_weighted,
+            "n_by_stake": n_by_stake,
             "dec_call": dec_call, "dec_by": dec_by, "calls": calls, "S": S,
             "cons_call": np.array([next((i for i, nc in enumerate(new_c) if r in set(int(x) for x in nc)), -1) for r in range(R)], np.int32)}
 

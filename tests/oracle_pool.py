@@ -1,7 +1,8 @@
 """Test scaffolding: the CPU oracle runs of the HEAVY parity cases (BASELINE.json configs[2..4]
 sizes, 1024 members, hot-member streams), started in background threads when the GPU session
 begins so that their single-core minutes overlap the rest of the suite (the oracle's C calls
-release the GIL; the GPU box has hundreds of host cores).  Never imported by the product."""
+release the GIL; the GPU box has hundreds of host cores) — and, under names that begin with "wide_stake/", the weighted
+cases of tests/wide_stake_cases.py.  Never imported by the product."""
 import importlib
 import os
 import threading
@@ -75,6 +76,29 @@ class OracleRun:
         return self
 
 
+WIDE_STAKE = "wide_stake/"    # names of the weighted cases of tests/wide_stake_cases.py in this pool
+
+
+class WideStakeRun:
+    """One weighted case of tests/wide_stake_cases.py: the oracle's whole pass (new_c and find_order of every call, the
+    final tables) as the `expected` side of wide_stake_cases.compare_pass."""
+
+    def __init__(self, name):
+        import wide_stake_cases as W
+        self.name = name
+        self.case = W.BY_NAME[name[len(WIDE_STAKE):]]
+        self.stream = self.stake = self.side = self.expected = None
+        self.seconds = 0.0
+
+    def run(self):
+        import wide_stake_cases as W
+        t0 = time.time()
+        self.stream, self.stake = W.stream_of(self.case), W.stake_of(self.case)
+        self.side, self.expected = W.oracle_pass(self.case, self.stake, self.stream)
+        self.seconds = time.time() - t0
+        return self
+
+
 class OraclePool:
     def __init__(self, names=None):
         # build / load both libraries once, before any thread touches them
@@ -90,7 +114,8 @@ class OraclePool:
     def start(self, name):
         with self._lock:
             if name not in self._fut:
-                self._fut[name] = self._ex.submit(OracleRun(name).run)
+                job = WideStakeRun(name) if name.startswith(WIDE_STAKE) else OracleRun(name)
+                self._fut[name] = self._ex.submit(job.run)
 
     def get(self, name, timeout=1500):
         self.start(name)

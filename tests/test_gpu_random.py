@@ -59,6 +59,8 @@ def test_random_shapes(pkg, monkeypatch, seed):
         stake = np.ones(n, np.uint64)
         stake[rng.integers(0, n, size=max(1, n // 10))] = 2
     o, h = Oracle(n, stake), pkg.Hashgraph(n, stake)
+    if stake is not None:   # whatever SW_TALLY_IMPL asked for: a weighted context runs the column-lane tally
+        assert h._L.sw_get_tally_impl(h._h) == 0
     chunk = chunk or N
     for a in range(0, N, chunk):
         b = min(N, a + chunk)
@@ -74,6 +76,7 @@ def test_random_shapes(pkg, monkeypatch, seed):
             with pytest.raises(pkg.SwirldHipError):
                 h.find_order(nch)
             assert h.num_ordered == len(before) and np.array_equal(h.transactions(), before)   # a failed call keeps nothing
+            assert stake is None or h._L.sw_get_tally_impl(h._h) == 0
             return
         assert list(h.find_order(nch)) == exp
     assert np.array_equal(h.rounds(), o.round)
@@ -84,4 +87,6 @@ def test_random_shapes(pkg, monkeypatch, seed):
     assert np.array_equal(h.famous()[m], o.famous_by_event[wit[m]])
     assert np.array_equal(h.consensus(), o.consensus())
     assert np.array_equal(h.transactions(), o.transactions)
+    if stake is not None:   # ... and still does at the end of the pass
+        assert h._L.sw_get_tally_impl(h._h) == 0
     h.close()
