@@ -1017,6 +1017,59 @@ int sw_set_forks(sw_ctx* ctx, int accept);
 int sw_get_exact(sw_ctx* ctx, int* out);
 int sw_get_witness_order(sw_ctx* ctx, int r, int32_t* members, int* n_out);
 
+/*
+ * THE HISTORY OF THE EXACT PATH (csrc/exact_history.hip.h): what the reference keeps on a forked hashgraph
+ * beyond the bare order (swirld.py:256-272, 283, 305).  A context switch, OFF by default: without it an exact context
+ * answers as described above (SW_ENOTSUP for everything below and for the consensus getters), call for call and launch for
+ * launch.  The vote history is the reference's unbounded dict: a caller opts in to its memory.
+ *
+ * sw_set_exact_history(ctx, 0 | 1)   only before the first event is appended (SW_EINVAL afterwards); sw_reset keeps it.
+ * sw_get_exact_history   the switch, and whether the votes are available right now (either pointer may be NULL).
+ *
+ * WITH THE SWITCH ON, on the exact path:
+ *   sw_get_round_received, sw_get_consensus_time, sw_export_ordered[_device], sw_get_consensus_stats answer with every
+ *   contract they have on the fast path (ids need the complete id index, stream contract, read-only); what the fast path
+ *   recorded before the fork stays.  A find_order call that returns an error records nothing.
+ *   sw_get_vote and sw_export_votes[_device] stay refused: their (round, member) form cannot name a voter that a later fork
+ *   sibling replaced in the witness table.
+ *
+ * THE VOTES KEYED BY EVENT, on either path (SW_ENOTSUP with the switch off):
+ *   sw_get_votes_by_event     out[i] = votes[voter[i]][cand[i]] for K pairs of dense event indices in HOST arrays; -1 = no
+ *                             entry (also for an index outside the stored events).
+ *   sw_export_vote_entries[_device]   the entries from position `first` on as three arrays (voter event, candidate event,
+ *                             value 0 / 1).  *n_total (host) = all entries, always written once the checks passed.  CAPACITY
+ *                             as for the other exports: cap_entries = 0 with NULL arrays asks for the size; fewer than
+ *                             n_total - first gives SW_ERANGE and writes nothing.  The device form takes arrays in memory of
+ *                             the context's device (SW_EINVAL otherwise, before anything is launched) and follows the STREAMS
+ *                             contract of sw_export_payload_device; it synchronises at most once, for the count.
+ *   sw_get_vote_store_stats   entries, capacity (entries), bytes of device memory, growths, entries taken over from the fast
+ *                             path's table, pairs looked up, entries exported.  Any pointer may be NULL.
+ *   ENTRY ORDER: the store's — first the entries taken over from the fast path (the rows of sw_export_votes: by round of
+ *   the voter, voter, candidate round, candidate member), then first insertion by the exact path.  It is NOT the
+ *   reference's dict order; a consumer that needs an order sorts.
+ *   On a context that is still fork-free the same entries are computed from the table of sw_export_votes, with that call's
+ *   preconditions (SW_EINVAL while rounds are divided that sw_decide_fame has not seen, SW_ENOTSUP after sw_commit_fame); the
+ *   store is refilled only when sw_divide_rounds or sw_decide_fame ran since the last read.  A table with more entries than
+ *   the ceiling is refused as "unavailable" on every read, like a store that overflowed.
+ *   UNAVAILABLE (SW_ENOTSUP, the message says "unavailable" and why) until sw_rewind / sw_reset: the store reached its
+ *   ceiling; a decide_fame call ended in the reference's KeyError; the context forked after sw_commit_fame, or with rounds
+ *   divided that sw_decide_fame had not seen.  Consensus results are the same either way.
+ *   Environment (read at sw_create, and again by sw_rewind / sw_reset on the exact path, where the store is empty):
+ *   SW_VOTE_STORE_INIT, the first capacity in entries (default 4096; the store doubles); SW_VOTE_STORE_MAX, the ceiling in
+ *   entries (default 2^24).  9 bytes of log and at least 8 bytes of index per entry.  MEMORY: before every sw_decide_fame the
+ *   store is grown to what the call could write at most, n^2 * w (w - 1) / 2 more entries for w undecided rounds, capped at the
+ *   ceiling — so a call over many undecided rounds (a batch pass, many members) reserves up to the ceiling, about 25 bytes per
+ *   entry of it (0.4 GB at the default), however few votes are cast; lower the ceiling where that is too much.
+ */
+int sw_set_exact_history(sw_ctx* ctx, int enable);
+int sw_get_exact_history(sw_ctx* ctx, int* enabled, int* votes_available);
+int sw_get_votes_by_event(sw_ctx* ctx, int64_t K, const int32_t* voter, const int32_t* cand, int8_t* out);
+int sw_export_vote_entries_device(sw_ctx* ctx, int64_t first, int64_t cap_entries, int32_t* d_voter, int32_t* d_cand, int8_t* d_value,
+                                  int64_t* n_total, void* user_stream);
+int sw_export_vote_entries(sw_ctx* ctx, int64_t first, int64_t cap_entries, int32_t* voter, int32_t* cand, int8_t* value, int64_t* n_total);
+int sw_get_vote_store_stats(sw_ctx* ctx, int64_t* entries, int64_t* capacity, int64_t* bytes, int64_t* grows, int64_t* imported,
+                            int64_t* lookups, int64_t* exported);
+
 /* Block until all work queued on the context's stream is complete. */
 int sw_synchronize(sw_ctx* ctx);
 

@@ -167,6 +167,13 @@ SIGNATURES = {
     "sw_set_forks": (C.c_int, [_P, C.c_int]),
     "sw_get_exact": (C.c_int, [_P, C.POINTER(C.c_int)]),
     "sw_get_witness_order": (C.c_int, [_P, C.c_int, C.c_void_p, C.POINTER(C.c_int)]),
+    # the history of the exact path (csrc/exact_history.hip.h)
+    "sw_set_exact_history": (C.c_int, [_P, C.c_int]),
+    "sw_get_exact_history": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "sw_get_votes_by_event": (C.c_int, [_P, C.c_int64, _P, _P, _P]),
+    "sw_export_vote_entries_device": (C.c_int, [_P, C.c_int64, C.c_int64, _P, _P, _P, C.POINTER(C.c_int64), _P]),
+    "sw_export_vote_entries": (C.c_int, [_P, C.c_int64, C.c_int64, _P, _P, _P, C.POINTER(C.c_int64)]),
+    "sw_get_vote_store_stats": (C.c_int, [_P] + [C.POINTER(C.c_int64)] * 7),
     "sw_set_window": (C.c_int, [_P, C.c_int, C.c_int]),
     "sw_get_window": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "sw_set_window_lapse": (C.c_int, [_P, C.c_int64]),

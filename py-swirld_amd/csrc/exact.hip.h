@@ -24,6 +24,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "exact_history.hip.h"
+
 #if defined(__HIPCC__) && !defined(SW_EXACT_HOST)
 #define SWX_HD __device__
 #define SWX_DEVICE 1
@@ -39,7 +41,10 @@ typedef uint64_t u64;
 enum { X_OK = 0, X_EKEY = -2, X_EINDEX = -3, X_EINVAL = -22 };
 
 // hdr[] slots (int64): written by lane 0, read by everyone after a sync, copied back by the host
-enum { H_R = 0, H_RC, H_NNEW, H_NOUT, H_VOTER_EVALS, H_MAJ_EVALS, H_COIN_VOTES, H_COIN_FLIPS, H_QH, H_QT, H_NITEMS, H_TMP, H_ERR_AT, H_WORDS = 16 };
+enum { H_R = 0, H_RC, H_NNEW, H_NOUT, H_VOTER_EVALS, H_MAJ_EVALS, H_COIN_VOTES, H_COIN_FLIPS, H_QH, H_QT, H_NITEMS, H_TMP, H_ERR_AT,
+       H_VCNT,   // entries of the vote store's log (exact_history.hip.h)
+       H_VOVF,   // sticky, nonzero = the store is incomplete: 1 the log was full, 2 a decide_fame ended in a KeyError
+       H_WORDS = 16 };
 
 struct State {
     int n, npad, coin_period;
@@ -167,7 +172,71 @@ struct FameScratch {
     unsigned char* s_m;     // [npad]
     unsigned char* done;    // [Rcap]
     int* new_rounds;        // [Rcap] sorted(new_c)
+    xh::Store hist;         // where every votes[y][x] = v goes, keyed by event (all zero: nowhere)
 };
+
+// Exclusive count of the lanes below this one whose flag is set, and the count over the wave.
+SWX_HD inline int wave_prefix(bool f, int* total) {
+#if SWX_DEVICE
+    const unsigned long long b = __ballot(f);
+    *total = __popcll(b);
+    return __popcll(b & ((1ull << threadIdx.x) - 1ull));
+#else
+    if (Wave::nl == 1) { *total = f; return 0; }
+    static int flags[64];
+    flags[Wave::lane()] = f;
+    Wave::sync();
+    int below = 0, all = 0;
+    for (int i = 0; i < Wave::nl; ++i) { if (i < Wave::lane()) below += flags[i]; all += flags[i]; }
+    Wave::sync();
+    *total = all;
+    return below;
+#endif
+}
+
+// The votes the voters of round r_ stored (`cur`, complete: the caller has synchronised) into the store — every
+// self.votes[y][x] = v of swirld.py:258, 266, 269, 272 with y = wit[r_][cy], x = wit[r][cx], both fixed for the call.
+// Keys of one layer are distinct, and so are those of different voter rounds; an existing key comes from an earlier call.
+// The whole wavefront: per trip of nl entries a look-up, a ballot prefix that hands out log slots, then writes and inserts.
+SWX_HD inline void flush_votes(const State& s, const FameScratch& x, const signed char* cur, int r_, int max_c) {
+    const xh::Store& st = x.hist;
+    if (!st.voter) return;
+    const long long ovf = s.hdr[H_VOVF];
+    long long cnt = s.hdr[H_VCNT];
+    Wave::sync();   // (every lane has read the two words before lane 0 may write them)
+    if (ovf) return;
+    const int n = s.n, np = s.npad, lane = Wave::lane();
+    const size_t vrow = (size_t)x.win * n;
+    bool full = false;
+    for (size_t base = 0; base < x.layer; base += Wave::nl) {
+        const size_t i = base + lane;
+        int y = -1, xe = -1, found = -1;
+        signed char v = -1;
+        if (i < x.layer) v = cur[i];
+        if (v >= 0) {
+            const size_t cy = i / vrow, rem = i % vrow;
+            y = s.wit[(size_t)r_ * np + cy];
+            xe = s.wit[(size_t)(max_c + (int)(rem / n)) * np + rem % n];
+            found = xh::find(st, y, xe);
+        }
+        int total = 0;
+        const int pre = wave_prefix(v >= 0 && found < 0, &total);
+        if (cnt + total > st.cap) { full = true; break; }
+        Wave::sync();   // every look-up is done before the index changes
+        if (v >= 0) {
+            if (found >= 0) st.value[found] = v;
+            else {
+                const long long at = cnt + pre;
+                st.voter[at] = y; st.cand[at] = xe; st.value[at] = v;
+                xh::insert(st, y, xe, (int)at);
+            }
+        }
+        cnt += total;
+        Wave::sync();
+    }
+    if (lane == 0) { s.hdr[H_VCNT] = cnt; if (full) s.hdr[H_VOVF] = 1; }
+    Wave::sync();
+}
 
 // Node.decide_fame(), swirld.py:224-277.  hdr[H_NNEW] = len(new_c).
 SWX_HD inline int decide_fame(const State& s, const FameScratch& x) {
@@ -206,7 +275,7 @@ SWX_HD inline int decide_fame(const State& s, const FameScratch& x) {
                 if (in_s && s.wit[(size_t)(r_ - 1) * np + c_] < 0) bad = 1;  // KeyError on self.witnesses[r_-1][c]
             }
             bad = Wave::sum(bad);
-            if (bad) { if (lane == 0) s.hdr[H_RC] = X_EKEY; return X_EKEY; }
+            if (bad) { if (lane == 0) { s.hdr[H_RC] = X_EKEY; if (x.hist.voter) s.hdr[H_VOVF] = 2; } return X_EKEY; }
             if (lane == 0) s.hdr[H_VOTER_EVALS]++;
             Wave::sync();
             for (int r = max_c; r < r_; ++r) {  // iter_undetermined(r_), :231-236
@@ -231,7 +300,7 @@ SWX_HD inline int decide_fame(const State& s, const FameScratch& x) {
                             else h0 += s.stake[s.cr[w]];
                         }
                         h0 = Wave::sum(h0); h1 = Wave::sum(h1); miss = Wave::sum(miss);
-                        if (miss) { if (lane == 0) s.hdr[H_RC] = X_EKEY; return X_EKEY; }
+                        if (miss) { if (lane == 0) { s.hdr[H_RC] = X_EKEY; if (x.hist.voter) s.hdr[H_VOVF] = 2; } return X_EKEY; }
                         const int v = !(h0 > h1);  // tie -> True
                         const u64 tt = v ? h1 : h0;
                         const bool sm = 3 * tt > 2 * s.tot;
@@ -251,6 +320,7 @@ SWX_HD inline int decide_fame(const State& s, const FameScratch& x) {
                 }
             }
         }
+        flush_votes(s, x, cur, r_, max_c);  // before the layer is recycled by round r_ + 2
     }
     if (lane == 0) {  // :274-277
         int cnt = 0;
@@ -282,6 +352,7 @@ struct OrderScratch {
     unsigned char* white;    // [64]
     int* items_ev;           // [N] received events, sorted per round, concatenated
     double* items_ts;        // [N]
+    int* items_rr;           // [N] the round that received the item (swirld.py:283); null: not kept
 };
 
 // (ts, white ^ sig) order of swirld.py:306: big-endian 512-bit integers = bytewise comparison
@@ -420,6 +491,8 @@ SWX_HD inline int find_order(const State& s, const OrderScratch& x, const int* r
         if (s.hdr[H_RC] != X_OK) return (int)s.hdr[H_RC];
         const long long nitems = s.hdr[H_NITEMS];
         if (lane == 0) sort_items(s, x, produced, nitems);  // :306
+        if (x.items_rr)  // all items of the round's slice share it
+            for (long long i = lane; i < nitems; i += Wave::nl) x.items_rr[produced + i] = r;
         produced += nitems;
         Wave::sync();
     }

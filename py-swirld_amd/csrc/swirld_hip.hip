@@ -129,6 +129,23 @@ struct sw_ctx {
     int x_Rcap = 0;               // rows of x_worder / x_wcnt / x_done / x_newr
     int64_t x_cap = 0;            // events of x_fam_ev / x_tbd / x_queue / x_visited / x_items_*
     FameCounters x_fc_base{};     // fame counters of the fast path at the switch (the exact path counts from zero)
+    // what the exact path computes beyond the order, kept (sw_set_exact_history; exact_history.hip.h): round
+    // received / consensus time into d_rr / d_cts / d_tx, and Node.votes keyed by event in a log + index on the device
+    struct HistoryState {
+        bool on = false;              // the switch: set before the first event, kept by sw_reset
+        bool votes_ok = true;         // false: the store is incomplete (overflow, KeyError, votes the fast path could not hand over) until sw_rewind / sw_reset
+        const char* why = "";         // ... and the reason, for the message
+        DBuf<int32_t> d_voter, d_cand, d_tab, d_items_rr, d_q;
+        DBuf<signed char> d_value, d_qout;
+        DBuf<long long> d_off;        // row offsets of an import
+        int64_t count = 0;            // entries of the log (host copy of hdr[H_VCNT])
+        int64_t cap = 0;              // entries the log has room for
+        size_t slots = 0;             // slots of the index in use (a power of two >= 2 cap)
+        int64_t cap0 = 4096;          // SW_VOTE_STORE_INIT (history_knobs): the first capacity
+        int64_t ceiling = (int64_t)1 << 24;   // SW_VOTE_STORE_MAX (history_knobs): the most entries; beyond it votes become unavailable
+        int64_t grows = 0, imported = 0, lookups = 0, exported = 0;   // sw_get_vote_store_stats (imported: the hand-over at the first fork)
+        int64_t table_calls = -1, table_divided = -1;   // fork-free context: the decide_fame calls and divided events the store was filled from (-1: not filled)
+    } hist;
     bool unit_stake = true;
     uint32_t tot = 0;
     std::vector<uint32_t> stake_h;
@@ -2988,6 +3005,23 @@ int do_find_order(sw_ctx* c, std::vector<int32_t> rounds, int32_t* out_events, i
 }
 
 
+// the history of the exact path (sw_set_exact_history; defined behind the votes export, whose table the hand-over expands)
+static_assert(xh::QNAN_BITS == cns::QNAN_BITS, "one quiet NaN for 'not ordered'");
+// SW_VOTE_STORE_INIT / SW_VOTE_STORE_MAX (measurement and test knobs), read at sw_create and again by sw_rewind / sw_reset,
+// where the store is empty: its first capacity and its ceiling, in entries
+void history_knobs(sw_ctx* c) {
+    c->hist.cap0 = 4096;
+    c->hist.ceiling = (int64_t)1 << 24;
+    if (const char* e_ = getenv("SW_VOTE_STORE_INIT")) { const long long w = atoll(e_); if (w >= 1 && w <= ((long long)1 << 29)) c->hist.cap0 = w; }
+    if (const char* e_ = getenv("SW_VOTE_STORE_MAX")) { const long long w = atoll(e_); if (w >= 1 && w <= ((long long)1 << 29)) c->hist.ceiling = w; }
+}
+int history_enter(sw_ctx* c);                                 // the end of exact_enter: normalise the per-event tables, take the fast path's votes over
+int history_defaults(sw_ctx* c, int64_t first, int64_t K);    // events [first, first + K) are not ordered
+int history_store_reserve(sw_ctx* c, int64_t need);           // room for `need` entries in all, up to the ceiling
+xh::Store history_store(sw_ctx* c);
+int history_record(sw_ctx* c, int64_t produced);              // behind a successful exact_order
+void history_votes_lost(sw_ctx* c, const char* why);
+
 }  // namespace
 
 // ====================================================================================
@@ -3124,6 +3158,7 @@ int sw_create(int n_members, const uint64_t* stake, int coin_period, int device,
     if (const char* e_ = getenv("SW_EXPORT_LANES")) { const int g = atoi(e_); if (g == 4 || g == 8) c->export_lanes = g; }
     if (const char* e_ = getenv("SW_WALK_THREADS")) { const int w = atoi(e_); if (w >= 64 && w <= wlk::MAX_THREADS && w % 64 == 0) c->walk_threads = w; }
     if (const char* e_ = getenv("SW_WIRE_BLOCKS")) { const int w = atoi(e_); if (w >= 1 && w <= 4096) c->wire_blocks = w; }
+    history_knobs(c);
     if (getenv("SW_DEBUG_CLOCKS")) {  // diagnostics: phase stamps of the round-loop kernels
         c->dbg_minor = atoi(getenv("SW_DEBUG_CLOCKS")) >= 2 ? 0 : 1;
         if (atoi(getenv("SW_DEBUG_CLOCKS")) == 3) {
@@ -3314,6 +3349,8 @@ int sw_destroy(sw_ctx* c) {
     dfree(c->votes.d_sched); dfree(c->votes.d_plan); dfree(c->votes.d_work); dfree(c->votes.d_out); dfree(c->votes.d_cnt);
     dfree(c->d_wk); dfree(c->d_wk_bits); dfree(c->d_wk_q); dfree(c->d_wk_list); dfree(c->d_wk_trunk); dfree(c->d_wk_children);
     dfree(c->d_rr); dfree(c->d_cts); dfree(c->d_tx); dfree(c->d_cs_ordpos); dfree(c->d_cs_out);
+    dfree(c->hist.d_voter); dfree(c->hist.d_cand); dfree(c->hist.d_tab); dfree(c->hist.d_items_rr); dfree(c->hist.d_q); dfree(c->hist.d_value);
+    dfree(c->hist.d_qout); dfree(c->hist.d_off);
     dfree(c->d_vkeys); dfree(c->d_vtab); dfree(c->d_v_in);
     dfree(c->d_pk_hdr); dfree(c->d_pk); dfree(c->d_pk_in); dfree(c->d_pk_out);
     dfree(c->d_wr_set); dfree(c->d_wr); dfree(c->d_wr_in); dfree(c->d_wr_out);
@@ -3390,6 +3427,10 @@ int exact_grow(sw_ctx* c) {
         HIPCHK(c, hipMemsetAsync(c->x_visited.p, 0, c->x_visited.cap, c->stream));  // all zero between calls
         c->x_cap = c->cap;
     }
+    if (c->hist.on) {   // (asked for on every call: the switch may have been set after a sw_reset that kept the buffers above)
+        CHK(dgrow(c, c->hist.d_items_rr, (size_t)c->cap + 1, 0));
+        CHK(consensus_reserve(c, (size_t)c->tx_len));   // d_rr / d_cts follow the capacity; what was recorded stays
+    }
     if (c->x_Rcap < c->Rcap) {
         const size_t keep = (size_t)c->x_Rcap, nc = (size_t)c->Rcap;
         CHK(dgrow(c, c->x_worder, nc * np, keep * np));
@@ -3438,6 +3479,7 @@ int exact_enter(sw_ctx* c) {
     c->ctr.kernel_launches++;
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (c->hist.on) CHK(history_enter(c));
     c->exact = true;
     return SW_OK;
 }
@@ -3485,6 +3527,7 @@ int append_exact(sw_ctx* c, int64_t K, const int32_t* creator, const int32_t* se
     HIPCHK(c, hipMemsetAsync(c->d_round.p + N0, 0xff, b4, c->stream));
     HIPCHK(c, hipMemsetAsync(c->x_fam_ev.p + N0, 0xff, (size_t)K, c->stream));
     HIPCHK(c, hipMemsetAsync(c->x_tbd.p + N0, 1, (size_t)K, c->stream));
+    if (c->hist.on) CHK(history_defaults(c, N0, K));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->cr.insert(c->cr.end(), creator, creator + K);
     c->sp.insert(c->sp.end(), self_parent, self_parent + K);
@@ -3525,6 +3568,12 @@ int exact_fame(sw_ctx* c, int32_t* new_rounds, int cap, int* n_new) {
     CHK(exact_grow(c));
     CHK(dgrow(c, c->x_votes, 2 * x.layer, 0));
     x.votes = c->x_votes.p; x.s_m = c->x_sm.p; x.done = c->x_done.p; x.new_rounds = c->x_newr.p;
+    if (c->hist.on && c->hist.votes_ok) {
+        // every voter round r_ stores at most n voters x (r_ - max_c) candidate rounds x n candidates
+        const int64_t w = R - max_c;
+        CHK(history_store_reserve(c, c->hist.count + (int64_t)c->n * c->n * (w * (w - 1) / 2)));
+        x.hist = history_store(c);
+    }
     CHK(exact_set_hdr(c, swx::H_RC, 0));
     CHK(exact_set_hdr(c, swx::H_NNEW, 0));
     hipLaunchKernelGGL(k_exact_fame, dim3(1), dim3(64), 0, c->stream, exact_state(c), x);
@@ -3532,6 +3581,11 @@ int exact_fame(sw_ctx* c, int32_t* new_rounds, int cap, int* n_new) {
     HIPCHK(c, hipGetLastError());
     long long hdr[swx::H_WORDS];
     CHK(exact_read_hdr(c, hdr));
+    if (x.hist.voter) {
+        c->hist.count = hdr[swx::H_VCNT];
+        if (hdr[swx::H_VOVF] == 1) history_votes_lost(c, "the vote store reached its ceiling (SW_VOTE_STORE_MAX)");
+        else if (hdr[swx::H_VOVF]) history_votes_lost(c, "a decide_fame call ended in the reference's KeyError");
+    }
     if (hdr[swx::H_RC] != swx::X_OK)
         return fail(c, SW_EINVAL, "exact decide_fame: a voter strongly sees a member without a witness in the previous round, or a vote is missing (KeyError in the reference, swirld.py:253 / 260)");
     const int cnt = (int)hdr[swx::H_NNEW];
@@ -3567,6 +3621,7 @@ int exact_order(sw_ctx* c, std::vector<int32_t> rounds, int32_t* out_events, int
     swx::OrderScratch x{};
     x.queue = c->x_queue.p; x.visited = c->x_visited.p; x.fw = c->x_fw.p; x.sflag = c->x_sflag.p; x.times = c->x_times.p;
     x.tsort = c->x_tsort.p; x.white = c->x_white.p; x.items_ev = c->x_items_ev.p; x.items_ts = c->x_items_ts.p;
+    if (c->hist.on) x.items_rr = c->hist.d_items_rr.p;
     hipLaunchKernelGGL(k_exact_order, dim3(1), dim3(64), 0, c->stream, exact_state(c), x, (const int*)c->x_rounds.p, nr);
     c->ctr.kernel_launches++;
     HIPCHK(c, hipGetLastError());
@@ -3583,6 +3638,7 @@ int exact_order(sw_ctx* c, std::vector<int32_t> rounds, int32_t* out_events, int
         HIPCHK(c, hipMemcpyAsync(c->transactions.data() + at, c->x_items_ev.p, (size_t)produced * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
     }
+    if (c->hist.on) CHK(history_record(c, produced));
     if (n_out) *n_out = produced;
     if (produced > cap) return fail(c, SW_ERANGE, "find_order: out_events capacity %lld < %lld", (long long)cap, (long long)produced);
     if (out_events) memcpy(out_events, c->transactions.data() + at, (size_t)produced * sizeof(int32_t));
@@ -3597,6 +3653,15 @@ int exact_rewind(sw_ctx* c) {
     }
     if (c->x_Rcap) HIPCHK(c, hipMemsetAsync(c->x_wcnt.p, 0, (size_t)c->x_Rcap * sizeof(int32_t), c->stream));
     HIPCHK(c, hipMemsetAsync(c->x_hdr.p, 0, swx::H_WORDS * sizeof(long long), c->stream));
+    if (c->hist.on) {   // nothing is ordered, no vote has been cast: the store is empty and complete again
+        if (c->N) CHK(history_defaults(c, 0, c->N));
+        if (c->hist.slots) HIPCHK(c, hipMemsetAsync(c->hist.d_tab.p, 0xff, c->hist.slots * sizeof(int32_t), c->stream));
+        c->hist.count = 0;
+        c->hist.votes_ok = true;
+        c->hist.why = "";
+        history_knobs(c);
+        if (c->hist.cap > c->hist.ceiling) c->hist.cap = c->hist.ceiling;   // (the buffers stay; the kernel stops at `cap`)
+    }
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->x_fc_base = c->fc_seen;
     return SW_OK;
@@ -4669,6 +4734,7 @@ int sw_rewind(sw_ctx* c) {
     HIPCHK(c, hipStreamSynchronize(c->stream_aux));
     const size_t rows = (size_t)c->Rcap * c->npad;
     c->fame_calls.clear();
+    c->hist.table_calls = c->hist.table_divided = -1;
     c->votes.sched_calls = -1;
     c->votes_partial = false;
     c->eval_src = 0;
@@ -5269,6 +5335,278 @@ int sw_get_votes_stats(sw_ctx* c, int64_t* calls, int64_t* rows, int64_t* entrie
     return SW_OK;
 }
 
+// ---- the history of the exact path (exact_history.hip.h) ---------------------------------------------------
+}  // extern "C"
+namespace {
+
+xh::Store history_store(sw_ctx* c) {
+    auto& h = c->hist;
+    xh::Store s{};
+    s.voter = h.d_voter.p; s.cand = h.d_cand.p; s.value = h.d_value.p; s.tab = h.d_tab.p;
+    s.cap = h.cap; s.tmask = (unsigned)(h.slots - 1);
+    return s;
+}
+
+void history_votes_lost(sw_ctx* c, const char* why) {
+    c->hist.votes_ok = false;
+    c->hist.why = why;
+}
+
+// Room for `need` entries in all — at most the ceiling: what does not fit makes the kernel set the overflow word.  The log
+// keeps its entries (dgrow copies them), the index is emptied and rebuilt by k_votes_reindex, one thread per entry.
+int history_store_reserve(sw_ctx* c, int64_t need) {
+    auto& h = c->hist;
+    need = std::min(need, h.ceiling);
+    if (need <= h.cap && h.slots) return SW_OK;
+    int64_t nc = std::max<int64_t>(h.cap0, 1);
+    while (nc < need) nc *= 2;
+    nc = std::min(std::max(nc, h.cap), h.ceiling);
+    size_t slots = 2;
+    while (slots < 2 * (size_t)nc) slots *= 2;
+    const size_t keep = (size_t)h.count;
+    CHK(dgrow(c, h.d_voter, (size_t)nc, keep));
+    CHK(dgrow(c, h.d_cand, (size_t)nc, keep));
+    CHK(dgrow(c, h.d_value, (size_t)nc, keep));
+    CHK(dgrow(c, h.d_tab, slots, 0));
+    h.cap = nc;
+    h.slots = slots;
+    HIPCHK(c, hipMemsetAsync(h.d_tab.p, 0xff, slots * sizeof(int32_t), c->stream));
+    if (h.count) {
+        hipLaunchKernelGGL(xh::k_votes_reindex, dim3((unsigned)((h.count + xh::THREADS - 1) / xh::THREADS)), dim3(xh::THREADS), 0, c->stream, history_store(c), (long long)h.count);
+        c->ctr.kernel_launches++;
+        HIPCHK(c, hipGetLastError());
+    }
+    h.grows++;
+    return SW_OK;
+}
+
+int history_defaults(sw_ctx* c, int64_t first, int64_t K) {
+    if (!K) return SW_OK;
+    hipLaunchKernelGGL(xh::k_history_defaults, dim3((unsigned)((K + xh::THREADS - 1) / xh::THREADS)), dim3(xh::THREADS), 0, c->stream, (long long)first, (long long)K,
+                       c->d_rr.p, (xh::u64*)c->d_cts.p);
+    c->ctr.kernel_launches++;
+    HIPCHK(c, hipGetLastError());
+    return SW_OK;
+}
+
+// Behind a successful exact_order: the two values of its `produced` items into the per-event tables, the items behind the
+// device copy of the order.  (A call that failed returned before this and records nothing.)
+int history_record(sw_ctx* c, int64_t produced) {
+    if (!produced) return SW_OK;
+    const size_t at = (size_t)c->tx_len;
+    CHK(consensus_reserve(c, at + (size_t)produced));
+    hipLaunchKernelGGL(xh::k_history_record, dim3((unsigned)((produced + xh::THREADS - 1) / xh::THREADS)), dim3(xh::THREADS), 0, c->stream, (long long)produced,
+                       (const int*)c->x_items_ev.p, (const xh::u64*)c->x_items_ts.p, (const int*)c->hist.d_items_rr.p, c->d_rr.p, (xh::u64*)c->d_cts.p);
+    c->ctr.kernel_launches++;
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(c->d_tx.p + at, c->x_items_ev.p, (size_t)produced * sizeof(int32_t), hipMemcpyDeviceToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));   // (the next call may overwrite the items)
+    c->tx_len = (int64_t)at + produced;
+    c->cs_record_calls++;
+    c->cs_recorded += produced;
+    return SW_OK;
+}
+
+// The votes of the fast path — the table of sw_export_votes_device over every voter round decide_fame has seen — as entries
+// at the head of the (emptied) store, indexed.  The table's preconditions are the caller's business (votes_pre).
+int history_table_import(sw_ctx* c, int seen) {
+    auto& h = c->hist;
+    h.count = 0;
+    if (h.slots) HIPCHK(c, hipMemsetAsync(h.d_tab.p, 0xff, h.slots * sizeof(int32_t), c->stream));
+    if (seen <= 1) return SW_OK;
+    VotesCall v;
+    CHK(votes_schedule(c, v));
+    CHK(votes_plan(c, v, 0, seen));
+    int64_t rows = 0, entries = 0;
+    CHK(votes_count(c, v, &rows, &entries));
+    if (!rows) return SW_OK;
+    if (entries > h.ceiling) { history_votes_lost(c, "the vote store reached its ceiling (SW_VOTE_STORE_MAX)"); return SW_OK; }
+    const size_t k = (size_t)rows, nwo = (size_t)(c->n + 63) / 64;
+    Carve cv;
+    const size_t o_ex = cv.take(k * nwo * 8), o_val = cv.take(k * nwo * 8), o_rv = cv.take(k * 4), o_rc = cv.take(k * 4);
+    CHK(dgrow(c, c->votes.d_out, cv.off + 256, 0));
+    unsigned char* B = c->votes.d_out.p;
+    CHK(votes_write(c, v, vts::Out{(int*)(B + o_rv), (int*)(B + o_rc), (vts::u64*)(B + o_ex), (vts::u64*)(B + o_val)}));
+    CHK(history_store_reserve(c, entries));
+    CHK(dgrow(c, h.d_off, k + 1, 0));
+    const unsigned blocks = (unsigned)((rows + xh::THREADS - 1) / xh::THREADS);
+    const xh::TableIn in{(const int*)(B + o_rv), (const int*)(B + o_rc), (const xh::u64*)(B + o_ex), (const xh::u64*)(B + o_val), (int)nwo, c->d_wit.p, c->npad, c->n};
+    hipLaunchKernelGGL(xh::k_votes_row_counts, dim3(blocks), dim3(xh::THREADS), 0, c->stream, (long long)rows, in.exists, (int)nwo, h.d_off.p);
+    hipLaunchKernelGGL(xh::k_votes_offsets, dim3(1), dim3(xh::SCAN_THREADS), 0, c->stream, (long long)rows, h.d_off.p);
+    hipLaunchKernelGGL(xh::k_votes_expand, dim3(blocks), dim3(xh::THREADS), 0, c->stream, (long long)rows, in, (const long long*)h.d_off.p, 0ll, history_store(c));
+    hipLaunchKernelGGL(xh::k_votes_reindex, dim3((unsigned)((entries + xh::THREADS - 1) / xh::THREADS)), dim3(xh::THREADS), 0, c->stream, history_store(c), (long long)entries);
+    c->ctr.kernel_launches += 4;
+    HIPCHK(c, hipGetLastError());
+    h.count = entries;
+    return SW_OK;
+}
+
+// The end of exact_enter with history on.  Per-event tables: every event outside the fast path's ordered chain prefixes gets
+// the "not ordered" defaults, so that from now on the tables answer as they are.  Votes: taken over from the table when it is
+// current — nothing divided since the last decide_fame call, no partitioned commit; unavailable otherwise.
+int history_enter(sw_ctx* c) {
+    auto& h = c->hist;
+    CHK(consensus_reserve(c, (size_t)c->tx_len));
+    CHK(dgrow(c, c->d_cs_ordpos, c->npad, 0));
+    if (c->N) {
+        HIPCHK(c, hipMemcpyAsync(c->d_cs_ordpos.p, c->ord_pos.data(), (size_t)c->n * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+        hipLaunchKernelGGL(xh::k_history_normalise, dim3((unsigned)((c->N + xh::THREADS - 1) / xh::THREADS)), dim3(xh::THREADS), 0, c->stream, (long long)c->N,
+                           (const int*)c->d_seq.p, (const int*)c->d_cr.p, (const int*)c->d_cs_ordpos.p, c->d_rr.p, (xh::u64*)c->d_cts.p);
+        c->ctr.kernel_launches++;
+        HIPCHK(c, hipGetLastError());
+        HIPCHK(c, hipStreamSynchronize(c->stream));   // (ord_pos is pageable memory)
+    }
+    h.votes_ok = true;
+    h.why = "";
+    h.count = 0;
+    const int seen = c->fame_calls.empty() ? 0 : c->fame_calls.back().R;
+    if (c->votes_partial) history_votes_lost(c, "the context forked after sw_commit_fame (the fast path had no votes to hand over)");
+    else if (!c->fame_calls.empty() && (c->fame_calls.back().divided != c->divided || seen > c->Sw_rows || c->sw_dirty_from < seen))
+        history_votes_lost(c, "rounds were divided that decide_fame had not seen when the first fork arrived (the fast path's voter masks were not current)");
+    else {
+        CHK(history_table_import(c, seen));
+        h.imported += h.count;
+    }
+    h.table_calls = h.table_divided = -1;
+    CHK(exact_set_hdr(c, swx::H_VCNT, h.count));
+    return SW_OK;
+}
+
+// what the three readers of the store check, and — on a context that is still fork-free — the store filled from the table
+int history_votes_pre(sw_ctx* c, const char* what) {
+    if (c->poisoned) return fail(c, SW_EIO, "context unusable after an earlier device failure");
+    if (!c->hist.on) return fail(c, SW_ENOTSUP, "%s needs sw_set_exact_history(ctx, 1)", what);
+    HIPCHK(c, hipSetDevice(c->device));
+    if (!c->exact) {
+        const int seen = c->fame_calls.empty() ? 0 : c->fame_calls.back().R;
+        bool empty = true;
+        CHK(votes_pre(c, 0, seen, what, &empty));
+        // (the table is a function of the decide_fame calls so far: filled once per call schedule, not once per read; what the
+        // fill found — the entries, or that they do not fit under the ceiling — stands until the schedule moves on)
+        if (c->hist.table_calls != (int64_t)c->fame_calls.size() || c->hist.table_divided != c->divided) {
+            c->hist.table_calls = c->hist.table_divided = -1;
+            c->hist.votes_ok = true;
+            c->hist.why = "";
+            CHK(history_table_import(c, seen));
+            c->hist.table_calls = (int64_t)c->fame_calls.size();
+            c->hist.table_divided = c->divided;
+        }
+    }
+    if (!c->hist.votes_ok) return fail(c, SW_ENOTSUP, "%s: the votes are unavailable until sw_rewind / sw_reset: %s", what, c->hist.why);
+    return SW_OK;
+}
+
+}  // namespace
+extern "C" {
+
+int sw_set_exact_history(sw_ctx* c, int enable) {
+    if (!c) return SW_EINVAL;
+    if (enable != 0 && enable != 1) return fail(c, SW_EINVAL, "sw_set_exact_history: 0 (off) or 1 (on)");
+    if (c->N) return fail(c, SW_EINVAL, "sw_set_exact_history: only before the first event is appended (%lld stored)", (long long)c->N);
+    c->hist.on = enable != 0;
+    return SW_OK;
+}
+
+int sw_get_exact_history(sw_ctx* c, int* enabled, int* votes_available) {
+    if (!c) return SW_EINVAL;
+    if (enabled) *enabled = c->hist.on ? 1 : 0;
+    // fork-free: the table answers unless a partitioned commit left it incomplete, or its last fill (still current) found more
+    // entries than the ceiling admits
+    const bool filled = c->hist.table_calls == (int64_t)c->fame_calls.size() && c->hist.table_divided == c->divided;
+    if (votes_available) *votes_available = c->hist.on && (!c->exact ? !c->votes_partial && !(filled && !c->hist.votes_ok) : c->hist.votes_ok) ? 1 : 0;
+    return SW_OK;
+}
+
+int sw_get_votes_by_event(sw_ctx* c, int64_t K, const int32_t* voter, const int32_t* cand, int8_t* out) {
+    if (!c) return SW_EINVAL;
+    const char* what = "sw_get_votes_by_event";
+    if (K < 0 || (K > 0 && (!voter || !cand || !out))) return fail(c, SW_EINVAL, "%s: NULL arrays (K = %lld)", what, (long long)K);
+    CHK(history_votes_pre(c, what));
+    if (!K) return SW_OK;
+    auto& h = c->hist;
+    if (!h.count) { memset(out, 0xff, (size_t)K); return SW_OK; }
+    CHK(dgrow(c, h.d_q, (size_t)2 * K, 0));
+    CHK(dgrow(c, h.d_qout, (size_t)K, 0));
+    HIPCHK(c, hipMemcpyAsync(h.d_q.p, voter, (size_t)K * 4, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(h.d_q.p + K, cand, (size_t)K * 4, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(xh::k_votes_lookup, dim3((unsigned)((K + xh::THREADS - 1) / xh::THREADS)), dim3(xh::THREADS), 0, c->stream, history_store(c), (long long)c->N,
+                       (long long)K, (const int*)h.d_q.p, (const int*)(h.d_q.p + K), h.d_qout.p);
+    c->ctr.kernel_launches++;
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(out, h.d_qout.p, (size_t)K, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    h.lookups += K;
+    return SW_OK;
+}
+
+static int vote_entries_range(sw_ctx* c, const char* what, int64_t first, int64_t cap, const void* a, const void* b, const void* v, int64_t* n_total) {
+    if (c->poisoned) return fail(c, SW_EIO, "context unusable after an earlier device failure");
+    if (!n_total) return fail(c, SW_EINVAL, "%s: n_total is NULL", what);
+    *n_total = 0;
+    if (first < 0 || cap < 0 || (cap > 0 && (!a || !b || !v))) return fail(c, SW_EINVAL, "%s: NULL output arrays (capacity %lld) or a negative position", what, (long long)cap);
+    return SW_OK;
+}
+
+int sw_export_vote_entries_device(sw_ctx* c, int64_t first, int64_t cap_entries, int32_t* d_voter, int32_t* d_cand, int8_t* d_value, int64_t* n_total,
+                                  void* user_stream) {
+    if (!c) return SW_EINVAL;
+    const char* what = "sw_export_vote_entries_device";
+    int64_t k = 0;
+    CHK(vote_entries_range(c, what, first, cap_entries, d_voter, d_cand, d_value, n_total));
+    if (!c->hist.on) return fail(c, SW_ENOTSUP, "%s needs sw_set_exact_history(ctx, 1)", what);
+    CHK(device_args(c, what, {{d_voter, (size_t)cap_entries * 4, 4}, {d_cand, (size_t)cap_entries * 4, 4}, {d_value, (size_t)cap_entries, 1}}));
+    UserStream bracket;   // earlier readers of the output arrays
+    CHK(bracket.join(c, (hipStream_t)user_stream));
+    CHK(history_votes_pre(c, what));   // (fork-free: the table's count is the one synchronisation; exact: the host knows the count)
+    auto& h = c->hist;
+    *n_total = h.count;
+    k = std::max<int64_t>(0, h.count - first);
+    if (k > cap_entries) return fail(c, SW_ERANGE, "%s: %lld entries to export, capacity %lld (nothing written)", what, (long long)k, (long long)cap_entries);
+    if (k) {
+        HIPCHK(c, hipMemcpyAsync(d_voter, h.d_voter.p + first, (size_t)k * 4, hipMemcpyDeviceToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(d_cand, h.d_cand.p + first, (size_t)k * 4, hipMemcpyDeviceToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(d_value, h.d_value.p + first, (size_t)k, hipMemcpyDeviceToDevice, c->stream));
+    }
+    CHK(bracket.leave());
+    h.exported += k;
+    return SW_OK;
+}
+
+int sw_export_vote_entries(sw_ctx* c, int64_t first, int64_t cap_entries, int32_t* voter, int32_t* cand, int8_t* value, int64_t* n_total) {
+    if (!c) return SW_EINVAL;
+    const char* what = "sw_export_vote_entries";
+    int64_t k = 0;
+    CHK(vote_entries_range(c, what, first, cap_entries, voter, cand, value, n_total));
+    CHK(history_votes_pre(c, what));
+    auto& h = c->hist;
+    *n_total = h.count;
+    k = std::max<int64_t>(0, h.count - first);
+    if (k > cap_entries) return fail(c, SW_ERANGE, "%s: %lld entries to export, capacity %lld (nothing written)", what, (long long)k, (long long)cap_entries);
+    if (k) {
+        HIPCHK(c, hipMemcpyAsync(voter, h.d_voter.p + first, (size_t)k * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(cand, h.d_cand.p + first, (size_t)k * 4, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(value, h.d_value.p + first, (size_t)k, hipMemcpyDeviceToHost, c->stream));
+    }
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    h.exported += k;
+    return SW_OK;
+}
+
+int sw_get_vote_store_stats(sw_ctx* c, int64_t* entries, int64_t* capacity, int64_t* bytes, int64_t* grows, int64_t* imported, int64_t* lookups,
+                            int64_t* exported) {
+    if (!c) return SW_EINVAL;
+    if (!c->hist.on) return fail(c, SW_ENOTSUP, "sw_get_vote_store_stats needs sw_set_exact_history(ctx, 1)");
+    const auto& h = c->hist;
+    if (entries) *entries = h.count;
+    if (capacity) *capacity = h.cap;
+    if (bytes) *bytes = (int64_t)(h.d_voter.cap * 4 + h.d_cand.cap * 4 + h.d_value.cap + h.d_tab.cap * 4);
+    if (grows) *grows = h.grows;
+    if (imported) *imported = h.imported;
+    if (lookups) *lookups = h.lookups;
+    if (exported) *exported = h.exported;
+    return SW_OK;
+}
+
 int sw_get_known_heights(sw_ctx* c, int64_t head_event, int32_t* out) {
     if (!c || !out) return SW_EINVAL;
     if (head_event < c->first_resident || head_event >= c->divided) return fail(c, SW_ERANGE, "head %lld is not a divided, resident event", (long long)head_event);
@@ -5540,7 +5878,7 @@ namespace {
 
 int consensus_pre(sw_ctx* c, const char* what) {
     if (c->poisoned) return fail(c, SW_EIO, "context unusable after an earlier device failure");
-    if (c->exact) return fail(c, SW_ENOTSUP, "%s is not available on the exact (forked-hashgraph) path", what);
+    if (c->exact && !c->hist.on) return fail(c, SW_ENOTSUP, "%s is not available on the exact (forked-hashgraph) path", what);
     return SW_OK;
 }
 
@@ -5551,6 +5889,13 @@ int consensus_events(sw_ctx* c, const char* what, int64_t first, int64_t K, int3
         return fail(c, SW_ERANGE, "%s: range [%lld, %lld) outside [0, %lld)", what, (long long)first, (long long)(first + K), (long long)c->N);
     if (!K || (!rr_out && !cts_out)) return SW_OK;
     HIPCHK(c, hipSetDevice(c->device));
+    if (c->exact) {
+        // (history on) the tables hold -1 / the quiet NaN for every event that is not ordered: they are copied as they are
+        if (rr_out) HIPCHK(c, hipMemcpyAsync(rr_out, c->d_rr.p + first, (size_t)K * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+        if (cts_out) HIPCHK(c, hipMemcpyAsync(cts_out, c->d_cts.p + first, (size_t)K * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        return SW_OK;
+    }
     const int np = c->npad;
     Stage st;
     const size_t o_rr = st.out_opt(rr_out, (size_t)K * 4), o_cts = st.out_opt(cts_out, (size_t)K * 8);

@@ -579,7 +579,11 @@ class Hashgraph:
 
     def votes_triples(self, rv0=1, rv1=None):
         """export_votes expanded to an int64 [K, 3] array of (y, x, v): voter, candidate (dense indices) and the vote, in row
-        order, candidates of a row by member index."""
+        order, candidates of a row by member index.  On the exact path with exact_history on: every entry of the store
+        (vote_entries(); rv0 and rv1 are not looked at — voters are no longer named by rounds)."""
+        if self.exact_history and self.exact:
+            y, x, v = self.vote_entries()
+            return np.stack([y, x, v], axis=1).astype(np.int64)
         row_voter, row_cand, exists, value = self.export_votes(rv0, rv1)
         rows = len(row_voter)
         bits = lambda w: np.unpackbits(np.ascontiguousarray(w.astype("<u8")).view(np.uint8).reshape(rows, -1), axis=1,  # noqa: E731
@@ -1277,6 +1281,64 @@ class Hashgraph:
         v = C.c_int(0)
         self._chk(self._L.sw_get_exact(self._h, C.byref(v)))
         return bool(v.value)
+
+    # ---- the history of the exact path (csrc/exact_history.hip.h; include/swirld_hip.h) ----
+    def set_exact_history(self, enable=True):
+        """Before the first append: keep round received, consensus time, the ordered stream and Node.votes (keyed by
+        event) once a forked event has moved the context to the exact path.  Off by default: the vote history is the
+        reference's unbounded dict."""
+        self._chk(self._L.sw_set_exact_history(self._h, 1 if enable else 0))
+
+    @property
+    def exact_history(self):
+        v = C.c_int(0)
+        self._chk(self._L.sw_get_exact_history(self._h, C.byref(v), None))
+        return bool(v.value)
+
+    @property
+    def votes_available(self):
+        """exact_history is on and the vote store is complete (not over its ceiling, no KeyError, handed over by the fast path)."""
+        v = C.c_int(0)
+        self._chk(self._L.sw_get_exact_history(self._h, None, C.byref(v)))
+        return bool(v.value)
+
+    def votes_by_event(self, y, x):
+        """Node.votes[y][x] for dense event indices (scalars or equally long arrays): 0 / 1, -1 = no entry."""
+        ya, xa = np.ascontiguousarray(np.atleast_1d(y), np.int32), np.ascontiguousarray(np.atleast_1d(x), np.int32)
+        if ya.shape != xa.shape:
+            raise ValueError("voter and candidate arrays differ in length")
+        out = np.empty(len(ya), np.int8)
+        self._chk(self._L.sw_get_votes_by_event(self._h, len(ya), _p(ya), _p(xa), _p(out)))
+        return int(out[0]) if np.ndim(y) == 0 and np.ndim(x) == 0 else out
+
+    def vote_entries(self, first=0):
+        """Every entry of Node.votes from position `first` of the store on as (voter, candidate, value) arrays of dense
+        event indices and 0 / 1, in the store's order (entries of the fast path first, then first insertion)."""
+        n = C.c_int64()
+        rc = self._L.sw_export_vote_entries(self._h, int(first), 0, None, None, None, C.byref(n))
+        if not (rc == -34 and n.value > first):
+            self._chk(rc)
+        K = max(int(n.value) - int(first), 0)
+        out = (np.empty(K, np.int32), np.empty(K, np.int32), np.empty(K, np.int8))
+        if K:
+            self._chk(self._L.sw_export_vote_entries(self._h, int(first), K, *[_p(a) for a in out], C.byref(n)))
+        return out
+
+    def vote_entries_device(self, first, cap_entries, voter=None, cand=None, value=None, stream=0):
+        """vote_entries written to DEVICE arrays (int32, int32, int8) of `cap_entries` entries; `stream` is made to wait for
+        them.  Too small a capacity raises SwirldHipError with code -34 and writes nothing (cap_entries = 0 with no arrays:
+        the size query, which does not raise).  Returns the number of entries in the store."""
+        a = [C.c_void_p(q) if q else None for q in (_dev_ptr(t)[0] for t in (voter, cand, value))]
+        n = C.c_int64()
+        rc = self._L.sw_export_vote_entries_device(self._h, int(first), int(cap_entries), *a, C.byref(n), C.c_void_p(int(stream)))
+        if not (rc == -34 and int(cap_entries) == 0 and n.value > first):
+            self._chk(rc)
+        return int(n.value)
+
+    def vote_store_stats(self):
+        v = [C.c_int64() for _ in range(7)]
+        self._chk(self._L.sw_get_vote_store_stats(self._h, *[C.byref(t) for t in v]))
+        return dict(zip(("entries", "capacity", "bytes", "grows", "imported", "lookups", "exported"), (int(t.value) for t in v)))
 
     def set_window(self, enable=True, chunk_mb=0, lapse_events=0):
         """Windowed can_see table (before the first append): rows no later call can read are evicted

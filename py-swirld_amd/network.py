@@ -11,8 +11,10 @@ from .engine import Hashgraph
 
 
 class DeviceNetwork:
-    def __init__(self, seeds, stake=None, device=0, event_class=("swirld", "Event"), clock=None):
-        """seeds: one 32-byte Ed25519 seed per node, in member order.  clock: the roots' timestamps (default time.time)."""
+    def __init__(self, seeds, stake=None, device=0, event_class=("swirld", "Event"), clock=None, exact_history=False):
+        """seeds: one 32-byte Ed25519 seed per node, in member order.  clock: the roots' timestamps (default time.time).
+        exact_history: every context keeps round received, consensus time and the votes (by event) once it has stored a
+        forked event (Hashgraph.set_exact_history); round_received(i), consensus_time(i) and votes(i) then go on answering."""
         from time import time
         clock = clock or time
         self.seeds = [bytes(s) for s in seeds]
@@ -24,6 +26,8 @@ class DeviceNetwork:
         self.results = []        # the TurnResult of every turn, in order
         for i in range(self.n):
             h = Hashgraph(self.n, stake, device=device)
+            if exact_history:
+                h.set_exact_history(True)
             h.set_member_keys(self.pks)
             h.set_event_class(*event_class)
             h.set_signing_seeds([i], [self.seeds[i]])

@@ -198,8 +198,17 @@ class _VoterVotes(Mapping):
                 raise VotesUnavailable(str(exc)) from None
             raise
 
+    def _entries(self):
+        """exact_history on a context that stored a fork: this voter's {candidate index -> bool} from the store."""
+        nd = self._n
+        return nd._vote_entries().get(nd._index[self._y], {})
+
     def __getitem__(self, x):
         nd = self._n
+        if nd._votes_by_event():
+            if x not in nd._index:
+                raise KeyError(x)
+            return self._entries()[nd._index[x]]   # (KeyError: no entry)
         (rv, mv), (rc, mc) = self._slot(self._y), self._slot(x)
         wit = nd._witness_table()
         if wit[rv, mv] != nd._index[self._y] or wit[rc, mc] != nd._index[x]:
@@ -211,6 +220,9 @@ class _VoterVotes(Mapping):
 
     def __iter__(self):
         nd = self._n
+        if nd._votes_by_event():
+            yield from (nd._ids[x] for x in self._entries())
+            return
         rv, mv = self._slot(self._y)
         wit = nd._witness_table()
         if not hasattr(nd._dev, "export_votes"):   # a backend without the bulk export: entry by entry
@@ -244,7 +256,7 @@ class _VotesView(Mapping):
         self._n = node
 
     def _check(self):
-        if self._n._dev.exact:
+        if self._n._dev.exact and not self._n.exact_history:
             raise VotesUnavailable("votes are not kept once a forked event was stored (exact path)")
 
     def __getitem__(self, y):
@@ -256,6 +268,9 @@ class _VotesView(Mapping):
     def __iter__(self):
         self._check()
         nd = self._n
+        if nd._votes_by_event():   # the voters of the store, in its order (with forks a voter may have left the witness table)
+            yield from (nd._ids[y] for y in nd._vote_entries())
+            return
         wit = nd._witness_table()
         for r in range(1, wit.shape[0]):
             for m in np.argsort(np.where(wit[r] >= 0, wit[r], np.iinfo(np.int32).max), kind="stable"):
@@ -310,6 +325,14 @@ class Node:
     # arrays take _batch_validate_plain's pack + validate and ingest_payload, and Event objects are built for the stored
     # events only.  Any other reply is unpickled as before.
     device_wire = False
+    # What the reference keeps on a forked hashgraph beyond the order, kept here too (Hashgraph.set_exact_history,
+    # csrc/exact_history.hip.h).  False: once this node has stored a fork, round_received / consensus_time raise
+    # NotImplementedError, ordered_data() fails and votes raises VotesUnavailable.  True: the context is created with the
+    # history; the three keep working after a stored fork, votes is then served by event from the context's store —
+    # votes[y][x], `in`, iteration and len, voters and candidates in the store's order (not the reference's dict order) —
+    # and VotesUnavailable is raised only when the store says so (its ceiling, a KeyError, no hand-over from the fast path).
+    # The store is the reference's unbounded dict in device memory: a deployment opts in.
+    exact_history = False
 
     def __init__(self, kp, network, n_nodes, stake, device=0, accept_forks=True):
         self.pk, self.sk = kp
@@ -360,6 +383,8 @@ class Node:
         self._divided = 0
         self._device = device
         self._dev = Hashgraph(n_nodes, [stake[pk] for pk in self._members], coin_period=C, device=device)
+        if self.exact_history:
+            self._dev.set_exact_history(True)
         self._dev.set_forks(self.accept_forks)
         self._round_cache = np.zeros(0, np.int32)
         self._wit_cache = None
@@ -923,7 +948,7 @@ class Node:
     def _consensus_values(self):
         """(round received, consensus time) by position of Node.transactions; the positions added since the last look
         are fetched in one range of events."""
-        if self._dev.exact:
+        if self._dev.exact and not self.exact_history:
             try:
                 self._dev.round_received(0, 0)
             except SwirldHipError as exc:
@@ -936,6 +961,26 @@ class Node:
             rr, ct = self._dev.round_received(lo, hi - lo), self._dev.consensus_time(lo, hi - lo)
             self._cons_cache = (np.concatenate([self._cons_cache[0], rr[ev - lo]]), np.concatenate([self._cons_cache[1], ct[ev - lo]]))
         return self._cons_cache
+
+    def _votes_by_event(self):
+        return self.exact_history and self._dev.exact
+
+    def _vote_entries(self):
+        """exact_history on a context that stored a fork: {voter index -> {candidate index -> bool}} of the whole store
+        (Hashgraph.vote_entries()), kept until the next divide_rounds or decide_fame."""
+        t = self._votes_cache.get("entries")
+        if t is None:
+            try:
+                y, x, v = self._dev.vote_entries()
+            except SwirldHipError as exc:
+                if exc.code == -95:
+                    raise VotesUnavailable(str(exc)) from None
+                raise
+            t = {}
+            for a, b, c in zip(y.tolist(), x.tolist(), v.tolist()):
+                t.setdefault(a, {})[b] = bool(c)
+            self._votes_cache["entries"] = t
+        return t
 
     def _votes_round(self, rv):
         """The votes table of voter round rv (Hashgraph.export_votes(rv, rv + 1)), kept until the next divide_rounds or
