@@ -24,9 +24,10 @@ def famous_table(wit, famous_by_event):
     return np.where(wit >= 0, np.asarray(famous_by_event)[np.maximum(wit, 0)], -1).astype(np.int8)
 
 
-def consensus_values(events, round_seq, L, wit, fam, cr, sp, ht, t, stake):
+def consensus_values(events, round_seq, L, wit, fam, cr, sp, ht, t, stake, sample_lists=None):
     """(round_received, consensus_time) of `events` (dense indices, any order, no repeats): int32 with -1 and float64 with
-    NaN where the event is not ordered by the rounds of `round_seq`."""
+    NaN where the event is not ordered by the rounds of `round_seq`.  `sample_lists` (a dict): filled with the sorted sample
+    list of every ordered event, by event index."""
     events = np.asarray(events, np.int64)
     L, cr, sp, ht, t = np.asarray(L), np.asarray(cr), np.asarray(sp), np.asarray(ht), np.asarray(t, np.float64)
     st = np.asarray(stake, np.int64)
@@ -64,6 +65,8 @@ def consensus_values(events, round_seq, L, wit, fam, cr, sp, ht, t, stake):
             if len(times) == 1:
                 raise IndexError("event %d is seen by a single famous witness (swirld.py:305)" % events[p])
             rr[p] = r
+            if sample_lists is not None:
+                sample_lists[int(events[p])] = times
             cts[p] = .5 * (times[len(times) // 2] + times[(len(times) + 1) // 2])
     return rr, cts
 
