@@ -969,6 +969,12 @@ int sw_debug_clocks(sw_ctx* ctx, unsigned long long* out, int64_t cap_words);
 /* Diagnostics: with SW_DEBUG_CLOCKS=3 every workgroup of the two round-loop kernels stamps the time it was done: copies up
  * to cap_words of the [4096 iterations][2 kernels][2048 workgroups] table.  profiles/block_ends.py reads it. */
 int sw_debug_block_clocks(sw_ctx* ctx, unsigned long long* out, int64_t cap_words);
+/* Diagnostics (no context: the counts are the process's): what the library's contexts and calls hold right now — bytes of
+ * device memory, bytes of pinned host memory, events, streams.  Any pointer may be NULL.  After the last sw_destroy every
+ * count is back at what it was before the first sw_create: a test sees a leak without asking the device how much memory
+ * other processes have left.  Not counted: the physical chunks of the windowed can_see table (sw_set_window), which are
+ * mapped and released apart from everything else. */
+int sw_debug_live_resources(int64_t* device_bytes, int64_t* pinned_bytes, int64_t* events, int64_t* streams);
 
 /* Measurement utility (no reference counterpart): forget all voting state (rounds,
  * witnesses, fame, consensus, order) as if divide_rounds had never been called; the

@@ -20,6 +20,7 @@
 
 #include "../../include/swirld_hip.h"
 #include "entry_plan.h"
+#include "owned.h"
 #include "kernels.hip.h"
 #define SW_PROV_ROWS 16   // sub-batches of one divide_rounds call that can be swept in chunks
 #define SW_RANGE_SLOTS 16 // event ranges swept by sw_cansee_range between two rewinds
@@ -42,34 +43,29 @@ namespace {
 
 std::string g_create_error;
 
-template <class T>
-struct DBuf {
-    T* p = nullptr;
-    size_t cap = 0;  // elements
-};
+using owned::DBuf;
+using owned::Event;
+using owned::Pinned;
+using owned::Stream;
 
 // growable int32 array in pinned host memory: the ordered events (Node.transactions) — device copies land in it directly
 struct PinnedVec {
-    int32_t* p = nullptr;
-    size_t n = 0, cap = 0;
+    Pinned<int32_t> buf;
+    size_t n = 0;
     size_t size() const { return n; }
-    int32_t* data() { return p; }
-    int32_t& operator[](size_t i) { return p[i]; }
+    int32_t* data() { return buf.p; }
+    int32_t& operator[](size_t i) { return buf.p[i]; }
     void clear() { n = 0; }
     bool resize(size_t m) {   // (only while nothing is in flight into the array)
-        if (m > cap) {
-            const size_t nc = std::max(m, cap + cap / 2 + 4096);
-            int32_t* q = nullptr;
-            if (hipHostMalloc((void**)&q, nc * sizeof(int32_t), hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); return false; }
-            if (n) memcpy(q, p, n * sizeof(int32_t));
-            if (p) (void)hipHostFree(p);
-            p = q;
-            cap = nc;
+        if (m > buf.cap) {
+            Pinned<int32_t> q;
+            if (!q.reserve(std::max(m, buf.cap + buf.cap / 2 + 4096))) return false;
+            if (n) memcpy(q.p, buf.p, n * sizeof(int32_t));
+            buf = std::move(q);
         }
         n = m;
         return true;
     }
-    void release() { if (p) (void)hipHostFree(p); p = nullptr; n = cap = 0; }
 };
 
 }  // namespace
@@ -103,12 +99,20 @@ struct SplitGroup {
 };
 
 struct sw_ctx {
+    // Every stream, event, device buffer and pinned buffer below is a member of an owning type (owned.h): ~sw_ctx gives them
+    // back, in reverse order of declaration — so the streams come first and go last.  sw_destroy has drained the device.
+    Stream stream;
+    Stream stream_cs;    // can_see sweeps run here, ahead of the round loop
+    Stream stream_aux;   // per-sub-batch finalize + voter masks run here, behind the round loop
+    Stream stream_io;    // payload (timestamps, signatures) uploads of bulk appends
+    Stream stream_ord;   // bulk find_order: the samples of group g run here beside the walk of group g + 1 ...
+    Stream stream_srt[2];   // ... and its sort (one workgroup per round: ~0.2 ms whatever the number of rounds) and read-back here, groups alternating
     int n = 0, nw = 0, npad = 0, coin_period = 6, device = 0;
     SplitGroup* split = nullptr;   // linked with other contexts (sw_split_link)
     int split_part = 0;
     long long split_iter = 0;      // iterations of the round loop enqueued since the link
     bool split_failed = false;     // a meeting of the parts failed (a part gave up): the call reports it
-    SplitDst* d_split = nullptr;   // device copies of the SplitDst the split kernels read: [0] this part's (linked), [q] part q's (SW_SPLIT_EMULATE)
+    DBuf<SplitDst> d_split;        // device copies of the SplitDst the split kernels read: [0] this part's (linked), [q] part q's (SW_SPLIT_EMULATE)
     SplitDst split_up[SW_MAX_PARTS] = {};   // ... and what was uploaded last
     int split_saved[4] = {0, 0, 0, 0};   // tally choice of the context before the link pinned the one-wave-per-slot tally (restored by the unlink)
     int split_emulate = 0;         // SW_SPLIT_EMULATE (measurement): this many parts played by this one context, one behind the other
@@ -149,11 +153,8 @@ struct sw_ctx {
     bool unit_stake = true;
     uint32_t tot = 0;
     std::vector<uint32_t> stake_h;
-    hipStream_t stream = nullptr;
-    hipStream_t stream_cs = nullptr;   // can_see sweeps run here, ahead of the round loop
-    hipStream_t stream_aux = nullptr;  // per-sub-batch finalize + voter masks run here, behind the round loop
     FameCounters fc_seen{};            // device fame counters already added to ctr
-    std::vector<hipEvent_t> cs_events;
+    std::vector<Event> cs_events;
     int pipe = 5;                       // sub-batches per divide_rounds call behind the short first one (pipelining depth)
     std::string err;
 
@@ -164,16 +165,13 @@ struct sw_ctx {
     std::vector<int32_t> nev;       // events per member so far (next chain position)
     bool pool_h_valid = true;       // chain_ev_h mirrors the device pool (bulk appends invalidate it)
     bool poisoned = false;          // a HIP failure left the context half-updated: every later call fails
-    hipStream_t stream_io = nullptr;  // payload (timestamps, signatures) uploads of bulk appends
-    hipEvent_t ev_payload = nullptr;  // ... and their completion (find_order / coin bits wait for it)
+    Event ev_payload;               // the payload uploads of bulk appends (stream_io) are complete (find_order / coin bits wait for it)
     bool payload_pending = false;
     std::vector<int32_t> seq_h;     // chain position of every event (host mirror: small appends pack creator(op) | seq(op))
-    SmallRec* h_small = nullptr;    // pinned staging of small appends (one packed record per event)
-    size_t h_small_cap = 0;
-    hipEvent_t ev_small = nullptr;  // ... and the completion of its last upload
+    Pinned<SmallRec> h_small;       // pinned staging of small appends (one packed record per event)
+    Event ev_small;                 // ... and the completion of its last upload
     bool small_pending = false;
-    char* h_pin = nullptr;          // pinned staging of bulk appends
-    size_t h_pin_cap = 0;
+    Pinned<char> h_pin;             // pinned staging of bulk appends
     int max_height = 0;
     int64_t N = 0, cap = 0, divided = 0;
     // device-side ingest (sw_append_events_device; ingest.hip.h)
@@ -181,7 +179,7 @@ struct sw_ctx {
     DBuf<int32_t> d_ing_hist;     // [tiles][npad] creators per tile, then chain position of each member at the head of each tile
     DBuf<int32_t> d_ht_stat;      // k_ingest_heights: [error, largest height, {min, max} per 4096-event block of the batch]
     std::vector<int32_t> ing_stage;   // host staging of d_ing_tab (persistent: uploaded and read back without a copy of a local)
-    hipEvent_t ev_ht = nullptr;   // the heights kernel of the last device append (it runs on stream_io, behind the call)
+    Event ev_ht;                  // the heights kernel of the last device append (it runs on stream_io, behind the call)
     bool ht_pending = false;      // ... has not been waited for yet: d_ht, max_height, blk_hmin / blk_hmax lack its events
     int64_t ht_first = 0, ht_K = 0;   // ... which are these
     int64_t ht_dev_upto = 0;      // events below this index and beyond the host mirror (sp.size()) have their height in d_ht
@@ -194,7 +192,7 @@ struct sw_ctx {
     DBuf<int32_t> d_idflag;       // [4] duplicate flag of an insert
     DBuf<unsigned char> d_pl;     // scratch of a payload call
     DBuf<unsigned char> d_pl_in;  // ... and the staged arrays of the host-array forms
-    int32_t* h_plcnt = nullptr;   // pinned: per-wave counts of one batch of waves
+    Pinned<int32_t> h_plcnt;      // pinned: per-wave counts of one batch of waves
     int64_t pl_calls = 0, pl_waves = 0, pl_accepted = 0, pl_rebuilds = 0;   // sw_get_payload_stats (waves, accepted: the last call's)
     double pl_ms[4] = {0, 0, 0, 0};   // ... host time of its phases under sw_set_profiling: resolve, waves, sort + gather, append + commit
     // answering a sync on the device (sw_export_payload[_device], sw_sync_pull; gossip.hip.h)
@@ -250,7 +248,7 @@ struct sw_ctx {
     DBuf<unsigned char> d_pk;     // tile sums of the scan
     DBuf<unsigned char> d_pk_in;  // the staged arrays and streams of the host-array form
     DBuf<unsigned char> d_pk_out; // sw_sync_pull_validated: offsets, streams, flags, verdicts, the count
-    int32_t* h_pkcnt = nullptr;   // pinned: the count of valid events of sw_sync_pull_validated
+    Pinned<int32_t> h_pkcnt;      // pinned: the count of valid events of sw_sync_pull_validated
     int64_t pk_calls = 0, pk_events = 0, pk_bytes = 0;   // sw_get_pack_stats
     double pk_ms[2] = {0, 0};     // ... host time under sw_set_profiling: lengths and scan, the two writers
     // the data of events (sw_set_event_data[_device], sw_gather_event_data[_device], sw_ingest_payload_data[_device],
@@ -295,7 +293,7 @@ struct sw_ctx {
     DBuf<double> d_t;
     DBuf<u64> d_S;
     DBuf<int32_t> d_finlist;   // events k_finalize_check found without a round from the band pass (one entry per event at most)
-    unsigned* d_fin = nullptr; // [0] length of that list for the launch in flight, [2..3] running total (u64)
+    DBuf<unsigned> d_fin;      // [0] length of that list for the launch in flight, [2..3] running total (u64)
     DBuf<int32_t> d_chain_start;  // npad: offset of each member's segment in the chain pool
     DBuf<int32_t> d_chain_cnt;    // npad: events per member (segments have slack: geometric growth)
     DBuf<int4> d_cdesc;           // pool-indexed chain descriptors of the dataflow can_see sweep (same indexing as chain_ev)
@@ -305,7 +303,6 @@ struct sw_ctx {
     // {w_0, a_0, w_1, a_1, ..., end, end}, the halo rows' scratch table, provisional-entry counters (inside d_rb)
     DBuf<int32_t> d_cbnd;
     DBuf<long long> d_ccuts;
-    unsigned* d_prov = nullptr;   // [SW_PROV_ROWS][SW_MAX_CHUNKS] provisional entries per chunk, then [SW_PROV_ROWS] repaired entries
     int chunks = 4;               // SW_CHUNKS: chunks swept concurrently per sub-batch (1 = the unchunked k_cansee_flow)
     int chunk_cfg = 0;            // SW_CHUNK_CFG: 0 = 4 columns per lane, FIFO 8, ring 8; 1 = 2 columns, 8 / 16; 2 = 4 columns, 4 / 8
     int64_t halo = 0;             // SW_HALO: events recomputed in front of a chunk (default 32 x npad: ~2.4x the age of a row's oldest entry at uniform gossip)
@@ -322,8 +319,8 @@ struct sw_ctx {
     DBuf<int32_t> d_rbnd;
     DBuf<long long> d_rcuts;
     std::vector<long long> rcuts_stage;
-    unsigned* d_rprov = nullptr;      // [SW_RANGE_SLOTS][SW_MAX_CHUNKS + 1]: provisional entries per chunk, repaired entries
-    hipEvent_t ev_user = nullptr;
+    DBuf<unsigned> d_rprov;           // [SW_RANGE_SLOTS][SW_MAX_CHUNKS + 1]: provisional entries per chunk, repaired entries
+    Event ev_user;                    // between a caller's stream and ours (UserStream), and between two contexts: made on first use
     std::vector<int32_t> chain_cap;   // per member: capacity of its segment
     int64_t pool_used = 0;             // ints of the chain pool handed out
     DBuf<int32_t> d_chain_len;    // [3][npad]: events per member visible to the running round loop, by iteration parity (the gated
@@ -354,14 +351,12 @@ struct sw_ctx {
     bool debug_timing = false;   // SW_DEBUG_TIMING=1
     double stage_us[8] = {0};    // sw_divide_rounds host stages: sweeps enqueued, loop set-up, round loop, front rows, aux launches, final syncs
     int64_t stage_calls = 0;
-    unsigned long long* d_dbg = nullptr;  // SW_DEBUG_CLOCKS=1: phase stamps of the round-loop kernels
-    unsigned long long* d_dbg_blk = nullptr;   // SW_DEBUG_CLOCKS=3: end time of every workgroup of the loop kernels, per iteration
+    DBuf<unsigned long long> d_dbg;       // SW_DEBUG_CLOCKS=1: phase stamps of the round-loop kernels
+    DBuf<unsigned long long> d_dbg_blk;        // SW_DEBUG_CLOCKS=3: end time of every workgroup of the loop kernels, per iteration
     int64_t dbg_iter_base = 0;            // round_iterations at the last rewind: the phase stamps are indexed by the iterations since
     int dbg_minor = 1;                    // SW_DEBUG_CLOCKS=2: only the entry / band start / end stamps (the others drain the wave)
-    struct { int32_t* p = nullptr; } d_front;   // inside d_rb
-    int32_t* d_treecnt = nullptr;                // inside d_rb: tallies evaluated per member in the running loop (k_tally_tree)
     DBuf<unsigned char> d_small;   // device copy of the packed records of the current small append
-    hipEvent_t ev_aux_done = nullptr, ev_cs_done = nullptr, ev_main_mark = nullptr, ev_bounds = nullptr, ev_loop_done = nullptr;
+    Event ev_aux_done, ev_cs_done, ev_main_mark, ev_bounds, ev_loop_done;   // (ev_bounds: made on first use)
     std::vector<int32_t> divided_cnt;   // per member: events already divided (chain positions below `divided`)
     std::vector<int32_t> bounds_stage;  // host staging of the cut table (persistent: uploaded without a sync)
     DBuf<int32_t> d_evalround, d_evalpos, d_lo_r, d_cur, d_unres, d_lo_next, d_pos_next, d_farslot, d_force, d_cand, d_gallop;
@@ -373,18 +368,22 @@ struct sw_ctx {
     DBuf<u64> d_found64;   // [2][npad] {event << 32 | slot << 26 | look-ahead} of the members' first passing candidates (LoopBufs::found64)
     // one device block read back with ONE copy per round-loop shot: loop state (x2), sweep error flag, per-member
     // front rounds; and its pinned host mirror
-    unsigned char* d_rb = nullptr;
-    unsigned char* h_rb = nullptr;        // the read-back slot that was read last (one of h_rb_all's)
-    unsigned char* h_rb_all = nullptr;    // SW_PROV_ROWS pinned slots: the loops of a call's sub-batches are read back one behind the other
-    std::vector<hipEvent_t> rb_events;   // per slot: read-back complete
+    DBuf<unsigned char> d_rb;
+    Pinned<unsigned char> h_rb_all;       // SW_PROV_ROWS pinned slots: the loops of a call's sub-batches are read back one behind the other
+    std::vector<Event> rb_events;        // per slot: read-back complete
+    // pointers INTO another allocation (nothing to free): the pieces of d_rb, the header of d_newc, a slot of h_rb_all
+    RState* d_state = nullptr;
+    int* d_flow_err = nullptr;            // set by k_cansee_flow when a polling loop gives up (protocol bug)
+    struct { int32_t* p = nullptr; } d_front;   // the members' front rounds
+    int32_t* d_treecnt = nullptr;         // tallies evaluated per member in the running loop (k_tally_tree)
+    unsigned* d_prov = nullptr;           // [SW_PROV_ROWS][SW_MAX_CHUNKS] provisional entries per chunk of the chunk-parallel sweep, then [SW_PROV_ROWS] repaired entries
+    FameCounters* d_fc = nullptr;         // header of d_newc: the fame counters travel with the new_c flags in one copy
+    unsigned char* h_rb = nullptr;        // the read-back slot that was read last
     int gate_lag = 0, gate_step = 1;   // SW_GATE_LAG / SW_GATE_STEP (test hook): the gated loop's stages published by the host, `gate_step` more every `gate_lag` iterations (0: by the sweep stream)
     int gated = 1;   // SW_GATED: one round loop per large call, gated on the device by the sweep's progress (0: one loop per sub-batch)
     int shot_pct = 100, shot_extra = 2;   // SW_SHOT_PCT / SW_SHOT_EXTRA: a loop's first shot = predicted iterations x pct / 100 + extra (tests: 50 makes every loop top up)
     size_t rb_bytes = 0;
-    RState* d_state = nullptr;
-    FameCounters* d_fc = nullptr;   // header of d_newc: the fame counters travel with the new_c flags in one copy
-    unsigned char* h_fame = nullptr;  // pinned: [FameCounters][newc flags]
-    size_t h_fame_cap = 0;
+    Pinned<unsigned char> h_fame;     // pinned: [FameCounters][newc flags]
     std::vector<int32_t> front;       // per member: max r with lo[r][c] finite (-1 none); the device keeps it (d_front), the host mirror follows
     std::vector<int32_t> front_dev;   // read-back buffer of d_front
     std::vector<int32_t> lo0_h;       // host copy of lo[0][.] (chain starts)
@@ -440,7 +439,7 @@ struct sw_ctx {
     bool profiling = false;
     sw_timings tm{};
     sw_counters ctr{};
-    std::vector<hipEvent_t> ev_pool;
+    std::vector<Event> ev_pool;
     size_t ev_used = 0;
     // find_order state (swirld.py:53-57): ordered events are a prefix of every member's chain
     PinnedVec transactions;
@@ -453,13 +452,9 @@ struct sw_ctx {
     // ([OrderInfo][new ordered prefixes: npad][acc_off: entries + 1]), per-group tables of the bulk kernels
     DBuf<int32_t> d_ord_rounds, d_fwm, d_ordat, d_rowsum, d_grp;
     DBuf<long long> d_oblk;
-    char* h_ord = nullptr;           // pinned staging of a find_order call (rounds and ordered prefixes up, the block and the host-sort flags down)
-    size_t h_ord_cap = 0;
-    hipStream_t stream_ord = nullptr;     // bulk find_order: the samples of group g run here beside the walk of group g + 1 ...
-    hipStream_t stream_srt[2] = {nullptr, nullptr};   // ... and its sort (one workgroup per round: ~0.2 ms whatever the number of rounds) and read-back here, groups alternating
-    std::vector<hipEvent_t> ord_events;   // per group: table walked / table consumed; then the ends of the three side streams
-    int32_t* h_ord_stage = nullptr;  // pinned: the [i0, i1) round-entry bounds of the groups of a bulk call
-    size_t h_ord_stage_cap = 0;
+    Pinned<char> h_ord;              // pinned staging of a find_order call (rounds and ordered prefixes up, the block and the host-sort flags down)
+    std::vector<Event> ord_events;   // bulk find_order, per group: table walked / table consumed; then the ends of the three side streams (stream_ord, stream_srt)
+    Pinned<int32_t> h_ord_stage;     // pinned: the [i0, i1) round-entry bounds of the groups of a bulk call
     DBuf<int32_t> d_big_ri, d_sk_ev;     // find_order: rounds too large for the LDS sort and their scratch keys (k_order_sort_big)
     DBuf<long long> d_big_off;
     DBuf<double> d_sk_ts;
@@ -469,9 +464,8 @@ struct sw_ctx {
     DBuf<unsigned char> d_white;
     DBuf<double> d_ts;
     DBuf<double> d_tch;    // bulk find_order: timestamps in chain-pool order (k_order_tchain)
-    int* d_err = nullptr;
-    int* d_flow_err = nullptr;   // set by k_cansee_flow when a polling loop gives up (protocol bug)
-    u64* d_flow_dbg = nullptr;   // SW_DEBUG_TIMING: counters of the dataflow sweep (column 0)
+    DBuf<int> d_err;
+    DBuf<u64> d_flow_dbg;        // SW_DEBUG_TIMING: counters of the dataflow sweep (column 0)
 };
 
 namespace {
@@ -525,19 +519,19 @@ int dgrow(sw_ctx* c, DBuf<T>& b, size_t need, size_t keep) {
         // the old buffer may still be in use on any of the context's streams (calls return without a
         // host synchronisation): drain the device before it is copied and freed — reallocation is rare
         HIPCHK(c, hipDeviceSynchronize());
-        if (keep) HIPCHK(c, hipMemcpy(q, b.p, keep * sizeof(T), hipMemcpyDeviceToDevice));
-        (void)hipFree(b.p);
+        if (keep) {
+            const hipError_t ec = hipMemcpy(q, b.p, keep * sizeof(T), hipMemcpyDeviceToDevice);
+            if (ec != hipSuccess) { (void)hipFree(q); return fail(c, SW_EIO, "hipMemcpy into a grown buffer failed: %s", hipGetErrorString(ec)); }
+        }
     }
-    b.p = q;
-    b.cap = nc;
+    b.adopt(q, nc);   // (frees the old block)
     return SW_OK;
 }
 
-template <class T>
-void dfree(DBuf<T>& b) {
-    if (b.p) (void)hipFree(b.p);
-    b.p = nullptr;
-    b.cap = 0;
+// an event made on first use
+int ensure_event(sw_ctx* c, Event& e) {
+    HIPCHK(c, (hipError_t)e.ensure(hipEventDisableTiming));
+    return SW_OK;
 }
 
 // ---- the entry protocol of the call forms (entry_plan.h) --------------------------------------------------------
@@ -590,7 +584,7 @@ struct UserStream {
         c = ctx;
         user = user_stream;
         ours = our_stream ? our_stream : ctx->stream;
-        if (!c->ev_user) HIPCHK(c, hipEventCreateWithFlags(&c->ev_user, hipEventDisableTiming));
+        CHK(ensure_event(c, c->ev_user));
         HIPCHK(c, hipEventRecord(c->ev_user, user));
         HIPCHK(c, hipStreamWaitEvent(ours, c->ev_user, 0));
         joined = true;
@@ -792,12 +786,7 @@ int ensure_rounds(sw_ctx* c, int need) {
     CHK(dgrow(c, c->d_newc, (size_t)nc + sizeof(FameCounters), c->d_newc.p ? sizeof(FameCounters) : 0));
     if (!c->d_fc) HIPCHK(c, hipMemset(c->d_newc.p, 0, sizeof(FameCounters)));
     c->d_fc = reinterpret_cast<FameCounters*>(c->d_newc.p);
-    if ((size_t)nc + sizeof(FameCounters) > c->h_fame_cap) {
-        if (c->h_fame) (void)hipHostFree(c->h_fame);
-        c->h_fame = nullptr;
-        c->h_fame_cap = (size_t)nc + sizeof(FameCounters);
-        if (hipHostMalloc((void**)&c->h_fame, c->h_fame_cap, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); c->h_fame_cap = 0; return fail(c, SW_ENOMEM, "hipHostMalloc for the fame read-back failed"); }
-    }
+    if (!c->h_fame.reserve((size_t)nc + sizeof(FameCounters))) return fail(c, SW_ENOMEM, "hipHostMalloc for the fame read-back failed");
     const size_t fresh = (size_t)(nc - c->Rcap) * np;
     CHK(fill_i32(c, c->d_lo.p + keep, fresh, SW_INF));
     CHK(fill_i32(c, c->d_lopos.p + keep, fresh, 0));
@@ -814,9 +803,9 @@ int ensure_rounds(sw_ctx* c, int need) {
 
 hipEvent_t next_event(sw_ctx* c) {
     if (c->ev_used == c->ev_pool.size()) {
-        hipEvent_t e;
-        if (hipEventCreate(&e) != hipSuccess) return nullptr;
-        c->ev_pool.push_back(e);
+        Event e;
+        if (e.ensure(hipEventDefault) != hipSuccess) return nullptr;
+        c->ev_pool.push_back(std::move(e));
     }
     return c->ev_pool[c->ev_used++];
 }
@@ -1021,7 +1010,7 @@ int launch_cansee_flow_t(sw_ctx* c, int i, int64_t first_event) {
     hipLaunchKernelGGL((k_cansee_flow<NW, MPL, F, H, WIDE, DBG>), dim3(npad), dim3(npad / MPL + 64), lds, c->stream_cs,
                        (const int4*)c->d_cdesc.p, (const int*)c->d_chain_start.p,
                        (const int*)c->d_bounds.p + (size_t)i * npad, (const int*)c->d_bounds.p + (size_t)(i + 1) * npad,
-                       (const int*)c->d_chain_ev.p, (int)first_event, c->d_L.p, c->d_flow_err, c->d_flow_dbg);
+                       (const int*)c->d_chain_ev.p, (int)first_event, c->d_L.p, c->d_flow_err, c->d_flow_dbg.p);
     c->ctr.kernel_launches++;
     HIPCHK(c, hipGetLastError());
     return SW_OK;
@@ -1106,7 +1095,7 @@ template <int NW, int MPL, int F, int H>
 int launch_cansee_flow_g(sw_ctx* c, int i, int64_t first_event) {
     // 32-bit row offsets while the can_see table stays below 4 GB
     const bool wide = (size_t)c->cap * (size_t)(64 * NW) * sizeof(int32_t) >= (1ull << 32);
-    if (c->d_flow_dbg) return wide ? launch_cansee_flow_t<NW, MPL, F, H, true, true>(c, i, first_event)
+    if (c->d_flow_dbg.p) return wide ? launch_cansee_flow_t<NW, MPL, F, H, true, true>(c, i, first_event)
                                    : launch_cansee_flow_t<NW, MPL, F, H, false, true>(c, i, first_event);
     return wide ? launch_cansee_flow_t<NW, MPL, F, H, true, false>(c, i, first_event)
                 : launch_cansee_flow_t<NW, MPL, F, H, false, false>(c, i, first_event);
@@ -1140,9 +1129,9 @@ LoopBufs loop_bufs(sw_ctx* c) {
     B.gallop = c->d_gallop.p;
     B.front = c->d_front.p;
     B.treecnt = c->d_treecnt;
-    B.dbg = c->d_dbg;
+    B.dbg = c->d_dbg.p;
     B.dbg_minor = c->dbg_minor;
-    B.dbg_blk = c->d_dbg_blk;
+    B.dbg_blk = c->d_dbg_blk.p;
     return B;
 }
 
@@ -1170,15 +1159,15 @@ SplitDst split_dst(const sw_ctx* c) {
 
 // the device copy of a SplitDst (slot 0: the linked part's; slot q: part q of an emulated split), uploaded when it changed
 const SplitDst* split_dev(sw_ctx* c, int slot, const SplitDst& d) {
-    if (!c->d_split) {
-        if (hipMalloc((void**)&c->d_split, sizeof(SplitDst) * SW_MAX_PARTS) != hipSuccess) { (void)hipGetLastError(); return nullptr; }
+    if (!c->d_split.p) {
+        if (dgrow(c, c->d_split, SW_MAX_PARTS, 0) != SW_OK) { (void)hipGetLastError(); return nullptr; }
         memset((void*)c->split_up, 0xff, sizeof c->split_up);
     }
     if (memcmp(&c->split_up[slot], &d, sizeof d) != 0) {
         c->split_up[slot] = d;
-        if (hipMemcpyAsync(c->d_split + slot, &c->split_up[slot], sizeof d, hipMemcpyHostToDevice, c->stream) != hipSuccess) return nullptr;
+        if (hipMemcpyAsync(c->d_split.p + slot, &c->split_up[slot], sizeof d, hipMemcpyHostToDevice, c->stream) != hipSuccess) return nullptr;
     }
-    return c->d_split + slot;
+    return c->d_split.p + slot;
 }
 
 // One boundary of a split iteration: this part's kernel of the boundary is enqueued — record its event, tell the others, and
@@ -1384,15 +1373,15 @@ int launch_finalize(sw_ctx* c, hipStream_t ax, int64_t first, int64_t K, int R, 
         c->ctr.kernel_launches++;
         return SW_OK;
     }
-    if (!c->d_fin) {
-        HIPCHK(c, hipMalloc((void**)&c->d_fin, 16));
-        HIPCHK(c, hipMemset(c->d_fin, 0, 16));
+    if (!c->d_fin.p) {
+        CHK(dgrow(c, c->d_fin, 4, 0));
+        HIPCHK(c, hipMemset(c->d_fin.p, 0, 16));
     }
-    HIPCHK(c, hipMemsetAsync(c->d_fin, 0, sizeof(unsigned), ax));
+    HIPCHK(c, hipMemsetAsync(c->d_fin.p, 0, sizeof(unsigned), ax));
     hipLaunchKernelGGL(k_finalize_check, dim3((unsigned)((K + 255) / 256)), dim3(256), 0, ax, (const int*)c->d_cr.p, (const int*)c->d_lo.p, R,
-                       (int)first, (int)K, (const int*)c->d_round.p, np, c->d_finlist.p, c->d_fin);
+                       (int)first, (int)K, (const int*)c->d_round.p, np, c->d_finlist.p, c->d_fin.p);
     hipLaunchKernelGGL(k_finalize_listed<NW>, dim3((unsigned)std::min<int64_t>((K + 3) / 4, std::min(blocks, 1024))), dim3(256), 0, ax, (const int*)c->d_L.p,
-                       (const int*)c->d_cr.p, (const int*)c->d_lo.p, R, (const int*)c->d_finlist.p, c->d_fin, c->d_round.p, c->d_S.p, np);
+                       (const int*)c->d_cr.p, (const int*)c->d_lo.p, R, (const int*)c->d_finlist.p, c->d_fin.p, c->d_round.p, c->d_S.p, np);
     c->ctr.kernel_launches += 2;
     return SW_OK;
 }
@@ -1423,9 +1412,7 @@ int launch_voter_masks(sw_ctx* c, int r0, int R, hipStream_t strm) {
         HIPCHK(c, hipStreamSynchronize(c->stream_aux));
         if (c->Sw_rows && c->d_Sw.p)
             HIPCHK(c, hipMemcpy(q, c->d_Sw.p, (size_t)c->Sw_rows * np * NW * sizeof(u64), hipMemcpyDeviceToDevice));
-        if (c->d_Sw.p) (void)hipFree(c->d_Sw.p);
-        c->d_Sw.p = q;
-        c->d_Sw.cap = (size_t)nr * np * NW;
+        c->d_Sw.adopt(q, (size_t)nr * np * NW);   // (frees the old block)
         c->Sw_rows = nr;
     }
     r0 = std::max(1, r0);
@@ -1555,7 +1542,7 @@ struct DivideCall {
     DivideCall(const sw_ctx* c, int64_t first_, int64_t K_) : first(first_), K(K_), clk(c->debug_timing) {}
 };
 
-LoopGate* loop_gate(sw_ctx* c) { return reinterpret_cast<LoopGate*>(c->d_rb + SW_GATE_OFF); }
+LoopGate* loop_gate(sw_ctx* c) { return reinterpret_cast<LoopGate*>(c->d_rb.p + SW_GATE_OFF); }
 
 // ---- phase: cut plan
 void plan_cuts(const sw_ctx* c, DivideCall& d) {
@@ -1653,9 +1640,8 @@ int size_level_tables(sw_ctx* c, DivideCall& d) {
 // host synchronisation); decides whether the call runs gated
 int open_sweep_stream(sw_ctx* c, DivideCall& d) {
     while ((int)c->cs_events.size() < d.S) {
-        hipEvent_t e;
-        HIPCHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-        c->cs_events.push_back(e);
+        c->cs_events.emplace_back();
+        CHK(ensure_event(c, c->cs_events.back()));
     }
     hipStream_t cs = c->stream_cs;
     HIPCHK(c, hipEventRecord(c->ev_main_mark, c->stream));
@@ -1694,7 +1680,7 @@ int build_bounds(sw_ctx* c, DivideCall& d) {
     // (read back behind the kernel; the host needs the table only for the round loops: do_divide waits for
     // `ev_bounds` after every sweep has been enqueued — the GPU starts sweeping ~0.1 ms earlier)
     HIPCHK(c, hipMemcpyAsync(bounds_h.data(), c->d_bounds.p, bounds_h.size() * sizeof(int32_t), hipMemcpyDeviceToHost, cs));
-    if (!c->ev_bounds) HIPCHK(c, hipEventCreateWithFlags(&c->ev_bounds, hipEventDisableTiming));
+    CHK(ensure_event(c, c->ev_bounds));
     HIPCHK(c, hipEventRecord(c->ev_bounds, cs));
     d.bounds_pending = true;
     return SW_OK;
@@ -1845,7 +1831,7 @@ void chunk_check(sw_ctx* c, int i) {
     // the sweep of this sub-batch is complete (the loop waited for it) and its counters came back with the
     // loop state: provisional entries per chunk, entries the repair changed.  (A loop never reports SW_OK
     // without at least one read-back behind a shot that waited for cs_events[i]: h_rb is this sub-batch's or a later one.)
-    const unsigned* pv = reinterpret_cast<const unsigned*>(c->h_rb + ((unsigned char*)c->d_prov - c->d_rb));
+    const unsigned* pv = reinterpret_cast<const unsigned*>(c->h_rb + ((unsigned char*)c->d_prov - c->d_rb.p));
     for (int k = 1; k < pl.G; ++k) {
         const unsigned cnt = pv[(size_t)i * SW_MAX_CHUNKS + k];
         const int64_t len = pl.a[k + 1] - pl.a[k];
@@ -1934,7 +1920,7 @@ void loop_start(sw_ctx* c, LoopRun& L, bool timed, int r_start, int64_t limit, c
 }
 
 // pinned read-back slot j of the call; -1: the slot that was read last
-unsigned char* rb_slot(sw_ctx* c, int j) { return j < 0 ? c->h_rb : c->h_rb_all + (size_t)j * c->rb_bytes; }
+unsigned char* rb_slot(sw_ctx* c, int j) { return j < 0 ? c->h_rb : c->h_rb_all.p + (size_t)j * c->rb_bytes; }
 
 // `n_it` more iterations on the main stream and behind them loop state, sweep error flag, the members' front rounds,
 // tree-tally and chunk counters: ONE copy into pinned slot j, its event recorded behind the copy (j >= 0)
@@ -1944,7 +1930,7 @@ int enqueue_shot(sw_ctx* c, LoopRun& L, int n_it, int j) {
     L.launched += n_it;
     if (c->split_failed) { c->poisoned = true; return fail(c, SW_EIO, "split round loop: a linked context did not arrive at iteration %lld (sw_split_link: every part calls sw_divide_rounds)", c->split_iter); }
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(rb_slot(c, j), c->d_rb, c->rb_bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(rb_slot(c, j), c->d_rb.p, c->rb_bytes, hipMemcpyDeviceToHost, c->stream));
     if (j >= 0) HIPCHK(c, hipEventRecord(c->rb_events[j], c->stream));
     return SW_OK;
 }
@@ -2005,7 +1991,7 @@ void account_loop(sw_ctx* c, DivideCall& d, const LoopRun& L, int64_t n_events, 
     c->eval_src = st.iter & 1;
     c->R = st.max_round + 1;
     if (c->unit_stake && c->tally_impl == 2) {   // the tree search counts the tallies it really evaluated (per member, read back with the state)
-        const int32_t* tc = reinterpret_cast<const int32_t*>(c->h_rb + ((unsigned char*)c->d_treecnt - c->d_rb));
+        const int32_t* tc = reinterpret_cast<const int32_t*>(c->h_rb + ((unsigned char*)c->d_treecnt - c->d_rb.p));
         for (int m = 0; m < c->npad; ++m) c->ctr.tally_evals += tc[m];
     } else
     c->ctr.tally_evals += (int64_t)st.evals;
@@ -2319,12 +2305,12 @@ int do_fame(sw_ctx* c, int32_t* new_rounds, int cap, int* n_new) {
     const int max_c = first_undecided_round(c);
     CHK(fame_launch<NW>(c, max_c, 0, 1, &sp_el));
     // fame counters + new_c flags: one copy into pinned memory
-    HIPCHK(c, hipMemcpyAsync(c->h_fame, c->d_newc.p, sizeof(FameCounters) + (size_t)R, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->h_fame.p, c->d_newc.p, sizeof(FameCounters) + (size_t)R, hipMemcpyDeviceToHost, c->stream));
     span_end(c, sp);
     HIPCHK(c, hipStreamSynchronize(c->stream));
     FameCounters fc;
-    memcpy(&fc, c->h_fame, sizeof fc);
-    const unsigned char* newc = c->h_fame + sizeof(FameCounters);
+    memcpy(&fc, c->h_fame.p, sizeof fc);
+    const unsigned char* newc = c->h_fame.p + sizeof(FameCounters);
     const int call_idx = (int)c->fame_calls.size();
     c->fame_calls.push_back({max_c, R, c->divided});
     int cnt = 0;
@@ -2350,14 +2336,14 @@ int do_fame_partial(sw_ctx* c, int part, int nparts, int8_t* famous, uint8_t* de
     const int max_c = first_undecided_round(c);
     CHK(fame_launch<NW>(c, max_c, part, nparts, nullptr));
     std::vector<signed char> fam((size_t)R * np);
-    HIPCHK(c, hipMemcpyAsync(c->h_fame, c->d_newc.p, sizeof(FameCounters) + (size_t)R, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->h_fame.p, c->d_newc.p, sizeof(FameCounters) + (size_t)R, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(fam.data(), c->d_fam.p, fam.size(), hipMemcpyDeviceToHost, c->stream));
     // the kernel marks the rounds it completed in the device-side consensus flags; they become
     // official in sw_commit_fame, for every part alike
     HIPCHK(c, hipStreamSynchronize(c->stream));
     FameCounters fc;
-    memcpy(&fc, c->h_fame, sizeof fc);
-    const unsigned char* newc = c->h_fame + sizeof(FameCounters);
+    memcpy(&fc, c->h_fame.p, sizeof fc);
+    const unsigned char* newc = c->h_fame.p + sizeof(FameCounters);
     for (int r = 0; r < R; ++r) {
         decided[r] = newc[r];
         const bool mine = r >= max_c && (r - max_c) % nparts == part;
@@ -2435,21 +2421,18 @@ int window_evict(sw_ctx* c) {
 
 // pinned staging of a find_order call (laid out by stage_order_call)
 int ensure_order_host(sw_ctx* c, size_t bytes) {
-    if (bytes <= c->h_ord_cap) return SW_OK;
-    if (c->h_ord) { HIPCHK(c, hipDeviceSynchronize()); (void)hipHostFree(c->h_ord); c->h_ord = nullptr; c->h_ord_cap = 0; }
-    size_t nc = bytes + bytes / 2 + 4096;
-    if (hipHostMalloc((void**)&c->h_ord, nc, hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); return fail(c, SW_ENOMEM, "hipHostMalloc(%zu bytes) for find_order failed", nc); }
-    c->h_ord_cap = nc;
+    if (bytes <= c->h_ord.cap) return SW_OK;
+    if (c->h_ord.p) HIPCHK(c, hipDeviceSynchronize());
+    const size_t nc = bytes + bytes / 2 + 4096;
+    if (!c->h_ord.reserve(nc)) return fail(c, SW_ENOMEM, "hipHostMalloc(%zu bytes) for find_order failed", nc);
     return SW_OK;
 }
 
 // pinned staging of the group bounds of a bulk find_order call
 int ensure_order_stage(sw_ctx* c, size_t ints) {
-    if (ints <= c->h_ord_stage_cap) return SW_OK;
-    if (c->h_ord_stage) { HIPCHK(c, hipDeviceSynchronize()); (void)hipHostFree(c->h_ord_stage); c->h_ord_stage = nullptr; c->h_ord_stage_cap = 0; }
-    const size_t nc = ints * 2 + 256;
-    if (hipHostMalloc((void**)&c->h_ord_stage, nc * sizeof(int32_t), hipHostMallocDefault) != hipSuccess) { (void)hipGetLastError(); return fail(c, SW_ENOMEM, "hipHostMalloc for find_order's group table failed"); }
-    c->h_ord_stage_cap = nc;
+    if (ints <= c->h_ord_stage.cap) return SW_OK;
+    if (c->h_ord_stage.p) HIPCHK(c, hipDeviceSynchronize());
+    if (!c->h_ord_stage.reserve(ints * 2 + 256)) return fail(c, SW_ENOMEM, "hipHostMalloc for find_order's group table failed");
     return SW_OK;
 }
 
@@ -2624,11 +2607,11 @@ int stage_order_call(sw_ctx* c, OrderCall& o) {
     const size_t ordpos_off = ((size_t)nr * 4 + 63) & ~(size_t)63, init_off = ordpos_off + (size_t)np * 4, blk_off = init_off + 64,
                  flag_off = blk_off + ((blk + 63) & ~(size_t)63);
     CHK(ensure_order_host(c, flag_off + (size_t)nr * 4));
-    o.h_rounds = reinterpret_cast<int32_t*>(c->h_ord);
-    o.h_ordpos = reinterpret_cast<int32_t*>(c->h_ord + ordpos_off);
-    o.h_init = reinterpret_cast<OrderInfo*>(c->h_ord + init_off);
-    o.h = OrderBlock(c->h_ord + blk_off, np);
-    o.hostflag = reinterpret_cast<int32_t*>(c->h_ord + flag_off);
+    o.h_rounds = reinterpret_cast<int32_t*>(c->h_ord.p);
+    o.h_ordpos = reinterpret_cast<int32_t*>(c->h_ord.p + ordpos_off);
+    o.h_init = reinterpret_cast<OrderInfo*>(c->h_ord.p + init_off);
+    o.h = OrderBlock(c->h_ord.p + blk_off, np);
+    o.hostflag = reinterpret_cast<int32_t*>(c->h_ord.p + flag_off);
     std::copy(o.rounds.begin(), o.rounds.end(), o.h_rounds);
     std::fill(o.h_ordpos, o.h_ordpos + np, 0);
     std::copy(c->ord_pos.begin(), c->ord_pos.end(), o.h_ordpos);
@@ -2743,18 +2726,21 @@ int plan_order_groups(sw_ctx* c, OrderCall& o) {
     CHK(dgrow(c, c->d_grp, (OrderGroup::ints(np) + 2) * std::max<size_t>(ng, 1), 0));
     int32_t* d_gbounds = c->d_grp.p + OrderGroup::ints(np) * ng;
     CHK(ensure_order_stage(c, ng * 2));
-    for (size_t gi = 0; gi < ng; ++gi) { c->h_ord_stage[2 * gi] = o.groups[gi].i0; c->h_ord_stage[2 * gi + 1] = o.groups[gi].i1; }
-    HIPCHK(c, hipMemcpyAsync(d_gbounds, c->h_ord_stage, ng * 2 * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    for (size_t gi = 0; gi < ng; ++gi) { c->h_ord_stage.p[2 * gi] = o.groups[gi].i0; c->h_ord_stage.p[2 * gi + 1] = o.groups[gi].i1; }
+    HIPCHK(c, hipMemcpyAsync(d_gbounds, c->h_ord_stage.p, ng * 2 * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
     hipLaunchKernelGGL(k_order_group, dim3((unsigned)ng), dim3(np), 0, c->stream, (const int*)c->d_ordat.p, (const int*)c->d_fwm.p,
                        (const int*)c->d_chain_start.p, (const int*)c->d_chain_cnt.p, (const int*)c->d_chain_ev.p, (const int*)d_gbounds, n, np, P, c->d_grp.p);
     c->ctr.kernel_launches++;
     if (o.two) {
-        if (!c->stream_ord) HIPCHK(c, hipStreamCreateWithFlags(&c->stream_ord, hipStreamNonBlocking));
-        for (auto& st : c->stream_srt) if (!st) HIPCHK(c, hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
+        for (Stream* st : {&c->stream_ord, &c->stream_srt[0], &c->stream_srt[1]})
+            if (!*st) {
+                hipStream_t made = nullptr;
+                HIPCHK(c, hipStreamCreateWithFlags(&made, hipStreamNonBlocking));
+                st->reset(made);
+            }
         while (c->ord_events.size() < 3 * ng + 3) {   // per group: table walked / table consumed / order on the host; then the ends of the three side streams
-            hipEvent_t e;
-            HIPCHK(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-            c->ord_events.push_back(e);
+            c->ord_events.emplace_back();
+            CHK(ensure_event(c, c->ord_events.back()));
         }
     }
     o.s1 = o.two ? c->stream_ord : c->stream;
@@ -3150,10 +3136,14 @@ int sw_create(int n_members, const uint64_t* stake, int coin_period, int device,
         delete c;
         return fail(nullptr, SW_EINVAL, "%s", knob_err.c_str());
     }
+    // a zeroed buffer of 64-bit words for diagnostics: without it (no memory) the context works all the same
+    auto debug_buf = [&](auto& b, size_t words) {
+        if (dgrow(c, b, words, 0) == SW_OK) (void)hipMemset(b.p, 0, words * 8);
+        else { (void)hipGetLastError(); c->err.clear(); }
+    };
     c->debug_timing = getenv("SW_DEBUG_TIMING") != nullptr;
     if (c->debug_timing) {
-        if (hipMalloc(&c->d_flow_dbg, 8 * sizeof(u64)) != hipSuccess) c->d_flow_dbg = nullptr;
-        else (void)hipMemset(c->d_flow_dbg, 0, 8 * sizeof(u64));
+        debug_buf(c->d_flow_dbg, 8);
     }
     if (const char* e_ = getenv("SW_EXPORT_LANES")) { const int g = atoi(e_); if (g == 4 || g == 8) c->export_lanes = g; }
     if (const char* e_ = getenv("SW_WALK_THREADS")) { const int w = atoi(e_); if (w >= 64 && w <= wlk::MAX_THREADS && w % 64 == 0) c->walk_threads = w; }
@@ -3162,11 +3152,9 @@ int sw_create(int n_members, const uint64_t* stake, int coin_period, int device,
     if (getenv("SW_DEBUG_CLOCKS")) {  // diagnostics: phase stamps of the round-loop kernels
         c->dbg_minor = atoi(getenv("SW_DEBUG_CLOCKS")) >= 2 ? 0 : 1;
         if (atoi(getenv("SW_DEBUG_CLOCKS")) == 3) {
-            if (hipMalloc(&c->d_dbg_blk, (size_t)SW_DBG_MAX_ITERS * 2 * 2048 * 8) != hipSuccess) c->d_dbg_blk = nullptr;
-            else (void)hipMemset(c->d_dbg_blk, 0, (size_t)SW_DBG_MAX_ITERS * 2 * 2048 * 8);
+            debug_buf(c->d_dbg_blk, (size_t)SW_DBG_MAX_ITERS * 2 * 2048);
         }
-        if (hipMalloc(&c->d_dbg, (size_t)SW_DBG_MAX_ITERS * 32 * 8) != hipSuccess) c->d_dbg = nullptr;
-        else (void)hipMemset(c->d_dbg, 0, (size_t)SW_DBG_MAX_ITERS * 32 * 8);
+        debug_buf(c->d_dbg, (size_t)SW_DBG_MAX_ITERS * 32);
     }
     c->nev.assign(n_members, 0);
     c->BATCH = (c->BATCH + 1) & ~1;  // even: the loop state is double-buffered by iteration parity
@@ -3184,18 +3172,18 @@ int sw_create(int n_members, const uint64_t* stake, int coin_period, int device,
         int least = 0, greatest = 0;
         const char* pe = getenv("SW_PRIO");
         const bool use_prio = !pe || atoi(pe) != 0;
-        if (use_prio && hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess && least != greatest) {
-            CHIP(hipStreamCreateWithPriority(&c->stream, hipStreamNonBlocking, greatest));
-            CHIP(hipStreamCreateWithPriority(&c->stream_cs, hipStreamNonBlocking, least));
-            CHIP(hipStreamCreateWithPriority(&c->stream_aux, hipStreamNonBlocking, least));
-            CHIP(hipStreamCreateWithPriority(&c->stream_io, hipStreamNonBlocking, least));
-        } else {
-            (void)hipGetLastError();
-            CHIP(hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
-            CHIP(hipStreamCreateWithFlags(&c->stream_cs, hipStreamNonBlocking));
-            CHIP(hipStreamCreateWithFlags(&c->stream_aux, hipStreamNonBlocking));
-            CHIP(hipStreamCreateWithFlags(&c->stream_io, hipStreamNonBlocking));
-        }
+        const bool prio = use_prio && hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess && least != greatest;
+        if (!prio) (void)hipGetLastError();
+        auto make_stream = [&](Stream& st, int priority) {
+            hipStream_t made = nullptr;
+            const hipError_t e_ = prio ? hipStreamCreateWithPriority(&made, hipStreamNonBlocking, priority) : hipStreamCreateWithFlags(&made, hipStreamNonBlocking);
+            if (e_ == hipSuccess) st.reset(made);
+            return e_;
+        };
+        CHIP(make_stream(c->stream, greatest));
+        CHIP(make_stream(c->stream_cs, least));
+        CHIP(make_stream(c->stream_aux, least));
+        CHIP(make_stream(c->stream_io, least));
         // experiment (SW_CS_CUS=<count>): confine the can_see sweeps to the first <count> compute units of
         // the CU mask, so that the round loop's kernels find the others free of polling waves
         if (const char* e = getenv("SW_CS_CUS")) {
@@ -3204,34 +3192,31 @@ int sw_create(int n_members, const uint64_t* stake, int coin_period, int device,
                 uint32_t mask[8] = {0};
                 for (int i = 0; i < cus; ++i) mask[i >> 5] |= 1u << (i & 31);
                 hipStream_t s2 = nullptr;
-                if (hipExtStreamCreateWithCUMask(&s2, 8, mask) == hipSuccess) { (void)hipStreamDestroy(c->stream_cs); c->stream_cs = s2; }
+                if (hipExtStreamCreateWithCUMask(&s2, 8, mask) == hipSuccess) c->stream_cs.reset(s2);
                 else (void)hipGetLastError();
             }
         }
-        CHIP(hipEventCreateWithFlags(&c->ev_payload, hipEventDisableTiming));
-        CHIP(hipEventCreateWithFlags(&c->ev_small, hipEventDisableTiming));
+        CCHK(ensure_event(c, c->ev_payload));
+        CCHK(ensure_event(c, c->ev_small));
     }
     {
         static_assert(2 * sizeof(RState) + sizeof(int) <= SW_GATE_OFF && SW_GATE_OFF % 8 == 0 && SW_GATE_OFF + sizeof(LoopGate) <= 256, "readback block header");
         const size_t tree_off = 256 + (size_t)c->npad * sizeof(int32_t);
         const size_t prov_off = tree_off + (size_t)c->npad * sizeof(int32_t);
         c->rb_bytes = prov_off + (size_t)SW_PROV_ROWS * (SW_MAX_CHUNKS + 1) * sizeof(unsigned);
-        CHIP(hipMalloc((void**)&c->d_rb, c->rb_bytes));
-        CHIP(hipMemset(c->d_rb, 0, c->rb_bytes));
-        CHIP(hipHostMalloc((void**)&c->h_rb_all, c->rb_bytes * SW_PROV_ROWS, hipHostMallocDefault));
-        c->h_rb = c->h_rb_all;
-        for (int i = 0; i < SW_PROV_ROWS; ++i) {
-            hipEvent_t e1;
-            CHIP(hipEventCreateWithFlags(&e1, hipEventDisableTiming));
-            c->rb_events.push_back(e1);
-        }
-        c->d_state = reinterpret_cast<RState*>(c->d_rb);
-        c->d_flow_err = reinterpret_cast<int*>(c->d_rb + 2 * sizeof(RState));
-        c->d_front.p = reinterpret_cast<int32_t*>(c->d_rb + 256);
-        c->d_treecnt = reinterpret_cast<int32_t*>(c->d_rb + tree_off);
-        c->d_prov = reinterpret_cast<unsigned*>(c->d_rb + prov_off);
+        CCHK(dgrow(c, c->d_rb, c->rb_bytes, 0));
+        CHIP(hipMemset(c->d_rb.p, 0, c->rb_bytes));
+        if (!c->h_rb_all.reserve(c->rb_bytes * SW_PROV_ROWS)) { fail(c, SW_ENOMEM, "hipHostMalloc for the read-back slots failed"); return bail(SW_ENOMEM); }
+        c->h_rb = c->h_rb_all.p;
+        c->rb_events.resize(SW_PROV_ROWS);
+        for (Event& e1 : c->rb_events) CCHK(ensure_event(c, e1));
+        c->d_state = reinterpret_cast<RState*>(c->d_rb.p);
+        c->d_flow_err = reinterpret_cast<int*>(c->d_rb.p + 2 * sizeof(RState));
+        c->d_front.p = reinterpret_cast<int32_t*>(c->d_rb.p + 256);
+        c->d_treecnt = reinterpret_cast<int32_t*>(c->d_rb.p + tree_off);
+        c->d_prov = reinterpret_cast<unsigned*>(c->d_rb.p + prov_off);
     }
-    CHIP(hipMalloc((void**)&c->d_err, sizeof(int)));
+    CCHK(dgrow(c, c->d_err, 1, 0));
 
     const int np = c->npad;
     CCHK(dgrow(c, c->d_stake, np, 0));
@@ -3250,19 +3235,16 @@ int sw_create(int n_members, const uint64_t* stake, int coin_period, int device,
     CCHK(dgrow(c, c->d_gallop, 2 * np, 0));
     CCHK(fill_i32(c, c->d_front.p, np, -1));
     c->divided_cnt.assign(np, 0);
-    CHIP(hipEventCreateWithFlags(&c->ev_aux_done, hipEventDisableTiming));
-    CHIP(hipEventCreateWithFlags(&c->ev_cs_done, hipEventDisableTiming));
-    CHIP(hipEventCreateWithFlags(&c->ev_main_mark, hipEventDisableTiming));
-    CHIP(hipEventCreateWithFlags(&c->ev_loop_done, hipEventDisableTiming));
+    for (Event* e1 : {&c->ev_aux_done, &c->ev_cs_done, &c->ev_main_mark, &c->ev_loop_done}) CCHK(ensure_event(c, *e1));
     CCHK(dgrow(c, c->d_chain_len, 3 * np, 0));
     CCHK(dgrow(c, c->d_chain_start, np, 0));
     CCHK(dgrow(c, c->d_chain_cnt, np, 0));
     // band masks; row 0 stays all-zero (the bit-sliced tally points "not a hop" at it), the band
     // proper starts at row 1
     CCHK(dgrow(c, c->d_Mb, ((size_t)c->MCAP + 1) * c->nw, 0));
-    if (hipMemset(c->d_Mb.p, 0, (size_t)c->nw * sizeof(u64)) != hipSuccess) { sw_destroy(c); return SW_EIO; }
+    CHIP(hipMemset(c->d_Mb.p, 0, (size_t)c->nw * sizeof(u64)));
     CCHK(dgrow(c, c->d_Pc, (size_t)c->MCAP + 1, 0));
-    if (hipMemset(c->d_Pc.p, 0, sizeof(int32_t)) != hipSuccess) { sw_destroy(c); return SW_EIO; }
+    CHIP(hipMemset(c->d_Pc.p, 0, sizeof(int32_t)));
     CCHK(fill_i32(c, c->d_evalround.p, 2 * np, -1));
     CCHK(fill_i32(c, c->d_evalpos.p, 2 * np, 0));
     CCHK(fill_i32(c, c->d_lo_r.p, 2 * np, SW_INF));
@@ -3286,12 +3268,11 @@ int sw_destroy(sw_ctx* c) {
     if (!c) return SW_OK;
     (void)hipSetDevice(c->device);
     (void)hipDeviceSynchronize();
-    if (c->debug_timing && c->d_flow_dbg) {
+    if (c->debug_timing && c->d_flow_dbg.p) {
         u64 d[8] = {0};
-        (void)hipMemcpy(d, c->d_flow_dbg, sizeof d, hipMemcpyDeviceToHost);
+        (void)hipMemcpy(d, c->d_flow_dbg.p, sizeof d, hipMemcpyDeviceToHost);
         fprintf(stderr, "[sw] dataflow sweep, column 0: %llu events, %llu rows re-read from memory, %llu starved lane-trips, %llu wave-trips over %llu wave runs "
                 "(%.1f trips per wave run), loader passes %llu (+%llu idle)\n", d[0], d[1], d[2], d[3], d[6], d[6] ? (double)d[3] / (double)d[6] : 0.0, d[4], d[5]);
-        (void)hipFree(c->d_flow_dbg);
     }
     if (c->debug_timing && c->stage_calls > 0) {
         const double k = 1.0 / (double)c->stage_calls;
@@ -3299,77 +3280,14 @@ int sw_destroy(sw_ctx* c) {
                 "round loop %.1f, front rows %.1f, aux launches %.1f, final syncs %.1f\n", (long long)c->stage_calls,
                 c->stage_us[0] * k, c->stage_us[1] * k, c->stage_us[2] * k, c->stage_us[3] * k, c->stage_us[4] * k, c->stage_us[5] * k);
     }
-    if (c->vm.active) { vm_destroy(c); c->d_L.p = nullptr; c->d_L.cap = 0; }
-    dfree(c->d_ordpos);
-    dfree(c->x_worder); dfree(c->x_wcnt); dfree(c->x_newr); dfree(c->x_queue); dfree(c->x_fw); dfree(c->x_items_ev); dfree(c->x_rounds);
-    dfree(c->x_fam_ev); dfree(c->x_votes); dfree(c->x_tbd); dfree(c->x_sm); dfree(c->x_done); dfree(c->x_visited); dfree(c->x_sflag);
-    dfree(c->x_white); dfree(c->x_times); dfree(c->x_tsort); dfree(c->x_items_ts); dfree(c->x_hdr);
-    dfree(c->d_cr); dfree(c->d_sp); dfree(c->d_op); dfree(c->d_ht); dfree(c->d_seq); dfree(c->d_round); dfree(c->d_L);
-    dfree(c->d_chain_ev); dfree(c->d_coin); dfree(c->d_sig); dfree(c->d_t); dfree(c->d_S); dfree(c->d_finlist);
-    if (c->d_fin) (void)hipFree(c->d_fin);
-    dfree(c->d_cdesc); dfree(c->d_bounds); dfree(c->d_cuts); dfree(c->d_chain_start); dfree(c->d_chain_cnt); dfree(c->d_chain_len); dfree(c->d_stake); dfree(c->d_lev_cnt); dfree(c->d_lev_start); dfree(c->d_lev_pin); dfree(c->d_lev_cback); dfree(c->d_lev_pinbase); dfree(c->d_lev_pos);
-    dfree(c->d_lev_cursor); dfree(c->d_desc); dfree(c->d_lo); dfree(c->d_lopos); dfree(c->d_wit);
-    dfree(c->d_fam); dfree(c->d_dec_call); dfree(c->d_dec_by); dfree(c->d_cons); dfree(c->d_newc); dfree(c->d_Sw); dfree(c->d_evalround);
-    dfree(c->d_evalpos); dfree(c->d_lo_r); dfree(c->d_cur); dfree(c->d_unres); dfree(c->d_lo_next);
-    if (c->d_dbg) (void)hipFree(c->d_dbg);
-    if (c->d_dbg_blk) (void)hipFree(c->d_dbg_blk);
-    dfree(c->d_pos_next); dfree(c->d_found64); dfree(c->d_rsc); dfree(c->d_farslot); dfree(c->d_force); dfree(c->d_cand); dfree(c->d_gallop); dfree(c->d_small); dfree(c->d_Mb); dfree(c->d_Pc);
-    if (c->d_rb) (void)hipFree(c->d_rb);
-    if (c->h_rb_all) (void)hipHostFree(c->h_rb_all);
-    for (hipEvent_t e : c->rb_events) (void)hipEventDestroy(e);
-    if (c->h_fame) (void)hipHostFree(c->h_fame);
-    if (c->d_err) (void)hipFree(c->d_err);
-    dfree(c->d_ord_rounds); dfree(c->d_fwm); dfree(c->d_ordat); dfree(c->d_rowsum); dfree(c->d_grp); dfree(c->d_oblk);
-    if (c->h_ord) (void)hipHostFree(c->h_ord);
-    if (c->h_ord_stage) (void)hipHostFree(c->h_ord_stage);
-    if (c->d_split) (void)hipFree(c->d_split);
-    c->transactions.release();
-    if (c->stream_ord) (void)hipStreamDestroy(c->stream_ord);
-    for (auto st : c->stream_srt) if (st) (void)hipStreamDestroy(st);
-    for (auto e : c->ord_events) (void)hipEventDestroy(e);
-    dfree(c->d_q); dfree(c->d_acc_ev); dfree(c->d_acc_ri); dfree(c->d_ts);
-    dfree(c->d_sorted); dfree(c->d_hostflag); dfree(c->d_white);
-    dfree(c->d_big_ri); dfree(c->d_sk_ev); dfree(c->d_big_off); dfree(c->d_sk_ts); dfree(c->d_sk_k8);
-    dfree(c->d_fd); dfree(c->d_seg); dfree(c->d_tch);
-    dfree(c->d_rbnd); dfree(c->d_rcuts);
-    if (c->d_rprov) (void)hipFree(c->d_rprov);
-    if (c->ev_user) (void)hipEventDestroy(c->ev_user);
+    if (c->vm.active) { vm_destroy(c); c->d_L.release(); }   // (d_L aliased the reservation)
+    if (c->d_sg_keys.p) { (void)hipMemset(c->d_sg_keys.p, 0, c->d_sg_keys.cap); (void)hipDeviceSynchronize(); }   // the secrets do not outlive the context
+    if (c->stream_io) (void)hipStreamSynchronize(c->stream_io);
     for (int g = 0; g < 4; ++g) {
         if (c->loop_exec[g]) (void)hipGraphExecDestroy(c->loop_exec[g]);
         if (c->loop_graph[g]) (void)hipGraphDestroy(c->loop_graph[g]);
     }
-    for (auto e : c->ev_pool) (void)hipEventDestroy(e);
-    for (auto e : c->cs_events) (void)hipEventDestroy(e);
-    if (c->stream_io) { (void)hipStreamSynchronize(c->stream_io); (void)hipStreamDestroy(c->stream_io); }
-    if (c->ev_payload) (void)hipEventDestroy(c->ev_payload);
-    if (c->ev_ht) (void)hipEventDestroy(c->ev_ht);
-    dfree(c->d_ing_tab); dfree(c->d_ing_hist); dfree(c->d_ht_stat);
-    dfree(c->d_id); dfree(c->d_idtab); dfree(c->d_idflag); dfree(c->d_pl); dfree(c->d_pl_in);
-    dfree(c->d_xp); dfree(c->d_xp_out);
-    dfree(c->votes.d_sched); dfree(c->votes.d_plan); dfree(c->votes.d_work); dfree(c->votes.d_out); dfree(c->votes.d_cnt);
-    dfree(c->d_wk); dfree(c->d_wk_bits); dfree(c->d_wk_q); dfree(c->d_wk_list); dfree(c->d_wk_trunk); dfree(c->d_wk_children);
-    dfree(c->d_rr); dfree(c->d_cts); dfree(c->d_tx); dfree(c->d_cs_ordpos); dfree(c->d_cs_out);
-    dfree(c->hist.d_voter); dfree(c->hist.d_cand); dfree(c->hist.d_tab); dfree(c->hist.d_items_rr); dfree(c->hist.d_q); dfree(c->hist.d_value);
-    dfree(c->hist.d_qout); dfree(c->hist.d_off);
-    dfree(c->d_vkeys); dfree(c->d_vtab); dfree(c->d_v_in);
-    dfree(c->d_pk_hdr); dfree(c->d_pk); dfree(c->d_pk_in); dfree(c->d_pk_out);
-    dfree(c->d_wr_set); dfree(c->d_wr); dfree(c->d_wr_in); dfree(c->d_wr_out);
-    dfree(c->d_data); dfree(c->d_data_off); dfree(c->d_data_none); dfree(c->d_dt); dfree(c->d_dt_in); dfree(c->d_dt_out);
-    if (c->d_sg_keys.p) { (void)hipMemset(c->d_sg_keys.p, 0, c->d_sg_keys.cap); (void)hipDeviceSynchronize(); }   // the secrets do not outlive the context
-    dfree(c->d_sg_keys); dfree(c->d_sg); dfree(c->d_sg_in);
-    if (c->h_pkcnt) (void)hipHostFree(c->h_pkcnt);
-    if (c->h_plcnt) (void)hipHostFree(c->h_plcnt);
-    if (c->ev_aux_done) (void)hipEventDestroy(c->ev_aux_done);
-    if (c->ev_cs_done) (void)hipEventDestroy(c->ev_cs_done);
-    if (c->ev_main_mark) (void)hipEventDestroy(c->ev_main_mark);
-    if (c->ev_bounds) (void)hipEventDestroy(c->ev_bounds);
-    if (c->ev_loop_done) (void)hipEventDestroy(c->ev_loop_done);
-    if (c->h_pin) (void)hipHostFree(c->h_pin);
-    if (c->h_small) (void)hipHostFree(c->h_small);
-    if (c->ev_small) (void)hipEventDestroy(c->ev_small);
-    if (c->stream_cs) (void)hipStreamDestroy(c->stream_cs);
-    if (c->stream_aux) (void)hipStreamDestroy(c->stream_aux);
-    if (c->stream) (void)hipStreamDestroy(c->stream);
+    // everything else is a member of an owning type (owned.h): ~sw_ctx gives it back — the device is idle and current
     delete c;
     return SW_OK;
 }
@@ -3676,16 +3594,9 @@ static int append_small(sw_ctx* c, int64_t K, const int32_t* creator, const int3
     const int64_t N0 = c->N;
     const int n = c->n, np = c->npad;
     CHK(ensure_dag_h(c));  // parents' heights (complete already unless a bulk append came before)
-    if ((size_t)K > c->h_small_cap) {
+    if ((size_t)K > c->h_small.cap) {
         if (c->small_pending) { HIPCHK(c, hipEventSynchronize(c->ev_small)); c->small_pending = false; }
-        if (c->h_small) (void)hipHostFree(c->h_small);
-        c->h_small = nullptr; c->h_small_cap = 0;
-        const size_t cap = std::max<size_t>(256, (size_t)K * 2);
-        if (hipHostMalloc((void**)&c->h_small, cap * sizeof(SmallRec), hipHostMallocDefault) != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(c, SW_ENOMEM, "hipHostMalloc for the small-append staging buffer failed");
-        }
-        c->h_small_cap = cap;
+        if (!c->h_small.reserve(std::max<size_t>(256, (size_t)K * 2))) return fail(c, SW_ENOMEM, "hipHostMalloc for the small-append staging buffer failed");
     }
     // ---- segments that overflow move to the end of the pool, doubled (device-to-device)
     bool moved = false;
@@ -3729,7 +3640,7 @@ static int append_small(sw_ctx* c, int64_t K, const int32_t* creator, const int3
     if (c->pool_h_valid && c->chain_ev_h.size() < (size_t)c->pool_used) c->chain_ev_h.resize((size_t)c->pool_used, -1);
     for (int64_t i = 0; i < K; ++i) {
         const int64_t e = N0 + i;
-        SmallRec& r = c->h_small[i];
+        SmallRec& r = c->h_small.p[i];
         const int32_t m = creator[i], s_ = self_parent[i], o_ = other_parent[i];
         r.cr = m; r.sp = s_; r.op = o_; r.seq = seq[i];
         const int32_t h = s_ < 0 ? 0 : std::max(c->ht[s_], c->ht[o_]) + 1;  // swirld.py:117-120 (parents are earlier: already mirrored)
@@ -3752,8 +3663,8 @@ static int append_small(sw_ctx* c, int64_t K, const int32_t* creator, const int3
     c->first_ev.swap(first_t);
     c->nev.swap(nev_t);
     c->N = N0 + K;
-    CHK(dgrow(c, c->d_small, (size_t)c->h_small_cap * sizeof(SmallRec), 0));
-    hipError_t e1 = hipMemcpyAsync(c->d_small.p, c->h_small, (size_t)K * sizeof(SmallRec), hipMemcpyHostToDevice, c->stream);
+    CHK(dgrow(c, c->d_small, c->h_small.cap * sizeof(SmallRec), 0));
+    hipError_t e1 = hipMemcpyAsync(c->d_small.p, c->h_small.p, (size_t)K * sizeof(SmallRec), hipMemcpyHostToDevice, c->stream);
     if (e1 == hipSuccess) {
         hipLaunchKernelGGL(k_ingest_small, dim3((unsigned)((K + 127) / 128)), dim3(128), 0, c->stream, (const SmallRec*)c->d_small.p, (int)N0, (int)K,
                            c->d_cr.p, c->d_sp.p, c->d_op.p, c->d_seq.p, c->d_ht.p, c->d_t.p, c->d_sig.p, c->d_coin.p, c->d_round.p,
@@ -3826,15 +3737,7 @@ int sw_append_events(sw_ctx* c, int64_t K, const int32_t* creator, const int32_t
     if (stage) {
         const size_t need = (size_t)K * 72;
         if (c->payload_pending) { HIPCHK(c, hipEventSynchronize(c->ev_payload)); c->payload_pending = false; }
-        if (need > c->h_pin_cap) {
-            if (c->h_pin) (void)hipHostFree(c->h_pin);
-            c->h_pin = nullptr; c->h_pin_cap = 0;
-            if (hipHostMalloc((void**)&c->h_pin, need, hipHostMallocDefault) != hipSuccess) {
-                (void)hipGetLastError();
-                return fail(c, SW_ENOMEM, "hipHostMalloc(%zu bytes) for the ingest staging buffer failed", need);
-            }
-            c->h_pin_cap = need;
-        }
+        if (!c->h_pin.reserve(need)) return fail(c, SW_ENOMEM, "hipHostMalloc(%zu bytes) for the ingest staging buffer failed", need);
     }
     // ---- 3. parent arrays to the (uncommitted) tail of the device arrays; bulk: device half of the validation
     HIPCHK(c, hipMemcpyAsync(c->d_cr.p + N0, creator, b4, hipMemcpyHostToDevice, c->stream));
@@ -3843,15 +3746,15 @@ int sw_append_events(sw_ctx* c, int64_t K, const int32_t* creator, const int32_t
     HIPCHK(c, hipMemcpyAsync(c->d_seq.p + N0, seq.data(), b4, hipMemcpyHostToDevice, c->stream));
     if (bulk) {
         int verdict = 0x7fffffff;
-        HIPCHK(c, hipMemcpyAsync(c->d_err, &verdict, sizeof verdict, hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(c->d_err.p, &verdict, sizeof verdict, hipMemcpyHostToDevice, c->stream));
         hipLaunchKernelGGL(k_validate_other_parent, dim3((unsigned)((K + 255) / 256)), dim3(256), 0, c->stream,
-                           (const int*)c->d_cr.p, (const int*)c->d_op.p, (int)N0, (int)K, c->d_err);
+                           (const int*)c->d_cr.p, (const int*)c->d_op.p, (int)N0, (int)K, c->d_err.p);
         c->ctr.kernel_launches++;
-        HIPCHK(c, hipMemcpyAsync(&verdict, c->d_err, sizeof verdict, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(&verdict, c->d_err.p, sizeof verdict, hipMemcpyDeviceToHost, c->stream));
         // the payload is staged while the device validates
         if (stage) {
-            if (t) parallel_memcpy(c->h_pin, t, (size_t)K * 8);
-            if (sig64) parallel_memcpy(c->h_pin + (size_t)K * 8, sig64, (size_t)K * 64);
+            if (t) parallel_memcpy(c->h_pin.p, t, (size_t)K * 8);
+            if (sig64) parallel_memcpy(c->h_pin.p + (size_t)K * 8, sig64, (size_t)K * 64);
         }
         HIPCHK(c, hipStreamSynchronize(c->stream));
         if (verdict != 0x7fffffff)
@@ -3893,8 +3796,8 @@ int sw_append_events(sw_ctx* c, int64_t K, const int32_t* creator, const int32_t
     // and by find_order only, so a bulk append uploads them behind the call on their own stream
     hipStream_t ps = stage ? c->stream_io : c->stream;
     if (stage) {
-        if (t) PHIP(hipMemcpyAsync(c->d_t.p + N0, c->h_pin, (size_t)K * 8, hipMemcpyHostToDevice, ps));
-        if (sig64) PHIP(hipMemcpyAsync(c->d_sig.p + (size_t)N0 * 64, c->h_pin + (size_t)K * 8, (size_t)K * 64, hipMemcpyHostToDevice, ps));
+        if (t) PHIP(hipMemcpyAsync(c->d_t.p + N0, c->h_pin.p, (size_t)K * 8, hipMemcpyHostToDevice, ps));
+        if (sig64) PHIP(hipMemcpyAsync(c->d_sig.p + (size_t)N0 * 64, c->h_pin.p + (size_t)K * 8, (size_t)K * 64, hipMemcpyHostToDevice, ps));
     } else {
         if (t) PHIP(hipMemcpyAsync(c->d_t.p + N0, t, (size_t)K * 8, hipMemcpyHostToDevice, ps));
         if (sig64) PHIP(hipMemcpyAsync(c->d_sig.p + (size_t)N0 * 64, sig64, (size_t)K * 64, hipMemcpyHostToDevice, ps));
@@ -3973,16 +3876,8 @@ static int append_device_body(sw_ctx* c, int64_t K, const int32_t* d_creator, co
     CHK(dgrow(c, c->d_ht_stat, (size_t)(2 + 2 * nblk), 0));
     // (the pinned staging buffer may still feed the payload upload of an earlier bulk host append)
     if (c->payload_pending) { HIPCHK(c, hipEventSynchronize(c->ev_payload)); c->payload_pending = false; }
-    if ((size_t)K * 8 > c->h_pin_cap) {
-        if (c->h_pin) (void)hipHostFree(c->h_pin);
-        c->h_pin = nullptr; c->h_pin_cap = 0;
-        if (hipHostMalloc((void**)&c->h_pin, (size_t)K * 8, hipHostMallocDefault) != hipSuccess) {
-            (void)hipGetLastError();
-            return fail(c, SW_ENOMEM, "hipHostMalloc(%zu bytes) for the ingest read-back buffer failed", (size_t)K * 8);
-        }
-        c->h_pin_cap = (size_t)K * 8;
-    }
-    if (!c->ev_ht) HIPCHK(c, hipEventCreateWithFlags(&c->ev_ht, hipEventDisableTiming));
+    if (!c->h_pin.reserve((size_t)K * 8)) return fail(c, SW_ENOMEM, "hipHostMalloc(%zu bytes) for the ingest read-back buffer failed", (size_t)K * 8);
+    CHK(ensure_event(c, c->ev_ht));
     // ---- the context's stream waits for what the caller enqueued; parent arrays to the (uncommitted) tail
     UserStream bracket;
     CHK(bracket.join(c, us));
@@ -4017,7 +3912,7 @@ static int append_device_body(sw_ctx* c, int64_t K, const int32_t* d_creator, co
     c->ctr.kernel_launches += 5;
     HIPCHK(c, hipGetLastError());
     // ---- one read-back: verdict and tables; the always-complete host mirrors (creator, chain position) ride along
-    int32_t* pin_cr = (int32_t*)c->h_pin;
+    int32_t* pin_cr = (int32_t*)c->h_pin.p;
     int32_t* pin_seq = pin_cr + K;
     HIPCHK(c, hipMemcpyAsync(tab.data(), c->d_ing_tab.p, tab.size() * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(pin_cr, c->d_cr.p + N0, b4, hipMemcpyDeviceToHost, c->stream));
@@ -4165,11 +4060,7 @@ int payload_core(sw_ctx* c, int64_t K, const uint8_t* d_id32, const uint8_t* d_s
     int* g_cr = (int*)(B + o_gcr); int* g_sp = (int*)(B + o_gsp); int* g_op = (int*)(B + o_gop);
     double* g_t = d_t ? (double*)(B + o_gt) : nullptr;
     unsigned char* g_sig = d_sig64 ? B + o_gsig : nullptr;
-    if (!c->h_plcnt && hipHostMalloc((void**)&c->h_plcnt, (2 * PL_WAVE_BATCH + 2) * sizeof(int32_t), hipHostMallocDefault) != hipSuccess) {
-        (void)hipGetLastError();
-        c->h_plcnt = nullptr;
-        return fail(c, SW_ENOMEM, "hipHostMalloc for the wave counts failed");
-    }
+    if (!c->h_plcnt.reserve(2 * PL_WAVE_BATCH + 2)) return fail(c, SW_ENOMEM, "hipHostMalloc for the wave counts failed");
     UserStream bracket;   // (left by the destructor on a failure; a success has drained the stream)
     CHK(bracket.join(c, us));
     // ---- resolve: the payload's own table (lowest position of every id), local checks, parent references
@@ -4194,15 +4085,15 @@ int payload_core(sw_ctx* c, int64_t K, const uint8_t* d_id32, const uint8_t* d_s
                                pend + w + 1, acc + w, (const int*)pr, (const int*)d_creator, (const int*)c->d_cr.p, wave, (int*)d_out);
         c->ctr.kernel_launches += PL_WAVE_BATCH;
         HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipMemcpyAsync(c->h_plcnt, pend + w0, (PL_WAVE_BATCH + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipMemcpyAsync(c->h_plcnt + PL_WAVE_BATCH + 1, acc + w0, PL_WAVE_BATCH * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(c->h_plcnt.p, pend + w0, (PL_WAVE_BATCH + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(c->h_plcnt.p + PL_WAVE_BATCH + 1, acc + w0, PL_WAVE_BATCH * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
         for (int j = 0; j < PL_WAVE_BATCH; ++j) {
-            const int a = c->h_plcnt[PL_WAVE_BATCH + 1 + j];
+            const int a = c->h_plcnt.p[PL_WAVE_BATCH + 1 + j];
             if (a == 0) { W = w0 + j; break; }
             A += a;
         }
-        ub = c->h_plcnt[PL_WAVE_BATCH];
+        ub = c->h_plcnt.p[PL_WAVE_BATCH];
     }
     hipLaunchKernelGGL(rsv::k_pl_leftover, ev_grid, dim3(256), 0, c->stream, (const int*)wave, (int)K, (int*)d_out);
     c->ctr.kernel_launches++;
@@ -4486,9 +4377,9 @@ static int do_cansee_range(sw_ctx* c, int64_t first, int64_t K) {
     if ((int)c->ranges.size() >= SW_RANGE_SLOTS) return fail(c, SW_ERANGE, "more than %d ranges between two rewinds", SW_RANGE_SLOTS);
     for (const auto& pr : c->present)
         if (first < pr.second && first + K > pr.first) return fail(c, SW_EINVAL, "sw_cansee_range: rows [%lld, %lld) are present already", (long long)pr.first, (long long)pr.second);
-    if (!c->d_rprov) {
-        HIPCHK(c, hipMalloc((void**)&c->d_rprov, (size_t)SW_RANGE_SLOTS * (SW_MAX_CHUNKS + 1) * sizeof(unsigned)));
-        if (!c->ev_user) HIPCHK(c, hipEventCreateWithFlags(&c->ev_user, hipEventDisableTiming));   // (an earlier call may have made it)
+    if (!c->d_rprov.p) {
+        CHK(dgrow(c, c->d_rprov, (size_t)SW_RANGE_SLOTS * (SW_MAX_CHUNKS + 1), 0));
+        CHK(ensure_event(c, c->ev_user));
     }
     if (c->d_L.cap < table_elems(c, c->cap)) return fail(c, SW_EIO, "the can_see table has no halo scratch rows (internal)");
     sw_ctx::RangeRec r;
@@ -4517,7 +4408,7 @@ static int do_cansee_range(sw_ctx* c, int64_t first, int64_t K) {
     hipLaunchKernelGGL(k_chain_bounds, dim3((unsigned)cc.size()), dim3(np), 0, cs, (const int*)c->d_chain_start.p,
                        (const int*)c->d_chain_cnt.p, (const int*)c->d_chain_ev.p, (const long long*)(c->d_rcuts.p + r.row0), np,
                        c->d_rbnd.p + (size_t)r.row0 * np);
-    unsigned* prov = c->d_rprov + (size_t)r.slot * (SW_MAX_CHUNKS + 1);
+    unsigned* prov = c->d_rprov.p + (size_t)r.slot * (SW_MAX_CHUNKS + 1);
     HIPCHK(c, hipMemsetAsync(prov, 0, (SW_MAX_CHUNKS + 1) * sizeof(unsigned), cs));
     c->ctr.kernel_launches++;
     CHK(launch_cansee_plan<NW>(c, r.pl, (const int*)c->d_rbnd.p + (size_t)r.row0 * np, prov, prov + SW_MAX_CHUNKS, 0, true, 0, 0));
@@ -4550,7 +4441,7 @@ int sw_cansee_repair(sw_ctx* c, int64_t first, int64_t K) {
         for (const auto& pr : c->present) if (pr.first <= covered) covered = std::max(covered, pr.second);
         if (covered < first) return fail(c, SW_EINVAL, "sw_cansee_repair: the rows [%lld, %lld) below the range are not present yet", (long long)covered, (long long)first);
         const int np = c->npad;
-        unsigned* prov = c->d_rprov + (size_t)r.slot * (SW_MAX_CHUNKS + 1);
+        unsigned* prov = c->d_rprov.p + (size_t)r.slot * (SW_MAX_CHUNKS + 1);
         const int k_from = r.pl.w[0] > 0 ? 0 : 1;   // (a range that starts at event 0 has no halo in front of its first chunk)
         int rc = SW_EINVAL;
         switch (c->nw) {
@@ -4598,11 +4489,11 @@ int sw_import_rows(sw_ctx* c, int64_t first, int64_t K, const void* src_device, 
 int sw_get_range_stats(sw_ctx* c, int64_t* provisional, int64_t* repaired, int64_t* resweeps) {
     if (!c) return SW_EINVAL;
     int64_t pv = 0, rp = 0, rs = 0;
-    if (c->d_rprov && !c->ranges.empty()) {
+    if (c->d_rprov.p && !c->ranges.empty()) {
         HIPCHK(c, hipSetDevice(c->device));
         HIPCHK(c, hipStreamSynchronize(c->stream_cs));
         std::vector<unsigned> h((size_t)SW_RANGE_SLOTS * (SW_MAX_CHUNKS + 1));
-        HIPCHK(c, hipMemcpy(h.data(), c->d_rprov, h.size() * sizeof(unsigned), hipMemcpyDeviceToHost));
+        HIPCHK(c, hipMemcpy(h.data(), c->d_rprov.p, h.size() * sizeof(unsigned), hipMemcpyDeviceToHost));
         for (const auto& r : c->ranges) {
             const unsigned* p = h.data() + (size_t)r.slot * (SW_MAX_CHUNKS + 1);
             const int Cc = c->chunk_cfg == 1 ? 2 : 4;
@@ -4628,14 +4519,14 @@ int sw_set_window(sw_ctx* c, int enable, int chunk_mb) {
         if (c->vm.active) {
             HIPCHK(c, hipDeviceSynchronize());
             vm_destroy(c);
-            c->d_L.p = nullptr; c->d_L.cap = 0;
+            c->d_L.release();
             if (c->cap) CHK(dgrow(c, c->d_L, table_elems(c, c->cap), 0));   // (with the halo scratch rows: ADVICE r3)
         }
         return SW_OK;
     }
     if (c->vm.active) return SW_OK;
     HIPCHK(c, hipDeviceSynchronize());
-    dfree(c->d_L);
+    c->d_L.reset();
     hipMemAllocationProp prop{};
     prop.type = hipMemAllocationTypePinned;
     prop.location.type = hipMemLocationTypeDevice;
@@ -4658,8 +4549,7 @@ int sw_set_window(sw_ctx* c, int enable, int chunk_mb) {
     v.handle.assign(va / v.chunk, hipMemGenericAllocationHandle_t{});
     v.mapped.assign(va / v.chunk, 0);
     v.active = true;
-    c->d_L.p = (int32_t*)base;
-    c->d_L.cap = va / sizeof(int32_t);
+    c->d_L.alias((int32_t*)base, va / sizeof(int32_t));
     c->first_resident = 0;
     return SW_OK;
 }
@@ -4782,7 +4672,7 @@ int sw_rewind(sw_ctx* c) {
         v.base = (char*)base;
         v.lo = 0; v.hi = 0;
         c->vm_scratch_ok = false;
-        c->d_L.p = (int32_t*)base;
+        c->d_L.alias((int32_t*)base, c->d_L.cap);
         c->first_resident = 0;
         CHK(vm_ensure(c, (size_t)c->N * c->npad * sizeof(int32_t)));
     }
@@ -5995,11 +5885,11 @@ int sw_get_consensus_stats(sw_ctx* c, int64_t* record_calls, int64_t* recorded_e
 
 // (one counter lives on the device: the events the finalize check sent back to their rows)
 static int refresh_device_counters(sw_ctx* c) {
-    if (!c->d_fin) return SW_OK;
+    if (!c->d_fin.p) return SW_OK;
     unsigned long long tot = 0;
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream_aux));
-    HIPCHK(c, hipMemcpy(&tot, c->d_fin + 2, sizeof tot, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(&tot, c->d_fin.p + 2, sizeof tot, hipMemcpyDeviceToHost));
     c->ctr.finalize_from_rows = (int64_t)tot;
     return SW_OK;
 }
@@ -6026,19 +5916,27 @@ int sw_set_profiling(sw_ctx* c, int enable) {
 
 int sw_debug_clocks(sw_ctx* c, unsigned long long* out, int64_t cap_words) {
     if (!c || !out) return SW_EINVAL;
-    if (!c->d_dbg) return fail(c, SW_EINVAL, "sw_debug_clocks: the context was not created with SW_DEBUG_CLOCKS=1");
+    if (!c->d_dbg.p) return fail(c, SW_EINVAL, "sw_debug_clocks: the context was not created with SW_DEBUG_CLOCKS=1");
     const int64_t nw = std::min<int64_t>(cap_words, (int64_t)SW_DBG_MAX_ITERS * 32);
     HIPCHK(c, hipDeviceSynchronize());
-    HIPCHK(c, hipMemcpy(out, c->d_dbg, (size_t)nw * 8, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(out, c->d_dbg.p, (size_t)nw * 8, hipMemcpyDeviceToHost));
+    return SW_OK;
+}
+
+int sw_debug_live_resources(int64_t* device_bytes, int64_t* pinned_bytes, int64_t* events, int64_t* streams) {
+    if (device_bytes) *device_bytes = owned::live.device_bytes.load(std::memory_order_relaxed);
+    if (pinned_bytes) *pinned_bytes = owned::live.pinned_bytes.load(std::memory_order_relaxed);
+    if (events) *events = owned::live.events.load(std::memory_order_relaxed);
+    if (streams) *streams = owned::live.streams.load(std::memory_order_relaxed);
     return SW_OK;
 }
 
 int sw_debug_block_clocks(sw_ctx* c, unsigned long long* out, int64_t cap_words) {
     if (!c || !out) return SW_EINVAL;
-    if (!c->d_dbg_blk) return fail(c, SW_EINVAL, "sw_debug_block_clocks: the context was not created with SW_DEBUG_CLOCKS=3");
+    if (!c->d_dbg_blk.p) return fail(c, SW_EINVAL, "sw_debug_block_clocks: the context was not created with SW_DEBUG_CLOCKS=3");
     const int64_t nw = std::min<int64_t>(cap_words, (int64_t)SW_DBG_MAX_ITERS * 2 * 2048);
     HIPCHK(c, hipDeviceSynchronize());
-    HIPCHK(c, hipMemcpy(out, c->d_dbg_blk, (size_t)nw * 8, hipMemcpyDeviceToHost));
+    HIPCHK(c, hipMemcpy(out, c->d_dbg_blk.p, (size_t)nw * 8, hipMemcpyDeviceToHost));
     return SW_OK;
 }
 
@@ -6836,15 +6734,11 @@ int pull_begin(sw_ctx* dst, int64_t dst_head, sw_ctx* src, bool validate, bool d
     if (data && src->n_data != src->N)
         return fail(dst, SW_ENOTSUP, "%s: %lld of the peer's %lld stored events have no data entry (sw_set_event_data first)", what, (long long)(src->N - src->n_data), (long long)src->N);
     HIPCHK(dst, hipSetDevice(dst->device));
-    if (validate && !dst->h_pkcnt && hipHostMalloc((void**)&dst->h_pkcnt, sizeof(int32_t), hipHostMallocDefault) != hipSuccess) {
-        (void)hipGetLastError();
-        dst->h_pkcnt = nullptr;
-        return fail(dst, SW_ENOMEM, "hipHostMalloc for the count of valid events failed");
-    }
+    if (validate && !dst->h_pkcnt.reserve(1)) return fail(dst, SW_ENOMEM, "hipHostMalloc for the count of valid events failed");
     CHK(heights_on_device(dst));
     const int np = dst->npad;
     CHK(dgrow(dst, dst->d_q, (size_t)3 * np, 0));
-    if (!dst->ev_user) HIPCHK(dst, hipEventCreateWithFlags(&dst->ev_user, hipEventDisableTiming));
+    CHK(ensure_event(dst, dst->ev_user));
     hipLaunchKernelGGL(k_known_heights, dim3(1), dim3(np), 0, dst->stream, (const int*)dst->d_L.p, (const int*)dst->d_ht.p, (int)dst_head, np, dst->d_q.p);
     dst->ctr.kernel_launches++;
     HIPCHK(dst, hipGetLastError());
@@ -6951,7 +6845,7 @@ int ingest_arrays(sw_ctx* dst, hipStream_t from, int64_t total, const ExportArra
                            B + o_ok, (const unsigned char*)(B + o_enc), (int*)(B + o_cnt));
         dst->ctr.kernel_launches++;
         HIPCHK(dst, hipGetLastError());
-        HIPCHK(dst, hipMemcpyAsync(dst->h_pkcnt, B + o_cnt, sizeof(int32_t), hipMemcpyDeviceToHost, dst->stream));
+        HIPCHK(dst, hipMemcpyAsync(dst->h_pkcnt.p, B + o_cnt, sizeof(int32_t), hipMemcpyDeviceToHost, dst->stream));
         ok = B + o_ok;
     }
     int64_t stored = 0;
@@ -6963,7 +6857,7 @@ int ingest_arrays(sw_ctx* dst, hipStream_t from, int64_t total, const ExportArra
     const hipError_t drained = hipStreamSynchronize(dst->stream);   // src's scratch is free again only once dst has read it
     if (rc != SW_OK) return rc;
     HIPCHK(dst, drained);
-    if (validate && n_valid) *n_valid = *dst->h_pkcnt;
+    if (validate && n_valid) *n_valid = *dst->h_pkcnt.p;
     if (n_stored) *n_stored = stored;
     return SW_OK;
 }
@@ -7487,12 +7381,8 @@ int wire_ingest_run(sw_ctx* c, const uint8_t* d_msg, int64_t msg_bytes, bool val
         return fail(c, SW_ENOTSUP, "%s: %lld of the %lld stored events have no id (sw_set_event_ids first)", what, (long long)(c->N - c->n_ids), (long long)c->N);
     if (with_data && c->n_data != c->N)
         return fail(c, SW_ENOTSUP, "%s: %lld of the %lld stored events have no data entry (sw_set_event_data first)", what, (long long)(c->N - c->n_data), (long long)c->N);
-    if (validate && !c->h_pkcnt && hipHostMalloc((void**)&c->h_pkcnt, sizeof(int32_t), hipHostMallocDefault) != hipSuccess) {
-        (void)hipGetLastError();
-        c->h_pkcnt = nullptr;
-        return fail(c, SW_ENOMEM, "hipHostMalloc for the count of valid events failed");
-    }
-    if (!c->ev_user) HIPCHK(c, hipEventCreateWithFlags(&c->ev_user, hipEventDisableTiming));
+    if (validate && !c->h_pkcnt.reserve(1)) return fail(c, SW_ENOMEM, "hipHostMalloc for the count of valid events failed");
+    CHK(ensure_event(c, c->ev_user));
     const int64_t kcap = std::min<int64_t>(msg_bytes / wir::REC_MIN, 0x3fffffff), dcap = msg_bytes;
     const size_t k = (size_t)kcap;
     Carve cv;
@@ -8330,11 +8220,6 @@ k_blake2b_batch(const uint8_t* __restrict__ msgs, const long long* __restrict__ 
     if (i >= K) return;
     swc::blake2b_256(msgs + off[i], (uint64_t)(off[i + 1] - off[i]), out + (size_t)i * 32);
 }
-struct DevTmp {
-    void* p = nullptr;
-    ~DevTmp() { if (p) (void)hipFree(p); }
-    hipError_t alloc(size_t n) { return hipMalloc(&p, n ? n : 1); }
-};
 int crypto_batch(int device, int64_t K, const uint8_t* msgs, const int64_t* off, const uint8_t* sig, const uint8_t* pk, uint8_t* out, bool verify) {
     if (K < 0 || (K > 0 && (!msgs || !off || !out || (verify && (!sig || !pk))))) return fail(nullptr, SW_EINVAL, "NULL batch arrays");
     if (K == 0) return SW_OK;
@@ -8345,16 +8230,16 @@ int crypto_batch(int device, int64_t K, const uint8_t* msgs, const int64_t* off,
     HIPCHK(nullptr, hipSetDevice(device));
     const size_t nbytes = (size_t)off[K];
     const size_t out_per = verify ? 1 : 32;
-    DevTmp d_m, d_off, d_sig, d_pk, d_out;
-    HIPCHK(nullptr, d_m.alloc(nbytes));
-    HIPCHK(nullptr, d_off.alloc((size_t)(K + 1) * 8));
-    HIPCHK(nullptr, d_out.alloc((size_t)K * out_per));
+    DBuf<unsigned char> d_m, d_off, d_sig, d_pk, d_out;
+    CHK(dgrow(nullptr, d_m, std::max<size_t>(nbytes, 1), 0));
+    CHK(dgrow(nullptr, d_off, (size_t)(K + 1) * 8, 0));
+    CHK(dgrow(nullptr, d_out, (size_t)K * out_per, 0));
     HIPCHK(nullptr, hipMemcpy(d_m.p, msgs, nbytes, hipMemcpyHostToDevice));
     HIPCHK(nullptr, hipMemcpy(d_off.p, off, (size_t)(K + 1) * 8, hipMemcpyHostToDevice));
     const unsigned blocks = (unsigned)((K + 63) / 64);
     if (verify) {
-        HIPCHK(nullptr, d_sig.alloc((size_t)K * 64));
-        HIPCHK(nullptr, d_pk.alloc((size_t)K * 32));
+        CHK(dgrow(nullptr, d_sig, (size_t)K * 64, 0));
+        CHK(dgrow(nullptr, d_pk, (size_t)K * 32, 0));
         HIPCHK(nullptr, hipMemcpy(d_sig.p, sig, (size_t)K * 64, hipMemcpyHostToDevice));
         HIPCHK(nullptr, hipMemcpy(d_pk.p, pk, (size_t)K * 32, hipMemcpyHostToDevice));
         hipLaunchKernelGGL(k_verify_batch, dim3(blocks), dim3(64), 0, nullptr, (const uint8_t*)d_m.p, (const long long*)d_off.p,

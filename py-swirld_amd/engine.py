@@ -1397,6 +1397,19 @@ class Hashgraph:
         self._chk(self._L.sw_synchronize(self._h))
 
 
+LiveResources = collections.namedtuple("LiveResources", "device_bytes pinned_bytes events streams")
+
+
+def live_resources():
+    """What the library's contexts and calls hold in this process right now (sw_debug_live_resources): bytes of device
+    memory, bytes of pinned host memory, events, streams.  Equal before a context is made and after it is closed."""
+    v = [C.c_int64() for _ in range(4)]
+    rc = _lib.load().sw_debug_live_resources(*[C.byref(x) for x in v])
+    if rc != 0:
+        raise SwirldHipError(rc, "sw_debug_live_resources")
+    return LiveResources(*[int(x.value) for x in v])
+
+
 def _pack_messages(msgs):
     off = np.zeros(len(msgs) + 1, np.int64)
     np.cumsum([len(m) for m in msgs], out=off[1:])
