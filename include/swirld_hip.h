@@ -1076,6 +1076,75 @@ int sw_export_vote_entries(sw_ctx* ctx, int64_t first, int64_t cap_entries, int3
 int sw_get_vote_store_stats(sw_ctx* ctx, int64_t* entries, int64_t* capacity, int64_t* bytes, int64_t* grows, int64_t* imported,
                             int64_t* lookups, int64_t* exported);
 
+/*
+ * BATCHES OF SMALL HASHGRAPHS (csrc/batch.hip.h, csrc/batch_layout.h).  A batch holds B independent
+ * hashgraphs of ONE member count in one device allocation; a step runs, for every hashgraph that takes part, the
+ * reference's main-loop step (swirld.py:325-328: divide_rounds(new events), decide_fame(), find_order(new_c)) by one
+ * wavefront per hashgraph in ONE launch — the statements of the exact path (csrc/exact.hip.h), so results are the
+ * reference's with or without forks.  What a batch does not have: growth (all capacity is fixed at create), mixed member
+ * counts, the event-keyed vote log, an id index, gossip, crypto — those remain features of a sw_ctx.
+ *
+ * sw_batch_bytes     the device bytes sw_batch_create will allocate (-1 for a shape it refuses: an argument out of range, or
+ *                    a total of 2^62 bytes or more — sw_batch_create answers SW_EINVAL to the same shapes): a head of 576 B per
+ *                    hashgraph and, per hashgraph, with np = n_members rounded up to a multiple of 16, E = cap_events,
+ *                    R = cap_rounds, every term rounded up to 64 B:
+ *                      4 E np (can_see) + 131 E + 21 (events, queue, items, log) + R (9 np + 10) (round tables)
+ *                      + 2 n^2 R (vote layers) + 26 np + 192.
+ * sw_batch_create    stake = NULL (unit stake) or uint64 [B][n_members], per hashgraph within the limits of sw_create
+ *                    (SW_EOVERFLOW otherwise).  cap_events >= 1 events per hashgraph; cap_rounds = 0 means cap_events + 3,
+ *                    which always suffices (round <= height) — lower it to save memory (the vote layers take 2 n^2 bytes
+ *                    per round): an append whose greatest height + 3 exceeds it is refused.  An allocation failure is
+ *                    SW_ENOMEM with the byte count in sw_batch_last_error(NULL).
+ * sw_batch_append    the new events of all hashgraphs, concatenated: hashgraph b gets [off[b], off[b + 1]) (off[0] = 0),
+ *                    parents are indices LOCAL to the hashgraph.  t and sig64 may be NULL (zeros).  Validated per
+ *                    hashgraph like sw_append_events on the exact path (creator range, 0 or 2 parents, parents earlier,
+ *                    self-parent by the creator, other-parent by another member); forks are stored.  ATOMIC over the
+ *                    batch: one bad event anywhere is SW_EINVAL, the message names hashgraph and event, nothing is
+ *                    stored anywhere.  SW_ERANGE, nothing stored, beyond cap_events or cap_rounds.
+ * sw_batch_step      hashgraph b divides its next K[b] undivided events, then decides fame and orders; K[b] = 0: it sits
+ *                    the step out (no decide_fame call is made for it — the call schedule is part of the reference's
+ *                    semantics); K = NULL: every hashgraph takes all its undivided events (none: it sits out).  SW_ERANGE,
+ *                    nothing run, if a K[b] exceeds the undivided events.  A hashgraph whose step ends in one of the
+ *                    reference's exceptions (KeyError, the IndexError of swirld.py:305) is FROZEN: its status is
+ *                    (stage, code, event) and it is left as the reference's Node is at the exception — divided rounds, settled fame,
+ *                    and the ordered events of the rounds of new_c that completed before the one that raised (swirld.py:307-309
+ *                    append per round; the summary's n_ordered counts them) —, all readable; later steps skip it whatever K says.  The
+ *                    call returns SW_OK with *n_failed (nullable) = hashgraphs frozen by THIS step.
+ * sw_batch_get_summary   out[B][SW_BATCH_SUMMARY_WORDS]: events, divided, rounds, ordered (total), then the last step's
+ *                    n_new_rounds and n_ordered, then the status: stage (SW_BATCH_STAGE_*), code (-2 KeyError, -3 IndexError,
+ *                    -22), event (meaningful with a stage: the event the IndexError or a missing round was met at, -1 if none).  No device access: the values of the last step's read-back.
+ * sw_batch_get_*     per hashgraph b, a copy out of its slab, with the meaning of the sw_get_* of the same name;
+ *                    sw_batch_get_new_rounds: sorted(new_c) of b's last step; sw_batch_get_transactions: the ordered events
+ *                    [first, first + K) with their round received and consensus timestamp (each array nullable).
+ */
+typedef struct sw_batch sw_batch;
+#define SW_BATCH_SUMMARY_WORDS 9
+#define SW_BATCH_STAGE_NONE   0
+#define SW_BATCH_STAGE_DIVIDE 1
+#define SW_BATCH_STAGE_FAME   2
+#define SW_BATCH_STAGE_ORDER  3
+int64_t sw_batch_bytes(int64_t B, int n_members, int64_t cap_events, int64_t cap_rounds);
+int sw_batch_create(int64_t B, int n_members, const uint64_t* stake, int coin_period, int64_t cap_events, int64_t cap_rounds, int device,
+                    sw_batch** out);
+int sw_batch_destroy(sw_batch* batch);
+const char* sw_batch_last_error(const sw_batch* batch);   /* batch may be NULL: last create() error */
+int sw_batch_shape(sw_batch* batch, int64_t* B, int* n_members, int* npad, int64_t* cap_events, int64_t* cap_rounds, int64_t* bytes);
+int sw_batch_append(sw_batch* batch, const int64_t* off, const int32_t* creator, const int32_t* self_parent, const int32_t* other_parent,
+                    const double* t, const uint8_t* sig64);
+int sw_batch_step(sw_batch* batch, const int64_t* K, int64_t* n_failed);
+int sw_batch_get_summary(sw_batch* batch, int64_t* out);
+int sw_batch_get_height(sw_batch* batch, int64_t b, int64_t first, int64_t K, int32_t* out);
+int sw_batch_get_round(sw_batch* batch, int64_t b, int64_t first, int64_t K, int32_t* out);
+int sw_batch_get_can_see(sw_batch* batch, int64_t b, int64_t first, int64_t K, int32_t* out);
+int sw_batch_get_witnesses(sw_batch* batch, int64_t b, int r0, int r1, int32_t* out);
+int sw_batch_get_witness_order(sw_batch* batch, int64_t b, int r, int32_t* members, int* n_out);
+int sw_batch_get_famous(sw_batch* batch, int64_t b, int r0, int r1, int8_t* out);
+int sw_batch_get_famous_events(sw_batch* batch, int64_t b, int64_t first, int64_t K, int8_t* out);
+int sw_batch_get_consensus(sw_batch* batch, int64_t b, int r0, int r1, uint8_t* out);
+int sw_batch_get_new_rounds(sw_batch* batch, int64_t b, int32_t* out, int cap, int* n_out);
+int sw_batch_get_transactions(sw_batch* batch, int64_t b, int64_t first, int64_t K, int32_t* events, int32_t* round_received,
+                              double* consensus_time);
+
 /* Block until all work queued on the context's stream is complete. */
 int sw_synchronize(sw_ctx* ctx);
 

@@ -175,6 +175,26 @@ SIGNATURES = {
     "sw_export_vote_entries_device": (C.c_int, [_P, C.c_int64, C.c_int64, _P, _P, _P, C.POINTER(C.c_int64), _P]),
     "sw_export_vote_entries": (C.c_int, [_P, C.c_int64, C.c_int64, _P, _P, _P, C.POINTER(C.c_int64)]),
     "sw_get_vote_store_stats": (C.c_int, [_P] + [C.POINTER(C.c_int64)] * 7),
+    # batches of small hashgraphs (csrc/batch.hip.h)
+    "sw_batch_bytes": (C.c_int64, [C.c_int64, C.c_int, C.c_int64, C.c_int64]),
+    "sw_batch_create": (C.c_int, [C.c_int64, C.c_int, _P, C.c_int, C.c_int64, C.c_int64, C.c_int, C.POINTER(_P)]),
+    "sw_batch_destroy": (C.c_int, [_P]),
+    "sw_batch_last_error": (C.c_char_p, [_P]),
+    "sw_batch_shape": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int), C.POINTER(C.c_int), C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                                 C.POINTER(C.c_int64)]),
+    "sw_batch_append": (C.c_int, [_P, _P, _P, _P, _P, _P, _P]),
+    "sw_batch_step": (C.c_int, [_P, _P, C.POINTER(C.c_int64)]),
+    "sw_batch_get_summary": (C.c_int, [_P, _P]),
+    "sw_batch_get_height": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int64, _P]),
+    "sw_batch_get_round": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int64, _P]),
+    "sw_batch_get_can_see": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int64, _P]),
+    "sw_batch_get_witnesses": (C.c_int, [_P, C.c_int64, C.c_int, C.c_int, _P]),
+    "sw_batch_get_witness_order": (C.c_int, [_P, C.c_int64, C.c_int, _P, C.POINTER(C.c_int)]),
+    "sw_batch_get_famous": (C.c_int, [_P, C.c_int64, C.c_int, C.c_int, _P]),
+    "sw_batch_get_famous_events": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int64, _P]),
+    "sw_batch_get_consensus": (C.c_int, [_P, C.c_int64, C.c_int, C.c_int, _P]),
+    "sw_batch_get_new_rounds": (C.c_int, [_P, C.c_int64, _P, C.c_int, C.POINTER(C.c_int)]),
+    "sw_batch_get_transactions": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int64, _P, _P, _P]),
     "sw_set_window": (C.c_int, [_P, C.c_int, C.c_int]),
     "sw_get_window": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "sw_set_window_lapse": (C.c_int, [_P, C.c_int64]),

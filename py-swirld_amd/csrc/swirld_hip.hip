@@ -30,6 +30,7 @@
 #include "sign.hip.h"
 #include "data.hip.h"
 #include "exact.hip.h"
+#include "batch.hip.h"
 #include "ingest.hip.h"
 #include "resolve.hip.h"
 #include "gossip.hip.h"
@@ -8262,3 +8263,6 @@ int sw_crypto_hash_batch(int device, int64_t K, const uint8_t* msgs, const int64
     return crypto_batch(device, K, msgs, msg_off, nullptr, nullptr, out32, false);
 }
 }  // extern "C"
+
+// ---- batches of small hashgraphs: one wavefront each, one launch (batch.hip.h) ----
+#include "batch_api.hip.h"

@@ -1397,6 +1397,207 @@ class Hashgraph:
         self._chk(self._L.sw_synchronize(self._h))
 
 
+BatchSummary = collections.namedtuple("BatchSummary", "events divided rounds ordered n_new_rounds n_ordered stage code event")
+BATCH_STAGES = {0: None, 1: "divide", 2: "fame", 3: "order"}
+
+
+class HashgraphBatch:
+    """B independent hashgraphs of one member count in one device allocation (sw_batch_*, csrc/batch.hip.h): a step runs the
+    reference's main-loop step — divide_rounds(new events), decide_fame(), find_order(new_c) — for every hashgraph that
+    takes part, one wavefront each, in one launch.  Exact with or without forks.  All capacity is fixed here: cap_events
+    events per hashgraph, cap_rounds rounds (0: cap_events + 3, which always suffices; the vote layers take 2 n^2 bytes per
+    round, so lower it where memory matters).  No id index, gossip, crypto or event-keyed vote log: those are Hashgraph's."""
+
+    def __init__(self, B, n_members, stake=None, coin_period=6, cap_events=1024, cap_rounds=0, device=0):
+        self._L = _lib.load()
+        self.B, self.n = int(B), int(n_members)
+        st = None
+        if stake is not None:
+            raw = np.asarray(stake)
+            if raw.shape == (self.n,):
+                raw = np.broadcast_to(raw, (self.B, self.n))
+            if raw.shape != (self.B, self.n):
+                raise ValueError("stake must have one entry per member, or one row of them per hashgraph")
+            if raw.dtype.kind not in "iu":
+                as_f = raw.astype(np.float64)
+                if not np.all(np.isfinite(as_f)) or np.any(as_f != np.floor(as_f)):
+                    raise ValueError("stakes must be integers")
+            if np.any(raw.astype(np.float64) < 0):
+                raise ValueError("stakes must be non-negative")
+            st = np.ascontiguousarray(raw, np.uint64)
+        self._h = C.c_void_p()
+        rc = self._L.sw_batch_create(self.B, self.n, _p(st), int(coin_period), int(cap_events), int(cap_rounds), int(device), C.byref(self._h))
+        if rc != 0:
+            raise SwirldHipError(rc, (self._L.sw_batch_last_error(None) or b"").decode())
+        v = [C.c_int64(), C.c_int(), C.c_int(), C.c_int64(), C.c_int64(), C.c_int64()]
+        self._chk(self._L.sw_batch_shape(self._h, *[C.byref(x) for x in v]))
+        self.npad, self.cap_events, self.cap_rounds, self.device_bytes = int(v[2].value), int(v[3].value), int(v[4].value), int(v[5].value)
+
+    @staticmethod
+    def bytes_needed(B, n_members, cap_events, cap_rounds=0):
+        """Device bytes a batch of this shape allocates (sw_batch_bytes)."""
+        return int(_lib.load().sw_batch_bytes(int(B), int(n_members), int(cap_events), int(cap_rounds)))
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            self._L.sw_batch_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _chk(self, rc):
+        if rc != 0:
+            raise SwirldHipError(rc, (self._L.sw_batch_last_error(self._h) or b"").decode())
+
+    def append(self, streams=None, *, off=None, creator=None, self_parent=None, other_parent=None, t=None, sig=None):
+        """New events for every hashgraph: `streams` is a list of B entries, each None (nothing) or a tuple (creator,
+        self_parent, other_parent[, t[, sig]]) with parents as indices local to the hashgraph; or the same as CSR arrays
+        (off of B + 1 entries and the concatenated arrays).  Atomic over the batch: one bad event anywhere stores nothing."""
+        if streams is not None:
+            if len(streams) != self.B:
+                raise ValueError("one entry per hashgraph (None for nothing)")
+            empty = (np.zeros(0, np.int32),) * 3
+            parts = [empty if s is None else tuple(s) for s in streams]
+            off = np.zeros(self.B + 1, np.int64)
+            np.cumsum([len(p[0]) for p in parts], out=off[1:])
+            creator, self_parent, other_parent = (np.concatenate([np.asarray(p[i], np.int32) for p in parts]) for i in range(3))
+            has_t = [len(p) > 3 and p[3] is not None for p in parts if len(p[0])]
+            has_s = [len(p) > 4 and p[4] is not None for p in parts if len(p[0])]
+            if any(has_t) != all(has_t) or any(has_s) != all(has_s):
+                raise ValueError("timestamps / signatures for every hashgraph of the call, or for none")
+            if has_t and has_t[0]:
+                t = np.concatenate([np.asarray(p[3], np.float64) for p in parts if len(p[0])])
+            if has_s and has_s[0]:
+                sig = np.concatenate([np.asarray(p[4], np.uint8).reshape(-1, 64) for p in parts if len(p[0])])
+        off = np.ascontiguousarray(off, np.int64)
+        if off.shape != (self.B + 1,):
+            raise ValueError("off must have B + 1 entries")
+        total = int(off[-1])
+        creator = np.ascontiguousarray(creator, np.int32)
+        sp = np.ascontiguousarray(self_parent, np.int32)
+        op = np.ascontiguousarray(other_parent, np.int32)
+        if not (creator.shape == sp.shape == op.shape == (total,)):
+            raise ValueError("creator / parents must have off[B] entries")
+        t = None if t is None else np.ascontiguousarray(t, np.float64)
+        sig = None if sig is None else np.ascontiguousarray(sig, np.uint8).reshape(total, 64)
+        if t is not None and t.shape != (total,):
+            raise ValueError("t must have off[B] entries")
+        self._chk(self._L.sw_batch_append(self._h, _p(off), _p(creator), _p(sp), _p(op), _p(t), _p(sig)))
+
+    def step(self, K=None, collect=True):
+        """One main-loop step.  K: events to divide per hashgraph (0: it sits the step out), None: all undivided ones.
+        Returns the number of hashgraphs this step froze when collect is False; else a list of B entries: (new_c,
+        transactions) of the step, or None for a hashgraph that sat out or is frozen (see summary())."""
+        Ka = None
+        if K is not None:
+            Ka = np.ascontiguousarray(K, np.int64)
+            if Ka.shape != (self.B,):
+                raise ValueError("K must have one entry per hashgraph")
+        before = self.summary_array() if collect else None
+        failed = C.c_int64(0)
+        self._chk(self._L.sw_batch_step(self._h, _p(Ka), C.byref(failed)))
+        self.n_failed = int(failed.value)
+        if not collect:
+            return self.n_failed
+        now = self.summary_array()
+        out = [None] * self.B
+        took = (now[:, 1] != before[:, 1]) & (now[:, 6] == 0)
+        for b in np.nonzero(took)[0]:   # (counts from the read-back in hand: one or two copies per hashgraph that took part)
+            b = int(b)
+            n_new, n_out = int(now[b, 4]), int(now[b, 5])
+            tx = self.transactions(b, int(now[b, 3]) - n_out, n_out) if n_out else np.zeros(0, np.int32)
+            out[b] = (self.new_rounds(b, n_new) if n_new else np.zeros(0, np.int32), tx)
+        return out
+
+    def summary_array(self):
+        """int64 [B][9]: events, divided, rounds, ordered, the last step's n_new_rounds and n_ordered, status (stage, code, event)."""
+        out = np.zeros((self.B, 9), np.int64)
+        self._chk(self._L.sw_batch_get_summary(self._h, _p(out)))
+        return out
+
+    def summary(self, b=None):
+        s = self.summary_array()
+        if b is not None:
+            return BatchSummary(*[int(x) for x in s[b]])
+        return [BatchSummary(*[int(x) for x in row]) for row in s]
+
+    def _events(self, b):
+        return self.summary(b).events
+
+    def heights(self, b, first=0, K=None):
+        K = self._events(b) - first if K is None else K
+        out = np.empty(K, np.int32)
+        self._chk(self._L.sw_batch_get_height(self._h, b, first, K, _p(out)))
+        return out
+
+    def rounds(self, b, first=0, K=None):
+        K = self._events(b) - first if K is None else K
+        out = np.empty(K, np.int32)
+        self._chk(self._L.sw_batch_get_round(self._h, b, first, K, _p(out)))
+        return out
+
+    def can_see(self, b, first=0, K=None):
+        K = self.summary(b).divided - first if K is None else K
+        out = np.empty((K, self.n), np.int32)
+        self._chk(self._L.sw_batch_get_can_see(self._h, b, first, K, _p(out)))
+        return out
+
+    def witnesses(self, b, r0=0, r1=None):
+        r1 = self.summary(b).rounds if r1 is None else r1
+        out = np.empty((r1 - r0, self.n), np.int32)
+        self._chk(self._L.sw_batch_get_witnesses(self._h, b, r0, r1, _p(out)))
+        return out
+
+    def witness_order(self, b, r):
+        out = np.empty(self.n, np.int32)
+        cnt = C.c_int(0)
+        self._chk(self._L.sw_batch_get_witness_order(self._h, b, r, _p(out), C.byref(cnt)))
+        return out[:cnt.value].copy()
+
+    def famous(self, b, r0=0, r1=None):
+        r1 = self.summary(b).rounds if r1 is None else r1
+        out = np.empty((r1 - r0, self.n), np.int8)
+        self._chk(self._L.sw_batch_get_famous(self._h, b, r0, r1, _p(out)))
+        return out
+
+    def famous_events(self, b, first=0, K=None):
+        K = self._events(b) - first if K is None else K
+        out = np.empty(K, np.int8)
+        self._chk(self._L.sw_batch_get_famous_events(self._h, b, first, K, _p(out)))
+        return out
+
+    def consensus(self, b, r0=0, r1=None):
+        r1 = self.summary(b).rounds if r1 is None else r1
+        out = np.empty(r1 - r0, np.uint8)
+        self._chk(self._L.sw_batch_get_consensus(self._h, b, r0, r1, _p(out)))
+        return out
+
+    def new_rounds(self, b, count=None):
+        """sorted(new_c) of hashgraph b's last step (count: its length where the caller has it from a summary)."""
+        cap = max(1, self.summary(b).n_new_rounds if count is None else int(count))
+        out = np.empty(cap, np.int32)
+        cnt = C.c_int(0)
+        self._chk(self._L.sw_batch_get_new_rounds(self._h, b, _p(out), cap, C.byref(cnt)))
+        return out[:cnt.value].copy()
+
+    def transactions(self, b, first=0, K=None):
+        K = self.summary(b).ordered - first if K is None else K
+        out = np.empty(K, np.int32)
+        self._chk(self._L.sw_batch_get_transactions(self._h, b, first, K, _p(out), None, None))
+        return out
+
+    def ordered(self, b, first=0, K=None):
+        """(events, round received, consensus timestamp) of hashgraph b's ordered events [first, first + K)."""
+        K = self.summary(b).ordered - first if K is None else K
+        ev, rr, ts = np.empty(K, np.int32), np.empty(K, np.int32), np.empty(K, np.float64)
+        self._chk(self._L.sw_batch_get_transactions(self._h, b, first, K, _p(ev), _p(rr), _p(ts)))
+        return ev, rr, ts
+
+
 LiveResources = collections.namedtuple("LiveResources", "device_bytes pinned_bytes events streams")
 
 
