@@ -1116,6 +1116,7 @@ int sw_get_vote_store_stats(sw_ctx* ctx, int64_t* entries, int64_t* capacity, in
  * sw_batch_get_*     per hashgraph b, a copy out of its slab, with the meaning of the sw_get_* of the same name;
  *                    sw_batch_get_new_rounds: sorted(new_c) of b's last step; sw_batch_get_transactions: the ordered events
  *                    [first, first + K) with their round received and consensus timestamp (each array nullable).
+ *                    One blocking copy per call and array: for every hashgraph at once see sw_export_batch_* below.
  */
 typedef struct sw_batch sw_batch;
 #define SW_BATCH_SUMMARY_WORDS 9
@@ -1144,6 +1145,53 @@ int sw_batch_get_consensus(sw_batch* batch, int64_t b, int r0, int r1, uint8_t* 
 int sw_batch_get_new_rounds(sw_batch* batch, int64_t b, int32_t* out, int cap, int* n_out);
 int sw_batch_get_transactions(sw_batch* batch, int64_t b, int64_t first, int64_t K, int32_t* events, int32_t* round_received,
                               double* consensus_time);
+
+/*
+ * THE RESULTS OF A WHOLE BATCH IN ONE CALL (csrc/batch_export.hip.h).  The sw_batch_get_* above cost one
+ * blocking copy per hashgraph and array; these return, for every hashgraph at once, RAGGED arrays: the segments of the
+ * hashgraphs concatenated, hashgraph b at entries [off[b], off[b + 1]) of every data array, off of B + 1 entries, off[B] =
+ * *total.  One kernel launch per call; the host form ends in ONE synchronisation (one copy back per requested array), the
+ * _device form in none.
+ *   CONTROL arrays (first, count, which, r0, r1, and off, which is written) are HOST memory in both forms: the ranges are
+ * checked against what the host already holds from the last step's read-back, and off is its prefix sum — *total is known
+ * before anything is enqueued.  DATA arrays are host memory in the plain form and memory of the batch's device, 16-byte
+ * aligned, in the _device form, whose user_stream (the caller's hipStream_t) has the earlier users of the arrays enqueued
+ * and is made to wait for the gather.  Every data array is nullable (not wanted).  With ALL of them NULL the call is a
+ * SIZING call: it fills off and *total (nullable), ignores cap, launches nothing.  cap: entries the data arrays can take.
+ *   Defaults: first / r0 NULL = 0; count / r1 NULL = up to the end (the ordered events, the stored events, the rounds of
+ * the hashgraph); which NULL = every hashgraph, which[b] = 0: an empty segment.
+ *   Refused before any device work, nothing written to a data array: NULL batch or off (SW_EINVAL); a negative range or one
+ * beyond the end (SW_ERANGE); *total > cap (SW_ERANGE, off and *total filled: size and retry); a device data array that is
+ * not 16-byte aligned or not memory of the batch's device (SW_EINVAL).  *total = 0: SW_OK, no launch.  FROZEN hashgraphs
+ * are exported like any other, with what their slab holds (the log of the rounds a failing call completed included).
+ *
+ * sw_export_batch_ordered      log positions [first[b], first[b] + count[b]): event, round received, consensus timestamp —
+ *                              sw_batch_get_transactions for every hashgraph, bit for bit.
+ * sw_export_batch_new_rounds   sorted(new_c) of each hashgraph's own last step (sw_batch_get_new_rounds); empty for a
+ *                              frozen hashgraph: the step that froze it returned no new_c.
+ * sw_export_batch_events       creator, height, round (-1: not divided yet) and famous_events of the stored events
+ *                              [first[b], first[b] + count[b]).
+ * sw_export_batch_rounds       rounds [r0[b], r1[b]): witnesses and famous as rows of n_members columns (off, cap and *total
+ *                              count ROUNDS: the arrays hold *total x n_members elements), consensus one byte per round.
+ * sw_export_batch_stats        out[4]: calls, kernel launches, entries written (*total of every call that launched),
+ *                              device-to-host copies, since the batch was created.
+ */
+int sw_export_batch_ordered(sw_batch* batch, const int64_t* first, const int64_t* count, int64_t cap, int64_t* off, int32_t* event,
+                            int32_t* round_received, double* time, int64_t* total);
+int sw_export_batch_ordered_device(sw_batch* batch, const int64_t* first, const int64_t* count, int64_t cap, int64_t* off, int32_t* d_event,
+                                   int32_t* d_round_received, double* d_time, int64_t* total, void* user_stream);
+int sw_export_batch_new_rounds(sw_batch* batch, const uint8_t* which, int64_t cap, int64_t* off, int32_t* rounds, int64_t* total);
+int sw_export_batch_new_rounds_device(sw_batch* batch, const uint8_t* which, int64_t cap, int64_t* off, int32_t* d_rounds, int64_t* total,
+                                      void* user_stream);
+int sw_export_batch_events(sw_batch* batch, const int64_t* first, const int64_t* count, int64_t cap, int64_t* off, int32_t* creator,
+                           int32_t* height, int32_t* round, int8_t* famous, int64_t* total);
+int sw_export_batch_events_device(sw_batch* batch, const int64_t* first, const int64_t* count, int64_t cap, int64_t* off, int32_t* d_creator,
+                                  int32_t* d_height, int32_t* d_round, int8_t* d_famous, int64_t* total, void* user_stream);
+int sw_export_batch_rounds(sw_batch* batch, const int32_t* r0, const int32_t* r1, int64_t cap, int64_t* off, int32_t* witnesses,
+                           int8_t* famous, uint8_t* consensus, int64_t* total);
+int sw_export_batch_rounds_device(sw_batch* batch, const int32_t* r0, const int32_t* r1, int64_t cap, int64_t* off, int32_t* d_witnesses,
+                                  int8_t* d_famous, uint8_t* d_consensus, int64_t* total, void* user_stream);
+int sw_export_batch_stats(sw_batch* batch, int64_t out[4]);
 
 /* Block until all work queued on the context's stream is complete. */
 int sw_synchronize(sw_ctx* ctx);

@@ -195,6 +195,16 @@ SIGNATURES = {
     "sw_batch_get_consensus": (C.c_int, [_P, C.c_int64, C.c_int, C.c_int, _P]),
     "sw_batch_get_new_rounds": (C.c_int, [_P, C.c_int64, _P, C.c_int, C.POINTER(C.c_int)]),
     "sw_batch_get_transactions": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int64, _P, _P, _P]),
+    # ... and their results, the whole batch per call (csrc/batch_export.hip.h)
+    "sw_export_batch_ordered": (C.c_int, [_P, _P, _P, C.c_int64, _P, _P, _P, _P, C.POINTER(C.c_int64)]),
+    "sw_export_batch_ordered_device": (C.c_int, [_P, _P, _P, C.c_int64, _P, _P, _P, _P, C.POINTER(C.c_int64), _P]),
+    "sw_export_batch_new_rounds": (C.c_int, [_P, _P, C.c_int64, _P, _P, C.POINTER(C.c_int64)]),
+    "sw_export_batch_new_rounds_device": (C.c_int, [_P, _P, C.c_int64, _P, _P, C.POINTER(C.c_int64), _P]),
+    "sw_export_batch_events": (C.c_int, [_P, _P, _P, C.c_int64, _P, _P, _P, _P, _P, C.POINTER(C.c_int64)]),
+    "sw_export_batch_events_device": (C.c_int, [_P, _P, _P, C.c_int64, _P, _P, _P, _P, _P, C.POINTER(C.c_int64), _P]),
+    "sw_export_batch_rounds": (C.c_int, [_P, _P, _P, C.c_int64, _P, _P, _P, _P, C.POINTER(C.c_int64)]),
+    "sw_export_batch_rounds_device": (C.c_int, [_P, _P, _P, C.c_int64, _P, _P, _P, _P, C.POINTER(C.c_int64), _P]),
+    "sw_export_batch_stats": (C.c_int, [_P, _P]),
     "sw_set_window": (C.c_int, [_P, C.c_int, C.c_int]),
     "sw_get_window": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "sw_set_window_lapse": (C.c_int, [_P, C.c_int64]),

@@ -17,6 +17,15 @@ struct sw_batch {
     std::vector<std::vector<int32_t>> cr, ht;
     std::vector<int32_t> hmax;
     std::vector<char> frozen;
+    // whole-batch exports (batch_export_api.hip.h): a plan is (B + 1) offsets and B source addresses per array
+    static constexpr int XP_SLOTS = 4;
+    owned::Pinned<unsigned char> xp_h[XP_SLOTS];   // a ring of plans, written by the host ...
+    owned::Event xp_up[XP_SLOTS];                  // ... each with the event recorded behind its upload
+    bool xp_busy[XP_SLOTS] = {};
+    int xp_next = 0;
+    owned::DBuf<unsigned char> xp_d;               // the plan the kernel reads (rewritten in stream order)
+    owned::Event ev_user;                          // between the caller's stream and ours
+    int64_t xp_calls = 0, xp_launches = 0, xp_entries = 0, xp_d2h = 0;   // sw_export_batch_stats
     const swb::Rec* recs() const { return (const swb::Rec*)(mem.p + lay.recs); }
     unsigned char* seg(int64_t b, int s) const { return mem.p + lay.at((uint64_t)b, s); }
 };

@@ -1399,6 +1399,8 @@ class Hashgraph:
 
 BatchSummary = collections.namedtuple("BatchSummary", "events divided rounds ordered n_new_rounds n_ordered stage code event")
 BATCH_STAGES = {0: None, 1: "divide", 2: "fame", 3: "order"}
+BatchStepArrays = collections.namedtuple("BatchStepArrays", "took rounds_off rounds tx_off event round_received time n_failed")
+BatchExportStats = collections.namedtuple("BatchExportStats", "calls launches entries d2h_copies")
 
 
 class HashgraphBatch:
@@ -1596,6 +1598,126 @@ class HashgraphBatch:
         ev, rr, ts = np.empty(K, np.int32), np.empty(K, np.int32), np.empty(K, np.float64)
         self._chk(self._L.sw_batch_get_transactions(self._h, b, first, K, _p(ev), _p(rr), _p(ts)))
         return ev, rr, ts
+
+    # ---- the whole batch per call (sw_export_batch_*): ragged arrays, hashgraph b at [off[b], off[b + 1]) ----
+    def _ctl(self, a, dtype, what):
+        if a is None:
+            return None
+        a = np.ascontiguousarray(a, dtype)
+        if a.shape != (self.B,):
+            raise ValueError("%s must have one entry per hashgraph" % what)
+        return a
+
+    def _export(self, fn, ctl, specs, cap=None):
+        """Host form: a sizing call (none where the caller knows `cap`), then the export.  specs: (name, dtype, columns)."""
+        off, total = np.zeros(self.B + 1, np.int64), C.c_int64(0)
+        ctl = [_p(a) for a in ctl]
+        if cap is None:
+            self._chk(fn(self._h, *ctl, 0, _p(off), *([None] * len(specs)), C.byref(total)))
+            cap = int(total.value)
+        out = {name: np.empty(cap if cols == 1 else (cap, cols), dtype) for name, dtype, cols in specs}
+        self._chk(fn(self._h, *ctl, int(cap), _p(off), *[_p(out[name]) for name, _, _ in specs], C.byref(total)))
+        T = int(total.value)
+        out = {name: a[:T] for name, a in out.items()}
+        out["off"] = off
+        return out
+
+    def _export_device(self, fn, ctl, arrays, cap, stream):
+        """Device form: arrays = (name, object or address or None, columns).  Returns (off, total)."""
+        ptrs, room = [], []
+        for name, a, cols in arrays:
+            ptr, _ = _dev_ptr(a)
+            ptrs.append(C.c_void_p(ptr) if ptr else None)
+            shape = getattr(a, "shape", None)
+            if ptr and shape is not None and not isinstance(a, (int, np.integer)):
+                room.append(int(np.prod(shape, dtype=np.int64)) // cols)
+        if cap is None:
+            if not room:
+                raise ValueError("the capacity of the arrays is not known: pass cap=")
+            cap = min(room)
+        elif room and min(room) < cap:
+            raise ValueError("an array holds %d entries, cap is %d" % (min(room), cap))
+        off, total = np.zeros(self.B + 1, np.int64), C.c_int64(0)
+        self._chk(fn(self._h, *[_p(a) for a in ctl], int(cap), _p(off), *ptrs, C.byref(total), C.c_void_p(int(stream))))
+        return off, int(total.value)
+
+    def export_ordered(self, first=None, count=None):
+        """Log positions [first[b], first[b] + count[b]) of every hashgraph (None: from 0 / to the end): a dict of off
+        (int64 [B + 1]), event, round_received (int32) and time (float64).  One launch, one synchronisation."""
+        ctl = [self._ctl(first, np.int64, "first"), self._ctl(count, np.int64, "count")]
+        return self._export(self._L.sw_export_batch_ordered, ctl, [("event", np.int32, 1), ("round_received", np.int32, 1), ("time", np.float64, 1)])
+
+    def export_new_rounds(self, which=None):
+        """sorted(new_c) of every hashgraph's own last step (which[b] = 0: left out; a frozen hashgraph: empty): off, rounds."""
+        w = None if which is None else self._ctl(np.asarray(which) != 0, np.uint8, "which")
+        return self._export(self._L.sw_export_batch_new_rounds, [w], [("rounds", np.int32, 1)])
+
+    def export_events(self, first=None, count=None):
+        """Events [first[b], first[b] + count[b]) of every hashgraph: off, creator, height, round (-1: not divided), famous (int8)."""
+        ctl = [self._ctl(first, np.int64, "first"), self._ctl(count, np.int64, "count")]
+        return self._export(self._L.sw_export_batch_events, ctl,
+                            [("creator", np.int32, 1), ("height", np.int32, 1), ("round", np.int32, 1), ("famous", np.int8, 1)])
+
+    def export_rounds(self, r0=None, r1=None):
+        """Rounds [r0[b], r1[b]) of every hashgraph: off (in rounds), witnesses (int32 [total][n]), famous (int8 [total][n]),
+        consensus (uint8 [total])."""
+        ctl = [self._ctl(r0, np.int32, "r0"), self._ctl(r1, np.int32, "r1")]
+        return self._export(self._L.sw_export_batch_rounds, ctl, [("witnesses", np.int32, self.n), ("famous", np.int8, self.n), ("consensus", np.uint8, 1)])
+
+    def export_ordered_device(self, first=None, count=None, event=None, round_received=None, time=None, cap=None, stream=0):
+        """export_ordered into DEVICE arrays (addresses, or objects with data_ptr() / __cuda_array_interface__, 16-byte aligned;
+        None = not wanted) of `cap` entries (default: the shortest array).  `stream` (a raw hipStream_t) is made to wait for
+        them; no host synchronisation.  Returns (off, total); more than cap entries raise SwirldHipError -34, nothing written."""
+        ctl = [self._ctl(first, np.int64, "first"), self._ctl(count, np.int64, "count")]
+        return self._export_device(self._L.sw_export_batch_ordered_device, ctl,
+                                   [("event", event, 1), ("round_received", round_received, 1), ("time", time, 1)], cap, stream)
+
+    def export_new_rounds_device(self, which=None, rounds=None, cap=None, stream=0):
+        """export_new_rounds into a DEVICE array (see export_ordered_device).  Returns (off, total)."""
+        w = None if which is None else self._ctl(np.asarray(which) != 0, np.uint8, "which")
+        return self._export_device(self._L.sw_export_batch_new_rounds_device, [w], [("rounds", rounds, 1)], cap, stream)
+
+    def export_events_device(self, first=None, count=None, creator=None, height=None, round=None, famous=None, cap=None, stream=0):
+        """export_events into DEVICE arrays (see export_ordered_device).  Returns (off, total)."""
+        ctl = [self._ctl(first, np.int64, "first"), self._ctl(count, np.int64, "count")]
+        return self._export_device(self._L.sw_export_batch_events_device, ctl,
+                                   [("creator", creator, 1), ("height", height, 1), ("round", round, 1), ("famous", famous, 1)], cap, stream)
+
+    def export_rounds_device(self, r0=None, r1=None, witnesses=None, famous=None, consensus=None, cap=None, stream=0):
+        """export_rounds into DEVICE arrays (see export_ordered_device; witnesses and famous hold cap x n elements).  Returns
+        (off, total), both in rounds."""
+        ctl = [self._ctl(r0, np.int32, "r0"), self._ctl(r1, np.int32, "r1")]
+        return self._export_device(self._L.sw_export_batch_rounds_device, ctl,
+                                   [("witnesses", witnesses, self.n), ("famous", famous, self.n), ("consensus", consensus, 1)], cap, stream)
+
+    def step_arrays(self, K=None):
+        """step(K) with the results of the whole batch as ragged arrays: hashgraph b's new_c is rounds[rounds_off[b]:
+        rounds_off[b + 1]], its newly ordered events event / round_received / time[tx_off[b]:tx_off[b + 1]].  `took` as
+        step(collect=True) decides it; a hashgraph that sat out or froze has empty segments.  Two export calls, whatever B."""
+        Ka = None
+        if K is not None:
+            Ka = np.ascontiguousarray(K, np.int64)
+            if Ka.shape != (self.B,):
+                raise ValueError("K must have one entry per hashgraph")
+        before = self.summary_array()
+        failed = C.c_int64(0)
+        self._chk(self._L.sw_batch_step(self._h, _p(Ka), C.byref(failed)))
+        self.n_failed = int(failed.value)
+        now = self.summary_array()
+        took = (now[:, 1] != before[:, 1]) & (now[:, 6] == 0)
+        which = np.ascontiguousarray(took, np.uint8)
+        r = self._export(self._L.sw_export_batch_new_rounds, [which], [("rounds", np.int32, 1)], cap=int(now[took, 4].sum()))
+        n_out = np.where(took, now[:, 5], 0).astype(np.int64)
+        first = np.where(took, now[:, 3] - now[:, 5], 0).astype(np.int64)
+        o = self._export(self._L.sw_export_batch_ordered, [first, n_out],
+                         [("event", np.int32, 1), ("round_received", np.int32, 1), ("time", np.float64, 1)], cap=int(n_out.sum()))
+        return BatchStepArrays(took, r["off"], r["rounds"], o["off"], o["event"], o["round_received"], o["time"], self.n_failed)
+
+    def export_stats(self):
+        """(calls, kernel launches, entries written, device-to-host copies) of the export_* calls since the batch was made."""
+        out = np.zeros(4, np.int64)
+        self._chk(self._L.sw_export_batch_stats(self._h, _p(out)))
+        return BatchExportStats(*[int(x) for x in out])
 
 
 LiveResources = collections.namedtuple("LiveResources", "device_bytes pinned_bytes events streams")
