@@ -11,10 +11,11 @@ from .engine import Hashgraph
 
 
 class DeviceNetwork:
-    def __init__(self, seeds, stake=None, device=0, event_class=("swirld", "Event"), clock=None, exact_history=False):
+    def __init__(self, seeds, stake=None, device=0, event_class=("swirld", "Event"), clock=None, exact_history=False, coin_period=6):
         """seeds: one 32-byte Ed25519 seed per node, in member order.  clock: the roots' timestamps (default time.time).
         exact_history: every context keeps round received, consensus time and the votes (by event) once it has stored a
-        forked event (Hashgraph.set_exact_history); round_received(i), consensus_time(i) and votes(i) then go on answering."""
+        forked event (Hashgraph.set_exact_history); round_received(i), consensus_time(i) and votes(i) then go on answering.
+        coin_period: the reference's module constant C (swirld.py:17), as `Node` passes its own to its context."""
         from time import time
         clock = clock or time
         self.seeds = [bytes(s) for s in seeds]
@@ -25,7 +26,7 @@ class DeviceNetwork:
         self.heads = []          # per node: the dense index of its head in its own context
         self.results = []        # the TurnResult of every turn, in order
         for i in range(self.n):
-            h = Hashgraph(self.n, stake, device=device)
+            h = Hashgraph(self.n, stake, coin_period=coin_period, device=device)
             if exact_history:
                 h.set_exact_history(True)
             h.set_member_keys(self.pks)

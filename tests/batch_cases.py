@@ -29,9 +29,9 @@ def ragged_schedule(N, seed, lo=1, hi=None):
 class Record:
     """What the oracle computes for a stream under a schedule: per call (new_c, transactions), or the call that raised."""
 
-    def __init__(self, n, stream, sched, stake=None):
+    def __init__(self, n, stream, sched, stake=None, coin_period=6):
         cr, sp, op, t, sig = stream
-        self.o = o = Oracle(n, stake)
+        self.o = o = Oracle(n, stake, coin_period)
         self.calls, self.failed_call, self.error = [], None, None
         a = 0
         for k in sched:

@@ -12,7 +12,7 @@ The table: one row per (voter witness y, candidate round rc) with at least one e
 exists / value as member bitmasks in ceil(n / 64) little-endian 64-bit words."""
 import numpy as np
 
-COIN_PERIOD = 6   # C of swirld.py
+COIN_PERIOD = 6   # C of swirld.py; the default of the `coin_period` arguments below
 
 
 def strongly_seen(g):
@@ -39,8 +39,8 @@ def strongly_seen(g):
 class Election:
     """The votes of every witness on the witnesses of round rc, level by level; level d is voter round rc + d."""
 
-    def __init__(self, g, S, rc):
-        self.g, self.S, self.rc = g, S, rc
+    def __init__(self, g, S, rc, coin_period=COIN_PERIOD):
+        self.g, self.S, self.rc, self.coin_period = g, S, rc, int(coin_period)
         self.stake = g["stake"].astype(np.int64)
         self.tot2 = 2 * int(self.stake.sum())
         self.coin = g["sig"][:, 0] >> 7
@@ -76,7 +76,7 @@ class Election:
                 by_stake = ((vote != vote_h) | (strong != strong_h)) & has[:, None]
             self.by_stake.append(by_stake)
             coined = np.zeros_like(vote)
-            if k % COIN_PERIOD == 0:
+            if k % self.coin_period == 0:
                 coined = ~strong & has[:, None]
                 vote = np.where(strong, vote, self.coin[np.maximum(wit, 0)][:, None].astype(bool))   # swirld.py:272
             self.V.append(vote & has[:, None])
@@ -85,11 +85,12 @@ class Election:
         return self.V[d], self.strong[d], self.coined[d]
 
 
-def model_votes(g, new_c=None):
+def model_votes(g, new_c=None, coin_period=COIN_PERIOD):
     """-> dict(row_voter, row_cand_round, exists [rows][nwo] uint64, value, n_entries, n_coin, n_weighted, n_by_stake (the
     evaluated entries whose outcome by stake differs from a head count of the same voters), and the
     tables the library keeps beside the hashgraph: dec_call, dec_by, calls, cons_call, S).
-    new_c: per call the rounds the reference put into `consensus` (default: the golden's record)."""
+    new_c: per call the rounds the reference put into `consensus` (default: the golden's record).
+    coin_period: the reference's C for this run (default: its own, 6)."""
     wit, rnd = g["witnesses"], g["round"]
     R, n = wit.shape
     S = strongly_seen(g)
@@ -127,12 +128,12 @@ def model_votes(g, new_c=None):
                     d = r_ - r
                     el = elections.get(r)
                     if el is None:
-                        el = elections[r] = Election(g, S, r)
+                        el = elections[r] = Election(g, S, r, coin_period)
                     V, strong, coined = el.level(d)
                     stored = und
                     if d > 1:
                         n_by_stake += int((und & el.by_stake[d][mv]).sum())
-                    if d > 1 and d % COIN_PERIOD != 0:
+                    if d > 1 and d % coin_period != 0:
                         decided = und & strong[mv]
                         if decided.any():
                             famous[r] |= decided

@@ -2,7 +2,8 @@
 sizes, 1024 members, hot-member streams), started in background threads when the GPU session
 begins so that their single-core minutes overlap the rest of the suite (the oracle's C calls
 release the GIL; the GPU box has hundreds of host cores) — and, under names that begin with "wide_stake/", the weighted
-cases of tests/wide_stake_cases.py.  Never imported by the product."""
+cases of tests/wide_stake_cases.py, and under "coin_period/" the runs at a coin period of 2 or 3 of
+tests/test_gpu_coin_period.py.  Never imported by the product."""
 import importlib
 import os
 import threading
@@ -99,6 +100,61 @@ class WideStakeRun:
         return self
 
 
+COIN_PERIOD = "coin_period/"   # names: coin_period/<shape>/c<period>/<unit | weighted>
+
+# shape -> (members, events of the unit-stake run, events of the weighted run, seed, generator mode, p0, p1): one call each.
+# The smallest shapes found at which the oracle alone shows coin votes of both kinds (swirld.py:267-272) at periods 2 AND 3
+# — and, up to 256 members, a round decided after a coin round at period 3 (tests/test_gpu_coin_period.py asserts both from
+# the oracle's counters; the figures stand in its table).  A weighted pass advances its rounds more slowly, so 520 members
+# need 28 000 events before the third level of an election exists.
+COIN_SHAPES = {
+    "n40": (40, 3000, 3000, 38, 0, 0.0, 0.0),
+    "n64": (64, 5000, 5000, 37, 0, 0.0, 0.0),
+    "n65": (65, 6000, 6000, 39, 0, 0.0, 0.0),
+    "n130": (130, 14000, 14000, 40, 2, 0.3, 0.05),
+    "n256": (256, 30000, 30000, 3, 2, 0.3, 0.05),
+    "n300": (300, 16000, 16000, 42, 0, 0.0, 0.0),
+    "n520": (520, 24000, 28000, 46, 0, 0.0, 0.0),
+}
+
+
+def coin_stake(n, weighted):
+    """Unit stake, or stake 3 on every 7th member (T = 1.29 n: rounds still advance, tests/wide_stake_cases.py)."""
+    st = np.ones(n, np.uint64)
+    if weighted:
+        st[::7] = 3
+    return st
+
+
+class CoinPeriodRun:
+    """One call of the oracle created with a coin period: divide_rounds, decide_fame, find_order."""
+
+    def __init__(self, name):
+        self.name = name
+        shape, period, kind = name[len(COIN_PERIOD):].split("/")
+        self.n, n_unit, n_weighted, self.seed, self.mode, self.p0, self.p1 = COIN_SHAPES[shape]
+        self.period, self.weighted = int(period[1:]), kind == "weighted"
+        assert kind in ("unit", "weighted")
+        self.N = n_weighted if self.weighted else n_unit
+        self.stake = coin_stake(self.n, self.weighted)
+        self.oracle = self.new_c = self.order = self.stream = None
+        self.seconds = 0.0
+
+    def run(self):
+        from oracle.oracle import Oracle
+        pkg = importlib.import_module("py-swirld_amd")
+        t0 = time.time()
+        self.stream = pkg.synth_hashgraph(self.n, self.N, self.seed, self.mode, self.p0, self.p1)
+        o = Oracle(self.n, self.stake, self.period)
+        o.append_events(*self.stream)
+        o.divide_rounds(0, self.N)
+        self.new_c = [int(r) for r in o.decide_fame()]
+        self.order = o.find_order(self.new_c)
+        self.oracle = o
+        self.seconds = time.time() - t0
+        return self
+
+
 class OraclePool:
     def __init__(self, names=None):
         # build / load both libraries once, before any thread touches them
@@ -114,7 +170,8 @@ class OraclePool:
     def start(self, name):
         with self._lock:
             if name not in self._fut:
-                job = WideStakeRun(name) if name.startswith(WIDE_STAKE) else OracleRun(name)
+                job = (WideStakeRun(name) if name.startswith(WIDE_STAKE) else CoinPeriodRun(name) if name.startswith(COIN_PERIOD)
+                       else OracleRun(name))
                 self._fut[name] = self._ex.submit(job.run)
 
     def get(self, name, timeout=1500):

@@ -13,7 +13,7 @@ BATCH = [n for n in golden_names() if n.endswith("batch") or n.endswith("cliques
 BATCH = [n for n in BATCH if not n.startswith("n130") and not n.startswith("n70")]
 
 
-def check(n, cr, sp, op, sig, stake, exp, K, MCAP):
+def check(n, cr, sp, op, sig, stake, exp, K, MCAP, coin_period=6):
     L, lo, _ = mb.bulk_rounds(n, cr, sp, op, stake, K=K, MCAP=MCAP)
     rnd, S, wit = mb.finalize(n, cr, L, lo)
     assert np.array_equal(L, exp["can_see"])
@@ -22,7 +22,7 @@ def check(n, cr, sp, op, sig, stake, exp, K, MCAP):
     Sw = mb.voter_masks(n, L, rnd, S, wit, stake)
     fam = np.full(wit.shape, -1, np.int8)
     cons = np.zeros(wit.shape[0], np.uint8)
-    new_c, p2 = mb.elections(n, wit, Sw, stake, sig[:, 0] >= 128, fam, cons)
+    new_c, p2 = mb.elections(n, wit, Sw, stake, sig[:, 0] >= 128, fam, cons, coin_period=coin_period)
     m = wit >= 0
     assert np.array_equal(fam[m], exp["famous"][wit[m]])
     assert np.array_equal(cons, exp["consensus"])

@@ -25,7 +25,7 @@ def emul(tmp_path_factory):
     return exe
 
 
-def run(emul, tmp_path, g, t, rv0, rv1):
+def run(emul, tmp_path, g, t, rv0, rv1, coin_period=mv.COIN_PERIOD):
     wit = g["witnesses"]
     R, n = wit.shape
     nw = 1
@@ -39,7 +39,7 @@ def run(emul, tmp_path, g, t, rv0, rv1):
     stake[:n] = g["stake"]
     src, dst = str(tmp_path / "in.bin"), str(tmp_path / "out.bin")
     with open(src, "wb") as f:
-        f.write(np.array([n, nw, R, N, mv.COIN_PERIOD, len(t["calls"]), rv0, rv1, int((g["stake"] == 1).all())], np.int32).tobytes())
+        f.write(np.array([n, nw, R, N, coin_period, len(t["calls"]), rv0, rv1, int((g["stake"] == 1).all())], np.int32).tobytes())
         f.write(pad(wit.astype(np.int32), -1).tobytes())
         f.write(mv.pack_words(Sbits.reshape(R * npad, nw * 64)).tobytes())
         f.write((g["sig"][:, 0] >> 7).astype(np.uint8).tobytes())
