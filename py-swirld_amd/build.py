@@ -7,7 +7,8 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OUT = os.path.join(CSRC, "libswirld_hip.so")
 SOURCES = ["swirld_hip.hip", "synth.cpp"]
-DEPS = SOURCES + ["entry_plan.h", "owned.h", "kernels.hip.h", "order.hip.h", "crypto.hip.h", "validate.hip.h", "pack.hip.h", "tmpl.hip.h", "sign.hip.h", "data.hip.h", "exact.hip.h", "exact_history.hip.h", "batch.hip.h", "batch_layout.h", "batch_api.hip.h", "batch_export.hip.h", "batch_export_api.hip.h", "ingest.hip.h", "resolve.hip.h", "gossip.hip.h", "walk.hip.h", "wire.hip.h", "turn.hip.h", "consensus.hip.h", "votes.hip.h", os.path.join("..", "..", "include", "swirld_hip.h")]
+# what the library is built from: every source and header under csrc/ and the public header (names relative to csrc/)
+DEPS = sorted(f for f in os.listdir(CSRC) if f.endswith((".h", ".hip", ".cpp"))) + [os.path.join("..", "..", "include", "swirld_hip.h")]
 
 
 def build(force=False, verbose=False):

@@ -126,16 +126,20 @@ struct sw_ctx {
     // exact path for forked hashgraphs (exact.hip.h): entered at the first forked event, left by sw_reset
     bool exact = false;
     int forks_mode = 1;           // 1: accept forks (exact path), 0: refuse them (SW_ENOTSUP, nothing stored)
-    DBuf<int32_t> x_worder, x_wcnt, x_newr, x_queue, x_fw, x_items_ev, x_rounds;
-    DBuf<signed char> x_fam_ev, x_votes;
-    DBuf<unsigned char> x_tbd, x_sm, x_done, x_visited, x_sflag, x_white;
-    DBuf<double> x_times, x_tsort, x_items_ts;
-    DBuf<long long> x_hdr;
-    int x_Rcap = 0;               // rows of x_worder / x_wcnt / x_done / x_newr
-    int64_t x_cap = 0;            // events of x_fam_ev / x_tbd / x_queue / x_visited / x_items_*
-    FameCounters x_fc_base{};     // fame counters of the fast path at the switch (the exact path counts from zero)
+    // Its rewind is exact_rewind, not a member here: the tables are device state, refilled on the stream, and the one host
+    // value, fc_base, is set there from the context's fc_seen.  sw_reset keeps the buffers for the next forked hashgraph.
+    struct ExactState {
+        DBuf<int32_t> worder, wcnt, newr, queue, fw, items_ev, rounds;
+        DBuf<signed char> fam_ev, votes;
+        DBuf<unsigned char> tbd, sm, done, visited, sflag, white;
+        DBuf<double> times, tsort, items_ts;
+        DBuf<long long> hdr;
+        int Rcap = 0;               // rows of worder / wcnt / done / newr
+        int64_t cap = 0;            // events of fam_ev / tbd / queue / visited / items_*
+        FameCounters fc_base{};     // fame counters of the fast path at the switch (the exact path counts from zero)
+    } ex;
     // what the exact path computes beyond the order, kept (sw_set_exact_history; exact_history.hip.h): round
-    // received / consensus time into d_rr / d_cts / d_tx, and Node.votes keyed by event in a log + index on the device
+    // received / consensus time into cons.d_rr / d_cts / d_tx, and Node.votes keyed by event in a log + index on the device
     struct HistoryState {
         bool on = false;              // the switch: set before the first event, kept by sw_reset
         bool votes_ok = true;         // false: the store is incomplete (overflow, KeyError, votes the fast path could not hand over) until sw_rewind / sw_reset
@@ -150,6 +154,10 @@ struct sw_ctx {
         int64_t ceiling = (int64_t)1 << 24;   // SW_VOTE_STORE_MAX (history_knobs): the most entries; beyond it votes become unavailable
         int64_t grows = 0, imported = 0, lookups = 0, exported = 0;   // sw_get_vote_store_stats (imported: the hand-over at the first fork)
         int64_t table_calls = -1, table_divided = -1;   // fork-free context: the decide_fame calls and divided events the store was filled from (-1: not filled)
+        // sw_rewind: a store filled from the fast path's table is stale (no decide_fame call stands); on the exact path
+        // exact_rewind empties the store on the stream.  sw_reset: nothing more — the switch and the buffers stay.
+        void rewind() { table_calls = table_divided = -1; }
+        void reset() {}
     } hist;
     bool unit_stake = true;
     uint32_t tot = 0;
@@ -176,31 +184,46 @@ struct sw_ctx {
     int max_height = 0;
     int64_t N = 0, cap = 0, divided = 0;
     // device-side ingest (sw_append_events_device; ingest.hip.h)
-    DBuf<int32_t> d_ing_tab;      // [4 + 3 npad]: verdict word (64 bits), pad; then [nev | head | first] of the members
-    DBuf<int32_t> d_ing_hist;     // [tiles][npad] creators per tile, then chain position of each member at the head of each tile
-    DBuf<int32_t> d_ht_stat;      // k_ingest_heights: [error, largest height, {min, max} per 4096-event block of the batch]
-    std::vector<int32_t> ing_stage;   // host staging of d_ing_tab (persistent: uploaded and read back without a copy of a local)
-    Event ev_ht;                  // the heights kernel of the last device append (it runs on stream_io, behind the call)
-    bool ht_pending = false;      // ... has not been waited for yet: d_ht, max_height, blk_hmin / blk_hmax lack its events
-    int64_t ht_first = 0, ht_K = 0;   // ... which are these
-    int64_t ht_dev_upto = 0;      // events below this index and beyond the host mirror (sp.size()) have their height in d_ht
-    int64_t st_dev_batches = 0, st_dev_events = 0, st_fallback = 0, st_host_ht = 0;   // sw_get_ingest_stats
+    struct IngestState {
+        DBuf<int32_t> d_tab;          // [4 + 3 npad]: verdict word (64 bits), pad; then [nev | head | first] of the members
+        DBuf<int32_t> d_hist;         // [tiles][npad] creators per tile, then chain position of each member at the head of each tile
+        DBuf<int32_t> d_ht_stat;      // k_ingest_heights: [error, largest height, {min, max} per 4096-event block of the batch]
+        std::vector<int32_t> stage;   // host staging of d_tab (persistent: uploaded and read back without a copy of a local)
+        Event ev_ht;                  // the heights kernel of the last device append (it runs on stream_io, behind the call)
+        bool ht_pending = false;      // ... has not been waited for yet: d_ht, max_height, blk_hmin / blk_hmax lack its events
+        int64_t ht_first = 0, ht_K = 0;   // ... which are these
+        int64_t ht_dev_upto = 0;      // events below this index and beyond the host mirror (sp.size()) have their height in d_ht
+        int64_t dev_batches = 0, dev_events = 0, fallback = 0, host_ht = 0;   // sw_get_ingest_stats
+        // sw_rewind keeps it (the events and their heights stay); sw_reset, which has drained stream_io, forgets the heights
+        void rewind() {}
+        void reset() { ht_pending = false; ht_dev_upto = 0; }
+    } ing;
     // id index (sw_set_event_ids, sw_ingest_payload[_device]; resolve.hip.h): allocated on first use
-    DBuf<unsigned char> d_id;     // 32 B per event that has an id, in dense order
-    DBuf<int32_t> d_idtab;        // id -> dense index: 1 << idtab_log slots, load <= 1/2, rebuilt from d_id when it grows
-    int idtab_log = 0;            // (0: no table yet)
-    int64_t n_ids = 0;            // events [0, n_ids) have ids; the index is COMPLETE when n_ids == N
-    DBuf<int32_t> d_idflag;       // [4] duplicate flag of an insert
-    DBuf<unsigned char> d_pl;     // scratch of a payload call
-    DBuf<unsigned char> d_pl_in;  // ... and the staged arrays of the host-array forms
-    Pinned<int32_t> h_plcnt;      // pinned: per-wave counts of one batch of waves
-    int64_t pl_calls = 0, pl_waves = 0, pl_accepted = 0, pl_rebuilds = 0;   // sw_get_payload_stats (waves, accepted: the last call's)
-    double pl_ms[4] = {0, 0, 0, 0};   // ... host time of its phases under sw_set_profiling: resolve, waves, sort + gather, append + commit
-    // answering a sync on the device (sw_export_payload[_device], sw_sync_pull; gossip.hip.h)
-    DBuf<int32_t> d_xp;           // [2: the total, 64 bits][npad + 1: offsets of the members' ranges][npad: chain pool base per member]
-    DBuf<unsigned char> d_xp_out; // the exported arrays of the host-array form and of sw_sync_pull
-    int64_t xp_calls = 0, xp_events = 0;   // sw_get_export_stats
-    double xp_ms[2] = {0, 0};     // ... host time of the most recent call's phases under sw_set_profiling: ranges + count, gather
+    struct IdState {
+        DBuf<unsigned char> d_id;     // 32 B per event that has an id, in dense order
+        DBuf<int32_t> d_idtab;        // id -> dense index: 1 << idtab_log slots, load <= 1/2, rebuilt from d_id when it grows
+        int idtab_log = 0;            // (0: no table yet)
+        int64_t n_ids = 0;            // events [0, n_ids) have ids; the index is COMPLETE when n_ids == N
+        DBuf<int32_t> d_idflag;       // [4] duplicate flag of an insert
+        DBuf<unsigned char> d_pl;     // scratch of a payload call
+        DBuf<unsigned char> d_pl_in;  // ... and the staged arrays of the host-array forms
+        Pinned<int32_t> h_plcnt;      // pinned: per-wave counts of one batch of waves
+        int64_t pl_calls = 0, pl_waves = 0, pl_accepted = 0, pl_rebuilds = 0;   // sw_get_payload_stats (waves, accepted: the last call's)
+        double pl_ms[4] = {0, 0, 0, 0};   // ... host time of its phases under sw_set_profiling: resolve, waves, sort + gather, append + commit
+        // sw_rewind keeps it (the events stay); sw_reset forgets it: the ids go with the events — the table keeps its size,
+        // and sw_reset empties it on the stream
+        void rewind() {}
+        void reset() { n_ids = 0; }
+    } ids;
+    // answering a sync on the device (sw_export_payload[_device], sw_sync_pull; gossip.hip.h): scratch, a knob and counters
+    // that sw_rewind / sw_reset leave alone
+    struct ExportState {
+        DBuf<int32_t> d;              // [2: the total, 64 bits][npad + 1: offsets of the members' ranges][npad: chain pool base per member]
+        DBuf<unsigned char> d_out;    // the exported arrays of the host-array form and of sw_sync_pull
+        int64_t calls = 0, events = 0;   // sw_get_export_stats
+        double ms[2] = {0, 0};        // ... host time of the most recent call's phases under sw_set_profiling: ranges + count, gather
+        int lanes = 16;               // SW_EXPORT_LANES (measurement knob, read at sw_create): lanes of a wave that share one output slot — 4, 8 or 16
+    } xp;
     // Node.votes in bulk (csrc/votes.hip.h; sw_export_votes[_device])
     struct VotesState {
         DBuf<unsigned char> d_sched, d_plan, d_work, d_out;   // call schedule, per-call plan, scratch, the host form's table
@@ -209,84 +232,114 @@ struct sw_ctx {
         DBuf<unsigned long long> d_cnt;     // vts::C_WORDS counters: rows and entries of the running call, levels replayed since sw_create
         int64_t calls = 0, rows = 0, entries = 0;             // sw_get_votes_stats
         double ms[2] = {0, 0};              // ... under sw_set_profiling: plan + existence + count, rows + values
+        // sw_rewind: no decide_fame call stands, the schedule is stale; sw_reset: nothing more
+        void rewind() { sched_calls = -1; }
+        void reset() {}
     } votes;
-    int export_lanes = 16;        // SW_EXPORT_LANES (measurement knob, read at sw_create): lanes of a wave that share one output slot — 4, 8 or 16
     // answering a sync by the pruned walk, forked hashgraphs included (sw_sync_walk, sw_export_walk[_device], sw_sync_pull_walk,
     // sw_get_fork_trunks; walk.hip.h)
-    DBuf<int32_t> d_wk;           // [wlk::H_WORDS: the header][npad: the asker's heights][npad: the cap]
-    DBuf<unsigned> d_wk_bits;     // the visited bitmap: head + 1 bits
-    DBuf<int32_t> d_wk_q;         // the queue of the frontiers: head + 1 entries
-    DBuf<int32_t> d_wk_list;      // the ascending list: head + 1 entries
-    DBuf<int32_t> d_wk_trunk;     // [npad: trunk per member][npad: roots per member], as of wk_trunk_N events
-    DBuf<int32_t> d_wk_children;  // children per self-parent (scratch of k_fork_trunks)
-    int64_t wk_trunk_N = -1;      // events d_wk_trunk was computed from (-1: never; sw_reset forgets it)
-    int walk_threads = 1024;      // SW_WALK_THREADS (read at sw_create): workgroup size of k_walk_bfs, a multiple of 64 up to 1024
-    int64_t wk_calls = 0, wk_events = 0, wk_levels = 0;   // sw_get_walk_stats (levels: the last call's)
-    double wk_ms[3] = {0, 0, 0};  // ... host time of the most recent call's phases under sw_set_profiling: walk + count, list, gather
+    struct WalkState {
+        DBuf<int32_t> d;              // [wlk::H_WORDS: the header][npad: the asker's heights][npad: the cap]
+        DBuf<unsigned> d_bits;        // the visited bitmap: head + 1 bits
+        DBuf<int32_t> d_q;            // the queue of the frontiers: head + 1 entries
+        DBuf<int32_t> d_list;         // the ascending list: head + 1 entries
+        DBuf<int32_t> d_trunk;        // [npad: trunk per member][npad: roots per member], as of trunk_N events
+        DBuf<int32_t> d_children;     // children per self-parent (scratch of k_fork_trunks)
+        int64_t trunk_N = -1;         // events d_trunk was computed from (-1: never)
+        int threads = 1024;           // SW_WALK_THREADS (read at sw_create): workgroup size of k_walk_bfs, a multiple of 64 up to 1024
+        int64_t calls = 0, events = 0, levels = 0;   // sw_get_walk_stats (levels: the last call's)
+        double ms[3] = {0, 0, 0};     // ... host time of the most recent call's phases under sw_set_profiling: walk + count, list, gather
+        // sw_rewind keeps the trunks (the events stay); sw_reset forgets them: the trunk heights were those of the forgotten events
+        void rewind() {}
+        void reset() { trunk_N = -1; }
+    } walk;
     // what find_order decided per event, kept (sw_get_round_received, sw_get_consensus_time, sw_export_ordered[_device];
     // consensus.hip.h): allocated by the first find_order call that orders something
-    DBuf<int32_t> d_rr;           // per event: round received (swirld.py:283); entries of events that are not ordered are unspecified
-    DBuf<double> d_cts;           // per event: consensus timestamp (swirld.py:305); likewise
-    DBuf<int32_t> d_tx;           // device copy of `transactions` ...
-    int64_t tx_len = 0;           // ... and its length (0 again after sw_rewind / sw_reset)
-    DBuf<int32_t> d_cs_ordpos;    // npad: the ordered prefixes as of now, uploaded by a getter (d_ordpos holds those at the head of the last call)
-    DBuf<unsigned char> d_cs_out; // the arrays of the host-array forms
-    int64_t cs_record_calls = 0, cs_recorded = 0, cs_export_calls = 0, cs_exported = 0;   // sw_get_consensus_stats
+    struct ConsensusState {
+        DBuf<int32_t> d_rr;           // per event: round received (swirld.py:283); entries of events that are not ordered are unspecified
+        DBuf<double> d_cts;           // per event: consensus timestamp (swirld.py:305); likewise
+        DBuf<int32_t> d_tx;           // device copy of `transactions` ...
+        int64_t tx_len = 0;           // ... and its length
+        DBuf<int32_t> d_ordpos;       // npad: the ordered prefixes as of now, uploaded by a getter (sw_ctx::d_ordpos holds those at the head of the last call)
+        DBuf<unsigned char> d_out;    // the arrays of the host-array forms
+        int64_t record_calls = 0, recorded = 0, export_calls = 0, exported = 0;   // sw_get_consensus_stats
+        // sw_rewind: nothing is ordered any more (d_rr / d_cts need nothing: no event is inside an ordered prefix); sw_reset:
+        // nothing more
+        void rewind() { tx_len = 0; }
+        void reset() {}
+    } cons;
     // validation of payloads against the member keys (sw_set_member_keys, sw_validate_payload[_device]; validate.hip.h):
     // nothing here belongs to the hashgraph, so sw_rewind / sw_reset leave it alone
-    std::vector<uint8_t> vkeys, vusable;   // host copies: n x 32 key bytes, n flags (empty: no keys set)
-    DBuf<unsigned char> d_vkeys;  // [n x 32 key bytes][n usable flags]
-    DBuf<unsigned char> d_vtab;   // (n + 1) rows of swv::ROW entries: the members' multiples of -A, then the base point's
-    DBuf<unsigned char> d_v_in;   // the staged arrays of the host-array form
-    int64_t v_calls = 0, v_events = 0, v_accepted = 0, v_builds = 0;   // sw_get_validate_stats
-    double v_ms[2] = {0, 0};      // ... host time under sw_set_profiling: the last table build, the last validation
+    struct ValidateState {
+        std::vector<uint8_t> keys, usable;   // host copies: n x 32 key bytes, n flags (empty: no keys set)
+        DBuf<unsigned char> d_keys;   // [n x 32 key bytes][n usable flags]
+        DBuf<unsigned char> d_tab;    // (n + 1) rows of swv::ROW entries: the members' multiples of -A, then the base point's
+        DBuf<unsigned char> d_in;     // the staged arrays of the host-array form
+        int64_t calls = 0, events = 0, accepted = 0, builds = 0;   // sw_get_validate_stats
+        double ms[2] = {0, 0};        // ... host time under sw_set_profiling: the last table build, the last validation
+    } val;
     // the signed bytes of events built on the device (sw_pack_events[_device], sw_sync_pull_validated; pack.hip.h): like the
     // keys, a setting and scratch that sw_rewind / sw_reset leave alone
-    std::string pk_mod = "swirld", pk_qual = "Event";   // module and qualified name of the Event class (sw_set_event_class)
-    bool pk_hdr_stale = true;     // d_pk_hdr does not hold the class header of pk_mod / pk_qual yet
-    std::vector<uint8_t> pk_hdr;  // host copy of the header as uploaded (it must outlive the asynchronous copy)
-    DBuf<unsigned char> d_pk_hdr; // the class header of the whole stream (pck::HDR_MAX bytes)
-    DBuf<unsigned char> d_pk;     // tile sums of the scan
-    DBuf<unsigned char> d_pk_in;  // the staged arrays and streams of the host-array form
-    DBuf<unsigned char> d_pk_out; // sw_sync_pull_validated: offsets, streams, flags, verdicts, the count
-    Pinned<int32_t> h_pkcnt;      // pinned: the count of valid events of sw_sync_pull_validated
-    int64_t pk_calls = 0, pk_events = 0, pk_bytes = 0;   // sw_get_pack_stats
-    double pk_ms[2] = {0, 0};     // ... host time under sw_set_profiling: lengths and scan, the two writers
+    struct PackState {
+        std::string mod = "swirld", qual = "Event";   // module and qualified name of the Event class (sw_set_event_class)
+        bool hdr_stale = true;        // d_hdr does not hold the class header of mod / qual yet
+        std::vector<uint8_t> hdr;     // host copy of the header as uploaded (it must outlive the asynchronous copy)
+        DBuf<unsigned char> d_hdr;    // the class header of the whole stream (pck::HDR_MAX bytes)
+        DBuf<unsigned char> d;        // tile sums of the scan
+        DBuf<unsigned char> d_in;     // the staged arrays and streams of the host-array form
+        DBuf<unsigned char> d_out;    // sw_sync_pull_validated: offsets, streams, flags, verdicts, the count
+        Pinned<int32_t> h_cnt;        // pinned: the count of valid events of sw_sync_pull_validated
+        int64_t calls = 0, events = 0, bytes = 0;   // sw_get_pack_stats
+        double ms[2] = {0, 0};        // ... host time under sw_set_profiling: lengths and scan, the two writers
+    } pack;
     // the data of events (sw_set_event_data[_device], sw_gather_event_data[_device], sw_ingest_payload_data[_device],
-    // sw_sync_pull_data; data.hip.h): allocated on first use; sw_rewind keeps it (the events stay), sw_reset forgets it
-    DBuf<unsigned char> d_data;   // the arena: 256-byte aligned, at least dat::SLACK readable bytes behind data_used
-    DBuf<long long> d_data_off;   // [n_data + 1] absolute offsets into the arena, contiguous; [0] = 0
-    DBuf<unsigned char> d_data_none;   // per event that has data: nonzero = None
-    int64_t n_data = 0;           // events [0, n_data) have data; the store is COMPLETE when n_data == N
-    int64_t data_used = 0;        // bytes of the arena in use
-    DBuf<unsigned char> d_dt;     // scratch of a call: scanned offsets + the bad-slot count, none flags, tile sums, slots, folded ok
-    DBuf<unsigned char> d_dt_in;  // the staged arrays of the host-array forms
-    DBuf<unsigned char> d_dt_out; // the gathered data: of the host-array gather, and of sw_sync_pull_data's exported events (in the answering context)
-    int64_t dt_store_calls = 0, dt_gather_calls = 0, dt_gather_bytes = 0;   // sw_get_data_stats
-    double dt_ms[2] = {0, 0};     // ... host time under sw_set_profiling: lengths + scan, the copy
+    // sw_sync_pull_data; data.hip.h): allocated on first use
+    struct DataState {
+        DBuf<unsigned char> d_arena;  // the arena: 256-byte aligned, at least dat::SLACK readable bytes behind `used`
+        DBuf<long long> d_off;        // [n_data + 1] absolute offsets into the arena, contiguous; [0] = 0
+        DBuf<unsigned char> d_none;   // per event that has data: nonzero = None
+        int64_t n_data = 0;           // events [0, n_data) have data; the store is COMPLETE when n_data == N
+        int64_t used = 0;             // bytes of the arena in use
+        DBuf<unsigned char> d;        // scratch of a call: scanned offsets + the bad-slot count, none flags, tile sums, slots, folded ok
+        DBuf<unsigned char> d_in;     // the staged arrays of the host-array forms
+        DBuf<unsigned char> d_out;    // the gathered data: of the host-array gather, and of sw_sync_pull_data's exported events (in the answering context)
+        int64_t store_calls = 0, gather_calls = 0, gather_bytes = 0;   // sw_get_data_stats
+        double ms[2] = {0, 0};        // ... host time under sw_set_profiling: lengths + scan, the copy
+        // sw_rewind keeps it (the events stay); sw_reset forgets it: the data goes with the events (the arena keeps its size)
+        void rewind() {}
+        void reset() { n_data = 0; used = 0; }
+    } data;
     // the wire bytes of a sync answer (sw_pack_message[_device], sw_unpack_message[_device], sw_export_message[_device],
-    // sw_ingest_message[_device]; wire.hip.h): settings derived from the event class and the member keys, and scratch
-    std::string wr_mod, wr_qual;  // the class d_wr_set's prefix was built for (empty: none yet)
-    std::vector<uint8_t> wr_pre;  // host copy of the bytes in front of the table's length field, as uploaded
-    std::vector<uint8_t> wr_keys, wr_skeys;   // the member keys the sorted table was built from; the sorted keys as uploaded
-    std::vector<int32_t> wr_sperm;            // ... and the member each belongs to
-    DBuf<unsigned char> d_wr_set; // [wir::PRE_MAX prefix][n x 32 sorted keys][n members][8 words: K, refusal flag, verdict, data bytes, length]
-    DBuf<unsigned char> d_wr;     // scratch of a call: record offsets, tile sums, the first unencodable event; data positions
-    DBuf<unsigned char> d_wr_in;  // the staged arrays and the message of the host-array forms
-    DBuf<unsigned char> d_wr_out; // the message of sw_export_message; the unpacked arrays of sw_ingest_message
-    int wire_blocks = 4096;       // SW_WIRE_BLOCKS (measurement and test knob, read at sw_create): the most workgroups of k_wire_write
-    int64_t wr_pack_calls = 0, wr_pack_events = 0, wr_pack_bytes = 0, wr_unpack_calls = 0, wr_unpack_events = 0, wr_refused = 0;   // sw_get_wire_stats
+    // sw_ingest_message[_device]; wire.hip.h): settings derived from the event class and the member keys, and scratch —
+    // like those, left alone by sw_rewind / sw_reset
+    struct WireState {
+        std::string mod, qual;        // the class d_set's prefix was built for (empty: none yet)
+        std::vector<uint8_t> pre;     // host copy of the bytes in front of the table's length field, as uploaded
+        std::vector<uint8_t> keys, skeys;   // the member keys the sorted table was built from; the sorted keys as uploaded
+        std::vector<int32_t> sperm;         // ... and the member each belongs to
+        DBuf<unsigned char> d_set;    // [wir::PRE_MAX prefix][n x 32 sorted keys][n members][8 words: K, refusal flag, verdict, data bytes, length]
+        DBuf<unsigned char> d;        // scratch of a call: record offsets, tile sums, the first unencodable event; data positions
+        DBuf<unsigned char> d_in;     // the staged arrays and the message of the host-array forms
+        DBuf<unsigned char> d_out;    // the message of sw_export_message; the unpacked arrays of sw_ingest_message
+        int blocks = 4096;            // SW_WIRE_BLOCKS (measurement and test knob, read at sw_create): the most workgroups of k_wire_write
+        int64_t pack_calls = 0, pack_events = 0, pack_bytes = 0, unpack_calls = 0, unpack_events = 0, refused = 0;   // sw_get_wire_stats
+    } wire;
     // creating signed events (sw_set_signing_keys, sw_sign_events[_device], sw_create_events[_device]; sign.hip.h): like the
     // member keys a setting that sw_rewind / sw_reset leave alone; sw_set_member_keys drops it
-    std::vector<uint8_t> sg_has;  // n flags: the members this context may sign for (empty: no signing key set)
-    DBuf<unsigned char> d_sg_keys;   // [n secrets of 64 B][n flags]: the ONLY copy of the secrets, never read back
-    DBuf<unsigned char> d_sg;     // scratch of a call: verdict block, levels, level counts and offsets, cursors, sorted events
-    DBuf<unsigned char> d_sg_in;  // the staged arrays of the host-array forms; the signed arrays of sw_create_events
-    int64_t sg_calls = 0, sg_events = 0, sg_levels = 0, sg_keysets = 0;   // sw_get_sign_stats (levels: the last call's)
-    double sg_ms[3] = {0, 0, 0};  // ... host time under sw_set_profiling: levels + sort, signing, commit
-    // one event signed by one wavefront, and the gossip turn around it (sw_create_event, sw_gossip_turn; turn.hip.h)
-    int64_t tn_calls = 0, tn_events = 0, tn_turns = 0, tn_profiled = 0;   // sw_get_turn_stats: sw_create_event calls, events the wave signed, turns, stamped launches
-    unsigned long long tn_stamps[8] = {0};   // wall_clock64() at the phase boundaries of the last stamped launch (swt::ST_COUNT)
+    struct SignState {
+        std::vector<uint8_t> has;     // n flags: the members this context may sign for (empty: no signing key set)
+        DBuf<unsigned char> d_keys;   // [n secrets of 64 B][n flags]: the ONLY copy of the secrets, never read back
+        DBuf<unsigned char> d;        // scratch of a call: verdict block, levels, level counts and offsets, cursors, sorted events
+        DBuf<unsigned char> d_in;     // the staged arrays of the host-array forms; the signed arrays of sw_create_events
+        int64_t calls = 0, events = 0, levels = 0, keysets = 0;   // sw_get_sign_stats (levels: the last call's)
+        double ms[3] = {0, 0, 0};     // ... host time under sw_set_profiling: levels + sort, signing, commit
+    } sign;
+    // one event signed by one wavefront, and the gossip turn around it (sw_create_event, sw_gossip_turn; turn.hip.h): counters
+    // that sw_rewind / sw_reset leave alone
+    struct TurnState {
+        int64_t calls = 0, events = 0, turns = 0, profiled = 0;   // sw_get_turn_stats: sw_create_event calls, events the wave signed, turns, stamped launches
+        unsigned long long stamps[8] = {0};   // wall_clock64() at the phase boundaries of the last stamped launch (swt::ST_COUNT)
+    } turn;
 
     // device: events
     DBuf<int32_t> d_cr, d_sp, d_op, d_ht, d_seq, d_round, d_L, d_chain_ev;
@@ -494,6 +547,11 @@ int fail(sw_ctx* c, int code, const char* fmt, ...) {
         int rc_ = (expr);         \
         if (rc_ != SW_OK) return rc_; \
     } while (0)
+
+// ... and behind the commit point of an append: from there on a failure leaves the context half-updated, so it is poisoned
+#define PCHK(expr) do { int rc_ = (expr); if (rc_ != SW_OK) { c->poisoned = true; return rc_; } } while (0)
+#define PHIP(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { c->poisoned = true; \
+        return fail(c, SW_EIO, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); } } while (0)
 
 // debugging aid (SW_POISON=<byte>): fresh device memory is filled with that byte, so that a read of
 // memory no kernel has written shows up in any test instead of depending on what the heap held before
@@ -736,7 +794,29 @@ int vm_map_scratch(sw_ctx* c) {
     return SW_OK;
 }
 
-int heights_ready(sw_ctx* c);
+// The heights kernel of a device append runs behind the call (stream_io).  Whoever reads d_ht, max_height or the
+// block spans, or moves the event arrays, waits for it here and folds its read-back into the host tables.
+int heights_ready(sw_ctx* c) {
+    if (!c->ing.ht_pending) return SW_OK;
+    c->ing.ht_pending = false;
+    const int64_t blk0 = c->ing.ht_first >> 12, nblk = ((c->ing.ht_first + c->ing.ht_K - 1) >> 12) - blk0 + 1;
+    std::vector<int32_t> st((size_t)(2 + 2 * nblk));
+    hipError_t e_ = hipEventSynchronize(c->ing.ev_ht);
+    if (e_ == hipSuccess) e_ = hipMemcpy(st.data(), c->ing.d_ht_stat.p, st.size() * sizeof(int32_t), hipMemcpyDeviceToHost);
+    if (e_ != hipSuccess) { c->poisoned = true; return fail(c, SW_EIO, "heights of a device append: %s", hipGetErrorString(e_)); }
+    if (st[0] != 0) {
+        c->poisoned = true;
+        return fail(c, SW_EIO, "heights of a device append: a tile did not settle within its trip bound (internal)");
+    }
+    c->max_height = std::max(c->max_height, st[1]);
+    c->blk_hmin.resize((size_t)(blk0 + nblk), 0x7fffffff);
+    c->blk_hmax.resize((size_t)(blk0 + nblk), -1);
+    for (int64_t b = 0; b < nblk; ++b) {
+        c->blk_hmin[blk0 + b] = std::min(c->blk_hmin[blk0 + b], st[2 + 2 * b]);
+        c->blk_hmax[blk0 + b] = std::max(c->blk_hmax[blk0 + b], st[3 + 2 * b]);
+    }
+    return SW_OK;
+}
 
 int ensure_events(sw_ctx* c, int64_t need) {
     if (need <= c->cap) return SW_OK;
@@ -877,29 +957,6 @@ int rebuild_chains(sw_ctx* c, const std::vector<int32_t>& cnt, int64_t n_events)
 // ---- lazily fetched host mirrors: the device arrays are the source of truth -------------------
 // self / other parents and heights (swirld.py:117-120) of all events: needed by sw_get_height and
 // by the level-bucketed can_see kernels only
-// The heights kernel of a device append runs behind the call (stream_io).  Whoever reads d_ht, max_height or the
-// block spans, or moves the event arrays, waits for it here and folds its read-back into the host tables.
-int heights_ready(sw_ctx* c) {
-    if (!c->ht_pending) return SW_OK;
-    c->ht_pending = false;
-    const int64_t blk0 = c->ht_first >> 12, nblk = ((c->ht_first + c->ht_K - 1) >> 12) - blk0 + 1;
-    std::vector<int32_t> st((size_t)(2 + 2 * nblk));
-    hipError_t e_ = hipEventSynchronize(c->ev_ht);
-    if (e_ == hipSuccess) e_ = hipMemcpy(st.data(), c->d_ht_stat.p, st.size() * sizeof(int32_t), hipMemcpyDeviceToHost);
-    if (e_ != hipSuccess) { c->poisoned = true; return fail(c, SW_EIO, "heights of a device append: %s", hipGetErrorString(e_)); }
-    if (st[0] != 0) {
-        c->poisoned = true;
-        return fail(c, SW_EIO, "heights of a device append: a tile did not settle within its trip bound (internal)");
-    }
-    c->max_height = std::max(c->max_height, st[1]);
-    c->blk_hmin.resize((size_t)(blk0 + nblk), 0x7fffffff);
-    c->blk_hmax.resize((size_t)(blk0 + nblk), -1);
-    for (int64_t b = 0; b < nblk; ++b) {
-        c->blk_hmin[blk0 + b] = std::min(c->blk_hmin[blk0 + b], st[2 + 2 * b]);
-        c->blk_hmax[blk0 + b] = std::max(c->blk_hmax[blk0 + b], st[3 + 2 * b]);
-    }
-    return SW_OK;
-}
 
 int ensure_dag_h(sw_ctx* c) {
     CHK(heights_ready(c));
@@ -908,7 +965,7 @@ int ensure_dag_h(sw_ctx* c) {
     const int64_t K = c->N - have;
     // events [have, dev) were appended from device memory: their heights are in d_ht already and are downloaded;
     // those behind came through a bulk host append, and the host loop below computes theirs
-    const int64_t dev = std::min(std::max(c->ht_dev_upto, have), c->N);
+    const int64_t dev = std::min(std::max(c->ing.ht_dev_upto, have), c->N);
     c->sp.resize(c->N); c->op.resize(c->N); c->ht.resize(c->N);
     HIPCHK(c, hipMemcpyAsync(c->sp.data() + have, c->d_sp.p + have, (size_t)K * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(c->op.data() + have, c->d_op.p + have, (size_t)K * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
@@ -917,7 +974,7 @@ int ensure_dag_h(sw_ctx* c) {
     c->blk_hmin.resize((size_t)((c->N + 4095) >> 12), 0x7fffffff);
     c->blk_hmax.resize((size_t)((c->N + 4095) >> 12), -1);
     if (dev >= c->N) return SW_OK;
-    c->st_host_ht += c->N - dev;
+    c->ing.host_ht += c->N - dev;
     for (int64_t e = dev; e < c->N; ++e) {
         const int32_t s_ = c->sp[e], o_ = c->op[e];
         const int32_t h = s_ < 0 ? 0 : std::max(c->ht[s_], c->ht[o_]) + 1;  // swirld.py:117-120
@@ -1475,7 +1532,7 @@ int heights_for_spans(sw_ctx* c, const std::vector<int64_t>& cut, EdgeHeights& e
     CHK(heights_ready(c));
     const int64_t have = (int64_t)c->sp.size();
     if (have >= c->N) return SW_OK;
-    if (c->ht_dev_upto < c->N) return ensure_dag_h(c);
+    if (c->ing.ht_dev_upto < c->N) return ensure_dag_h(c);
     for (size_t i = 0; i < cut.size(); ++i) {
         const int64_t x = cut[i];
         const int64_t a = std::max<int64_t>(x & ~(int64_t)4095, have), b = std::min<int64_t>((x | (int64_t)4095) + 1, c->N);
@@ -2441,24 +2498,24 @@ int ensure_order_stage(sw_ctx* c, size_t ints) {
 // room for `tx_total` ordered events and for every stored event's two values; earlier records survive a growth
 int consensus_reserve(sw_ctx* c, size_t tx_total) {
     const size_t ev = (size_t)std::max<int64_t>(c->cap, c->N);
-    CHK(dgrow(c, c->d_rr, ev, c->d_rr.cap));
-    CHK(dgrow(c, c->d_cts, ev, c->d_cts.cap));
-    CHK(dgrow(c, c->d_tx, tx_total, (size_t)c->tx_len));
+    CHK(dgrow(c, c->cons.d_rr, ev, c->cons.d_rr.cap));
+    CHK(dgrow(c, c->cons.d_cts, ev, c->cons.d_cts.cap));
+    CHK(dgrow(c, c->cons.d_tx, tx_total, (size_t)c->cons.tx_len));
     return SW_OK;
 }
 
 int consensus_record_enqueue(sw_ctx* c, int64_t n_acc, size_t tx_at, int nr, const long long* acc_off, const int32_t* hostflag, const int32_t* sorted) {
     hipLaunchKernelGGL(cns::k_consensus_record, dim3((unsigned)((n_acc + cns::THREADS - 1) / cns::THREADS)), dim3(cns::THREADS), 0, c->stream,
                        (const int*)c->d_acc_ev.p, (const int*)c->d_acc_ri.p, (const int*)c->d_ord_rounds.p, (const unsigned long long*)c->d_ts.p,
-                       (long long)n_acc, c->d_rr.p, (unsigned long long*)c->d_cts.p);
+                       (long long)n_acc, c->cons.d_rr.p, (unsigned long long*)c->cons.d_cts.p);
     c->ctr.kernel_launches++;
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(c->d_tx.p + tx_at, c->d_sorted.p, (size_t)n_acc * sizeof(int32_t), hipMemcpyDeviceToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->cons.d_tx.p + tx_at, c->d_sorted.p, (size_t)n_acc * sizeof(int32_t), hipMemcpyDeviceToDevice, c->stream));
     bool patched = false;
     for (int i = 0; i < nr; ++i) {
         const int64_t len = acc_off[i + 1] - acc_off[i];
         if (!hostflag[i] || !len) continue;
-        HIPCHK(c, hipMemcpyAsync(c->d_tx.p + tx_at + acc_off[i], sorted + acc_off[i], (size_t)len * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(c->cons.d_tx.p + tx_at + acc_off[i], sorted + acc_off[i], (size_t)len * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
         patched = true;
     }
     if (patched) HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -2473,9 +2530,9 @@ int consensus_record_enqueue(sw_ctx* c, int64_t n_acc, size_t tx_at, int nr, con
 int consensus_record(sw_ctx* c, int64_t n_acc, size_t tx_at, int nr, const long long* acc_off, const int32_t* hostflag, const int32_t* sorted) {
     const int rc = consensus_record_enqueue(c, n_acc, tx_at, nr, acc_off, hostflag, sorted);
     if (rc != SW_OK) { c->poisoned = true; return rc; }   // (the host's order is extended, the device's is not)
-    c->tx_len = (int64_t)tx_at + n_acc;
-    c->cs_record_calls++;
-    c->cs_recorded += n_acc;
+    c->cons.tx_len = (int64_t)tx_at + n_acc;
+    c->cons.record_calls++;
+    c->cons.recorded += n_acc;
     return SW_OK;
 }
 
@@ -2992,7 +3049,7 @@ int do_find_order(sw_ctx* c, std::vector<int32_t> rounds, int32_t* out_events, i
 }
 
 
-// the history of the exact path (sw_set_exact_history; defined behind the votes export, whose table the hand-over expands)
+// the history of the exact path (sw_set_exact_history; exact_history.hip.h): what exact_* calls
 static_assert(xh::QNAN_BITS == cns::QNAN_BITS, "one quiet NaN for 'not ordered'");
 // SW_VOTE_STORE_INIT / SW_VOTE_STORE_MAX (measurement and test knobs), read at sw_create and again by sw_rewind / sw_reset,
 // where the store is empty: its first capacity and its ceiling, in entries
@@ -3002,12 +3059,78 @@ void history_knobs(sw_ctx* c) {
     if (const char* e_ = getenv("SW_VOTE_STORE_INIT")) { const long long w = atoll(e_); if (w >= 1 && w <= ((long long)1 << 29)) c->hist.cap0 = w; }
     if (const char* e_ = getenv("SW_VOTE_STORE_MAX")) { const long long w = atoll(e_); if (w >= 1 && w <= ((long long)1 << 29)) c->hist.ceiling = w; }
 }
-int history_enter(sw_ctx* c);                                 // the end of exact_enter: normalise the per-event tables, take the fast path's votes over
-int history_defaults(sw_ctx* c, int64_t first, int64_t K);    // events [first, first + K) are not ordered
-int history_store_reserve(sw_ctx* c, int64_t need);           // room for `need` entries in all, up to the ceiling
-xh::Store history_store(sw_ctx* c);
-int history_record(sw_ctx* c, int64_t produced);              // behind a successful exact_order
-void history_votes_lost(sw_ctx* c, const char* why);
+
+xh::Store history_store(sw_ctx* c) {
+    auto& h = c->hist;
+    xh::Store s{};
+    s.voter = h.d_voter.p; s.cand = h.d_cand.p; s.value = h.d_value.p; s.tab = h.d_tab.p;
+    s.cap = h.cap; s.tmask = (unsigned)(h.slots - 1);
+    return s;
+}
+
+void history_votes_lost(sw_ctx* c, const char* why) {
+    c->hist.votes_ok = false;
+    c->hist.why = why;
+}
+
+// Room for `need` entries in all — at most the ceiling: what does not fit makes the kernel set the overflow word.  The log
+// keeps its entries (dgrow copies them), the index is emptied and rebuilt by k_votes_reindex, one thread per entry.
+int history_store_reserve(sw_ctx* c, int64_t need) {
+    auto& h = c->hist;
+    need = std::min(need, h.ceiling);
+    if (need <= h.cap && h.slots) return SW_OK;
+    int64_t nc = std::max<int64_t>(h.cap0, 1);
+    while (nc < need) nc *= 2;
+    nc = std::min(std::max(nc, h.cap), h.ceiling);
+    size_t slots = 2;
+    while (slots < 2 * (size_t)nc) slots *= 2;
+    const size_t keep = (size_t)h.count;
+    CHK(dgrow(c, h.d_voter, (size_t)nc, keep));
+    CHK(dgrow(c, h.d_cand, (size_t)nc, keep));
+    CHK(dgrow(c, h.d_value, (size_t)nc, keep));
+    CHK(dgrow(c, h.d_tab, slots, 0));
+    h.cap = nc;
+    h.slots = slots;
+    HIPCHK(c, hipMemsetAsync(h.d_tab.p, 0xff, slots * sizeof(int32_t), c->stream));
+    if (h.count) {
+        hipLaunchKernelGGL(xh::k_votes_reindex, dim3((unsigned)((h.count + xh::THREADS - 1) / xh::THREADS)), dim3(xh::THREADS), 0, c->stream, history_store(c), (long long)h.count);
+        c->ctr.kernel_launches++;
+        HIPCHK(c, hipGetLastError());
+    }
+    h.grows++;
+    return SW_OK;
+}
+
+int history_defaults(sw_ctx* c, int64_t first, int64_t K) {
+    if (!K) return SW_OK;
+    hipLaunchKernelGGL(xh::k_history_defaults, dim3((unsigned)((K + xh::THREADS - 1) / xh::THREADS)), dim3(xh::THREADS), 0, c->stream, (long long)first, (long long)K,
+                       c->cons.d_rr.p, (xh::u64*)c->cons.d_cts.p);
+    c->ctr.kernel_launches++;
+    HIPCHK(c, hipGetLastError());
+    return SW_OK;
+}
+
+// Behind a successful exact_order: the two values of its `produced` items into the per-event tables, the items behind the
+// device copy of the order.  (A call that failed returned before this and records nothing.)
+int history_record(sw_ctx* c, int64_t produced) {
+    if (!produced) return SW_OK;
+    const size_t at = (size_t)c->cons.tx_len;
+    CHK(consensus_reserve(c, at + (size_t)produced));
+    hipLaunchKernelGGL(xh::k_history_record, dim3((unsigned)((produced + xh::THREADS - 1) / xh::THREADS)), dim3(xh::THREADS), 0, c->stream, (long long)produced,
+                       (const int*)c->ex.items_ev.p, (const xh::u64*)c->ex.items_ts.p, (const int*)c->hist.d_items_rr.p, c->cons.d_rr.p, (xh::u64*)c->cons.d_cts.p);
+    c->ctr.kernel_launches++;
+    HIPCHK(c, hipGetLastError());
+    HIPCHK(c, hipMemcpyAsync(c->cons.d_tx.p + at, c->ex.items_ev.p, (size_t)produced * sizeof(int32_t), hipMemcpyDeviceToDevice, c->stream));
+    HIPCHK(c, hipStreamSynchronize(c->stream));   // (the next call may overwrite the items)
+    c->cons.tx_len = (int64_t)at + produced;
+    c->cons.record_calls++;
+    c->cons.recorded += produced;
+    return SW_OK;
+}
+
+// The one declaration ahead of its definition, for a true cycle: exact_enter ends in history_enter, and history_enter
+// writes the exact path's header (exact_set_hdr) and expands the table of the votes export, both defined behind exact_*.
+int history_enter(sw_ctx* c);
 
 }  // namespace
 
@@ -3146,9 +3269,9 @@ int sw_create(int n_members, const uint64_t* stake, int coin_period, int device,
     if (c->debug_timing) {
         debug_buf(c->d_flow_dbg, 8);
     }
-    if (const char* e_ = getenv("SW_EXPORT_LANES")) { const int g = atoi(e_); if (g == 4 || g == 8) c->export_lanes = g; }
-    if (const char* e_ = getenv("SW_WALK_THREADS")) { const int w = atoi(e_); if (w >= 64 && w <= wlk::MAX_THREADS && w % 64 == 0) c->walk_threads = w; }
-    if (const char* e_ = getenv("SW_WIRE_BLOCKS")) { const int w = atoi(e_); if (w >= 1 && w <= 4096) c->wire_blocks = w; }
+    if (const char* e_ = getenv("SW_EXPORT_LANES")) { const int g = atoi(e_); if (g == 4 || g == 8) c->xp.lanes = g; }
+    if (const char* e_ = getenv("SW_WALK_THREADS")) { const int w = atoi(e_); if (w >= 64 && w <= wlk::MAX_THREADS && w % 64 == 0) c->walk.threads = w; }
+    if (const char* e_ = getenv("SW_WIRE_BLOCKS")) { const int w = atoi(e_); if (w >= 1 && w <= 4096) c->wire.blocks = w; }
     history_knobs(c);
     if (getenv("SW_DEBUG_CLOCKS")) {  // diagnostics: phase stamps of the round-loop kernels
         c->dbg_minor = atoi(getenv("SW_DEBUG_CLOCKS")) >= 2 ? 0 : 1;
@@ -3262,7 +3385,20 @@ int sw_create(int n_members, const uint64_t* stake, int coin_period, int device,
     return SW_OK;
 }
 
-static void split_dissolve(SplitGroup* g);
+static void split_dissolve(SplitGroup* g) {
+    if (!g) return;
+    for (int q = 0; q < g->parts; ++q)
+        if (g->ctx[q]) {
+            sw_ctx* c = g->ctx[q];
+            (void)hipStreamSynchronize(c->stream);
+            if (c->split == g) { c->tally_impl = c->split_saved[0]; c->tally_auto = c->split_saved[1] != 0; c->K = c->split_saved[2]; c->K_auto = c->split_saved[3] != 0; }   // (what the link pinned)
+            c->split = nullptr;
+        }
+    for (int w = 0; w < 2; ++w)
+        for (int q = 0; q < SW_MAX_PARTS; ++q)
+            for (auto e : g->ev[w][q]) if (e) (void)hipEventDestroy(e);
+    delete g;
+}
 
 int sw_destroy(sw_ctx* c) {
     if (c && c->split) split_dissolve(c->split);
@@ -3282,7 +3418,7 @@ int sw_destroy(sw_ctx* c) {
                 c->stage_us[0] * k, c->stage_us[1] * k, c->stage_us[2] * k, c->stage_us[3] * k, c->stage_us[4] * k, c->stage_us[5] * k);
     }
     if (c->vm.active) { vm_destroy(c); c->d_L.release(); }   // (d_L aliased the reservation)
-    if (c->d_sg_keys.p) { (void)hipMemset(c->d_sg_keys.p, 0, c->d_sg_keys.cap); (void)hipDeviceSynchronize(); }   // the secrets do not outlive the context
+    if (c->sign.d_keys.p) { (void)hipMemset(c->sign.d_keys.p, 0, c->sign.d_keys.cap); (void)hipDeviceSynchronize(); }   // the secrets do not outlive the context
     if (c->stream_io) (void)hipStreamSynchronize(c->stream_io);
     for (int g = 0; g < 4; ++g) {
         if (c->loop_exec[g]) (void)hipGraphExecDestroy(c->loop_exec[g]);
@@ -3324,52 +3460,52 @@ swx::State exact_state(sw_ctx* c) {
     swx::State s{};
     s.n = c->n; s.npad = c->npad; s.coin_period = c->coin_period; s.tot = c->tot; s.stake = c->d_stake.p;
     s.cr = c->d_cr.p; s.sp = c->d_sp.p; s.op = c->d_op.p; s.ht = c->d_ht.p; s.t = c->d_t.p; s.sig = c->d_sig.p;
-    s.round = c->d_round.p; s.L = c->d_L.p; s.tbd = c->x_tbd.p; s.fam_ev = c->x_fam_ev.p;
-    s.Rcap = c->Rcap; s.wit = c->d_wit.p; s.worder = c->x_worder.p; s.wcnt = c->x_wcnt.p; s.cons = c->d_cons.p;
-    s.fam_slot = c->d_fam.p; s.hdr = c->x_hdr.p;
+    s.round = c->d_round.p; s.L = c->d_L.p; s.tbd = c->ex.tbd.p; s.fam_ev = c->ex.fam_ev.p;
+    s.Rcap = c->Rcap; s.wit = c->d_wit.p; s.worder = c->ex.worder.p; s.wcnt = c->ex.wcnt.p; s.cons = c->d_cons.p;
+    s.fam_slot = c->d_fam.p; s.hdr = c->ex.hdr.p;
     return s;
 }
 
 // per-event and per-round buffers of the exact path follow the context's capacities
 int exact_grow(sw_ctx* c) {
     const size_t np = c->npad;
-    if (c->x_cap < c->cap) {
-        const size_t keep = (size_t)c->x_cap, nc = (size_t)c->cap;
-        CHK(dgrow(c, c->x_fam_ev, nc, keep));
-        CHK(dgrow(c, c->x_tbd, nc, keep));
-        CHK(dgrow(c, c->x_queue, nc + 1, 0));
-        CHK(dgrow(c, c->x_visited, nc + 1, 0));
-        CHK(dgrow(c, c->x_items_ev, nc + 1, 0));
-        CHK(dgrow(c, c->x_items_ts, nc + 1, 0));
-        HIPCHK(c, hipMemsetAsync(c->x_fam_ev.p + keep, 0xff, nc - keep, c->stream));
-        HIPCHK(c, hipMemsetAsync(c->x_tbd.p + keep, 1, nc - keep, c->stream));
-        HIPCHK(c, hipMemsetAsync(c->x_visited.p, 0, c->x_visited.cap, c->stream));  // all zero between calls
-        c->x_cap = c->cap;
+    if (c->ex.cap < c->cap) {
+        const size_t keep = (size_t)c->ex.cap, nc = (size_t)c->cap;
+        CHK(dgrow(c, c->ex.fam_ev, nc, keep));
+        CHK(dgrow(c, c->ex.tbd, nc, keep));
+        CHK(dgrow(c, c->ex.queue, nc + 1, 0));
+        CHK(dgrow(c, c->ex.visited, nc + 1, 0));
+        CHK(dgrow(c, c->ex.items_ev, nc + 1, 0));
+        CHK(dgrow(c, c->ex.items_ts, nc + 1, 0));
+        HIPCHK(c, hipMemsetAsync(c->ex.fam_ev.p + keep, 0xff, nc - keep, c->stream));
+        HIPCHK(c, hipMemsetAsync(c->ex.tbd.p + keep, 1, nc - keep, c->stream));
+        HIPCHK(c, hipMemsetAsync(c->ex.visited.p, 0, c->ex.visited.cap, c->stream));  // all zero between calls
+        c->ex.cap = c->cap;
     }
     if (c->hist.on) {   // (asked for on every call: the switch may have been set after a sw_reset that kept the buffers above)
         CHK(dgrow(c, c->hist.d_items_rr, (size_t)c->cap + 1, 0));
-        CHK(consensus_reserve(c, (size_t)c->tx_len));   // d_rr / d_cts follow the capacity; what was recorded stays
+        CHK(consensus_reserve(c, (size_t)c->cons.tx_len));   // d_rr / d_cts follow the capacity; what was recorded stays
     }
-    if (c->x_Rcap < c->Rcap) {
-        const size_t keep = (size_t)c->x_Rcap, nc = (size_t)c->Rcap;
-        CHK(dgrow(c, c->x_worder, nc * np, keep * np));
-        CHK(dgrow(c, c->x_wcnt, nc, keep));
-        CHK(dgrow(c, c->x_done, nc, 0));
-        CHK(dgrow(c, c->x_newr, nc, 0));
-        HIPCHK(c, hipMemsetAsync(c->x_wcnt.p + keep, 0, (nc - keep) * sizeof(int32_t), c->stream));
-        c->x_Rcap = c->Rcap;
+    if (c->ex.Rcap < c->Rcap) {
+        const size_t keep = (size_t)c->ex.Rcap, nc = (size_t)c->Rcap;
+        CHK(dgrow(c, c->ex.worder, nc * np, keep * np));
+        CHK(dgrow(c, c->ex.wcnt, nc, keep));
+        CHK(dgrow(c, c->ex.done, nc, 0));
+        CHK(dgrow(c, c->ex.newr, nc, 0));
+        HIPCHK(c, hipMemsetAsync(c->ex.wcnt.p + keep, 0, (nc - keep) * sizeof(int32_t), c->stream));
+        c->ex.Rcap = c->Rcap;
     }
     return SW_OK;
 }
 
 int exact_read_hdr(sw_ctx* c, long long* hdr) {
-    HIPCHK(c, hipMemcpyAsync(hdr, c->x_hdr.p, swx::H_WORDS * sizeof(long long), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(hdr, c->ex.hdr.p, swx::H_WORDS * sizeof(long long), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return SW_OK;
 }
 
 int exact_set_hdr(sw_ctx* c, int slot, long long v) {
-    HIPCHK(c, hipMemcpyAsync(c->x_hdr.p + slot, &v, sizeof v, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->ex.hdr.p + slot, &v, sizeof v, hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return SW_OK;
 }
@@ -3382,19 +3518,19 @@ int exact_enter(sw_ctx* c) {
     CHK(ensure_dag_h(c));  // host sp / op / height complete, heights on the device
     CHK(ensure_rounds(c, std::max(c->max_height + 3, c->R + 1)));
     const size_t np = c->npad;
-    CHK(dgrow(c, c->x_hdr, (size_t)swx::H_WORDS, 0));
-    CHK(dgrow(c, c->x_sm, np, 0)); CHK(dgrow(c, c->x_fw, np, 0)); CHK(dgrow(c, c->x_sflag, np, 0));
-    CHK(dgrow(c, c->x_times, np, 0)); CHK(dgrow(c, c->x_tsort, np, 0)); CHK(dgrow(c, c->x_white, 64, 0));
+    CHK(dgrow(c, c->ex.hdr, (size_t)swx::H_WORDS, 0));
+    CHK(dgrow(c, c->ex.sm, np, 0)); CHK(dgrow(c, c->ex.fw, np, 0)); CHK(dgrow(c, c->ex.sflag, np, 0));
+    CHK(dgrow(c, c->ex.times, np, 0)); CHK(dgrow(c, c->ex.tsort, np, 0)); CHK(dgrow(c, c->ex.white, 64, 0));
     CHK(exact_grow(c));
     long long hdr[swx::H_WORDS] = {0};
     hdr[swx::H_R] = c->R;
-    HIPCHK(c, hipMemcpyAsync(c->x_hdr.p, hdr, sizeof hdr, hipMemcpyHostToDevice, c->stream));
-    HIPCHK(c, hipMemsetAsync(c->x_wcnt.p, 0, (size_t)c->x_Rcap * sizeof(int32_t), c->stream));
-    c->x_fc_base = c->fc_seen;
+    HIPCHK(c, hipMemcpyAsync(c->ex.hdr.p, hdr, sizeof hdr, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemsetAsync(c->ex.wcnt.p, 0, (size_t)c->ex.Rcap * sizeof(int32_t), c->stream));
+    c->ex.fc_base = c->fc_seen;
     const long long n_tx = (long long)c->transactions.size();
-    if (n_tx) HIPCHK(c, hipMemcpyAsync(c->x_items_ev.p, c->transactions.data(), (size_t)n_tx * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    if (n_tx) HIPCHK(c, hipMemcpyAsync(c->ex.items_ev.p, c->transactions.data(), (size_t)n_tx * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    hipLaunchKernelGGL(k_exact_import, dim3(1), dim3(64), 0, c->stream, exact_state(c), (long long)c->N, (const int*)c->x_items_ev.p, n_tx);
+    hipLaunchKernelGGL(k_exact_import, dim3(1), dim3(64), 0, c->stream, exact_state(c), (long long)c->N, (const int*)c->ex.items_ev.p, n_tx);
     c->ctr.kernel_launches++;
     HIPCHK(c, hipGetLastError());
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -3444,8 +3580,8 @@ int append_exact(sw_ctx* c, int64_t K, const int32_t* creator, const int32_t* se
     if (sig64) HIPCHK(c, hipMemcpyAsync(c->d_sig.p + (size_t)N0 * 64, sig64, (size_t)K * 64, hipMemcpyHostToDevice, c->stream));
     else HIPCHK(c, hipMemsetAsync(c->d_sig.p + (size_t)N0 * 64, 0, (size_t)K * 64, c->stream));
     HIPCHK(c, hipMemsetAsync(c->d_round.p + N0, 0xff, b4, c->stream));
-    HIPCHK(c, hipMemsetAsync(c->x_fam_ev.p + N0, 0xff, (size_t)K, c->stream));
-    HIPCHK(c, hipMemsetAsync(c->x_tbd.p + N0, 1, (size_t)K, c->stream));
+    HIPCHK(c, hipMemsetAsync(c->ex.fam_ev.p + N0, 0xff, (size_t)K, c->stream));
+    HIPCHK(c, hipMemsetAsync(c->ex.tbd.p + N0, 1, (size_t)K, c->stream));
     if (c->hist.on) CHK(history_defaults(c, N0, K));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     c->cr.insert(c->cr.end(), creator, creator + K);
@@ -3485,8 +3621,8 @@ int exact_fame(sw_ctx* c, int32_t* new_rounds, int cap, int* n_new) {
     x.layer = (size_t)c->n * x.win * c->n;
     if (x.layer > ((size_t)4 << 30)) return fail(c, SW_ENOMEM, "exact decide_fame: %d undecided rounds x %d members need %zu GB of vote storage", x.win, c->n, (2 * x.layer) >> 30);
     CHK(exact_grow(c));
-    CHK(dgrow(c, c->x_votes, 2 * x.layer, 0));
-    x.votes = c->x_votes.p; x.s_m = c->x_sm.p; x.done = c->x_done.p; x.new_rounds = c->x_newr.p;
+    CHK(dgrow(c, c->ex.votes, 2 * x.layer, 0));
+    x.votes = c->ex.votes.p; x.s_m = c->ex.sm.p; x.done = c->ex.done.p; x.new_rounds = c->ex.newr.p;
     if (c->hist.on && c->hist.votes_ok) {
         // every voter round r_ stores at most n voters x (r_ - max_c) candidate rounds x n candidates
         const int64_t w = R - max_c;
@@ -3510,7 +3646,7 @@ int exact_fame(sw_ctx* c, int32_t* new_rounds, int cap, int* n_new) {
     const int cnt = (int)hdr[swx::H_NNEW];
     std::vector<int32_t> nr(std::max(cnt, 1));
     if (cnt) {
-        HIPCHK(c, hipMemcpyAsync(nr.data(), c->x_newr.p, (size_t)cnt * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(nr.data(), c->ex.newr.p, (size_t)cnt * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
     }
     for (int i = 0; i < cnt; ++i) {
@@ -3519,10 +3655,10 @@ int exact_fame(sw_ctx* c, int32_t* new_rounds, int cap, int* n_new) {
     }
     if (n_new) *n_new = cnt;
     FameCounters fc{};
-    fc.voter_evals = (u64)hdr[swx::H_VOTER_EVALS] + c->x_fc_base.voter_evals;
-    fc.majority_evals = (u64)hdr[swx::H_MAJ_EVALS] + c->x_fc_base.majority_evals;
-    fc.coin_votes = (u64)hdr[swx::H_COIN_VOTES] + c->x_fc_base.coin_votes;
-    fc.coin_flips = (u64)hdr[swx::H_COIN_FLIPS] + c->x_fc_base.coin_flips;
+    fc.voter_evals = (u64)hdr[swx::H_VOTER_EVALS] + c->ex.fc_base.voter_evals;
+    fc.majority_evals = (u64)hdr[swx::H_MAJ_EVALS] + c->ex.fc_base.majority_evals;
+    fc.coin_votes = (u64)hdr[swx::H_COIN_VOTES] + c->ex.fc_base.coin_votes;
+    fc.coin_flips = (u64)hdr[swx::H_COIN_FLIPS] + c->ex.fc_base.coin_flips;
     fame_counters(c, fc);
     if (cnt > cap) return fail(c, SW_ERANGE, "new_rounds capacity %d < %d", cap, cnt);
     return SW_OK;
@@ -3533,15 +3669,15 @@ int exact_order(sw_ctx* c, std::vector<int32_t> rounds, int32_t* out_events, int
     const int nr = (int)rounds.size();
     if (nr == 0) return SW_OK;
     CHK(exact_grow(c));
-    CHK(dgrow(c, c->x_rounds, nr, 0));
-    HIPCHK(c, hipMemcpyAsync(c->x_rounds.p, rounds.data(), (size_t)nr * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    CHK(dgrow(c, c->ex.rounds, nr, 0));
+    HIPCHK(c, hipMemcpyAsync(c->ex.rounds.p, rounds.data(), (size_t)nr * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
     CHK(exact_set_hdr(c, swx::H_RC, 0));
     CHK(exact_set_hdr(c, swx::H_NOUT, 0));
     swx::OrderScratch x{};
-    x.queue = c->x_queue.p; x.visited = c->x_visited.p; x.fw = c->x_fw.p; x.sflag = c->x_sflag.p; x.times = c->x_times.p;
-    x.tsort = c->x_tsort.p; x.white = c->x_white.p; x.items_ev = c->x_items_ev.p; x.items_ts = c->x_items_ts.p;
+    x.queue = c->ex.queue.p; x.visited = c->ex.visited.p; x.fw = c->ex.fw.p; x.sflag = c->ex.sflag.p; x.times = c->ex.times.p;
+    x.tsort = c->ex.tsort.p; x.white = c->ex.white.p; x.items_ev = c->ex.items_ev.p; x.items_ts = c->ex.items_ts.p;
     if (c->hist.on) x.items_rr = c->hist.d_items_rr.p;
-    hipLaunchKernelGGL(k_exact_order, dim3(1), dim3(64), 0, c->stream, exact_state(c), x, (const int*)c->x_rounds.p, nr);
+    hipLaunchKernelGGL(k_exact_order, dim3(1), dim3(64), 0, c->stream, exact_state(c), x, (const int*)c->ex.rounds.p, nr);
     c->ctr.kernel_launches++;
     HIPCHK(c, hipGetLastError());
     long long hdr[swx::H_WORDS];
@@ -3554,7 +3690,7 @@ int exact_order(sw_ctx* c, std::vector<int32_t> rounds, int32_t* out_events, int
     const size_t at = c->transactions.size();
     if (!c->transactions.resize(at + (size_t)produced)) return fail(c, SW_ENOMEM, "pinned host memory for the ordered events");
     if (produced) {
-        HIPCHK(c, hipMemcpyAsync(c->transactions.data() + at, c->x_items_ev.p, (size_t)produced * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(c->transactions.data() + at, c->ex.items_ev.p, (size_t)produced * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
     }
     if (c->hist.on) CHK(history_record(c, produced));
@@ -3567,11 +3703,11 @@ int exact_order(sw_ctx* c, std::vector<int32_t> rounds, int32_t* out_events, int
 // state of the exact path back to "nothing divided" (sw_rewind; the events and their forks stay)
 int exact_rewind(sw_ctx* c) {
     if (c->N) {
-        HIPCHK(c, hipMemsetAsync(c->x_fam_ev.p, 0xff, (size_t)c->N, c->stream));
-        HIPCHK(c, hipMemsetAsync(c->x_tbd.p, 1, (size_t)c->N, c->stream));
+        HIPCHK(c, hipMemsetAsync(c->ex.fam_ev.p, 0xff, (size_t)c->N, c->stream));
+        HIPCHK(c, hipMemsetAsync(c->ex.tbd.p, 1, (size_t)c->N, c->stream));
     }
-    if (c->x_Rcap) HIPCHK(c, hipMemsetAsync(c->x_wcnt.p, 0, (size_t)c->x_Rcap * sizeof(int32_t), c->stream));
-    HIPCHK(c, hipMemsetAsync(c->x_hdr.p, 0, swx::H_WORDS * sizeof(long long), c->stream));
+    if (c->ex.Rcap) HIPCHK(c, hipMemsetAsync(c->ex.wcnt.p, 0, (size_t)c->ex.Rcap * sizeof(int32_t), c->stream));
+    HIPCHK(c, hipMemsetAsync(c->ex.hdr.p, 0, swx::H_WORDS * sizeof(long long), c->stream));
     if (c->hist.on) {   // nothing is ordered, no vote has been cast: the store is empty and complete again
         if (c->N) CHK(history_defaults(c, 0, c->N));
         if (c->hist.slots) HIPCHK(c, hipMemsetAsync(c->hist.d_tab.p, 0xff, c->hist.slots * sizeof(int32_t), c->stream));
@@ -3582,7 +3718,7 @@ int exact_rewind(sw_ctx* c) {
         if (c->hist.cap > c->hist.ceiling) c->hist.cap = c->hist.ceiling;   // (the buffers stay; the kernel stops at `cap`)
     }
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->x_fc_base = c->fc_seen;
+    c->ex.fc_base = c->fc_seen;
     return SW_OK;
 }
 
@@ -3762,9 +3898,6 @@ int sw_append_events(sw_ctx* c, int64_t K, const int32_t* creator, const int32_t
             return fail(c, SW_EINVAL, "event %d: other-parent is by the same member", verdict);
     }
     // ---- 4. commit.  From here on a device failure leaves the context inconsistent: it is poisoned.
-#define PCHK(expr) do { int rc_ = (expr); if (rc_ != SW_OK) { c->poisoned = true; return rc_; } } while (0)
-#define PHIP(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { c->poisoned = true; \
-        return fail(c, SW_EIO, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); } } while (0)
     c->cr.insert(c->cr.end(), creator, creator + K);
     c->seq_h.insert(c->seq_h.end(), seq.begin(), seq.end());
     // the lazily fetched mirrors stay complete when they were complete (a Node appends a few events per
@@ -3813,8 +3946,6 @@ int sw_append_events(sw_ctx* c, int64_t K, const int32_t* creator, const int32_t
     PCHK(rebuild_chains(c, nev_t, c->N));
     c->nev.swap(nev_t);
     PHIP(hipStreamSynchronize(c->stream));  // caller buffers may be released on return (bulk payload: staged copy)
-#undef PCHK
-#undef PHIP
     return SW_OK;
 }
 
@@ -3824,7 +3955,7 @@ namespace {
 // Everything outside the bulk fork-free fast path: the batch goes to the host and through sw_append_events.
 int ingest_fallback(sw_ctx* c, int64_t K, const int32_t* d_creator, const int32_t* d_self_parent, const int32_t* d_other_parent,
                     const double* d_t, const uint8_t* d_sig64, hipStream_t us) {
-    c->st_fallback++;
+    c->ing.fallback++;
     std::vector<int32_t> cr((size_t)K), sp((size_t)K), op((size_t)K);
     std::vector<double> t(d_t ? (size_t)K : 0);
     std::vector<uint8_t> sig(d_sig64 ? (size_t)K * 64 : 0);
@@ -3840,21 +3971,6 @@ int ingest_fallback(sw_ctx* c, int64_t K, const int32_t* d_creator, const int32_
 
 }  // namespace
 
-static int append_device_body(sw_ctx* c, int64_t K, const int32_t* d_creator, const int32_t* d_self_parent, const int32_t* d_other_parent,
-                              const double* d_t, const uint8_t* d_sig64, hipStream_t us);
-
-int sw_append_events_device(sw_ctx* c, int64_t K, const int32_t* d_creator, const int32_t* d_self_parent,
-                            const int32_t* d_other_parent, const double* d_t, const uint8_t* d_sig64, void* user_stream) {
-    if (!c) return SW_EINVAL;
-    if (c->poisoned) return fail(c, SW_EIO, "context unusable after an earlier device failure");
-    if (K < 0 || (K > 0 && (!d_creator || !d_self_parent || !d_other_parent))) return fail(c, SW_EINVAL, "NULL event arrays");
-    if (K == 0) return SW_OK;
-    if (c->N + K > 0x7ffffff0ll) return fail(c, SW_ERANGE, "more than 2^31 events");
-    const size_t k = (size_t)K;
-    CHK(device_args(c, "sw_append_events_device", {{d_creator, k * 4, 1}, {d_self_parent, k * 4, 1}, {d_other_parent, k * 4, 1}, {d_t, k * 8, 1}, {d_sig64, k * 64, 1}}));
-    return append_device_body(c, K, d_creator, d_self_parent, d_other_parent, d_t, d_sig64, (hipStream_t)user_stream);
-}
-
 // The call itself, behind the argument checks: K > 0 events in memory of the context's device, produced on `us`.
 // (Also the last step of sw_ingest_payload[_device], with `us` the context's own stream.)
 static int append_device_body(sw_ctx* c, int64_t K, const int32_t* d_creator, const int32_t* d_self_parent, const int32_t* d_other_parent,
@@ -3867,18 +3983,18 @@ static int append_device_body(sw_ctx* c, int64_t K, const int32_t* d_creator, co
         return ingest_fallback(c, K, d_creator, d_self_parent, d_other_parent, d_t, d_sig64, us);
     // heights of the events so far must be on the device (a bulk HOST append leaves them to ensure_dag_h)
     CHK(heights_ready(c));
-    if ((int64_t)c->sp.size() < N0 && c->ht_dev_upto < N0) CHK(ensure_dag_h(c));
+    if ((int64_t)c->sp.size() < N0 && c->ing.ht_dev_upto < N0) CHK(ensure_dag_h(c));
     // ---- allocations (nothing committed)
     CHK(ensure_events(c, N0 + K));
     const int tiles = (int)((K + ing::TILE - 1) / ing::TILE);
     const int64_t blk0 = N0 >> 12, nblk = ((N0 + K - 1) >> 12) - blk0 + 1;
-    CHK(dgrow(c, c->d_ing_tab, (size_t)4 + 3 * np, 0));
-    CHK(dgrow(c, c->d_ing_hist, (size_t)tiles * np, 0));
-    CHK(dgrow(c, c->d_ht_stat, (size_t)(2 + 2 * nblk), 0));
+    CHK(dgrow(c, c->ing.d_tab, (size_t)4 + 3 * np, 0));
+    CHK(dgrow(c, c->ing.d_hist, (size_t)tiles * np, 0));
+    CHK(dgrow(c, c->ing.d_ht_stat, (size_t)(2 + 2 * nblk), 0));
     // (the pinned staging buffer may still feed the payload upload of an earlier bulk host append)
     if (c->payload_pending) { HIPCHK(c, hipEventSynchronize(c->ev_payload)); c->payload_pending = false; }
     if (!c->h_pin.reserve((size_t)K * 8)) return fail(c, SW_ENOMEM, "hipHostMalloc(%zu bytes) for the ingest read-back buffer failed", (size_t)K * 8);
-    CHK(ensure_event(c, c->ev_ht));
+    CHK(ensure_event(c, c->ing.ev_ht));
     // ---- the context's stream waits for what the caller enqueued; parent arrays to the (uncommitted) tail
     UserStream bracket;
     CHK(bracket.join(c, us));
@@ -3886,7 +4002,7 @@ static int append_device_body(sw_ctx* c, int64_t K, const int32_t* d_creator, co
     HIPCHK(c, hipMemcpyAsync(c->d_sp.p + N0, d_self_parent, b4, hipMemcpyDeviceToDevice, c->stream));
     HIPCHK(c, hipMemcpyAsync(c->d_op.p + N0, d_other_parent, b4, hipMemcpyDeviceToDevice, c->stream));
     // ---- verdict word and per-member tables [nev | head | first]
-    std::vector<int32_t>& tab = c->ing_stage;
+    std::vector<int32_t>& tab = c->ing.stage;
     tab.assign((size_t)4 + 3 * np, 0);
     const unsigned long long none = ing::V_NONE;
     memcpy(tab.data(), &none, sizeof none);
@@ -3895,19 +4011,19 @@ static int append_device_body(sw_ctx* c, int64_t K, const int32_t* d_creator, co
         tab[4 + np + m] = m < n ? c->head[m] : -1;
         tab[4 + 2 * np + m] = (m < n && c->first_ev[m] >= 0) ? c->first_ev[m] : 0x7fffffff;
     }
-    HIPCHK(c, hipMemcpyAsync(c->d_ing_tab.p, tab.data(), tab.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
-    unsigned long long* d_v = (unsigned long long*)c->d_ing_tab.p;
-    int* d_tab = c->d_ing_tab.p + 4;
+    HIPCHK(c, hipMemcpyAsync(c->ing.d_tab.p, tab.data(), tab.size() * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    unsigned long long* d_v = (unsigned long long*)c->ing.d_tab.p;
+    int* d_tab = c->ing.d_tab.p + 4;
     int nbits = 0;
     while ((1 << nbits) < np) ++nbits;
     const dim3 ev_grid((unsigned)((K + 255) / 256));
     hipLaunchKernelGGL(ing::k_ingest_local, ev_grid, dim3(256), 0, c->stream, c->d_cr.p, (const int*)c->d_sp.p, (const int*)c->d_op.p,
                        (int)N0, (int)K, n, d_v);
     hipLaunchKernelGGL(ing::k_ingest_hist, dim3(tiles), dim3(ing::THREADS), 0, c->stream, (const int*)c->d_cr.p, (int)N0, (int)K, np,
-                       c->d_ing_hist.p, d_tab);
-    hipLaunchKernelGGL(ing::k_ingest_scan, dim3((np + 63) / 64), dim3(64), 0, c->stream, c->d_ing_hist.p, tiles, np, d_tab);
+                       c->ing.d_hist.p, d_tab);
+    hipLaunchKernelGGL(ing::k_ingest_scan, dim3((np + 63) / 64), dim3(64), 0, c->stream, c->ing.d_hist.p, tiles, np, d_tab);
     hipLaunchKernelGGL(ing::k_ingest_rank, dim3(tiles), dim3(ing::THREADS), 0, c->stream, (const int*)c->d_cr.p, (int)N0, (int)K, np, nbits,
-                       (const int*)c->d_ing_hist.p, c->d_seq.p);
+                       (const int*)c->ing.d_hist.p, c->d_seq.p);
     hipLaunchKernelGGL(ing::k_ingest_links, ev_grid, dim3(256), 0, c->stream, (const int*)c->d_cr.p, (const int*)c->d_sp.p,
                        (const int*)c->d_op.p, (const int*)c->d_seq.p, (int)N0, (int)K, d_v);
     c->ctr.kernel_launches += 5;
@@ -3915,7 +4031,7 @@ static int append_device_body(sw_ctx* c, int64_t K, const int32_t* d_creator, co
     // ---- one read-back: verdict and tables; the always-complete host mirrors (creator, chain position) ride along
     int32_t* pin_cr = (int32_t*)c->h_pin.p;
     int32_t* pin_seq = pin_cr + K;
-    HIPCHK(c, hipMemcpyAsync(tab.data(), c->d_ing_tab.p, tab.size() * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(tab.data(), c->ing.d_tab.p, tab.size() * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(pin_cr, c->d_cr.p + N0, b4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipMemcpyAsync(pin_seq, c->d_seq.p + N0, b4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -3935,9 +4051,6 @@ static int append_device_body(sw_ctx* c, int64_t K, const int32_t* d_creator, co
         }
     }
     // ---- commit.  From here on a device failure leaves the context inconsistent: it is poisoned.
-#define PCHK(expr) do { int rc_ = (expr); if (rc_ != SW_OK) { c->poisoned = true; return rc_; } } while (0)
-#define PHIP(expr) do { hipError_t e_ = (expr); if (e_ != hipSuccess) { c->poisoned = true; \
-        return fail(c, SW_EIO, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); } } while (0)
     c->cr.insert(c->cr.end(), pin_cr, pin_cr + K);
     c->seq_h.insert(c->seq_h.end(), pin_seq, pin_seq + K);
     std::vector<int32_t> nev_t(c->nev);
@@ -3959,30 +4072,40 @@ static int append_device_body(sw_ctx* c, int64_t K, const int32_t* d_creator, co
     std::vector<int32_t> st0((size_t)(2 + 2 * nblk));
     st0[0] = 0; st0[1] = -1;
     for (int64_t b = 0; b < nblk; ++b) { st0[2 + 2 * b] = 0x7fffffff; st0[3 + 2 * b] = -1; }
-    PHIP(hipMemcpy(c->d_ht_stat.p, st0.data(), st0.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+    PHIP(hipMemcpy(c->ing.d_ht_stat.p, st0.data(), st0.size() * sizeof(int32_t), hipMemcpyHostToDevice));
     hipLaunchKernelGGL(ing::k_ingest_heights, dim3(1), dim3(ing::HT_TILE), 0, c->stream_io, (const int*)c->d_sp.p, (const int*)c->d_op.p,
-                       c->d_ht.p, (int)N0, (int)K, (int)blk0, c->d_ht_stat.p);
+                       c->d_ht.p, (int)N0, (int)K, (int)blk0, c->ing.d_ht_stat.p);
     c->ctr.kernel_launches++;
     PHIP(hipGetLastError());
-    PHIP(hipEventRecord(c->ev_ht, c->stream_io));
-    c->ht_pending = true; c->ht_first = N0; c->ht_K = K; c->ht_dev_upto = N0 + K;
+    PHIP(hipEventRecord(c->ing.ev_ht, c->stream_io));
+    c->ing.ht_pending = true; c->ing.ht_first = N0; c->ing.ht_K = K; c->ing.ht_dev_upto = N0 + K;
     PCHK(rebuild_chains(c, nev_t, c->N));
     c->nev.swap(nev_t);
     PHIP(hipStreamSynchronize(c->stream));  // the caller's arrays may be reused or freed on return
     // ... and the caller's stream may not overwrite them before the copies above are done (they are: drained)
-    c->st_dev_batches++;
-    c->st_dev_events += K;
-#undef PCHK
-#undef PHIP
+    c->ing.dev_batches++;
+    c->ing.dev_events += K;
     return SW_OK;
+}
+
+int sw_append_events_device(sw_ctx* c, int64_t K, const int32_t* d_creator, const int32_t* d_self_parent,
+                            const int32_t* d_other_parent, const double* d_t, const uint8_t* d_sig64, void* user_stream) {
+    if (!c) return SW_EINVAL;
+    if (c->poisoned) return fail(c, SW_EIO, "context unusable after an earlier device failure");
+    if (K < 0 || (K > 0 && (!d_creator || !d_self_parent || !d_other_parent))) return fail(c, SW_EINVAL, "NULL event arrays");
+    if (K == 0) return SW_OK;
+    if (c->N + K > 0x7ffffff0ll) return fail(c, SW_ERANGE, "more than 2^31 events");
+    const size_t k = (size_t)K;
+    CHK(device_args(c, "sw_append_events_device", {{d_creator, k * 4, 1}, {d_self_parent, k * 4, 1}, {d_other_parent, k * 4, 1}, {d_t, k * 8, 1}, {d_sig64, k * 64, 1}}));
+    return append_device_body(c, K, d_creator, d_self_parent, d_other_parent, d_t, d_sig64, (hipStream_t)user_stream);
 }
 
 int sw_get_ingest_stats(sw_ctx* c, int64_t* device_batches, int64_t* device_events, int64_t* fallback_batches, int64_t* host_height_events) {
     if (!c) return SW_EINVAL;
-    if (device_batches) *device_batches = c->st_dev_batches;
-    if (device_events) *device_events = c->st_dev_events;
-    if (fallback_batches) *fallback_batches = c->st_fallback;
-    if (host_height_events) *host_height_events = c->st_host_ht;
+    if (device_batches) *device_batches = c->ing.dev_batches;
+    if (device_events) *device_events = c->ing.dev_events;
+    if (fallback_batches) *fallback_batches = c->ing.fallback;
+    if (host_height_events) *host_height_events = c->ing.host_ht;
     return SW_OK;
 }
 
@@ -3994,38 +4117,38 @@ constexpr int PL_WAVE_BATCH = 32;   // waves launched between two read-backs of 
 
 // (re)build the table from the ids the context holds
 int idtab_rebuild(sw_ctx* c) {
-    HIPCHK(c, hipMemsetAsync(c->d_idtab.p, 0xff, sizeof(int32_t) << c->idtab_log, c->stream));
-    if (c->n_ids) {
-        hipLaunchKernelGGL(rsv::k_tab_insert, dim3((unsigned)((c->n_ids + 255) / 256)), dim3(256), 0, c->stream, c->d_idtab.p, c->idtab_log,
-                           (const unsigned char*)c->d_id.p, 0, (int)c->n_ids, (int*)nullptr);
+    HIPCHK(c, hipMemsetAsync(c->ids.d_idtab.p, 0xff, sizeof(int32_t) << c->ids.idtab_log, c->stream));
+    if (c->ids.n_ids) {
+        hipLaunchKernelGGL(rsv::k_tab_insert, dim3((unsigned)((c->ids.n_ids + 255) / 256)), dim3(256), 0, c->stream, c->ids.d_idtab.p, c->ids.idtab_log,
+                           (const unsigned char*)c->ids.d_id.p, 0, (int)c->ids.n_ids, (int*)nullptr);
         c->ctr.kernel_launches++;
         HIPCHK(c, hipGetLastError());
     }
-    c->pl_rebuilds++;
+    c->ids.pl_rebuilds++;
     return SW_OK;
 }
 
 // room for `count` ids: the id array (contents kept) and a table of load <= 1/2
 int idindex_reserve(sw_ctx* c, int64_t count) {
-    CHK(dgrow(c, c->d_id, (size_t)count * 32, (size_t)c->n_ids * 32));
-    CHK(dgrow(c, c->d_idflag, 4, 0));
+    CHK(dgrow(c, c->ids.d_id, (size_t)count * 32, (size_t)c->ids.n_ids * 32));
+    CHK(dgrow(c, c->ids.d_idflag, 4, 0));
     int lg = 10;
     while ((1ll << lg) < 2 * count) ++lg;
-    if (lg <= c->idtab_log) return SW_OK;
-    CHK(dgrow(c, c->d_idtab, (size_t)1 << lg, 0));
-    c->idtab_log = lg;
+    if (lg <= c->ids.idtab_log) return SW_OK;
+    CHK(dgrow(c, c->ids.d_idtab, (size_t)1 << lg, 0));
+    c->ids.idtab_log = lg;
     return idtab_rebuild(c);
 }
 
 // insert the ids of the events [first, first + K) (already in d_id); *flag = 0 fine, 1 an id was present or twice, 2 table full
 int idtab_insert(sw_ctx* c, int64_t first, int64_t K, int* flag) {
-    HIPCHK(c, hipMemsetAsync(c->d_idflag.p, 0, sizeof(int32_t), c->stream));
-    hipLaunchKernelGGL(rsv::k_tab_insert, dim3((unsigned)((K + 255) / 256)), dim3(256), 0, c->stream, c->d_idtab.p, c->idtab_log,
-                       (const unsigned char*)c->d_id.p, (int)first, (int)K, c->d_idflag.p);
+    HIPCHK(c, hipMemsetAsync(c->ids.d_idflag.p, 0, sizeof(int32_t), c->stream));
+    hipLaunchKernelGGL(rsv::k_tab_insert, dim3((unsigned)((K + 255) / 256)), dim3(256), 0, c->stream, c->ids.d_idtab.p, c->ids.idtab_log,
+                       (const unsigned char*)c->ids.d_id.p, (int)first, (int)K, c->ids.d_idflag.p);
     c->ctr.kernel_launches++;
     HIPCHK(c, hipGetLastError());
     int32_t f = 0;
-    HIPCHK(c, hipMemcpyAsync(&f, c->d_idflag.p, sizeof f, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(&f, c->ids.d_idflag.p, sizeof f, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     *flag = f;
     return SW_OK;
@@ -4051,8 +4174,8 @@ int payload_core(sw_ctx* c, int64_t K, const uint8_t* d_id32, const uint8_t* d_s
     const size_t o_rank = cv.take((size_t)K * 4), o_hist = cv.take(tiles0 * 1024 * 4), o_tab = cv.take(3 * 1024 * 4), o_base = cv.take(1024 * 4);
     const size_t o_gcr = cv.take((size_t)K * 4), o_gsp = cv.take((size_t)K * 4), o_gop = cv.take((size_t)K * 4);
     const size_t o_gt = cv.take(d_t ? (size_t)K * 8 : 0), o_gsig = cv.take(d_sig64 ? (size_t)K * 64 : 0);
-    CHK(dgrow(c, c->d_pl, cv.off, 0));
-    unsigned char* B = c->d_pl.p;
+    CHK(dgrow(c, c->ids.d_pl, cv.off, 0));
+    unsigned char* B = c->ids.d_pl.p;
     int* lslots = (int*)(B + o_lslots); int* wave = (int*)(B + o_wave); int* pr = (int*)(B + o_pr);
     int* lst[2] = {(int*)(B + o_la), (int*)(B + o_lb)};
     int* pend = (int*)(B + o_pend); int* acc = (int*)(B + o_acc);
@@ -4061,7 +4184,7 @@ int payload_core(sw_ctx* c, int64_t K, const uint8_t* d_id32, const uint8_t* d_s
     int* g_cr = (int*)(B + o_gcr); int* g_sp = (int*)(B + o_gsp); int* g_op = (int*)(B + o_gop);
     double* g_t = d_t ? (double*)(B + o_gt) : nullptr;
     unsigned char* g_sig = d_sig64 ? B + o_gsig : nullptr;
-    if (!c->h_plcnt.reserve(2 * PL_WAVE_BATCH + 2)) return fail(c, SW_ENOMEM, "hipHostMalloc for the wave counts failed");
+    if (!c->ids.h_plcnt.reserve(2 * PL_WAVE_BATCH + 2)) return fail(c, SW_ENOMEM, "hipHostMalloc for the wave counts failed");
     UserStream bracket;   // (left by the destructor on a failure; a success has drained the stream)
     CHK(bracket.join(c, us));
     // ---- resolve: the payload's own table (lowest position of every id), local checks, parent references
@@ -4069,13 +4192,13 @@ int payload_core(sw_ctx* c, int64_t K, const uint8_t* d_id32, const uint8_t* d_s
     HIPCHK(c, hipMemsetAsync(lslots, 0xff, sizeof(int32_t) << llog, c->stream));
     HIPCHK(c, hipMemsetAsync(pend, 0, (o_acc - o_pend) + nctr * 4, c->stream));   // (pend and acc are neighbours)
     hipLaunchKernelGGL(rsv::k_tab_insert, ev_grid, dim3(256), 0, c->stream, lslots, llog, (const unsigned char*)d_id32, 0, (int)K, (int*)nullptr);
-    hipLaunchKernelGGL(rsv::k_pl_local, ev_grid, dim3(256), 0, c->stream, (const int*)c->d_idtab.p, N0 ? c->idtab_log : 0,
-                       (const unsigned char*)c->d_id.p, (const int*)lslots, llog, (const unsigned char*)d_id32, (const unsigned char*)d_sp_id32,
+    hipLaunchKernelGGL(rsv::k_pl_local, ev_grid, dim3(256), 0, c->stream, (const int*)c->ids.d_idtab.p, N0 ? c->ids.idtab_log : 0,
+                       (const unsigned char*)c->ids.d_id.p, (const int*)lslots, llog, (const unsigned char*)d_id32, (const unsigned char*)d_sp_id32,
                        (const unsigned char*)d_op_id32, (const unsigned char*)d_arity, (const int*)d_creator, (const unsigned char*)d_ok, (int)K, c->n,
                        (int*)d_out, wave, pr, lst[0], pend);
     c->ctr.kernel_launches += 2;
     HIPCHK(c, hipGetLastError());
-    if (prof) { HIPCHK(c, hipStreamSynchronize(c->stream)); c->pl_ms[0] = ms_since(t0); t0 = std::chrono::steady_clock::now(); }
+    if (prof) { HIPCHK(c, hipStreamSynchronize(c->stream)); c->ids.pl_ms[0] = ms_since(t0); t0 = std::chrono::steady_clock::now(); }
     // ---- waves: batches of launches, one read-back of their counts each; ends with the first wave that accepts nothing
     int64_t W = -1, A = 0, ub = K;
     for (int64_t w0 = 0; W < 0; w0 += PL_WAVE_BATCH) {
@@ -4086,23 +4209,23 @@ int payload_core(sw_ctx* c, int64_t K, const uint8_t* d_id32, const uint8_t* d_s
                                pend + w + 1, acc + w, (const int*)pr, (const int*)d_creator, (const int*)c->d_cr.p, wave, (int*)d_out);
         c->ctr.kernel_launches += PL_WAVE_BATCH;
         HIPCHK(c, hipGetLastError());
-        HIPCHK(c, hipMemcpyAsync(c->h_plcnt.p, pend + w0, (PL_WAVE_BATCH + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipMemcpyAsync(c->h_plcnt.p + PL_WAVE_BATCH + 1, acc + w0, PL_WAVE_BATCH * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(c->ids.h_plcnt.p, pend + w0, (PL_WAVE_BATCH + 1) * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(c->ids.h_plcnt.p + PL_WAVE_BATCH + 1, acc + w0, PL_WAVE_BATCH * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
         for (int j = 0; j < PL_WAVE_BATCH; ++j) {
-            const int a = c->h_plcnt.p[PL_WAVE_BATCH + 1 + j];
+            const int a = c->ids.h_plcnt.p[PL_WAVE_BATCH + 1 + j];
             if (a == 0) { W = w0 + j; break; }
             A += a;
         }
-        ub = c->h_plcnt.p[PL_WAVE_BATCH];
+        ub = c->ids.h_plcnt.p[PL_WAVE_BATCH];
     }
     hipLaunchKernelGGL(rsv::k_pl_leftover, ev_grid, dim3(256), 0, c->stream, (const int*)wave, (int)K, (int*)d_out);
     c->ctr.kernel_launches++;
-    c->pl_waves = W;
-    c->pl_accepted = A;
-    c->pl_calls++;
-    if (prof) { HIPCHK(c, hipStreamSynchronize(c->stream)); c->pl_ms[1] = ms_since(t0); t0 = std::chrono::steady_clock::now(); }
-    c->pl_ms[2] = c->pl_ms[3] = 0;
+    c->ids.pl_waves = W;
+    c->ids.pl_accepted = A;
+    c->ids.pl_calls++;
+    if (prof) { HIPCHK(c, hipStreamSynchronize(c->stream)); c->ids.pl_ms[1] = ms_since(t0); t0 = std::chrono::steady_clock::now(); }
+    c->ids.pl_ms[2] = c->ids.pl_ms[3] = 0;
     if (A == 0) {
         HIPCHK(c, hipStreamSynchronize(c->stream));
         bracket.drained();
@@ -4132,12 +4255,12 @@ int payload_core(sw_ctx* c, int64_t K, const uint8_t* d_id32, const uint8_t* d_s
     const dim3 a_grid((unsigned)((A + 255) / 256));
     hipLaunchKernelGGL(rsv::k_pl_ranks, a_grid, dim3(256), 0, c->stream, cur, (int)A, (int)N0, rank_of, (int*)d_out);
     hipLaunchKernelGGL(rsv::k_pl_gather, a_grid, dim3(256), 0, c->stream, cur, (int)A, (int)N0, (const int*)rank_of, (const int*)pr, (const int*)d_creator,
-                       (const unsigned char*)d_id32, d_t, g_cr, g_sp, g_op, g_t, c->d_id.p + (size_t)N0 * 32);
+                       (const unsigned char*)d_id32, d_t, g_cr, g_sp, g_op, g_t, c->ids.d_id.p + (size_t)N0 * 32);
     if (d_sig64)
         hipLaunchKernelGGL(rsv::k_pl_gather_sig, dim3((unsigned)((A * 16 + 255) / 256)), dim3(256), 0, c->stream, cur, (int)A, (const unsigned char*)d_sig64, g_sig);
     c->ctr.kernel_launches += 3;
     HIPCHK(c, hipGetLastError());
-    if (prof) { HIPCHK(c, hipStreamSynchronize(c->stream)); c->pl_ms[2] = ms_since(t0); t0 = std::chrono::steady_clock::now(); }
+    if (prof) { HIPCHK(c, hipStreamSynchronize(c->stream)); c->ids.pl_ms[2] = ms_since(t0); t0 = std::chrono::steady_clock::now(); }
     // ---- append (bulk device path or its fallbacks; atomic), then — only then — the ids
     CHK(append_device_body(c, A, g_cr, g_sp, g_op, g_t, g_sig, c->stream));
     int flag = 0;
@@ -4146,9 +4269,9 @@ int payload_core(sw_ctx* c, int64_t K, const uint8_t* d_id32, const uint8_t* d_s
         c->poisoned = true;
         return rc != SW_OK ? rc : fail(c, SW_EIO, "id table insert after the append reported %d (internal error)", flag);
     }
-    c->n_ids = N0 + A;
+    c->ids.n_ids = N0 + A;
     *n_stored = A;
-    if (prof) c->pl_ms[3] = ms_since(t0);
+    if (prof) c->ids.pl_ms[3] = ms_since(t0);
     bracket.drained();   // (idtab_insert has synchronised)
     return SW_OK;
 }
@@ -4160,8 +4283,8 @@ int payload_args(sw_ctx* c, int64_t K, const void* id, const void* sp, const voi
     *n_stored = 0;
     if (K < 0 || (K > 0 && (!id || !sp || !op || !ar || !cr || !out))) return fail(c, SW_EINVAL, "%s: NULL payload arrays", what);
     if (K > 0x3fffffffll || c->N + K > 0x7ffffff0ll) return fail(c, SW_ERANGE, "%s: more than 2^31 events", what);
-    if (c->n_ids != c->N)
-        return fail(c, SW_ENOTSUP, "%s: %lld of the %lld stored events have no id (sw_set_event_ids first)", what, (long long)(c->N - c->n_ids), (long long)c->N);
+    if (c->ids.n_ids != c->N)
+        return fail(c, SW_ENOTSUP, "%s: %lld of the %lld stored events have no id (sw_set_event_ids first)", what, (long long)(c->N - c->ids.n_ids), (long long)c->N);
     return SW_OK;
 }
 
@@ -4172,12 +4295,12 @@ int sw_set_event_ids(sw_ctx* c, int64_t first, int64_t K, const uint8_t* id32) {
     if (!c) return SW_EINVAL;
     if (c->poisoned) return fail(c, SW_EIO, "context unusable after an earlier device failure");
     if (K < 0 || (K > 0 && !id32)) return fail(c, SW_EINVAL, "sw_set_event_ids: NULL ids");
-    if (first != c->n_ids) return fail(c, SW_EINVAL, "sw_set_event_ids must continue at event %lld (got %lld): ids are contiguous from 0", (long long)c->n_ids, (long long)first);
+    if (first != c->ids.n_ids) return fail(c, SW_EINVAL, "sw_set_event_ids must continue at event %lld (got %lld): ids are contiguous from 0", (long long)c->ids.n_ids, (long long)first);
     if (first + K > c->N) return fail(c, SW_ERANGE, "events [%lld, %lld) outside the stored hashgraph", (long long)first, (long long)(first + K));
     if (K == 0) return SW_OK;
     HIPCHK(c, hipSetDevice(c->device));
     CHK(idindex_reserve(c, first + K));
-    HIPCHK(c, hipMemcpyAsync(c->d_id.p + (size_t)first * 32, id32, (size_t)K * 32, hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->ids.d_id.p + (size_t)first * 32, id32, (size_t)K * 32, hipMemcpyHostToDevice, c->stream));
     int flag = 0;
     CHK(idtab_insert(c, first, K, &flag));
     if (flag != 0) {
@@ -4186,17 +4309,17 @@ int sw_set_event_ids(sw_ctx* c, int64_t first, int64_t K, const uint8_t* id32) {
         if (flag == 1) return fail(c, SW_EINVAL, "sw_set_event_ids: an id is already present, or occurs twice in the call");
         return fail(c, SW_EIO, "sw_set_event_ids: id table full (internal error)");
     }
-    c->n_ids = first + K;
+    c->ids.n_ids = first + K;
     return SW_OK;
 }
 
 int sw_get_event_ids(sw_ctx* c, int64_t first, int64_t K, uint8_t* out) {
     if (!c) return SW_EINVAL;
-    if (first < 0 || K < 0 || first + K > c->n_ids) return fail(c, SW_ERANGE, "events [%lld, %lld) beyond the %lld events that have ids", (long long)first, (long long)(first + K), (long long)c->n_ids);
+    if (first < 0 || K < 0 || first + K > c->ids.n_ids) return fail(c, SW_ERANGE, "events [%lld, %lld) beyond the %lld events that have ids", (long long)first, (long long)(first + K), (long long)c->ids.n_ids);
     if (K == 0) return SW_OK;
     if (!out) return fail(c, SW_EINVAL, "sw_get_event_ids: NULL output");
     HIPCHK(c, hipSetDevice(c->device));
-    HIPCHK(c, hipMemcpyAsync(out, c->d_id.p + (size_t)first * 32, (size_t)K * 32, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(out, c->ids.d_id.p + (size_t)first * 32, (size_t)K * 32, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return SW_OK;
 }
@@ -4210,9 +4333,9 @@ int sw_lookup_event_ids(sw_ctx* c, int64_t K, const uint8_t* id32, int32_t* inde
     Stage st;
     const size_t o_id = st.in(id32, (size_t)K * 32), o_out = st.out(index_out, (size_t)K * 4);
     unsigned char* B = nullptr;
-    CHK(stage_up(c, c->d_pl_in, st, &B));
-    hipLaunchKernelGGL(rsv::k_tab_lookup, dim3((unsigned)((K + 255) / 256)), dim3(256), 0, c->stream, (const int*)c->d_idtab.p, c->n_ids ? c->idtab_log : 0,
-                       (const unsigned char*)c->d_id.p, (const unsigned char*)(B + o_id), (int)K, (int*)(B + o_out));
+    CHK(stage_up(c, c->ids.d_pl_in, st, &B));
+    hipLaunchKernelGGL(rsv::k_tab_lookup, dim3((unsigned)((K + 255) / 256)), dim3(256), 0, c->stream, (const int*)c->ids.d_idtab.p, c->ids.n_ids ? c->ids.idtab_log : 0,
+                       (const unsigned char*)c->ids.d_id.p, (const unsigned char*)(B + o_id), (int)K, (int*)(B + o_out));
     c->ctr.kernel_launches++;
     HIPCHK(c, hipGetLastError());
     return stage_down(c, st, B);
@@ -4241,7 +4364,7 @@ int sw_ingest_payload(sw_ctx* c, int64_t K, const uint8_t* id32, const uint8_t* 
     const size_t o_id = st.in(id32, k * 32), o_sp = st.in(sp_id32, k * 32), o_op = st.in(op_id32, k * 32), o_ar = st.in(arity, k), o_cr = st.in(creator, k * 4);
     const size_t o_ok = st.in(ok, k), o_t = st.in(t, k * 8), o_sig = st.in(sig64, k * 64), o_out = st.out(index_out, k * 4);
     unsigned char* B = nullptr;
-    CHK(stage_up(c, c->d_pl_in, st, &B));
+    CHK(stage_up(c, c->ids.d_pl_in, st, &B));
     CHK(payload_core(c, K, B + o_id, B + o_sp, B + o_op, B + o_ar, (const int32_t*)(B + o_cr), ok ? B + o_ok : nullptr,
                      t ? (const double*)(B + o_t) : nullptr, sig64 ? B + o_sig : nullptr, c->stream, (int32_t*)(B + o_out), n_stored));
     return stage_down(c, st, B);
@@ -4249,11 +4372,11 @@ int sw_ingest_payload(sw_ctx* c, int64_t K, const uint8_t* id32, const uint8_t* 
 
 int sw_get_payload_stats(sw_ctx* c, int64_t* calls, int64_t* waves, int64_t* accepted, int64_t* table_rebuilds, double* phase_ms) {
     if (!c) return SW_EINVAL;
-    if (calls) *calls = c->pl_calls;
-    if (waves) *waves = c->pl_waves;
-    if (accepted) *accepted = c->pl_accepted;
-    if (table_rebuilds) *table_rebuilds = c->pl_rebuilds;
-    if (phase_ms) for (int i = 0; i < 4; ++i) phase_ms[i] = c->pl_ms[i];
+    if (calls) *calls = c->ids.pl_calls;
+    if (waves) *waves = c->ids.pl_waves;
+    if (accepted) *accepted = c->ids.pl_accepted;
+    if (table_rebuilds) *table_rebuilds = c->ids.pl_rebuilds;
+    if (phase_ms) for (int i = 0; i < 4; ++i) phase_ms[i] = c->ids.pl_ms[i];
     return SW_OK;
 }
 
@@ -4600,8 +4723,8 @@ int sw_get_witness_order(sw_ctx* c, int r, int32_t* members, int* n_out) {
     if (c->exact) {
         int32_t cnt = 0;
         std::vector<int32_t> row(np);
-        HIPCHK(c, hipMemcpyAsync(&cnt, c->x_wcnt.p + r, sizeof cnt, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(c, hipMemcpyAsync(row.data(), c->x_worder.p + (size_t)r * np, np * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(&cnt, c->ex.wcnt.p + r, sizeof cnt, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(row.data(), c->ex.worder.p + (size_t)r * np, np * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
         for (int i = 0; i < cnt; ++i) members[i] = row[i];
         *n_out = cnt;
@@ -4618,15 +4741,22 @@ int sw_get_witness_order(sw_ctx* c, int r, int32_t* members, int* n_out) {
     return SW_OK;
 }
 
+// What a rewind and a reset do to a subsystem's state is written ONCE, in the rewind() / reset() of its state struct
+// (sw_ctx); a struct without them is left alone by both calls.  Here: the list of those calls, the core's own tables,
+// and the device work at its place in stream order.
 int sw_rewind(sw_ctx* c) {
     if (!c) return SW_EINVAL;
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream_cs));   // (calls return without a host synchronisation)
     HIPCHK(c, hipStreamSynchronize(c->stream_aux));
     const size_t rows = (size_t)c->Rcap * c->npad;
+    c->hist.rewind();
+    c->votes.rewind();
+    c->ing.rewind();
+    c->ids.rewind();
+    c->data.rewind();
+    c->walk.rewind();
     c->fame_calls.clear();
-    c->hist.table_calls = c->hist.table_divided = -1;
-    c->votes.sched_calls = -1;
     c->votes_partial = false;
     c->eval_src = 0;
     std::fill(c->cons_call.begin(), c->cons_call.end(), -1);
@@ -4687,7 +4817,7 @@ int sw_rewind(sw_ctx* c) {
     c->sw_dirty_from = 1;
     c->dbg_iter_base = c->ctr.round_iterations;   // (the phase stamps of the loop kernels count from the rewind)
     c->transactions.clear();
-    c->tx_len = 0;   // (d_rr / d_cts need nothing: no event is inside an ordered prefix any more)
+    c->cons.rewind();   // (with the host's order, behind the device work: an early return above leaves both as they were)
     std::fill(c->ord_pos.begin(), c->ord_pos.end(), 0);
     if (c->exact) CHK(exact_rewind(c));
     return SW_OK;
@@ -4711,31 +4841,17 @@ int sw_reset(sw_ctx* c) {
     c->pool_h_valid = true;
     if (c->stream_io) HIPCHK(c, hipStreamSynchronize(c->stream_io));  // a payload upload may still be writing t / sig
     c->payload_pending = false;
-    c->ht_pending = false;   // (the heights kernel of a device append ran there too)
-    c->ht_dev_upto = 0;
-    c->n_ids = 0;   // the ids go with the events (the table keeps its size and is emptied)
-    c->n_data = 0;  // ... and so does their data (the arena keeps its size)
-    c->data_used = 0;
-    c->wk_trunk_N = -1;   // (the trunk heights were those of the forgotten events)
-    if (c->idtab_log) HIPCHK(c, hipMemsetAsync(c->d_idtab.p, 0xff, sizeof(int32_t) << c->idtab_log, c->stream));
+    c->hist.reset();
+    c->votes.reset();
+    c->cons.reset();
+    c->ing.reset();    // (the heights kernel of a device append ran on stream_io too)
+    c->ids.reset();    // ... and its table is emptied here, on the stream
+    c->data.reset();
+    c->walk.reset();
+    if (c->ids.idtab_log) HIPCHK(c, hipMemsetAsync(c->ids.d_idtab.p, 0xff, sizeof(int32_t) << c->ids.idtab_log, c->stream));
     c->exact = false;  // (a fresh hashgraph starts on the fast path again)
     c->chunks_off = false;  // ... and with the chunked sweep
     return SW_OK;
-}
-
-static void split_dissolve(SplitGroup* g) {
-    if (!g) return;
-    for (int q = 0; q < g->parts; ++q)
-        if (g->ctx[q]) {
-            sw_ctx* c = g->ctx[q];
-            (void)hipStreamSynchronize(c->stream);
-            if (c->split == g) { c->tally_impl = c->split_saved[0]; c->tally_auto = c->split_saved[1] != 0; c->K = c->split_saved[2]; c->K_auto = c->split_saved[3] != 0; }   // (what the link pinned)
-            c->split = nullptr;
-        }
-    for (int w = 0; w < 2; ++w)
-        for (int q = 0; q < SW_MAX_PARTS; ++q)
-            for (auto e : g->ev[w][q]) if (e) (void)hipEventDestroy(e);
-    delete g;
 }
 
 int sw_split_link(sw_ctx* const* ctxs, int parts) {
@@ -4876,7 +4992,7 @@ int sw_get_famous_events(sw_ctx* c, int64_t first, int64_t K, int8_t* out) {
     if (!K) return SW_OK;
     HIPCHK(c, hipSetDevice(c->device));
     if (c->exact) {
-        HIPCHK(c, hipMemcpyAsync(out, c->x_fam_ev.p + first, (size_t)K, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(c, hipMemcpyAsync(out, c->ex.fam_ev.p + first, (size_t)K, hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
         return SW_OK;
     }
@@ -5230,74 +5346,6 @@ int sw_get_votes_stats(sw_ctx* c, int64_t* calls, int64_t* rows, int64_t* entrie
 }  // extern "C"
 namespace {
 
-xh::Store history_store(sw_ctx* c) {
-    auto& h = c->hist;
-    xh::Store s{};
-    s.voter = h.d_voter.p; s.cand = h.d_cand.p; s.value = h.d_value.p; s.tab = h.d_tab.p;
-    s.cap = h.cap; s.tmask = (unsigned)(h.slots - 1);
-    return s;
-}
-
-void history_votes_lost(sw_ctx* c, const char* why) {
-    c->hist.votes_ok = false;
-    c->hist.why = why;
-}
-
-// Room for `need` entries in all — at most the ceiling: what does not fit makes the kernel set the overflow word.  The log
-// keeps its entries (dgrow copies them), the index is emptied and rebuilt by k_votes_reindex, one thread per entry.
-int history_store_reserve(sw_ctx* c, int64_t need) {
-    auto& h = c->hist;
-    need = std::min(need, h.ceiling);
-    if (need <= h.cap && h.slots) return SW_OK;
-    int64_t nc = std::max<int64_t>(h.cap0, 1);
-    while (nc < need) nc *= 2;
-    nc = std::min(std::max(nc, h.cap), h.ceiling);
-    size_t slots = 2;
-    while (slots < 2 * (size_t)nc) slots *= 2;
-    const size_t keep = (size_t)h.count;
-    CHK(dgrow(c, h.d_voter, (size_t)nc, keep));
-    CHK(dgrow(c, h.d_cand, (size_t)nc, keep));
-    CHK(dgrow(c, h.d_value, (size_t)nc, keep));
-    CHK(dgrow(c, h.d_tab, slots, 0));
-    h.cap = nc;
-    h.slots = slots;
-    HIPCHK(c, hipMemsetAsync(h.d_tab.p, 0xff, slots * sizeof(int32_t), c->stream));
-    if (h.count) {
-        hipLaunchKernelGGL(xh::k_votes_reindex, dim3((unsigned)((h.count + xh::THREADS - 1) / xh::THREADS)), dim3(xh::THREADS), 0, c->stream, history_store(c), (long long)h.count);
-        c->ctr.kernel_launches++;
-        HIPCHK(c, hipGetLastError());
-    }
-    h.grows++;
-    return SW_OK;
-}
-
-int history_defaults(sw_ctx* c, int64_t first, int64_t K) {
-    if (!K) return SW_OK;
-    hipLaunchKernelGGL(xh::k_history_defaults, dim3((unsigned)((K + xh::THREADS - 1) / xh::THREADS)), dim3(xh::THREADS), 0, c->stream, (long long)first, (long long)K,
-                       c->d_rr.p, (xh::u64*)c->d_cts.p);
-    c->ctr.kernel_launches++;
-    HIPCHK(c, hipGetLastError());
-    return SW_OK;
-}
-
-// Behind a successful exact_order: the two values of its `produced` items into the per-event tables, the items behind the
-// device copy of the order.  (A call that failed returned before this and records nothing.)
-int history_record(sw_ctx* c, int64_t produced) {
-    if (!produced) return SW_OK;
-    const size_t at = (size_t)c->tx_len;
-    CHK(consensus_reserve(c, at + (size_t)produced));
-    hipLaunchKernelGGL(xh::k_history_record, dim3((unsigned)((produced + xh::THREADS - 1) / xh::THREADS)), dim3(xh::THREADS), 0, c->stream, (long long)produced,
-                       (const int*)c->x_items_ev.p, (const xh::u64*)c->x_items_ts.p, (const int*)c->hist.d_items_rr.p, c->d_rr.p, (xh::u64*)c->d_cts.p);
-    c->ctr.kernel_launches++;
-    HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(c->d_tx.p + at, c->x_items_ev.p, (size_t)produced * sizeof(int32_t), hipMemcpyDeviceToDevice, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));   // (the next call may overwrite the items)
-    c->tx_len = (int64_t)at + produced;
-    c->cs_record_calls++;
-    c->cs_recorded += produced;
-    return SW_OK;
-}
-
 // The votes of the fast path — the table of sw_export_votes_device over every voter round decide_fame has seen — as entries
 // at the head of the (emptied) store, indexed.  The table's preconditions are the caller's business (votes_pre).
 int history_table_import(sw_ctx* c, int seen) {
@@ -5337,12 +5385,12 @@ int history_table_import(sw_ctx* c, int seen) {
 // current — nothing divided since the last decide_fame call, no partitioned commit; unavailable otherwise.
 int history_enter(sw_ctx* c) {
     auto& h = c->hist;
-    CHK(consensus_reserve(c, (size_t)c->tx_len));
-    CHK(dgrow(c, c->d_cs_ordpos, c->npad, 0));
+    CHK(consensus_reserve(c, (size_t)c->cons.tx_len));
+    CHK(dgrow(c, c->cons.d_ordpos, c->npad, 0));
     if (c->N) {
-        HIPCHK(c, hipMemcpyAsync(c->d_cs_ordpos.p, c->ord_pos.data(), (size_t)c->n * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+        HIPCHK(c, hipMemcpyAsync(c->cons.d_ordpos.p, c->ord_pos.data(), (size_t)c->n * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
         hipLaunchKernelGGL(xh::k_history_normalise, dim3((unsigned)((c->N + xh::THREADS - 1) / xh::THREADS)), dim3(xh::THREADS), 0, c->stream, (long long)c->N,
-                           (const int*)c->d_seq.p, (const int*)c->d_cr.p, (const int*)c->d_cs_ordpos.p, c->d_rr.p, (xh::u64*)c->d_cts.p);
+                           (const int*)c->d_seq.p, (const int*)c->d_cr.p, (const int*)c->cons.d_ordpos.p, c->cons.d_rr.p, (xh::u64*)c->cons.d_cts.p);
         c->ctr.kernel_launches++;
         HIPCHK(c, hipGetLastError());
         HIPCHK(c, hipStreamSynchronize(c->stream));   // (ord_pos is pageable memory)
@@ -5558,19 +5606,12 @@ namespace {
 
 struct ExportArrays { uint8_t *id, *sp_id, *op_id, *arity; int32_t* creator; double* t; uint8_t* sig; int32_t* event; };
 
-// the parts every sw_sync_pull* shares (defined behind the data store's functions, which the last of them needs)
-int pull_pre(sw_ctx* dst, int64_t dst_head, sw_ctx* src, bool validate, bool data, const char* what);
-int pull_begin(sw_ctx* dst, int64_t dst_head, sw_ctx* src, bool validate, bool data, const char* what);
-int pull_ranges(sw_ctx* dst, sw_ctx* src, int64_t src_head, bool with_event, const char* what, int64_t* total, ExportArrays* d);
-int pull_finish(sw_ctx* dst, sw_ctx* src, int64_t total, const ExportArrays& d, bool validate, bool data, const char* what, int64_t* n_valid,
-                int64_t* n_stored);
-
 // what both forms and sw_sync_pull ask of the answering context
 int export_pre(sw_ctx* c, int64_t head, const char* what) {
     if (c->poisoned) return fail(c, SW_EIO, "context unusable after an earlier device failure");
     if (c->exact) return fail(c, SW_ENOTSUP, "%s is not available on the exact (forked-hashgraph) path", what);
-    if (c->n_ids != c->N)
-        return fail(c, SW_ENOTSUP, "%s: %lld of the %lld stored events have no id (sw_set_event_ids first)", what, (long long)(c->N - c->n_ids), (long long)c->N);
+    if (c->ids.n_ids != c->N)
+        return fail(c, SW_ENOTSUP, "%s: %lld of the %lld stored events have no id (sw_set_event_ids first)", what, (long long)(c->N - c->ids.n_ids), (long long)c->N);
     if (head < c->first_resident || head >= c->divided) return fail(c, SW_ERANGE, "%s: head %lld is not a divided, resident event", what, (long long)head);
     return SW_OK;
 }
@@ -5581,7 +5622,7 @@ int export_pre(sw_ctx* c, int64_t head, const char* what) {
 // (ht_dev_upto), and only a bulk HOST append leaves heights to ensure_dag_h's loop — the test append_device_body makes.
 int heights_on_device(sw_ctx* c) {
     CHK(heights_ready(c));
-    if ((int64_t)c->sp.size() < c->N && c->ht_dev_upto < c->N) CHK(ensure_dag_h(c));
+    if ((int64_t)c->sp.size() < c->N && c->ing.ht_dev_upto < c->N) CHK(ensure_dag_h(c));
     return SW_OK;
 }
 
@@ -5591,7 +5632,7 @@ int export_ranges(sw_ctx* c, int64_t head, const int32_t* known, hipMemcpyKind k
     CHK(heights_on_device(c));
     const int np = c->npad, n = c->n;
     CHK(dgrow(c, c->d_q, (size_t)3 * np, 0));
-    CHK(dgrow(c, c->d_xp, (size_t)2 * np + 8, 0));
+    CHK(dgrow(c, c->xp.d, (size_t)2 * np + 8, 0));
     if (c->payload_pending) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_payload, 0));   // timestamps / signatures of a bulk host append
     HIPCHK(c, hipMemsetAsync(c->d_q.p, 0xff, (size_t)np * sizeof(int32_t), c->stream));
     if (known) HIPCHK(c, hipMemcpyAsync(c->d_q.p, known, (size_t)n * sizeof(int32_t), kind, c->stream));
@@ -5599,11 +5640,11 @@ int export_ranges(sw_ctx* c, int64_t head, const int32_t* known, hipMemcpyKind k
                        (const int*)c->d_cr.p, (const int*)c->d_chain_start.p, (const int*)c->d_chain_ev.p, (const int*)c->d_q.p,
                        (int)head, np, c->d_q.p + np, c->d_q.p + 2 * np);
     hipLaunchKernelGGL(gsp::k_export_offsets, dim3(1), dim3(gsp::SCAN_THREADS), 0, c->stream, (const int*)(c->d_q.p + np), (const int*)(c->d_q.p + 2 * np),
-                       (const int*)c->d_chain_start.p, n, c->d_xp.p + 2, c->d_xp.p + 2 + np + 1, (long long*)c->d_xp.p);
+                       (const int*)c->d_chain_start.p, n, c->xp.d.p + 2, c->xp.d.p + 2 + np + 1, (long long*)c->xp.d.p);
     c->ctr.kernel_launches += 2;
     HIPCHK(c, hipGetLastError());
     long long tot = 0;
-    HIPCHK(c, hipMemcpyAsync(&tot, c->d_xp.p, sizeof tot, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(&tot, c->xp.d.p, sizeof tot, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (tot < 1 || tot > c->N) return fail(c, SW_EIO, "export: the ranges hold %lld events of %lld (internal error)", tot, (long long)c->N);
     *total = tot;
@@ -5613,9 +5654,9 @@ int export_ranges(sw_ctx* c, int64_t head, const int32_t* known, hipMemcpyKind k
 // the gather of `total` slots behind export_ranges, on the context's stream (asynchronous)
 int export_gather(sw_ctx* c, int64_t total, const ExportArrays& o) {
     const int np = c->npad;
-    gsp::ExportIn in{c->d_xp.p + 2, c->d_xp.p + 2 + np + 1, c->d_chain_ev.p, c->d_sp.p, c->d_op.p, c->d_id.p, c->d_sig.p, (const unsigned long long*)c->d_t.p};
+    gsp::ExportIn in{c->xp.d.p + 2, c->xp.d.p + 2 + np + 1, c->d_chain_ev.p, c->d_sp.p, c->d_op.p, c->ids.d_id.p, c->d_sig.p, (const unsigned long long*)c->d_t.p};
     gsp::ExportOut out{o.id, o.sp_id, o.op_id, o.arity, o.creator, (unsigned long long*)o.t, o.sig, o.event};
-    const int G = c->export_lanes;
+    const int G = c->xp.lanes;
     const size_t lds = (size_t)(2 * c->n + 1) * sizeof(int);   // off[n + 1] | base[n]
     const dim3 grid((unsigned)std::min<int64_t>(2048, (total * G + gsp::GATHER_THREADS - 1) / gsp::GATHER_THREADS)), block(gsp::GATHER_THREADS);
     if (G == 4) hipLaunchKernelGGL(gsp::k_export_gather<4>, grid, block, lds, c->stream, in, out, c->n, (int)total);
@@ -5626,7 +5667,7 @@ int export_gather(sw_ctx* c, int64_t total, const ExportArrays& o) {
     return SW_OK;
 }
 
-// the exported arrays for `total` events inside d_xp_out; with `st` and `host` (the host-array forms) stage_down(st, d_xp_out)
+// the exported arrays for `total` events inside xp.d_out; with `st` and `host` (the host-array forms) stage_down(st, xp.d_out)
 // brings them to the caller's arrays
 int export_scratch(sw_ctx* c, int64_t total, bool with_t, bool with_sig, bool with_event, ExportArrays* o, Stage* st = nullptr, const ExportArrays& host = {}) {
     const size_t k = (size_t)total;
@@ -5635,7 +5676,7 @@ int export_scratch(sw_ctx* c, int64_t total, bool with_t, bool with_sig, bool wi
     const size_t o_id = s.out(host.id, k * 32), o_sp = s.out(host.sp_id, k * 32), o_op = s.out(host.op_id, k * 32), o_ar = s.out(host.arity, k), o_cr = s.out(host.creator, k * 4);
     const size_t o_t = s.out(host.t, with_t ? k * 8 : 0), o_sig = s.out(host.sig, with_sig ? k * 64 : 0), o_ev = s.out(host.event, with_event ? k * 4 : 0);
     unsigned char* B = nullptr;
-    CHK(stage_up(c, c->d_xp_out, s, &B));
+    CHK(stage_up(c, c->xp.d_out, s, &B));
     *o = ExportArrays{B + o_id, B + o_sp, B + o_op, B + o_ar, (int32_t*)(B + o_cr), with_t ? (double*)(B + o_t) : nullptr,
                       with_sig ? B + o_sig : nullptr, with_event ? (int32_t*)(B + o_ev) : nullptr};
     return SW_OK;
@@ -5683,15 +5724,15 @@ int sw_export_payload_device(sw_ctx* c, int64_t head_event, const int32_t* d_kno
     int64_t total = 0;
     CHK(export_ranges(c, head_event, d_known_height, hipMemcpyDeviceToDevice, &total));
     *n_out = total;
-    c->xp_ms[0] = prof ? ms_since(t0) : 0;
-    c->xp_ms[1] = 0;
+    c->xp.ms[0] = prof ? ms_since(t0) : 0;
+    c->xp.ms[1] = 0;
     if (total > cap) return fail(c, SW_ERANGE, "sw_export_payload_device: %lld events to export, capacity %lld (nothing written)", (long long)total, (long long)cap);
     t0 = std::chrono::steady_clock::now();
     CHK(export_gather(c, total, ExportArrays{d_id32, d_sp_id32, d_op_id32, d_arity, d_creator, d_t, d_sig64, d_event}));
     CHK(bracket.leave());
-    if (prof) { HIPCHK(c, hipStreamSynchronize(c->stream)); c->xp_ms[1] = ms_since(t0); }
-    c->xp_calls++;
-    c->xp_events += total;
+    if (prof) { HIPCHK(c, hipStreamSynchronize(c->stream)); c->xp.ms[1] = ms_since(t0); }
+    c->xp.calls++;
+    c->xp.events += total;
     return SW_OK;
 }
 
@@ -5709,44 +5750,26 @@ int sw_export_payload(sw_ctx* c, int64_t head_event, const int32_t* known_height
     int64_t total = 0;
     CHK(export_ranges(c, head_event, known_height, hipMemcpyHostToDevice, &total));
     *n_out = total;
-    c->xp_ms[0] = prof ? ms_since(t0) : 0;
-    c->xp_ms[1] = 0;
+    c->xp.ms[0] = prof ? ms_since(t0) : 0;
+    c->xp.ms[1] = 0;
     if (total > cap) return fail(c, SW_ERANGE, "sw_export_payload: %lld events to export, capacity %lld (nothing written)", (long long)total, (long long)cap);
     t0 = std::chrono::steady_clock::now();
     ExportArrays d{};
     Stage st;
     CHK(export_scratch(c, total, t != nullptr, sig64 != nullptr, event != nullptr, &d, &st, ExportArrays{id32, sp_id32, op_id32, arity, creator, t, sig64, event}));
     CHK(export_gather(c, total, d));
-    CHK(stage_down(c, st, c->d_xp_out.p));
-    if (prof) c->xp_ms[1] = ms_since(t0);
-    c->xp_calls++;
-    c->xp_events += total;
+    CHK(stage_down(c, st, c->xp.d_out.p));
+    if (prof) c->xp.ms[1] = ms_since(t0);
+    c->xp.calls++;
+    c->xp.events += total;
     return SW_OK;
-}
-
-int sw_sync_pull(sw_ctx* dst, int64_t dst_head, sw_ctx* src, int64_t src_head, int64_t* n_sent, int64_t* n_stored) {
-    if (!dst || !src) return SW_EINVAL;
-    if (n_sent) *n_sent = 0;
-    if (n_stored) *n_stored = 0;
-    const char* what = "sw_sync_pull";
-    CHK(pull_pre(dst, dst_head, src, false, false, what));
-    if (const int rc = export_pre(src, src_head, "sw_sync_pull (peer)"); rc != SW_OK) { dst->err = src->err; return rc; }
-    // ---- 1. what dst knows at its head (swirld.py:125-126), left in its own scratch; src's stream waits for it
-    CHK(pull_begin(dst, dst_head, src, false, false, what));
-    // ---- 2. src: ranges, count (its one synchronisation: dst's heights have been consumed by then), gather into its own scratch
-    int64_t total = 0;
-    ExportArrays d{};
-    CHK(pull_ranges(dst, src, src_head, false, what, &total, &d));
-    if (n_sent) *n_sent = total;
-    // ---- 3. dst ingests (Node.sync's loop, swirld.py:130-136), its stream ordered behind src's
-    return pull_finish(dst, src, total, d, false, false, what, nullptr, n_stored);
 }
 
 int sw_get_export_stats(sw_ctx* c, int64_t* calls, int64_t* events, double* phase_ms) {
     if (!c) return SW_EINVAL;
-    if (calls) *calls = c->xp_calls;
-    if (events) *events = c->xp_events;
-    if (phase_ms) for (int i = 0; i < 2; ++i) phase_ms[i] = c->xp_ms[i];
+    if (calls) *calls = c->xp.calls;
+    if (events) *events = c->xp.events;
+    if (phase_ms) for (int i = 0; i < 2; ++i) phase_ms[i] = c->xp.ms[i];
     return SW_OK;
 }
 
@@ -5782,8 +5805,8 @@ int consensus_events(sw_ctx* c, const char* what, int64_t first, int64_t K, int3
     HIPCHK(c, hipSetDevice(c->device));
     if (c->exact) {
         // (history on) the tables hold -1 / the quiet NaN for every event that is not ordered: they are copied as they are
-        if (rr_out) HIPCHK(c, hipMemcpyAsync(rr_out, c->d_rr.p + first, (size_t)K * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
-        if (cts_out) HIPCHK(c, hipMemcpyAsync(cts_out, c->d_cts.p + first, (size_t)K * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+        if (rr_out) HIPCHK(c, hipMemcpyAsync(rr_out, c->cons.d_rr.p + first, (size_t)K * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+        if (cts_out) HIPCHK(c, hipMemcpyAsync(cts_out, c->cons.d_cts.p + first, (size_t)K * sizeof(double), hipMemcpyDeviceToHost, c->stream));
         HIPCHK(c, hipStreamSynchronize(c->stream));
         return SW_OK;
     }
@@ -5791,15 +5814,15 @@ int consensus_events(sw_ctx* c, const char* what, int64_t first, int64_t K, int3
     Stage st;
     const size_t o_rr = st.out_opt(rr_out, (size_t)K * 4), o_cts = st.out_opt(cts_out, (size_t)K * 8);
     unsigned char* B = nullptr;
-    CHK(stage_up(c, c->d_cs_out, st, &B));
-    CHK(dgrow(c, c->d_cs_ordpos, np, 0));
+    CHK(stage_up(c, c->cons.d_out, st, &B));
+    CHK(dgrow(c, c->cons.d_ordpos, np, 0));
     // (a pageable source: staged before the call returns; every entry below n is written, the kernel reads no other)
-    HIPCHK(c, hipMemcpyAsync(c->d_cs_ordpos.p, c->ord_pos.data(), (size_t)c->n * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->cons.d_ordpos.p, c->ord_pos.data(), (size_t)c->n * sizeof(int32_t), hipMemcpyHostToDevice, c->stream));
     int32_t* d_rr_out = rr_out ? (int32_t*)(B + o_rr) : nullptr;
     unsigned long long* d_cts_out = cts_out ? (unsigned long long*)(B + o_cts) : nullptr;
     const unsigned grid = (unsigned)std::min<int64_t>(4096, (K + cns::THREADS - 1) / cns::THREADS);
     hipLaunchKernelGGL(cns::k_consensus_events, dim3(grid), dim3(cns::THREADS), 0, c->stream, (long long)first, (long long)K, (const int*)c->d_seq.p,
-                       (const int*)c->d_cr.p, (const int*)c->d_cs_ordpos.p, (const int*)c->d_rr.p, (const unsigned long long*)c->d_cts.p, d_rr_out, d_cts_out);
+                       (const int*)c->d_cr.p, (const int*)c->cons.d_ordpos.p, (const int*)c->cons.d_rr.p, (const unsigned long long*)c->cons.d_cts.p, d_rr_out, d_cts_out);
     c->ctr.kernel_launches++;
     HIPCHK(c, hipGetLastError());
     return stage_down(c, st, B);
@@ -5810,24 +5833,24 @@ struct OrderedArrays { int32_t* event; uint8_t* id; int32_t* creator; int32_t* r
 // what both export forms check before anything is enqueued
 int ordered_pre(sw_ctx* c, const char* what, int64_t first, int64_t K, bool want_ids) {
     CHK(consensus_pre(c, what));
-    if (first < 0 || K < 0 || first + K > c->tx_len)
-        return fail(c, SW_ERANGE, "%s: positions [%lld, %lld) outside the %lld ordered events (nothing written)", what, (long long)first, (long long)(first + K), (long long)c->tx_len);
-    if (want_ids && c->n_ids != c->N)
-        return fail(c, SW_ENOTSUP, "%s: %lld of the %lld stored events have no id (sw_set_event_ids first, or pass no id array)", what, (long long)(c->N - c->n_ids), (long long)c->N);
+    if (first < 0 || K < 0 || first + K > c->cons.tx_len)
+        return fail(c, SW_ERANGE, "%s: positions [%lld, %lld) outside the %lld ordered events (nothing written)", what, (long long)first, (long long)(first + K), (long long)c->cons.tx_len);
+    if (want_ids && c->ids.n_ids != c->N)
+        return fail(c, SW_ENOTSUP, "%s: %lld of the %lld stored events have no id (sw_set_event_ids first, or pass no id array)", what, (long long)(c->N - c->ids.n_ids), (long long)c->N);
     return SW_OK;
 }
 
 // the gather of K > 0 positions on the context's stream (asynchronous)
 int ordered_gather(sw_ctx* c, int64_t first, int64_t K, const OrderedArrays& o) {
-    cns::OrderedIn in{c->d_tx.p, c->d_id.p, c->d_cr.p, c->d_rr.p, (const unsigned long long*)c->d_cts.p};
+    cns::OrderedIn in{c->cons.d_tx.p, c->ids.d_id.p, c->d_cr.p, c->cons.d_rr.p, (const unsigned long long*)c->cons.d_cts.p};
     cns::OrderedOut out{o.event, o.id, o.creator, o.rr, (unsigned long long*)o.t};
     constexpr int G = cns::GATHER_LANES;
     const dim3 grid((unsigned)std::min<int64_t>(2048, (K * G + cns::THREADS - 1) / cns::THREADS)), block(cns::THREADS);
     hipLaunchKernelGGL(cns::k_ordered_gather<G>, grid, block, 0, c->stream, in, out, (long long)first, (long long)K);
     c->ctr.kernel_launches++;
     HIPCHK(c, hipGetLastError());
-    c->cs_export_calls++;
-    c->cs_exported += K;
+    c->cons.export_calls++;
+    c->cons.exported += K;
     return SW_OK;
 }
 
@@ -5868,7 +5891,7 @@ int sw_export_ordered(sw_ctx* c, int64_t first, int64_t K, int32_t* event, uint8
     const size_t o_ev = st.out_opt(event, k * 4), o_id = st.out_opt(id32, k * 32), o_cr = st.out_opt(creator, k * 4),
                  o_rr = st.out_opt(round_received, k * 4), o_t = st.out_opt(time, k * 8);
     unsigned char* B = nullptr;
-    CHK(stage_up(c, c->d_cs_out, st, &B));
+    CHK(stage_up(c, c->cons.d_out, st, &B));
     const OrderedArrays d{event ? (int32_t*)(B + o_ev) : nullptr, id32 ? B + o_id : nullptr, creator ? (int32_t*)(B + o_cr) : nullptr,
                           round_received ? (int32_t*)(B + o_rr) : nullptr, time ? (double*)(B + o_t) : nullptr};
     CHK(ordered_gather(c, first, K, d));
@@ -5877,10 +5900,10 @@ int sw_export_ordered(sw_ctx* c, int64_t first, int64_t K, int32_t* event, uint8
 
 int sw_get_consensus_stats(sw_ctx* c, int64_t* record_calls, int64_t* recorded_events, int64_t* export_calls, int64_t* exported_events) {
     if (!c) return SW_EINVAL;
-    if (record_calls) *record_calls = c->cs_record_calls;
-    if (recorded_events) *recorded_events = c->cs_recorded;
-    if (export_calls) *export_calls = c->cs_export_calls;
-    if (exported_events) *exported_events = c->cs_exported;
+    if (record_calls) *record_calls = c->cons.record_calls;
+    if (recorded_events) *recorded_events = c->cons.recorded;
+    if (export_calls) *export_calls = c->cons.export_calls;
+    if (exported_events) *exported_events = c->cons.exported;
     return SW_OK;
 }
 
@@ -5963,8 +5986,8 @@ namespace {
 int validate_launch(sw_ctx* c, int64_t K, const swv::Payload& p, uint8_t* d_ok) {
     const int n = c->n;
     const unsigned blocks = (unsigned)((K + 63) / 64);
-    hipLaunchKernelGGL(swv::k_validate_payload, dim3(blocks), dim3(64), 0, c->stream, p, (long long)K, n, (const uint8_t*)c->d_vkeys.p,
-                       (const uint8_t*)c->d_vkeys.p + (size_t)n * 32, (const swv::niels*)c->d_vtab.p, d_ok);
+    hipLaunchKernelGGL(swv::k_validate_payload, dim3(blocks), dim3(64), 0, c->stream, p, (long long)K, n, (const uint8_t*)c->val.d_keys.p,
+                       (const uint8_t*)c->val.d_keys.p + (size_t)n * 32, (const swv::niels*)c->val.d_tab.p, d_ok);
     c->ctr.kernel_launches++;
     HIPCHK(c, hipGetLastError());
     return SW_OK;
@@ -5972,9 +5995,9 @@ int validate_launch(sw_ctx* c, int64_t K, const swv::Payload& p, uint8_t* d_ok) 
 
 // the signing keys of the context, overwritten with zeros (sw_clear_signing_keys, sw_set_member_keys, sw_destroy)
 int sign_keys_clear(sw_ctx* c) {
-    c->sg_has.clear();
-    if (!c->d_sg_keys.p) return SW_OK;
-    HIPCHK(c, hipMemsetAsync(c->d_sg_keys.p, 0, c->d_sg_keys.cap, c->stream));   // (behind whatever still signs on this stream)
+    c->sign.has.clear();
+    if (!c->sign.d_keys.p) return SW_OK;
+    HIPCHK(c, hipMemsetAsync(c->sign.d_keys.p, 0, c->sign.d_keys.cap, c->stream));   // (behind whatever still signs on this stream)
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return SW_OK;
 }
@@ -5982,7 +6005,7 @@ int sign_keys_clear(sw_ctx* c) {
 int validate_pre(sw_ctx* c, int64_t K, const void* msgs, const void* msg_off, int64_t msg_bytes, const void* whole, const void* whole_off,
                  int64_t whole_bytes, const void* sig, const void* creator, const void* id, const void* ok, const char* what) {
     if (c->poisoned) return fail(c, SW_EIO, "context unusable after an earlier device failure");
-    if (c->vkeys.empty()) return fail(c, SW_ENOTSUP, "%s: no member keys (sw_set_member_keys first)", what);
+    if (c->val.keys.empty()) return fail(c, SW_ENOTSUP, "%s: no member keys (sw_set_member_keys first)", what);
     if (K < 0 || msg_bytes < 0 || whole_bytes < 0) return fail(c, SW_EINVAL, "%s: negative count or length", what);
     if (K > 0x7fffffff) return fail(c, SW_ERANGE, "%s: more than 2^31 events", what);
     if (K > 0 && (!msg_off || !sig || !creator || !ok || (msg_bytes > 0 && !msgs))) return fail(c, SW_EINVAL, "%s: NULL arrays", what);
@@ -6005,32 +6028,32 @@ int sw_set_member_keys(sw_ctx* c, const uint8_t* pk32, int32_t* n_unusable) {
     const size_t n = (size_t)c->n;
     const auto t0 = std::chrono::steady_clock::now();
     CHK(sign_keys_clear(c));   // signing keys belong to the member keys they were checked against
-    CHK(dgrow(c, c->d_vkeys, n * 33, 0));
-    CHK(dgrow(c, c->d_vtab, (n + 1) * swv::ROW * sizeof(swv::niels), 0));
+    CHK(dgrow(c, c->val.d_keys, n * 33, 0));
+    CHK(dgrow(c, c->val.d_tab, (n + 1) * swv::ROW * sizeof(swv::niels), 0));
     // (an earlier validation may still be reading the old table on this stream: the build is ordered behind it)
     std::vector<uint8_t> keys(pk32, pk32 + n * 32), usable(n);
-    HIPCHK(c, hipMemcpyAsync(c->d_vkeys.p, keys.data(), n * 32, hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(swv::k_validate_table, dim3((unsigned)n + 1), dim3(swv::POSITIONS), 0, c->stream, (const uint8_t*)c->d_vkeys.p, (int)n,
-                       (swv::niels*)c->d_vtab.p, (uint8_t*)c->d_vkeys.p + n * 32);
+    HIPCHK(c, hipMemcpyAsync(c->val.d_keys.p, keys.data(), n * 32, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(swv::k_validate_table, dim3((unsigned)n + 1), dim3(swv::POSITIONS), 0, c->stream, (const uint8_t*)c->val.d_keys.p, (int)n,
+                       (swv::niels*)c->val.d_tab.p, (uint8_t*)c->val.d_keys.p + n * 32);
     c->ctr.kernel_launches++;
     HIPCHK(c, hipGetLastError());
-    HIPCHK(c, hipMemcpyAsync(usable.data(), c->d_vkeys.p + n * 32, n, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(usable.data(), c->val.d_keys.p + n * 32, n, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->vkeys.swap(keys);
-    c->vusable.swap(usable);
-    c->v_builds++;
-    c->v_ms[0] = c->profiling ? ms_since(t0) : 0;
+    c->val.keys.swap(keys);
+    c->val.usable.swap(usable);
+    c->val.builds++;
+    c->val.ms[0] = c->profiling ? ms_since(t0) : 0;
     int32_t bad = 0;
-    for (uint8_t u : c->vusable) bad += !u;
+    for (uint8_t u : c->val.usable) bad += !u;
     if (n_unusable) *n_unusable = bad;
     return SW_OK;
 }
 
 int sw_get_member_keys(sw_ctx* c, uint8_t* pk32_out, uint8_t* usable_out) {
     if (!c) return SW_EINVAL;
-    if (c->vkeys.empty()) return fail(c, SW_ENOTSUP, "sw_get_member_keys: no member keys (sw_set_member_keys first)");
-    if (pk32_out) memcpy(pk32_out, c->vkeys.data(), c->vkeys.size());
-    if (usable_out) memcpy(usable_out, c->vusable.data(), c->vusable.size());
+    if (c->val.keys.empty()) return fail(c, SW_ENOTSUP, "sw_get_member_keys: no member keys (sw_set_member_keys first)");
+    if (pk32_out) memcpy(pk32_out, c->val.keys.data(), c->val.keys.size());
+    if (usable_out) memcpy(usable_out, c->val.usable.data(), c->val.usable.size());
     return SW_OK;
 }
 
@@ -6053,15 +6076,15 @@ int sw_validate_payload_device(sw_ctx* c, int64_t K, const uint8_t* d_msgs, cons
     CHK(bracket.join(c, (hipStream_t)user_stream));
     // (a zero-length buffer may be NULL: the kernel then only forms pointers it never reads through; `whole` non-NULL is
     // what selects the id check there)
-    const uint8_t* anchor = (const uint8_t*)c->d_vkeys.p;
+    const uint8_t* anchor = (const uint8_t*)c->val.d_keys.p;
     const swv::Payload p{d_msgs ? d_msgs : anchor, (const long long*)d_msg_off, (long long)msg_bytes, idchk ? (d_whole ? d_whole : anchor) : nullptr,
                          (const long long*)d_whole_off, (long long)whole_bytes, d_sig64, d_creator, d_id32};
     CHK(validate_launch(c, K, p, d_ok));
     CHK(bracket.leave());   // whatever the caller enqueues next reads a complete d_ok
-    c->v_ms[1] = 0;
-    if (prof) { HIPCHK(c, hipStreamSynchronize(c->stream)); c->v_ms[1] = ms_since(t0); }
-    c->v_calls++;
-    c->v_events += K;
+    c->val.ms[1] = 0;
+    if (prof) { HIPCHK(c, hipStreamSynchronize(c->stream)); c->val.ms[1] = ms_since(t0); }
+    c->val.calls++;
+    c->val.events += K;
     return SW_OK;
 }
 
@@ -6079,28 +6102,28 @@ int sw_validate_payload(sw_ctx* c, int64_t K, const uint8_t* msgs, const int64_t
     const size_t o_moff = st.in(msg_off, (k + 1) * 8), o_m = st.in(msgs, mb), o_woff = st.in(whole_off, (k + 1) * 8), o_w = st.in(whole, wb);
     const size_t o_sig = st.in(sig64, k * 64), o_cr = st.in(creator, k * 4), o_id = st.in(idchk ? id32 : nullptr, k * 32), o_ok = st.out(ok, k);
     unsigned char* B = nullptr;
-    CHK(stage_up(c, c->d_v_in, st, &B));
+    CHK(stage_up(c, c->val.d_in, st, &B));
     const swv::Payload p{B + o_m, (const long long*)(B + o_moff), (long long)msg_bytes, idchk ? B + o_w : nullptr,
                          idchk ? (const long long*)(B + o_woff) : nullptr, (long long)whole_bytes, B + o_sig, (const int32_t*)(B + o_cr),
                          idchk ? B + o_id : nullptr};
     CHK(validate_launch(c, K, p, B + o_ok));
     CHK(stage_down(c, st, B));
-    c->v_ms[1] = prof ? ms_since(t0) : 0;
+    c->val.ms[1] = prof ? ms_since(t0) : 0;
     int64_t acc = 0;
     for (size_t i = 0; i < k; ++i) acc += ok[i] != 0;
-    c->v_calls++;
-    c->v_events += K;
-    c->v_accepted += acc;
+    c->val.calls++;
+    c->val.events += K;
+    c->val.accepted += acc;
     return SW_OK;
 }
 
 int sw_get_validate_stats(sw_ctx* c, int64_t* calls, int64_t* events, int64_t* accepted, int64_t* table_builds, double* phase_ms) {
     if (!c) return SW_EINVAL;
-    if (calls) *calls = c->v_calls;
-    if (events) *events = c->v_events;
-    if (accepted) *accepted = c->v_accepted;
-    if (table_builds) *table_builds = c->v_builds;
-    if (phase_ms) for (int i = 0; i < 2; ++i) phase_ms[i] = c->v_ms[i];
+    if (calls) *calls = c->val.calls;
+    if (events) *events = c->val.events;
+    if (accepted) *accepted = c->val.accepted;
+    if (table_builds) *table_builds = c->val.builds;
+    if (phase_ms) for (int i = 0; i < 2; ++i) phase_ms[i] = c->val.ms[i];
     return SW_OK;
 }
 
@@ -6149,7 +6172,7 @@ bool utf8_name(const char* s) {   // 1 .. 255 bytes of well-formed UTF-8
     return true;
 }
 
-int pack_hdr_len(const sw_ctx* c) { return (int)(c->pk_mod.size() + c->pk_qual.size() + 8); }
+int pack_hdr_len(const sw_ctx* c) { return (int)(c->pack.mod.size() + c->pack.qual.size() + 8); }
 
 void pack_bound(const sw_ctx* c, int64_t K, int64_t data_bytes, int64_t* msg, int64_t* whole) {
     *msg = K * pck::MSG_MAX + data_bytes;
@@ -6158,11 +6181,11 @@ void pack_bound(const sw_ctx* c, int64_t K, int64_t data_bytes, int64_t* msg, in
 
 // the class header of the whole stream in device memory (after sw_create and after sw_set_event_class: one small copy)
 int pack_header(sw_ctx* c) {
-    if (!c->pk_hdr_stale) return SW_OK;
-    CHK(dgrow(c, c->d_pk_hdr, (size_t)pck::HDR_MAX + 248, 0));
-    std::vector<uint8_t>& h = c->pk_hdr;
+    if (!c->pack.hdr_stale) return SW_OK;
+    CHK(dgrow(c, c->pack.d_hdr, (size_t)pck::HDR_MAX + 248, 0));
+    std::vector<uint8_t>& h = c->pack.hdr;
     h.clear();
-    for (const std::string* s : {&c->pk_mod, &c->pk_qual}) {
+    for (const std::string* s : {&c->pack.mod, &c->pack.qual}) {
         h.push_back(0x8c);
         h.push_back((uint8_t)s->size());
         h.insert(h.end(), s->begin(), s->end());
@@ -6170,8 +6193,8 @@ int pack_header(sw_ctx* c) {
     }
     h.push_back(0x93);
     h.push_back(0x94);
-    HIPCHK(c, hipMemcpyAsync(c->d_pk_hdr.p, h.data(), h.size(), hipMemcpyHostToDevice, c->stream));
-    c->pk_hdr_stale = false;
+    HIPCHK(c, hipMemcpyAsync(c->pack.d_hdr.p, h.data(), h.size(), hipMemcpyHostToDevice, c->stream));
+    c->pack.hdr_stale = false;
     return SW_OK;
 }
 
@@ -6182,10 +6205,10 @@ int pack_launch(sw_ctx* c, int64_t K, const PackArrays& a, int64_t bound_msg, in
     auto t0 = std::chrono::steady_clock::now();
     CHK(pack_header(c));
     const int64_t tiles = (K + pck::TILE - 1) / pck::TILE;
-    CHK(dgrow(c, c->d_pk, (size_t)(2 * tiles) * sizeof(int64_t) + 256, 0));
-    pck::i64* tsum = (pck::i64*)c->d_pk.p;
+    CHK(dgrow(c, c->pack.d, (size_t)(2 * tiles) * sizeof(int64_t) + 256, 0));
+    pck::i64* tsum = (pck::i64*)c->pack.d.p;
     const pck::PackIn in{a.sp_id, a.op_id, a.arity, a.creator, (const pck::u64*)a.t, a.sig, a.data, (const pck::i64*)a.data_off,
-                         (pck::i64)a.data_bytes, a.data_none, (const unsigned char*)c->d_vkeys.p, (const unsigned char*)c->d_pk_hdr.p,
+                         (pck::i64)a.data_bytes, a.data_none, (const unsigned char*)c->val.d_keys.p, (const unsigned char*)c->pack.d_hdr.p,
                          pack_hdr_len(c), c->n};
     pck::i64* moff = (pck::i64*)a.msg_off;
     pck::i64* woff = (pck::i64*)a.whole_off;
@@ -6197,7 +6220,7 @@ int pack_launch(sw_ctx* c, int64_t K, const PackArrays& a, int64_t bound_msg, in
                        (const pck::i64*)tsum);
     c->ctr.kernel_launches += 4;
     HIPCHK(c, hipGetLastError());
-    if (prof) { HIPCHK(c, hipStreamSynchronize(c->stream)); c->pk_ms[0] = ms_since(t0); t0 = std::chrono::steady_clock::now(); }
+    if (prof) { HIPCHK(c, hipStreamSynchronize(c->stream)); c->pack.ms[0] = ms_since(t0); t0 = std::chrono::steady_clock::now(); }
     for (int w = 0; w < 2; ++w) {
         const int64_t chunks = ((w ? bound_whole : bound_msg) + 15) / 16;
         const int64_t blocks = std::max<int64_t>(1, std::min<int64_t>(4096, (chunks + pck::WRITE_THREADS - 1) / pck::WRITE_THREADS));
@@ -6209,11 +6232,11 @@ int pack_launch(sw_ctx* c, int64_t K, const PackArrays& a, int64_t bound_msg, in
     }
     c->ctr.kernel_launches += 2;
     HIPCHK(c, hipGetLastError());
-    c->pk_ms[0] = prof ? c->pk_ms[0] : 0;
-    c->pk_ms[1] = 0;
-    if (prof) { HIPCHK(c, hipStreamSynchronize(c->stream)); c->pk_ms[1] = ms_since(t0); }
-    c->pk_calls++;
-    c->pk_events += K;
+    c->pack.ms[0] = prof ? c->pack.ms[0] : 0;
+    c->pack.ms[1] = 0;
+    if (prof) { HIPCHK(c, hipStreamSynchronize(c->stream)); c->pack.ms[1] = ms_since(t0); }
+    c->pack.calls++;
+    c->pack.events += K;
     return SW_OK;
 }
 
@@ -6222,7 +6245,7 @@ int pack_pre(sw_ctx* c, int64_t K, const void* sp, const void* op, const void* a
              const void* data, const void* data_off, int64_t data_bytes, const void* data_none, const void* msgs, const void* msg_off,
              int64_t msg_cap, const void* whole, const void* whole_off, int64_t whole_cap, int64_t* bm, int64_t* bw, const char* what) {
     if (c->poisoned) return fail(c, SW_EIO, "context unusable after an earlier device failure");
-    if (c->vkeys.empty()) return fail(c, SW_ENOTSUP, "%s: no member keys (sw_set_member_keys first)", what);
+    if (c->val.keys.empty()) return fail(c, SW_ENOTSUP, "%s: no member keys (sw_set_member_keys first)", what);
     if (K < 0 || data_bytes < 0 || msg_cap < 0 || whole_cap < 0) return fail(c, SW_EINVAL, "%s: negative count, length or capacity", what);
     if (K > 0x7fffffff) return fail(c, SW_ERANGE, "%s: more than 2^31 events", what);
     if (!msg_off || !whole_off) return fail(c, SW_EINVAL, "%s: NULL offset arrays", what);
@@ -6243,19 +6266,19 @@ extern "C" {
 int sw_set_event_class(sw_ctx* c, const char* module, const char* qualname) {
     if (!c) return SW_EINVAL;
     if (!utf8_name(module) || !utf8_name(qualname)) return fail(c, SW_EINVAL, "sw_set_event_class: module and qualified name must be 1 .. 255 bytes of UTF-8");
-    if (c->pk_mod == module && c->pk_qual == qualname) return SW_OK;
+    if (c->pack.mod == module && c->pack.qual == qualname) return SW_OK;
     HIPCHK(c, hipSetDevice(c->device));
     HIPCHK(c, hipStreamSynchronize(c->stream));   // a pack call may still be reading the old header
-    c->pk_mod = module;
-    c->pk_qual = qualname;
-    c->pk_hdr_stale = true;
+    c->pack.mod = module;
+    c->pack.qual = qualname;
+    c->pack.hdr_stale = true;
     return SW_OK;
 }
 
 int sw_get_event_class(sw_ctx* c, char* module_out, char* qualname_out) {
     if (!c) return SW_EINVAL;
-    if (module_out) memcpy(module_out, c->pk_mod.c_str(), c->pk_mod.size() + 1);
-    if (qualname_out) memcpy(qualname_out, c->pk_qual.c_str(), c->pk_qual.size() + 1);
+    if (module_out) memcpy(module_out, c->pack.mod.c_str(), c->pack.mod.size() + 1);
+    if (qualname_out) memcpy(qualname_out, c->pack.qual.c_str(), c->pack.qual.size() + 1);
     return SW_OK;
 }
 
@@ -6322,7 +6345,7 @@ int sw_pack_events(sw_ctx* c, int64_t K, const uint8_t* sp_id32, const uint8_t* 
     const size_t o_moff = st.out(msg_off, (k + 1) * 8), o_woff = st.out(whole_off, (k + 1) * 8), o_m = st.out(msgs, (size_t)bm, 0), o_w = st.out(whole, (size_t)bw, 0);
     const size_t o_enc = st.out(encodable, k);
     unsigned char* B = nullptr;
-    CHK(stage_up(c, c->d_pk_in, st, &B));
+    CHK(stage_up(c, c->pack.d_in, st, &B));
     CHK(pack_launch(c, K, PackArrays{B + o_sp, B + o_op, B + o_ar, (const int32_t*)(B + o_cr), (const double*)(B + o_t), B + o_sig,
                                      data_off ? B + o_d : nullptr, data_off ? (const int64_t*)(B + o_doff) : nullptr, data_bytes,
                                      data_none ? B + o_dn : nullptr, B + o_m, (int64_t*)(B + o_moff), B + o_w, (int64_t*)(B + o_woff), B + o_enc}, bm, bw));
@@ -6332,37 +6355,18 @@ int sw_pack_events(sw_ctx* c, int64_t K, const uint8_t* sp_id32, const uint8_t* 
     st.out_bytes(msgs, (size_t)tm);
     st.out_bytes(whole, (size_t)tw);
     CHK(stage_down(c, st, B));
-    c->pk_bytes += tm + tw;
+    c->pack.bytes += tm + tw;
     if (msg_bytes) *msg_bytes = tm;
     if (whole_bytes) *whole_bytes = tw;
     return SW_OK;
 }
 
-int sw_sync_pull_validated(sw_ctx* dst, int64_t dst_head, sw_ctx* src, int64_t src_head, int64_t* n_sent, int64_t* n_valid, int64_t* n_stored) {
-    if (!dst || !src) return SW_EINVAL;
-    const char* what = "sw_sync_pull_validated";
-    if (n_sent) *n_sent = 0;
-    if (n_valid) *n_valid = 0;
-    if (n_stored) *n_stored = 0;
-    CHK(pull_pre(dst, dst_head, src, true, false, what));
-    if (const int rc = export_pre(src, src_head, "sw_sync_pull_validated (peer)"); rc != SW_OK) { dst->err = src->err; return rc; }
-    // ---- 1. and 2. as in sw_sync_pull: dst's known heights, src's ranges, count and gather
-    CHK(pull_begin(dst, dst_head, src, true, false, what));
-    int64_t total = 0;
-    ExportArrays d{};
-    CHK(pull_ranges(dst, src, src_head, false, what, &total, &d));
-    if (n_sent) *n_sent = total;
-    // ---- 3. and 4. dst, its stream ordered behind src's: the signed bytes (data None: the context stores no event data), the
-    // verdicts by dst's OWN keys and event class, and the ingest of what is valid (Node.sync's loop, swirld.py:130-136)
-    return pull_finish(dst, src, total, d, true, false, what, n_valid, n_stored);
-}
-
 int sw_get_pack_stats(sw_ctx* c, int64_t* calls, int64_t* events, int64_t* bytes, double* phase_ms) {
     if (!c) return SW_EINVAL;
-    if (calls) *calls = c->pk_calls;
-    if (events) *events = c->pk_events;
-    if (bytes) *bytes = c->pk_bytes;
-    if (phase_ms) for (int i = 0; i < 2; ++i) phase_ms[i] = c->pk_ms[i];
+    if (calls) *calls = c->pack.calls;
+    if (events) *events = c->pack.events;
+    if (bytes) *bytes = c->pack.bytes;
+    if (phase_ms) for (int i = 0; i < 2; ++i) phase_ms[i] = c->pack.ms[i];
     return SW_OK;
 }
 
@@ -6371,7 +6375,7 @@ int sw_get_pack_stats(sw_ctx* c, int64_t* calls, int64_t* events, int64_t* bytes
 
 namespace {
 
-struct DataPlan {   // the scratch of one call inside d_dt
+struct DataPlan {   // the scratch of one call inside data.d
     dat::i64* off;            // [K + 1] lengths, then scanned offsets; [K + 1]: the bad-slot count (low 32 bits)
     unsigned char* none;      // [K]
     dat::i64* tsum;           // tile sums of the scan
@@ -6383,17 +6387,17 @@ int data_scratch(sw_ctx* c, int64_t K, int64_t slots, int64_t oks, DataPlan* p) 
     const size_t k = (size_t)K, tiles = (k + pck::TILE - 1) / pck::TILE;
     Carve cv;
     const size_t o_off = cv.take((k + 2) * 8), o_none = cv.take(k), o_ts = cv.take((tiles + 1) * 8), o_slot = cv.take((size_t)slots * 4), o_ok = cv.take((size_t)oks);
-    CHK(dgrow(c, c->d_dt, cv.off + 256, 0));
-    unsigned char* B = c->d_dt.p;
+    CHK(dgrow(c, c->data.d, cv.off + 256, 0));
+    unsigned char* B = c->data.d.p;
     *p = DataPlan{(dat::i64*)(B + o_off), B + o_none, (dat::i64*)(B + o_ts), (int*)(B + o_slot), B + o_ok};
     return SW_OK;
 }
 
 // room for the data of `events` events in `bytes` bytes (contents kept): arena with its slack, offsets, flags
 int data_reserve(sw_ctx* c, int64_t events, int64_t bytes) {
-    CHK(dgrow(c, c->d_data, (size_t)bytes + dat::SLACK + 256, (size_t)c->data_used));
-    CHK(dgrow(c, c->d_data_off, (size_t)events + 1, c->d_data_off.p ? (size_t)c->n_data + 1 : 0));
-    CHK(dgrow(c, c->d_data_none, (size_t)events + 256, (size_t)c->n_data));
+    CHK(dgrow(c, c->data.d_arena, (size_t)bytes + dat::SLACK + 256, (size_t)c->data.used));
+    CHK(dgrow(c, c->data.d_off, (size_t)events + 1, c->data.d_off.p ? (size_t)c->data.n_data + 1 : 0));
+    CHK(dgrow(c, c->data.d_none, (size_t)events + 256, (size_t)c->data.n_data));
     return SW_OK;
 }
 
@@ -6417,8 +6421,8 @@ int data_plan(sw_ctx* c, int64_t K, const dat::SegIn& in, const DataPlan& p, int
     HIPCHK(c, hipStreamSynchronize(c->stream));
     *total = rb[0];
     *bad = rb[1] & 0xffffffffll;
-    c->dt_ms[0] = c->profiling ? ms_since(t0) : 0;
-    c->dt_ms[1] = 0;
+    c->data.ms[0] = c->profiling ? ms_since(t0) : 0;
+    c->data.ms[1] = 0;
     return SW_OK;
 }
 
@@ -6439,7 +6443,7 @@ int data_copy(sw_ctx* c, int64_t K, const dat::SegIn& in, const DataPlan& p, int
                        (dat::i64*)off_out, (const unsigned char*)p.none, none_out);
     c->ctr.kernel_launches++;
     HIPCHK(c, hipGetLastError());
-    if (c->profiling) { HIPCHK(c, hipStreamSynchronize(c->stream)); c->dt_ms[1] = ms_since(t0); }
+    if (c->profiling) { HIPCHK(c, hipStreamSynchronize(c->stream)); c->data.ms[1] = ms_since(t0); }
     return SW_OK;
 }
 
@@ -6447,7 +6451,7 @@ int data_copy(sw_ctx* c, int64_t K, const dat::SegIn& in, const DataPlan& p, int
 int data_set_args(sw_ctx* c, int64_t first, int64_t K, const void* data, const void* data_off, int64_t data_bytes, const void* data_none, const char* what) {
     if (c->poisoned) return fail(c, SW_EIO, "context unusable after an earlier device failure");
     if (K < 0 || data_bytes < 0) return fail(c, SW_EINVAL, "%s: negative count or length", what);
-    if (first != c->n_data) return fail(c, SW_EINVAL, "%s must continue at event %lld (got %lld): data is contiguous from 0", what, (long long)c->n_data, (long long)first);
+    if (first != c->data.n_data) return fail(c, SW_EINVAL, "%s must continue at event %lld (got %lld): data is contiguous from 0", what, (long long)c->data.n_data, (long long)first);
     if (first + K > c->N) return fail(c, SW_ERANGE, "%s: events [%lld, %lld) outside the stored hashgraph", what, (long long)first, (long long)(first + K));
     if (!data_off && (data || data_bytes || data_none)) return fail(c, SW_EINVAL, "%s: data needs its offsets (or none of data, offsets, length, flags)", what);
     if (data_off && data_bytes > 0 && !data) return fail(c, SW_EINVAL, "%s: %lld data bytes and a NULL buffer", what, (long long)data_bytes);
@@ -6464,11 +6468,11 @@ int data_set_body(sw_ctx* c, int64_t K, const uint8_t* d_data, const int64_t* d_
     if (bad) return fail(c, SW_EINVAL, "%s: %lld events with offsets that are negative, decreasing, beyond the %lld data bytes, or a length above %d (nothing stored)",
                          what, (long long)bad, (long long)data_bytes, dat::MAX_DATA);
     if (total < 0 || total > data_bytes) return fail(c, SW_EIO, "%s: %lld bytes from a buffer of %lld (internal error)", what, (long long)total, (long long)data_bytes);
-    CHK(data_reserve(c, c->n_data + K, c->data_used + total));
-    CHK(data_copy(c, K, in, p, total, c->d_data.p, c->data_used, c->data_used, (int64_t*)c->d_data_off.p + c->n_data, c->d_data_none.p + c->n_data));
-    c->n_data += K;
-    c->data_used += total;
-    c->dt_store_calls++;
+    CHK(data_reserve(c, c->data.n_data + K, c->data.used + total));
+    CHK(data_copy(c, K, in, p, total, c->data.d_arena.p, c->data.used, c->data.used, (int64_t*)c->data.d_off.p + c->data.n_data, c->data.d_none.p + c->data.n_data));
+    c->data.n_data += K;
+    c->data.used += total;
+    c->data.store_calls++;
     return SW_OK;
 }
 
@@ -6481,17 +6485,17 @@ int data_gather_args(sw_ctx* c, int64_t K, const void* event, int64_t cap, const
     if (K > 0 && !event) return fail(c, SW_EINVAL, "%s: NULL event indices", what);
     *query = cap == 0 && !data && !off && !none;
     if (!*query && (!off || (K > 0 && !none) || (cap > 0 && !data))) return fail(c, SW_EINVAL, "%s: NULL output arrays (capacity %lld)", what, (long long)cap);
-    if (K > 0 && c->n_data == 0) return fail(c, SW_ERANGE, "%s: no event has data (nothing written)", what);
+    if (K > 0 && c->data.n_data == 0) return fail(c, SW_ERANGE, "%s: no event has data (nothing written)", what);
     return SW_OK;
 }
 
 // the gather behind the argument checks, in two steps: lengths, scan and the refusals (one synchronisation) ...
 int data_gather_plan(sw_ctx* c, int64_t K, const int32_t* d_event, int64_t cap, int64_t* n_bytes, DataPlan* p, dat::SegIn* in, const char* what) {
     CHK(data_scratch(c, K, 0, 0, p));
-    *in = dat::SegIn{c->d_data.p, (const dat::i64*)c->d_data_off.p, c->d_data_none.p, d_event, (dat::i64)c->n_data, (dat::i64)c->data_used, 1};
+    *in = dat::SegIn{c->data.d_arena.p, (const dat::i64*)c->data.d_off.p, c->data.d_none.p, d_event, (dat::i64)c->data.n_data, (dat::i64)c->data.used, 1};
     int64_t total = 0, bad = 0;
     CHK(data_plan(c, K, *in, *p, &total, &bad));
-    if (bad) return fail(c, SW_ERANGE, "%s: %lld indices outside the %lld events that have data (nothing written)", what, (long long)bad, (long long)c->n_data);
+    if (bad) return fail(c, SW_ERANGE, "%s: %lld indices outside the %lld events that have data (nothing written)", what, (long long)bad, (long long)c->data.n_data);
     *n_bytes = total;
     if (total > cap) return fail(c, SW_ERANGE, "%s: %lld bytes to gather, capacity %lld (nothing written)", what, (long long)total, (long long)cap);
     return SW_OK;
@@ -6499,14 +6503,14 @@ int data_gather_plan(sw_ctx* c, int64_t K, const int32_t* d_event, int64_t cap, 
 // ... and the copy into device arrays that hold *n_bytes bytes, K + 1 offsets and K flags
 int data_gather_copy(sw_ctx* c, int64_t K, const DataPlan& p, const dat::SegIn& in, int64_t total, uint8_t* d_data, int64_t* d_off, uint8_t* d_none) {
     CHK(data_copy(c, K, in, p, total, d_data, 0, 0, d_off, d_none));
-    c->dt_gather_calls++;
-    c->dt_gather_bytes += total;
+    c->data.gather_calls++;
+    c->data.gather_bytes += total;
     return SW_OK;
 }
 
 int data_payload_args(sw_ctx* c, const void* data, const void* data_off, int64_t data_bytes, const void* data_none, const char* what) {
-    if (c->n_data != c->N)
-        return fail(c, SW_ENOTSUP, "%s: %lld of the %lld stored events have no data entry (sw_set_event_data first)", what, (long long)(c->N - c->n_data), (long long)c->N);
+    if (c->data.n_data != c->N)
+        return fail(c, SW_ENOTSUP, "%s: %lld of the %lld stored events have no data entry (sw_set_event_data first)", what, (long long)(c->N - c->data.n_data), (long long)c->N);
     if (data_bytes < 0) return fail(c, SW_EINVAL, "%s: negative data length", what);
     if (!data_off && (data || data_bytes || data_none)) return fail(c, SW_EINVAL, "%s: data needs its offsets (or none of data, offsets, length, flags)", what);
     if (data_off && data_bytes > 0 && !data) return fail(c, SW_EINVAL, "%s: %lld data bytes and a NULL buffer", what, (long long)data_bytes);
@@ -6521,7 +6525,7 @@ int ingest_data_core(sw_ctx* c, int64_t K, const uint8_t* d_id32, const uint8_t*
     const int64_t N0 = c->N;
     DataPlan p{};
     CHK(data_scratch(c, K, K, K, &p));
-    CHK(data_reserve(c, N0 + K, c->data_used + data_bytes));
+    CHK(data_reserve(c, N0 + K, c->data.used + data_bytes));
     UserStream bracket;   // (left by the destructor on a failure; a success has drained the stream)
     CHK(bracket.join(c, us));
     // an event whose data range cannot be used is not valid (-3): pack's d_encodable rule, folded into a copy of d_ok
@@ -6553,11 +6557,11 @@ int ingest_data_core(sw_ctx* c, int64_t K, const uint8_t* d_id32, const uint8_t*
         CHK(data_plan(c, A, in, p, &total, &bad));
         if (bad || total < 0 || total > data_bytes)   // (the stored events' ranges are among the usable ones, summed above)
             return fail(c, SW_EIO, "data of the accepted events: %lld bad slots, %lld bytes of %lld (internal error)", (long long)bad, (long long)total, (long long)data_bytes);
-        CHK(data_copy(c, A, in, p, total, c->d_data.p, c->data_used, c->data_used, (int64_t*)c->d_data_off.p + N0, c->d_data_none.p + N0));
+        CHK(data_copy(c, A, in, p, total, c->data.d_arena.p, c->data.used, c->data.used, (int64_t*)c->data.d_off.p + N0, c->data.d_none.p + N0));
         HIPCHK(c, hipStreamSynchronize(c->stream));   // the copy has read the caller's arrays: on return they may be reused or freed
-        c->n_data = N0 + A;
-        c->data_used += total;
-        c->dt_store_calls++;
+        c->data.n_data = N0 + A;
+        c->data.used += total;
+        c->data.store_calls++;
         return SW_OK;
     };
     const int rc = after();
@@ -6600,7 +6604,7 @@ int sw_set_event_data(sw_ctx* c, int64_t first, int64_t K, const uint8_t* data, 
     Stage st;
     const size_t o_off = st.in(data_off, (k + 1) * 8), o_d = st.in(data, (size_t)data_bytes), o_n = st.in(data_none, k);
     unsigned char* B = nullptr;
-    CHK(stage_up(c, c->d_dt_in, st, &B));
+    CHK(stage_up(c, c->data.d_in, st, &B));
     return data_set_body(c, K, data_off ? B + o_d : nullptr, data_off ? (const int64_t*)(B + o_off) : nullptr, data_bytes, data_none ? B + o_n : nullptr, what);
 }
 
@@ -6608,21 +6612,21 @@ int sw_get_event_data(sw_ctx* c, int64_t first, int64_t K, int64_t cap, uint8_t*
     if (!c) return SW_EINVAL;
     if (!n_bytes) return fail(c, SW_EINVAL, "sw_get_event_data: n_bytes is NULL");
     *n_bytes = 0;
-    if (first < 0 || K < 0 || first + K > c->n_data)
-        return fail(c, SW_ERANGE, "events [%lld, %lld) beyond the %lld events that have data", (long long)first, (long long)(first + K), (long long)c->n_data);
+    if (first < 0 || K < 0 || first + K > c->data.n_data)
+        return fail(c, SW_ERANGE, "events [%lld, %lld) beyond the %lld events that have data", (long long)first, (long long)(first + K), (long long)c->data.n_data);
     if (cap < 0) return fail(c, SW_EINVAL, "sw_get_event_data: negative capacity");
     if (K == 0) { if (data_off) data_off[0] = 0; return SW_OK; }
     HIPCHK(c, hipSetDevice(c->device));
     std::vector<int64_t> off((size_t)K + 1);
-    HIPCHK(c, hipMemcpyAsync(off.data(), c->d_data_off.p + first, ((size_t)K + 1) * 8, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(off.data(), c->data.d_off.p + first, ((size_t)K + 1) * 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     const int64_t a = off[0], bytes = off[(size_t)K] - a;
-    if (a < 0 || bytes < 0 || off[(size_t)K] > c->data_used) return fail(c, SW_EIO, "sw_get_event_data: stored offsets [%lld, %lld) (internal error)", (long long)a, (long long)off[(size_t)K]);
+    if (a < 0 || bytes < 0 || off[(size_t)K] > c->data.used) return fail(c, SW_EIO, "sw_get_event_data: stored offsets [%lld, %lld) (internal error)", (long long)a, (long long)off[(size_t)K]);
     *n_bytes = bytes;
     if (bytes > cap) return fail(c, SW_ERANGE, "sw_get_event_data: %lld bytes, capacity %lld (nothing written)", (long long)bytes, (long long)cap);
     if (!data_off || !data_none || (bytes > 0 && !data)) return fail(c, SW_EINVAL, "sw_get_event_data: NULL output arrays");
-    if (bytes) HIPCHK(c, hipMemcpyAsync(data, c->d_data.p + a, (size_t)bytes, hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipMemcpyAsync(data_none, c->d_data_none.p + first, (size_t)K, hipMemcpyDeviceToHost, c->stream));
+    if (bytes) HIPCHK(c, hipMemcpyAsync(data, c->data.d_arena.p + a, (size_t)bytes, hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(data_none, c->data.d_none.p + first, (size_t)K, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     for (int64_t i = 0; i <= K; ++i) data_off[i] = off[(size_t)i] - a;
     return SW_OK;
@@ -6658,7 +6662,7 @@ int sw_gather_event_data(sw_ctx* c, int64_t K, const int32_t* event, int64_t cap
     Stage si;
     si.in(event, k * 4);
     unsigned char* E = nullptr;
-    CHK(stage_up(c, c->d_dt_in, si, &E));
+    CHK(stage_up(c, c->data.d_in, si, &E));
     DataPlan p{};
     dat::SegIn in{};
     CHK(data_gather_plan(c, K, (const int32_t*)E, cap, n_bytes, &p, &in, what));
@@ -6666,7 +6670,7 @@ int sw_gather_event_data(sw_ctx* c, int64_t K, const int32_t* event, int64_t cap
     Stage st;   // the outputs, sized from the total (not from the caller's capacity)
     const size_t o_off = st.out(data_off, (k + 1) * 8), o_n = st.out(data_none, k), o_d = st.out(data, (size_t)*n_bytes + 16, (size_t)*n_bytes);
     unsigned char* B = nullptr;
-    CHK(stage_up(c, c->d_dt_out, st, &B));
+    CHK(stage_up(c, c->data.d_out, st, &B));
     CHK(data_gather_copy(c, K, p, in, *n_bytes, B + o_d, (int64_t*)(B + o_off), B + o_n));
     return stage_down(c, st, B);
 }
@@ -6702,7 +6706,7 @@ int sw_ingest_payload_data(sw_ctx* c, int64_t K, const uint8_t* id32, const uint
     const size_t o_ok = st.in(ok, k), o_t = st.in(t, k * 8), o_sig = st.in(sig64, k * 64), o_out = st.out(index_out, k * 4);
     const size_t o_doff = st.in(data_off, (k + 1) * 8), o_d = st.in(data, (size_t)data_bytes), o_dn = st.in(data_none, k);
     unsigned char* B = nullptr;
-    CHK(stage_up(c, c->d_dt_in, st, &B));
+    CHK(stage_up(c, c->data.d_in, st, &B));
     CHK(ingest_data_core(c, K, B + o_id, B + o_sp, B + o_op, B + o_ar, (const int32_t*)(B + o_cr), ok ? B + o_ok : nullptr,
                          t ? (const double*)(B + o_t) : nullptr, sig64 ? B + o_sig : nullptr, data_off ? B + o_d : nullptr,
                          data_off ? (const int64_t*)(B + o_doff) : nullptr, data_bytes, data_none ? B + o_dn : nullptr, c->stream,
@@ -6720,11 +6724,11 @@ int pull_pre(sw_ctx* dst, int64_t dst_head, sw_ctx* src, bool validate, bool dat
     if (dst->device != src->device) return fail(dst, SW_ENOTSUP, "%s: the contexts live on devices %d and %d (same device only)", what, dst->device, src->device);
     if (dst->n != src->n) return fail(dst, SW_EINVAL, "%s: %d members here, %d at the peer", what, dst->n, src->n);
     if (dst->poisoned) return fail(dst, SW_EIO, "context unusable after an earlier device failure");
-    if (validate && dst->vkeys.empty()) return fail(dst, SW_ENOTSUP, "%s: no member keys (sw_set_member_keys first)", what);
-    if (dst->n_ids != dst->N)
-        return fail(dst, SW_ENOTSUP, "%s: %lld of the %lld stored events have no id (sw_set_event_ids first)", what, (long long)(dst->N - dst->n_ids), (long long)dst->N);
-    if (data && dst->n_data != dst->N)
-        return fail(dst, SW_ENOTSUP, "%s: %lld of the %lld stored events have no data entry (sw_set_event_data first)", what, (long long)(dst->N - dst->n_data), (long long)dst->N);
+    if (validate && dst->val.keys.empty()) return fail(dst, SW_ENOTSUP, "%s: no member keys (sw_set_member_keys first)", what);
+    if (dst->ids.n_ids != dst->N)
+        return fail(dst, SW_ENOTSUP, "%s: %lld of the %lld stored events have no id (sw_set_event_ids first)", what, (long long)(dst->N - dst->ids.n_ids), (long long)dst->N);
+    if (data && dst->data.n_data != dst->N)
+        return fail(dst, SW_ENOTSUP, "%s: %lld of the %lld stored events have no data entry (sw_set_event_data first)", what, (long long)(dst->N - dst->data.n_data), (long long)dst->N);
     if (dst_head < dst->first_resident || dst_head >= dst->divided) return fail(dst, SW_ERANGE, "%s: head %lld is not a divided, resident event", what, (long long)dst_head);
     return SW_OK;
 }
@@ -6732,10 +6736,10 @@ int pull_pre(sw_ctx* dst, int64_t dst_head, sw_ctx* src, bool validate, bool dat
 // behind the checks of the answering context: what dst knows at its head (swirld.py:125-126), left in its own scratch
 // (dst->d_q); src's stream waits for it
 int pull_begin(sw_ctx* dst, int64_t dst_head, sw_ctx* src, bool validate, bool data, const char* what) {
-    if (data && src->n_data != src->N)
-        return fail(dst, SW_ENOTSUP, "%s: %lld of the peer's %lld stored events have no data entry (sw_set_event_data first)", what, (long long)(src->N - src->n_data), (long long)src->N);
+    if (data && src->data.n_data != src->N)
+        return fail(dst, SW_ENOTSUP, "%s: %lld of the peer's %lld stored events have no data entry (sw_set_event_data first)", what, (long long)(src->N - src->data.n_data), (long long)src->N);
     HIPCHK(dst, hipSetDevice(dst->device));
-    if (validate && !dst->h_pkcnt.reserve(1)) return fail(dst, SW_ENOMEM, "hipHostMalloc for the count of valid events failed");
+    if (validate && !dst->pack.h_cnt.reserve(1)) return fail(dst, SW_ENOMEM, "hipHostMalloc for the count of valid events failed");
     CHK(heights_on_device(dst));
     const int np = dst->npad;
     CHK(dgrow(dst, dst->d_q, (size_t)3 * np, 0));
@@ -6757,22 +6761,73 @@ int pull_ranges(sw_ctx* dst, sw_ctx* src, int64_t src_head, bool with_event, con
     auto t0 = std::chrono::steady_clock::now();
     int64_t total = 0;
     if (const int rc = export_ranges(src, src_head, dst->d_q.p, hipMemcpyDeviceToDevice, &total); rc != SW_OK) { dst->err = src->err; return rc; }
-    src->xp_ms[0] = prof ? ms_since(t0) : 0;
-    src->xp_ms[1] = 0;
+    src->xp.ms[0] = prof ? ms_since(t0) : 0;
+    src->xp.ms[1] = 0;
     if (total > 0x3fffffffll || dst->N + total > 0x7ffffff0ll) return fail(dst, SW_ERANGE, "%s: more than 2^31 events", what);
     t0 = std::chrono::steady_clock::now();
     int rc = export_scratch(src, total, true, true, with_event, d);
     if (rc == SW_OK) rc = export_gather(src, total, *d);
     if (rc != SW_OK) { dst->err = src->err; return rc; }
-    if (prof) { HIPCHK(src, hipStreamSynchronize(src->stream)); src->xp_ms[1] = ms_since(t0); }
-    src->xp_calls++;
-    src->xp_events += total;
+    if (prof) { HIPCHK(src, hipStreamSynchronize(src->stream)); src->xp.ms[1] = ms_since(t0); }
+    src->xp.calls++;
+    src->xp.events += total;
     *total_out = total;
     return SW_OK;
 }
 
+// `total` events in device arrays written on stream `from` (the peer's, or dst's own), with or without data arrays:
+//   validate  dst, its stream ordered behind `from`, builds the signed bytes (with the data, or with data None), judges them by
+//             its OWN keys and event class, ANDs the verdicts with the encodable flags and counts them
+//   then      dst ingests what is valid (Node.sync's loop, swirld.py:130-136), keeping the data when `store_data`; the dense
+//             indices are left in dst->ids.d_pl_in.  dst's stream is drained before the call returns.
 int ingest_arrays(sw_ctx* dst, hipStream_t from, int64_t total, const ExportArrays& d, const uint8_t* x_data, const int64_t* x_off, int64_t dbytes,
-                  const uint8_t* x_none, bool validate, bool store_data, int64_t* n_valid, int64_t* n_stored);
+                  const uint8_t* x_none, bool validate, bool store_data, int64_t* n_valid, int64_t* n_stored) {
+    const size_t k = (size_t)total;
+    int rc = SW_OK;
+    CHK(dgrow(dst, dst->ids.d_pl_in, k * sizeof(int32_t), 0));
+    const uint8_t* ok = nullptr;
+    if (validate) {
+        int64_t bm = 0, bw = 0;
+        pack_bound(dst, total, dbytes, &bm, &bw);
+        Carve cv;
+        const size_t o_moff = cv.take((k + 1) * 8), o_woff = cv.take((k + 1) * 8), o_m = cv.take((size_t)bm), o_w = cv.take((size_t)bw);
+        const size_t o_enc = cv.take(k), o_ok = cv.take(k), o_cnt = cv.take(sizeof(int32_t));
+        CHK(dgrow(dst, dst->pack.d_out, cv.off + 256, 0));
+        unsigned char* B = dst->pack.d_out.p;
+        // (not a UserStream: `from` is the peer's stream or our own, and nothing is handed back to it: our stream is drained
+        // before the call returns, which is what frees the peer's scratch)
+        HIPCHK(dst, hipEventRecord(dst->ev_user, from));
+        HIPCHK(dst, hipStreamWaitEvent(dst->stream, dst->ev_user, 0));
+        HIPCHK(dst, hipMemsetAsync(B + o_cnt, 0, sizeof(int32_t), dst->stream));
+        rc = pack_launch(dst, total, PackArrays{d.sp_id, d.op_id, d.arity, d.creator, d.t, d.sig, x_data, x_off, dbytes, x_none, B + o_m, (int64_t*)(B + o_moff),
+                                                B + o_w, (int64_t*)(B + o_woff), B + o_enc}, bm, bw);
+        if (rc == SW_OK) {
+            const swv::Payload p{B + o_m, (const long long*)(B + o_moff), (long long)bm, B + o_w, (const long long*)(B + o_woff), (long long)bw, d.sig, d.creator, d.id};
+            rc = validate_launch(dst, total, p, B + o_ok);
+        }
+        if (rc != SW_OK) { (void)hipStreamSynchronize(dst->stream); return rc; }   // (src's scratch is free again only once dst has read it)
+        dst->val.calls++;
+        dst->val.events += total;
+        hipLaunchKernelGGL(pck::k_pack_and_count, dim3((unsigned)std::min<int64_t>(1024, (total + 255) / 256)), dim3(256), 0, dst->stream, (pck::i64)total,
+                           B + o_ok, (const unsigned char*)(B + o_enc), (int*)(B + o_cnt));
+        dst->ctr.kernel_launches++;
+        HIPCHK(dst, hipGetLastError());
+        HIPCHK(dst, hipMemcpyAsync(dst->pack.h_cnt.p, B + o_cnt, sizeof(int32_t), hipMemcpyDeviceToHost, dst->stream));
+        ok = B + o_ok;
+    }
+    int64_t stored = 0;
+    if (store_data)
+        rc = ingest_data_core(dst, total, d.id, d.sp_id, d.op_id, d.arity, d.creator, ok, d.t, d.sig, x_data, x_off, dbytes, x_none, from,
+                              (int32_t*)dst->ids.d_pl_in.p, &stored);
+    else
+        rc = payload_core(dst, total, d.id, d.sp_id, d.op_id, d.arity, d.creator, ok, d.t, d.sig, from, (int32_t*)dst->ids.d_pl_in.p, &stored);
+    const hipError_t drained = hipStreamSynchronize(dst->stream);   // src's scratch is free again only once dst has read it
+    if (rc != SW_OK) return rc;
+    HIPCHK(dst, drained);
+    if (validate && n_valid) *n_valid = *dst->pack.h_cnt.p;
+    if (n_stored) *n_stored = stored;
+    return SW_OK;
+}
 
 // behind src's export of `total` events into `d` (its scratch, written on its stream):
 //   data      src gathers the data of those events beside the other arrays (its second synchronisation: the byte total)
@@ -6790,18 +6845,18 @@ int pull_finish(sw_ctx* dst, sw_ctx* src, int64_t total, const ExportArrays& d, 
     if (data) {
         DataPlan sp{};
         int64_t bad = 0;
-        const dat::SegIn sin{src->d_data.p, (const dat::i64*)src->d_data_off.p, src->d_data_none.p, d.event, (dat::i64)src->n_data, (dat::i64)src->data_used, 1};
+        const dat::SegIn sin{src->data.d_arena.p, (const dat::i64*)src->data.d_off.p, src->data.d_none.p, d.event, (dat::i64)src->data.n_data, (dat::i64)src->data.used, 1};
         rc = data_scratch(src, total, 0, 0, &sp);
         if (rc == SW_OK) rc = data_plan(src, total, sin, sp, &dbytes, &bad);
         if (rc == SW_OK && bad) rc = fail(src, SW_EIO, "%s: %lld exported events without data (internal error)", what, (long long)bad);
         Carve sv;
         const size_t s_d = sv.take((size_t)dbytes + 16), s_off = sv.take((k + 1) * 8), s_n = sv.take(k);
-        if (rc == SW_OK) rc = dgrow(src, src->d_dt_out, sv.off + 256, 0);
-        unsigned char* S = src->d_dt_out.p;
+        if (rc == SW_OK) rc = dgrow(src, src->data.d_out, sv.off + 256, 0);
+        unsigned char* S = src->data.d_out.p;
         if (rc == SW_OK) rc = data_copy(src, total, sin, sp, dbytes, S + s_d, 0, 0, (int64_t*)(S + s_off), S + s_n);
         if (rc != SW_OK) { dst->err = src->err; return rc; }
-        src->dt_gather_calls++;
-        src->dt_gather_bytes += dbytes;
+        src->data.gather_calls++;
+        src->data.gather_bytes += dbytes;
         x_data = S + s_d;
         x_off = (const int64_t*)(S + s_off);
         x_none = S + s_n;
@@ -6809,94 +6864,40 @@ int pull_finish(sw_ctx* dst, sw_ctx* src, int64_t total, const ExportArrays& d, 
     return ingest_arrays(dst, src->stream, total, d, x_data, x_off, dbytes, x_none, validate, data, n_valid, n_stored);
 }
 
-// `total` events in device arrays written on stream `from` (the peer's, or dst's own), with or without data arrays:
-//   validate  dst, its stream ordered behind `from`, builds the signed bytes (with the data, or with data None), judges them by
-//             its OWN keys and event class, ANDs the verdicts with the encodable flags and counts them
-//   then      dst ingests what is valid (Node.sync's loop, swirld.py:130-136), keeping the data when `store_data`; the dense
-//             indices are left in dst->d_pl_in.  dst's stream is drained before the call returns.
-int ingest_arrays(sw_ctx* dst, hipStream_t from, int64_t total, const ExportArrays& d, const uint8_t* x_data, const int64_t* x_off, int64_t dbytes,
-                  const uint8_t* x_none, bool validate, bool store_data, int64_t* n_valid, int64_t* n_stored) {
-    const size_t k = (size_t)total;
-    int rc = SW_OK;
-    CHK(dgrow(dst, dst->d_pl_in, k * sizeof(int32_t), 0));
-    const uint8_t* ok = nullptr;
-    if (validate) {
-        int64_t bm = 0, bw = 0;
-        pack_bound(dst, total, dbytes, &bm, &bw);
-        Carve cv;
-        const size_t o_moff = cv.take((k + 1) * 8), o_woff = cv.take((k + 1) * 8), o_m = cv.take((size_t)bm), o_w = cv.take((size_t)bw);
-        const size_t o_enc = cv.take(k), o_ok = cv.take(k), o_cnt = cv.take(sizeof(int32_t));
-        CHK(dgrow(dst, dst->d_pk_out, cv.off + 256, 0));
-        unsigned char* B = dst->d_pk_out.p;
-        // (not a UserStream: `from` is the peer's stream or our own, and nothing is handed back to it: our stream is drained
-        // before the call returns, which is what frees the peer's scratch)
-        HIPCHK(dst, hipEventRecord(dst->ev_user, from));
-        HIPCHK(dst, hipStreamWaitEvent(dst->stream, dst->ev_user, 0));
-        HIPCHK(dst, hipMemsetAsync(B + o_cnt, 0, sizeof(int32_t), dst->stream));
-        rc = pack_launch(dst, total, PackArrays{d.sp_id, d.op_id, d.arity, d.creator, d.t, d.sig, x_data, x_off, dbytes, x_none, B + o_m, (int64_t*)(B + o_moff),
-                                                B + o_w, (int64_t*)(B + o_woff), B + o_enc}, bm, bw);
-        if (rc == SW_OK) {
-            const swv::Payload p{B + o_m, (const long long*)(B + o_moff), (long long)bm, B + o_w, (const long long*)(B + o_woff), (long long)bw, d.sig, d.creator, d.id};
-            rc = validate_launch(dst, total, p, B + o_ok);
-        }
-        if (rc != SW_OK) { (void)hipStreamSynchronize(dst->stream); return rc; }   // (src's scratch is free again only once dst has read it)
-        dst->v_calls++;
-        dst->v_events += total;
-        hipLaunchKernelGGL(pck::k_pack_and_count, dim3((unsigned)std::min<int64_t>(1024, (total + 255) / 256)), dim3(256), 0, dst->stream, (pck::i64)total,
-                           B + o_ok, (const unsigned char*)(B + o_enc), (int*)(B + o_cnt));
-        dst->ctr.kernel_launches++;
-        HIPCHK(dst, hipGetLastError());
-        HIPCHK(dst, hipMemcpyAsync(dst->h_pkcnt.p, B + o_cnt, sizeof(int32_t), hipMemcpyDeviceToHost, dst->stream));
-        ok = B + o_ok;
-    }
-    int64_t stored = 0;
-    if (store_data)
-        rc = ingest_data_core(dst, total, d.id, d.sp_id, d.op_id, d.arity, d.creator, ok, d.t, d.sig, x_data, x_off, dbytes, x_none, from,
-                              (int32_t*)dst->d_pl_in.p, &stored);
-    else
-        rc = payload_core(dst, total, d.id, d.sp_id, d.op_id, d.arity, d.creator, ok, d.t, d.sig, from, (int32_t*)dst->d_pl_in.p, &stored);
-    const hipError_t drained = hipStreamSynchronize(dst->stream);   // src's scratch is free again only once dst has read it
-    if (rc != SW_OK) return rc;
-    HIPCHK(dst, drained);
-    if (validate && n_valid) *n_valid = *dst->h_pkcnt.p;
-    if (n_stored) *n_stored = stored;
-    return SW_OK;
-}
-
 // ---- answering a sync by the pruned walk (walk.hip.h) ------------------------------------------------------
 // what every walk call asks of the answering context: either path, but every can_see row resident
 int walk_pre(sw_ctx* c, int64_t head, bool need_ids, const char* what) {
     if (c->poisoned) return fail(c, SW_EIO, "context unusable after an earlier device failure");
     if (c->vm.active) return fail(c, SW_ENOTSUP, "%s is not available with the windowed table", what);
-    if (need_ids && c->n_ids != c->N)
-        return fail(c, SW_ENOTSUP, "%s: %lld of the %lld stored events have no id (sw_set_event_ids first)", what, (long long)(c->N - c->n_ids), (long long)c->N);
+    if (need_ids && c->ids.n_ids != c->N)
+        return fail(c, SW_ENOTSUP, "%s: %lld of the %lld stored events have no id (sw_set_event_ids first)", what, (long long)(c->N - c->ids.n_ids), (long long)c->N);
     if (head < c->first_resident || head >= c->divided || head >= c->N)
         return fail(c, SW_ERANGE, "%s: head %lld is not a divided, resident event", what, (long long)head);
     return SW_OK;
 }
 
-// trunk[c] of every member as of the stored events, in d_wk_trunk, on the context's stream (asynchronous).  Recomputed only
+// trunk[c] of every member as of the stored events, in walk.d_trunk, on the context's stream (asynchronous).  Recomputed only
 // when events have arrived since.
 int fork_trunks(sw_ctx* c) {
     const int np = c->npad;
-    CHK(dgrow(c, c->d_wk_trunk, (size_t)2 * np, 0));
-    if (c->wk_trunk_N == c->N) return SW_OK;
+    CHK(dgrow(c, c->walk.d_trunk, (size_t)2 * np, 0));
+    if (c->walk.trunk_N == c->N) return SW_OK;
     CHK(heights_on_device(c));
     const int64_t N = c->N;
     if (N > 0) {
-        CHK(dgrow(c, c->d_wk_children, (size_t)N, 0));
-        HIPCHK(c, hipMemsetAsync(c->d_wk_children.p, 0, (size_t)N * sizeof(int32_t), c->stream));
+        CHK(dgrow(c, c->walk.d_children, (size_t)N, 0));
+        HIPCHK(c, hipMemsetAsync(c->walk.d_children.p, 0, (size_t)N * sizeof(int32_t), c->stream));
     }
-    HIPCHK(c, hipMemsetAsync(c->d_wk_trunk.p + np, 0, (size_t)np * sizeof(int32_t), c->stream));
-    CHK(fill_i32(c, c->d_wk_trunk.p, (size_t)np, wlk::NO_CAP));
+    HIPCHK(c, hipMemsetAsync(c->walk.d_trunk.p + np, 0, (size_t)np * sizeof(int32_t), c->stream));
+    CHK(fill_i32(c, c->walk.d_trunk.p, (size_t)np, wlk::NO_CAP));
     if (N > 0) {
         const unsigned blocks = (unsigned)std::min<int64_t>(2048, (N + wlk::TRUNK_THREADS - 1) / wlk::TRUNK_THREADS);
         hipLaunchKernelGGL(wlk::k_fork_trunks, dim3(blocks), dim3(wlk::TRUNK_THREADS), 0, c->stream, (const int*)c->d_sp.p, (const int*)c->d_cr.p,
-                           (const int*)c->d_ht.p, c->n, (long long)N, c->d_wk_children.p, c->d_wk_trunk.p + np, c->d_wk_trunk.p);
+                           (const int*)c->d_ht.p, c->n, (long long)N, c->walk.d_children.p, c->walk.d_trunk.p + np, c->walk.d_trunk.p);
         c->ctr.kernel_launches++;
         HIPCHK(c, hipGetLastError());
     }
-    c->wk_trunk_N = N;
+    c->walk.trunk_N = N;
     return SW_OK;
 }
 
@@ -6907,54 +6908,54 @@ int walk_run(sw_ctx* c, int64_t head, const int32_t* known, const int32_t* cap, 
     CHK(heights_on_device(c));
     const int np = c->npad, n = c->n;
     const size_t ev = (size_t)head + 1, words = (ev + 31) / 32;
-    CHK(dgrow(c, c->d_wk, (size_t)wlk::H_WORDS + 2 * (size_t)np, 0));
-    CHK(dgrow(c, c->d_wk_bits, words, 0));
-    CHK(dgrow(c, c->d_wk_q, ev, 0));
-    CHK(dgrow(c, c->d_wk_list, ev, 0));
+    CHK(dgrow(c, c->walk.d, (size_t)wlk::H_WORDS + 2 * (size_t)np, 0));
+    CHK(dgrow(c, c->walk.d_bits, words, 0));
+    CHK(dgrow(c, c->walk.d_q, ev, 0));
+    CHK(dgrow(c, c->walk.d_list, ev, 0));
     if (c->payload_pending) HIPCHK(c, hipStreamWaitEvent(c->stream, c->ev_payload, 0));   // timestamps / signatures of a bulk host append
-    int32_t* d_hdr = c->d_wk.p;
+    int32_t* d_hdr = c->walk.d.p;
     int32_t* d_known = d_hdr + wlk::H_WORDS;
     int32_t* d_cap = d_known + np;
     HIPCHK(c, hipMemsetAsync(d_hdr, 0, wlk::H_WORDS * sizeof(int32_t), c->stream));
     if (known) HIPCHK(c, hipMemcpyAsync(d_known, known, (size_t)n * sizeof(int32_t), kind, c->stream));
     if (cap) HIPCHK(c, hipMemcpyAsync(d_cap, cap, (size_t)n * sizeof(int32_t), kind, c->stream));
-    HIPCHK(c, hipMemsetAsync(c->d_wk_bits.p, 0, words * sizeof(unsigned), c->stream));
+    HIPCHK(c, hipMemsetAsync(c->walk.d_bits.p, 0, words * sizeof(unsigned), c->stream));
     const bool prof = c->profiling;
     auto t0 = std::chrono::steady_clock::now();
     const wlk::WalkIn in{c->d_sp.p, c->d_op.p, c->d_cr.p, c->d_ht.p, n, (int)head};
     const size_t lds = (size_t)(n + wlk::C_WORDS) * sizeof(int);
-    hipLaunchKernelGGL(wlk::k_walk_bfs, dim3(1), dim3(c->walk_threads), lds, c->stream, in, known ? (const int*)d_known : nullptr,
-                       cap ? (const int*)d_cap : nullptr, c->d_wk_bits.p, c->d_wk_q.p, d_hdr);
+    hipLaunchKernelGGL(wlk::k_walk_bfs, dim3(1), dim3(c->walk.threads), lds, c->stream, in, known ? (const int*)d_known : nullptr,
+                       cap ? (const int*)d_cap : nullptr, c->walk.d_bits.p, c->walk.d_q.p, d_hdr);
     c->ctr.kernel_launches++;
     HIPCHK(c, hipGetLastError());
-    c->wk_ms[0] = c->wk_ms[1] = c->wk_ms[2] = 0;
-    if (prof) { HIPCHK(c, hipStreamSynchronize(c->stream)); c->wk_ms[0] = ms_since(t0); t0 = std::chrono::steady_clock::now(); }
+    c->walk.ms[0] = c->walk.ms[1] = c->walk.ms[2] = 0;
+    if (prof) { HIPCHK(c, hipStreamSynchronize(c->stream)); c->walk.ms[0] = ms_since(t0); t0 = std::chrono::steady_clock::now(); }
     if (with_list) {
-        hipLaunchKernelGGL(wlk::k_walk_list, dim3(1), dim3(wlk::LIST_THREADS), 0, c->stream, (const unsigned*)c->d_wk_bits.p, (int)head, d_hdr, c->d_wk_list.p);
+        hipLaunchKernelGGL(wlk::k_walk_list, dim3(1), dim3(wlk::LIST_THREADS), 0, c->stream, (const unsigned*)c->walk.d_bits.p, (int)head, d_hdr, c->walk.d_list.p);
         c->ctr.kernel_launches++;
         HIPCHK(c, hipGetLastError());
     }
     int32_t hdr[wlk::H_WORDS] = {0};
     HIPCHK(c, hipMemcpyAsync(hdr, d_hdr, sizeof hdr, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (prof) c->wk_ms[with_list ? 1 : 0] += ms_since(t0);
+    if (prof) c->walk.ms[with_list ? 1 : 0] += ms_since(t0);
     if (hdr[wlk::H_ERR] || hdr[wlk::H_COUNT] < 1 || hdr[wlk::H_COUNT] > head + 1) {
         c->poisoned = true;
         return fail(c, SW_EIO, "walk from head %lld: error %d after %d levels, %d events (a parent or creator table entry out of range, or the queue overran)",
                     (long long)head, hdr[wlk::H_ERR], hdr[wlk::H_LEVELS], hdr[wlk::H_COUNT]);
     }
-    c->wk_levels = hdr[wlk::H_LEVELS];
+    c->walk.levels = hdr[wlk::H_LEVELS];
     *total = hdr[wlk::H_COUNT];
     return SW_OK;
 }
 
 // the gather of `total` slots behind walk_run's list, on the context's stream (asynchronous)
 int walk_gather(sw_ctx* c, int64_t total, const ExportArrays& o) {
-    const gsp::ExportIn in{nullptr, nullptr, nullptr, c->d_sp.p, c->d_op.p, c->d_id.p, c->d_sig.p, (const unsigned long long*)c->d_t.p};
+    const gsp::ExportIn in{nullptr, nullptr, nullptr, c->d_sp.p, c->d_op.p, c->ids.d_id.p, c->d_sig.p, (const unsigned long long*)c->d_t.p};
     const gsp::ExportOut out{o.id, o.sp_id, o.op_id, o.arity, o.creator, (unsigned long long*)o.t, o.sig, o.event};
-    const int G = c->export_lanes;
+    const int G = c->xp.lanes;
     const dim3 grid((unsigned)std::min<int64_t>(2048, (total * G + wlk::GATHER_THREADS - 1) / wlk::GATHER_THREADS)), block(wlk::GATHER_THREADS);
-    const int* list = c->d_wk_list.p;
+    const int* list = c->walk.d_list.p;
     const int* cr = c->d_cr.p;
     if (G == 4) hipLaunchKernelGGL(wlk::k_walk_gather<4>, grid, block, 0, c->stream, in, out, list, cr, (int)total);
     else if (G == 8) hipLaunchKernelGGL(wlk::k_walk_gather<8>, grid, block, 0, c->stream, in, out, list, cr, (int)total);
@@ -6974,7 +6975,7 @@ int sw_get_fork_trunks(sw_ctx* c, int32_t* trunk_out) {
     HIPCHK(c, hipSetDevice(c->device));
     CHK(fork_trunks(c));
     std::vector<int32_t> tmp(c->npad);
-    HIPCHK(c, hipMemcpyAsync(tmp.data(), c->d_wk_trunk.p, (size_t)c->npad * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(tmp.data(), c->walk.d_trunk.p, (size_t)c->npad * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     std::copy(tmp.begin(), tmp.begin() + c->n, trunk_out);
     return SW_OK;
@@ -6991,10 +6992,10 @@ int sw_sync_walk(sw_ctx* c, int64_t head, const int32_t* known, const int32_t* c
     CHK(walk_run(c, head, known, cap, hipMemcpyHostToDevice, cap_events > 0, &total));
     *n_out = total;
     if (total > cap_events) return fail(c, SW_ERANGE, "sw_sync_walk: %lld events, capacity %lld (nothing written)", (long long)total, (long long)cap_events);
-    HIPCHK(c, hipMemcpyAsync(events_out, c->d_wk_list.p, (size_t)total * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
+    HIPCHK(c, hipMemcpyAsync(events_out, c->walk.d_list.p, (size_t)total * sizeof(int32_t), hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    c->wk_calls++;
-    c->wk_events += total;
+    c->walk.calls++;
+    c->walk.events += total;
     return SW_OK;
 }
 
@@ -7022,9 +7023,9 @@ int sw_export_walk_device(sw_ctx* c, int64_t head, const int32_t* d_known, const
     const auto t0 = std::chrono::steady_clock::now();
     CHK(walk_gather(c, total, ExportArrays{d_id32, d_sp_id32, d_op_id32, d_arity, d_creator, d_t, d_sig64, d_event}));
     CHK(bracket.leave());   // whatever the caller enqueues next reads complete arrays
-    if (c->profiling) { HIPCHK(c, hipStreamSynchronize(c->stream)); c->wk_ms[2] = ms_since(t0); }
-    c->wk_calls++;
-    c->wk_events += total;
+    if (c->profiling) { HIPCHK(c, hipStreamSynchronize(c->stream)); c->walk.ms[2] = ms_since(t0); }
+    c->walk.calls++;
+    c->walk.events += total;
     return SW_OK;
 }
 
@@ -7047,10 +7048,10 @@ int sw_export_walk(sw_ctx* c, int64_t head, const int32_t* known, const int32_t*
     Stage st;
     CHK(export_scratch(c, total, t != nullptr, sig64 != nullptr, event != nullptr, &d, &st, ExportArrays{id32, sp_id32, op_id32, arity, creator, t, sig64, event}));
     CHK(walk_gather(c, total, d));
-    CHK(stage_down(c, st, c->d_xp_out.p));
-    if (c->profiling) c->wk_ms[2] = ms_since(t0);
-    c->wk_calls++;
-    c->wk_events += total;
+    CHK(stage_down(c, st, c->xp.d_out.p));
+    if (c->profiling) c->walk.ms[2] = ms_since(t0);
+    c->walk.calls++;
+    c->walk.events += total;
     return SW_OK;
 }
 
@@ -7070,16 +7071,16 @@ int sw_sync_pull_walk(sw_ctx* dst, int64_t dst_head, sw_ctx* src, int64_t src_he
     int64_t total = 0;
     ExportArrays d{};
     int rc = use_trunks ? fork_trunks(src) : SW_OK;
-    if (rc == SW_OK) rc = walk_run(src, src_head, dst->d_q.p, use_trunks ? src->d_wk_trunk.p : nullptr, hipMemcpyDeviceToDevice, true, &total);
+    if (rc == SW_OK) rc = walk_run(src, src_head, dst->d_q.p, use_trunks ? src->walk.d_trunk.p : nullptr, hipMemcpyDeviceToDevice, true, &total);
     if (rc != SW_OK) { dst->err = src->err; return rc; }
     if (total > 0x3fffffffll || dst->N + total > 0x7ffffff0ll) return fail(dst, SW_ERANGE, "%s: more than 2^31 events", what);
     const auto t0 = std::chrono::steady_clock::now();
     rc = export_scratch(src, total, true, true, data != 0, &d);
     if (rc == SW_OK) rc = walk_gather(src, total, d);
     if (rc != SW_OK) { dst->err = src->err; return rc; }
-    if (src->profiling) { HIPCHK(src, hipStreamSynchronize(src->stream)); src->wk_ms[2] = ms_since(t0); }
-    src->wk_calls++;
-    src->wk_events += total;
+    if (src->profiling) { HIPCHK(src, hipStreamSynchronize(src->stream)); src->walk.ms[2] = ms_since(t0); }
+    src->walk.calls++;
+    src->walk.events += total;
     if (n_sent) *n_sent = total;
     // ---- 3. the rest as in sw_sync_pull_data / sw_sync_pull_validated / sw_sync_pull
     return pull_finish(dst, src, total, d, validate != 0, data != 0, what, n_valid, n_stored);
@@ -7087,11 +7088,48 @@ int sw_sync_pull_walk(sw_ctx* dst, int64_t dst_head, sw_ctx* src, int64_t src_he
 
 int sw_get_walk_stats(sw_ctx* c, int64_t* calls, int64_t* events, int64_t* levels, double* phase_ms) {
     if (!c) return SW_EINVAL;
-    if (calls) *calls = c->wk_calls;
-    if (events) *events = c->wk_events;
-    if (levels) *levels = c->wk_levels;
-    if (phase_ms) for (int i = 0; i < 3; ++i) phase_ms[i] = c->wk_ms[i];
+    if (calls) *calls = c->walk.calls;
+    if (events) *events = c->walk.events;
+    if (levels) *levels = c->walk.levels;
+    if (phase_ms) for (int i = 0; i < 3; ++i) phase_ms[i] = c->walk.ms[i];
     return SW_OK;
+}
+
+int sw_sync_pull(sw_ctx* dst, int64_t dst_head, sw_ctx* src, int64_t src_head, int64_t* n_sent, int64_t* n_stored) {
+    if (!dst || !src) return SW_EINVAL;
+    if (n_sent) *n_sent = 0;
+    if (n_stored) *n_stored = 0;
+    const char* what = "sw_sync_pull";
+    CHK(pull_pre(dst, dst_head, src, false, false, what));
+    if (const int rc = export_pre(src, src_head, "sw_sync_pull (peer)"); rc != SW_OK) { dst->err = src->err; return rc; }
+    // ---- 1. what dst knows at its head (swirld.py:125-126), left in its own scratch; src's stream waits for it
+    CHK(pull_begin(dst, dst_head, src, false, false, what));
+    // ---- 2. src: ranges, count (its one synchronisation: dst's heights have been consumed by then), gather into its own scratch
+    int64_t total = 0;
+    ExportArrays d{};
+    CHK(pull_ranges(dst, src, src_head, false, what, &total, &d));
+    if (n_sent) *n_sent = total;
+    // ---- 3. dst ingests (Node.sync's loop, swirld.py:130-136), its stream ordered behind src's
+    return pull_finish(dst, src, total, d, false, false, what, nullptr, n_stored);
+}
+
+int sw_sync_pull_validated(sw_ctx* dst, int64_t dst_head, sw_ctx* src, int64_t src_head, int64_t* n_sent, int64_t* n_valid, int64_t* n_stored) {
+    if (!dst || !src) return SW_EINVAL;
+    const char* what = "sw_sync_pull_validated";
+    if (n_sent) *n_sent = 0;
+    if (n_valid) *n_valid = 0;
+    if (n_stored) *n_stored = 0;
+    CHK(pull_pre(dst, dst_head, src, true, false, what));
+    if (const int rc = export_pre(src, src_head, "sw_sync_pull_validated (peer)"); rc != SW_OK) { dst->err = src->err; return rc; }
+    // ---- 1. and 2. as in sw_sync_pull: dst's known heights, src's ranges, count and gather
+    CHK(pull_begin(dst, dst_head, src, true, false, what));
+    int64_t total = 0;
+    ExportArrays d{};
+    CHK(pull_ranges(dst, src, src_head, false, what, &total, &d));
+    if (n_sent) *n_sent = total;
+    // ---- 3. and 4. dst, its stream ordered behind src's: the signed bytes (data None: the context stores no event data), the
+    // verdicts by dst's OWN keys and event class, and the ingest of what is valid (Node.sync's loop, swirld.py:130-136)
+    return pull_finish(dst, src, total, d, true, false, what, n_valid, n_stored);
 }
 
 int sw_sync_pull_data(sw_ctx* dst, int64_t dst_head, sw_ctx* src, int64_t src_head, int validate, int64_t* n_sent, int64_t* n_valid, int64_t* n_stored) {
@@ -7114,12 +7152,12 @@ int sw_sync_pull_data(sw_ctx* dst, int64_t dst_head, sw_ctx* src, int64_t src_he
 
 int sw_get_data_stats(sw_ctx* c, int64_t* events, int64_t* bytes, int64_t* store_calls, int64_t* gather_calls, int64_t* gather_bytes, double* phase_ms) {
     if (!c) return SW_EINVAL;
-    if (events) *events = c->n_data;
-    if (bytes) *bytes = c->data_used;
-    if (store_calls) *store_calls = c->dt_store_calls;
-    if (gather_calls) *gather_calls = c->dt_gather_calls;
-    if (gather_bytes) *gather_bytes = c->dt_gather_bytes;
-    if (phase_ms) for (int i = 0; i < 2; ++i) phase_ms[i] = c->dt_ms[i];
+    if (events) *events = c->data.n_data;
+    if (bytes) *bytes = c->data.used;
+    if (store_calls) *store_calls = c->data.store_calls;
+    if (gather_calls) *gather_calls = c->data.gather_calls;
+    if (gather_bytes) *gather_bytes = c->data.gather_bytes;
+    if (phase_ms) for (int i = 0; i < 2; ++i) phase_ms[i] = c->data.ms[i];
     return SW_OK;
 }
 
@@ -7137,7 +7175,7 @@ struct WireArrays {   // what the message writer reads, every array in device me
     const uint8_t* data_none;
 };
 
-int wire_pre_len(const sw_ctx* c) { return (int)(c->pk_mod.size() + c->pk_qual.size() + 10); }
+int wire_pre_len(const sw_ctx* c) { return (int)(c->pack.mod.size() + c->pack.qual.size() + 10); }
 int64_t wire_base(const sw_ctx* c, int64_t K) { return (int64_t)wire_pre_len(c) + 8 + 8 * (K + 1) + wir::HEAD_PART; }
 int64_t wire_bound(const sw_ctx* c, int64_t K, int64_t data_bytes) { return wire_base(c, K) + K * wir::REC_MAX + data_bytes + 3; }
 
@@ -7145,40 +7183,40 @@ struct WireSet { unsigned char* pre; unsigned char* skeys; int32_t* sperm; wir::
 WireSet wire_set(const sw_ctx* c) {
     Carve cv;
     const size_t o_pre = cv.take(wir::PRE_MAX), o_keys = cv.take((size_t)c->n * 32), o_perm = cv.take((size_t)c->n * 4), o_res = cv.take(64);
-    unsigned char* B = c->d_wr_set.p;
+    unsigned char* B = c->wire.d_set.p;
     return WireSet{B + o_pre, B + o_keys, (int32_t*)(B + o_perm), (wir::i64*)(B + o_res)};
 }
 
 // the prefix under the context's event class and the sorted key table, in device memory: rebuilt when either has changed
 int wire_settings(sw_ctx* c) {
-    CHK(dgrow(c, c->d_wr_set, (size_t)wir::PRE_MAX + (size_t)c->n * 36 + 4 * 256 + 64, 0));
+    CHK(dgrow(c, c->wire.d_set, (size_t)wir::PRE_MAX + (size_t)c->n * 36 + 4 * 256 + 64, 0));
     const WireSet ws = wire_set(c);
-    const bool pre_stale = c->wr_mod != c->pk_mod || c->wr_qual != c->pk_qual, keys_stale = c->wr_keys != c->vkeys;
+    const bool pre_stale = c->wire.mod != c->pack.mod || c->wire.qual != c->pack.qual, keys_stale = c->wire.keys != c->val.keys;
     if (!pre_stale && !keys_stale) return SW_OK;
     HIPCHK(c, hipStreamSynchronize(c->stream));   // an earlier call may still be reading the old settings, or copying them
     if (pre_stale) {
-        std::vector<uint8_t>& h = c->wr_pre;
+        std::vector<uint8_t>& h = c->wire.pre;
         h.assign({0x80, 0x04});
-        for (const std::string* s : {&c->pk_mod, &c->pk_qual}) {
+        for (const std::string* s : {&c->pack.mod, &c->pack.qual}) {
             h.push_back(0x8c);
             h.push_back((uint8_t)s->size());
             h.insert(h.end(), s->begin(), s->end());
         }
         for (const uint8_t b : {0x93, 0x94, 0x30, 0x8e}) h.push_back(b);
         HIPCHK(c, hipMemcpyAsync(ws.pre, h.data(), h.size(), hipMemcpyHostToDevice, c->stream));
-        c->wr_mod = c->pk_mod;
-        c->wr_qual = c->pk_qual;
+        c->wire.mod = c->pack.mod;
+        c->wire.qual = c->pack.qual;
     }
     if (keys_stale) {
-        const int n = c->vkeys.empty() ? 0 : c->n;
-        c->wr_skeys.assign((size_t)c->n * 32, 0);
-        c->wr_sperm.assign((size_t)c->n, -1);
+        const int n = c->val.keys.empty() ? 0 : c->n;
+        c->wire.skeys.assign((size_t)c->n * 32, 0);
+        c->wire.sperm.assign((size_t)c->n, -1);
         if (n) {
-            wir::sort_keys(c->vkeys.data(), n, c->wr_skeys.data(), c->wr_sperm.data());
-            HIPCHK(c, hipMemcpyAsync(ws.skeys, c->wr_skeys.data(), (size_t)n * 32, hipMemcpyHostToDevice, c->stream));
-            HIPCHK(c, hipMemcpyAsync(ws.sperm, c->wr_sperm.data(), (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
+            wir::sort_keys(c->val.keys.data(), n, c->wire.skeys.data(), c->wire.sperm.data());
+            HIPCHK(c, hipMemcpyAsync(ws.skeys, c->wire.skeys.data(), (size_t)n * 32, hipMemcpyHostToDevice, c->stream));
+            HIPCHK(c, hipMemcpyAsync(ws.sperm, c->wire.sperm.data(), (size_t)n * 4, hipMemcpyHostToDevice, c->stream));
         }
-        c->wr_keys = c->vkeys;
+        c->wire.keys = c->val.keys;
     }
     return SW_OK;
 }
@@ -7201,13 +7239,13 @@ int wire_pack_launch(sw_ctx* c, int64_t K, const WireArrays& a, uint8_t* d_msg, 
     const int64_t tiles = (K + pck::TILE - 1) / pck::TILE;
     Carve cv;
     const size_t o_off = cv.take((size_t)(K + 1) * 8), o_ts = cv.take((size_t)(tiles + 1) * 8), o_bad = cv.take(8);
-    CHK(dgrow(c, c->d_wr, cv.off + 256, 0));
-    unsigned char* B = c->d_wr.p;
+    CHK(dgrow(c, c->wire.d, cv.off + 256, 0));
+    unsigned char* B = c->wire.d.p;
     pck::i64* off = (pck::i64*)(B + o_off);
     pck::u64* bad = (pck::u64*)(B + o_bad);
     const WireSet ws = wire_set(c);
     const wir::WireIn w{pck::PackIn{a.sp_id, a.op_id, a.arity, a.creator, (const pck::u64*)a.t, a.sig, a.data, (const pck::i64*)a.data_off, (pck::i64)a.data_bytes,
-                                    a.data_none, (const unsigned char*)c->d_vkeys.p, ws.pre, wire_pre_len(c), c->n},
+                                    a.data_none, (const unsigned char*)c->val.d_keys.p, ws.pre, wire_pre_len(c), c->n},
                         a.id, a.head};
     HIPCHK(c, hipMemsetAsync(bad, 0xff, 8, c->stream));
     if (K > 0) {
@@ -7216,22 +7254,22 @@ int wire_pack_launch(sw_ctx* c, int64_t K, const WireArrays& a, uint8_t* d_msg, 
     }
     wire_scan(c, K, off, (pck::i64*)(B + o_ts));
     const int64_t chunks = (bound + 15) / 16;
-    const int64_t blocks = std::max<int64_t>(1, std::min<int64_t>(c->wire_blocks, (chunks + wir::WRITE_THREADS - 1) / wir::WRITE_THREADS));
+    const int64_t blocks = std::max<int64_t>(1, std::min<int64_t>(c->wire.blocks, (chunks + wir::WRITE_THREADS - 1) / wir::WRITE_THREADS));
     const int64_t trips = (chunks + blocks * wir::WRITE_THREADS - 1) / (blocks * wir::WRITE_THREADS);
     hipLaunchKernelGGL(wir::k_wire_write, dim3((unsigned)blocks), dim3(wir::WRITE_THREADS), 0, c->stream, w, (pck::i64)K, (const pck::i64*)off,
                        (pck::i64)wire_base(c, K), (const pck::u64*)bad, d_msg, (pck::i64*)d_msg_len, (pck::i64)trips);
     c->ctr.kernel_launches++;
     HIPCHK(c, hipGetLastError());
     if (d_bad_out) *d_bad_out = bad;
-    c->wr_pack_calls++;
-    c->wr_pack_events += K;
+    c->wire.pack_calls++;
+    c->wire.pack_events += K;
     return SW_OK;
 }
 
 // what both forms of sw_pack_message check before anything else
 int wire_pack_pre(sw_ctx* c, int64_t K, const WireArrays& a, const void* msg, const char* what) {
     if (c->poisoned) return fail(c, SW_EIO, "context unusable after an earlier device failure");
-    if (c->vkeys.empty()) return fail(c, SW_ENOTSUP, "%s: no member keys (sw_set_member_keys first)", what);
+    if (c->val.keys.empty()) return fail(c, SW_ENOTSUP, "%s: no member keys (sw_set_member_keys first)", what);
     if (K < 0 || a.data_bytes < 0) return fail(c, SW_EINVAL, "%s: negative count or length", what);
     if (K > 0x7fffffff) return fail(c, SW_ERANGE, "%s: more than 2^31 events", what);
     if (!a.head || !msg) return fail(c, SW_EINVAL, "%s: NULL head or message buffer", what);
@@ -7257,18 +7295,18 @@ int wire_unpack_run(sw_ctx* c, const uint8_t* d_msg, int64_t msg_bytes, int64_t 
     *n_events = -1;
     *n_data = 0;
     CHK(wire_settings(c));
-    c->wr_unpack_calls++;
+    c->wire.unpack_calls++;
     const int pre_len = wire_pre_len(c);
-    if (msg_bytes < pre_len + 8) { c->wr_refused++; return SW_OK; }
+    if (msg_bytes < pre_len + 8) { c->wire.refused++; return SW_OK; }
     const WireSet ws = wire_set(c);
-    const wir::ReadIn in{d_msg, (wir::i64)msg_bytes, ws.pre, pre_len, ws.skeys, ws.sperm, c->vkeys.empty() ? 0 : c->n};
+    const wir::ReadIn in{d_msg, (wir::i64)msg_bytes, ws.pre, pre_len, ws.skeys, ws.sperm, c->val.keys.empty() ? 0 : c->n};
     hipLaunchKernelGGL(wir::k_wire_header, dim3(1), dim3(256), 0, c->stream, in, ws.res);
     c->ctr.kernel_launches++;
     HIPCHK(c, hipGetLastError());
     long long K = -1;
     HIPCHK(c, hipMemcpyAsync(&K, ws.res, 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (K < 0) { c->wr_refused++; return SW_OK; }
+    if (K < 0) { c->wire.refused++; return SW_OK; }
     if (K > cap_events) {
         *n_events = K;
         *n_data = msg_bytes - wire_base(c, K) - 3 - K * wir::REC_MIN;
@@ -7278,8 +7316,8 @@ int wire_unpack_run(sw_ctx* c, const uint8_t* d_msg, int64_t msg_bytes, int64_t 
     const int64_t tiles = (K + pck::TILE - 1) / pck::TILE;
     Carve cv;
     const size_t o_ts = cv.take((size_t)(tiles + 1) * 8), o_src = cv.take((size_t)K * 8);
-    CHK(dgrow(c, c->d_wr, cv.off + 256, 0));
-    unsigned char* B = c->d_wr.p;
+    CHK(dgrow(c, c->wire.d, cv.off + 256, 0));
+    unsigned char* B = c->wire.d.p;
     const wir::ReadOut ro{o.head, o.id, o.sp_id, o.op_id, o.arity, o.creator, (wir::u64*)o.t, o.sig, (wir::i64*)o.data_off, o.data_none, (wir::i64*)(B + o_src)};
     wir::i64* flag = ws.res + 1;
     hipLaunchKernelGGL(wir::k_wire_table, dim3((unsigned)((K + 256) / 256)), dim3(256), 0, c->stream, in, (wir::i64)K, o.head, flag);
@@ -7298,11 +7336,11 @@ int wire_unpack_run(sw_ctx* c, const uint8_t* d_msg, int64_t msg_bytes, int64_t 
     long long v[2] = {-1, 0};
     HIPCHK(c, hipMemcpyAsync(v, ws.res + 2, 16, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (v[0] < 0) { c->wr_refused++; return SW_OK; }
+    if (v[0] < 0) { c->wire.refused++; return SW_OK; }
     *n_events = K;
     *n_data = v[1];
     if (v[1] > cap_data) return fail(c, SW_ERANGE, "%s: %lld data bytes in the message, capacity %lld (no data written)", what, v[1], (long long)cap_data);
-    c->wr_unpack_events += K;
+    c->wire.unpack_events += K;
     return SW_OK;
 }
 
@@ -7318,20 +7356,20 @@ int wire_unpack_pre(sw_ctx* c, const void* msg, int64_t msg_bytes, int64_t cap_e
     return SW_OK;
 }
 
-// walk, export, data gather and the message of sw_export_message, left in d_wr_out (*d_msg, *len bytes; *K events)
+// walk, export, data gather and the message of sw_export_message, left in wire.d_out (*d_msg, *len bytes; *K events)
 int wire_export_run(sw_ctx* c, int64_t head, const int32_t* known, const int32_t* cap, hipMemcpyKind kind, bool with_data, const char* what, uint8_t** d_msg,
                     int64_t* len, int64_t* n_events) {
     CHK(walk_pre(c, head, true, what));
-    if (c->vkeys.empty()) return fail(c, SW_ENOTSUP, "%s: no member keys (sw_set_member_keys first)", what);
-    if (with_data && c->n_data != c->N)
-        return fail(c, SW_ENOTSUP, "%s: %lld of the %lld stored events have no data entry (sw_set_event_data first)", what, (long long)(c->N - c->n_data), (long long)c->N);
+    if (c->val.keys.empty()) return fail(c, SW_ENOTSUP, "%s: no member keys (sw_set_member_keys first)", what);
+    if (with_data && c->data.n_data != c->N)
+        return fail(c, SW_ENOTSUP, "%s: %lld of the %lld stored events have no data entry (sw_set_event_data first)", what, (long long)(c->N - c->data.n_data), (long long)c->N);
     int64_t total = 0;
     CHK(walk_run(c, head, known, cap, kind, true, &total));
     ExportArrays d{};
     CHK(export_scratch(c, total, true, true, true, &d));
     CHK(walk_gather(c, total, d));
-    c->wk_calls++;
-    c->wk_events += total;
+    c->walk.calls++;
+    c->walk.events += total;
     const size_t k = (size_t)total;
     int64_t dbytes = 0;
     const uint8_t* x_data = nullptr;
@@ -7340,33 +7378,33 @@ int wire_export_run(sw_ctx* c, int64_t head, const int32_t* known, const int32_t
     if (with_data) {
         DataPlan sp{};
         int64_t bad = 0;
-        const dat::SegIn sin{c->d_data.p, (const dat::i64*)c->d_data_off.p, c->d_data_none.p, d.event, (dat::i64)c->n_data, (dat::i64)c->data_used, 1};
+        const dat::SegIn sin{c->data.d_arena.p, (const dat::i64*)c->data.d_off.p, c->data.d_none.p, d.event, (dat::i64)c->data.n_data, (dat::i64)c->data.used, 1};
         CHK(data_scratch(c, total, 0, 0, &sp));
         CHK(data_plan(c, total, sin, sp, &dbytes, &bad));
         if (bad) return fail(c, SW_EIO, "%s: %lld exported events without data (internal error)", what, (long long)bad);
         Carve sv;
         const size_t s_d = sv.take((size_t)dbytes + 16), s_off = sv.take((k + 1) * 8), s_n = sv.take(k);
-        CHK(dgrow(c, c->d_dt_out, sv.off + 256, 0));
-        unsigned char* S = c->d_dt_out.p;
+        CHK(dgrow(c, c->data.d_out, sv.off + 256, 0));
+        unsigned char* S = c->data.d_out.p;
         CHK(data_copy(c, total, sin, sp, dbytes, S + s_d, 0, 0, (int64_t*)(S + s_off), S + s_n));
-        c->dt_gather_calls++;
-        c->dt_gather_bytes += dbytes;
+        c->data.gather_calls++;
+        c->data.gather_bytes += dbytes;
         x_data = S + s_d;
         x_off = (const int64_t*)(S + s_off);
         x_none = S + s_n;
     }
     const int64_t bound = wire_bound(c, total, dbytes);
-    CHK(dgrow(c, c->d_wr_out, (size_t)bound + 256, 0));
+    CHK(dgrow(c, c->wire.d_out, (size_t)bound + 256, 0));
     CHK(wire_settings(c));
     int64_t* d_len = (int64_t*)(wire_set(c).res + 4);
-    CHK(wire_pack_launch(c, total, WireArrays{c->d_id.p + (size_t)head * 32, d.id, d.sp_id, d.op_id, d.arity, d.creator, d.t, d.sig, x_data, x_off, dbytes, x_none},
-                         c->d_wr_out.p, bound, d_len, nullptr));
+    CHK(wire_pack_launch(c, total, WireArrays{c->ids.d_id.p + (size_t)head * 32, d.id, d.sp_id, d.op_id, d.arity, d.creator, d.t, d.sig, x_data, x_off, dbytes, x_none},
+                         c->wire.d_out.p, bound, d_len, nullptr));
     long long l = -1;
     HIPCHK(c, hipMemcpyAsync(&l, d_len, 8, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (l < 0 || l > bound) return fail(c, SW_EIO, "%s: a stored event cannot be encoded (length %lld, bound %lld: internal error)", what, l, (long long)bound);
-    c->wr_pack_bytes += l;
-    *d_msg = c->d_wr_out.p;
+    c->wire.pack_bytes += l;
+    *d_msg = c->wire.d_out.p;
     *len = l;
     *n_events = total;
     return SW_OK;
@@ -7377,20 +7415,20 @@ int wire_export_run(sw_ctx* c, int64_t head, const int32_t* known, const int32_t
 int wire_ingest_run(sw_ctx* c, const uint8_t* d_msg, int64_t msg_bytes, bool validate, bool with_data, const char* what, uint8_t** d_head, int64_t* n_events,
                     int64_t* n_valid, int64_t* n_stored) {
     if (c->poisoned) return fail(c, SW_EIO, "context unusable after an earlier device failure");
-    if (validate && c->vkeys.empty()) return fail(c, SW_ENOTSUP, "%s: no member keys (sw_set_member_keys first)", what);
-    if (c->n_ids != c->N)
-        return fail(c, SW_ENOTSUP, "%s: %lld of the %lld stored events have no id (sw_set_event_ids first)", what, (long long)(c->N - c->n_ids), (long long)c->N);
-    if (with_data && c->n_data != c->N)
-        return fail(c, SW_ENOTSUP, "%s: %lld of the %lld stored events have no data entry (sw_set_event_data first)", what, (long long)(c->N - c->n_data), (long long)c->N);
-    if (validate && !c->h_pkcnt.reserve(1)) return fail(c, SW_ENOMEM, "hipHostMalloc for the count of valid events failed");
+    if (validate && c->val.keys.empty()) return fail(c, SW_ENOTSUP, "%s: no member keys (sw_set_member_keys first)", what);
+    if (c->ids.n_ids != c->N)
+        return fail(c, SW_ENOTSUP, "%s: %lld of the %lld stored events have no id (sw_set_event_ids first)", what, (long long)(c->N - c->ids.n_ids), (long long)c->N);
+    if (with_data && c->data.n_data != c->N)
+        return fail(c, SW_ENOTSUP, "%s: %lld of the %lld stored events have no data entry (sw_set_event_data first)", what, (long long)(c->N - c->data.n_data), (long long)c->N);
+    if (validate && !c->pack.h_cnt.reserve(1)) return fail(c, SW_ENOMEM, "hipHostMalloc for the count of valid events failed");
     CHK(ensure_event(c, c->ev_user));
     const int64_t kcap = std::min<int64_t>(msg_bytes / wir::REC_MIN, 0x3fffffff), dcap = msg_bytes;
     const size_t k = (size_t)kcap;
     Carve cv;
     const size_t o_head = cv.take(32), o_id = cv.take(k * 32), o_sp = cv.take(k * 32), o_op = cv.take(k * 32), o_ar = cv.take(k), o_cr = cv.take(k * 4);
     const size_t o_t = cv.take(k * 8), o_sig = cv.take(k * 64), o_doff = cv.take((k + 1) * 8), o_dn = cv.take(k), o_d = cv.take((size_t)dcap + 16);
-    CHK(dgrow(c, c->d_wr_out, cv.off + 256, 0));
-    unsigned char* B = c->d_wr_out.p;
+    CHK(dgrow(c, c->wire.d_out, cv.off + 256, 0));
+    unsigned char* B = c->wire.d_out.p;
     const WireOut o{B + o_head, B + o_id, B + o_sp, B + o_op, B + o_ar, (int32_t*)(B + o_cr), (double*)(B + o_t), B + o_sig, B + o_d, (int64_t*)(B + o_doff), B + o_dn};
     int64_t K = -1, dbytes = 0;
     CHK(wire_unpack_run(c, d_msg, msg_bytes, kcap, dcap, o, &K, &dbytes, what));
@@ -7458,7 +7496,7 @@ int sw_pack_message(sw_ctx* c, int64_t K, const uint8_t* head32, const uint8_t* 
     const size_t o_cr = st.in(creator, k * 4), o_t = st.in(t, k * 8), o_sig = st.in(sig64, k * 64), o_doff = st.in(data_off, (k + 1) * 8);
     const size_t o_d = st.in(data, (size_t)data_bytes), o_dn = st.in(data_none, k), o_len = st.scratch(8), o_m = st.out(msg, (size_t)bound, 0);
     unsigned char* B = nullptr;
-    CHK(stage_up(c, c->d_wr_in, st, &B));
+    CHK(stage_up(c, c->wire.d_in, st, &B));
     unsigned long long* d_bad = nullptr;
     CHK(wire_pack_launch(c, K, WireArrays{B + o_head, B + o_id, B + o_sp, B + o_op, B + o_ar, (const int32_t*)(B + o_cr), (const double*)(B + o_t), B + o_sig,
                                           data_off ? B + o_d : nullptr, data_off ? (const int64_t*)(B + o_doff) : nullptr, data_bytes,
@@ -7476,7 +7514,7 @@ int sw_pack_message(sw_ctx* c, int64_t K, const uint8_t* head32, const uint8_t* 
     if (len > msg_cap) return fail(c, SW_ERANGE, "%s: the message has %lld bytes, capacity %lld (nothing written)", what, len, (long long)msg_cap);
     st.out_bytes(msg, (size_t)len);
     CHK(stage_down(c, st, B));
-    c->wr_pack_bytes += len;
+    c->wire.pack_bytes += len;
     return SW_OK;
 }
 
@@ -7521,7 +7559,7 @@ int sw_unpack_message(sw_ctx* c, const uint8_t* msg, int64_t msg_bytes, int64_t 
     const size_t o_op = st.out(op_id32, k * 32, 0), o_ar = st.out(arity, k, 0), o_cr = st.out(creator, k * 4, 0), o_t = st.out(t, k * 8, 0), o_sig = st.out(sig64, k * 64, 0);
     const size_t o_doff = st.out(data_off, (k + 1) * 8, 0), o_dn = st.out(data_none, k, 0), o_d = st.out(data, (size_t)kd + 16, 0);
     unsigned char* B = nullptr;
-    CHK(stage_up(c, c->d_wr_in, st, &B));
+    CHK(stage_up(c, c->wire.d_in, st, &B));
     const WireOut o{B + o_head, B + o_id, B + o_sp, B + o_op, B + o_ar, (int32_t*)(B + o_cr), (double*)(B + o_t), B + o_sig, B + o_d, (int64_t*)(B + o_doff), B + o_dn};
     int64_t K = -1, nd = 0;
     const int rc = wire_unpack_run(c, B + o_msg, msg_bytes, ke, kd, o, &K, &nd, what);
@@ -7585,7 +7623,7 @@ int sw_ingest_message_device(sw_ctx* c, const uint8_t* d_msg, int64_t msg_bytes,
     CHK(wire_ingest_run(c, d_msg, msg_bytes, validate != 0, with_data != 0, what, &d_head, n_events, n_valid, n_stored));
     if (*n_events < 0) return bracket.leave();   // (a refused message: nothing is written, and the caller's stream is handed back)
     if (d_head32_out) HIPCHK(c, hipMemcpyAsync(d_head32_out, d_head, 32, hipMemcpyDeviceToDevice, c->stream));
-    if (d_index_out && *n_events > 0) HIPCHK(c, hipMemcpyAsync(d_index_out, c->d_pl_in.p, (size_t)*n_events * 4, hipMemcpyDeviceToDevice, c->stream));
+    if (d_index_out && *n_events > 0) HIPCHK(c, hipMemcpyAsync(d_index_out, c->ids.d_pl_in.p, (size_t)*n_events * 4, hipMemcpyDeviceToDevice, c->stream));
     return bracket.leave();
 }
 
@@ -7599,25 +7637,25 @@ int sw_ingest_message(sw_ctx* c, const uint8_t* msg, int64_t msg_bytes, int vali
     if (n_stored) *n_stored = 0;
     if (msg_bytes < 0 || (msg_bytes > 0 && !msg)) return fail(c, SW_EINVAL, "%s: NULL message (%lld bytes)", what, (long long)msg_bytes);
     HIPCHK(c, hipSetDevice(c->device));
-    CHK(dgrow(c, c->d_wr_in, (size_t)msg_bytes + 256, 0));
-    if (msg_bytes) HIPCHK(c, hipMemcpyAsync(c->d_wr_in.p, msg, (size_t)msg_bytes, hipMemcpyHostToDevice, c->stream));
+    CHK(dgrow(c, c->wire.d_in, (size_t)msg_bytes + 256, 0));
+    if (msg_bytes) HIPCHK(c, hipMemcpyAsync(c->wire.d_in.p, msg, (size_t)msg_bytes, hipMemcpyHostToDevice, c->stream));
     uint8_t* d_head = nullptr;
-    CHK(wire_ingest_run(c, c->d_wr_in.p, msg_bytes, validate != 0, with_data != 0, what, &d_head, n_events, n_valid, n_stored));
+    CHK(wire_ingest_run(c, c->wire.d_in.p, msg_bytes, validate != 0, with_data != 0, what, &d_head, n_events, n_valid, n_stored));
     if (*n_events < 0) return SW_OK;
     if (head32_out) HIPCHK(c, hipMemcpyAsync(head32_out, d_head, 32, hipMemcpyDeviceToHost, c->stream));
-    if (index_out && *n_events > 0) HIPCHK(c, hipMemcpyAsync(index_out, c->d_pl_in.p, (size_t)*n_events * 4, hipMemcpyDeviceToHost, c->stream));
+    if (index_out && *n_events > 0) HIPCHK(c, hipMemcpyAsync(index_out, c->ids.d_pl_in.p, (size_t)*n_events * 4, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
     return SW_OK;
 }
 
 int sw_get_wire_stats(sw_ctx* c, int64_t* pack_calls, int64_t* pack_events, int64_t* pack_bytes, int64_t* unpack_calls, int64_t* unpack_events, int64_t* refused) {
     if (!c) return SW_EINVAL;
-    if (pack_calls) *pack_calls = c->wr_pack_calls;
-    if (pack_events) *pack_events = c->wr_pack_events;
-    if (pack_bytes) *pack_bytes = c->wr_pack_bytes;
-    if (unpack_calls) *unpack_calls = c->wr_unpack_calls;
-    if (unpack_events) *unpack_events = c->wr_unpack_events;
-    if (refused) *refused = c->wr_refused;
+    if (pack_calls) *pack_calls = c->wire.pack_calls;
+    if (pack_events) *pack_events = c->wire.pack_events;
+    if (pack_bytes) *pack_bytes = c->wire.pack_bytes;
+    if (unpack_calls) *unpack_calls = c->wire.unpack_calls;
+    if (unpack_events) *unpack_events = c->wire.unpack_events;
+    if (refused) *refused = c->wire.refused;
     return SW_OK;
 }
 
@@ -7640,10 +7678,10 @@ struct SignArrays {   // what a sign call reads and writes, every array in devic
 int sign_pre(sw_ctx* c, int64_t K, const void* creator, const void* sp, const void* op, const void* t, const void* data, const void* data_off,
              int64_t data_bytes, const void* data_none, const char* what) {
     if (c->poisoned) return fail(c, SW_EIO, "context unusable after an earlier device failure");
-    if (c->vkeys.empty()) return fail(c, SW_ENOTSUP, "%s: no member keys (sw_set_member_keys first)", what);
-    if (c->sg_has.empty()) return fail(c, SW_ENOTSUP, "%s: no signing keys (sw_set_signing_keys first)", what);
-    if (c->n_ids != c->N)
-        return fail(c, SW_ENOTSUP, "%s: %lld of the %lld stored events have no id (sw_set_event_ids first)", what, (long long)(c->N - c->n_ids), (long long)c->N);
+    if (c->val.keys.empty()) return fail(c, SW_ENOTSUP, "%s: no member keys (sw_set_member_keys first)", what);
+    if (c->sign.has.empty()) return fail(c, SW_ENOTSUP, "%s: no signing keys (sw_set_signing_keys first)", what);
+    if (c->ids.n_ids != c->N)
+        return fail(c, SW_ENOTSUP, "%s: %lld of the %lld stored events have no id (sw_set_event_ids first)", what, (long long)(c->N - c->ids.n_ids), (long long)c->N);
     if (K < 0 || data_bytes < 0) return fail(c, SW_EINVAL, "%s: negative count or length", what);
     if (K > 0x3fffffffll || c->N + K > 0x7ffffff0ll) return fail(c, SW_ERANGE, "%s: more than 2^31 events", what);
     if (K > 0 && (!creator || !sp || !op || !t)) return fail(c, SW_EINVAL, "%s: NULL event arrays", what);
@@ -7658,14 +7696,14 @@ int sign_pre(sw_ctx* c, int64_t K, const void* creator, const void* sp, const vo
 int sign_core(sw_ctx* c, int64_t K, const SignArrays& a, const char* what, int64_t* usable) {
     const bool prof = c->profiling;
     auto t0 = std::chrono::steady_clock::now();
-    c->sg_ms[0] = c->sg_ms[1] = c->sg_ms[2] = 0;
+    c->sign.ms[0] = c->sign.ms[1] = c->sign.ms[2] = 0;
     CHK(pack_header(c));
     const size_t k = (size_t)K;
     Carve cv;
     const size_t o_blk = cv.take(256), o_lvl = cv.take(k * 4), o_cnt = cv.take((k + 2) * 8), o_cur = cv.take(k * 4), o_ev = cv.take(k * 4);
     const size_t o_ts = cv.take(((k + pck::TILE - 1) / pck::TILE + 1) * 8);
-    CHK(dgrow(c, c->d_sg, cv.off + 256, 0));
-    unsigned char* B = c->d_sg.p;
+    CHK(dgrow(c, c->sign.d, cv.off + 256, 0));
+    unsigned char* B = c->sign.d.p;
     unsigned long long* d_v = (unsigned long long*)(B + o_blk);   // [0] verdict, [1] data bytes, then stat[4] as ints
     int* d_stat = (int*)(B + o_blk + 16);
     int* lvl = (int*)(B + o_lvl);
@@ -7675,9 +7713,9 @@ int sign_core(sw_ctx* c, int64_t K, const SignArrays& a, const char* what, int64
     pck::i64* tsum = (pck::i64*)(B + o_ts);
     const int n = c->n;
     const sws::SignIn in{a.creator, a.sp, a.op, (const sws::u64*)a.t, a.data, (const sws::i64*)a.data_off, (sws::i64)a.data_bytes, a.data_none,
-                         (const int*)c->d_cr.p, (const uint8_t*)c->d_id.p, (int)c->N, n, (const uint8_t*)c->d_vkeys.p,
-                         (const uint8_t*)c->d_sg_keys.p + (size_t)n * sizeof(sws::Secret), (const sws::Secret*)c->d_sg_keys.p,
-                         (const swv::niels*)c->d_vtab.p + (size_t)n * swv::ROW, (const uint8_t*)c->d_pk_hdr.p, pack_hdr_len(c)};
+                         (const int*)c->d_cr.p, (const uint8_t*)c->ids.d_id.p, (int)c->N, n, (const uint8_t*)c->val.d_keys.p,
+                         (const uint8_t*)c->sign.d_keys.p + (size_t)n * sizeof(sws::Secret), (const sws::Secret*)c->sign.d_keys.p,
+                         (const swv::niels*)c->val.d_tab.p + (size_t)n * swv::ROW, (const uint8_t*)c->pack.d_hdr.p, pack_hdr_len(c)};
     const sws::SignOut out{a.id, a.sp_id, a.op_id, a.arity, a.sig};
     HIPCHK(c, hipMemsetAsync(B + o_blk, 0, 256, c->stream));
     HIPCHK(c, hipMemsetAsync(B + o_blk, 0xff, 8, c->stream));   // ing::V_NONE
@@ -7720,17 +7758,17 @@ int sign_core(sw_ctx* c, int64_t K, const SignArrays& a, const char* what, int64
     hipLaunchKernelGGL(sws::k_sign_scatter, ev_grid, dim3(256), 0, c->stream, (int)K, (const int*)lvl, (const sws::i64*)cnt, cursor, level_events);
     c->ctr.kernel_launches += 4;
     HIPCHK(c, hipGetLastError());
-    if (prof) { HIPCHK(c, hipStreamSynchronize(c->stream)); c->sg_ms[0] = ms_since(t0); t0 = std::chrono::steady_clock::now(); }
+    if (prof) { HIPCHK(c, hipStreamSynchronize(c->stream)); c->sign.ms[0] = ms_since(t0); t0 = std::chrono::steady_clock::now(); }
     // ---- one launch per level, back to back
     const dim3 lv_grid((unsigned)((widest + 63) / 64));
     for (int l = 0; l < nlev; ++l)
         hipLaunchKernelGGL(sws::k_sign_level, lv_grid, dim3(64), 0, c->stream, in, out, (const sws::i64*)cnt, (const int*)level_events, l);
     c->ctr.kernel_launches += nlev;
     HIPCHK(c, hipGetLastError());
-    if (prof) { HIPCHK(c, hipStreamSynchronize(c->stream)); c->sg_ms[1] = ms_since(t0); }
-    c->sg_calls++;
-    c->sg_events += K;
-    c->sg_levels = nlev;
+    if (prof) { HIPCHK(c, hipStreamSynchronize(c->stream)); c->sign.ms[1] = ms_since(t0); }
+    c->sign.calls++;
+    c->sign.events += K;
+    c->sign.levels = nlev;
     return SW_OK;
 }
 
@@ -7743,7 +7781,7 @@ int sign_device_args(sw_ctx* c, int64_t K, const int32_t* cr, const int32_t* sp,
                                  {cr, k * 4, 4}, {sp, k * 4, 4}, {op, k * 4, 4}, {data, (size_t)data_bytes, 1}, {data_none, k, 1}, {arity, k, 1}});
 }
 
-// the signed arrays of a create call at the front of d_sg_in (the host form stages its inputs behind `end`)
+// the signed arrays of a create call at the front of sign.d_in (the host form stages its inputs behind `end`)
 struct CreateScratch { size_t id, sp, op, ar, sig, end; };
 CreateScratch create_scratch(size_t k) {
     Carve cv;
@@ -7765,27 +7803,27 @@ struct OneSign {
 int sign_one_core(sw_ctx* c, SignArrays a, const char* what, int64_t* usable, OneSign* one, const int32_t** d_op) {
     const bool prof = c->profiling;
     const auto t0 = std::chrono::steady_clock::now();
-    c->sg_ms[0] = c->sg_ms[1] = c->sg_ms[2] = 0;
+    c->sign.ms[0] = c->sign.ms[1] = c->sign.ms[2] = 0;
     CHK(pack_header(c));
-    CHK(dgrow(c, c->d_sg, 512, 0));
-    unsigned char* B = c->d_sg.p;   // [0] verdict, [1] data bytes, [4] the looked-up parent (int), [8 .. 8 + ST_COUNT) stamps
+    CHK(dgrow(c, c->sign.d, 512, 0));
+    unsigned char* B = c->sign.d.p;   // [0] verdict, [1] data bytes, [4] the looked-up parent (int), [8 .. 8 + ST_COUNT) stamps
     unsigned long long* d_v = (unsigned long long*)B;
     int32_t* d_slot = (int32_t*)(B + 32);
     unsigned long long* d_stamps = d_v + 8;
     HIPCHK(c, hipMemsetAsync(B, 0, 256, c->stream));
     HIPCHK(c, hipMemsetAsync(B, 0xff, 8, c->stream));   // ing::V_NONE
     if (one->d_head_id) {
-        hipLaunchKernelGGL(rsv::k_tab_lookup, dim3(1), dim3(64), 0, c->stream, (const int*)c->d_idtab.p, c->n_ids ? c->idtab_log : 0,
-                           (const unsigned char*)c->d_id.p, (const unsigned char*)one->d_head_id, 1, (int*)d_slot);
+        hipLaunchKernelGGL(rsv::k_tab_lookup, dim3(1), dim3(64), 0, c->stream, (const int*)c->ids.d_idtab.p, c->ids.n_ids ? c->ids.idtab_log : 0,
+                           (const unsigned char*)c->ids.d_id.p, (const unsigned char*)one->d_head_id, 1, (int*)d_slot);
         c->ctr.kernel_launches++;
         a.op = d_slot;
     }
     *d_op = a.op;
     const int n = c->n;
     const sws::SignIn in{a.creator, a.sp, a.op, (const sws::u64*)a.t, a.data, (const sws::i64*)a.data_off, (sws::i64)a.data_bytes, a.data_none,
-                         (const int*)c->d_cr.p, (const uint8_t*)c->d_id.p, (int)c->N, n, (const uint8_t*)c->d_vkeys.p,
-                         (const uint8_t*)c->d_sg_keys.p + (size_t)n * sizeof(sws::Secret), (const sws::Secret*)c->d_sg_keys.p,
-                         (const swv::niels*)c->d_vtab.p + (size_t)n * swv::ROW, (const uint8_t*)c->d_pk_hdr.p, pack_hdr_len(c)};
+                         (const int*)c->d_cr.p, (const uint8_t*)c->ids.d_id.p, (int)c->N, n, (const uint8_t*)c->val.d_keys.p,
+                         (const uint8_t*)c->sign.d_keys.p + (size_t)n * sizeof(sws::Secret), (const sws::Secret*)c->sign.d_keys.p,
+                         (const swv::niels*)c->val.d_tab.p + (size_t)n * swv::ROW, (const uint8_t*)c->pack.d_hdr.p, pack_hdr_len(c)};
     const sws::SignOut out{a.id, a.sp_id, a.op_id, a.arity, a.sig};
     hipLaunchKernelGGL(sws::k_sign_check, dim3(1), dim3(256), 0, c->stream, in, 1, d_v, d_v + 1);
     if (prof) hipLaunchKernelGGL(swt::k_sign_one<true>, dim3(1), dim3(swt::LANES), 0, c->stream, in, out, (const unsigned long long*)d_v, d_stamps);
@@ -7811,11 +7849,11 @@ int sign_one_core(sw_ctx* c, SignArrays a, const char* what, int64_t* usable, On
     }
     *usable = (int64_t)rb[1];
     if (prof) {
-        c->sg_ms[1] = ms_since(t0);
-        memcpy(c->tn_stamps, rb + 8, sizeof c->tn_stamps);
-        c->tn_profiled++;
+        c->sign.ms[1] = ms_since(t0);
+        memcpy(c->turn.stamps, rb + 8, sizeof c->turn.stamps);
+        c->turn.profiled++;
     }
-    c->tn_events++;
+    c->turn.events++;
     return SW_OK;
 }
 
@@ -7825,19 +7863,19 @@ int create_core(sw_ctx* c, int64_t K, const int32_t* d_cr, const int32_t* d_sp, 
                 const int64_t* d_off, int64_t data_bytes, const uint8_t* d_none, uint8_t* d_id_out, uint8_t* d_sig_out, const char* what,
                 OneSign* one = nullptr) {
     const int64_t N0 = c->N;
-    const bool with_data = c->n_data == N0;
+    const bool with_data = c->data.n_data == N0;
     const size_t k = (size_t)K;
     // ---- reservations: ids and table, the data store, the signed arrays
     CHK(idindex_reserve(c, N0 + K));
     DataPlan p{};
     if (with_data) {
         CHK(data_scratch(c, K, 0, 0, &p));
-        CHK(data_reserve(c, N0 + K, c->data_used + data_bytes));
+        CHK(data_reserve(c, N0 + K, c->data.used + data_bytes));
     }
     const CreateScratch L = create_scratch(k);
     const size_t o_id = L.id, o_sp = L.sp, o_op = L.op, o_ar = L.ar, o_sig = L.sig;
-    CHK(dgrow(c, c->d_sg_in, L.end + 256, 0));
-    unsigned char* B = c->d_sg_in.p;
+    CHK(dgrow(c, c->sign.d_in, L.end + 256, 0));
+    unsigned char* B = c->sign.d_in.p;
     int64_t usable = 0;
     const SignArrays sa{d_cr, d_sp, d_op, d_t, d_data, d_off, data_bytes, d_none, B + o_id, B + o_sp, B + o_op, B + o_ar, B + o_sig};
     if (one) {   // K == 1: the one-wave signer (turn.hip.h); the other parent may come from the id index, and be absent
@@ -7850,7 +7888,7 @@ int create_core(sw_ctx* c, int64_t K, const int32_t* d_cr, const int32_t* d_sp, 
         return fail(c, SW_EINVAL, "%s: the data ranges hold %lld bytes, the buffer %lld: ranges overlap (nothing stored)", what, (long long)usable, (long long)data_bytes);
     const auto t0 = std::chrono::steady_clock::now();
     // ---- the ids into the (uncommitted) tail and the table: two equal events, or one that is stored already, show here
-    HIPCHK(c, hipMemcpyAsync(c->d_id.p + (size_t)N0 * 32, B + o_id, k * 32, hipMemcpyDeviceToDevice, c->stream));
+    HIPCHK(c, hipMemcpyAsync(c->ids.d_id.p + (size_t)N0 * 32, B + o_id, k * 32, hipMemcpyDeviceToDevice, c->stream));
     int flag = 0;
     CHK(idtab_insert(c, N0, K, &flag));
     if (flag != 0) {
@@ -7869,7 +7907,7 @@ int create_core(sw_ctx* c, int64_t K, const int32_t* d_cr, const int32_t* d_sp, 
         }
         return rc;
     }
-    c->n_ids = N0 + K;
+    c->ids.n_ids = N0 + K;
     // ---- committed
     const auto after = [&]() -> int {
         if (with_data) CHK(data_set_body(c, K, d_data, d_off, data_bytes, d_none, what));
@@ -7880,7 +7918,7 @@ int create_core(sw_ctx* c, int64_t K, const int32_t* d_cr, const int32_t* d_sp, 
     };
     const int rc2 = after();
     if (rc2 != SW_OK) c->poisoned = true;
-    if (c->profiling) c->sg_ms[2] = ms_since(t0);
+    if (c->profiling) c->sign.ms[2] = ms_since(t0);
     return rc2;
 }
 
@@ -7892,7 +7930,7 @@ int sw_set_signing_keys(sw_ctx* c, int64_t K, const int32_t* member, const uint8
     if (!c) return SW_EINVAL;
     const char* what = "sw_set_signing_keys";
     if (c->poisoned) return fail(c, SW_EIO, "context unusable after an earlier device failure");
-    if (c->vkeys.empty()) return fail(c, SW_ENOTSUP, "%s: no member keys (sw_set_member_keys first)", what);
+    if (c->val.keys.empty()) return fail(c, SW_ENOTSUP, "%s: no member keys (sw_set_member_keys first)", what);
     if (K < 0 || K > c->n || (K > 0 && (!member || !seed32))) return fail(c, SW_EINVAL, "%s: bad count or NULL arrays", what);
     if (K == 0) return SW_OK;
     const size_t n = (size_t)c->n, k = (size_t)K;
@@ -7900,22 +7938,22 @@ int sw_set_signing_keys(sw_ctx* c, int64_t K, const int32_t* member, const uint8
     for (int64_t j = 0; j < K; ++j) {
         const int m = member[j];
         if (m < 0 || m >= c->n) return fail(c, SW_EINVAL, "%s: member %d out of range", what, m);
-        if (!c->vusable[(size_t)m]) return fail(c, SW_EINVAL, "%s: member %d has an unusable key", what, m);
+        if (!c->val.usable[(size_t)m]) return fail(c, SW_EINVAL, "%s: member %d has an unusable key", what, m);
         if (seen[(size_t)m]) return fail(c, SW_EINVAL, "%s: member %d given twice", what, m);
         seen[(size_t)m] = 1;
     }
     HIPCHK(c, hipSetDevice(c->device));
-    if (!c->d_sg_keys.p) {
-        CHK(dgrow(c, c->d_sg_keys, n * (sizeof(sws::Secret) + 1), 0));
-        HIPCHK(c, hipMemsetAsync(c->d_sg_keys.p, 0, c->d_sg_keys.cap, c->stream));
+    if (!c->sign.d_keys.p) {
+        CHK(dgrow(c, c->sign.d_keys, n * (sizeof(sws::Secret) + 1), 0));
+        HIPCHK(c, hipMemsetAsync(c->sign.d_keys.p, 0, c->sign.d_keys.cap, c->stream));
     }
     Carve cv;
     const size_t o_m = cv.take(k * 4), o_seed = cv.take(k * 32), o_ok = cv.take(k);
-    CHK(dgrow(c, c->d_sg, cv.off + 256, 0));
-    unsigned char* B = c->d_sg.p;
-    sws::Secret* secret = (sws::Secret*)c->d_sg_keys.p;
-    uint8_t* has = c->d_sg_keys.p + n * sizeof(sws::Secret);
-    const swv::niels* rowB = (const swv::niels*)c->d_vtab.p + n * swv::ROW;
+    CHK(dgrow(c, c->sign.d, cv.off + 256, 0));
+    unsigned char* B = c->sign.d.p;
+    sws::Secret* secret = (sws::Secret*)c->sign.d_keys.p;
+    uint8_t* has = c->sign.d_keys.p + n * sizeof(sws::Secret);
+    const swv::niels* rowB = (const swv::niels*)c->val.d_tab.p + n * swv::ROW;
     std::vector<uint8_t> ok(k);
     // the seeds pass through scratch for the length of this call, and are overwritten before it returns whatever happens
     const auto run = [&]() -> int {
@@ -7923,7 +7961,7 @@ int sw_set_signing_keys(sw_ctx* c, int64_t K, const int32_t* member, const uint8
         HIPCHK(c, hipMemcpyAsync(B + o_seed, seed32, k * 32, hipMemcpyHostToDevice, c->stream));
         const dim3 grid((unsigned)((K + 63) / 64));
         hipLaunchKernelGGL(sws::k_sign_keys, grid, dim3(64), 0, c->stream, (int)K, (const int*)(B + o_m), (const uint8_t*)(B + o_seed),
-                           (const uint8_t*)c->d_vkeys.p, rowB, 0, secret, has, B + o_ok);
+                           (const uint8_t*)c->val.d_keys.p, rowB, 0, secret, has, B + o_ok);
         c->ctr.kernel_launches++;
         HIPCHK(c, hipGetLastError());
         HIPCHK(c, hipMemcpyAsync(ok.data(), B + o_ok, k, hipMemcpyDeviceToHost, c->stream));
@@ -7931,7 +7969,7 @@ int sw_set_signing_keys(sw_ctx* c, int64_t K, const int32_t* member, const uint8
         for (int64_t j = 0; j < K; ++j)
             if (!ok[(size_t)j]) return fail(c, SW_EINVAL, "%s: the seed given for member %d does not derive that member's key (nothing changed)", what, member[j]);
         hipLaunchKernelGGL(sws::k_sign_keys, grid, dim3(64), 0, c->stream, (int)K, (const int*)(B + o_m), (const uint8_t*)(B + o_seed),
-                           (const uint8_t*)c->d_vkeys.p, rowB, 1, secret, has, B + o_ok);
+                           (const uint8_t*)c->val.d_keys.p, rowB, 1, secret, has, B + o_ok);
         c->ctr.kernel_launches++;
         HIPCHK(c, hipGetLastError());
         return SW_OK;
@@ -7940,9 +7978,9 @@ int sw_set_signing_keys(sw_ctx* c, int64_t K, const int32_t* member, const uint8
     (void)hipMemsetAsync(B + o_seed, 0, k * 32, c->stream);
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (rc != SW_OK) return rc;
-    if (c->sg_has.empty()) c->sg_has.assign(n, 0);
-    for (int64_t j = 0; j < K; ++j) c->sg_has[(size_t)member[j]] = 1;
-    c->sg_keysets++;
+    if (c->sign.has.empty()) c->sign.has.assign(n, 0);
+    for (int64_t j = 0; j < K; ++j) c->sign.has[(size_t)member[j]] = 1;
+    c->sign.keysets++;
     return SW_OK;
 }
 
@@ -7955,7 +7993,7 @@ int sw_clear_signing_keys(sw_ctx* c) {
 int sw_get_signing_members(sw_ctx* c, uint8_t* has_key) {
     if (!c) return SW_EINVAL;
     if (!has_key) return fail(c, SW_EINVAL, "sw_get_signing_members: NULL output");
-    for (int m = 0; m < c->n; ++m) has_key[m] = c->sg_has.empty() ? 0 : c->sg_has[(size_t)m];
+    for (int m = 0; m < c->n; ++m) has_key[m] = c->sign.has.empty() ? 0 : c->sign.has[(size_t)m];
     return SW_OK;
 }
 
@@ -7981,7 +8019,7 @@ int sw_sign_events_device(sw_ctx* c, int64_t K, const int32_t* d_creator, const 
 
 namespace {
 
-// the inputs of the host-array forms staged in d_sg_in behind what `st` holds already (the signed arrays); pointers into the
+// the inputs of the host-array forms staged in sign.d_in behind what `st` holds already (the signed arrays); pointers into the
 // staging come back
 struct SignStaged { const int32_t *cr, *sp, *op; const double* t; const uint8_t* data; const int64_t* off; const uint8_t* none; };
 int sign_stage(sw_ctx* c, int64_t K, Stage& st, const int32_t* creator, const int32_t* sp, const int32_t* op, const double* t, const uint8_t* data,
@@ -7990,7 +8028,7 @@ int sign_stage(sw_ctx* c, int64_t K, Stage& st, const int32_t* creator, const in
     const size_t o_cr = st.in(creator, k * 4), o_sp = st.in(sp, k * 4), o_op = st.in(op, k * 4), o_t = st.in(t, k * 8);
     const size_t o_doff = st.in(data_off, (k + 1) * 8), o_d = st.in(data, (size_t)data_bytes), o_dn = st.in(data_none, k);
     unsigned char* B = nullptr;
-    CHK(stage_up(c, c->d_sg_in, st, &B));
+    CHK(stage_up(c, c->sign.d_in, st, &B));
     *s = SignStaged{(const int32_t*)(B + o_cr), (const int32_t*)(B + o_sp), (const int32_t*)(B + o_op), (const double*)(B + o_t),
                     data_off ? B + o_d : nullptr, data_off ? (const int64_t*)(B + o_doff) : nullptr, data_none ? B + o_dn : nullptr};
     return SW_OK;
@@ -8014,7 +8052,7 @@ int sw_sign_events(sw_ctx* c, int64_t K, const int32_t* creator, const int32_t* 
     const size_t o_id = st.out(id32, k * 32), o_spid = st.out(sp_id32, k * 32), o_opid = st.out(op_id32, k * 32), o_ar = st.out(arity, k), o_sig = st.out(sig64, k * 64);
     SignStaged s{};
     CHK(sign_stage(c, K, st, creator, self_parent, other_parent, t, data, data_off, data_bytes, data_none, &s));
-    unsigned char* B = c->d_sg_in.p;
+    unsigned char* B = c->sign.d_in.p;
     int64_t usable = 0;
     CHK(sign_core(c, K, SignArrays{s.cr, s.sp, s.op, s.t, s.data, s.off, data_bytes, s.none, B + o_id, B + o_spid, B + o_opid, B + o_ar, B + o_sig}, what, &usable));
     return stage_down(c, st, B);
@@ -8053,7 +8091,7 @@ int sw_create_events(sw_ctx* c, int64_t K, const int32_t* creator, const int32_t
     SignStaged s{};
     CHK(sign_stage(c, K, st, creator, self_parent, other_parent, t, data, data_off, data_bytes, data_none, &s));
     CHK(create_core(c, K, s.cr, s.sp, s.op, s.t, s.data, s.off, data_bytes, s.none, nullptr, nullptr, what));
-    const unsigned char* B = c->d_sg_in.p;   // (create_core found the buffer large enough: it has not moved)
+    const unsigned char* B = c->sign.d_in.p;   // (create_core found the buffer large enough: it has not moved)
     if (id32) HIPCHK(c, hipMemcpyAsync(id32, B + L.id, k * 32, hipMemcpyDeviceToHost, c->stream));
     if (sig64) HIPCHK(c, hipMemcpyAsync(sig64, B + L.sig, k * 64, hipMemcpyDeviceToHost, c->stream));
     HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -8062,11 +8100,11 @@ int sw_create_events(sw_ctx* c, int64_t K, const int32_t* creator, const int32_t
 
 int sw_get_sign_stats(sw_ctx* c, int64_t* calls, int64_t* events, int64_t* levels, int64_t* key_sets, double* phase_ms) {
     if (!c) return SW_EINVAL;
-    if (calls) *calls = c->sg_calls;
-    if (events) *events = c->sg_events;
-    if (levels) *levels = c->sg_levels;
-    if (key_sets) *key_sets = c->sg_keysets;
-    if (phase_ms) for (int i = 0; i < 3; ++i) phase_ms[i] = c->sg_ms[i];
+    if (calls) *calls = c->sign.calls;
+    if (events) *events = c->sign.events;
+    if (levels) *levels = c->sign.levels;
+    if (key_sets) *key_sets = c->sign.keysets;
+    if (phase_ms) for (int i = 0; i < 3; ++i) phase_ms[i] = c->sign.ms[i];
     return SW_OK;
 }
 
@@ -8098,7 +8136,7 @@ int create_one(sw_ctx* c, int member, int64_t sp, int64_t op, double t, const ui
         CHK(sign_stage(c, 1, plan, &cr, &s, &o, &t, nbytes ? data : nullptr, off, nbytes, &none, &st));
         CHK(create_core(c, 1, st.cr, st.sp, st.op, st.t, st.data, st.off, nbytes, st.none, nullptr, nullptr, what, one));
         if (one->absent) return SW_OK;
-        const unsigned char* B = c->d_sg_in.p;   // (create_core found the buffer large enough: it has not moved)
+        const unsigned char* B = c->sign.d_in.p;   // (create_core found the buffer large enough: it has not moved)
         if (id32_out) HIPCHK(c, hipMemcpyAsync(id32_out, B + L.id, 32, hipMemcpyDeviceToHost, c->stream));
         if (sig64_out) HIPCHK(c, hipMemcpyAsync(sig64_out, B + L.sig, 64, hipMemcpyDeviceToHost, c->stream));
         if (id32_out || sig64_out) HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -8120,7 +8158,7 @@ int sw_create_event(sw_ctx* c, int member, int64_t self_parent, int64_t other_pa
     OneSign one;
     CHK(create_one(c, member, self_parent, other_parent, t, data, data_len, &one, id32_out, sig64_out, "sw_create_event"));
     if (index_out) *index_out = N0;
-    c->tn_calls++;
+    c->turn.calls++;
     return SW_OK;
 }
 
@@ -8141,12 +8179,12 @@ int sw_gossip_turn(sw_ctx* dst, int member, int64_t dst_head, sw_ctx* src, int64
     if (dst->n != src->n) return fail(dst, SW_EINVAL, "%s: %d members here, %d at the peer", what, dst->n, src->n);
     if (dst->poisoned || src->poisoned) return fail(dst, SW_EIO, "context unusable after an earlier device failure");
     if (dst->vm.active || src->vm.active) return fail(dst, SW_ENOTSUP, "%s is not available with the windowed table", what);
-    if (dst->vkeys.empty()) return fail(dst, SW_ENOTSUP, "%s: no member keys (sw_set_member_keys first)", what);
+    if (dst->val.keys.empty()) return fail(dst, SW_ENOTSUP, "%s: no member keys (sw_set_member_keys first)", what);
     if (member < 0 || member >= dst->n) return fail(dst, SW_EINVAL, "%s: member %d out of range", what, member);
-    if (dst->sg_has.empty() || !dst->sg_has[(size_t)member]) return fail(dst, SW_ENOTSUP, "%s: no signing key for member %d (sw_set_signing_keys first)", what, member);
-    if (dst->n_ids != dst->N || src->n_ids != src->N) return fail(dst, SW_ENOTSUP, "%s: the id index of %s is incomplete (sw_set_event_ids first)", what, dst->n_ids != dst->N ? "this context" : "the peer");
-    if (with_data && (dst->n_data != dst->N || src->n_data != src->N))
-        return fail(dst, SW_ENOTSUP, "%s: the data store of %s is incomplete (sw_set_event_data first)", what, dst->n_data != dst->N ? "this context" : "the peer");
+    if (dst->sign.has.empty() || !dst->sign.has[(size_t)member]) return fail(dst, SW_ENOTSUP, "%s: no signing key for member %d (sw_set_signing_keys first)", what, member);
+    if (dst->ids.n_ids != dst->N || src->ids.n_ids != src->N) return fail(dst, SW_ENOTSUP, "%s: the id index of %s is incomplete (sw_set_event_ids first)", what, dst->ids.n_ids != dst->N ? "this context" : "the peer");
+    if (with_data && (dst->data.n_data != dst->N || src->data.n_data != src->N))
+        return fail(dst, SW_ENOTSUP, "%s: the data store of %s is incomplete (sw_set_event_data first)", what, dst->data.n_data != dst->N ? "this context" : "the peer");
     if (dst->divided != dst->N) return fail(dst, SW_EINVAL, "%s: %lld undivided events (sw_divide_rounds first)", what, (long long)(dst->N - dst->divided));
     if (dst_head < 0 || dst_head >= dst->N || dst->cr[(size_t)dst_head] != member)
         return fail(dst, SW_EINVAL, "%s: head %lld is not an event of member %d (swirld.py:86)", what, (long long)dst_head, member);
@@ -8162,10 +8200,10 @@ int sw_gossip_turn(sw_ctx* dst, int member, int64_t dst_head, sw_ctx* src, int64
     CHK(sw_sync_pull_walk(dst, dst_head, src, src_head, trunks, validate, with_data, &res.n_sent, &res.n_valid, &res.n_stored));
     res.stage = SW_TURN_STAGE_PULLED;
     put();
-    dst->tn_turns++;
+    dst->turn.turns++;
     // ---- 2. and 3. the new event on my head and the peer's, whose index comes from the id index on the device
     OneSign one;
-    one.d_head_id = (const uint8_t*)src->d_id.p + (size_t)src_head * 32;
+    one.d_head_id = (const uint8_t*)src->ids.d_id.p + (size_t)src_head * 32;
     const int64_t N_pulled = dst->N;
     CHK(create_one(dst, member, dst_head, -1, t, data, data_len, &one, nullptr, nullptr, what));
     if (!one.absent) res.new_head = N_pulled;
@@ -8190,11 +8228,11 @@ int sw_gossip_turn(sw_ctx* dst, int member, int64_t dst_head, sw_ctx* src, int64
 
 int sw_get_turn_stats(sw_ctx* c, int64_t* create_calls, int64_t* events, int64_t* turns, int64_t* stamped, uint64_t* stamps, double* tick_ns) {
     if (!c) return SW_EINVAL;
-    if (create_calls) *create_calls = c->tn_calls;
-    if (events) *events = c->tn_events;
-    if (turns) *turns = c->tn_turns;
-    if (stamped) *stamped = c->tn_profiled;
-    if (stamps) for (int i = 0; i < swt::ST_COUNT; ++i) stamps[i] = c->tn_stamps[i];
+    if (create_calls) *create_calls = c->turn.calls;
+    if (events) *events = c->turn.events;
+    if (turns) *turns = c->turn.turns;
+    if (stamped) *stamped = c->turn.profiled;
+    if (stamps) for (int i = 0; i < swt::ST_COUNT; ++i) stamps[i] = c->turn.stamps[i];
     if (tick_ns) {
         int khz = 0;
         if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, c->device) != hipSuccess || khz <= 0) { (void)hipGetLastError(); khz = 100000; }
