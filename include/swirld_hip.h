@@ -1082,7 +1082,9 @@ int sw_get_vote_store_stats(sw_ctx* ctx, int64_t* entries, int64_t* capacity, in
  * reference's main-loop step (swirld.py:325-328: divide_rounds(new events), decide_fame(), find_order(new_c)) by one
  * wavefront per hashgraph in ONE launch — the statements of the exact path (csrc/exact.hip.h), so results are the
  * reference's with or without forks.  What a batch does not have: growth (all capacity is fixed at create), mixed member
- * counts, the event-keyed vote log, an id index, gossip, crypto — those remain features of a sw_ctx.
+ * counts, the event-keyed vote log, an id index, gossip between nodes, crypto — those remain features of a sw_ctx.  (What it
+ * does have is a generator of whole gossip histories, sw_synth_batch below: one hashgraph's DAG as sw_synth_hashgraph
+ * draws it, not a network of nodes.)
  *
  * sw_batch_bytes     the device bytes sw_batch_create will allocate (-1 for a shape it refuses: an argument out of range, or
  *                    a total of 2^62 bytes or more — sw_batch_create answers SW_EINVAL to the same shapes): a head of 576 B per
@@ -1145,6 +1147,47 @@ int sw_batch_get_consensus(sw_batch* batch, int64_t b, int r0, int r1, uint8_t* 
 int sw_batch_get_new_rounds(sw_batch* batch, int64_t b, int32_t* out, int cap, int* n_out);
 int sw_batch_get_transactions(sw_batch* batch, int64_t b, int64_t first, int64_t K, int32_t* events, int32_t* round_received,
                               double* consensus_time);
+
+/*
+ * GOSSIP HISTORIES GENERATED ON THE DEVICE (csrc/batch_synth.hip.h).  Instead of generating every hashgraph
+ * on the host (sw_synth_hashgraph), validating and uploading it (sw_batch_append, 88 bytes per event), give a seed and
+ * parameters per hashgraph and let the batch generate its own events, in instalments: one wavefront per participating
+ * hashgraph, one launch and one read-back of 8 bytes per participating hashgraph per call.
+ *   THE INVARIANT: after sw_synth_batch_begin with (seed_b, mode_b, p0_b, p1_b) and any sequence of sw_synth_batch calls
+ * that stored N_b events in total, hashgraph b holds exactly what sw_synth_hashgraph(n_members, N_b, seed_b, mode_b, p0_b,
+ * p1_b, ...) writes — creator, parents, t[i] = (double)i and the 64 signature bytes, bit for bit — with the heights of
+ * swirld.py:117-120 and the per-event defaults of an appended event.  Steps, getters and exports cannot tell the two apart.
+ *
+ * sw_synth_batch_begin      which: NULL = every hashgraph, else which[b] != 0 selects b.  seed: [B] (read where selected).
+ *                           mode / p0 / p1: [B], each nullable (0 / 0.0 / 0.0); meaning and ranges: sw_synth_hashgraph's.
+ *                           SW_EINVAL, nothing changed: NULL seed, a batch of fewer than 2 members, a selected hashgraph
+ *                           that already holds events, a mode outside 0..3.  Again on a hashgraph that is still empty:
+ *                           replaces its parameters.  The first call allocates the generator state, outside
+ *                           sw_batch_bytes: 16 n_members + 160 bytes per hashgraph, its three parts rounded up to 64 B.
+ * sw_synth_batch            hashgraph b generates and stores its next K[b] events (0: none); *total (nullable) = events
+ *                           stored.  SW_EINVAL, nothing stored: NULL K, a negative K[b], K[b] > 0 for a hashgraph without
+ *                           parameters, a first instalment with 0 < K[b] < n_members (the roots come first and together),
+ *                           K[b] > 0 for a hashgraph that has taken a sw_batch_append since begin (the generator's heads no
+ *                           longer describe it).  A frozen hashgraph may still be fed, as by sw_batch_append.  ATOMIC over
+ *                           the batch: a hashgraph that would exceed cap_events, or whose greatest height + 3 would exceed
+ *                           cap_rounds, is SW_ERANGE, the message names it, nothing observable is stored anywhere and no
+ *                           generator advances — the same call repeated with an admissible K gives what it would have
+ *                           given had the refused call never been made.  Every call ends synchronised.
+ * sw_synth_batch_stats      out[4]: sw_synth_batch calls that stored events, events generated, kernel launches (begin's
+ *                           included), refreshes of the append mirror: sw_synth_batch does not copy creators and heights
+ *                           back to the host, so the first sw_batch_append that feeds a hashgraph with generated events
+ *                           reads that hashgraph's two columns from its slab first (counted once per hashgraph and
+ *                           append), then validates and stores exactly as on a host-fed batch.
+ * sw_get_batch_events       the stored events [first, first + K) of hashgraph b as sw_batch_append takes them; every array
+ *                           nullable.  One blocking copy per requested array; SW_ERANGE for a hashgraph or a range outside
+ *                           what is stored.  Any batch, generated or host-fed.
+ */
+int sw_synth_batch_begin(sw_batch* batch, const uint8_t* which, const uint64_t* seed, const int32_t* mode, const double* p0,
+                         const double* p1);
+int sw_synth_batch(sw_batch* batch, const int64_t* K, int64_t* total);
+int sw_synth_batch_stats(sw_batch* batch, int64_t out[4]);
+int sw_get_batch_events(sw_batch* batch, int64_t b, int64_t first, int64_t K, int32_t* creator, int32_t* self_parent,
+                        int32_t* other_parent, double* t, uint8_t* sig64);
 
 /*
  * THE RESULTS OF A WHOLE BATCH IN ONE CALL (csrc/batch_export.hip.h).  The sw_batch_get_* above cost one

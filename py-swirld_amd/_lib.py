@@ -195,6 +195,11 @@ SIGNATURES = {
     "sw_batch_get_consensus": (C.c_int, [_P, C.c_int64, C.c_int, C.c_int, _P]),
     "sw_batch_get_new_rounds": (C.c_int, [_P, C.c_int64, _P, C.c_int, C.POINTER(C.c_int)]),
     "sw_batch_get_transactions": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int64, _P, _P, _P]),
+    # ... their histories generated on the device (csrc/batch_synth.hip.h)
+    "sw_synth_batch_begin": (C.c_int, [_P, _P, _P, _P, _P, _P]),
+    "sw_synth_batch": (C.c_int, [_P, _P, C.POINTER(C.c_int64)]),
+    "sw_synth_batch_stats": (C.c_int, [_P, _P]),
+    "sw_get_batch_events": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int64, _P, _P, _P, _P, _P]),
     # ... and their results, the whole batch per call (csrc/batch_export.hip.h)
     "sw_export_batch_ordered": (C.c_int, [_P, _P, _P, C.c_int64, _P, _P, _P, _P, C.POINTER(C.c_int64)]),
     "sw_export_batch_ordered_device": (C.c_int, [_P, _P, _P, C.c_int64, _P, _P, _P, _P, C.POINTER(C.c_int64), _P]),

@@ -26,6 +26,12 @@ struct sw_batch {
     owned::DBuf<unsigned char> xp_d;               // the plan the kernel reads (rewritten in stream order)
     owned::Event ev_user;                          // between the caller's stream and ours
     int64_t xp_calls = 0, xp_launches = 0, xp_entries = 0, xp_d2h = 0;   // sw_export_batch_stats
+    // generated histories (batch_synth_api.hip.h): the generator state of every hashgraph, made by the first begin
+    owned::DBuf<unsigned char> sy_state;
+    swbs::StateLayout sy_lay{};
+    std::vector<char> sy_has, sy_cur, sy_behind, sy_fed;   // per hashgraph: has parameters; the current copy of its state;
+                                                          // cr / ht mirrors behind the slab; a host append since begin
+    int64_t sy_calls = 0, sy_events = 0, sy_launches = 0, sy_refreshes = 0;   // sw_synth_batch_stats
     const swb::Rec* recs() const { return (const swb::Rec*)(mem.p + lay.recs); }
     unsigned char* seg(int64_t b, int s) const { return mem.p + lay.at((uint64_t)b, s); }
 };
@@ -33,6 +39,8 @@ struct sw_batch {
 namespace {
 
 std::string g_batch_create_error;
+
+int batch_synth_refresh(sw_batch* c, const int64_t* off);   // batch_synth_api.hip.h
 
 int bfail(sw_batch* c, int code, const char* fmt, ...) {
     char buf[512];
@@ -189,6 +197,7 @@ int sw_batch_create(int64_t B, int n_members, const uint64_t* stake, int coin_pe
     c->events.assign((size_t)B, 0); c->divided.assign((size_t)B, 0);
     c->cr.resize((size_t)B); c->ht.resize((size_t)B);
     c->hmax.assign((size_t)B, 0); c->frozen.assign((size_t)B, 0);
+    c->sy_has.assign((size_t)B, 0); c->sy_cur.assign((size_t)B, 0); c->sy_behind.assign((size_t)B, 0); c->sy_fed.assign((size_t)B, 0);
     *out = c;
     return SW_OK;
 }
@@ -207,6 +216,7 @@ int sw_batch_append(sw_batch* c, const int64_t* off, const int32_t* creator, con
     if (total == 0) return SW_OK;
     if (!creator || !self_parent || !other_parent) return bfail(c, SW_EINVAL, "creator / self_parent / other_parent is NULL");
     const int n = c->n;
+    CHK(batch_synth_refresh(c, off));   // generated events are in the slab only: the mirrors of the hashgraphs this call feeds
     std::vector<int32_t> hnew((size_t)total);
     std::vector<int32_t> hmax_new(c->hmax);
     for (int64_t b = 0; b < B; ++b) {
@@ -264,6 +274,7 @@ int sw_batch_append(sw_batch* c, const int64_t* off, const int32_t* creator, con
         c->cr[b].insert(c->cr[b].end(), creator + off[b], creator + off[b + 1]);
         c->ht[b].insert(c->ht[b].end(), hnew.begin() + off[b], hnew.begin() + off[b + 1]);
         c->events[b] += K;
+        c->sy_fed[b] = 1;
     }
     c->hmax.swap(hmax_new);
     return SW_OK;

@@ -1401,6 +1401,7 @@ BatchSummary = collections.namedtuple("BatchSummary", "events divided rounds ord
 BATCH_STAGES = {0: None, 1: "divide", 2: "fame", 3: "order"}
 BatchStepArrays = collections.namedtuple("BatchStepArrays", "took rounds_off rounds tx_off event round_received time n_failed")
 BatchExportStats = collections.namedtuple("BatchExportStats", "calls launches entries d2h_copies")
+BatchSynthStats = collections.namedtuple("BatchSynthStats", "calls events launches mirror_refreshes")
 
 
 class HashgraphBatch:
@@ -1408,7 +1409,10 @@ class HashgraphBatch:
     reference's main-loop step — divide_rounds(new events), decide_fame(), find_order(new_c) — for every hashgraph that
     takes part, one wavefront each, in one launch.  Exact with or without forks.  All capacity is fixed here: cap_events
     events per hashgraph, cap_rounds rounds (0: cap_events + 3, which always suffices; the vote layers take 2 n^2 bytes per
-    round, so lower it where memory matters).  No id index, gossip, crypto or event-keyed vote log: those are Hashgraph's."""
+    round, so lower it where memory matters).  No id index, gossip, crypto or event-keyed vote log: those are Hashgraph's.
+    Events come from the host (append) or are generated on the device: synth_begin(seed, mode, p0, p1) then synth(K), in
+    instalments, leave in hashgraph b exactly what synth_hashgraph(n, N_b, seed_b, ...) returns, bit for bit, without the
+    host generating, validating or uploading an event; events(b) reads stored events back."""
 
     def __init__(self, B, n_members, stake=None, coin_period=6, cap_events=1024, cap_rounds=0, device=0):
         self._L = _lib.load()
@@ -1489,6 +1493,42 @@ class HashgraphBatch:
         if t is not None and t.shape != (total,):
             raise ValueError("t must have off[B] entries")
         self._chk(self._L.sw_batch_append(self._h, _p(off), _p(creator), _p(sp), _p(op), _p(t), _p(sig)))
+
+    def _per_hashgraph(self, v, dtype, what):
+        a = np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype), (self.B,)) if np.ndim(v) == 0 else v, dtype)
+        if a.shape != (self.B,):
+            raise ValueError("%s must be a scalar or have one entry per hashgraph" % what)
+        return a
+
+    def synth_begin(self, seed, mode=0, p0=0.0, p1=0.0, which=None):
+        """Seed and parameters of synth_hashgraph per hashgraph (scalars broadcast over B; which: a mask, None = all).  The
+        selected hashgraphs must be empty; calling again on a still-empty hashgraph replaces its parameters."""
+        w = None if which is None else self._ctl(np.asarray(which) != 0, np.uint8, "which")
+        self._chk(self._L.sw_synth_batch_begin(self._h, _p(w), _p(self._per_hashgraph(seed, np.uint64, "seed")),
+                                               _p(self._per_hashgraph(mode, np.int32, "mode")), _p(self._per_hashgraph(p0, np.float64, "p0")),
+                                               _p(self._per_hashgraph(p1, np.float64, "p1"))))
+
+    def synth(self, K):
+        """Every hashgraph generates and stores its next K[b] events on the device (an int broadcasts; 0: none).  Returns
+        the number of events stored.  Atomic over the batch: beyond cap_events or cap_rounds anywhere nothing is stored."""
+        total = C.c_int64(0)
+        self._chk(self._L.sw_synth_batch(self._h, _p(self._per_hashgraph(K, np.int64, "K")), C.byref(total)))
+        return int(total.value)
+
+    def synth_stats(self):
+        """(synth calls that stored events, events generated, kernel launches, refreshes of the append mirror)."""
+        out = np.zeros(4, np.int64)
+        self._chk(self._L.sw_synth_batch_stats(self._h, _p(out)))
+        return BatchSynthStats(*[int(x) for x in out])
+
+    def events(self, b, first=0, K=None):
+        """The stored events [first, first + K) of hashgraph b as append() takes them: (creator, self_parent, other_parent,
+        t, sig) with sig uint8 [K][64].  Generated or appended."""
+        K = self._events(b) - first if K is None else K
+        cr, sp, op = np.empty(K, np.int32), np.empty(K, np.int32), np.empty(K, np.int32)
+        t, sig = np.empty(K, np.float64), np.empty((K, 64), np.uint8)
+        self._chk(self._L.sw_get_batch_events(self._h, b, first, K, _p(cr), _p(sp), _p(op), _p(t), _p(sig)))
+        return cr, sp, op, t, sig
 
     def step(self, K=None, collect=True):
         """One main-loop step.  K: events to divide per hashgraph (0: it sits the step out), None: all undivided ones.
