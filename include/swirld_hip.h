@@ -1236,6 +1236,71 @@ int sw_export_batch_rounds_device(sw_batch* batch, const int32_t* r0, const int3
                                   int8_t* d_famous, uint8_t* d_consensus, int64_t* total, void* user_stream);
 int sw_export_batch_stats(sw_batch* batch, int64_t out[4]);
 
+/*
+ * GOSSIP NETWORKS IN A BATCH (csrc/batch_network.hip.h).  Consecutive hashgraphs of a batch form a network:
+ * with n = n_members and G = B / n, hashgraph g n + i is node i's VIEW of network g, and one wavefront runs the turns of
+ * one network, one after the other, in one launch — the reference's test(n_nodes, n_turns) (swirld.py:331-345) without a
+ * host between the turns.  Turn (i, j): node i pulls from node j != i what the reference's ask_sync answers (the BFS of
+ * swirld.py:154-159 in view j, pruned by the heights of can_see[head_i]), stores what it does not hold behind its events in
+ * ascending local index of j, creates its event on (head_i, head_j) and runs the main-loop step over all of it (the step of
+ * sw_batch_step, unchanged).  Stored events carry their NETWORK EVENT NUMBER, the creation order inside the network: root
+ * i is number i, turn k creates number n + k, the same in every view.  There is no crypto and there are no ids.
+ *   LIMITS: no forks (every node is honest), no crypto, one turn at a time per network, cap_events bounds the events a
+ * NETWORK creates (n + its turns), not only what a view holds.
+ *   STOPPED networks: a turn whose step freezes the puller's view — where the reference raises and test() dies — stops the
+ * network with status (stage, code, view): SW_BATCH_STAGE_* of the frozen step.  The one deliberate deviation: an imported
+ * event with a parent that resolves neither in the puller's view nor earlier in the import stops the network with
+ * SW_NETWORK_STAGE_BROKEN before the turn stores anything, where the reference skips the invalid event (swirld.py:135);
+ * between honest nodes it does not happen.  A stopped network runs no further turn, in this call or a later one, whatever
+ * the schedule says; the other networks go on.
+ *   THE NETWORK STATE is an allocation of its own, made by the first begin, outside sw_batch_bytes:
+ * align64(128 G) + align64(16 B) + 2 B align64(4 cap_events) bytes (per view the number column and the number -> index
+ * table, per network both generators and the counts).
+ *
+ * sw_network_batch_begin   which: NULL = every network, else which[g] != 0 selects g.  seed: [G] (read where selected).
+ *                          View i stores root i (t = root_t[g][i], NULL: (double)i; signature root_sig64[g][i], NULL: the
+ *                          generated one) and divides it.  SW_EINVAL, nothing changed: B not a multiple of n_members,
+ *                          n_members < 2, a selected network with a non-empty view or a view with generator parameters,
+ *                          views of one network with different stake rows.
+ * sw_network_batch_turns   the explicit schedule, ragged like sw_batch_append: network g runs the turns [off[g], off[g + 1])
+ *                          of puller / peer, with t and sig64 (each nullable) per turn for the created event.
+ * sw_network_batch_run     network g runs its next T[g] turns of the schedule it draws itself: bit for bit what
+ *                          sw_network_batch_turns does with sw_synth_schedule's turns and NULL t / sig64, and prefix-stable:
+ *                          run(T1) then run(T2) equals run(T1 + T2).
+ *                          GENERATED: t = (double)number; the signature of event number e is the words [8 e, 8 e + 8) of
+ *                          sw_synth_hashgraph's signature stream for seed[g] (it advances by 8 words per created event
+ *                          whether or not an explicit signature replaced it).
+ *                          Both forms check everything before anything is enqueued, ATOMIC over the batch.  SW_EINVAL: a
+ *                          network with turns that was never begun, puller == peer, a node outside 0..n_members-1.
+ *                          SW_ERANGE: n_members + turns so far + turns of this call > cap_events, or that + 3 > cap_rounds
+ *                          (conservative: a view never holds more than the network has created).  SW_OK with *n_stopped
+ *                          (nullable) = networks stopped by THIS call.  One launch per 64 turns of the longest network,
+ *                          one read-back per call; the counts, summaries and getters of the views end up exactly as after
+ *                          the equivalent sw_batch_append + sw_batch_step calls.
+ * sw_network_batch_get     out[G][SW_NETWORK_BATCH_WORDS]: begun, turns run, events created, status: stage, code, view (-1).
+ * sw_network_batch_heads   out[B]: the local index of each view's head (-1: not a view of a begun network).
+ * sw_get_network_event_numbers   the network event numbers of the stored events [first, first + K) of view b.
+ * sw_export_network_event_numbers[_device]   the same for every hashgraph at once, ragged, with the control arrays and the
+ *                          refusals of sw_export_batch_events (a hashgraph that is no view has no entries).
+ * sw_network_batch_stats   out[4]: calls that ran turns, turns run, events imported, kernel launches (begin's included).
+ * AFTERWARDS sw_batch_append and sw_synth_batch on a view are SW_EINVAL, sw_batch_step finds nothing undivided there;
+ * hashgraphs of networks that were not begun behave exactly as before.
+ */
+#define SW_NETWORK_BATCH_WORDS 6
+#define SW_NETWORK_STAGE_BROKEN 4
+int sw_network_batch_begin(sw_batch* batch, const uint8_t* which, const uint64_t* seed, const double* root_t, const uint8_t* root_sig64);
+int sw_network_batch_turns(sw_batch* batch, const int64_t* off, const int32_t* puller, const int32_t* peer, const double* t,
+                           const uint8_t* sig64, int64_t* n_stopped);
+int sw_network_batch_run(sw_batch* batch, const int64_t* T, int64_t* n_stopped);
+int sw_network_batch_get(sw_batch* batch, int64_t* out);
+int sw_network_batch_heads(sw_batch* batch, int32_t* out);
+int sw_network_batch_stats(sw_batch* batch, int64_t out[4]);
+int sw_get_network_event_numbers(sw_batch* batch, int64_t b, int64_t first, int64_t K, int32_t* out);
+int sw_export_network_event_numbers(sw_batch* batch, const int64_t* first, const int64_t* count, int64_t cap, int64_t* off, int32_t* numbers,
+                                  int64_t* total);
+int sw_export_network_event_numbers_device(sw_batch* batch, const int64_t* first, const int64_t* count, int64_t cap, int64_t* off,
+                                         int32_t* d_numbers, int64_t* total, void* user_stream);
+
 /* Block until all work queued on the context's stream is complete. */
 int sw_synchronize(sw_ctx* ctx);
 
@@ -1250,6 +1315,12 @@ int sw_synchronize(sw_ctx* ctx);
 int sw_synth_hashgraph(int n, int64_t N, uint64_t seed, int mode, double p0, double p1,
                        int32_t* creator, int32_t* self_parent, int32_t* other_parent,
                        double* t, uint8_t* sig64);
+/*
+ * Host utility (no GPU): the turns [first_turn, first_turn + T) of the schedule a network of n nodes draws for itself
+ * under `seed` (sw_network_batch_run): per turn the puller, uniform in 0..n-1, and its peer, uniform among the others
+ * (swirld.py:342, 323).  SW_EINVAL for n < 2, a negative range, NULL arrays with T > 0.
+ */
+int sw_synth_schedule(int n, uint64_t seed, int64_t first_turn, int64_t T, int32_t* puller, int32_t* peer);
 
 #ifdef __cplusplus
 }

@@ -8,9 +8,9 @@ with `importlib.import_module("py-swirld_amd")` or through the alias module
 `swirld_amd` at the repo root.
 """
 from ._lib import SwirldHipError, LIB_PATH  # noqa: F401
-from .engine import Hashgraph, HashgraphBatch, hash_batch, synth_hashgraph, verify_batch  # noqa: F401
+from .engine import Hashgraph, HashgraphBatch, hash_batch, synth_hashgraph, synth_schedule, verify_batch  # noqa: F401
 from .node import C, Event, Node, VotesUnavailable, majority, test  # noqa: F401
 from .network import DeviceNetwork  # noqa: F401
 
-__all__ = ["Hashgraph", "HashgraphBatch", "synth_hashgraph", "verify_batch", "hash_batch", "SwirldHipError", "LIB_PATH",
+__all__ = ["Hashgraph", "HashgraphBatch", "synth_hashgraph", "synth_schedule", "verify_batch", "hash_batch", "SwirldHipError", "LIB_PATH",
            "Node", "Event", "C", "majority", "test", "VotesUnavailable", "DeviceNetwork"]

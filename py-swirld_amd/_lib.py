@@ -210,6 +210,17 @@ SIGNATURES = {
     "sw_export_batch_rounds": (C.c_int, [_P, _P, _P, C.c_int64, _P, _P, _P, _P, C.POINTER(C.c_int64)]),
     "sw_export_batch_rounds_device": (C.c_int, [_P, _P, _P, C.c_int64, _P, _P, _P, _P, C.POINTER(C.c_int64), _P]),
     "sw_export_batch_stats": (C.c_int, [_P, _P]),
+    # ... and gossip networks of consecutive hashgraphs (csrc/batch_network.hip.h)
+    "sw_network_batch_begin": (C.c_int, [_P, _P, _P, _P, _P]),
+    "sw_network_batch_turns": (C.c_int, [_P, _P, _P, _P, _P, _P, C.POINTER(C.c_int64)]),
+    "sw_network_batch_run": (C.c_int, [_P, _P, C.POINTER(C.c_int64)]),
+    "sw_network_batch_get": (C.c_int, [_P, _P]),
+    "sw_network_batch_heads": (C.c_int, [_P, _P]),
+    "sw_network_batch_stats": (C.c_int, [_P, _P]),
+    "sw_get_network_event_numbers": (C.c_int, [_P, C.c_int64, C.c_int64, C.c_int64, _P]),
+    "sw_export_network_event_numbers": (C.c_int, [_P, _P, _P, C.c_int64, _P, _P, C.POINTER(C.c_int64)]),
+    "sw_export_network_event_numbers_device": (C.c_int, [_P, _P, _P, C.c_int64, _P, _P, C.POINTER(C.c_int64), _P]),
+    "sw_synth_schedule": (C.c_int, [C.c_int, C.c_uint64, C.c_int64, C.c_int64, _P, _P]),
     "sw_set_window": (C.c_int, [_P, C.c_int, C.c_int]),
     "sw_get_window": (C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "sw_set_window_lapse": (C.c_int, [_P, C.c_int64]),

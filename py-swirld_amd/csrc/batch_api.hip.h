@@ -32,6 +32,14 @@ struct sw_batch {
     std::vector<char> sy_has, sy_cur, sy_behind, sy_fed;   // per hashgraph: has parameters; the current copy of its state;
                                                           // cr / ht mirrors behind the slab; a host append since begin
     int64_t sy_calls = 0, sy_events = 0, sy_launches = 0, sy_refreshes = 0;   // sw_synth_batch_stats
+    // gossip networks (batch_network_api.hip.h): the network state, made by the first begin, and the host's copy of its words
+    std::vector<uint32_t> stake_rows;              // [B][npad] as uploaded at create: views of one network share a stake row
+    owned::DBuf<unsigned char> nw_state;
+    swbn::Layout nw_lay{};
+    owned::Pinned<unsigned char> nw_h;             // the last read-back: [Net x G] [View x B]
+    std::vector<char> nw_begun, nw_stopped;        // per network
+    std::vector<char> nw_view;                     // per hashgraph: a view of a begun network
+    int64_t nw_calls = 0, nw_turns = 0, nw_imported = 0, nw_launches = 0;   // sw_network_batch_stats
     const swb::Rec* recs() const { return (const swb::Rec*)(mem.p + lay.recs); }
     unsigned char* seg(int64_t b, int s) const { return mem.p + lay.at((uint64_t)b, s); }
 };
@@ -198,6 +206,8 @@ int sw_batch_create(int64_t B, int n_members, const uint64_t* stake, int coin_pe
     c->cr.resize((size_t)B); c->ht.resize((size_t)B);
     c->hmax.assign((size_t)B, 0); c->frozen.assign((size_t)B, 0);
     c->sy_has.assign((size_t)B, 0); c->sy_cur.assign((size_t)B, 0); c->sy_behind.assign((size_t)B, 0); c->sy_fed.assign((size_t)B, 0);
+    c->stake_rows.swap(stake_h);
+    c->nw_view.assign((size_t)B, 0);
     *out = c;
     return SW_OK;
 }
@@ -216,6 +226,9 @@ int sw_batch_append(sw_batch* c, const int64_t* off, const int32_t* creator, con
     if (total == 0) return SW_OK;
     if (!creator || !self_parent || !other_parent) return bfail(c, SW_EINVAL, "creator / self_parent / other_parent is NULL");
     const int n = c->n;
+    for (int64_t b = 0; b < B; ++b)
+        if (off[b + 1] > off[b] && c->nw_view[b])
+            return bfail(c, SW_EINVAL, "hashgraph %lld is a view of a gossip network: its events come from the network's turns", (long long)b);
     CHK(batch_synth_refresh(c, off));   // generated events are in the slab only: the mirrors of the hashgraphs this call feeds
     std::vector<int32_t> hnew((size_t)total);
     std::vector<int32_t> hmax_new(c->hmax);

@@ -8,7 +8,8 @@
 
 namespace {
 
-struct XArr { void* out; int seg, width, cols; long long stride; };   // a data array of a call: out NULL = not wanted
+// a data array of a call: out NULL = not wanted; numbers: the source is the view's number column of the network state, not a segment
+struct XArr { void* out; int seg, width, cols; long long stride; bool numbers = false; };
 
 bool on_batch_device(const sw_batch* c, const void* p, size_t bytes) {
     const char* ends[2] = {(const char*)p, (const char*)p + (bytes ? bytes - 1 : 0)};
@@ -18,6 +19,13 @@ bool on_batch_device(const sw_batch* c, const void* p, size_t bytes) {
         if (at.type != hipMemoryTypeDevice || at.device != c->device) return false;
     }
     return true;
+}
+
+// where array x of hashgraph b starts (NULL: a number column of a batch without network state; such a hashgraph has no entries)
+const unsigned char* export_source(const sw_batch* c, int64_t b, const XArr& x) {
+    if (!x.numbers) return c->seg(b, x.seg);
+    if (!c->nw_state.p) return nullptr;
+    return (const unsigned char*)c->nw_lay.number(c->nw_state.p, (uint64_t)b);
 }
 
 // The ring slot of this call's plan.  A slot is rewritten only once its last upload has left it: with fewer than
@@ -78,7 +86,7 @@ int batch_export(sw_batch* c, const char* what, const std::vector<int64_t>& star
         const XArr& x = want[k];
         unsigned long long* src = (unsigned long long*)(h + off_bytes + (size_t)k * src_bytes);
         for (int64_t b = 0; b < B; ++b)
-            src[b] = (unsigned long long)(uintptr_t)c->seg(b, x.seg) + (unsigned long long)start[b] * (unsigned long long)x.stride * (unsigned)x.width;
+            src[b] = (unsigned long long)(uintptr_t)export_source(c, b, x) + (unsigned long long)start[b] * (unsigned long long)x.stride * (unsigned)x.width;
         out_bytes[k] = (size_t)T * x.cols * x.width;
         out_off[k] = stage_bytes;
         stage_bytes += (out_bytes[k] + 255) & ~(size_t)255;

@@ -103,6 +103,7 @@ int sw_synth_batch(sw_batch* c, const int64_t* K, int64_t* total) {
     for (int64_t b = 0; b < B; ++b) {
         if (K[b] < 0) return bfail(c, SW_EINVAL, "K[%lld] = %lld is negative", (long long)b, (long long)K[b]);
         if (!K[b]) continue;
+        if (c->nw_view[b]) return bfail(c, SW_EINVAL, "hashgraph %lld is a view of a gossip network: its events come from the network's turns", (long long)b);
         if (!c->sy_has[b]) return bfail(c, SW_EINVAL, "hashgraph %lld has no generator parameters (sw_synth_batch_begin)", (long long)b);
         if (c->sy_fed[b])
             return bfail(c, SW_EINVAL, "hashgraph %lld has taken a host append since sw_synth_batch_begin: the generator's heads no longer describe it", (long long)b);

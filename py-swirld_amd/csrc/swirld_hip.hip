@@ -8304,8 +8304,11 @@ int sw_crypto_hash_batch(int device, int64_t K, const uint8_t* msgs, const int64
 
 // ---- batches of small hashgraphs: one wavefront each, one launch (batch.hip.h) ----
 #include "batch_synth.hip.h"
+#include "batch_network.hip.h"
 #include "batch_api.hip.h"
 #include "batch_synth_api.hip.h"
 // ... and their results read in one call: a ragged gather over the whole batch (sw_export_batch_*)
 #include "batch_export.hip.h"
 #include "batch_export_api.hip.h"
+// ... and gossip networks of consecutive hashgraphs: one wavefront runs a network's turns (sw_network_batch_*)
+#include "batch_network_api.hip.h"

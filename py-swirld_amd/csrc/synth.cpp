@@ -93,3 +93,18 @@ extern "C" int sw_synth_hashgraph(int n, int64_t N, uint64_t seed, int mode, dou
     }
     return SW_OK;
 }
+
+// The schedule a network of a batch draws for itself (sw_network_batch_run): turns [first_turn, first_turn + T) of the
+// stream seeded with seed * 0x2545F4914F6CDD1D + 0x1234567 + 4; per turn the puller, then a peer among the others
+// (swirld.py:342, 323).  This function is the specification of the drawn form.
+extern "C" int sw_synth_schedule(int n, uint64_t seed, int64_t first_turn, int64_t T, int32_t* puller, int32_t* peer) {
+    if (n < 2 || first_turn < 0 || T < 0 || (T > 0 && (!puller || !peer))) return SW_EINVAL;
+    Xoshiro rng(seed * 0x2545F4914F6CDD1Dull + 0x1234567ull + 4ull);
+    for (int64_t k = 0; k < first_turn + T; ++k) {
+        const int a = (int)rng.below((uint32_t)n);
+        int b = (int)rng.below((uint32_t)(n - 1));
+        if (b >= a) ++b;
+        if (k >= first_turn) { puller[k - first_turn] = a; peer[k - first_turn] = b; }
+    }
+    return SW_OK;
+}

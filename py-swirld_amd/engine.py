@@ -1402,6 +1402,8 @@ BATCH_STAGES = {0: None, 1: "divide", 2: "fame", 3: "order"}
 BatchStepArrays = collections.namedtuple("BatchStepArrays", "took rounds_off rounds tx_off event round_received time n_failed")
 BatchExportStats = collections.namedtuple("BatchExportStats", "calls launches entries d2h_copies")
 BatchSynthStats = collections.namedtuple("BatchSynthStats", "calls events launches mirror_refreshes")
+BatchNetworkStatus = collections.namedtuple("BatchNetworkStatus", "begun turns created stage code view")
+BatchNetworkStats = collections.namedtuple("BatchNetworkStats", "calls turns imported launches")
 
 
 class HashgraphBatch:
@@ -1759,6 +1761,112 @@ class HashgraphBatch:
         self._chk(self._L.sw_export_batch_stats(self._h, _p(out)))
         return BatchExportStats(*[int(x) for x in out])
 
+    # ---- gossip networks (sw_network_batch_*): hashgraph g * n + i is node i's view of network g; one wavefront runs a
+    # network's turns, one launch.  No forks, no crypto, one turn at a time per network; cap_events bounds n + the turns.
+    @property
+    def n_networks(self):
+        return self.B // self.n
+
+    def _per_network(self, v, dtype, what):
+        G = self.n_networks
+        a = np.ascontiguousarray(np.broadcast_to(np.asarray(v, dtype), (G,)) if np.ndim(v) == 0 else v, dtype)
+        if a.shape != (G,):
+            raise ValueError("%s must be a scalar or have one entry per network" % what)
+        return a
+
+    def network_begin(self, seed, which=None, root_t=None, root_sig=None):
+        """Begin the selected networks (which: a mask over the B // n networks, None = all): view i stores root i and divides
+        it.  seed per network (a scalar broadcasts); root_t [G][n] and root_sig [G][n][64] replace the generated ones."""
+        G = self.n_networks
+        w = None if which is None else self._per_network(np.asarray(which) != 0, np.uint8, "which")
+        rt = None if root_t is None else np.ascontiguousarray(root_t, np.float64)
+        rs = None if root_sig is None else np.ascontiguousarray(root_sig, np.uint8)
+        if rt is not None and rt.shape != (G, self.n):
+            raise ValueError("root_t must be [networks][members]")
+        if rs is not None and rs.shape != (G, self.n, 64):
+            raise ValueError("root_sig must be [networks][members][64]")
+        self._chk(self._L.sw_network_batch_begin(self._h, _p(w), _p(self._per_network(seed, np.uint64, "seed")), _p(rt), _p(rs)))
+
+    def network_turns(self, schedules=None, *, off=None, puller=None, peer=None, t=None, sig=None):
+        """Explicit turns: `schedules` is a list of one entry per network, each None or (puller, peer[, t[, sig]]); or the same
+        as ragged arrays.  t and sig are the created events' (None: generated).  Returns the networks this call stopped."""
+        G = self.n_networks
+        if schedules is not None:
+            if len(schedules) != G:
+                raise ValueError("one entry per network (None for no turns)")
+            parts = [(np.zeros(0, np.int32),) * 2 if s is None else tuple(s) for s in schedules]
+            off = np.zeros(G + 1, np.int64)
+            np.cumsum([len(p[0]) for p in parts], out=off[1:])
+            puller = np.concatenate([np.asarray(p[0], np.int32) for p in parts])
+            peer = np.concatenate([np.asarray(p[1], np.int32) for p in parts])
+            has_t = [len(p) > 2 and p[2] is not None for p in parts if len(p[0])]
+            has_s = [len(p) > 3 and p[3] is not None for p in parts if len(p[0])]
+            if any(has_t) != all(has_t) or any(has_s) != all(has_s):
+                raise ValueError("timestamps / signatures for every network of the call, or for none")
+            if has_t and has_t[0]:
+                t = np.concatenate([np.asarray(p[2], np.float64) for p in parts if len(p[0])])
+            if has_s and has_s[0]:
+                sig = np.concatenate([np.asarray(p[3], np.uint8).reshape(-1, 64) for p in parts if len(p[0])])
+        off = np.ascontiguousarray(off, np.int64)
+        if off.shape != (G + 1,):
+            raise ValueError("off must have one entry per network and one more")
+        total = int(off[-1])
+        puller = np.ascontiguousarray(puller, np.int32)
+        peer = np.ascontiguousarray(peer, np.int32)
+        if not (puller.shape == peer.shape == (total,)):
+            raise ValueError("puller / peer must have off[-1] entries")
+        t = None if t is None else np.ascontiguousarray(t, np.float64)
+        sig = None if sig is None else np.ascontiguousarray(sig, np.uint8).reshape(total, 64)
+        if t is not None and t.shape != (total,):
+            raise ValueError("t must have off[-1] entries")
+        stopped = C.c_int64(0)
+        self._chk(self._L.sw_network_batch_turns(self._h, _p(off), _p(puller), _p(peer), _p(t), _p(sig), C.byref(stopped)))
+        return int(stopped.value)
+
+    def network_run(self, T):
+        """Every network runs its next T[g] turns of the schedule it draws itself (synth_schedule; an int broadcasts).
+        Returns the networks this call stopped."""
+        stopped = C.c_int64(0)
+        self._chk(self._L.sw_network_batch_run(self._h, _p(self._per_network(T, np.int64, "T")), C.byref(stopped)))
+        return int(stopped.value)
+
+    def network_status(self, g=None):
+        """Per network: BatchNetworkStatus(begun, turns, created, stage, code, view); stage 4 = broken."""
+        out = np.zeros((self.n_networks, 6), np.int64)
+        self._chk(self._L.sw_network_batch_get(self._h, _p(out)))
+        if g is not None:
+            return BatchNetworkStatus(*[int(x) for x in out[g]])
+        return [BatchNetworkStatus(*[int(x) for x in row]) for row in out]
+
+    def network_heads(self):
+        """int32 [B]: the local index of each view's head (-1: not a view of a begun network)."""
+        out = np.zeros(self.B, np.int32)
+        self._chk(self._L.sw_network_batch_heads(self._h, _p(out)))
+        return out
+
+    def network_stats(self):
+        """(calls that ran turns, turns run, events imported, kernel launches)."""
+        out = np.zeros(4, np.int64)
+        self._chk(self._L.sw_network_batch_stats(self._h, _p(out)))
+        return BatchNetworkStats(*[int(x) for x in out])
+
+    def event_numbers(self, b, first=0, K=None):
+        """The network event numbers of view b's stored events [first, first + K)."""
+        K = self._events(b) - first if K is None else K
+        out = np.empty(K, np.int32)
+        self._chk(self._L.sw_get_network_event_numbers(self._h, b, first, K, _p(out)))
+        return out
+
+    def export_event_numbers(self, first=None, count=None):
+        """Network event numbers of the events [first[b], first[b] + count[b]) of every view: off, numbers."""
+        ctl = [self._ctl(first, np.int64, "first"), self._ctl(count, np.int64, "count")]
+        return self._export(self._L.sw_export_network_event_numbers, ctl, [("numbers", np.int32, 1)])
+
+    def export_event_numbers_device(self, first=None, count=None, numbers=None, cap=None, stream=0):
+        """export_event_numbers into a DEVICE array (see export_ordered_device).  Returns (off, total)."""
+        ctl = [self._ctl(first, np.int64, "first"), self._ctl(count, np.int64, "count")]
+        return self._export_device(self._L.sw_export_network_event_numbers_device, ctl, [("numbers", numbers, 1)], cap, stream)
+
 
 LiveResources = collections.namedtuple("LiveResources", "device_bytes pinned_bytes events streams")
 
@@ -1809,6 +1917,17 @@ def hash_batch(msgs, device=0):
     if rc != 0:
         raise SwirldHipError(rc, (L.sw_last_error(None) or b"").decode())
     return [bytes(out[i]) for i in range(K)]
+
+
+def synth_schedule(n, seed, first_turn, T):
+    """Turns [first_turn, first_turn + T) of the schedule a batch network of n nodes draws under `seed` (csrc/synth.cpp, no
+    GPU): (puller, peer) as int32 arrays."""
+    L = _lib.load()
+    puller, peer = np.empty(max(int(T), 0), np.int32), np.empty(max(int(T), 0), np.int32)
+    rc = L.sw_synth_schedule(int(n), int(seed), int(first_turn), int(T), _p(puller), _p(peer))
+    if rc != 0:
+        raise SwirldHipError(rc, "sw_synth_schedule: invalid arguments")
+    return puller, peer
 
 
 def synth_hashgraph(n, N, seed, mode=0, p0=0.0, p1=0.0, with_sig=True):
